@@ -2,7 +2,8 @@
 """Headline benchmark: output frames/s of the recurrent denoise+demosaic hot
 path on N MI355X (one process per GPU), BASELINE.json's metric.
 
-  python bench.py                                  # N=1, config C2, finishes in minutes
+  python bench.py                                  # N=1, config C2: the headline figure only
+  python bench.py --full                           # and everything else it measures (minutes)
   python bench.py --gpus N --steps K --warmup W    # launches its own N ranks (torch.distributed.run child)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W          # or is launched as one of them
@@ -11,7 +12,7 @@ A "step" is one pass of the hot path over one batch of synthetic input already
 resident in HBM: B independent sequences of T frames advanced in lockstep on
 each GPU (T-1-future output frames per sequence).  Sequences share nothing, so
 ranks never exchange data inside the timed region; the only collectives are the
-barrier/max that bracket it, one all-gather of the per-frame PSNR values
+barrier/max that bracket it, with --full one all-gather of the per-frame PSNR values
 afterwards and, with --collate-outputs, one all-gather of the output frames
 (timed on its own, outside the compute region).
 
@@ -19,7 +20,12 @@ afterwards and, with --collate-outputs, one all-gather of the output frames
   N > 1   config C5 (B = 8 sequences of 90 frames per GPU: 64 sequences on 8 GPUs), weak scaling;
           --scaling strong fixes the total at --sequences (64) instead and runs each rank's share in groups of B
 
-The JSON line carries `roofline` for the dominant kernel (the 48->48 3x3 conv; by
+A plain run sets up, warms up, times the --steps steps, writes the outputs of the last
+step with --dump-outputs DIR and prints the JSON line: `value` (frames/s) and
+`ms_per_step` (wall milliseconds of one timed step).  What else the benchmark
+measures or checks runs only with --full (the keys stay in the line, null without it):
+`task_psnr_db` of every output frame, `gpu_clock_power`, `exact_f32_kernels`, `kernels`,
+`roofline` for the dominant kernel (the 48->48 3x3 conv; by
 default on the F16 matrix pipe with split f32 operands, dense peak 2.5 PFLOP/s),
 measured with HIP events around a uniform sample of its launches inside the timed
 region -- `achieved` / `frac` are ALGORITHMIC flops, the executed-MFMA
@@ -28,7 +34,7 @@ and HBM fractions sit beside them --, `cpu_baseline`: the CPU oracle
 timed on this host's cores on a bounded sample of the same workload, and
 `other_configs`: a short run of each of BASELINE.json's other configurations (and of C2 with the flow recomputed online by TV-L1)
 (C3, C4, C5's per-GPU share, C1) after the timed region, so that the driver's
-record holds them too.
+record holds them too.  --all-kernel-events brackets launches with or without --full.
 """
 import argparse
 import json
@@ -91,8 +97,14 @@ def _free_port():
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: task PSNR, kernel events and roofline, "
+                         "shader clock / power, the exact-f32 kernels, the other configurations, the CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output frames of the last step as float32 DIR/<name>.npy "
+                         "(a fixed, seeded sample of them when they exceed 48 MiB; see dump_outputs)")
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS), help="default: C2 on one GPU, C5 on several")
     ap.add_argument("--batch", type=int, default=0, help="sequences advanced in lockstep per GPU (default: the config's)")
     ap.add_argument("--frames", type=int, default=0, help="override frames per sequence")
@@ -108,22 +120,25 @@ def parse_args(argv=None):
                     help="--online-flow: the sequences of a GPU as this many independent groups on as many HIP streams (1 = round 5's single stream)")
     ap.add_argument("--collate-outputs", action="store_true",
                     help="after the timed region, all-gather the output frames of the last group (timed separately)")
-    ap.add_argument("--cpu-frames", type=int, default=10, help="timed frames of the CPU-oracle sample (0 = skip)")
-    ap.add_argument("--cpu-frames-8", type=int, default=4, help="timed frames of the second CPU sample at 8 threads (0 = skip)")
+    ap.add_argument("--cpu-frames", type=int, default=10, help="--full: timed frames of the CPU-oracle sample (0 = skip)")
+    ap.add_argument("--cpu-frames-8", type=int, default=4, help="--full: timed frames of the second CPU sample at 8 threads (0 = skip)")
     ap.add_argument("--cpu-frames-wide", type=int, default=3,
-                    help="timed frames of a third CPU sample at min(affinity, cgroup quota, 64) threads, when that exceeds 16 (0 = skip)")
+                    help="--full: timed frames of a third CPU sample at min(affinity, cgroup quota, 64) threads, when that exceeds 16 (0 = skip)")
     ap.add_argument("--no-exact-ab", action="store_true",
-                    help="skip the second, untimed-region-external run on the exact-f32-product kernels (one GPU only)")
+                    help="--full: skip the second, untimed-region-external run on the exact-f32-product kernels (one GPU only)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short runs of the other configurations after the timed region (one GPU, default config only)")
+                    help="--full: skip the short runs of the other configurations after the timed region (one GPU, default config only)")
     ap.add_argument("--other-steps", type=int, default=6,
                     help="timed steps of each of those short runs (six: 2-6 s each, enough to resolve 1 %%; round 5 ran two)")
-    ap.add_argument("--no-gpu-sampler", action="store_true", help="do not sample shader clock / package power (rocm-smi) during the timed regions")
-    ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--no-gpu-sampler", action="store_true", help="--full: do not sample shader clock / package power (rocm-smi) during the timed regions")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: do not bracket kernels with HIP events")
     ap.add_argument("--all-kernel-events", action="store_true",
                     help="diagnostic: bracket EVERY launch of every kernel (costs ~6 %% of the frame rate); "
                          f"default brackets every {EVENT_STRIDE}rd launch of the dominant kernel only")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -482,6 +497,30 @@ def quick_config(name, steps, dev_index, online_flow=False, batch=None, sampler=
     return res
 
 
+DUMP_WHOLE_BYTES = 48 << 20     # --dump-outputs: an output up to this size is written whole
+DUMP_SAMPLE = 1 << 22           # elements of the seeded sample of a larger one (16 MiB)
+
+
+def dump_outputs(outs, out_dir):
+    """--dump-outputs: what the timed path returned in its last step -- the output frames [T-1-future, B, 3, H, W] of the
+    last group of sequences of rank 0 -- as float32 .npy files.  Up to DUMP_WHOLE_BYTES the whole tensor (outputs.npy);
+    above, the last output frame of sequence 0 whole (outputs_last_frame_seq0.npy, [3, H, W]) and DUMP_SAMPLE elements of
+    the whole tensor (outputs_sample.npy) at flat indices drawn by torch.randint from a CPU generator seeded with 0, sorted:
+    the same elements in every run of the same arguments (27 MiB in all at C2).  -> the names written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if outs.numel() * outs.element_size() <= DUMP_WHOLE_BYTES:
+        arrays = {"outputs": outs}
+    else:
+        gen = torch.Generator(device="cpu").manual_seed(0)
+        idx = torch.randint(0, outs.numel(), (DUMP_SAMPLE,), generator=gen).sort().values
+        arrays = {"outputs_last_frame_seq0": outs[-1, 0], "outputs_sample": outs.reshape(-1)[idx.to(outs.device)]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+    return sorted(arrays)
+
+
 def main():
     args = parse_args()
     # the host driver only supports dmabuf IPC: RCCL (and any sharing of device memory between processes) needs this
@@ -547,7 +586,7 @@ def main():
         fprev = torch.stack([s.flow_prev for s in seqs], 1).contiguous()
         fnext = torch.stack([s.flow_next for s in seqs], 1).contiguous() if fut else None
         inputs.append((raw, fprev, fnext))
-        if gi == len(groups) - 1:
+        if args.full and gi == len(groups) - 1:
             gt = torch.stack([s.gt for s in seqs], 1).contiguous()     # ground truth of the last group (task PSNR)
         del seqs
     outs = torch.empty(n_out, B, 3, H, W, dtype=torch.float32, device=dev)   # outputs of the group being advanced
@@ -575,11 +614,13 @@ def main():
 
     for _ in range(args.warmup):
         one_step()
-    # shader clock and package power through every timed region of this process (rank 0 of a single-node run samples its own GPU)
+    # --full: shader clock and package power through every timed region of this process (rank 0 of a single-node run samples
+    # its own GPU)
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith("ROCPROF") for k in os.environ)
-    sampler = GpuSampler(dev_index) if (rank == 0 and not stub and not args.no_gpu_sampler and not under_profiler) else None
+    sampler = GpuSampler(dev_index) if (args.full and rank == 0 and not stub and not args.no_gpu_sampler and not under_profiler) else None
+    kernel_events = (args.full or args.all_kernel_events) and not args.no_kernel_events
     barrier()
-    if not args.no_kernel_events:
+    if kernel_events:
         if args.all_kernel_events:
             rt.profile_select(None, 1)
         else:
@@ -594,7 +635,7 @@ def main():
     t1 = time.perf_counter()
     wall = t1 - t0
     clock_power = sampler.window(t0, t1) if sampler is not None else None
-    prof = rt.profile_read() if not args.no_kernel_events else []
+    prof = rt.profile_read() if kernel_events else []
     rt.profile_enable(False)
     if og is not None:
         prof = []                # the launches ran on the groups' handles, not on `rt`
@@ -610,9 +651,11 @@ def main():
     frames_total = args.steps * n_out * total_seqs
     fps = frames_total / elapsed
 
-    # ---- task PSNR of every output frame of the last group of the last step (outside the timed region)
-    psnr = torch.tensor([[rt.psnr_l1(outs[k], gt[k + 1])[1] for k in range(n_out)]], dtype=torch.float64, device=dev)
-    psnr_mean = float(shard.gather_metrics(psnr.cpu() if on_host else psnr, dist).mean().item())    # the collate collective
+    # ---- --full: task PSNR of every output frame of the last group of the last step (outside the timed region)
+    psnr_mean = None
+    if args.full:
+        psnr = torch.tensor([[rt.psnr_l1(outs[k], gt[k + 1])[1] for k in range(n_out)]], dtype=torch.float64, device=dev)
+        psnr_mean = float(shard.gather_metrics(psnr.cpu() if on_host else psnr, dist).mean().item())    # the collate collective
 
     # ---- optional: collate the output frames themselves (north star: "one all-gather only to collate outputs")
     collate = None
@@ -633,6 +676,7 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    dumped = dump_outputs(outs, args.dump_outputs) if args.dump_outputs else None
     if sampler is not None and (world > 1 or args.no_other_configs or args.online_flow or config != "C2" or args.batch or args.frames):
         sampler.close()          # nothing else is timed in this process
         sampler = None
@@ -648,7 +692,7 @@ def main():
     # ---- the same workload on the kernels that multiply f32 operands directly (f32 MFMA): what the split-f16 matrix path
     # buys, and how far apart the two paths' frames are.  One GPU only, outside the timed region.
     exact = None
-    if world == 1 and not stub and not args.no_exact_ab and not args.online_flow:
+    if args.full and world == 1 and not stub and not args.no_exact_ab and not args.online_flow:
         rt2 = RvddRuntime(arch, fut, B, H, W, dev_index)
         rt2.set_option("next_split" if arch.startswith("next") else "conv_kernel", 0 if arch.startswith("next") else 4)
         rt2.load_state_dict(sd)
@@ -670,7 +714,7 @@ def main():
     # ---- the other configurations of BASELINE.json, a short run each (outside the timed region): C3, C4, C5's per-GPU
     # share and C1 at their default batch, so that the driver's record holds more than the headline config
     other = None
-    if world == 1 and not stub and not rehearsal and not args.no_other_configs and not args.online_flow and config == "C2" \
+    if args.full and world == 1 and not stub and not rehearsal and not args.no_other_configs and not args.online_flow and config == "C2" \
             and not args.batch and not args.frames:
         other = {}
         for name in ("C3", "C4", "C5", "C1"):
@@ -689,7 +733,7 @@ def main():
 
     # ---- CPU baseline: the oracle on this host's cores, bounded sample, sequence 0
     cpu = None
-    if world == 1 and args.cpu_frames > 0 and not stub:
+    if args.full and world == 1 and args.cpu_frames > 0 and not stub:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import rvdd_oracle as O
         share = host_cpu_share()
@@ -783,10 +827,10 @@ def main():
         "gpu_event_ms_per_step": round(ev_ms / args.steps, 3),
         "algorithmic_gflop_per_frame": gflop_frame,
         "whole_path_algorithmic_tflops": round(fps / world * gflop_frame / 1e3, 2),
-        "task_psnr_db": round(psnr_mean, 3),
+        "task_psnr_db": round(psnr_mean, 3) if psnr_mean is not None else None,
         "gpu_clock_power": clock_power,
         "roofline": roofline, "cpu_baseline": cpu, "exact_f32_kernels": exact, "other_configs": other, "collate": collate,
-        "kernels": kernels,
+        "kernels": kernels, "full": args.full, "dumped_outputs": dumped,
     }
     if cpu:
         line["gpu_over_cpu"] = round(fps / cpu["value"], 1)

@@ -16,7 +16,7 @@ import pytest
 from conftest import GOLDEN, REPO, WEIGHTS
 
 REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "models")), reason="reference tree not present")
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "models")), reason="reference tree not present")
 
 
 def _run(script, out, *extra, env=None):
@@ -43,6 +43,7 @@ def _compare_npz(out, names):
             _same(a[k], b[k], f"{f}:{k}")
 
 
+@needs_reference
 def test_make_golden_regenerates_the_committed_fixtures(tmp_path):
     out = _run("make_golden.py", str(tmp_path), "--out", str(tmp_path))
     names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(out, "*.npz")))
@@ -54,6 +55,7 @@ def test_make_golden_regenerates_the_committed_fixtures(tmp_path):
         assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a), p
 
 
+@needs_reference
 def test_make_golden_long_and_nowarp_regenerate(tmp_path):
     out = _run("make_golden_long.py", str(tmp_path), "--out", str(tmp_path), "--only", "long30-feat-iso3200")
     _compare_npz(out, ["seq_long30-feat-iso3200.npz"])
@@ -63,6 +65,7 @@ def test_make_golden_long_and_nowarp_regenerate(tmp_path):
                              + glob.glob(os.path.join(out, "seq_prevnoisy*.npz"))))
 
 
+@needs_reference
 def test_make_golden_ppipe_regenerates(tmp_path):
     out = _run("make_golden_ppipe.py", str(tmp_path), env={"RVDD_GOLDEN_OUT": str(tmp_path)})
     _compare_npz(out, sorted(os.path.basename(p) for p in glob.glob(os.path.join(out, "ppipe_*.npz"))))

@@ -253,7 +253,7 @@ def test_rccl_collectives_run_at_world_size_one():
     env["OMP_NUM_THREADS"] = "4"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "1", "--config", "C5", "--frames", "4",
-           "--steps", "1", "--warmup", "1", "--collate-outputs", "--cpu-frames", "0"]
+           "--steps", "1", "--warmup", "1", "--collate-outputs", "--cpu-frames", "0", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -7,7 +7,12 @@ kernel follows the reference's operation order with contraction off and differs 
 3x3 matrix accumulation order: |diff| <= 2e-3 relative to max(|value|, 255) (observed ~1e-5).  The
 uint8 image can therefore differ by one level where the float value sits on a rounding boundary: at
 most 0.1 % of samples off by exactly 1, none by more.  PSNR on uint8 is exact integer arithmetic up
-to the final float64 division/log: 1e-9 dB.  SSIM: 1e-9."""
+to the final float64 division/log: 1e-9 dB.  SSIM: 1e-9.
+
+The oracle against the reference's own float sRGB image: bit-exact on the CPU the fixtures were made on.  On
+another CPU torch's float32 pow / matrix product take other vector code paths and round some samples
+differently (up to 4.9e-4 on the x255 scale, 1.9e-6 relative, measured with every ATen CPU capability):
+|diff| <= 4e-6 relative to max(|value|, 255) there, and the uint8 image stays exactly equal."""
 import glob
 import os
 
@@ -21,6 +26,13 @@ from conftest import GOLDEN, REPO
 CASES = sorted(os.path.basename(p)[6:-4] for p in glob.glob(os.path.join(GOLDEN, "ppipe_*.npz"))
                if "bitdepth" not in p)
 BITDEPTH = [0, 10, 12]
+
+
+def _same_float_srgb(got, want):
+    if np.array_equal(got, want):
+        return
+    d = np.abs(got.astype(np.float64) - want) / np.maximum(np.abs(want.astype(np.float64)), 255.0)
+    assert got.shape == want.shape and got.dtype == want.dtype and d.max() <= 4e-6, float(d.max())
 
 
 def _gains(seq, iso):
@@ -39,7 +51,7 @@ def test_oracle_matches_reference(name):
     img = P.tensor2im(torch.from_numpy(g["x"]))
     assert np.array_equal(img, g["tif"])
     srgb = P.ppipe(P.normalise_bit_depth(img, 8), *_gains(int(g["seq"]), int(g["iso"])), int(g["iso"]))
-    assert np.array_equal(srgb, g["srgb"])                      # same torch build, same ops: bit-exact
+    _same_float_srgb(srgb, g["srgb"])                           # same torch build, same ops: bit-exact on the same CPU
     assert np.array_equal(P.to_uint8(srgb), g["u8"])
     assert abs(P.psnr_u8(g["u8"], g["gt_u8"]) - float(g["psnr"])) < 1e-12
 
@@ -48,7 +60,7 @@ def test_oracle_matches_reference(name):
 def test_oracle_bit_depths(bd):
     g = np.load(os.path.join(GOLDEN, f"ppipe_bitdepth{bd}.npz"))
     srgb = P.ppipe(P.normalise_bit_depth(g["img"], bd), *_gains(int(g["seq"]), int(g["iso"])), int(g["iso"]))
-    assert np.array_equal(srgb, g["srgb"])
+    _same_float_srgb(srgb, g["srgb"])
 
 
 def test_ssim_analytic():

@@ -105,21 +105,73 @@ def test_bench_self_launch_two_ranks_weak(tmp_path):
     assert r["config"]["workload"].startswith("C5")           # the multi-GPU default configuration
     assert r["config"]["sequences_total"] == 4 and r["config"]["sequences_per_gpu"] == 2
     assert r["value"] > 0 and r["steps"] == 2 and r["warmup"] == 1
-    assert abs(r["value"] - 2 * 3 * 4 / (r["ms_per_step"] * 2 / 1e3)) / r["value"] < 1e-3    # frames of ALL ranks / max time
+    # frames of ALL ranks / max time (ms_per_step is rounded to 1 us: sub-millisecond stub steps need the absolute form)
+    assert abs(1e3 * 2 * 3 * 4 / r["value"] / 2 - r["ms_per_step"]) < 1e-3
     assert r["collate"]["gathered_shape"] == [2, 3, 2, 3, 32, 48]
     assert "STUB" in r["data"] and r["cpu_baseline"] is None and r["vs_baseline"] is None
 
 
 def test_bench_self_launch_strong_scaling(tmp_path):
     r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--frames", "3", "--batch", "2", "--scaling", "strong",
-                "--sequences", "8"], tmp_path)
+                "--sequences", "8", "--full"], tmp_path)
     assert r["scaling"] == "strong" and r["n_ranks_seen"] == 2
     assert r["config"]["sequences_total"] == 8 and r["config"]["sequences_per_gpu"] == 4
     assert r["config"]["output_frames_per_step_per_gpu"] == 2 * 4
     one = _bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--frames", "3", "--batch", "2", "--config", "C5",
-                  "--scaling", "strong", "--sequences", "8"], tmp_path)
+                  "--scaling", "strong", "--sequences", "8", "--full"], tmp_path)
     assert one["n_gpus"] == 1 and one["config"]["sequences_per_gpu"] == 8
     assert abs(one["task_psnr_db"] - r["task_psnr_db"]) < 20       # same generator; both finite numbers
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, reports ms_per_step, measures nothing else, and with
+    --dump-outputs writes the last step's output frames as float32 .npy files: the same bits from a second run."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "4", "--batch", "2", "--config", "C5",
+                    "--dump-outputs", str(d)], tmp_path)
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["full"] is False
+        assert abs(1e3 * 3 * 3 * 2 / r["value"] / 3 - r["ms_per_step"]) < 1e-3    # ms_per_step is rounded to 1 us
+        for key in ("task_psnr_db", "roofline", "cpu_baseline", "exact_f32_kernels", "other_configs", "gpu_clock_power"):
+            assert r[key] is None, key
+        assert r["kernels"] == {} and r["dumped_outputs"] == ["outputs"]
+        a = np.load(d / "outputs.npy")
+        assert a.dtype == np.float32 and a.shape == (3, 2, 3, 32, 48) and np.isfinite(a).all()
+        runs.append(a)
+    assert np.array_equal(runs[0], runs[1])
+
+
+def test_bench_dump_outputs_samples_a_large_output(tmp_path):
+    """Above the whole-tensor limit: the last frame of sequence 0 whole and a fixed, seeded sample of every frame."""
+    import numpy as np
+    import bench
+    outs = torch.randn(29, 8, 3, 90, 160)
+    for k in range(2):
+        real = bench.DUMP_WHOLE_BYTES
+        try:
+            bench.DUMP_WHOLE_BYTES = 1 << 20
+            names = bench.dump_outputs(outs, str(tmp_path / f"d{k}"))
+        finally:
+            bench.DUMP_WHOLE_BYTES = real
+        assert names == ["outputs_last_frame_seq0", "outputs_sample"]
+        last = np.load(tmp_path / f"d{k}" / "outputs_last_frame_seq0.npy")
+        sample = np.load(tmp_path / f"d{k}" / "outputs_sample.npy")
+        assert last.dtype == sample.dtype == np.float32 and sample.shape == (bench.DUMP_SAMPLE,)
+        assert np.array_equal(last, outs[-1, 0].numpy())
+        assert sum(os.path.getsize(p) for p in (tmp_path / f"d{k}").iterdir()) < 64 << 20
+    gen = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, outs.numel(), (bench.DUMP_SAMPLE,), generator=gen).sort().values
+    assert np.array_equal(sample, outs.reshape(-1)[idx].numpy())
+    assert np.array_equal(np.load(tmp_path / "d0" / "outputs_sample.npy"), sample)
+
+
+def test_bench_refuses_zero_steps(tmp_path):
+    env = dict(os.environ, RVDD_BENCH_STUB="1")
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         env=env, timeout=120)
+    assert out.returncode != 0 and "--steps" in out.stderr
 
 
 def test_bench_refuses_mismatched_world(tmp_path):

@@ -21,7 +21,7 @@ fi
 cp rvdd-release_amd/librvdd_hip.so /tmp/librvdd_hip_keep.so
 for xp in $2; do
   cp rvdd-release_amd/librvdd_hip_xp$xp.so rvdd-release_amd/librvdd_hip.so
-  python bench.py --config C4 --steps 8 --warmup 1 --cpu-frames 0 --cpu-frames-8 0 --cpu-frames-wide 0 --no-exact-ab --no-other-configs > /tmp/xp_bench.json 2>/dev/null &
+  python bench.py --full --config C4 --steps 8 --warmup 1 --cpu-frames 0 --cpu-frames-8 0 --cpu-frames-wide 0 --no-exact-ab --no-other-configs > /tmp/xp_bench.json 2>/dev/null &
   BP=$!
   : > /tmp/xp_power.log
   for i in $(seq 1 80); do

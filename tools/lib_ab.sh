@@ -3,7 +3,7 @@
 # (variants are rvdd-release_amd/librvdd_hip_<variant>.so; the first one is restored at the end)
 ARGS=$1; shift
 cd rvdd-release_amd
-for rep in 1 2; do for v in "$@"; do cp librvdd_hip_$v.so librvdd_hip.so; (cd .. && timeout -k 10 300 python bench.py $ARGS 2>/dev/null | python -c "
+for rep in 1 2; do for v in "$@"; do cp librvdd_hip_$v.so librvdd_hip.so; (cd .. && timeout -k 10 300 python bench.py --full $ARGS 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 cd $ROOT
 for rep in 1 2; do for g in 1 2; do
-  timeout -k 10 300 python bench.py --online-flow --online-groups $g --steps ${STEPS:-3} --warmup 1 --cpu-frames 0 --no-exact-ab --no-other-configs 2>/dev/null | python -c "
+  timeout -k 10 300 python bench.py --full --online-flow --online-groups $g --steps ${STEPS:-3} --warmup 1 --cpu-frames 0 --no-exact-ab --no-other-configs 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
