@@ -79,13 +79,28 @@ int rvdd_finalize_weights(rvdd_t* h);
  * rvdd_step re-initialises lastden from raw_prev and zeroes the features. */
 int rvdd_reset(rvdd_t* h);
 
+/* FirstOfVideo per sequence: `mask` (HOST, [cfg.batch] bytes; nonzero = that
+ * slot starts a new video) marks slots whose next rvdd_step[_strided]
+ * re-initialises lastden from their slice of raw_prev and zeroes their features
+ * (and their block-floating-point words); the other slots carry on.  Marks
+ * accumulate (OR) until a step that succeeds consumes them; a step that fails
+ * leaves them pending.  raw_prev is required on such a step and read only for
+ * the marked slots.  A mask of every slot is rvdd_reset (same launches, same
+ * bits); an empty mask changes nothing.  Every output of a marked slot is bit
+ * for bit what a handle of batch 1 gives for the same video after rvdd_reset,
+ * so videos of any length can share a batch.  A mask of some but not all slots
+ * needs batch <= 64 (RVDD_ERR_ARG otherwise), and its step runs launch by
+ * launch (never replayed from a captured graph). */
+int rvdd_reset_slots(rvdd_t* h, const uint8_t* mask);
+
 /* One output frame for each of the B sequences: recurrentModel.set_input +
  * forward, test branch (models/recurrent_model.py:105-135, 161-349):
  * Hamilton-Adams demosaic, flow x2 upsample, bicubic backward warp of the
  * previous output / features / next frame, U-Net forward, state hand-over.
  *   raw_prev, raw_cur, raw_next : [B,4,H/2,W/2] packed GBRG raw in [-1,1]
  *                                 (raw_prev is read only on the first step after
- *                                  create/reset; raw_next only when future=1)
+ *                                  create/reset, and for the slots rvdd_reset_slots
+ *                                  marked; raw_next only when future=1)
  *   flow_prev : [B,2,H/2,W/2] raw-resolution flow cur->prev (x first)
  *   flow_next : [B,2,H/2,W/2] raw-resolution flow cur->next (future=1)
  *   out_rgb   : [B,3,H,W] denoised linear RGB
@@ -113,6 +128,14 @@ int rvdd_set_state(rvdd_t* h, const float* lastden, const float* lastfeat, void*
  * 10*log10(4/mean((den-gt)^2)) } over `count` elements.  Synchronises
  * `stream` (the reference reads the losses back with float(), base_model.py:151). */
 int rvdd_psnr_l1(rvdd_t* h, const float* den, const float* gt, int64_t count, float* out2, void* stream);
+
+/* rvdd_psnr_l1 over `n` dense slices of `count` elements each (den / gt
+ * [n][count], e.g. one output frame per sequence of a step): out (HOST,
+ * [n][2] floats) = { L1*100, PSNR } of each slice, bit for bit what
+ * rvdd_psnr_l1 returns for that slice alone.  One batched reduction and one
+ * synchronisation of `stream` for all slices; checks a pending asynchronous
+ * rvdd_tvl1flow_batch as rvdd_psnr_l1 does.  n = 0 does nothing. */
+int rvdd_psnr_l1_batch(rvdd_t* h, const float* den, const float* gt, int32_t n, int64_t count, float* out, void* stream);
 
 /* ---- the same ops one at a time (plugin-level entry points; also test hooks) */
 

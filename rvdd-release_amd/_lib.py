@@ -30,11 +30,13 @@ _PROTOS = {
     "rvdd_set_weight": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int32]),
     "rvdd_finalize_weights": (C.c_int, [_P]),
     "rvdd_reset": (C.c_int, [_P]),
+    "rvdd_reset_slots": (C.c_int, [_P, _P]),
     "rvdd_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "rvdd_step_strided": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P]),
     "rvdd_get_state": (C.c_int, [_P, _P, _P, _P]),
     "rvdd_set_state": (C.c_int, [_P, _P, _P, _P]),
     "rvdd_psnr_l1": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_float), _P]),
+    "rvdd_psnr_l1_batch": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P]),
     "rvdd_unet_forward": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "rvdd_demosaic_ha": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_warp_bicubic": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

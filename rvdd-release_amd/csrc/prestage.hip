@@ -424,13 +424,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 // Up to three raw frames (the current one, the next one, and on the first step of a video the previous one, whose demosaic is
 // the "previous output"; each nullable); `prev_words` (nullable) = words whose maximum bounds the previous output (the slot
 // PostConvs wrote in the last step: features and output frame together); grid (blocks, B).
+// `latch` (rvdd_reset_slots): the sequences that start a video on this step (seq_latched) -- they bound from raw_c and ignore
+// prev_words, the others ignore raw_c and read prev_words: each sequence gets the bound it would get alone.
 __global__ __launch_bounds__(256) void netin_bound_kernel(const float* __restrict__ raw_a, const float* __restrict__ raw_b,
                                                           const float* __restrict__ raw_c, int64_t n, int64_t rbs,
                                                           const unsigned* __restrict__ prev_words, unsigned* __restrict__ words,
                                                           unsigned* __restrict__ zero_a, size_t zero_na, unsigned* __restrict__ zero_b,
-                                                          size_t zero_nb) {
+                                                          size_t zero_nb, unsigned long long latch) {
     __shared__ unsigned red[4];
     const int b = blockIdx.y;
+    const bool lat = raw_c && seq_latched(latch, b);
     // housekeeping for the step AFTER this one: its set of amax words and its features slot, which nobody touches meanwhile
     {
         const size_t me = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x, all = (size_t)gridDim.x * gridDim.y * 256;
@@ -439,7 +442,7 @@ __global__ __launch_bounds__(256) void netin_bound_kernel(const float* __restric
     }
     float m = 0.f;
     for (int pass = 0; pass < 3; ++pass) {
-        const float* src = pass == 0 ? raw_a : pass == 1 ? raw_b : raw_c;
+        const float* src = pass == 0 ? raw_a : pass == 1 ? raw_b : lat ? raw_c : nullptr;
         if (!src) continue;
         const f32x4* p = reinterpret_cast<const f32x4*>(src + (size_t)b * rbs);
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (n >> 2); i += (int64_t)gridDim.x * 256) {
@@ -448,7 +451,7 @@ __global__ __launch_bounds__(256) void netin_bound_kernel(const float* __restric
         }
     }
     unsigned bits = __float_as_uint(m);
-    if (blockIdx.x == 0 && prev_words && threadIdx.x < kAmaxLines)
+    if (blockIdx.x == 0 && prev_words && !lat && threadIdx.x < kAmaxLines)
         bits = max(bits, prev_words[(size_t)b * kAmaxSeqWords + threadIdx.x * kAmaxLineWords]);
     // x 16: four up on the exponent (a maximum that is zero, denormal, or within 2^4 of overflow stays as it is)
     const unsigned e = (bits >> 23) & 0xffu;
@@ -465,11 +468,13 @@ __global__ __launch_bounds__(256) void netin_bound_kernel(const float* __restric
 // atomic per block on the amax words costs 100 us at 28 800 blocks (720p, round 4) -- launch_netin_small refuses above 1024 blocks.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void netin_small_kernel(
     NetinArgs a, float* __restrict__ netin, const float* __restrict__ raw_prev, const unsigned* __restrict__ prev_words,
-    unsigned* __restrict__ words, unsigned* __restrict__ zero_a, size_t zero_na, unsigned* __restrict__ zero_b, size_t zero_nb, int tiles_x) {
+    unsigned* __restrict__ words, unsigned* __restrict__ zero_a, size_t zero_na, unsigned* __restrict__ zero_b, size_t zero_nb, int tiles_x,
+    unsigned long long latch) {
     __shared__ float gs[18][20];
     __shared__ unsigned red[4];
     const int H = 2 * a.h, W = 2 * a.w;
     const int b = blockIdx.y, t = threadIdx.x;
+    const bool lat = raw_prev && seq_latched(latch, b);      // netin_bound_kernel's choice of bound
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int y0 = ty * 16, x0 = tx * 16;
     {   // housekeeping for the step AFTER this one (netin_bound_kernel's)
@@ -529,11 +534,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         o[2] = f32x4{0.f, 0.f, 0.f, 0.f};
         m = fabsf(q.r[1][1]);
         // (the first step of a video: the "previous output" is the demosaic of the previous raw frame, whose samples bound it)
-        if (raw_prev) m = fmaxf(m, fabsf(raw_prev[(size_t)b * a.rbs + ((size_t)q.site[1][1] * c.h + (y >> 1)) * c.w + (x >> 1)]));
+        if (lat) m = fmaxf(m, fabsf(raw_prev[(size_t)b * a.rbs + ((size_t)q.site[1][1] * c.h + (y >> 1)) * c.w + (x >> 1)]));
     }
     if (words) {      // netin_bound_kernel's tail
         unsigned bits = __float_as_uint(m);
-        if (blockIdx.x == 0 && prev_words && t < kAmaxLines) bits = max(bits, prev_words[(size_t)b * kAmaxSeqWords + t * kAmaxLineWords]);
+        if (blockIdx.x == 0 && prev_words && !lat && t < kAmaxLines) bits = max(bits, prev_words[(size_t)b * kAmaxSeqWords + t * kAmaxLineWords]);
         const unsigned e = (bits >> 23) & 0xffu;
         if (e >= 1 && e < 250) bits += 4u << 23;
         amax_commit_block(words, b, blockIdx.x, __uint_as_float(bits), red);
@@ -935,6 +940,10 @@ __global__ void conv1x1_out_kernel(const float* __restrict__ feat, const float* 
 // sum |a-b| and sum (a-b)^2 (models/recurrent_model.py:512-525, util/util.py:9-20)
 __global__ void loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
                                     double* __restrict__ partial) {
+    // slice blockIdx.y of a batch (launch_loss_reduce_batch): the same blocks over the same elements as a call of its own
+    a += (size_t)blockIdx.y * n;
+    b += (size_t)blockIdx.y * n;
+    partial += (size_t)blockIdx.y * 2 * gridDim.x;
     double s1 = 0.0, s2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
@@ -960,6 +969,8 @@ __global__ void loss_partial_kernel(const float* __restrict__ a, const float* __
     }
 }
 __global__ void loss_final_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ res) {
+    partial += (size_t)blockIdx.x * 2 * nblk;      // one block per slice
+    res += 2 * blockIdx.x;
     double s1 = 0.0, s2 = 0.0;
     for (int i = threadIdx.x; i < nblk; i += 64) {
         s1 += partial[2 * i];
@@ -1039,14 +1050,14 @@ hipError_t launch_netin(const float* raw_cur, float* green_scratch, const float*
 
 hipError_t launch_netin_bound(const float* raw_a, const float* raw_b, const float* raw_c, int B, int h, int w, int64_t raw_bstride,
                               const unsigned* prev_words, unsigned* words, hipStream_t s, unsigned* zero_a, size_t zero_na,
-                              unsigned* zero_b, size_t zero_nb) {
+                              unsigned* zero_b, size_t zero_nb, unsigned long long latch) {
     const int64_t n = (int64_t)4 * h * w;
     if (B <= 0 || n <= 0) return hipSuccess;
     if ((n & 3) || (raw_bstride & 3)) return hipErrorInvalidValue;      // 16-B loads (n = 4hw: always)
     int nblk = (int)((n / 4 + 256 * 8 - 1) / (256 * 8));
     nblk = nblk < 1 ? 1 : (nblk > 64 ? 64 : nblk);
     hipLaunchKernelGGL(netin_bound_kernel, dim3(nblk, B), dim3(256), 0, s, raw_a, raw_b, raw_c, n, raw_bstride ? raw_bstride : n,
-                       prev_words, words, zero_a, zero_na, zero_b, zero_nb);
+                       prev_words, words, zero_a, zero_na, zero_b, zero_nb, latch);
     return hipGetLastError();
 }
 
@@ -1059,13 +1070,13 @@ bool netin_small_applies(int B, int h, int w, bool future) {
 }
 hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const float* prev4, const float* flow_prev, float* netin, int B,
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,
-                              hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb) {
+                              hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb, unsigned long long latch) {
     if (B <= 0 || h <= 0 || w <= 0) return hipSuccess;
     const int tiles_x = (2 * w + 15) / 16, tiles_y = (2 * h + 15) / 16;
     const int64_t rbs = raw_bstride ? raw_bstride : (int64_t)4 * h * w, fbs = flow_bstride ? flow_bstride : (int64_t)2 * h * w;
     const NetinArgs a{raw_cur, nullptr, prev4, flow_prev, nullptr, nullptr, B, h, w, rbs, fbs};
     hipLaunchKernelGGL(netin_small_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, s, a, netin, raw_prev, prev_words, words, zero_a,
-                       zero_na, zero_b, zero_nb, tiles_x);
+                       zero_na, zero_b, zero_nb, tiles_x, latch);
     return hipGetLastError();
 }
 
@@ -1217,5 +1228,50 @@ hipError_t launch_loss_reduce(const float* a, const float* b, int64_t n, double*
                               double* result2, hipStream_t s) {
     hipLaunchKernelGGL(loss_partial_kernel, dim3(nblk), dim3(256), 0, s, a, b, n, partial);
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, s, partial, nblk, result2);
+    return hipGetLastError();
+}
+
+hipError_t launch_loss_reduce_batch(const float* a, const float* b, int nslices, int64_t n, double* partial, int nblk,
+                                    double* result2, hipStream_t s) {
+    if (nslices <= 0) return hipSuccess;
+    hipLaunchKernelGGL(loss_partial_kernel, dim3(nblk, nslices), dim3(256), 0, s, a, b, n, partial);
+    hipLaunchKernelGGL(loss_final_kernel, dim3(nslices), dim3(64), 0, s, partial, nblk, result2);
+    return hipGetLastError();
+}
+
+// The latch of a partial reset (rvdd_reset_slots): the recurrent features and every set of amax words of the sequences in
+// `mask` are zeroed, as the memsets of a first step zero them for the whole batch.  Grid (blocks, popcount(mask)): block row y
+// serves the y-th set bit, so one launch covers any set of slots without a mask on the device.  Pure store bandwidth (177 MB of
+// features per 720p sequence): 16-B stores, grid-stride.  `feat` (nullable): [B][feat4] float4; `words` (nullable):
+// [nsets][B][kAmaxSeqWords].
+__global__ __launch_bounds__(256) void latch_zero_kernel(unsigned long long mask, f32x4* __restrict__ feat, int64_t feat4,
+                                                         unsigned* __restrict__ words, int nsets, int B) {
+    unsigned long long m = mask;
+    for (unsigned k = 0; k < blockIdx.y; ++k) m &= m - 1;
+    const int b = __builtin_ctzll(m);
+    const int64_t me = (int64_t)blockIdx.x * 256 + threadIdx.x, all = (int64_t)gridDim.x * 256;
+    if (feat) {
+        f32x4* p = feat + (size_t)b * feat4;
+        for (int64_t i = me; i < feat4; i += all) p[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (words) {
+        constexpr int kQ = kAmaxSeqWords / 4;
+        for (int64_t i = me; i < (int64_t)nsets * kQ; i += all) {
+            const int set = (int)(i / kQ), j = (int)(i - (int64_t)set * kQ);
+            reinterpret_cast<uint4*>(words + ((size_t)set * B + b) * kAmaxSeqWords)[j] = uint4{0u, 0u, 0u, 0u};
+        }
+    }
+}
+
+hipError_t launch_latch_zero(unsigned long long mask, float* feat, int64_t feat_per_seq, unsigned* words, int nsets, int B, hipStream_t s) {
+    const int nseq = __builtin_popcountll(mask);
+    if (!nseq || (!feat && !words)) return hipSuccess;
+    if (B > 64 || (B < 64 && (mask >> B)) || (feat_per_seq & 3)) return hipErrorInvalidValue;
+    const int64_t feat4 = feat ? feat_per_seq / 4 : 0, words4 = words ? (int64_t)nsets * (kAmaxSeqWords / 4) : 0;
+    const int64_t work = feat4 > words4 ? feat4 : words4;
+    int64_t nblk = (work + 256 * 4 - 1) / (256 * 4);        // four 16-B stores per thread, at most 1024 blocks per sequence
+    nblk = nblk < 1 ? 1 : (nblk > 1024 ? 1024 : nblk);
+    hipLaunchKernelGGL(latch_zero_kernel, dim3((unsigned)nblk, nseq), dim3(256), 0, s, mask, reinterpret_cast<f32x4*>(feat), feat4,
+                       words, nsets, B);
     return hipGetLastError();
 }

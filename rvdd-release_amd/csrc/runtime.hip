@@ -134,7 +134,9 @@ struct rvdd_handle {
     rvdd_cfg cfg{};
     std::string err;
     bool finalized = false;
-    bool need_init = true;
+    bool need_init = true;        // every sequence starts a video on the next step (create, rvdd_reset)
+    uint64_t pend_mask = 0;       // rvdd_reset_slots: the sequences that start a video on the next step (B <= 64; never all of them:
+                                  // a full mask is need_init, so that the all-slots step issues the launches it always has)
     bool force_wino = false;      // Winograd at every size (RVDD_CONV=winograd / rvdd_set_option "conv_kernel" 2): tests + measurement
     bool warp_raw = false;        // --warp_raw (rvdd_set_option): warp the re-mosaicked frames at raw resolution, demosaic afterwards
     bool prev_noisy = false;      // --prev_noisy_frame (rvdd_set_option): the next step's "previous frame" is the demosaiced noisy one
@@ -186,6 +188,8 @@ struct rvdd_handle {
     bool amax_zero_pending = false;               // the next netin_bound launch zeroes the step-after-next's set and features slot
     double* loss_partial = nullptr;
     double* loss_result = nullptr;
+    double* loss_batch = nullptr;    // rvdd_psnr_l1_batch: partial sums and results of every slice, grown on demand
+    size_t loss_batch_cap = 0;       // doubles
     float* scratch = nullptr;
     size_t scratch_bytes = 0;
     Tvl1Workspace* tvl1 = nullptr;   // cached for the last (nx, ny)
@@ -726,7 +730,8 @@ int run_pre5(rvdd_t* h, const float* netin, float* part, hipStream_t s, Sub sub)
 // What rvdd_step does in front of the net (demosaic, warps): the caller's frame and flow pointers of one step.
 // run_convunet calls it per sequence when the full-resolution stages run depth first; null for rvdd_unet_forward.
 struct StepInputs {
-    const float* raw_prev = nullptr;      // only on the first step of a video
+    const float* raw_prev = nullptr;      // only on the first step of a video (of any sequence)
+    unsigned long long latch = 0;         // the sequences that start a video on this step: ~0 = all, else bit b (B <= 64)
     const float* raw_cur = nullptr;
     const float* raw_next = nullptr;
     const float* flow_prev = nullptr;
@@ -1017,6 +1022,7 @@ void rvdd_destroy(rvdd_t* h) {
     if (h->gstream) (void)hipStreamDestroy(h->gstream);
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->scratch) (void)hipFree(h->scratch);
+    if (h->loss_batch) (void)hipFree(h->loss_batch);
     tvl1_free(h->tvl1);
     for (auto& p : h->pending) {
         (void)hipEventDestroy(p.e0);
@@ -1266,6 +1272,29 @@ int rvdd_reset(rvdd_t* h) {
     return RVDD_OK;
 }
 
+int rvdd_reset_slots(rvdd_t* h, const uint8_t* mask) {
+    if (!h) return RVDD_ERR_ARG;
+    if (!mask) return fail(h, RVDD_ERR_ARG, "rvdd_reset_slots: mask is required");
+    const int B = h->cfg.batch;
+    int count = 0;
+    for (int b = 0; b < B; ++b) count += mask[b] != 0;
+    if (count == 0) return RVDD_OK;
+    if (count == B) {                 // every slot: exactly rvdd_reset (and its launches)
+        h->need_init = true;
+        return RVDD_OK;
+    }
+    if (B > 64) return fail(h, RVDD_ERR_ARG, "rvdd_reset_slots: a mask of some slots needs batch <= 64 (batch is %d)", B);
+    uint64_t m = h->pend_mask;
+    for (int b = 0; b < B; ++b)
+        if (mask[b]) m |= 1ull << b;
+    if (m == (B == 64 ? ~0ull : (1ull << B) - 1)) {
+        h->need_init = true;
+        m = 0;
+    }
+    h->pend_mask = m;
+    return RVDD_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1294,6 +1323,9 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
     const size_t zero_na = amax_bytes(h->cfg.batch, AMAX_NREG) / 4, zero_nb = amax_bytes(h->cfg.batch, 1) / 4;
     const bool zero_now = bfp && h->amax_zero_pending;
     h->amax_zero_pending = false;
+    // which of these sequences start a video (rvdd_reset_slots): they bound the network input from raw_prev, the others from the
+    // words of their previous output -- each sequence gets the words it would get alone
+    const unsigned long long latch = in.latch == ~0ull ? ~0ull : (o < 64 ? in.latch >> o : 0ull);
     if (h->warp_raw && !nw) {
         // warp_frame with --warp_raw (models/recurrent_model.py:149-152): HA(warp(remosaick(frame), raw-resolution flow)).
         // remosaick(HA(raw)) is raw itself, so the next frame is warped as it came.  next4 is free in this mode: its
@@ -1337,8 +1369,8 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
             h->netin_proj = false;
             const float* rp_ = in.raw_prev ? in.raw_prev + o * in.rawf : nullptr;
             HIPCHK(h, launch_netin_small(rc_, rp_, h->lastden4 + o * img * 4, fp_, netin, n, H / 2, W / 2, (int64_t)in.rawf, (int64_t)in.flowf,
-                                         amax_netin && !in.raw_prev ? amax_words(h, h->amax_feat_in, o) : nullptr, amax_netin, s,
-                                         zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb));
+                                         amax_netin && latch != ~0ull ? amax_words(h, h->amax_feat_in, o) : nullptr, amax_netin, s,
+                                         zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch));
             goto prologue_features;
         }
         if (amax_netin) {
@@ -1346,9 +1378,16 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
             // with --prev_noisy_frame the "previous output" is a demosaicked frame whose raw data is gone: its own maximum
             const float* rp_ = in.raw_prev ? in.raw_prev + o * in.rawf : nullptr;
             HIPCHK(h, launch_netin_bound(rc_, rn_, rp_, n, H / 2, W / 2, (int64_t)in.rawf,
-                                         in.raw_prev ? nullptr : amax_words(h, h->amax_feat_in, o), amax_netin, s,
-                                         zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb));
-            if (h->prev_noisy && !in.raw_prev) HIPCHK(h, launch_amax_reduce(h->lastden4 + o * img * 4, n, (int64_t)img * 4, amax_netin, s, 1));
+                                         latch == ~0ull ? nullptr : amax_words(h, h->amax_feat_in, o), amax_netin, s,
+                                         zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch));
+            if (h->prev_noisy && latch != ~0ull)      // over the runs of sequences that continue a video (one run without a reset)
+                for (int b = 0; b < n;) {
+                    if ((latch >> b) & 1ull) { ++b; continue; }
+                    int e = b + 1;
+                    while (e < n && !((latch >> e) & 1ull)) ++e;
+                    HIPCHK(h, launch_amax_reduce(h->lastden4 + (o + b) * img * 4, e - b, (int64_t)img * 4, amax_netin + (size_t)b * kAmaxSeqWords, s, 1));
+                    b = e;
+                }
         }
         // ConvNeXtUnet: the input's only reader is the 1x1 projection of the first ConvBlock, which rides in the same kernel
         const NextBlk* first = h->is_next() && h->next_projfuse ? &h->nx[h->has_feat() ? NX_PRE : NX_ENC0_0] : nullptr;
@@ -1372,12 +1411,14 @@ prologue_features:
 
 // Every launch of one frame-step, in order, on stream s.  `init` = first frame of a video.
 int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const float* raw_next, const float* flow_prev,
-                 const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, bool init, hipStream_t s) {
+                 const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, bool init, uint64_t pend, hipStream_t s) {
     const bool nw = h->no_warp;
     const int B = h->cfg.batch, H = h->cfg.height, W = h->cfg.width;
     const size_t npix = (size_t)B * H * W;
+    if (init) pend = 0;
     StepInputs in;
-    in.raw_prev = init ? raw_prev : nullptr;
+    in.raw_prev = init || pend ? raw_prev : nullptr;
+    in.latch = init ? ~0ull : pend;
     in.raw_cur = raw_cur; in.raw_next = raw_next; in.flow_prev = flow_prev; in.flow_next = flow_next;
     in.rawf = raw_stride ? (size_t)raw_stride : (size_t)4 * (H / 2) * (W / 2);
     in.flowf = flow_stride ? (size_t)flow_stride : (size_t)2 * (H / 2) * (W / 2);
@@ -1395,6 +1436,22 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
         // (models/recurrent_model.py:233-245)
         HIPCHK(h, launch_demosaic(raw_prev, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf));
         if (h->has_feat()) HIPCHK(h, hipMemsetAsync(h->lastfeat, 0, npix * kF * sizeof(float), s));
+    } else if (pend) {
+        // some sequences start a video (rvdd_reset_slots): the same latch for them alone -- the demosaic over each run of
+        // them, then ONE launch that zeroes their features and their words in every set (the rotation of the sets by step_ctr
+        // is harmless only because a latched sequence has all of them zeroed)
+        const size_t img = (size_t)H * W;
+        for (int b = 0; b < B;) {
+            if (!((pend >> b) & 1u)) { ++b; continue; }
+            int e = b + 1;
+            while (e < B && ((pend >> e) & 1u)) ++e;
+            HIPCHK(h, launch_demosaic(raw_prev + b * in.rawf, h->green + b * img, h->lastden4 + b * img * 4, e - b, H / 2, W / 2,
+                                      (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf));
+            b = e;
+        }
+        const bool words = h->bfp && h->split16 && !h->is_next();
+        HIPCHK(h, launch_latch_zero(pend, h->has_feat() ? h->lastfeat : nullptr, (int64_t)img * kF, words ? h->amax : nullptr, AMAX_SLOTS,
+                                    B, s));
     }
     // without warping the previous features are read in place: the net consumes them in its first layer and only
     // its last one writes the new ones
@@ -1437,22 +1494,24 @@ int rvdd_step_strided(rvdd_t* h, const float* raw_prev, const float* raw_cur, co
     }
     const bool nw = h->no_warp;
     if (!raw_cur || (!flow_prev && !nw) || !out_rgb) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_cur, flow_prev and out_rgb are required");
-    if (h->need_init && !raw_prev) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_prev is required on the first step of a video");
+    if ((h->need_init || h->pend_mask) && !raw_prev) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_prev is required on the first step of a video");
     if (h->cfg.future && (!raw_next || (!flow_next && !nw))) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_next and flow_next are required when future=1");
     if (nw) flow_prev = flow_next = nullptr;      // the flows are not looked at (the reference's dataset does not even load them)
     hipStream_t s = static_cast<hipStream_t>(stream);
     // need_init is cleared only once the step has been enqueued: a step that failed half way leaves the handle asking
     // for the first frame of a video again (raw_prev, zeroed features), never a later frame on stale state
     const bool init = h->need_init;
+    const uint64_t pend = init ? 0 : h->pend_mask;
     auto eager = [&]() -> int {
-        const int rc = enqueue_step(h, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, s);
+        const int rc = enqueue_step(h, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, pend, s);
         if (rc == RVDD_OK) {
             h->need_init = false;
+            h->pend_mask = 0;
             h->step_ctr = (h->step_ctr + 1) % 6;      // (the amax words' set and slots follow it: & 1, % 3)
         }
         return rc;
     };
-    if (!h->use_graphs || h->prof_on || !h->ran_eagerly || !h->gstream) {
+    if (!h->use_graphs || h->prof_on || !h->ran_eagerly || !h->gstream || pend) {      // a partial reset is never captured
         h->ran_eagerly = true;
         return eager();
     }
@@ -1466,7 +1525,7 @@ int rvdd_step_strided(rvdd_t* h, const float* raw_prev, const float* raw_cur, co
         int rc = RVDD_OK;
         if (e == hipSuccess) {
             const bool serp = h->serpentine;
-            rc = enqueue_step(h, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, h->gstream);
+            rc = enqueue_step(h, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, 0, h->gstream);
             h->serpentine = serp;                              // the replay below advances it
             e = hipStreamEndCapture(h->gstream, &g);
         }
@@ -1499,6 +1558,7 @@ int rvdd_step_strided(rvdd_t* h, const float* raw_prev, const float* raw_cur, co
     HIPCHK(h, hipEventRecord(h->g_out, h->gstream));
     HIPCHK(h, hipStreamWaitEvent(s, h->g_out, 0));
     h->need_init = false;
+    h->pend_mask = 0;
     h->step_ctr = (h->step_ctr + 1) % 6;
     if (seq_major_on(h)) h->serpentine = !h->serpentine;
     return RVDD_OK;
@@ -1526,6 +1586,7 @@ int rvdd_set_state(rvdd_t* h, const float* lastden, const float* lastfeat, void*
     if (lastden) {
         HIPCHK(h, launch_nchw_to_nhwc(lastden, h->lastden4, B, 3, H, W, 4, s));
         h->need_init = false;
+        h->pend_mask = 0;
     }
     if (lastfeat) HIPCHK(h, launch_nchw_to_nhwc(lastfeat, h->lastfeat, B, kF, H, W, kF, s));
     if ((lastden || lastfeat) && h->bfp && h->split16 && !h->is_next()) {
@@ -1553,6 +1614,38 @@ int rvdd_psnr_l1(rvdd_t* h, const float* den, const float* gt, int64_t count, fl
         return fail(h, RVDD_ERR_HIP, "rvdd_psnr_l1: an asynchronous rvdd_tvl1flow_batch before this call failed: %s", hipGetErrorString(e));
     out2[0] = (float)(100.0 * r[0] / (double)count);
     out2[1] = (float)(10.0 * std::log10(4.0 / (r[1] / (double)count)));
+    return RVDD_OK;
+}
+
+int rvdd_psnr_l1_batch(rvdd_t* h, const float* den, const float* gt, int32_t n, int64_t count, float* out, void* stream) {
+    if (h && n == 0) return RVDD_OK;
+    if (!h || !den || !gt || !out || n < 0 || count <= 0) return fail(h, RVDD_ERR_ARG, "rvdd_psnr_l1_batch: bad argument");
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int nblk = (int)((count + 256 * 16 - 1) / (256 * 16));      // rvdd_psnr_l1's partition of every slice
+    if (nblk > 1024) nblk = 1024;
+    const size_t need = (size_t)n * (2 * nblk + 2);
+    if (h->loss_batch_cap < need) {
+        if (h->loss_batch) {
+            HIPCHK(h, hipDeviceSynchronize());
+            HIPCHK(h, hipFree(h->loss_batch));
+            h->loss_batch = nullptr;
+            h->loss_batch_cap = 0;
+        }
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->loss_batch), need * sizeof(double)));
+        h->loss_batch_cap = need;
+    }
+    double* res = h->loss_batch + (size_t)n * 2 * nblk;
+    HIPCHK(h, launch_loss_reduce_batch(den, gt, n, count, h->loss_batch, nblk, res, s));
+    std::vector<double> r((size_t)2 * n);
+    HIPCHK(h, hipMemcpyAsync(r.data(), res, r.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (hipError_t e = tvl1_check(h->tvl1, s); e != hipSuccess)
+        return fail(h, RVDD_ERR_HIP, "rvdd_psnr_l1_batch: an asynchronous rvdd_tvl1flow_batch before this call failed: %s", hipGetErrorString(e));
+    for (int i = 0; i < n; ++i) {
+        out[2 * i] = (float)(100.0 * r[2 * i] / (double)count);
+        out[2 * i + 1] = (float)(10.0 * std::log10(4.0 / (r[2 * i + 1] / (double)count)));
+    }
     return RVDD_OK;
 }
 

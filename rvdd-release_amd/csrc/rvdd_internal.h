@@ -173,6 +173,11 @@ __device__ __forceinline__ void amax_commit_block(unsigned* words, int b, unsign
         if (t) atomicMax(words + (size_t)b * kAmaxSeqWords + (spread % kAmaxLines) * kAmaxLineWords, t);
     }
 }
+// Does sequence b start a video on this step?  `mask`: ~0 = every sequence (a first step, any B); otherwise bit b (B <= 64:
+// rvdd_reset_slots) of the launch's own sequences.
+__device__ __forceinline__ bool seq_latched(unsigned long long mask, int b) {
+    return mask == ~0ull || (b < 64 && ((mask >> b) & 1ull));
+}
 #endif
 // amax words of a dense NHWC map [B][HW][C] (the maps no split kernel's producer wrote: caller-supplied inputs and states)
 hipError_t launch_amax_reduce(const float* map, int B, int64_t hw_c, unsigned* words, hipStream_t s, int up = 0);
@@ -225,14 +230,15 @@ hipError_t launch_netin(const float* raw_cur, float* green_scratch, const float*
 // (zero_a / zero_b, nullable: word ranges the kernel also clears -- the next step's amax words, runtime.hip)
 hipError_t launch_netin_bound(const float* raw_a, const float* raw_b, const float* raw_c, int B, int h, int w, int64_t raw_bstride,
                               const unsigned* prev_words, unsigned* words, hipStream_t s, unsigned* zero_a = nullptr, size_t zero_na = 0,
-                              unsigned* zero_b = nullptr, size_t zero_nb = 0);
+                              unsigned* zero_b = nullptr, size_t zero_nb = 0, unsigned long long latch = ~0ull);
 // src NHWC48 -> dst NHWC48.
 // the three pre-stage kernels of a small frame-step without a future frame in one launch (prestage.hip netin_small_kernel); same bits
 bool netin_small_applies(int B, int h, int w, bool future);
 // (raw_prev: the first step of a video, whose bound also covers the previous raw frame -- prev_words is null then)
 hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const float* prev4, const float* flow_prev, float* netin, int B,
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,
-                              hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb);
+                              hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb,
+                              unsigned long long latch = ~0ull);
 void prestage_set_small(bool on);      // false: never; process-wide
 hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W,
                          hipStream_t s, int64_t flow_bstride = 0);
@@ -264,6 +270,13 @@ hipError_t launch_conv1x1_out(const float* feat, const float* w3x48, const float
 // partial[2*nblk] doubles scratch; result2 device floats {sum|d|, sum d^2} as doubles -> host math
 hipError_t launch_loss_reduce(const float* a, const float* b, int64_t n, double* partial, int nblk,
                               double* result2, hipStream_t s);
+// the same for `nslices` dense slices of n elements: partial[nslices][2*nblk], result2[nslices][2]; each slice's two sums are
+// bit for bit what launch_loss_reduce gives for it alone
+hipError_t launch_loss_reduce_batch(const float* a, const float* b, int nslices, int64_t n, double* partial, int nblk,
+                                    double* result2, hipStream_t s);
+// rvdd_reset_slots' latch: zero the features (feat_per_seq floats per sequence) and the amax words of every set (nsets, layout
+// [nsets][B][kAmaxSeqWords]) of the sequences in `mask` (B <= 64); either pointer nullable
+hipError_t launch_latch_zero(unsigned long long mask, float* feat, int64_t feat_per_seq, unsigned* words, int nsets, int B, hipStream_t s);
 
 // -------------------------------------------------------------- ConvNeXt ---
 struct NextBlockW {          // device pointers, one ConvBlock (networks/new_unet.py:74-103)

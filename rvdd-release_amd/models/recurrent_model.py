@@ -58,7 +58,11 @@ class recurrentModel(BaseModel):
         self.n = self.to_device(input['n'])
         self.gt = self.to_device(input['gt'])
         self.image_paths = input['n_path']
-        self.first_frame = False if self.isTrain else input['FirstOfVideo']
+        # FirstOfVideo: one bool for the whole batch, or one per sequence (a length-B sequence / bool tensor: videos packed
+        # into the batch slots, data/packed.py) -- then only those slots restart and the losses are kept per sequence
+        first = False if self.isTrain else input['FirstOfVideo']
+        self.per_slot = not isinstance(first, bool)
+        self.first_frame = [bool(v) for v in (first.tolist() if hasattr(first, "tolist") else first)] if self.per_slot else first
         # --no_warp: the dataset yields no flows and the reference never reads them (recurrent_model.py:117-122)
         self.flow = None if self.opt.no_warp else self.to_device(input['flow'])
 
@@ -79,7 +83,14 @@ class recurrentModel(BaseModel):
             rt.set_option("prev_noisy_frame", int(bool(self.opt.prev_noisy_frame)))
             rt.set_option("warp_raw", int(bool(self.opt.warp_raw)))
             rt.reset()
-        if self.training_unrollings == 1 or self.first_frame:
+        if self.training_unrollings == 1:
+            rt.reset()
+        elif self.per_slot:
+            if len(self.first_frame) != B:
+                raise RuntimeError(f"FirstOfVideo has {len(self.first_frame)} entries for a batch of {B}")
+            if any(self.first_frame):
+                rt.reset(slots=self.first_frame)
+        elif self.first_frame:
             rt.reset()
         n, fl = self.n, self.flow
         self.denoised = rt.step(n[:, 0:4], n[:, 4:8], n[:, 8:12] if fD else None,
@@ -88,7 +99,19 @@ class recurrentModel(BaseModel):
     def compute_losses(self):
         """Test branch of recurrent_model.py:512-525."""
         gt_2 = self.gt[:, -self.gt_nc:, :, :]
+        if getattr(self, "per_slot", False):
+            # per sequence (one synchronisation), each what a batch of one gives; get_current_losses() holds their means
+            scale = self.opt.lambda_L1 / 100.0
+            self.sample_losses = [{'L1': l1 * scale, 'PSNR': p, 'Denoiser': l1 * scale}
+                                  for l1, p in self._rt.psnr_l1_batch(self.denoised, gt_2.contiguous())]
+            for name in self.loss_names:
+                setattr(self, 'loss_' + name, sum(d[name] for d in self.sample_losses) / len(self.sample_losses))
+            return
         l1, p = self._rt.psnr_l1(self.denoised, gt_2)
         self.loss_L1 = l1 * (self.opt.lambda_L1 / 100.0)
         self.loss_PSNR = p
         self.loss_Denoiser = self.loss_L1
+
+    def get_sample_losses(self):
+        """Per-sequence losses of the last compute_losses on a batch with a per-sequence FirstOfVideo: [{name: value}] * B."""
+        return list(getattr(self, "sample_losses", []))

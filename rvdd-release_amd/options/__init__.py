@@ -26,6 +26,7 @@ def make_opt(**overrides) -> Namespace:
         dataset_mode='axel4rec', serial_batches=False, num_threads=4, max_dataset_size=90000,
         val_dataroot='./datasets/validation_dataset', val_dataset_mode='infer4rec', val_videos='000,001,002,003,004',
         crop_data=None, warpeddata=False,
+        val_batch_size=1,                    # validation: videos packed into this many batch slots (data/packed.py); 1 = one frame per step
     )
     for k, v in overrides.items():
         if not hasattr(opt, k):

@@ -7,7 +7,7 @@ is what crosses the C ABI) and the HIP stream; all arithmetic is in
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -108,8 +108,26 @@ class RvddRuntime:
         self._check(self.lib.rvdd_finalize_weights(self.h), "rvdd_finalize_weights")
 
     # -- hot path -----------------------------------------------------------
-    def reset(self):
-        self._check(self.lib.rvdd_reset(self.h), "rvdd_reset")
+    def reset(self, slots=None):
+        """FirstOfVideo.  `slots=None`: every sequence (rvdd_reset); otherwise the sequences that start a new video on the
+        next step, as an iterable of slot indices or a [B] bool mask (rvdd_reset_slots; the others carry on)."""
+        if slots is None:
+            self._check(self.lib.rvdd_reset(self.h), "rvdd_reset")
+            return
+        items = slots.tolist() if hasattr(slots, "tolist") else list(slots)
+        mask = (C.c_uint8 * self.B)()
+        if items and all(isinstance(v, bool) for v in items):      # a [B] bool mask
+            if len(items) != self.B:
+                raise ValueError(f"reset: a slot mask needs {self.B} entries, got {len(items)}")
+            for b, v in enumerate(items):
+                mask[b] = int(v)
+        else:                                                     # slot indices
+            for b in items:
+                b = int(b)
+                if not 0 <= b < self.B:
+                    raise ValueError(f"reset: slot {b} outside 0..{self.B - 1}")
+                mask[b] = 1
+        self._check(self.lib.rvdd_reset_slots(self.h, mask), "rvdd_reset_slots")
 
     def set_option(self, name: str, value: int):
         """Options of recurrentModel that change what a step does; "no_warp" = --no_warp (flows then unused)."""
@@ -170,6 +188,19 @@ class RvddRuntime:
         self._check(self.lib.rvdd_psnr_l1(self.h, _ptr(den), _ptr(gt), den.numel(), out, self._stream()),
                     "rvdd_psnr_l1")
         return float(out[0]), float(out[1])
+
+    def psnr_l1_batch(self, den: torch.Tensor, gt: torch.Tensor) -> List[Tuple[float, float]]:
+        """psnr_l1 of every sequence of a batch ([n, ...] each), one synchronisation: [(L1*100, PSNR)] * n, each pair
+        bit for bit what psnr_l1 gives for that sequence alone."""
+        den = _chk_dev(den, den.shape, "den", self.device)
+        gt = _chk_dev(gt, den.shape, "gt", self.device)
+        n = den.shape[0] if den.dim() else 1
+        if n == 0:
+            return []
+        out = (C.c_float * (2 * n))()
+        self._check(self.lib.rvdd_psnr_l1_batch(self.h, _ptr(den), _ptr(gt), n, den.numel() // n, out, self._stream()),
+                    "rvdd_psnr_l1_batch")
+        return [(float(out[2 * i]), float(out[2 * i + 1])) for i in range(n)]
 
     # -- single ops -----------------------------------------------------------
     def unet_forward(self, x, feat_in=None):
