@@ -40,6 +40,16 @@ enum rvdd_status {
     RVDD_ERR_NOMEM = -5
 };
 
+/* Colour-filter layouts of the packed raw frames (util/Hamilton_Adam_demo.py:175-224).  The packing is the same for
+ * every pattern: channel k of a [B,4,h,w] frame holds CFA position (k >> 1, k & 1) of each 2x2 cell (pack_in_one,
+ * :226-234); the pattern names the colours at the four positions, row by row: GBRG = G B / R G, and so on. */
+enum rvdd_bayer {
+    RVDD_BAYER_GBRG = 0,    /* the reference model's pattern (models/recurrent_model.py:99); the default */
+    RVDD_BAYER_GRBG = 1,
+    RVDD_BAYER_RGGB = 2,
+    RVDD_BAYER_BGGR = 3
+};
+
 /* netDenoiser families (networks/__init__.py:121-176). */
 enum rvdd_arch {
     RVDD_ARCH_CONVUNET = 0,       /* convunet-mode=fixedfeatures       networks/unet.py:595-720 */
@@ -97,7 +107,8 @@ int rvdd_reset_slots(rvdd_t* h, const uint8_t* mask);
  * forward, test branch (models/recurrent_model.py:105-135, 161-349):
  * Hamilton-Adams demosaic, flow x2 upsample, bicubic backward warp of the
  * previous output / features / next frame, U-Net forward, state hand-over.
- *   raw_prev, raw_cur, raw_next : [B,4,H/2,W/2] packed GBRG raw in [-1,1]
+ *   raw_prev, raw_cur, raw_next : [B,4,H/2,W/2] packed raw in the handle's Bayer pattern
+ *                                 (rvdd_set_option "bayer_pattern", default GBRG), in [-1,1]
  *                                 (raw_prev is read only on the first step after
  *                                  create/reset, and for the slots rvdd_reset_slots
  *                                  marked; raw_next only when future=1)
@@ -146,9 +157,14 @@ int rvdd_unet_forward(rvdd_t* h, const float* x, const float* feat_in, float* ou
                       void* stream);
 
 /* HamiltonAdam('gbrg').forward (util/Hamilton_Adam_demo.py:249-289):
- *   raw [n,4,h,w] -> rgb [n,3,2h,2w]. */
+ *   raw [n,4,h,w] -> rgb [n,3,2h,2w].  rvdd_demosaic_ha_bayer with RVDD_BAYER_GBRG. */
 int rvdd_demosaic_ha(rvdd_t* h, const float* raw, int32_t n, int32_t hh, int32_t ww, float* rgb,
                      void* stream);
+
+/* HamiltonAdam(pattern).forward (util/Hamilton_Adam_demo.py:175-289) for any of the four patterns (enum
+ * rvdd_bayer; any other value is RVDD_ERR_ARG): raw [n,4,h,w] -> rgb [n,3,2h,2w]. */
+int rvdd_demosaic_ha_bayer(rvdd_t* h, const float* raw, int32_t n, int32_t hh, int32_t ww, int32_t pattern,
+                           float* rgb, void* stream);
 
 /* util.flow_utils.warp(x, flow, "bicubic")[0] (util/flow_utils.py:70-102):
  *   x [n,c,H,W], flow [n,2,H,W] at full resolution -> y [n,c,H,W]. */
@@ -259,6 +275,10 @@ int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, 
  *               order, a few 1e-7 apart).
  *   "block_fp": 0 = the split-f16 convs split their operands without the per-map power of two (the A/B reference of the block
  *               floating point; right only while every activation stays within 2^-14 .. 65504).  Default 1.
+ *   "bayer_pattern": enum rvdd_bayer of the packed raw frames rvdd_step is handed (--bayer_pattern): every demosaic and
+ *               re-mosaic of a step follows it -- the current and next frames, raw_prev on a first step and on
+ *               rvdd_reset_slots, --prev_noisy_frame and --warp_raw.  Default 0 (GBRG); any other value than 0..3 is
+ *               RVDD_ERR_ARG.  Per handle.
  * Unknown names are an error. */
 int rvdd_set_option(rvdd_t* h, const char* name, int32_t value);
 

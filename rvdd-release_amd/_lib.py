@@ -39,6 +39,7 @@ _PROTOS = {
     "rvdd_psnr_l1_batch": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P]),
     "rvdd_unet_forward": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "rvdd_demosaic_ha": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rvdd_demosaic_ha_bayer": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_warp_bicubic": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_upsample_factor_2": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                          _P, _P]),

@@ -14,8 +14,16 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 __device__ __forceinline__ float signf(float v) { return (float)((v > 0.f) - (v < 0.f)); }
 
 // ------------------------------------------------------------------ demosaic --
-// CFA of the packed GBRG frame (util/Hamilton_Adam_demo.py:226-234), replicate
-// padded: coordinates are clamped BEFORE the lookup.
+// CFA of a packed frame (util/Hamilton_Adam_demo.py:226-234), replicate
+// padded: coordinates are clamped BEFORE the lookup.  Channel k of the packed
+// frame is CFA position (k >> 1, k & 1) whatever the Bayer pattern; the pattern
+// only decides which colour sits there.  With the phase PH = (py << 1) | px
+// (bayer_phase: GBRG 0, BGGR 1, RGGB 2, GRBG 3) the colour site of full-
+// resolution pixel (y, x) is the GBRG site of (y ^ py, x ^ px), i.e. its
+// memory site XOR PH.  Memory addressing keeps (y & 1, x & 1); the demosaic's
+// arithmetic is the same for every pattern, only the site selection moves.
+// PH is a template parameter: the GBRG instantiations are the kernels as they
+// were before the pattern existed.
 struct Cfa {
     const float* raw;  // [4][h][w] of one frame
     int h, w, H, W;
@@ -24,18 +32,21 @@ struct Cfa {
         x = clampi(x, 0, W - 1);
         return raw[((size_t)(((y & 1) << 1) | (x & 1)) * h + (y >> 1)) * w + (x >> 1)];
     }
-    // sparse colour plane `site` (0 = G(e,e), 1 = B(e,o), 2 = R(o,e), 3 = G(o,o)), replicate padded
+    // sparse colour plane `site` (GBRG sites: 0 = Gb, 1 = B, 2 = R, 3 = Gr), replicate padded
+    template <int PH>
     __device__ __forceinline__ float plane(int y, int x, int site) const {
         y = clampi(y, 0, H - 1);
         x = clampi(x, 0, W - 1);
         const int s = ((y & 1) << 1) | (x & 1);
-        return s == site ? raw[((size_t)s * h + (y >> 1)) * w + (x >> 1)] : 0.f;
+        return (s ^ PH) == site ? raw[((size_t)s * h + (y >> 1)) * w + (x >> 1)] : 0.f;
     }
 };
 
+template <int PH>
 __device__ __forceinline__ float ha_green_at(const Cfa& c, int y, int x);
 // algo1 (util/Hamilton_Adam_demo.py:123-142)
 // rbs = floats from one sequence's raw frame to the next one's (4hw when dense; more for a channel slice of a wider tensor)
+template <int PH>
 __global__ void ha_green_kernel(const float* __restrict__ raw, float* __restrict__ green, int n, int h,
                                 int w, int64_t rbs) {
     const int H = 2 * h, W = 2 * w;
@@ -45,12 +56,13 @@ __global__ void ha_green_kernel(const float* __restrict__ raw, float* __restrict
     const int y = (idx / W) % H;
     const int b = idx / ((size_t)W * H);
     Cfa c{raw + (size_t)b * rbs, h, w, H, W};
-    green[idx] = ha_green_at(c, y, x);
+    green[idx] = ha_green_at<PH>(c, y, x);
 }
+template <int PH>
 __device__ __forceinline__ float ha_green_at(const Cfa& c, int y, int x) {
     const float cc = c.at(y, x);
     float gval;
-    if (((y ^ x) & 1) == 0) {
+    if (((y ^ x ^ (PH >> 1) ^ PH) & 1) == 0) {      // y ^ x ^ py ^ px even: GBRG / GRBG's green diagonal, RGGB / BGGR's other one
         gval = cc;  // measured green
     } else {
         const float l1 = c.at(y, x - 1), r1 = c.at(y, x + 1), l2 = c.at(y, x - 2), r2 = c.at(y, x + 2);
@@ -77,8 +89,9 @@ __device__ __forceinline__ float ha_green_at(const Cfa& c, int y, int x) {
 // its s_waitcnt vmcnt(0) -- 25 dependent round trips per pixel in netin_kernel, profiles/r06g_netin_load_batches.txt).
 struct Ring {
     float g[3][3], r[3][3];
-    int site[3][3];      // CFA site of the (clamped) neighbour
+    int site[3][3];      // colour site of the (clamped) neighbour (GBRG numbering: the memory site XOR PH)
 };
+template <int PH>
 __device__ __forceinline__ void load_ring(const Cfa& c, const float* __restrict__ gp, int H, int W, int y, int x, Ring& q) {
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy)
@@ -86,19 +99,20 @@ __device__ __forceinline__ void load_ring(const Cfa& c, const float* __restrict_
         for (int dx = 0; dx < 3; ++dx) {
             const int yy = clampi(y + dy - 1, 0, H - 1), xx = clampi(x + dx - 1, 0, W - 1);
             const int st = ((yy & 1) << 1) | (xx & 1);
-            q.site[dy][dx] = st;
+            q.site[dy][dx] = st ^ PH;
             q.g[dy][dx] = gp[(size_t)yy * W + xx];
             q.r[dy][dx] = c.raw[((size_t)st * c.h + (yy >> 1)) * c.w + (xx >> 1)];
         }
 }
 
 // algo2 (util/Hamilton_Adam_demo.py:145-172) for red (k = 0) and blue (k = 1) at the ring's centre pixel (y, x)
+template <int PH>
 __device__ __forceinline__ void ha_red_blue(const Ring& q, int y, int x, float (&rb)[2]) {
     auto G = [&](int dy, int dx) { return q.g[dy + 1][dx + 1]; };
     // sparse colour plane `own` at a neighbour (Cfa::plane): the sample where the neighbour's site is `own`, zero elsewhere
     auto P = [&](int dy, int dx, int own) { return q.site[dy + 1][dx + 1] == own ? q.r[dy + 1][dx + 1] : 0.f; };
     const float g0 = q.g[1][1];
-    const int site = ((y & 1) << 1) | (x & 1);   // 0 Gb(e,e) 1 B 2 R 3 Gr(o,o)
+    const int site = (((y & 1) << 1) | (x & 1)) ^ PH;   // colour site: 0 Gb 1 B 2 R 3 Gr (GBRG: (e,e) (e,o) (o,e) (o,o))
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int own = k == 0 ? 2 : 1;          // the channel's own CFA site (R / B)
@@ -135,6 +149,7 @@ __device__ __forceinline__ void ha_red_blue(const Ring& q, int y, int x, float (
     }
 }
 
+template <int PH>
 __global__ void ha_rb_kernel(const float* __restrict__ raw, const float* __restrict__ green,
                              float* __restrict__ out, int n, int h, int w, int64_t bstride, int pstride,
                              int cstride, int64_t rbs) {
@@ -147,10 +162,10 @@ __global__ void ha_rb_kernel(const float* __restrict__ raw, const float* __restr
     Cfa c{raw + (size_t)b * rbs, h, w, H, W};
     const float* gp = green + (size_t)b * H * W;
     Ring q;
-    load_ring(c, gp, H, W, y, x, q);
+    load_ring<PH>(c, gp, H, W, y, x, q);
     const float g0 = q.g[1][1];
     float rb[2];
-    ha_red_blue(q, y, x, rb);
+    ha_red_blue<PH>(q, y, x, rb);
     float* o = out + (size_t)b * bstride + ((size_t)y * W + x) * pstride;
     o[0] = rb[0];
     o[cstride] = g0;
@@ -297,6 +312,7 @@ __device__ __forceinline__ f32x4 warp3_sum(const Taps& t, const f32x4 (&v)[16]) 
 struct NetinArgs {
     const float *raw_cur, *green, *prev4, *flow_prev, *next4, *flow_next;
     int B, h, w;
+    int bayer;          // enum rvdd_bayer of raw_cur: picks the kernel's instantiation (the kernels read their phase PH, not this)
     int64_t rbs, fbs;
 };
 // Three batches of loads, each in flight together: (1) the flow vectors around the pixel (both directions) and the 3x3 rings of the
@@ -304,6 +320,7 @@ struct NetinArgs {
 // arithmetic between them.  Written as one expression after another (round 1-5) the compiler kept the kernel at 8 waves per SIMD by
 // issuing every load next to its use: ~60 dependent memory round trips per pixel, waves 75 % of their life in s_waitcnt
 // (profiles/r06f_c4_prestage_counters.json).  Same operations on the same values: same bits.
+template <int PH>
 __device__ __forceinline__ void netin_pixel(const NetinArgs& a, size_t idx, f32x4 (&o)[3]) {
     const int H = 2 * a.h, W = 2 * a.w;
     const unsigned i32 = (unsigned)idx;      // (B H W < 2^32: launch_netin checks; 64-bit divisions are ~100 instructions each)
@@ -321,7 +338,7 @@ __device__ __forceinline__ void netin_pixel(const NetinArgs& a, size_t idx, f32x
     if (warp_p) flow_fetch(a.flow_prev + (size_t)b * a.fbs, a.h, a.w, H, W, y, x, fq_p);
     if (warp_n) flow_fetch(a.flow_next + (size_t)b * a.fbs, a.h, a.w, H, W, y, x, fq_n);
     Ring q;
-    load_ring(c, gp, H, W, y, x, q);
+    load_ring<PH>(c, gp, H, W, y, x, q);
     // ---- batch 2: the taps of the previous output, gathered together (--no_warp: the pixel itself, models/recurrent_model.py:156-158)
     Taps tp;
     f32x4 vt[16];
@@ -336,7 +353,7 @@ __device__ __forceinline__ void netin_pixel(const NetinArgs& a, size_t idx, f32x
     }
     // ---- the demosaic's red and blue under the gather's flight
     float rb[2];
-    ha_red_blue(q, y, x, rb);
+    ha_red_blue<PH>(q, y, x, rb);
     const float g0 = q.g[1][1];
     if (warp_p) p = warp3_sum(tp, vt);
     // ---- batch 3: the next frame's taps (one gather's 64 registers at a time: both in flight spill)
@@ -363,11 +380,12 @@ __device__ __forceinline__ unsigned xcd_contiguous_block() {
 }
 
 // (at most five waves per SIMD asked of the compiler: with the default target of eight it serialises the loads again to save registers)
+template <int PH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void netin_kernel(NetinArgs a, float* __restrict__ netin) {
     const size_t idx = (size_t)xcd_contiguous_block() * blockDim.x + threadIdx.x;
     if (idx >= (size_t)a.B * 4 * a.h * a.w) return;
     f32x4 v[3];
-    netin_pixel(a, idx, v);
+    netin_pixel<PH>(a, idx, v);
     f32x4* o = reinterpret_cast<f32x4*>(netin) + idx * 4;
     o[0] = v[0];
     o[1] = v[1];
@@ -379,6 +397,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 // through LDS (pixel pitch 24 floats: the 16 lanes of a ds_read_b128 group on 16 distinct bank quads) and each wave projects
 // four 16-pixel groups on the f32 matrix pipe (16x16x4, exact f32 products).  pw as proj1x1_kernel<16, 0>'s:
 // [m 3][lr 16][g 4][i 4] = W[16m+lr][4g+i] (zero for channels the input does not have).
+template <int PH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void netin_proj_kernel(NetinArgs a, const float* __restrict__ pw, const float* __restrict__ bias,
                                                          float* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float s_t[256][24];
@@ -392,7 +411,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         bv[m] = *reinterpret_cast<const f32x4*>(bias + 16 * m + 4 * g);
     }
     f32x4 v[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    if (base + threadIdx.x < total) netin_pixel(a, base + threadIdx.x, v);
+    if (base + threadIdx.x < total) netin_pixel<PH>(a, base + threadIdx.x, v);
 #pragma unroll
     for (int k = 0; k < 3; ++k) *reinterpret_cast<f32x4*>(&s_t[threadIdx.x][4 * k]) = v[k];
     __syncthreads();
@@ -466,6 +485,7 @@ __global__ __launch_bounds__(256) void netin_bound_kernel(const float* __restric
 // sequence per pixel with the ring's greens from LDS, then netin_bound_kernel's tail: every raw sample of the current frame is some
 // thread's own CFA sample.  Same operations on the same values: same bits as the three kernels.  Only where the launch is small: one
 // atomic per block on the amax words costs 100 us at 28 800 blocks (720p, round 4) -- launch_netin_small refuses above 1024 blocks.
+template <int PH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void netin_small_kernel(
     NetinArgs a, float* __restrict__ netin, const float* __restrict__ raw_prev, const unsigned* __restrict__ prev_words,
     unsigned* __restrict__ words, unsigned* __restrict__ zero_a, size_t zero_na, unsigned* __restrict__ zero_b, size_t zero_nb, int tiles_x,
@@ -485,7 +505,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     Cfa c{a.raw_cur + (size_t)b * a.rbs, a.h, a.w, H, W};
     for (int i = t; i < 18 * 18; i += 256) {
         const int r = i / 18, cc = i - r * 18;
-        gs[r][cc] = ha_green_at(c, clampi(y0 - 1 + r, 0, H - 1), clampi(x0 - 1 + cc, 0, W - 1));
+        gs[r][cc] = ha_green_at<PH>(c, clampi(y0 - 1 + r, 0, H - 1), clampi(x0 - 1 + cc, 0, W - 1));
     }
     const int ly = t >> 4, lx = t & 15, y = y0 + ly, x = x0 + lx;
     const bool inside = y < H && x < W;
@@ -502,7 +522,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
             for (int dx = 0; dx < 3; ++dx) {
                 const int yy = clampi(y + dy - 1, 0, H - 1), xx = clampi(x + dx - 1, 0, W - 1);
                 const int st = ((yy & 1) << 1) | (xx & 1);
-                q.site[dy][dx] = st;
+                q.site[dy][dx] = st ^ PH;
                 q.r[dy][dx] = c.raw[((size_t)st * c.h + (yy >> 1)) * c.w + (xx >> 1)];
             }
     }
@@ -525,7 +545,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
             p = sp[(size_t)y * W + x];
         }
         float rb[2];
-        ha_red_blue(q, y, x, rb);
+        ha_red_blue<PH>(q, y, x, rb);
         const float g0 = q.g[1][1];
         if (warp_p) p = warp3_sum(tp, vt);
         f32x4* o = reinterpret_cast<f32x4*>(netin) + ((size_t)b * H * W + (size_t)y * W + x) * 4;
@@ -534,7 +554,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         o[2] = f32x4{0.f, 0.f, 0.f, 0.f};
         m = fabsf(q.r[1][1]);
         // (the first step of a video: the "previous output" is the demosaic of the previous raw frame, whose samples bound it)
-        if (lat) m = fmaxf(m, fabsf(raw_prev[(size_t)b * a.rbs + ((size_t)q.site[1][1] * c.h + (y >> 1)) * c.w + (x >> 1)]));
+        if (lat) m = fmaxf(m, fabsf(raw_prev[(size_t)b * a.rbs + ((size_t)(q.site[1][1] ^ PH) * c.h + (y >> 1)) * c.w + (x >> 1)]));
     }
     if (words) {      // netin_bound_kernel's tail
         unsigned bits = __float_as_uint(m);
@@ -989,21 +1009,38 @@ __global__ void loss_final_kernel(const double* __restrict__ partial, int nblk, 
 
 inline unsigned nblocks(size_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
+// enum rvdd_bayer -> the phase PH of the kernels' instantiations: (py << 1) | px, the row and column offset of the pattern
+// from GBRG (GBRG (0,0), GRBG (1,1), RGGB (1,0), BGGR (0,1)); -1 for a value that is no pattern
+constexpr int bayer_phase(int bayer) { return bayer == 0 ? 0 : bayer == 1 ? 3 : bayer == 2 ? 2 : bayer == 3 ? 1 : -1; }
+
+// the instantiation of kernel template K for the phase of `bayer` (a hipError_t when it is no pattern)
+#define RVDD_BAYER_DISPATCH(bayer, K, ...)                                           \
+    switch (bayer_phase(bayer)) {                                                    \
+    case 0: hipLaunchKernelGGL(K<0>, __VA_ARGS__); break;                            \
+    case 1: hipLaunchKernelGGL(K<1>, __VA_ARGS__); break;                            \
+    case 2: hipLaunchKernelGGL(K<2>, __VA_ARGS__); break;                            \
+    case 3: hipLaunchKernelGGL(K<3>, __VA_ARGS__); break;                            \
+    default: return hipErrorInvalidValue;                                            \
+    }
+
 }  // namespace
 
 hipError_t launch_demosaic(const float* raw, float* green_scratch, float* out, int n, int h, int w,
-                           int64_t bstride, int pstride, int cstride, hipStream_t s, int64_t raw_bstride) {
+                           int64_t bstride, int pstride, int cstride, hipStream_t s, int64_t raw_bstride, int bayer) {
     const size_t npix = (size_t)n * 4 * h * w;
     if (!npix) return hipSuccess;
     const int64_t rbs = raw_bstride ? raw_bstride : (int64_t)4 * h * w;
-    hipLaunchKernelGGL(ha_green_kernel, dim3(nblocks(npix, 256)), dim3(256), 0, s, raw, green_scratch, n, h, w, rbs);
-    hipLaunchKernelGGL(ha_rb_kernel, dim3(nblocks(npix, 256)), dim3(256), 0, s, raw, green_scratch, out, n, h,
-                       w, bstride, pstride, cstride, rbs);
+    RVDD_BAYER_DISPATCH(bayer, ha_green_kernel, dim3(nblocks(npix, 256)), dim3(256), 0, s, raw, green_scratch, n, h, w, rbs);
+    RVDD_BAYER_DISPATCH(bayer, ha_rb_kernel, dim3(nblocks(npix, 256)), dim3(256), 0, s, raw, green_scratch, out, n, h,
+                        w, bstride, pstride, cstride, rbs);
     return hipGetLastError();
 }
 
-// HamiltonAdam.remosaick (util/Hamilton_Adam_demo.py:237-246) from the NHWC4 previous output: packed GBRG planes
-// [B][4][H/2][W/2] = G(even row, even col), B(even, odd), R(odd, even), G(odd, odd).  Pure indexing.
+// HamiltonAdam.remosaick from the NHWC4 previous output: the packed planes [B][4][H/2][W/2] of the pattern, channel c =
+// CFA position (c >> 1, c & 1) holding the colour of its site c ^ PH -- the inverse of the packing, so remosaick(HA(raw)) is
+// raw for every pattern.  For GBRG (util/Hamilton_Adam_demo.py:237-246): G(even row, even col), B(even, odd), R(odd, even),
+// G(odd, odd).  Pure indexing.
+template <int PH>
 __global__ void remosaick4_kernel(const float* __restrict__ rgb4, float* __restrict__ raw, int B, int H, int W) {
     const int h = H / 2, w = W / 2;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1013,14 +1050,15 @@ __global__ void remosaick4_kernel(const float* __restrict__ rgb4, float* __restr
     const int c = (idx / ((size_t)w * h)) % 4;
     const int b = idx / ((size_t)4 * w * h);
     const int yy = 2 * y + (c >> 1), xx = 2 * x + (c & 1);
-    const int ch = c == 0 || c == 3 ? 1 : (c == 1 ? 2 : 0);
+    const int site = c ^ PH;
+    const int ch = site == 0 || site == 3 ? 1 : (site == 1 ? 2 : 0);
     raw[idx] = rgb4[(((size_t)b * H + yy) * W + xx) * 4 + ch];
 }
 
-hipError_t launch_remosaick4(const float* rgb4, float* raw, int B, int H, int W, hipStream_t s) {
+hipError_t launch_remosaick4(const float* rgb4, float* raw, int B, int H, int W, hipStream_t s, int bayer) {
     const size_t n = (size_t)B * H * W;
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(remosaick4_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, rgb4, raw, B, H, W);
+    RVDD_BAYER_DISPATCH(bayer, remosaick4_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, rgb4, raw, B, H, W);
     return hipGetLastError();
 }
 
@@ -1034,17 +1072,18 @@ hipError_t launch_warp3(const float* src4, const float* flow_raw, float* dst, in
 
 hipError_t launch_netin(const float* raw_cur, float* green_scratch, const float* prev4, const float* flow_prev,
                         const float* next4, const float* flow_next, float* netin, int B, int h, int w, hipStream_t s,
-                        int64_t raw_bstride, int64_t flow_bstride, const float* proj_w16, const float* proj_b, float* proj_out) {
+                        int64_t raw_bstride, int64_t flow_bstride, const float* proj_w16, const float* proj_b, float* proj_out, int bayer) {
     const size_t n = (size_t)B * 4 * h * w;
     if (!n) return hipSuccess;
     if (n >= 0x100000000ull) return hipErrorInvalidValue;      // netin_pixel's 32-bit pixel index
     const int64_t rbs = raw_bstride ? raw_bstride : (int64_t)4 * h * w, fbs = flow_bstride ? flow_bstride : (int64_t)2 * h * w;
-    hipLaunchKernelGGL(ha_green_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, raw_cur, green_scratch, B, h, w, rbs);
-    const NetinArgs a{raw_cur, green_scratch, prev4, flow_prev, next4, flow_next, B, h, w, rbs, fbs};
-    if (proj_w16)
-        hipLaunchKernelGGL(netin_proj_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, a, proj_w16, proj_b, proj_out);
-    else
-        hipLaunchKernelGGL(netin_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, a, netin);
+    const NetinArgs a{raw_cur, green_scratch, prev4, flow_prev, next4, flow_next, B, h, w, bayer, rbs, fbs};
+    RVDD_BAYER_DISPATCH(a.bayer, ha_green_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, raw_cur, green_scratch, B, h, w, rbs);
+    if (proj_w16) {
+        RVDD_BAYER_DISPATCH(a.bayer, netin_proj_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, a, proj_w16, proj_b, proj_out);
+    } else {
+        RVDD_BAYER_DISPATCH(a.bayer, netin_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, a, netin);
+    }
     return hipGetLastError();
 }
 
@@ -1070,13 +1109,14 @@ bool netin_small_applies(int B, int h, int w, bool future) {
 }
 hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const float* prev4, const float* flow_prev, float* netin, int B,
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,
-                              hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb, unsigned long long latch) {
+                              hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb, unsigned long long latch,
+                              int bayer) {
     if (B <= 0 || h <= 0 || w <= 0) return hipSuccess;
     const int tiles_x = (2 * w + 15) / 16, tiles_y = (2 * h + 15) / 16;
     const int64_t rbs = raw_bstride ? raw_bstride : (int64_t)4 * h * w, fbs = flow_bstride ? flow_bstride : (int64_t)2 * h * w;
-    const NetinArgs a{raw_cur, nullptr, prev4, flow_prev, nullptr, nullptr, B, h, w, rbs, fbs};
-    hipLaunchKernelGGL(netin_small_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, s, a, netin, raw_prev, prev_words, words, zero_a,
-                       zero_na, zero_b, zero_nb, tiles_x, latch);
+    const NetinArgs a{raw_cur, nullptr, prev4, flow_prev, nullptr, nullptr, B, h, w, bayer, rbs, fbs};
+    RVDD_BAYER_DISPATCH(a.bayer, netin_small_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, s, a, netin, raw_prev, prev_words, words,
+                        zero_a, zero_na, zero_b, zero_nb, tiles_x, latch);
     return hipGetLastError();
 }
 

@@ -141,6 +141,8 @@ struct rvdd_handle {
     bool warp_raw = false;        // --warp_raw (rvdd_set_option): warp the re-mosaicked frames at raw resolution, demosaic afterwards
     bool prev_noisy = false;      // --prev_noisy_frame (rvdd_set_option): the next step's "previous frame" is the demosaiced noisy one
     bool no_warp = false;         // --no_warp (rvdd_set_option): previous output / features / next frame enter the net unwarped
+    int bayer = 0;                // enum rvdd_bayer of the packed raw frames (rvdd_set_option "bayer_pattern"): every demosaic and
+                                  // re-mosaic of a step
     bool use_wino = true;         // 48->48 3x3 convs: Winograd F(2x2,3x3) (RVDD_CONV=direct selects the direct kernel)
     bool split16 = true;          // 48->48 3x3 convs on the F16 matrix pipe with split f32 operands (conv3x3h.hip); RVDD_CONV=f32 | direct |
                                   // winograd / "conv_kernel" 1, 2, 4 select the f32-MFMA kernels (the A/B reference)
@@ -1253,6 +1255,13 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         h->seq_major = value;
         return RVDD_OK;
     }
+    if (std::strcmp(name, "bayer_pattern") == 0) {
+        // enum rvdd_bayer of the packed raw frames rvdd_step is handed: every demosaic and re-mosaic of a step follows it
+        if (value < RVDD_BAYER_GBRG || value > RVDD_BAYER_BGGR)
+            return fail(h, RVDD_ERR_ARG, "rvdd_set_option: bayer_pattern must be 0 (GBRG), 1 (GRBG), 2 (RGGB) or 3 (BGGR)");
+        h->bayer = value;
+        return RVDD_OK;
+    }
     if (std::strcmp(name, "conv_kernel") == 0) {
         // which kernel runs the 3x3 convs: 0 = the default (48-channel layers on the split-f16 kernel, the others on an f32
         // kernel chosen by launch size), 1 = the direct f32 kernel everywhere, 2 = the Winograd f32 kernel everywhere (also
@@ -1263,7 +1272,7 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         h->split16 = value == 0;
         return RVDD_OK;
     }
-    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, cout_split, small_prestage)", name);
+    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, cout_split, small_prestage, bayer_pattern)", name);
 }
 
 int rvdd_reset(rvdd_t* h) {
@@ -1334,20 +1343,21 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
         const bool dense = in.rawf == (size_t)4 * (H / 2) * (W / 2) && in.flowf == (size_t)2 * (H / 2) * (W / 2);
         {
             Scope sc(h, s, "demosaic(ha_green+ha_rb)", 0.0, (double)n * img * 16.0);
-            HIPCHK(h, launch_demosaic(rc_, green, netin + 3, n, H / 2, W / 2, (int64_t)H * W * kNetInC, kNetInC, 1, s, (int64_t)in.rawf));
+            HIPCHK(h, launch_demosaic(rc_, green, netin + 3, n, H / 2, W / 2, (int64_t)H * W * kNetInC, kNetInC, 1, s, (int64_t)in.rawf,
+                                      h->bayer));
         }
         for (int b = 0; b < n; b += dense ? n : 1) {
             const int nb = dense ? n : 1;
             float* packed = h->next4 + (o + b) * img;
             float* warped = h->next4 + npix + (o + b) * img;
-            HIPCHK(h, launch_remosaick4(h->lastden4 + (o + b) * img * 4, packed, nb, H, W, s));
+            HIPCHK(h, launch_remosaick4(h->lastden4 + (o + b) * img * 4, packed, nb, H, W, s, h->bayer));
             HIPCHK(h, launch_warp_nchw(packed, fp_ + b * in.flowf, warped, nb, 4, H / 2, W / 2, s));
             HIPCHK(h, launch_demosaic(warped, green + b * img, netin + b * img * kNetInC + 0, nb, H / 2, W / 2, (int64_t)H * W * kNetInC,
-                                      kNetInC, 1, s));
+                                      kNetInC, 1, s, 0, h->bayer));
             if (h->cfg.future) {
                 HIPCHK(h, launch_warp_nchw(rn_ + b * in.rawf, fn_ + b * in.flowf, warped, nb, 4, H / 2, W / 2, s));
                 HIPCHK(h, launch_demosaic(warped, green + b * img, netin + b * img * kNetInC + 6, nb, H / 2, W / 2,
-                                          (int64_t)H * W * kNetInC, kNetInC, 1, s));
+                                          (int64_t)H * W * kNetInC, kNetInC, 1, s, 0, h->bayer));
             }
         }
         if (amax_netin) HIPCHK(h, launch_amax_reduce(netin, n, (int64_t)img * kNetInC, amax_netin, s));
@@ -1361,7 +1371,7 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
         float* next4 = nullptr;
         if (h->cfg.future) {
             next4 = h->next4 + o * img * 4;
-            HIPCHK(h, launch_demosaic(rn_, green, next4, n, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf));
+            HIPCHK(h, launch_demosaic(rn_, green, next4, n, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf, h->bayer));
         }
         Scope sc(h, s, "netin(ha_green+netin_kernel)", 0.0, (double)n * img * (16.0 + 16.0 + 48.0 + (next4 ? 16.0 : 0.0)));
         // small frames without a future frame: the bound, the green plane and the network input in ONE launch
@@ -1370,7 +1380,7 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
             const float* rp_ = in.raw_prev ? in.raw_prev + o * in.rawf : nullptr;
             HIPCHK(h, launch_netin_small(rc_, rp_, h->lastden4 + o * img * 4, fp_, netin, n, H / 2, W / 2, (int64_t)in.rawf, (int64_t)in.flowf,
                                          amax_netin && latch != ~0ull ? amax_words(h, h->amax_feat_in, o) : nullptr, amax_netin, s,
-                                         zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch));
+                                         zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch, h->bayer));
             goto prologue_features;
         }
         if (amax_netin) {
@@ -1394,7 +1404,7 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
         h->netin_proj = first != nullptr;
         HIPCHK(h, launch_netin(rc_, green, h->lastden4 + o * img * 4, fp_, next4, fn_, netin, n, H / 2, W / 2, s, (int64_t)in.rawf,
                                (int64_t)in.flowf, first ? first->w.proj_w : nullptr, first ? first->w.proj_b : nullptr,
-                               first ? h->lv[0].t[0] + o * img * kF : nullptr));
+                               first ? h->lv[0].t[0] + o * img * kF : nullptr, h->bayer));
     }
 prologue_features:
     if (h->has_feat() && !nw) {
@@ -1434,7 +1444,8 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
     if (init) {
         // lastden = n[:, :3] (demosaiced previous noisy frame), features = 0
         // (models/recurrent_model.py:233-245)
-        HIPCHK(h, launch_demosaic(raw_prev, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf));
+        HIPCHK(h, launch_demosaic(raw_prev, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf,
+                                  h->bayer));
         if (h->has_feat()) HIPCHK(h, hipMemsetAsync(h->lastfeat, 0, npix * kF * sizeof(float), s));
     } else if (pend) {
         // some sequences start a video (rvdd_reset_slots): the same latch for them alone -- the demosaic over each run of
@@ -1446,7 +1457,7 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
             int e = b + 1;
             while (e < B && ((pend >> e) & 1u)) ++e;
             HIPCHK(h, launch_demosaic(raw_prev + b * in.rawf, h->green + b * img, h->lastden4 + b * img * 4, e - b, H / 2, W / 2,
-                                      (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf));
+                                      (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf, h->bayer));
             b = e;
         }
         const bool words = h->bfp && h->split16 && !h->is_next();
@@ -1457,7 +1468,8 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
     // its last one writes the new ones
     const int rc = run_net(h, h->netin, nw ? h->lastfeat : h->featw, h->lastfeat, out_rgb, h->lastden4, s, &in);
     if (rc == RVDD_OK && h->prev_noisy)     // store_frame = the noisy current frame (models/recurrent_model.py:335-337)
-        HIPCHK(h, launch_demosaic(raw_cur, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf));
+        HIPCHK(h, launch_demosaic(raw_cur, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf,
+                                  h->bayer));
     return rc;
 }
 
@@ -1674,15 +1686,21 @@ int rvdd_unet_forward(rvdd_t* h, const float* x, const float* feat_in, float* ou
     return RVDD_OK;
 }
 
-int rvdd_demosaic_ha(rvdd_t* h, const float* raw, int32_t n, int32_t hh, int32_t ww, float* rgb, void* stream) {
+int rvdd_demosaic_ha_bayer(rvdd_t* h, const float* raw, int32_t n, int32_t hh, int32_t ww, int32_t pattern, float* rgb, void* stream) {
+    if (h && (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR))
+        return fail(h, RVDD_ERR_ARG, "rvdd_demosaic_ha_bayer: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
     if (h && n == 0) return RVDD_OK;       // an empty batch is valid and launches nothing
-    if (!h || !raw || !rgb || n < 0 || hh < 1 || ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_demosaic_ha: bad argument");
+    if (!h || !raw || !rgb || n < 0 || hh < 1 || ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_demosaic_ha_bayer: bad argument");
     ENTER(h);
     hipStream_t s = static_cast<hipStream_t>(stream);
     RC(ensure_scratch(h, (size_t)n * 4 * hh * ww * sizeof(float)));
     const int64_t hw = (int64_t)4 * hh * ww;
-    HIPCHK(h, launch_demosaic(raw, h->scratch, rgb, n, hh, ww, 3 * hw, 1, (int)hw, s));
+    HIPCHK(h, launch_demosaic(raw, h->scratch, rgb, n, hh, ww, 3 * hw, 1, (int)hw, s, 0, pattern));
     return RVDD_OK;
+}
+
+int rvdd_demosaic_ha(rvdd_t* h, const float* raw, int32_t n, int32_t hh, int32_t ww, float* rgb, void* stream) {
+    return rvdd_demosaic_ha_bayer(h, raw, n, hh, ww, RVDD_BAYER_GBRG, rgb, stream);
 }
 
 int rvdd_warp_bicubic(rvdd_t* h, const float* x, const float* flow, int32_t n, int32_t c, int32_t H, int32_t W,

@@ -209,8 +209,10 @@ void conv3x3_set_variant(int v);   // A/B switch used by rvdd_debug_conv_bench o
 // Hamilton-Adams: raw [n][4][h][w] -> green plane scratch [n][2h][2w] -> RGB
 // written at out[b*bstride + (y*W+x)*pstride + c*cstride].  raw_bstride: floats between the raw frames of consecutive
 // sequences (0 = dense, 4hw): the caller's raw frames may be channel slices of a wider [B][4k][h][w] tensor.
+// `bayer` (every launcher that demosaics or re-mosaics): enum rvdd_bayer of the packed raw frames (channel k = CFA position
+// (k >> 1, k & 1) of each 2x2 cell, whatever the pattern); hipErrorInvalidValue for any other value.
 hipError_t launch_demosaic(const float* raw, float* green_scratch, float* out, int n, int h, int w,
-                           int64_t bstride, int pstride, int cstride, hipStream_t s, int64_t raw_bstride = 0);
+                           int64_t bstride, int pstride, int cstride, hipStream_t s, int64_t raw_bstride, int bayer);
 
 // bicubic backward warp with the raw-resolution flow (x2 bilinear upsample,
 // align_corners=True, times 2, fused).  src NHWC4 -> dst[(b*H*W + p)*dpstride + c], c<3.
@@ -223,8 +225,8 @@ hipError_t launch_warp3(const float* src4, const float* flow_raw, float* dst, in
 // proj_w16 / proj_b (launch_proj1x1's (16, 0) arrangement) instead (prestage.hip netin_proj_kernel)
 hipError_t launch_netin(const float* raw_cur, float* green_scratch, const float* prev4, const float* flow_prev,
                         const float* next4, const float* flow_next, float* netin, int B, int h, int w, hipStream_t s,
-                        int64_t raw_bstride = 0, int64_t flow_bstride = 0, const float* proj_w16 = nullptr,
-                        const float* proj_b = nullptr, float* proj_out = nullptr);
+                        int64_t raw_bstride, int64_t flow_bstride, const float* proj_w16, const float* proj_b, float* proj_out,
+                        int bayer);
 // amax words of that network input (block floating point of the split-f16 convs, below): an upper bound from the packed raw
 // frames it is made of (up to three, each nullable) and from `prev_words`, words that bound the previous output (nullable)
 // (zero_a / zero_b, nullable: word ranges the kernel also clears -- the next step's amax words, runtime.hip)
@@ -238,7 +240,7 @@ bool netin_small_applies(int B, int h, int w, bool future);
 hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const float* prev4, const float* flow_prev, float* netin, int B,
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,
                               hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb,
-                              unsigned long long latch = ~0ull);
+                              unsigned long long latch, int bayer);
 void prestage_set_small(bool on);      // false: never; process-wide
 hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W,
                          hipStream_t s, int64_t flow_bstride = 0);
@@ -247,7 +249,8 @@ hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, in
 hipError_t launch_warp48_proj(const float* src, const float* flow_raw, float* dst, int B, int H, int W, const float* frag,
                               int inv_e, const float* bias, hipStream_t s, int64_t flow_bstride = 0);
 // generic NCHW warp with a full-resolution flow (util.flow_utils.warp).
-hipError_t launch_remosaick4(const float* rgb4, float* raw, int B, int H, int W, hipStream_t s);
+// HamiltonAdam(pattern).remosaick of an NHWC4 frame: the packed planes of the pattern (the inverse of its packing)
+hipError_t launch_remosaick4(const float* rgb4, float* raw, int B, int H, int W, hipStream_t s, int bayer);
 hipError_t launch_warp_nchw(const float* x, const float* flow, float* y, int n, int c, int H, int W,
                             hipStream_t s);
 hipError_t launch_upsample_flow(const float* t, float* out, int nc, int h, int w, float mul,

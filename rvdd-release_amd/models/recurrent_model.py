@@ -10,6 +10,7 @@ import torch
 
 from .base_model import BaseModel
 from .. import networks
+from ..runtime import BAYER_PATTERNS
 
 
 class recurrentModel(BaseModel):
@@ -22,6 +23,9 @@ class recurrentModel(BaseModel):
         parser.add_argument('--feature_rec', action='store_true', default=False)
         parser.add_argument('--prev_noisy_frame', action='store_true', default=False)
         parser.add_argument('--warp_raw', action='store_true', default=False)
+        # colour-filter layout of the raw frames (the reference's data are GBRG, recurrent_model.py:99); every demosaic and
+        # re-mosaic of a step follows it (rvdd_set_option "bayer_pattern")
+        parser.add_argument('--bayer_pattern', type=str, default='gbrg', choices=BAYER_PATTERNS)
         return parser
 
     def __init__(self, opt):
@@ -47,6 +51,9 @@ class recurrentModel(BaseModel):
             raise ValueError("--feature_rec must be given exactly with the +feat / mode=feat networks")
         self.gt_nc = opt.input_nc
         self.data_nc = 4
+        self.bayer_pattern = getattr(opt, 'bayer_pattern', 'gbrg')
+        if self.bayer_pattern not in BAYER_PATTERNS:
+            raise ValueError(f"--bayer_pattern {self.bayer_pattern!r}: one of {', '.join(BAYER_PATTERNS)}")
         self._rt = None
 
     def to_device(self, x):
@@ -82,6 +89,7 @@ class recurrentModel(BaseModel):
             rt.set_option("no_warp", int(no_warp))
             rt.set_option("prev_noisy_frame", int(bool(self.opt.prev_noisy_frame)))
             rt.set_option("warp_raw", int(bool(self.opt.warp_raw)))
+            rt.set_option("bayer_pattern", BAYER_PATTERNS.index(self.bayer_pattern))
             rt.reset()
         if self.training_unrollings == 1:
             rt.reset()

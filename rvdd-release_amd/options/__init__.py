@@ -9,6 +9,8 @@ can be driven exactly like validate.py:117-138 does.
 """
 from argparse import Namespace
 
+from ..runtime import BAYER_PATTERNS
+
 
 def make_opt(**overrides) -> Namespace:
     opt = Namespace(
@@ -19,6 +21,7 @@ def make_opt(**overrides) -> Namespace:
         future_patch_depth=0, epoch='latest_val', verbose=False, suffix='', no_predemosaic=False,
         raw_gt=False, val_flow_from_denoised=False, model_patch_depth=2, feature_rec=False,
         prev_noisy_frame=False, warp_raw=False, path2epoch='', lambda_L1=100.0, lr=0.00016,
+        bayer_pattern='gbrg',                # colour-filter layout of the raw frames (recurrentModel --bayer_pattern)
         isTrain=True,                        # validate.py parses TrainOptions (isTrain=True at parse time)
         # dataset side (base_options.py:36-52, train_options.py:34-36, data/infer4rec_dataset.py:34-38)
         dataroot='./datasets/train_dataset', nFolder='noisy', gtFolder='gt', gt_linear_RGB_Folder='gt_linear_RGB',
@@ -54,6 +57,8 @@ def parse(argv=None) -> Namespace:
             continue
         if k == 'gpu_ids':
             parser.add_argument('--gpu_ids', type=str, default='0')
+        elif k == 'bayer_pattern':
+            parser.add_argument('--bayer_pattern', type=str, default=v, choices=BAYER_PATTERNS)
         elif isinstance(v, bool):
             parser.add_argument('--' + k, action='store_true', default=v)
         elif v is None:

@@ -20,6 +20,9 @@ ARCH_BY_NAME = {
     "next+feat": _lib.ARCH_CONVNEXT_FEAT,
 }
 
+# enum rvdd_bayer, in order: the index of a pattern is its value (rvdd_set_option "bayer_pattern", rvdd_demosaic_ha_bayer)
+BAYER_PATTERNS = ("gbrg", "grbg", "rggb", "bggr")
+
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
@@ -214,14 +217,17 @@ class RvddRuntime:
                                                self._stream()), "rvdd_unet_forward")
         return out, fo
 
-    def demosaic(self, raw: torch.Tensor) -> torch.Tensor:
+    def demosaic(self, raw: torch.Tensor, pattern: str = "gbrg") -> torch.Tensor:
+        """HamiltonAdam(pattern)(raw): [n,4k,h,w] packed raw -> [n,3k,2h,2w] (pattern: one of BAYER_PATTERNS)."""
+        if pattern not in BAYER_PATTERNS:
+            raise ValueError(f"demosaic: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
         n, c, h, w = raw.shape
         raw = _chk_dev(raw, raw.shape, "raw", self.device)
         assert c % 4 == 0
         k = n * (c // 4)
         out = torch.empty(n, 3 * (c // 4), 2 * h, 2 * w, dtype=torch.float32, device=raw.device)
-        self._check(self.lib.rvdd_demosaic_ha(self.h, _ptr(raw), k, h, w, _ptr(out), self._stream()),
-                    "rvdd_demosaic_ha")
+        self._check(self.lib.rvdd_demosaic_ha_bayer(self.h, _ptr(raw), k, h, w, BAYER_PATTERNS.index(pattern), _ptr(out),
+                                                    self._stream()), "rvdd_demosaic_ha_bayer")
         return out
 
     def warp(self, x: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:

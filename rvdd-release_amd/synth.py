@@ -3,7 +3,8 @@
 Follows the recipe of SURVEY.md section 8d: a smooth multi-frequency colour
 texture in linear RGB, translated by a known sub-pixel velocity per sequence
 (so the optical flow is analytic instead of TV-L1), mapped to the 12-bit DN
-range of the reference's data synthesis, GBRG-mosaicked, corrupted by the
+range of the reference's data synthesis, GBRG-mosaicked (or in another Bayer
+pattern on request), corrupted by the
 reference's heteroscedastic Gaussian noise model and normalised the way the
 reference's loader does.
 
@@ -32,10 +33,14 @@ ISO_PARAMS = {
 
 CAM_GAINS = (0.5, 1.0, 0.6)   # approx. 1/red_gain, 1, 1/blue_gain
 
+# Bayer patterns: the colour of CFA position (r, c) under a pattern is the GBRG colour of (r ^ py, c ^ px)
+_PHASE = {"gbrg": (0, 0), "grbg": (1, 1), "rggb": (1, 0), "bggr": (0, 1)}
+_GBRG_COLOUR = (1, 2, 0, 1)   # RGB channel of the GBRG sites G(e,e), B(e,o), R(o,e), G(o,o)
+
 
 @dataclass
 class SynthSequence:
-    raw: torch.Tensor        # [T,4,h,w]  packed noisy GBRG raw in [-1,1]
+    raw: torch.Tensor        # [T,4,h,w]  packed noisy raw (GBRG unless asked otherwise) in [-1,1]
     flow_prev: torch.Tensor  # [T,2,h,w]  raw-res flow t -> t-1 (entry 0 unused)
     flow_next: torch.Tensor  # [T,2,h,w]  raw-res flow t -> t+1 (last entry unused)
     gt: torch.Tensor         # [T,3,H,W]  clean linear RGB in [-1,1]
@@ -68,9 +73,12 @@ def _texture(xs: torch.Tensor, ys: torch.Tensor, gen: torch.Generator, nfreq: in
 
 
 def make_sequence(T: int, H: int, W: int, iso: int = 3200, seed: int = 0,
-                  device: str = "cpu", max_speed: float = 3.0) -> SynthSequence:
-    """One synthetic sequence of T frames at RGB size HxW (both even)."""
+                  device: str = "cpu", max_speed: float = 3.0, pattern: str = "gbrg") -> SynthSequence:
+    """One synthetic sequence of T frames at RGB size HxW (both even), mosaicked in Bayer `pattern` (gbrg, grbg, rggb,
+    bggr): raw channel k holds CFA position (k >> 1, k & 1) of each 2x2 cell, in the colour the pattern has there."""
     assert H % 2 == 0 and W % 2 == 0
+    if pattern not in _PHASE:
+        raise ValueError(f"make_sequence: pattern {pattern!r} is not one of {', '.join(_PHASE)}")
     P = ISO_PARAMS[iso]
     gen = torch.Generator(device="cpu").manual_seed(int(seed))
     dev = torch.device(device)
@@ -89,12 +97,10 @@ def make_sequence(T: int, H: int, W: int, iso: int = 3200, seed: int = 0,
     clean = torch.stack(frames, 0)                      # [T,3,H,W] in [0,1]
     dn = P["lo"] + clean * (P["hi"] - P["lo"])          # 12-bit DN
 
-    # GBRG mosaic of the clean DN image, then noise
-    g0 = dn[:, 1, 0::2, 0::2]
-    b = dn[:, 2, 0::2, 1::2]
-    r = dn[:, 0, 1::2, 0::2]
-    g1 = dn[:, 1, 1::2, 1::2]
-    u = torch.stack((g0, b, r, g1), 1)                  # [T,4,h,w]
+    # mosaic of the clean DN image in the pattern (GBRG: G, B, R, G), then noise
+    oy, ox = _PHASE[pattern]
+    u = torch.stack([dn[:, _GBRG_COLOUR[(((k >> 1) ^ oy) << 1) | ((k & 1) ^ ox)], (k >> 1)::2, (k & 1)::2]
+                     for k in range(4)], 1)             # [T,4,h,w]
     ngen = torch.Generator(device="cpu").manual_seed(int(seed) * 7919 + 13)
     z = torch.randn(u.shape, generator=ngen).to(dev)
     noisy = u + torch.sqrt(torch.clamp(P["a"] * u - P["b"], min=0.0)) * z

@@ -27,6 +27,12 @@ from .util._ops import ops_runtime
 from .util.Hamilton_Adam_demo import HamiltonAdam
 
 
+def _pattern_of(model) -> str:
+    """The Bayer pattern of the model's raw frames (--bayer_pattern): the re-mosaic of the previous output follows it, so
+    that it lines up with the noisy frame it is matched against."""
+    return getattr(model, "bayer_pattern", "gbrg")
+
+
 def compute_flows_from_denoised(data: dict, model, opt) -> None:
     """Replace the flow towards the previous frame in data['flow'] by the TV-L1 flow from the current noisy frame
     to the re-mosaicked previous OUTPUT.
@@ -40,7 +46,7 @@ def compute_flows_from_denoised(data: dict, model, opt) -> None:
     towards the next frame -- which no output exists for yet -- stays the dataset's pre-computed one."""
     dev = model.device
     noisy_cur = data['n'][0, 4:8, :, :].to(dev, torch.float32)                       # packed raw, [-1,1]
-    prev_out = HamiltonAdam('gbrg').remosaick(model.denoised.to(dev))[0]
+    prev_out = HamiltonAdam(_pattern_of(model)).remosaick(model.denoised.to(dev))[0]
     # the reference hands (x+1)/2 images to CPPbridge, which reduces 4 channels to their mean (library.py:67-68, :165-167)
     target = ((noisy_cur + 1.0) / 2.0).mean(dim=0).contiguous()
     moving = ((prev_out + 1.0) / 2.0).mean(dim=0).contiguous()
@@ -129,7 +135,7 @@ def _flows_from_denoised_packed(data: dict, model, opt, rt) -> None:
     if not sel:
         return
     dev = model.device
-    ha = HamiltonAdam('gbrg')
+    ha = HamiltonAdam(_pattern_of(model))
     targets, movings = [], []
     for b in sel:
         noisy_cur = data['n'][b, 4:8, :, :].to(dev, torch.float32)
