@@ -128,6 +128,48 @@ int rvdd_step_strided(rvdd_t* h, const float* raw_prev, const float* raw_cur, co
                       const float* flow_prev, const float* flow_next, int64_t raw_batch_stride,
                       int64_t flow_batch_stride, float* out_rgb, void* stream);
 
+/* rvdd_step_strided for slots [0, n_live) alone, 1 <= n_live <= cfg.batch: the
+ * tensors hold n_live sequences (out_rgb is [n_live,3,H,W]; the strides mean
+ * what they mean for rvdd_step_strided) and every launch of the step -- the
+ * first-frame latch, the stages in front of the net, both nets, the
+ * --prev_noisy_frame hand-over, the launches of a partial reset -- covers
+ * n_live sequences.  Choices that depend on a launch's size (which conv kernel
+ * "conv_kernel" 4 picks, the one-kernel pre-stage, the output-channel split,
+ * "seq_major") are made for n_live, as a handle of that batch makes them.
+ * n_live == cfg.batch is rvdd_step_strided: the same launches, the same bits.
+ * Every output frame of a live slot is bit for bit what a handle of batch 1
+ * gives for that video (the contract of rvdd_reset_slots, extended).
+ *
+ * Reset marks (rvdd_reset, rvdd_reset_slots) of the live slots are consumed;
+ * a mark of a slot >= n_live stays pending.
+ *
+ * UNDEFINED SLOTS.  A step of n_live < cfg.batch leaves the recurrent state
+ * of slots >= n_live undefined: the block-floating-point words rotate through
+ * their sets with every step of the handle, so a sequence that sat a step out
+ * cannot carry on.  The handle remembers these slots.  A later step that
+ * covers one of them without a pending reset mark for it fails with
+ * RVDD_ERR_STATE (the message names the slot) and changes nothing; rvdd_reset,
+ * a mark of rvdd_reset_slots, rvdd_set_state (with lastden) or being the
+ * destination of rvdd_move_slots makes a slot defined again.  Needs batch <= 64
+ * when n_live < cfg.batch.  With option "graphs" on, a step of fewer slots
+ * runs launch by launch (never replayed from a captured graph). */
+int rvdd_step_live(rvdd_t* h, int32_t n_live, const float* raw_prev, const float* raw_cur, const float* raw_next,
+                   const float* flow_prev, const float* flow_next, int64_t raw_batch_stride,
+                   int64_t flow_batch_stride, float* out_rgb, void* stream);
+
+/* The whole per-sequence state of slot from[k] replaces that of slot to[k],
+ * k < count (`from`, `to`: HOST arrays of slot indices): the previous output,
+ * the recurrent features, the sequence's block-floating-point words in every
+ * set, and the host-side marks (pending reset, undefined).  Slot from[k] is
+ * undefined afterwards (see rvdd_step_live) and carries no reset mark.  One
+ * kernel launch for all pairs, ordered in `stream`; 208 bytes per pixel read
+ * and written per pair.  The pairs must be disjoint -- no slot twice across
+ * `from` and `to` -- and inside 0..cfg.batch-1: RVDD_ERR_ARG otherwise, and
+ * nothing is moved.  count == 0 does nothing.  Needs batch <= 64.  Together
+ * with rvdd_step_live this keeps the live sequences of a pack of videos in
+ * the first slots once no video is left to refill a finished one. */
+int rvdd_move_slots(rvdd_t* h, const int32_t* from, const int32_t* to, int32_t count, void* stream);
+
 /* Recurrent state in the reference's layout, for get_current_features /
  * set_rec_features parity (networks/unet.py:814-818) and for tests.
  *   lastden  [B,3,H,W]; lastfeat [B,48,H,W] (NULL to skip either). */

@@ -33,6 +33,8 @@ _PROTOS = {
     "rvdd_reset_slots": (C.c_int, [_P, _P]),
     "rvdd_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "rvdd_step_strided": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    "rvdd_step_live": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    "rvdd_move_slots": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _P]),
     "rvdd_get_state": (C.c_int, [_P, _P, _P, _P]),
     "rvdd_set_state": (C.c_int, [_P, _P, _P, _P]),
     "rvdd_psnr_l1": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_float), _P]),

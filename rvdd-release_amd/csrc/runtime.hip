@@ -137,6 +137,9 @@ struct rvdd_handle {
     bool need_init = true;        // every sequence starts a video on the next step (create, rvdd_reset)
     uint64_t pend_mask = 0;       // rvdd_reset_slots: the sequences that start a video on the next step (B <= 64; never all of them:
                                   // a full mask is need_init, so that the all-slots step issues the launches it always has)
+    uint64_t undef_mask = 0;      // rvdd_step_live / rvdd_move_slots: the sequences whose recurrent state is undefined (they sat a step out, or
+                                  // were moved away); a step may cover one only together with a reset mark for it
+    int nrun = 0;                 // the sequences the running step launches over: cfg.batch, or n_live inside rvdd_step_live
     bool force_wino = false;      // Winograd at every size (RVDD_CONV=winograd / rvdd_set_option "conv_kernel" 2): tests + measurement
     bool warp_raw = false;        // --warp_raw (rvdd_set_option): warp the re-mosaicked frames at raw resolution, demosaic afterwards
     bool prev_noisy = false;      // --prev_noisy_frame (rvdd_set_option): the next step's "previous frame" is the demosaiced noisy one
@@ -619,7 +622,7 @@ struct ConvCall {
 };
 
 bool wino_applies(const rvdd_t* h, int H, int W) {
-    return h->use_wino && (h->force_wino || h->cfg.batch * ((W + 31) / 32) * ((H + 7) / 8) >= 200);
+    return h->use_wino && (h->force_wino || h->nrun * ((W + 31) / 32) * ((H + 7) / 8) >= 200);
 }
 
 // Sequences [b0, b0 + nb) of the batch: the maps of a ConvCall are those of the WHOLE batch, a launch may cover a part.
@@ -634,10 +637,10 @@ struct Sub {
 // more to their tails (3600 units on 256 CUs = 14.06 rounds) and to four filter-bank loads per layer than the cache
 // gives back.  Kept because it is free and pins an invariant the tests use: a launch's batch size does not enter a
 // tile's sums, so both schedules give bit-identical frames.
-bool seq_major_on(const rvdd_t* h) { return h->cfg.batch > 1 && h->seq_major == 1; }
+bool seq_major_on(const rvdd_t* h) { return h->nrun > 1 && h->seq_major == 1; }
 
 int run_conv(rvdd_t* h, const Conv3& L, const ConvCall& c, hipStream_t s, Sub sub = Sub{0, -1}) {
-    if (sub.nb < 0) sub.nb = h->cfg.batch;
+    if (sub.nb < 0) sub.nb = h->nrun;
     const int cin_in = L.cin_pad[c.src];
     const int Ho = c.epi == EPI_POOL ? c.H / 2 : (c.Hout ? c.Hout : c.H), Wo = c.epi == EPI_POOL ? c.W / 2 : (c.Wout ? c.Wout : c.W);
     const size_t px_in = (size_t)sub.b0 * c.H * c.W, px_out = (size_t)sub.b0 * Ho * Wo;
@@ -707,7 +710,7 @@ int run_conv(rvdd_t* h, const Conv3& L, const ConvCall& c, hipStream_t s, Sub su
 
 // The composed 5x5 conv of the network input (compose_pre_enc0) into `part`, and its border fix; sequences of `sub`.
 int run_pre5(rvdd_t* h, const float* netin, float* part, hipStream_t s, Sub sub) {
-    if (sub.nb < 0) sub.nb = h->cfg.batch;
+    if (sub.nb < 0) sub.nb = h->nrun;
     const int H = h->cfg.height, W = h->cfg.width;
     const size_t px0 = (size_t)sub.b0 * H * W;
     ConvArgs a{};
@@ -746,7 +749,7 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s);
 int run_convunet(rvdd_t* h, const float* netin, const float* featw, float* feat_dst, float* out_nchw,
                  float* out_nhwc4, hipStream_t s, const StepInputs* prologue) {
     const bool feat = h->has_feat();
-    const int B = h->cfg.batch;
+    const int B = h->nrun;
     Level* lv = h->lv;
     const Conv3* cu = h->cu;
     // `from` = the amax slot of the input map (L(the layer that wrote it), AMAX_NETIN, h->amax_feat_in); a layer's output slot is L(its id)
@@ -899,7 +902,7 @@ int run_net(rvdd_t* h, const float* netin, const float* featw, float* feat_dst, 
     if (!h->is_next()) {
         return run_convunet(h, netin, featw, feat_dst, out_nchw, out_nhwc4, s, prologue);
     }
-    const int B = h->cfg.batch;
+    const int B = h->nrun;
     h->featw_proj = false;          // a caller's own features (rvdd_unet_forward) come as they are
     h->netin_proj = false;          // and so does a caller's own network input
     if (prologue) RC(run_prologue(h, *prologue, Sub{0, B}, s));
@@ -953,6 +956,7 @@ int rvdd_create(const rvdd_cfg* cfg, rvdd_t** out) {
 
     rvdd_t* h = new rvdd_handle();
     h->cfg = *cfg;
+    h->nrun = cfg->batch;
     if (const char* sm = std::getenv("RVDD_SEQ_MAJOR")) h->seq_major = std::atoi(sm) != 0;     // measurement switches
     if (const char* fu = std::getenv("RVDD_FUSE_UPSAMPLE")) h->fuse_upsample = std::atoi(fu) != 0;
     if (const char* bf = std::getenv("RVDD_BFP")) h->bfp = std::atoi(bf) != 0;
@@ -1423,7 +1427,7 @@ prologue_features:
 int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const float* raw_next, const float* flow_prev,
                  const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, bool init, uint64_t pend, hipStream_t s) {
     const bool nw = h->no_warp;
-    const int B = h->cfg.batch, H = h->cfg.height, W = h->cfg.width;
+    const int B = h->nrun, H = h->cfg.height, W = h->cfg.width;      // B: the sequences this step covers (rvdd_step_live: the live ones)
     const size_t npix = (size_t)B * H * W;
     if (init) pend = 0;
     StepInputs in;
@@ -1438,7 +1442,7 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
     h->amax_post_out = AMAX_FEAT0 + h->step_ctr % 3;
     if (h->bfp && h->split16 && !h->is_next()) {
         // the first step of a video starts from zero features: zero words; later steps find their set zeroed by the step before
-        if (init) HIPCHK(h, hipMemsetAsync(h->amax, 0, amax_bytes(B, AMAX_SLOTS), s));
+        if (init) HIPCHK(h, hipMemsetAsync(h->amax, 0, amax_bytes(h->cfg.batch, AMAX_SLOTS), s));
         h->amax_zero_pending = true;
     }
     if (init) {
@@ -1462,7 +1466,7 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
         }
         const bool words = h->bfp && h->split16 && !h->is_next();
         HIPCHK(h, launch_latch_zero(pend, h->has_feat() ? h->lastfeat : nullptr, (int64_t)img * kF, words ? h->amax : nullptr, AMAX_SLOTS,
-                                    B, s));
+                                    h->cfg.batch, s));
     }
     // without warping the previous features are read in place: the net consumes them in its first layer and only
     // its last one writes the new ones
@@ -1474,6 +1478,24 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
 }
 
 constexpr size_t kMaxStepGraphs = 128;      // one per distinct set of caller buffers; least recently used goes first
+
+// The reset marks as one mask of B <= 64 slots (need_init = all of them), and back: a full mask is always stored as need_init.
+uint64_t slots_below(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
+uint64_t reset_marks(const rvdd_t* h) { return h->need_init ? slots_below(h->cfg.batch) : h->pend_mask; }
+void set_reset_marks(rvdd_t* h, uint64_t m) {
+    h->need_init = m == slots_below(h->cfg.batch);
+    h->pend_mask = h->need_init ? 0 : m;
+}
+
+// nrun = n for the launches of one partial step, cfg.batch again when it is over (however it ends)
+struct LiveScope {
+    rvdd_t* h;
+    LiveScope(rvdd_t* h_, int n) : h(h_) { h->nrun = n; }
+    ~LiveScope() { h->nrun = h->cfg.batch; }
+};
+
+int step_n(rvdd_t* h, int n, const float* raw_prev, const float* raw_cur, const float* raw_next, const float* flow_prev,
+           const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, void* stream);
 
 }  // namespace
 
@@ -1496,6 +1518,62 @@ int rvdd_step_strided(rvdd_t* h, const float* raw_prev, const float* raw_cur, co
                       const float* flow_prev, const float* flow_next, int64_t raw_stride, int64_t flow_stride,
                       float* out_rgb, void* stream) {
     if (!h) return RVDD_ERR_ARG;
+    return step_n(h, h->cfg.batch, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, stream);
+}
+
+// Slots [0, n_live) alone: the launches of a step of n_live sequences over the first n_live slices of the handle's maps (every
+// launch of a step takes a sequence range already; the amax words keep the handle's own batch stride).  The sequences that sit
+// the step out are undefined afterwards: the sets of words rotate with step_ctr, which this step advances for the whole handle.
+int rvdd_step_live(rvdd_t* h, int32_t n_live, const float* raw_prev, const float* raw_cur, const float* raw_next,
+                   const float* flow_prev, const float* flow_next, int64_t raw_stride, int64_t flow_stride,
+                   float* out_rgb, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (n_live < 1 || n_live > h->cfg.batch)
+        return fail(h, RVDD_ERR_ARG, "rvdd_step_live: n_live must be 1..%d (the handle's batch), got %d", h->cfg.batch, n_live);
+    if (n_live < h->cfg.batch && h->cfg.batch > 64)
+        return fail(h, RVDD_ERR_ARG, "rvdd_step_live: a step of some slots needs batch <= 64 (batch is %d)", h->cfg.batch);
+    return step_n(h, n_live, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, stream);
+}
+
+int rvdd_move_slots(rvdd_t* h, const int32_t* from, const int32_t* to, int32_t count, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (count == 0) return RVDD_OK;
+    if (count < 0 || !from || !to) return fail(h, RVDD_ERR_ARG, "rvdd_move_slots: bad argument");
+    const int B = h->cfg.batch, H = h->cfg.height, W = h->cfg.width;
+    if (B > 64) return fail(h, RVDD_ERR_ARG, "rvdd_move_slots: needs batch <= 64 (batch is %d)", B);
+    uint64_t seen = 0;
+    for (int k = 0; k < count; ++k)
+        for (const int b : {from[k], to[k]}) {
+            if (b < 0 || b >= B) return fail(h, RVDD_ERR_ARG, "rvdd_move_slots: slot %d outside 0..%d", b, B - 1);
+            if ((seen >> b) & 1ull)
+                return fail(h, RVDD_ERR_ARG, "rvdd_move_slots: slot %d appears twice (the pairs of a call must be disjoint)", b);
+            seen |= 1ull << b;
+        }
+    // (disjoint slots below 64: count <= 32 = kMaxMovePairs)
+    ENTER(h);
+    const size_t img = (size_t)H * W;
+    const bool words = h->bfp && h->split16 && !h->is_next();
+    HIPCHK(h, launch_move_slots(from, to, count, h->lastden4, (int64_t)img * 4, h->has_feat() ? h->lastfeat : nullptr, (int64_t)img * kF,
+                                words ? h->amax : nullptr, AMAX_SLOTS, B, static_cast<hipStream_t>(stream)));
+    // the host-side marks travel with the state; the source is undefined from here on (and has no mark of its own any more)
+    uint64_t marks = reset_marks(h), undef = h->undef_mask;
+    for (int k = 0; k < count; ++k) {
+        const uint64_t f = 1ull << from[k], t = 1ull << to[k];
+        marks = (marks & ~(f | t)) | ((marks & f) ? t : 0);
+        undef = (undef & ~t) | ((undef & f) ? t : 0) | f;
+    }
+    set_reset_marks(h, marks);
+    h->undef_mask = undef;
+    return RVDD_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// rvdd_step_strided (n = cfg.batch) and rvdd_step_live
+int step_n(rvdd_t* h, const int n, const float* raw_prev, const float* raw_cur, const float* raw_next, const float* flow_prev,
+           const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, void* stream) {
     ENTER(h);
     if (!h->finalized) return fail(h, RVDD_ERR_STATE, "rvdd_step: weights not finalized");
     {
@@ -1506,24 +1584,42 @@ int rvdd_step_strided(rvdd_t* h, const float* raw_prev, const float* raw_cur, co
     }
     const bool nw = h->no_warp;
     if (!raw_cur || (!flow_prev && !nw) || !out_rgb) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_cur, flow_prev and out_rgb are required");
-    if ((h->need_init || h->pend_mask) && !raw_prev) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_prev is required on the first step of a video");
     if (h->cfg.future && (!raw_next || (!flow_next && !nw))) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_next and flow_next are required when future=1");
     if (nw) flow_prev = flow_next = nullptr;      // the flows are not looked at (the reference's dataset does not even load them)
     hipStream_t s = static_cast<hipStream_t>(stream);
     // need_init is cleared only once the step has been enqueued: a step that failed half way leaves the handle asking
     // for the first frame of a video again (raw_prev, zeroed features), never a later frame on stale state
-    const bool init = h->need_init;
-    const uint64_t pend = init ? 0 : h->pend_mask;
+    const int B = h->cfg.batch;
+    const bool part = n < B;                       // (B <= 64 then: rvdd_step_live)
+    bool init = h->need_init;
+    uint64_t pend = init ? 0 : h->pend_mask, keep = 0;
+    if (part) {
+        // the marks of the live slots are this step's; those of the others stay pending.  Every live slot marked = the first
+        // step of a handle of n sequences, launch for launch.
+        const uint64_t marks = reset_marks(h), live = slots_below(n);
+        keep = marks & ~live;
+        init = (marks & live) == live;
+        pend = init ? 0 : marks & live;
+    }
+    if (h->undef_mask) {
+        const uint64_t covered = slots_below(part ? n : (B < 64 ? B : 64));
+        if (const uint64_t bad = h->undef_mask & covered & ~(init ? covered : pend))
+            return fail(h, RVDD_ERR_STATE, "rvdd_step: the state of slot %d is undefined (it sat out a step of fewer slots, or was moved "
+                        "away): mark it with rvdd_reset_slots, set its state, or move a sequence into it first", __builtin_ctzll(bad));
+    }
+    if ((init || pend) && !raw_prev) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_prev is required on the first step of a video");
     auto eager = [&]() -> int {
+        LiveScope live(h, n);
         const int rc = enqueue_step(h, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, pend, s);
         if (rc == RVDD_OK) {
             h->need_init = false;
-            h->pend_mask = 0;
+            h->pend_mask = keep;
+            h->undef_mask = part ? (h->undef_mask & ~slots_below(n)) | (slots_below(B) & ~slots_below(n)) : 0;
             h->step_ctr = (h->step_ctr + 1) % 6;      // (the amax words' set and slots follow it: & 1, % 3)
         }
         return rc;
     };
-    if (!h->use_graphs || h->prof_on || !h->ran_eagerly || !h->gstream || pend) {      // a partial reset is never captured
+    if (!h->use_graphs || h->prof_on || !h->ran_eagerly || !h->gstream || pend || part) {      // a partial reset and a step of some slots are never captured
         h->ran_eagerly = true;
         return eager();
     }
@@ -1571,10 +1667,15 @@ int rvdd_step_strided(rvdd_t* h, const float* raw_prev, const float* raw_cur, co
     HIPCHK(h, hipStreamWaitEvent(s, h->g_out, 0));
     h->need_init = false;
     h->pend_mask = 0;
+    h->undef_mask = 0;
     h->step_ctr = (h->step_ctr + 1) % 6;
     if (seq_major_on(h)) h->serpentine = !h->serpentine;
     return RVDD_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int rvdd_get_state(rvdd_t* h, float* lastden, float* lastfeat, void* stream) {
     if (!h) return RVDD_ERR_ARG;
@@ -1599,6 +1700,7 @@ int rvdd_set_state(rvdd_t* h, const float* lastden, const float* lastfeat, void*
         HIPCHK(h, launch_nchw_to_nhwc(lastden, h->lastden4, B, 3, H, W, 4, s));
         h->need_init = false;
         h->pend_mask = 0;
+        h->undef_mask = 0;
     }
     if (lastfeat) HIPCHK(h, launch_nchw_to_nhwc(lastfeat, h->lastfeat, B, kF, H, W, kF, s));
     if ((lastden || lastfeat) && h->bfp && h->split16 && !h->is_next()) {

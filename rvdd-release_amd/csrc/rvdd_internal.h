@@ -280,6 +280,13 @@ hipError_t launch_loss_reduce_batch(const float* a, const float* b, int nslices,
 // rvdd_reset_slots' latch: zero the features (feat_per_seq floats per sequence) and the amax words of every set (nsets, layout
 // [nsets][B][kAmaxSeqWords]) of the sequences in `mask` (B <= 64); either pointer nullable
 hipError_t launch_latch_zero(unsigned long long mask, float* feat, int64_t feat_per_seq, unsigned* words, int nsets, int B, hipStream_t s);
+// rvdd_move_slots: the recurrent state of sequence from[k] replaces that of sequence to[k], k < count <= kMaxMovePairs, in ONE
+// launch: the previous output (den, NHWC4), the features (feat, feat_per_seq floats per sequence, nullable) and the amax words
+// of every set (nullable, layout as above).  The pairs travel as kernel arguments, one byte per slot (B <= 64); they must be
+// disjoint (no slot twice across from and to): the caller checks that, it is what makes one launch race-free
+constexpr int kMaxMovePairs = 32;
+hipError_t launch_move_slots(const int* from, const int* to, int count, float* den, int64_t den_per_seq, float* feat, int64_t feat_per_seq,
+                             unsigned* words, int nsets, int B, hipStream_t s);
 
 // -------------------------------------------------------------- ConvNeXt ---
 struct NextBlockW {          // device pointers, one ConvBlock (networks/new_unet.py:74-103)

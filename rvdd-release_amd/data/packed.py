@@ -16,6 +16,12 @@ outputs do not depend on its slot or on what the other slots hold, so every fram
 
 Each step yields {'n', 'gt', 'flow': [B, ...], 'n_path', 'gt_path': B-lists, 'FirstOfVideo', 'live': [B] bool tensors,
 'index': B-list of dataset indices}.
+
+`compact=True` removes the tail: a step holds only live sequences, always in slots 0 .. n-1 (n <= B), and the runtime steps
+those alone (`RvddRuntime.step(live=n)`).  While videos are left, a finished slot is refilled as above; once none is left,
+the hole is filled by MOVING the highest live slot into it (`RvddRuntime.move_slots`), so the live slots stay a prefix.
+Each step then yields the keys above with leading dimension n ('live' all true), and 'slots': B, 'moves': [(from, to)] to
+apply before the step, 'prev_index': for every sequence its index in the previous step's batch (-1 on a first frame).
 """
 from __future__ import annotations
 
@@ -51,13 +57,65 @@ def split_videos(dataset, count: int) -> List[List[int]]:
     return videos
 
 
-def plan_packs(videos: List[List[int]], sizes: List[Tuple[int, ...]], batch: int) -> List[List[List[Tuple[int, bool, bool]]]]:
-    """-> packs, each a list of steps, each step B entries (sample index, FirstOfVideo, live).  Pure bookkeeping."""
+class CompactStep(list):
+    """A step of a compact plan: n <= B entries (sample index, FirstOfVideo, True) for slots 0 .. n-1, plus `moves`
+    [(from slot, to slot)] to apply before it and `prev_index` (each entry's index in the previous step, -1 = first frame)."""
+
+    def __init__(self, entries, moves, prev_index):
+        super().__init__(entries)
+        self.moves = list(moves)
+        self.prev_index = list(prev_index)
+
+
+def _plan_compact(vids: List[List[int]], batch: int) -> List[CompactStep]:
+    queue = list(vids)
+    cur: List[List[int]] = []            # remaining samples of the video in each used slot; the live ones are a prefix
+    steps = []
+    while True:
+        prev = list(range(len(cur)))     # where each slot's sequence sat in the last step
+        for b in range(batch):
+            if b < len(cur) and cur[b]:
+                continue
+            if not queue:
+                continue
+            if b == len(cur):
+                cur.append([])
+                prev.append(-1)
+            elif b > len(cur):
+                break
+            cur[b] = list(queue.pop(0))  # a video that has not started: assigned to the hole, no move
+            prev[b] = -1
+        # no video left for the remaining holes: the highest live slot moves into the lowest hole (two pointers)
+        moves = []
+        lo, hi = 0, len(cur) - 1
+        while True:
+            while lo < len(cur) and cur[lo]:
+                lo += 1
+            while hi >= 0 and not cur[hi]:
+                hi -= 1
+            if lo >= hi:
+                break
+            moves.append((hi, lo))
+            cur[lo], cur[hi] = cur[hi], []
+            prev[lo] = prev[hi]
+        n = hi + 1
+        del cur[n:], prev[n:]
+        if n == 0:
+            break
+        steps.append(CompactStep([(cur[b].pop(0), prev[b] < 0, True) for b in range(n)], moves, prev))
+    return steps
+
+
+def plan_packs(videos: List[List[int]], sizes: List[Tuple[int, ...]], batch: int, compact: bool = False):
+    """-> packs, each a list of steps, each step B entries (sample index, FirstOfVideo, live).  Pure bookkeeping.
+    `compact`: each step a `CompactStep` of its live entries only (see the module's text)."""
     if batch < 1:
         raise ValueError("batch must be >= 1")
     groups: Dict[Tuple[int, ...], List[List[int]]] = {}
     for v, s in zip(videos, sizes):
         groups.setdefault(s, []).append(v)
+    if compact:
+        return [_plan_compact(vids, batch) for vids in groups.values()]
     packs = []
     for vids in groups.values():
         queue = list(vids)
@@ -101,14 +159,15 @@ def _stack(values):
 class PackedLoader:
     """Batched steps over videos packed into `batch` slots; `loader` = the serial loader (`create_dataset(opt)`)."""
 
-    def __init__(self, loader, batch: int):
+    def __init__(self, loader, batch: int, compact: bool = False):
         self.loader = loader
         self.dataset = loader.dataset
         self.batch = int(batch)
+        self.compact = bool(compact)
         count = len(loader)
         videos = split_videos(self.dataset, count)
         sizes = [frame_size(self.dataset, v[0]) for v in videos]
-        self.packs = plan_packs(videos, sizes, self.batch)
+        self.packs = plan_packs(videos, sizes, self.batch, compact=self.compact)
         self.samples = count
 
     def __len__(self):
@@ -121,7 +180,27 @@ class PackedLoader:
         """Slot-steps whose output is discarded."""
         return sum(not live for p in self.packs for row in p for _, _, live in row)
 
+    def moves(self) -> int:
+        """Slot moves of a compact plan (0 otherwise)."""
+        return sum(len(getattr(row, 'moves', ())) for p in self.packs for row in p)
+
+    def _iter_compact(self):
+        for steps in self.packs:
+            for row in steps:
+                samples = [self.dataset[i] for i, _, _ in row]      # every entry is a new frame: nothing to hold
+                out = {k: _stack([s[k] for s in samples]) for k in samples[0]}
+                out['FirstOfVideo'] = torch.tensor([first for _, first, _ in row], dtype=torch.bool)
+                out['live'] = torch.ones(len(row), dtype=torch.bool)
+                out['index'] = [i for i, _, _ in row]
+                out['slots'] = self.batch
+                out['moves'] = list(row.moves)
+                out['prev_index'] = list(row.prev_index)
+                yield out
+
     def __iter__(self):
+        if self.compact:
+            yield from self._iter_compact()
+            return
         for steps in self.packs:
             held: Dict[int, dict] = {}           # slot -> its last sample (a repeat costs no load)
             for row in steps:

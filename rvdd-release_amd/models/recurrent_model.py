@@ -72,6 +72,10 @@ class recurrentModel(BaseModel):
         self.first_frame = [bool(v) for v in (first.tolist() if hasattr(first, "tolist") else first)] if self.per_slot else first
         # --no_warp: the dataset yields no flows and the reference never reads them (recurrent_model.py:117-122)
         self.flow = None if self.opt.no_warp else self.to_device(input['flow'])
+        # compact packing (data/packed.py, compact=True): the tensors carry the live sequences only, in slots 0 .. n-1 of a
+        # runtime of 'slots' sequences; 'moves' = the (from, to) slot moves that bring them there, applied before the step
+        self.slots = int(input['slots']) if 'slots' in input else None
+        self.moves = [(int(f), int(t)) for f, t in input.get('moves', ())]
 
     def forward(self):
         if self.isTrain:
@@ -83,7 +87,10 @@ class recurrentModel(BaseModel):
         if C != 4 * (2 + fD) or (not no_warp and self.flow.shape[1] != 1 + fD):
             raise RuntimeError(f"input 'n' has {C} channels / 'flow' {None if no_warp else tuple(self.flow.shape)}; "
                                f"expected {4 * (2 + fD)} raw channels and {1 + fD} flows")
-        rt = self._netDenoise.runtime_for(B, 2 * h, 2 * w, pin=True)
+        slots = self.slots if self.slots is not None else B
+        if B > slots:
+            raise RuntimeError(f"input carries {B} sequences for a runtime of {slots} slots")
+        rt = self._netDenoise.runtime_for(slots, 2 * h, 2 * w, pin=True)
         if rt is not self._rt:
             self._rt = rt
             rt.set_option("no_warp", int(no_warp))
@@ -91,18 +98,21 @@ class recurrentModel(BaseModel):
             rt.set_option("warp_raw", int(bool(self.opt.warp_raw)))
             rt.set_option("bayer_pattern", BAYER_PATTERNS.index(self.bayer_pattern))
             rt.reset()
+        if self.moves:
+            rt.move_slots(self.moves)
         if self.training_unrollings == 1:
             rt.reset()
         elif self.per_slot:
             if len(self.first_frame) != B:
                 raise RuntimeError(f"FirstOfVideo has {len(self.first_frame)} entries for a batch of {B}")
             if any(self.first_frame):
-                rt.reset(slots=self.first_frame)
+                rt.reset(slots=self.first_frame if B == slots else [b for b, f in enumerate(self.first_frame) if f])
         elif self.first_frame:
             rt.reset()
         n, fl = self.n, self.flow
         self.denoised = rt.step(n[:, 0:4], n[:, 4:8], n[:, 8:12] if fD else None,
-                                None if no_warp else fl[:, 0], fl[:, 1] if (fD and not no_warp) else None)
+                                None if no_warp else fl[:, 0], fl[:, 1] if (fD and not no_warp) else None,
+                                live=None if self.slots is None else B)
 
     def compute_losses(self):
         """Test branch of recurrent_model.py:512-525."""

@@ -30,6 +30,7 @@ def make_opt(**overrides) -> Namespace:
         val_dataroot='./datasets/validation_dataset', val_dataset_mode='infer4rec', val_videos='000,001,002,003,004',
         crop_data=None, warpeddata=False,
         val_batch_size=1,                    # validation: videos packed into this many batch slots (data/packed.py); 1 = one frame per step
+        val_compact_slots=False,             # with val_batch_size > 1: step only the live slots once no video is left to refill one (no tail)
     )
     for k, v in overrides.items():
         if not hasattr(opt, k):

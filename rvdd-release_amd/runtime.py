@@ -138,8 +138,26 @@ class RvddRuntime:
         if name == "no_warp":
             self.no_warp = bool(value)
 
-    def step(self, raw_prev, raw_cur, raw_next, flow_prev, flow_next, out=None) -> torch.Tensor:
+    def move_slots(self, pairs):
+        """The whole recurrent state of slot `f` replaces that of slot `t` for every (f, t) of `pairs`, one launch
+        (rvdd_move_slots).  The pairs are disjoint; a source slot is undefined afterwards."""
+        pairs = [(int(f), int(t)) for f, t in pairs]
+        n = len(pairs)
+        if n == 0:
+            return
+        fr = (C.c_int32 * n)(*[f for f, _ in pairs])
+        to = (C.c_int32 * n)(*[t for _, t in pairs])
+        self._check(self.lib.rvdd_move_slots(self.h, fr, to, n, self._stream()), "rvdd_move_slots")
+
+    def step(self, raw_prev, raw_cur, raw_next, flow_prev, flow_next, out=None, live=None) -> torch.Tensor:
+        """One frame for every sequence.  `live=n`: slots 0 .. n-1 alone (rvdd_step_live); the tensors then hold n
+        sequences and the other slots are undefined afterwards."""
         B, H, W = self.B, self.H, self.W
+        if live is not None:
+            live = int(live)
+            if not 1 <= live <= self.B:
+                raise ValueError(f"step: live={live} outside 1..{self.B}")
+            B = live
         rs, fs = (B, 4, H // 2, W // 2), (B, 2, H // 2, W // 2)
         if getattr(self, "no_warp", False):
             flow_prev = flow_next = None
@@ -162,6 +180,11 @@ class RvddRuntime:
         else:
             _chk_dev(out, (B, 3, H, W), "out", self.device)
             assert out.is_contiguous()
+        if live is not None:
+            self._check(self.lib.rvdd_step_live(self.h, live, _ptr(raws[0][0]), _ptr(raws[1][0]), _ptr(raws[2][0]),
+                                                _ptr(flows[0][0]), _ptr(flows[1][0]), rstride, fstride, _ptr(out),
+                                                self._stream()), "rvdd_step_live")
+            return out
         self._check(self.lib.rvdd_step_strided(self.h, _ptr(raws[0][0]), _ptr(raws[1][0]), _ptr(raws[2][0]),
                                                _ptr(flows[0][0]), _ptr(flows[1][0]), rstride, fstride, _ptr(out),
                                                self._stream()), "rvdd_step")

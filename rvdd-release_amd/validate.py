@@ -7,6 +7,8 @@
   towards the previous DENOISED frame, recomputed online: remosaick -> TV-L1 on the device (`rvdd_tvl1flow`).
 * `compute_validation(..., batch_size=B)` (`--val_batch_size B`): the same frames, files, log lines and losses with the
   videos packed into B batch slots (data/packed.py) -- a slot restarts when its video ends, the others carry on.
+* `compute_validation(..., batch_size=B, compact=True)` (`--val_compact_slots`): the same again, but a step holds only the
+  live sequences, kept in the first slots by moving a sequence into a hole no video is left for (no discarded tail).
 * `init_validation_dataloader(opt)` -- validate.py:40-52; `main(argv)` -- validate.py:117-153, so that
   `python -m rvdd_release_amd.validate <the flags of scripts/test-*.sh>` reads frames and flows from disk and
   writes `<checkpoints_dir>/<name>/val_visuals/<video>/<frame>_denoised.tif` + `output.log`.
@@ -71,16 +73,18 @@ def init_validation_dataloader(opt):
 
 
 def compute_validation(model, val_dataset: Iterable[Dict], opt, on_frame: Optional[Callable] = None,
-                       val_image_dir: Optional[str] = None, batch_size: int = 1) -> dict:
+                       val_image_dir: Optional[str] = None, batch_size: int = 1, compact: bool = False) -> dict:
     """validate.py:54-114.  With `val_image_dir` (and a dataset made by `create_dataset`) every frame is written
     to <val_image_dir>/<video>/<frame>_denoised.tif and its losses appended to output.log, as the reference does;
     `on_frame(i, data, visuals, losses)` is an in-memory hook beside that.
 
     `batch_size` > 1: the videos packed into that many batch slots (`val_dataset` made by `create_dataset`, or a
     `data.packed.PackedLoader`).  Same files, same output.log lines in the same order, same returned losses; `on_frame`
-    sees each frame once (data / visuals of its own slot, batch dimension 1), in the order the frames are computed."""
+    sees each frame once (data / visuals of its own slot, batch dimension 1), in the order the frames are computed.
+
+    `compact` (with `batch_size` > 1): no slot steps on a repeated frame; see `data.packed.plan_packs`.  Same results again."""
     if batch_size > 1 or hasattr(val_dataset, "packs"):
-        return _compute_validation_packed(model, val_dataset, opt, on_frame, val_image_dir, batch_size)
+        return _compute_validation_packed(model, val_dataset, opt, on_frame, val_image_dir, batch_size, compact)
     online_flow = (not model.isTrain) and bool(getattr(opt, "val_flow_from_denoised", False)) and not opt.no_warp
     was_training = model.isTrain
     model.isTrain = False
@@ -116,6 +120,8 @@ def _slot(data: dict, b: int) -> dict:
     """Slot b of a packed step as the serial loader would have yielded it (batch dimension 1)."""
     out = {}
     for k, v in data.items():
+        if k in ('slots', 'moves', 'prev_index'):        # bookkeeping of a compact step: the serial loader has none
+            continue
         if torch.is_tensor(v) and v.dim() >= 1 and k not in ('FirstOfVideo', 'live'):
             out[k] = v[b:b + 1]
         elif isinstance(v, list) and len(v) == len(data['index']):
@@ -129,8 +135,10 @@ def _slot(data: dict, b: int) -> dict:
 def _flows_from_denoised_packed(data: dict, model, opt, rt) -> None:
     """compute_flows_from_denoised for the live slots that continue a video, with ONE rvdd_tvl1flow_batch (bit for bit
     the single calls).  The images are formed per slot exactly as the serial path forms them; the other slots keep the
-    dataset's flow, as a first frame does in serial mode."""
+    dataset's flow, as a first frame does in serial mode.  A compact step names, per sequence, its index in the previous
+    step's batch ('prev_index'): a sequence that was moved to another slot finds its previous output there."""
     live, first = data['live'].tolist(), data['FirstOfVideo'].tolist()
+    prev_index = data.get('prev_index')
     sel = [b for b in range(len(live)) if live[b] and not first[b]]
     if not sel:
         return
@@ -139,7 +147,8 @@ def _flows_from_denoised_packed(data: dict, model, opt, rt) -> None:
     targets, movings = [], []
     for b in sel:
         noisy_cur = data['n'][b, 4:8, :, :].to(dev, torch.float32)
-        prev_out = ha.remosaick(model.denoised[b:b + 1].to(dev))[0]
+        p = b if prev_index is None else int(prev_index[b])
+        prev_out = ha.remosaick(model.denoised[p:p + 1].to(dev))[0]
         targets.append(((noisy_cur + 1.0) / 2.0).mean(dim=0))
         movings.append(((prev_out + 1.0) / 2.0).mean(dim=0))
     flows = rt.tvl1flow_batch(torch.stack(targets).contiguous(), torch.stack(movings).contiguous())
@@ -148,9 +157,9 @@ def _flows_from_denoised_packed(data: dict, model, opt, rt) -> None:
     data['flow'] = flow
 
 
-def _compute_validation_packed(model, val_dataset, opt, on_frame, val_image_dir, batch_size) -> dict:
+def _compute_validation_packed(model, val_dataset, opt, on_frame, val_image_dir, batch_size, compact=False) -> dict:
     from .data.packed import PackedLoader
-    loader = val_dataset if hasattr(val_dataset, "packs") else PackedLoader(val_dataset, batch_size)
+    loader = val_dataset if hasattr(val_dataset, "packs") else PackedLoader(val_dataset, batch_size, compact=compact)
     online_flow = (not model.isTrain) and bool(getattr(opt, "val_flow_from_denoised", False)) and not opt.no_warp
     was_training = model.isTrain
     model.isTrain = False
@@ -238,7 +247,8 @@ def main(argv=None) -> dict:
     t0 = time.time()
     val_losses = compute_validation(model, val_dataset, opt,
                                     val_image_dir=os.path.join(opt.checkpoints_dir, opt.name, "val_visuals"),
-                                    batch_size=int(getattr(opt, "val_batch_size", 1)))
+                                    batch_size=int(getattr(opt, "val_batch_size", 1)),
+                                    compact=bool(getattr(opt, "val_compact_slots", False)))
     dt = time.time() - t0
     print('(validation, %d images, %.3f s, %.2f frames/s) ' % (len(val_dataset), dt, len(val_dataset) / max(dt, 1e-9))
           + ', '.join('%s: %.3f' % kv for kv in val_losses.items()))

@@ -1,0 +1,313 @@
+"""Stepping only the live slots (rvdd_step_live) and moving a sequence's state between slots (rvdd_move_slots) on the
+device: a compact plan (data/packed.py, compact=True) over staggered videos -- refills, moves, the live count shrinking
+to 1 -- gives every frame bit for bit as the same video alone on a batch-1 handle; a full-width live step is
+rvdd_step_strided; a slot that sat a step out is refused until it is reset; validate.py --val_compact_slots writes what
+the serial mode writes."""
+import ctypes as C
+import os
+
+import pytest
+import torch
+
+from conftest import WEIGHTS, load_weights
+
+pytestmark = pytest.mark.gpu
+
+LENGTHS = [7, 3, 5, 9, 4, 6]     # frames per video: 6, 2, 4, 8, 3, 5 outputs; through 4 slots: two refills, two moves, n down to 1
+
+# id -> (arch, weights stem, future, options): the cases of tests/test_gpu_packed.py, a plain ConvNeXtUnet, and one with graphs
+CASES = {
+    "convunet": ("convunet", "recurrent-convunet-iso3200", 0, {}),
+    "convunet-k2": ("convunet", "recurrent-convunet-iso3200", 0, {"conv_kernel": 2}),
+    "feat": ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {}),
+    "feat-k2": ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"conv_kernel": 2}),
+    "feat-future": ("convunet+feat", "recurrent-convunet+feat-future-iso12800", 1, {}),
+    "feat-future-k2": ("convunet+feat", "recurrent-convunet+feat-future-iso12800", 1, {"conv_kernel": 2}),
+    "next-feat-future": ("next+feat", "recurrent-ConvNeXtUnet+feat-future-iso3200", 1, {}),
+    "feat-no_warp": ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"no_warp": 1}),
+    "convunet-warp_raw": ("convunet", "recurrent-convunet-iso3200", 0, {"warp_raw": 1}),
+    "feat-prev_noisy": ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"prev_noisy_frame": 1}),
+    "feat-block_fp0": ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"block_fp": 0}),
+    "next": ("next", "recurrent-ConvNeXtUnet-iso3200", 0, {}),
+    "feat-graphs": ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"graphs": 1}),
+}
+
+RVDD_ERR_ARG = -1      # RVDD_ERR_STATE is -2: the wrapper's message carries "(-2)"
+
+
+def _videos(lengths, H, W, future, seed0=500):
+    from rvdd_release_amd import synth
+    return [synth.make_sequence(T + future, H, W, iso=3200, seed=seed0 + v, device="cuda") for v, T in enumerate(lengths)]
+
+
+def _runtime(arch, sd, future, B, H, W, opts):
+    from rvdd_release_amd.runtime import RvddRuntime
+    rt = RvddRuntime(arch, future, B, H, W, 0)
+    rt.load_state_dict(sd)
+    for k, v in opts.items():
+        rt.set_option(k, v)
+    return rt
+
+
+def _frames(seq, future):
+    return seq.raw.shape[0] - future
+
+
+def _step(rt, seqs, frame, future, live=None):
+    """One step over frame = [(video, t)] * n."""
+    st = lambda f: torch.stack([f(seqs[v], t) for v, t in frame])
+    return rt.step(st(lambda s, t: s.raw[t - 1]), st(lambda s, t: s.raw[t]), st(lambda s, t: s.raw[t + 1]) if future else None,
+                   st(lambda s, t: s.flow_prev[t]), st(lambda s, t: s.flow_next[t]) if future else None, live=live)
+
+
+def run_alone(arch, sd, future, seqs, H, W, opts):
+    """Each video on a batch-1 handle from rvdd_reset: -> per video, its output frames [T-1-f, 3, H, W]."""
+    rt = _runtime(arch, sd, future, 1, H, W, opts)
+    outs = []
+    for v, s in enumerate(seqs):
+        rt.reset()
+        outs.append(torch.cat([_step(rt, seqs, [(v, t)], future).clone() for t in range(1, _frames(s, future))]))
+    rt.close()
+    return outs
+
+
+def compact_plan(seqs, future, B):
+    """The compact plan of the videos: -> (steps, sample index -> (video, t))."""
+    from rvdd_release_amd.data.packed import plan_packs
+    videos, where = [], {}
+    for v, s in enumerate(seqs):
+        videos.append([])
+        for t in range(1, _frames(s, future)):
+            where[len(where)] = (v, t)
+            videos[-1].append(len(where) - 1)
+    (pack,) = plan_packs(videos, [(1, 1)] * len(videos), B, compact=True)
+    return pack, where
+
+
+def run_compact(rt, seqs, future):
+    """The videos through rt's B slots by the compact plan: moves, per-slot resets, a step of the live slots.
+    -> per video its output frames, and the plan."""
+    pack, where = compact_plan(seqs, future, rt.B)
+    outs = [[] for _ in seqs]
+    rt.reset()
+    for row in pack:
+        if row.moves:
+            rt.move_slots(row.moves)
+        first = [b for b, (_, f, _) in enumerate(row) if f]
+        if first:
+            rt.reset(slots=first)
+        frame = [where[i] for i, _, _ in row]
+        out = _step(rt, seqs, frame, future, live=len(row))
+        assert out.shape[0] == len(row)
+        for b, (v, _) in enumerate(frame):
+            outs[v].append(out[b].clone())
+    return [torch.stack(o) for o in outs], pack
+
+
+def _assert_videos_equal(got, want, tag):
+    for v in range(len(want)):
+        assert got[v].shape == want[v].shape
+        for t in range(want[v].shape[0]):
+            assert torch.equal(got[v][t], want[v][t]), (tag, v, t, float((got[v][t] - want[v][t]).abs().max()))
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_compact_plan_exact(case):
+    arch, stem, future, opts = CASES[case]
+    H, W = 96, 128
+    sd = load_weights(stem)
+    seqs = _videos(LENGTHS, H, W, future)
+    want = run_alone(arch, sd, future, seqs, H, W, opts)
+    rt = _runtime(arch, sd, future, 4, H, W, opts)
+    got, pack = run_compact(rt, seqs, future)
+    rt.close()
+    # the plan does exercise what the test is about: refills, moves, every live count from 4 down to 1
+    assert sum(len(r.moves) for r in pack) >= 2 and sorted({len(r) for r in pack}) == [1, 2, 3, 4]
+    assert any(f for r in pack[1:] for _, f, _ in r)
+    _assert_videos_equal(got, want, case)
+
+
+def test_compact_tail_exact_720p_b8():
+    """C2 at 1280x720, B = 8: the tail from 8 live slots down to 1, with its moves."""
+    H, W = 720, 1280
+    sd = load_weights("recurrent-convunet+feat-iso3200")
+    lengths = [3, 6, 4, 8, 2, 5, 9, 7]
+    seqs = _videos(lengths, H, W, 0, seed0=700)
+    want = run_alone("convunet+feat", sd, 0, seqs, H, W, {})
+    rt = _runtime("convunet+feat", sd, 0, 8, H, W, {})
+    got, pack = run_compact(rt, seqs, 0)
+    rt.close()
+    assert sorted({len(r) for r in pack}) == list(range(1, 9))
+    assert sum(len(r.moves) for r in pack) >= 3
+    _assert_videos_equal(got, want, "720p")
+
+
+def _launches(rt):
+    return {p["name"]: (p["launches"], p["bytes"]) for p in rt.profile_read() if p["launches"]}
+
+
+def test_full_width_is_step_strided():
+    H, W, B, n = 96, 128, 4, 2
+    sd = load_weights("recurrent-convunet+feat-iso3200")
+    seqs = _videos([6] * B, H, W, 0, seed0=300)
+    seen = {}
+    for tag, live in (("strided", None), ("live_full", B), ("live_part", n)):
+        rt = _runtime("convunet+feat", sd, 0, B, H, W, {})
+        rt.reset()
+        outs = []
+        for t in range(1, 5):
+            if t == 3:
+                rt.reset(slots=[1])                      # a step with a partial reset goes the same way too
+            if t == 4:
+                rt.profile_enable(True)
+            frame = [(v, t) for v in range(B if live is None else live)]
+            outs.append(_step(rt, seqs, frame, 0, live=live).clone())
+        seen[tag] = (_launches(rt), outs)
+        rt.profile_enable(False)
+        rt.close()
+    strided, full, part = seen["strided"], seen["live_full"], seen["live_part"]
+    for x, y in zip(strided[1], full[1]):
+        assert torch.equal(x, y)
+    assert strided[0] and strided[0] == full[0]
+    for x, y in zip(strided[1], part[1]):
+        assert torch.equal(x[:n], y)
+    # fewer slots: the same launches per class, each over fewer sequences
+    assert {k: v[0] for k, v in part[0].items()} == {k: v[0] for k, v in strided[0].items()}
+    for k, (_, by) in part[0].items():
+        assert by == pytest.approx(strided[0][k][1] * n / B, rel=1e-9), k
+
+
+def test_move_semantics():
+    H, W, B = 96, 128, 3
+    arch, stem = "convunet+feat", "recurrent-convunet+feat-iso3200"      # block floating point on: the words must move too
+    sd = load_weights(stem)
+    seqs = _videos([8, 8, 8, 4], H, W, 0, seed0=900)
+    want = run_alone(arch, sd, 0, seqs, H, W, {})
+    rt = _runtime(arch, sd, 0, B, H, W, {})
+    rt.reset()
+    for t in (1, 2, 3):
+        _step(rt, seqs, [(0, t), (1, t), (2, t)], 0)
+    den, feat = rt.get_state()
+    lib, h = rt.lib, rt.h
+    arr = lambda *v: (C.c_int32 * len(v))(*v)
+    s = torch.cuda.current_stream().cuda_stream
+    # refused pairs (a slot twice, a slot out of range) change nothing; count = 0 does nothing
+    for fr, to in (((0, 1), (1, 2)), ((0, 0), (1, 2)), ((0, 1), (2, 2)), ((0,), (0,)), ((3,), (0,)), ((0,), (-1,))):
+        assert lib.rvdd_move_slots(h, arr(*fr), arr(*to), len(fr), s) == RVDD_ERR_ARG, (fr, to)
+        assert lib.rvdd_last_error(h)
+    assert lib.rvdd_move_slots(h, arr(0), arr(1), 0, s) == 0
+    assert lib.rvdd_move_slots(h, None, None, 0, s) == 0
+    den2, feat2 = rt.get_state()
+    assert torch.equal(den, den2) and torch.equal(feat, feat2)
+    # slot 2 -> slot 0: the destination holds the source's former state exactly, slot 1 is untouched
+    rt.move_slots([(2, 0)])
+    den2, feat2 = rt.get_state()
+    assert torch.equal(den2[0], den[2]) and torch.equal(feat2[0], feat[2])
+    assert torch.equal(den2[1], den[1]) and torch.equal(feat2[1], feat[1])
+    # the moved sequence carries on bit for bit (its words moved in every set), and so does its neighbour
+    out = _step(rt, seqs, [(2, 4), (1, 4)], 0, live=2)
+    assert torch.equal(out[0], want[2][3]) and torch.equal(out[1], want[1][3])
+    # the source is undefined afterwards
+    with pytest.raises(RuntimeError, match=r"\(-2\).*slot 2 is undefined"):
+        _step(rt, seqs, [(2, 5), (1, 5), (0, 5)], 0)
+    # a pending reset mark travels with the state: mark slot 0, move it to slot 2 -- slot 0 has no mark any more (and is
+    # undefined); move it back -- the mark is on slot 0 again, which starts a video on the next step
+    rt.reset(slots=[0])
+    rt.move_slots([(0, 2)])
+    with pytest.raises(RuntimeError, match=r"\(-2\).*slot 0 is undefined"):
+        _step(rt, seqs, [(2, 5)], 0, live=1)
+    rt.move_slots([(2, 0)])
+    out = _step(rt, seqs, [(3, 1), (1, 5)], 0, live=2)
+    assert torch.equal(out[0], want[3][0]) and torch.equal(out[1], want[1][4])
+    out = _step(rt, seqs, [(3, 2), (1, 6)], 0, live=2)
+    assert torch.equal(out[0], want[3][1]) and torch.equal(out[1], want[1][5])
+    rt.close()
+
+
+def test_move_keeps_the_sequence_in_every_set():
+    """A sequence moved after k = 1 .. 4 steps carries on bit for bit: the block-floating-point words rotate through their
+    sets with the step count, and they were moved in every set."""
+    H, W = 96, 128
+    arch, stem = "convunet+feat", "recurrent-convunet+feat-iso3200"
+    sd = load_weights(stem)
+    seqs = _videos([8, 8], H, W, 0, seed0=950)
+    want = run_alone(arch, sd, 0, seqs, H, W, {})
+    for k in (1, 2, 3, 4):
+        rt = _runtime(arch, sd, 0, 2, H, W, {})
+        rt.reset()
+        for t in range(1, k + 1):
+            _step(rt, seqs, [(0, t), (1, t)], 0)
+        rt.move_slots([(1, 0)])
+        for t in range(k + 1, 8):
+            out = _step(rt, seqs, [(1, t)], 0, live=1)
+            assert torch.equal(out[0], want[1][t - 1]), (k, t)
+        rt.close()
+
+
+def test_undefined_slots():
+    H, W, B = 96, 128, 3
+    arch, stem = "convunet+feat", "recurrent-convunet+feat-iso3200"
+    sd = load_weights(stem)
+    seqs = _videos([10, 10, 8, 5], H, W, 0, seed0=1100)
+    want = run_alone(arch, sd, 0, seqs, H, W, {})
+    rt = _runtime(arch, sd, 0, B, H, W, {})
+    rt.reset()
+    for t in (1, 2):
+        _step(rt, seqs, [(0, t), (1, t), (2, t)], 0)
+    out = _step(rt, seqs, [(0, 3), (1, 3)], 0, live=2)
+    assert torch.equal(out[0], want[0][2]) and torch.equal(out[1], want[1][2])
+    # slot 2 sat the step out: a full step without a mark for it is refused, through either entry point ...
+    for live in (None, 3):
+        with pytest.raises(RuntimeError, match=r"\(-2\).*slot 2 is undefined"):
+            _step(rt, seqs, [(0, 4), (1, 4), (2, 4)], 0, live=live)
+    assert "slot 2" in rt.lib.rvdd_last_error(rt.h).decode()
+    # ... and the handle is as it was: the live slots carry on,
+    out = _step(rt, seqs, [(0, 4), (1, 4)], 0, live=2)
+    assert torch.equal(out[0], want[0][3]) and torch.equal(out[1], want[1][3])
+    # a mark for a slot >= n_live stays pending over a partial step,
+    rt.reset(slots=[2])
+    out = _step(rt, seqs, [(0, 5), (1, 5)], 0, live=2)
+    assert torch.equal(out[0], want[0][4]) and torch.equal(out[1], want[1][4])
+    # and with it the full step succeeds: the left-out slot starts a video and equals batch 1
+    for t in (1, 2, 3):
+        out = _step(rt, seqs, [(0, 5 + t), (1, 5 + t), (3, t)], 0)
+        assert torch.equal(out[0], want[0][4 + t]) and torch.equal(out[1], want[1][4 + t])
+        assert torch.equal(out[2], want[3][t - 1]), t
+    # n_live out of range
+    s = torch.cuda.current_stream().cuda_stream
+    for n in (0, -1, B + 1):
+        assert rt.lib.rvdd_step_live(rt.h, n, None, None, None, None, None, 0, 0, None, s) == RVDD_ERR_ARG
+    rt.close()
+
+
+@pytest.mark.parametrize("online", [False, True], ids=["dataset_flow", "online_flow"])
+def test_compact_validation_on_disk(tmp_path, online):
+    from rvdd_release_amd import synth, validate
+    from test_formats import write_dataset
+    seqs = [synth.make_sequence(T, 64, 96, iso=3200, seed=80 + v) for v, T in enumerate([4, 2, 5, 3, 3])]
+    root = tmp_path / "validation"
+    write_dataset(str(root), seqs, iso=3200)
+    name = "recurrent-convunet+feat-iso3200"
+
+    def run(B, compact):
+        ck = tmp_path / f"ck{B}"
+        argv = ["--netDenoiser", "convunet-mode=fixedfeatures+feat", "--path2epoch", os.path.join(WEIGHTS, name),
+                "--val_dataroot", str(root), "--gtFolder", "gt_iso3200", "--nFolder", "noisy_iso3200",
+                "--gt_linear_RGB_Folder", "gt_raw_linear_RGB_iso3200", "--suffix", "t", "--checkpoints_dir", str(ck),
+                "--val_videos", "000,001,002,003,004", "--feature_rec", "--val_batch_size", str(B)]
+        if compact:
+            argv.append("--val_compact_slots")
+        if online:
+            argv.append("--val_flow_from_denoised")
+        res = validate.main(argv)
+        out = ck / "recurrent-convunet-mode=fixedfeatures+feat-warp-i3o3-t" / "val_visuals"
+        files = {os.path.relpath(os.path.join(d, f), out): open(os.path.join(d, f), "rb").read()
+                 for d, _, fs in os.walk(out) for f in fs}
+        return res, files
+
+    serial, compact = run(1, False), run(4, True)
+    assert compact[0] == serial[0]
+    assert sorted(compact[1]) == sorted(serial[1])
+    assert len([f for f in serial[1] if f.endswith(".tif")]) == 3 + 1 + 4 + 2 + 2
+    for f in serial[1]:
+        assert compact[1][f] == serial[1][f], f
