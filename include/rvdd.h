@@ -14,7 +14,10 @@
  *    rvdd_last_error() gives the message (per handle; NULL -> last create error);
  *  - all tensor pointers are DEVICE pointers to dense fp32 tensors in the
  *    reference's own layout (NCHW), owned by the caller (e.g. obtained from
- *    torch.Tensor.data_ptr() on PyTorch-ROCm);
+ *    torch.Tensor.data_ptr() on PyTorch-ROCm).  The one exception: `frames`
+ *    of rvdd_ingest_raw / rvdd_video_push, DEVICE pointers to sensor frames
+ *    of 16-bit unsigned integers or fp32 in one of the two layouts of
+ *    enum rvdd_raw_layout;
  *  - `stream` is a hipStream_t passed as void* (NULL = the default stream);
  *    calls are asynchronous and stream-ordered unless stated otherwise;
  *  - a handle owns its weights, workspace and the recurrent state; one handle
@@ -238,6 +241,65 @@ int rvdd_tvl1flow(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t
 int rvdd_tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny,
                         int32_t* iterations, void* stream);
 
+/* ---- raw footage: sensor frames in, denoised frames out --------------------- */
+
+enum rvdd_raw_dtype  { RVDD_RAW_U16 = 0, RVDD_RAW_F32 = 1 };
+enum rvdd_raw_layout { RVDD_RAW_MOSAIC = 0,      /* [n,2hh,2ww]: one plane, as a sensor writes it            */
+                       RVDD_RAW_PACKED_HWC = 1 };/* [n,hh,ww,4]: the reference dataset's TIFF (iio layout)    */
+
+/* Sensor frames (digital numbers, DN) -> what a frame-step and TV-L1 read, in one kernel:
+ *   packed [n,4,hh,ww] = 2 * (dn / (2^bit_depth - 1)) - 1, each operation rounded to f32 on its own and the division
+ *          correctly rounded: bit for bit the dataset's transform of library.load_image(path, bit_depth)
+ *          (library.py:75-90; data/base_dataset.py define_transforms).  Channel k holds CFA position (k >> 1, k & 1) of each
+ *          2x2 cell, packed[k][y][x] = mosaic[2y + (k >> 1)][2x + (k & 1)] -- the packing of enum rvdd_bayer, whatever the
+ *          pattern.  No black level is subtracted: the reference leaves it in the data and the checkpoints were trained so.
+ *   gray   [n,hh,ww]   = (((c0 + c1) + c2) + c3) * 0.25f of the four DN values of a cell (NOT the normalised ones), an f32
+ *          sum in channel order: what library._gray (library.py:118-126, mean over the channels) hands TV-L1.  On
+ *          integer-valued frames every summation order gives these bits; on other float frames a reduction that sums in
+ *          another order (torch's on the device is free to) may differ in the last bit.
+ * Either output may be NULL.  bit_depth 1..16, dtype / layout as the enums: RVDD_ERR_ARG otherwise.  n = 0 does nothing.
+ * `frames` 16-byte aligned with ww % 4 == 0 takes the wide form (16-byte accesses, 1 KiB runs per wave). */
+int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t n, int32_t hh, int32_t ww,
+                    int32_t bit_depth, float* packed /* [n,4,hh,ww], nullable */, float* gray /* [n,hh,ww], nullable */,
+                    void* stream);
+
+enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
+
+/* The stream: one call hands every batch slot its next sensor frame (`frames`: cfg.batch frames of H/2 x W/2 cells, one
+ * per slot, dtype / layout / bit_depth as rvdd_ingest_raw) and enqueues, in stream order, at most one output frame per
+ * slot.  Everything between the frames and out_rgb stays on the device; nothing is read back, `stream` is not synchronised.
+ *   ctl (HOST [cfg.batch], NULL = all NEXT): FIRST = this frame starts a new video in the slot (its older frames are
+ *       forgotten); NEXT = it continues the slot's video; IDLE = the slot gets no frame (its slice of `frames` is not read).
+ *       After IDLE a slot goes on with FIRST or IDLE only; NEXT there, or on a slot that never had a FIRST, is
+ *       RVDD_ERR_STATE (the message names the slot) and nothing is changed.
+ *   valid (HOST [cfg.batch]): 1 for the slots that are READY -- that hold 2 + future frames of their video -- and out_rgb[b]
+ *       [cfg.batch,3,H,W] then holds the denoised CENTRE frame: with future = 0 the frame just pushed, with future = 1 the
+ *       frame pushed one call earlier.  The outputs of a video of N frames are its frames 1 .. N-1-future, the frames
+ *       data/infer4rec_dataset.py yields; frame 0 and, with a future frame, the last frame are never output (no flush).
+ *       out_rgb[b] of a slot that is not ready is unspecified.
+ * The handle keeps the last 2 + future ingested frames of every slot (packed and gray) on the device: allocated by the
+ * first push, freed with the handle (20 (2 + future) + 24 (1 + future) bytes per raw cell and slot with the flow batch's
+ * buffers).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
+ * I1 = gray[previous]) and, with a future frame, (gray[centre], gray[next]) for all of them in ONE batch call in the form of
+ * option "tvl1_async" 1 (whatever the option says), then one rvdd_step_strided on the kept packed frames and those flows.  A
+ * slot's first ready push carries its reset mark (rvdd_reset_slots; raw_prev = its oldest frame), so every output is bit for
+ * bit what a handle of batch 1 gives for that video.  With option "no_warp" no flow is computed; "warp_raw",
+ * "prev_noisy_frame", "bayer_pattern" and the kernel-selection options act inside the step, unchanged.
+ * The step has no per-slot skip: slots that are idle or not ready step too, on the finite frames their ring holds and a zero
+ * flow (no TV-L1 pair), and their state is re-initialised by the reset mark of their first ready push.  The cost is 1 + future
+ * discarded slot-steps per video that starts while others run.  If no slot is ready the push only ingests.
+ * Limits, reported as RVDD_ERR_ARG by the first push: cfg.batch <= 64 (the partial marks of rvdd_reset_slots); without
+ * "no_warp", frames of at least 16 x 16 cells that rvdd_tvl1flow_batch accepts.
+ * A TV-L1 exchange that gave up leaves the batch's control word set, as option "tvl1_async" describes: a streaming loop of
+ * pushes never reads it.  It is read -- and reported as RVDD_ERR_HIP -- by rvdd_psnr_l1[_batch], by a TV-L1 call that returns
+ * iteration counts, and by rvdd_set_option(h, "tvl1_async", 0), which synchronises the device: call one of them wherever the
+ * loop synchronises anyway (python -m rvdd_release_amd.denoise does at the end of every video).
+ * rvdd_reset / rvdd_reset_slots / rvdd_step* keep working on such a handle exactly as before: they do not touch the kept
+ * frames (and the kept frames do not know of them: a stream goes on from the recurrent state such calls leave). */
+int rvdd_video_push(rvdd_t* h, const void* frames /* [B, one frame each] */, int32_t dtype, int32_t layout,
+                    int32_t bit_depth, const uint8_t* ctl /* HOST [B], NULL = all NEXT */,
+                    float* out_rgb /* [B,3,H,W] */, uint8_t* valid /* HOST [B] */, void* stream);
+
 /* dataset/fwd_ppipe.py `ppipe(im, rgb_gain, red_gain, blue_gain, iso)` (:48-77) fused with the range
  * normalisation in front of it (:131-137) and the uint8 conversion behind it (:141): linear camera RGB ->
  * display sRGB (inverse percentile matching per ISO, black level, white-balance gains, inverse CCM,
@@ -321,6 +383,9 @@ int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, 
  *               re-mosaic of a step follows it -- the current and next frames, raw_prev on a first step and on
  *               rvdd_reset_slots, --prev_noisy_frame and --warp_raw.  Default 0 (GBRG); any other value than 0..3 is
  *               RVDD_ERR_ARG.  Per handle.
+ *   "stream_reset_each": 1 = every step of rvdd_video_push carries the reset mark of every ready slot: non-recurrent checkpoints
+ *               (--patch_depth 2, the model's training_unrollings == 1: recurrentModel.forward resets before every step,
+ *               models/recurrent_model.py:233-245).  Default 0.  Acts on rvdd_video_push only.  Per handle.
  * Unknown names are an error. */
 int rvdd_set_option(rvdd_t* h, const char* name, int32_t value);
 

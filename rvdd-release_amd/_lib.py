@@ -14,6 +14,11 @@ LIB_PATH = os.path.join(_HERE, "librvdd_hip.so")
 
 RVDD_OK = 0
 ARCH_CONVUNET, ARCH_CONVUNET_FEAT, ARCH_CONVNEXT, ARCH_CONVNEXT_FEAT = 0, 1, 2, 3
+# enum rvdd_raw_dtype / rvdd_raw_layout (rvdd_ingest_raw, rvdd_video_push) and enum rvdd_push (rvdd_video_push's ctl)
+RAW_U16, RAW_F32 = 0, 1
+RAW_MOSAIC, RAW_PACKED_HWC = 0, 1
+PUSH_NEXT, PUSH_FIRST, PUSH_IDLE = 0, 1, 2
+PPIPE_FROM_NET = -1      # RVDD_PPIPE_FROM_NET: rvdd_ppipe's bit_depth for a network output in [-1,1]
 
 
 class RvddCfg(C.Structure):
@@ -49,6 +54,8 @@ _PROTOS = {
     "rvdd_tiff_lzw_decode": (C.c_int64, [_P, C.c_int64, _P, C.c_int64]),
     "rvdd_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "rvdd_tvl1flow_batch": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P]),
+    "rvdd_ingest_raw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_ppipe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                              C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P]),
     "rvdd_srgb_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double),

@@ -1,0 +1,224 @@
+// Sensor frames -> the inputs of a frame-step (packed raw in [-1, 1]) and of TV-L1 (gray plane in DN), and the two small
+// copy kernels rvdd_video_push composes its flow batch with.  Compiled -ffp-contract=off: every operation below is rounded
+// to f32 on its own, which is what makes the outputs the bits of the reference's loader (library.py load_image + the
+// dataset's transform) and of library._gray on integer-valued frames.
+//
+// ingest_raw_kernel is a pure streaming kernel (2 B read, 4 B + 1 B written per CFA site for a u16 mosaic).  The fast form
+// gives a thread FOUR neighbouring 2x2 cells of one cell row: for a mosaic it reads 16 B (u16) / 2 x 16 B (f32) from each of
+// the two sensor rows, for the packed HWC layout 2 x 16 B (u16) / 4 x 16 B (f32) of one row, and writes one 16-B vector per
+// packed channel and one for the gray plane -- so the 64 lanes of a wave read 1 KiB runs of each sensor row and write 1 KiB
+// runs of each output plane.  It needs ww % 4 == 0 and 16-B aligned pointers; any other shape takes the one-cell form.
+#include "rvdd_internal.h"
+
+namespace {
+
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+// one 2x2 cell: c[k] = CFA position (k >> 1, k & 1) in DN
+template <typename T, int LAYOUT>
+__device__ __forceinline__ void load_cell(const T* __restrict__ f, int64_t img, int y, int x, int hh, int ww, float c[4]) {
+    if constexpr (LAYOUT == 0) {
+        const T* r0 = f + (img * 2 * hh + 2 * (int64_t)y) * (2 * (int64_t)ww) + 2 * x;
+        const T* r1 = r0 + 2 * (int64_t)ww;
+        c[0] = (float)r0[0]; c[1] = (float)r0[1]; c[2] = (float)r1[0]; c[3] = (float)r1[1];
+    } else {
+        const T* p = f + ((img * hh + y) * (int64_t)ww + x) * 4;
+        c[0] = (float)p[0]; c[1] = (float)p[1]; c[2] = (float)p[2]; c[3] = (float)p[3];
+    }
+}
+
+// four cells x .. x+3 of a cell row (x % 4 == 0, ww % 4 == 0, 16-B aligned base): c[i][k]
+template <typename T, int LAYOUT>
+__device__ __forceinline__ void load_cells4(const T* __restrict__ f, int64_t img, int y, int x, int hh, int ww, float c[4][4]) {
+    if constexpr (LAYOUT == 0) {
+        const T* r0 = f + (img * 2 * hh + 2 * (int64_t)y) * (2 * (int64_t)ww) + 2 * x;
+        const T* r1 = r0 + 2 * (int64_t)ww;
+        if constexpr (sizeof(T) == 2) {
+            const u16x8 a = *reinterpret_cast<const u16x8*>(r0), b = *reinterpret_cast<const u16x8*>(r1);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                c[i][0] = (float)a[2 * i]; c[i][1] = (float)a[2 * i + 1];
+                c[i][2] = (float)b[2 * i]; c[i][3] = (float)b[2 * i + 1];
+            }
+        } else {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(r0), a1 = *reinterpret_cast<const f32x4*>(r0 + 4);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(r1), b1 = *reinterpret_cast<const f32x4*>(r1 + 4);
+            c[0][0] = a0[0]; c[0][1] = a0[1]; c[1][0] = a0[2]; c[1][1] = a0[3];
+            c[2][0] = a1[0]; c[2][1] = a1[1]; c[3][0] = a1[2]; c[3][1] = a1[3];
+            c[0][2] = b0[0]; c[0][3] = b0[1]; c[1][2] = b0[2]; c[1][3] = b0[3];
+            c[2][2] = b1[0]; c[2][3] = b1[1]; c[3][2] = b1[2]; c[3][3] = b1[3];
+        }
+    } else {
+        const T* p = f + ((img * hh + y) * (int64_t)ww + x) * 4;
+        if constexpr (sizeof(T) == 2) {
+            const u16x8 a = *reinterpret_cast<const u16x8*>(p), b = *reinterpret_cast<const u16x8*>(p + 8);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                c[0][k] = (float)a[k]; c[1][k] = (float)a[4 + k];
+                c[2][k] = (float)b[k]; c[3][k] = (float)b[4 + k];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(p + 4 * i);
+                c[i][0] = v[0]; c[i][1] = v[1]; c[i][2] = v[2]; c[i][3] = v[3];
+            }
+        }
+    }
+}
+
+// packed = 2 * (dn / maxv) - 1: the division correctly rounded, then the product, then the difference
+__device__ __forceinline__ float norm_dn(float dn, float maxv) { return 2.0f * __fdiv_rn(dn, maxv) - 1.0f; }
+// library._gray of a 4-channel frame: the f32 sum in channel order, left to right, times 0.25
+__device__ __forceinline__ float gray_dn(const float c[4]) { return (((c[0] + c[1]) + c[2]) + c[3]) * 0.25f; }
+
+template <typename T, int LAYOUT, bool VEC>
+__global__ void __launch_bounds__(256) ingest_raw_kernel(const T* __restrict__ frames, float* __restrict__ packed, float* __restrict__ gray,
+                                                         int n, int hh, int ww, float maxv) {
+    const int64_t hw = (int64_t)hh * ww;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (VEC) {
+        const int wq = ww >> 2;
+        if (t >= (int64_t)n * hh * wq) return;
+        const int xq = (int)(t % wq);
+        const int64_t row = t / wq;              // img * hh + y
+        const int y = (int)(row % hh);
+        const int64_t img = row / hh;
+        float c[4][4];
+        load_cells4<T, LAYOUT>(frames, img, y, 4 * xq, hh, ww, c);
+        const int64_t o = (int64_t)y * ww + 4 * xq;
+        if (packed) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                f32x4 v;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = norm_dn(c[i][k], maxv);
+                *reinterpret_cast<f32x4*>(packed + (img * 4 + k) * hw + o) = v;
+            }
+        }
+        if (gray) {
+            f32x4 g;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) g[i] = gray_dn(c[i]);
+            *reinterpret_cast<f32x4*>(gray + img * hw + o) = g;
+        }
+    } else {
+        if (t >= (int64_t)n * hw) return;
+        const int x = (int)(t % ww);
+        const int64_t row = t / ww;
+        const int y = (int)(row % hh);
+        const int64_t img = row / hh;
+        float c[4];
+        load_cell<T, LAYOUT>(frames, img, y, x, hh, ww, c);
+        const int64_t o = (int64_t)y * ww + x;
+        if (packed) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) packed[(img * 4 + k) * hw + o] = norm_dn(c[k], maxv);
+        }
+        if (gray) gray[img * hw + o] = gray_dn(c);
+    }
+}
+
+template <typename T, int LAYOUT>
+hipError_t launch_ingest_t(const T* frames, int n, int hh, int ww, float maxv, float* packed, float* gray, hipStream_t s) {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(gray);
+    const bool vec = (ww & 3) == 0 && (al & 15) == 0;
+    const int64_t work = vec ? (int64_t)n * hh * (ww >> 2) : (int64_t)n * hh * ww;
+    const int64_t blocks = (work + 255) / 256;
+    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    if (vec)
+        hipLaunchKernelGGL((ingest_raw_kernel<T, LAYOUT, true>), dim3((unsigned)blocks), dim3(256), 0, s, frames, packed, gray, n, hh, ww, maxv);
+    else
+        hipLaunchKernelGGL((ingest_raw_kernel<T, LAYOUT, false>), dim3((unsigned)blocks), dim3(256), 0, s, frames, packed, gray, n, hh, ww, maxv);
+    return hipGetLastError();
+}
+
+// ---- rvdd_video_push: the flow batch's operands and results ------------------------------------------------------------
+// The ready slots of a push, one byte each (B <= 64 on a partial set; the full set needs no list)
+struct SlotList {
+    unsigned char slot[64];
+};
+
+// (V = f32x4 where a plane is a whole number of 16-B vectors, float otherwise; hw4 / hw2_4 count V's)
+// I0[q] / I1[q], q < npairs: pair q < nready = (centre, previous) of ready slot q, pair nready + q = (centre, next).
+// gray_c / gray_p / gray_n: the [B][hw] planes of the ring positions that hold the centre, previous and next frames.
+template <typename V>
+__global__ void __launch_bounds__(256) stream_gather_kernel(const float* __restrict__ gray_c, const float* __restrict__ gray_p,
+                                                            const float* __restrict__ gray_n, float* __restrict__ I0, float* __restrict__ I1,
+                                                            SlotList sl, int nready, int all, int64_t hw4) {
+    const int q = blockIdx.y;
+    const int r = q < nready ? q : q - nready;
+    const int b = all ? r : sl.slot[r];
+    const V* c = reinterpret_cast<const V*>(gray_c) + (int64_t)b * hw4;
+    const V* o = reinterpret_cast<const V*>(q < nready ? gray_p : gray_n) + (int64_t)b * hw4;
+    V* d0 = reinterpret_cast<V*>(I0) + (int64_t)q * hw4;
+    V* d1 = reinterpret_cast<V*>(I1) + (int64_t)q * hw4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw4; i += (int64_t)gridDim.x * blockDim.x) {
+        d0[i] = c[i];
+        d1[i] = o[i];
+    }
+}
+
+// flows [ndir][B][2][hw] of a step from the batch's u [ndir * nready][2][hw]: the flow of a ready slot, zero for the others.
+// rank[b] = position of slot b among the ready ones, 255 = not ready.
+template <typename V>
+__global__ void __launch_bounds__(256) stream_scatter_kernel(const float* __restrict__ u, float* __restrict__ flows, SlotList rank, int nready,
+                                                             int B, int64_t hw2_4) {
+    const int b = blockIdx.y % B, dir = blockIdx.y / B;
+    const int r = rank.slot[b];
+    V* d = reinterpret_cast<V*>(flows) + ((int64_t)dir * B + b) * hw2_4;
+    const V* src = r == 255 ? nullptr : reinterpret_cast<const V*>(u) + ((int64_t)dir * nready + r) * hw2_4;
+    const V zero = {};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw2_4; i += (int64_t)gridDim.x * blockDim.x)
+        d[i] = src ? src[i] : zero;
+}
+
+}  // namespace
+
+hipError_t launch_ingest_raw(const void* frames, int dtype, int layout, int n, int hh, int ww, int bit_depth, float* packed, float* gray,
+                             hipStream_t s) {
+    if (n <= 0 || (!packed && !gray)) return hipSuccess;
+    const float maxv = (float)((1u << bit_depth) - 1u);
+    if (dtype == 0) {
+        const unsigned short* f = static_cast<const unsigned short*>(frames);
+        return layout == 0 ? launch_ingest_t<unsigned short, 0>(f, n, hh, ww, maxv, packed, gray, s)
+                           : launch_ingest_t<unsigned short, 1>(f, n, hh, ww, maxv, packed, gray, s);
+    }
+    const float* f = static_cast<const float*>(frames);
+    return layout == 0 ? launch_ingest_t<float, 0>(f, n, hh, ww, maxv, packed, gray, s) : launch_ingest_t<float, 1>(f, n, hh, ww, maxv, packed, gray, s);
+}
+
+// planes of the handle's own buffers (hipMalloc alignment); slots: the ready slots in order (ignored when nready == B)
+hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const float* gray_n, float* I0, float* I1, const int* slots,
+                                int nready, int B, int64_t hw, hipStream_t s) {
+    SlotList sl{};
+    const int all = nready == B;
+    if (!all) {
+        if (nready > 64) return hipErrorInvalidValue;
+        for (int q = 0; q < nready; ++q) sl.slot[q] = (unsigned char)slots[q];
+    }
+    const int npairs = nready * (gray_n ? 2 : 1);
+    const bool vec = (hw & 3) == 0;
+    const int64_t hw4 = vec ? hw / 4 : hw;
+    const int gx = (int)((hw4 + 255) / 256 < 256 ? (hw4 + 255) / 256 : 256);
+    if (vec)
+        hipLaunchKernelGGL(stream_gather_kernel<f32x4>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, I0, I1, sl, nready, all, hw4);
+    else
+        hipLaunchKernelGGL(stream_gather_kernel<float>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, I0, I1, sl, nready, all, hw4);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_scatter(const float* u, float* flows, const int* slots, int nready, int ndir, int B, int64_t hw, hipStream_t s) {
+    if (B > 64) return hipErrorInvalidValue;
+    SlotList rank;
+    for (int b = 0; b < 64; ++b) rank.slot[b] = 255;
+    for (int q = 0; q < nready; ++q) rank.slot[slots[q]] = (unsigned char)q;
+    const bool vec = (hw & 1) == 0;
+    const int64_t n4 = vec ? 2 * hw / 4 : 2 * hw;
+    const int gx = (int)((n4 + 255) / 256 < 256 ? (n4 + 255) / 256 : 256);
+    if (vec)
+        hipLaunchKernelGGL(stream_scatter_kernel<f32x4>, dim3(gx, ndir * B), dim3(256), 0, s, u, flows, rank, nready, B, n4);
+    else
+        hipLaunchKernelGGL(stream_scatter_kernel<float>, dim3(gx, ndir * B), dim3(256), 0, s, u, flows, rank, nready, B, n4);
+    return hipGetLastError();
+}

@@ -200,6 +200,23 @@ struct rvdd_handle {
     Tvl1Workspace* tvl1 = nullptr;   // cached for the last (nx, ny)
     bool tvl1_async = false;         // option "tvl1_async": rvdd_tvl1flow_batch without iteration counts enqueues and returns (see rvdd.h)
 
+    // rvdd_video_push: the last 2 + future ingested frames of every slot, allocated by the first push.  The slots share ONE
+    // ring position per push (push k writes position k % depth of every slot that gets a frame), so the centre, previous and
+    // next frames of all slots are dense [B] tensors and the step takes them without a copy.
+    struct Stream {
+        int depth = 0;               // 2 + future
+        float* packed = nullptr;     // [depth][B][4][hh][ww]
+        float* gray = nullptr;       // [depth][B][hh][ww]
+        float* I0 = nullptr;         // [(1 + future) B][hh][ww]: the flow batch's operands (launch_stream_gather)
+        float* I1 = nullptr;
+        float* u = nullptr;          // [(1 + future) B][2][hh][ww]: its flows when only some slots are ready
+        float* flows = nullptr;      // [1 + future][B][2][hh][ww]: flow_prev | flow_next of the step
+        uint64_t pushes = 0;
+        std::vector<int> count;      // per slot: frames of its video pushed in a row (0: never started, or idle on the last push)
+        std::vector<uint8_t> was_idle;
+    } st;
+    bool stream_reset_each = false;  // option "stream_reset_each": every ready step of rvdd_video_push carries the reset mark of every ready slot
+
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
         const void* p[6];
@@ -1237,6 +1254,11 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         h->tvl1_async = value != 0;
         return RVDD_OK;
     }
+    if (std::strcmp(name, "stream_reset_each") == 0) {
+        // 1 = non-recurrent checkpoints (training_unrollings == 1: recurrentModel.forward resets before every step)
+        h->stream_reset_each = value != 0;
+        return RVDD_OK;
+    }
     if (std::strcmp(name, "fuse_pre") == 0) {
         // 0 = preprocessing_layer and EncoderConvs[0][0] as the two convs they are, instead of their composition (the A/B
         // reference: same map up to fp32 rounding of a different summation order)
@@ -1276,7 +1298,7 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         h->split16 = value == 0;
         return RVDD_OK;
     }
-    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, cout_split, small_prestage, bayer_pattern)", name);
+    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, cout_split, small_prestage, bayer_pattern, stream_reset_each)", name);
 }
 
 int rvdd_reset(rvdd_t* h) {
@@ -1896,6 +1918,111 @@ int rvdd_tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, i
     if (iterations)
         for (int i = 0; i < n; ++i) iterations[i] = it[(size_t)i];
     return RVDD_OK;
+}
+
+int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+                    float* packed, float* gray, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (dtype != RVDD_RAW_U16 && dtype != RVDD_RAW_F32) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: dtype must be 0 (u16) or 1 (f32), got %d", dtype);
+    if (layout != RVDD_RAW_MOSAIC && layout != RVDD_RAW_PACKED_HWC)
+        return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: layout must be 0 (mosaic) or 1 (packed HWC), got %d", layout);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: bit_depth must be 1..16, got %d", bit_depth);
+    if (n == 0) return RVDD_OK;
+    if (!frames || n < 0 || hh < 1 || ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: bad argument (frames, n >= 0, hh, ww >= 1)");
+    ENTER(h);
+    HIPCHK(h, launch_ingest_raw(frames, dtype, layout, n, hh, ww, bit_depth, packed, gray, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t bit_depth, const uint8_t* ctl, float* out_rgb,
+                    uint8_t* valid, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (dtype != RVDD_RAW_U16 && dtype != RVDD_RAW_F32) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: dtype must be 0 (u16) or 1 (f32), got %d", dtype);
+    if (layout != RVDD_RAW_MOSAIC && layout != RVDD_RAW_PACKED_HWC)
+        return fail(h, RVDD_ERR_ARG, "rvdd_video_push: layout must be 0 (mosaic) or 1 (packed HWC), got %d", layout);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: bit_depth must be 1..16, got %d", bit_depth);
+    if (!frames || !out_rgb || !valid) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: frames, out_rgb and valid are required");
+    if (!h->finalized) return fail(h, RVDD_ERR_STATE, "rvdd_video_push: weights not finalized");
+    const int B = h->cfg.batch, hh = h->cfg.height / 2, ww = h->cfg.width / 2, fut = h->cfg.future;
+    const size_t hw = (size_t)hh * ww;
+    auto& st = h->st;
+    for (int b = 0; b < B; ++b)
+        if (ctl && ctl[b] > RVDD_PUSH_IDLE) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: ctl[%d] = %d is not 0 (NEXT), 1 (FIRST) or 2 (IDLE)", b, ctl[b]);
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!st.packed) {      // the first push
+        if (B > 64) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: needs batch <= 64, as the partial reset marks of rvdd_reset_slots do (batch is %d)", B);
+        if (!h->no_warp && (hh < 16 || ww < 16 || !tvl1_size_ok(ww, hh)))
+            return fail(h, RVDD_ERR_ARG, "rvdd_video_push: raw frames of %d x %d cells are not a size rvdd_tvl1flow_batch accepts (at least 16 x 16 and not too "
+                        "skinny for the flow's pyramid); only option no_warp streams this size", ww, hh);
+        const int depth = 2 + fut, nd = 1 + fut;
+        st.count.assign((size_t)B, 0);
+        st.was_idle.assign((size_t)B, 0);
+        float *pk = nullptr, *gr = nullptr;
+        RC(dmalloc(h, reinterpret_cast<void**>(&gr), (size_t)depth * B * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&st.I0), (size_t)nd * B * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&st.I1), (size_t)nd * B * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&st.u), (size_t)nd * B * 2 * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&st.flows), (size_t)nd * B * 2 * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&pk), (size_t)depth * B * 4 * hw * sizeof(float)));
+        st.gray = gr;
+        st.depth = depth;
+        st.pushes = 0;
+        st.packed = pk;      // last: the mark of a complete allocation
+    }
+    // the whole ctl is judged before anything changes
+    for (int b = 0; b < B; ++b)
+        if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
+            return st.was_idle[(size_t)b]
+                       ? fail(h, RVDD_ERR_STATE, "rvdd_video_push: slot %d was idle on the last push: it goes on with FIRST or IDLE, not NEXT", b)
+                       : fail(h, RVDD_ERR_STATE, "rvdd_video_push: slot %d has no video yet: its first frame is pushed with FIRST", b);
+    // ingest: one launch per run of slots that get a frame
+    const int pos = (int)(st.pushes % (uint64_t)st.depth);
+    const size_t esz = dtype == RVDD_RAW_U16 ? 2 : 4;
+    for (int b = 0; b < B;) {
+        if (ctl && ctl[b] == RVDD_PUSH_IDLE) { ++b; continue; }
+        int e = b + 1;
+        while (e < B && !(ctl && ctl[e] == RVDD_PUSH_IDLE)) ++e;
+        HIPCHK(h, launch_ingest_raw(static_cast<const char*>(frames) + (size_t)b * 4 * hw * esz, dtype, layout, e - b, hh, ww, bit_depth,
+                                    st.packed + ((size_t)pos * B + b) * 4 * hw, st.gray + ((size_t)pos * B + b) * hw, s));
+        b = e;
+    }
+    std::vector<int> ready, fresh;
+    for (int b = 0; b < B; ++b) {
+        const int c = ctl ? ctl[b] : RVDD_PUSH_NEXT;
+        int& n = st.count[(size_t)b];
+        n = c == RVDD_PUSH_IDLE ? 0 : c == RVDD_PUSH_FIRST ? 1 : (n < (1 << 30) ? n + 1 : n);
+        st.was_idle[(size_t)b] = c == RVDD_PUSH_IDLE;
+        valid[b] = n >= st.depth;
+        if (n >= st.depth) ready.push_back(b);
+        if (n == st.depth || (h->stream_reset_each && n >= st.depth)) fresh.push_back(b);
+    }
+    st.pushes++;
+    if (ready.empty()) return RVDD_OK;
+    const int nready = (int)ready.size();
+    // ring positions: with a future frame the centre is the frame of the push before
+    const int pc = (pos + st.depth - fut) % st.depth, pp = (pc + st.depth - 1) % st.depth;
+    auto packed_at = [&](int p) { return st.packed + (size_t)p * B * 4 * hw; };
+    auto gray_at = [&](int p) { return st.gray + (size_t)p * B * hw; };
+    const float *flow_prev = nullptr, *flow_next = nullptr;
+    if (!h->no_warp) {
+        HIPCHK(h, launch_stream_gather(gray_at(pc), gray_at(pp), fut ? gray_at(pos) : nullptr, st.I0, st.I1, ready.data(), nready, B, (int64_t)hw, s));
+        float* u = nready == B ? st.flows : st.u;      // every slot ready: the batch writes the step's flows itself
+        const bool was_async = h->tvl1_async;
+        h->tvl1_async = true;
+        const int rc = rvdd_tvl1flow_batch(h, st.I0, st.I1, u, nready * (1 + fut), ww, hh, nullptr, stream);
+        h->tvl1_async = was_async;
+        RC(rc);
+        if (nready != B) HIPCHK(h, launch_stream_scatter(st.u, st.flows, ready.data(), nready, 1 + fut, B, (int64_t)hw, s));
+        flow_prev = st.flows;
+        flow_next = fut ? st.flows + (size_t)B * 2 * hw : nullptr;
+    }
+    if (!fresh.empty()) {
+        std::vector<uint8_t> mask((size_t)B, 0);
+        for (int b : fresh) mask[(size_t)b] = 1;
+        RC(rvdd_reset_slots(h, mask.data()));
+    }
+    return rvdd_step_strided(h, packed_at(pp), packed_at(pc), fut ? packed_at(pos) : nullptr, flow_prev, flow_next, 0, 0, out_rgb, stream);
 }
 
 int rvdd_profile_enable(rvdd_t* h, int32_t on) {

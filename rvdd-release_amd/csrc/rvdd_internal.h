@@ -344,6 +344,18 @@ hipError_t launch_ppipe(const float* img, int n, int H, int W, int64_t sn, int64
 size_t srgb_metrics_workspace(int n, int H, int W);
 hipError_t launch_srgb_metrics(const uint8_t* a, const uint8_t* b, int n, int H, int W, void* ws, hipStream_t s);
 
+// ingest.hip -- sensor frames to the inputs of a step and of TV-L1 (rvdd_ingest_raw), and rvdd_video_push's two copy kernels
+// frames: n frames, dtype 0 = u16 / 1 = f32, layout 0 = mosaic [n][2hh][2ww] / 1 = packed HWC [n][hh][ww][4];
+// packed [n][4][hh][ww] = 2 * (dn / (2^bit_depth - 1)) - 1, gray [n][hh][ww] = (((c0 + c1) + c2) + c3) * 0.25 in DN; either nullable
+hipError_t launch_ingest_raw(const void* frames, int dtype, int layout, int n, int hh, int ww, int bit_depth, float* packed, float* gray,
+                             hipStream_t s);
+// the flow batch of a push: I0 / I1 [npairs][hw] from the gray planes [B][hw] of the ring positions of the centre, previous and
+// next (nullable: no future frame) frames -- pair q < nready = (centre, previous) of slots[q], pair nready + q = (centre, next)
+hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const float* gray_n, float* I0, float* I1, const int* slots,
+                                int nready, int B, int64_t hw, hipStream_t s);
+// flows [ndir][B][2][hw] of the step from the batch's u [ndir * nready][2][hw]: zero for the slots that are not ready (B <= 64)
+hipError_t launch_stream_scatter(const float* u, float* flows, const int* slots, int nready, int ndir, int B, int64_t hw, hipStream_t s);
+
 // ------------------------------------------------------------------ TV-L1 --
 struct Tvl1Workspace;
 hipError_t tvl1_alloc(Tvl1Workspace** out, int nx, int ny);

@@ -1,0 +1,156 @@
+"""Denoise raw footage: `python -m rvdd_release_amd.denoise --dataroot D --nFolder noisy --results_dir R <model flags>`.
+
+Reads `<dataroot>/<nFolder>/<video>/<frame>.tif` (`--dataset_mode rawvideo`: sensor frames as 1-channel mosaics or
+4-channel packed frames, uint16 or float32; no ground truth, no flow folder) and writes, for every frame the reference's
+test-time dataset yields (frames 1 .. N-1-future of a video of N frames),
+
+    <results_dir>/<video>/<frame>_denoised.tif
+
+-- the float32 [H,W,3] image `validate.py` writes for that frame (`util.visualizer.save_images`).  Everything between
+the file and the output frame runs on the device (`RvddRuntime.video_push`: ingest, TV-L1 flows, the frame-step).
+
+The model flags are the reference's (`--netDenoiser --path2epoch / --checkpoints_dir --feature_rec --future_patch_depth
+--no_warp --warp_raw --prev_noisy_frame --bayer_pattern --bit_depth --patch_depth --gpu_ids`; `options.parse`).  Beside them:
+  --results_dir DIR   where the frames go (default ./results)
+  --batch_size B      B videos advance in lockstep: the videos are dealt to B slots in order, a slot whose video ended
+                      takes the next unstarted one, or idles when none is left (`deal_slots`).  Same files, same bytes.
+  --srgb ISO,n,red_gain,blue_gain   also write <frame>_srgb.png: the display image of dataset/fwd_ppipe.py for that ISO and
+                      white balance (rgb_gain = 1/n), `rvdd_ppipe` on the network output.
+Videos of different frame sizes are grouped by size and run one group after the other, one runtime per size.
+"""
+from __future__ import annotations
+
+import argparse
+import copy
+import os
+import time
+from typing import List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .runtime import BAYER_PATTERNS, raw_frames_to_device
+
+NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
+
+
+def deal_slots(lengths: Sequence[int], slots: int) -> List[List[Tuple[int, int, int]]]:
+    """The pushes of videos of `lengths` frames on `slots` batch slots: a list of steps, each a list of one
+    (ctl, video, frame) per slot.  The videos are dealt in order; a slot whose video ended takes the next unstarted
+    video (FIRST on its frame 0), or goes IDLE -- (IDLE, -1, -1) -- when none is left; the list ends with the last step
+    that carries a frame.  Every frame of every video appears once, in order, and NEXT never follows IDLE."""
+    if slots < 1:
+        raise ValueError("deal_slots: at least one slot")
+    if any(n < 1 for n in lengths):
+        raise ValueError("deal_slots: a video has at least one frame")
+    nxt = 0                                   # the next unstarted video
+    cur = [(-1, 0)] * slots                   # per slot: (video, frames already pushed)
+    steps = []
+    while True:
+        step = []
+        for b in range(slots):
+            v, k = cur[b]
+            if v >= 0 and k < lengths[v]:
+                step.append((NEXT, v, k))
+                cur[b] = (v, k + 1)
+            elif nxt < len(lengths):
+                step.append((FIRST, nxt, 0))
+                cur[b] = (nxt, 1)
+                nxt += 1
+            else:
+                step.append((IDLE, -1, -1))
+                cur[b] = (-1, 0)
+        if all(c == IDLE for c, _, _ in step):
+            return steps
+        steps.append(step)
+
+
+def _parse(argv):
+    from .options import parse
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument('--results_dir', type=str, default='./results')
+    p.add_argument('--srgb', type=str, default=None, help='ISO,n,red_gain,blue_gain: also write <frame>_srgb.png')
+    own, rest = p.parse_known_args(argv)
+    opt = parse(rest)
+    opt.results_dir, opt.srgb = own.results_dir, own.srgb
+    if not any(a == '--dataset_mode' or a.startswith('--dataset_mode=') for a in rest):
+        opt.dataset_mode = 'rawvideo'
+    if opt.srgb is not None:
+        f = opt.srgb.split(',')
+        if len(f) != 4:
+            raise SystemExit("--srgb takes ISO,n,red_gain,blue_gain")
+        opt.srgb = (int(f[0]), float(f[1]), float(f[2]), float(f[3]))
+    return opt
+
+
+def _frame_size(dataset, path):
+    a = dataset.read_frame(path)
+    return (a.shape[0], a.shape[1]) if dataset.layout == "mosaic" else (2 * a.shape[0], 2 * a.shape[1])
+
+
+def main(argv=None) -> dict:
+    from .data import create_dataset
+    from .library import iio_write
+    from .models import create_model
+    from .util.visualizer import save_images
+    opt = _parse(argv)
+    v = copy.deepcopy(opt)
+    v.max_dataset_size, v.num_threads, v.batch_size, v.serial_batches = float("inf"), 0, 1, True
+    dataset = create_dataset(v).dataset
+    if not hasattr(dataset, "read_frame"):
+        raise SystemExit("denoise reads --dataset_mode rawvideo")
+    model = create_model(opt)
+    model.setup(opt)
+    net, dev = model._netDenoise, model.device
+    fut = int(opt.future_patch_depth)
+
+    groups = {}                                   # frame size -> its videos, in dataset order
+    for key, frames in dataset.videos:
+        groups.setdefault(_frame_size(dataset, frames[0]), []).append((key, frames))
+    written = 0
+    t0 = time.time()
+    for (H, W), videos in groups.items():
+        B = max(1, min(int(opt.batch_size), len(videos)))
+        rt = net.runtime_for(B, H, W, pin=True)
+        rt.set_option("no_warp", int(bool(opt.no_warp)))
+        rt.set_option("prev_noisy_frame", int(bool(opt.prev_noisy_frame)))
+        rt.set_option("warp_raw", int(bool(opt.warp_raw)))
+        rt.set_option("bayer_pattern", BAYER_PATTERNS.index(opt.bayer_pattern))
+        rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
+        shape = (B, H, W) if dataset.layout == "mosaic" else (B, H // 2, W // 2, 4)
+        out = None
+        for step in deal_slots([len(f) for _, f in videos], B):
+            batch = np.zeros(shape, dtype=dataset.dtype)
+            for b, (c, vid, k) in enumerate(step):
+                if c != IDLE:
+                    batch[b] = dataset.read_frame(videos[vid][1][k])
+            out, valid = rt.video_push(raw_frames_to_device(batch, dev), [c for c, _, _ in step], int(opt.bit_depth),
+                                       dataset.layout, out)
+            ended = False
+            for b, (c, vid, k) in enumerate(step):
+                if c == IDLE:
+                    continue
+                key, frames = videos[vid]
+                ended = ended or k == len(frames) - 1
+                if not valid[b]:
+                    continue
+                path = frames[k - fut]                  # the centre frame
+                save_images(opt.results_dir, {'denoised': out[b:b + 1]}, [os.path.basename(path)], subfolder=key)
+                if opt.srgb is not None:
+                    iso, n, red, blue = opt.srgb
+                    png = rt.ppipe(out[b:b + 1], 1.0 / n, red, blue, iso, _lib.PPIPE_FROM_NET, "nchw")
+                    stem = os.path.splitext(os.path.basename(path))[0]
+                    iio_write(png[0].cpu().numpy(), os.path.join(opt.results_dir, key, stem + '_srgb.png'))
+                written += 1
+            if ended:
+                rt.set_option("tvl1_async", 0)          # synchronises: reports a TV-L1 exchange of this video's pushes that gave up
+        rt.set_option("tvl1_async", 0)
+    torch.cuda.synchronize(dev)
+    dt = time.time() - t0
+    print('(denoise, %d frames, %.3f s, %.2f frames/s)' % (written, dt, written / max(dt, 1e-9)))
+    return {'frames': written, 'seconds': dt, 'fps': written / max(dt, 1e-9)}
+
+
+if __name__ == '__main__':
+    main()

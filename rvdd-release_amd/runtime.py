@@ -24,6 +24,51 @@ ARCH_BY_NAME = {
 BAYER_PATTERNS = ("gbrg", "grbg", "rggb", "bggr")
 
 
+# enum rvdd_raw_layout by name (rvdd_ingest_raw, rvdd_video_push)
+RAW_LAYOUTS = {"mosaic": _lib.RAW_MOSAIC, "packed_hwc": _lib.RAW_PACKED_HWC}
+
+
+def raw_frames_to_device(frames, device) -> torch.Tensor:
+    """Host sensor frames (a numpy array or CPU tensor of uint16 / int16 / float32) -> a tensor on `device` that
+    `ingest_raw` / `video_push` accept.  uint16 arrays travel as their int16 view: the bytes are what crosses the ABI."""
+    import numpy as np
+    if not torch.is_tensor(frames):
+        a = np.ascontiguousarray(frames)
+        if a.dtype == np.uint16:
+            a = a.view(np.int16)
+        elif a.dtype not in (np.int16, np.float32):
+            raise RuntimeError(f"raw frames must be uint16 or float32, got {a.dtype}")
+        frames = torch.from_numpy(a)
+    return frames.to(device)
+
+
+def _raw_frames(t: torch.Tensor, layout: str, name: str, device: int):
+    """-> (contiguous tensor, enum rvdd_raw_dtype, enum rvdd_raw_layout, n, hh, ww) of sensor frames [n,2hh,2ww] ("mosaic")
+    or [n,hh,ww,4] ("packed_hwc").  Accepted dtypes: torch.uint16, torch.int16 (read as the same 16 bits, unsigned: the
+    view numpy's uint16 arrays upload as where torch's own uint16 support is thin) and torch.float32."""
+    if layout not in RAW_LAYOUTS:
+        raise ValueError(f"{name}: layout {layout!r} is not one of {', '.join(RAW_LAYOUTS)}")
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{name}: frames must be a GPU tensor (rvdd has no CPU path)")
+    if t.device.index != device:
+        raise RuntimeError(f"{name}: frames live on cuda:{t.device.index} but this runtime drives cuda:{device}")
+    if t.dtype == torch.float32:
+        dtype = _lib.RAW_F32
+    elif t.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        dtype = _lib.RAW_U16
+    else:
+        raise RuntimeError(f"{name}: frames must be uint16 (or its int16 view) or float32, got {t.dtype}")
+    if layout == "mosaic":
+        if t.dim() != 3 or t.shape[1] % 2 or t.shape[2] % 2:
+            raise RuntimeError(f"{name}: mosaic frames are [n,2hh,2ww], got {tuple(t.shape)}")
+        n, hh, ww = t.shape[0], t.shape[1] // 2, t.shape[2] // 2
+    else:
+        if t.dim() != 4 or t.shape[3] != 4:
+            raise RuntimeError(f"{name}: packed_hwc frames are [n,hh,ww,4], got {tuple(t.shape)}")
+        n, hh, ww = t.shape[0], t.shape[1], t.shape[2]
+    return (t if t.is_contiguous() else t.contiguous()), dtype, RAW_LAYOUTS[layout], n, hh, ww
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -189,6 +234,46 @@ class RvddRuntime:
                                                _ptr(flows[0][0]), _ptr(flows[1][0]), rstride, fstride, _ptr(out),
                                                self._stream()), "rvdd_step")
         return out
+
+    # -- raw footage ----------------------------------------------------------
+    def ingest_raw(self, frames: torch.Tensor, bit_depth: int = 12, layout: str = "mosaic", want_packed: bool = True,
+                   want_gray: bool = True):
+        """Sensor frames -> (packed [n,4,hh,ww] in [-1,1], gray [n,hh,ww] in DN), None for an output not wanted
+        (rvdd_ingest_raw).  frames: [n,2hh,2ww] ("mosaic") or [n,hh,ww,4] ("packed_hwc") GPU tensor of torch.uint16,
+        torch.int16 (the same 16 bits, read unsigned) or torch.float32 digital numbers."""
+        t, dtype, lay, n, hh, ww = _raw_frames(frames, layout, "ingest_raw", self.device)
+        packed = torch.empty(n, 4, hh, ww, dtype=torch.float32, device=self._tdev) if want_packed else None
+        gray = torch.empty(n, hh, ww, dtype=torch.float32, device=self._tdev) if want_gray else None
+        self._check(self.lib.rvdd_ingest_raw(self.h, _ptr(t), dtype, lay, n, hh, ww, int(bit_depth), _ptr(packed), _ptr(gray),
+                                             self._stream()), "rvdd_ingest_raw")
+        return packed, gray
+
+    def video_push(self, frames: torch.Tensor, ctl=None, bit_depth: int = 12, layout: str = "mosaic", out=None):
+        """Every slot's next sensor frame in, at most one denoised frame per slot out (rvdd_video_push).
+        frames: [B,2hh,2ww] / [B,hh,ww,4] as `ingest_raw` takes them; ctl: None (every slot continues its video) or B
+        values of _lib.PUSH_NEXT / PUSH_FIRST / PUSH_IDLE.  -> (out [B,3,H,W], valid: B bools); out[b] is the denoised
+        centre frame of slot b where valid[b], unspecified elsewhere.  Nothing is synchronised."""
+        t, dtype, lay, n, hh, ww = _raw_frames(frames, layout, "video_push", self.device)
+        B, H, W = self.B, self.H, self.W
+        if (n, 2 * hh, 2 * ww) != (B, H, W):
+            raise RuntimeError(f"video_push: frames of {n} x {2 * hh} x {2 * ww} sites for a runtime of {B} slots of {H} x {W}")
+        c = None
+        if ctl is not None:
+            items = [int(v) for v in (ctl.tolist() if hasattr(ctl, "tolist") else ctl)]
+            if len(items) != B:
+                raise ValueError(f"video_push: ctl needs {B} entries, got {len(items)}")
+            if any(not 0 <= v <= 255 for v in items):
+                raise ValueError("video_push: ctl entries are PUSH_NEXT (0), PUSH_FIRST (1) or PUSH_IDLE (2)")
+            c = (C.c_uint8 * B)(*items)
+        if out is None:
+            out = torch.empty(B, 3, H, W, dtype=torch.float32, device=self._tdev)
+        else:
+            _chk_dev(out, (B, 3, H, W), "out", self.device)
+            assert out.is_contiguous()
+        valid = (C.c_uint8 * B)()
+        self._check(self.lib.rvdd_video_push(self.h, _ptr(t), dtype, lay, int(bit_depth), c, _ptr(out), valid, self._stream()),
+                    "rvdd_video_push")
+        return out, [bool(v) for v in valid]
 
     def get_state(self, want_feat: bool = True):
         B, H, W = self.B, self.H, self.W
