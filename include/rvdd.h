@@ -263,6 +263,19 @@ int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
                     int32_t bit_depth, float* packed /* [n,4,hh,ww], nullable */, float* gray /* [n,hh,ww], nullable */,
                     void* stream);
 
+/* The gray plane TV-L1 reads, of an RGB frame's re-mosaic: what rvdd_ingest_raw's `gray` would be for the sensor frame whose
+ * demosaic is `rgb`.  For each 2x2 cell (y, x) and CFA position k = 0..3 in the packing of enum rvdd_bayer,
+ *   v_k  = rgb[colour of `pattern` at k][2y + (k >> 1)][2x + (k & 1)]     (HamiltonAdam(pattern).remosaick: the inverse of the packing)
+ *   dn_k = ((v_k + 1.0f) * 0.5f) * (float)(2^bit_depth - 1)
+ *   gray = (((dn_0 + dn_1) + dn_2) + dn_3) * 0.25f
+ * every operation rounded to f32 on its own.  The result is in digital numbers, the unit of rvdd_ingest_raw's gray plane: TV-L1
+ * normalises a pair with one joint minimum and maximum, so the two images of a pair must share a scale.
+ *   rgb [n,3,H,W] in [-1,1] (values outside are not clamped); gray [n,H/2,W/2].
+ * pattern 0..3, bit_depth 1..16, H and W even: RVDD_ERR_ARG otherwise (the message names the argument).  n = 0 does nothing.
+ * `rgb` and `gray` 16-byte aligned with (W/2) % 4 == 0 takes the wide form (16-byte accesses); same bits either way. */
+int rvdd_gray_of_rgb(rvdd_t* h, const float* rgb /* [n,3,H,W] in [-1,1] */, int32_t n, int32_t H, int32_t W,
+                     int32_t pattern /* enum rvdd_bayer */, int32_t bit_depth, float* gray /* [n,H/2,W/2] */, void* stream);
+
 enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
 
 /* The stream: one call hands every batch slot its next sensor frame (`frames`: cfg.batch frames of H/2 x W/2 cells, one
@@ -279,7 +292,7 @@ enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
  *       out_rgb[b] of a slot that is not ready is unspecified.
  * The handle keeps the last 2 + future ingested frames of every slot (packed and gray) on the device: allocated by the
  * first push, freed with the handle (20 (2 + future) + 24 (1 + future) bytes per raw cell and slot with the flow batch's
- * buffers).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
+ * buffers; 4 more with option "stream_flow_from_denoised", allocated by the first push that has it on).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
  * I1 = gray[previous]) and, with a future frame, (gray[centre], gray[next]) for all of them in ONE batch call in the form of
  * option "tvl1_async" 1 (whatever the option says), then one rvdd_step_strided on the kept packed frames and those flows.  A
  * slot's first ready push carries its reset mark (rvdd_reset_slots; raw_prev = its oldest frame), so every output is bit for
@@ -386,6 +399,16 @@ int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, 
  *   "stream_reset_each": 1 = every step of rvdd_video_push carries the reset mark of every ready slot: non-recurrent checkpoints
  *               (--patch_depth 2, the model's training_unrollings == 1: recurrentModel.forward resets before every step,
  *               models/recurrent_model.py:233-245).  Default 0.  Acts on rvdd_video_push only.  Per handle.
+ *   "stream_flow_from_denoised": 1 = --val_flow_from_denoised (validate.py:16-38, 81-82) in rvdd_video_push: after its frame-step a push
+ *               takes rvdd_gray_of_rgb of the out_rgb it has just written (the handle's "bayer_pattern", the push's bit_depth) into a
+ *               plane per slot, and the NEXT push forms the pair towards the previous frame of every ready slot whose previous push
+ *               gave an output of the same video as (I0 = gray[centre], I1 = that plane) instead of (gray[centre], gray[previous]).
+ *               A slot's first ready push keeps the noisy pair (the reference's first frame keeps the dataset's flow), and so does
+ *               the pair towards the next frame: no output exists for that frame yet.  With "stream_reset_each" it applies all the
+ *               same (the reference skips the online flow on FirstOfVideo only); with "no_warp" it changes nothing.  The plane is
+ *               taken from out_rgb inside the push that wrote it, so the caller may overwrite out_rgb between pushes.  Still one
+ *               asynchronous rvdd_tvl1flow_batch per push.  Default 0: exactly the launches of a push without it.  Acts on
+ *               rvdd_video_push only.  Per handle.
  * Unknown names are an error. */
 int rvdd_set_option(rvdd_t* h, const char* name, int32_t value);
 

@@ -55,6 +55,7 @@ _PROTOS = {
     "rvdd_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "rvdd_tvl1flow_batch": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P]),
     "rvdd_ingest_raw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "rvdd_gray_of_rgb": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_ppipe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                              C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P]),

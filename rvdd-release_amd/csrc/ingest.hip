@@ -1,4 +1,5 @@
-// Sensor frames -> the inputs of a frame-step (packed raw in [-1, 1]) and of TV-L1 (gray plane in DN), and the two small
+// Sensor frames -> the inputs of a frame-step (packed raw in [-1, 1]) and of TV-L1 (gray plane in DN), the same gray plane of
+// an output frame's re-mosaic (rvdd_gray_of_rgb), and the two small
 // copy kernels rvdd_video_push composes its flow batch with.  Compiled -ffp-contract=off: every operation below is rounded
 // to f32 on its own, which is what makes the outputs the bits of the reference's loader (library.py load_image + the
 // dataset's transform) and of library._gray on integer-valued frames.
@@ -133,6 +134,49 @@ hipError_t launch_ingest_t(const T* frames, int n, int hh, int ww, float maxv, f
     return hipGetLastError();
 }
 
+// ---- rvdd_gray_of_rgb: the gray plane (DN) of an RGB frame's re-mosaic ---------------------------------------------------
+// HamiltonAdam(pattern).remosaick picks, at CFA position k = (k >> 1, k & 1) of a 2x2 cell, the colour the pattern has there;
+// `cols` carries those four plane indices, two bits each.  Per cell: dn_k = ((v_k + 1) * 0.5) * top, then ingest's gray_dn.
+// Of the six plane-rows of a pair of pixel rows four are read (one colour per position), half of each used.  The wide form
+// gives a thread four neighbouring cells of a cell row: 2 x 16 B from each of the four plane-rows, one 16-B store.
+__device__ __forceinline__ float dn_of(float v, float top) { return ((v + 1.0f) * 0.5f) * top; }
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) gray_of_rgb_kernel(const float* __restrict__ rgb, float* __restrict__ gray, int n, int hh, int ww,
+                                                          int cols, float top) {
+    const int64_t W = 2 * (int64_t)ww, HW = 2 * (int64_t)hh * W;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    constexpr int NC = VEC ? 4 : 1;                  // cells per thread
+    const int wq = ww / NC;
+    if (t >= (int64_t)n * hh * wq) return;
+    const int x = NC * (int)(t % wq);
+    const int64_t row = t / wq;                      // img * hh + y
+    const int y = (int)(row % hh);
+    const int64_t img = row / hh;
+    float c[NC][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float* p = rgb + (img * 3 + ((cols >> (2 * k)) & 3)) * HW + (2 * (int64_t)y + (k >> 1)) * W + 2 * x + (k & 1);
+        if constexpr (VEC) {
+            const float* a = p - (k & 1);            // the 16-B aligned run of eight pixels; position k takes its even / odd ones
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(a), v1 = *reinterpret_cast<const f32x4*>(a + 4);
+            c[0][k] = dn_of(v0[k & 1], top); c[1][k] = dn_of(v0[2 + (k & 1)], top);
+            c[2][k] = dn_of(v1[k & 1], top); c[3][k] = dn_of(v1[2 + (k & 1)], top);
+        } else {
+            c[0][k] = dn_of(p[0], top);
+        }
+    }
+    float* g = gray + img * hh * ww + (int64_t)y * ww + x;
+    if constexpr (VEC) {
+        f32x4 v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = gray_dn(c[i]);
+        *reinterpret_cast<f32x4*>(g) = v;
+    } else {
+        g[0] = gray_dn(c[0]);
+    }
+}
+
 // ---- rvdd_video_push: the flow batch's operands and results ------------------------------------------------------------
 // The ready slots of a push, one byte each (B <= 64 on a partial set; the full set needs no list)
 struct SlotList {
@@ -142,15 +186,19 @@ struct SlotList {
 // (V = f32x4 where a plane is a whole number of 16-B vectors, float otherwise; hw4 / hw2_4 count V's)
 // I0[q] / I1[q], q < npairs: pair q < nready = (centre, previous) of ready slot q, pair nready + q = (centre, next).
 // gray_c / gray_p / gray_n: the [B][hw] planes of the ring positions that hold the centre, previous and next frames.
+// dgray [B][hw]: the gray planes of the slots' previous OUTPUTS; slot b's pair towards the previous frame is matched against
+// it where bit b of from_den is set (option "stream_flow_from_denoised"), against gray_p elsewhere.
 template <typename V>
 __global__ void __launch_bounds__(256) stream_gather_kernel(const float* __restrict__ gray_c, const float* __restrict__ gray_p,
-                                                            const float* __restrict__ gray_n, float* __restrict__ I0, float* __restrict__ I1,
-                                                            SlotList sl, int nready, int all, int64_t hw4) {
+                                                            const float* __restrict__ gray_n, const float* __restrict__ dgray,
+                                                            float* __restrict__ I0, float* __restrict__ I1, SlotList sl, int nready, int all,
+                                                            uint64_t from_den, int64_t hw4) {
     const int q = blockIdx.y;
     const int r = q < nready ? q : q - nready;
     const int b = all ? r : sl.slot[r];
     const V* c = reinterpret_cast<const V*>(gray_c) + (int64_t)b * hw4;
-    const V* o = reinterpret_cast<const V*>(q < nready ? gray_p : gray_n) + (int64_t)b * hw4;
+    const float* other = q >= nready ? gray_n : ((from_den >> b) & 1) ? dgray : gray_p;
+    const V* o = reinterpret_cast<const V*>(other) + (int64_t)b * hw4;
     V* d0 = reinterpret_cast<V*>(I0) + (int64_t)q * hw4;
     V* d1 = reinterpret_cast<V*>(I1) + (int64_t)q * hw4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -188,23 +236,45 @@ hipError_t launch_ingest_raw(const void* frames, int dtype, int layout, int n, i
     return layout == 0 ? launch_ingest_t<float, 0>(f, n, hh, ww, maxv, packed, gray, s) : launch_ingest_t<float, 1>(f, n, hh, ww, maxv, packed, gray, s);
 }
 
+hipError_t launch_gray_of_rgb(const float* rgb, int n, int hh, int ww, int bayer, int bit_depth, float* gray, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    // RGB plane of each GBRG site -- G(e,e), B(e,o), R(o,e), G(o,o) -- and the phase (py << 1) | px of the pattern: CFA position k
+    // of the pattern is the GBRG site k ^ phase (prestage.hip's bayer_phase)
+    constexpr int gbrg[4] = {1, 2, 0, 1}, phase[4] = {0, 3, 2, 1};
+    if (bayer < 0 || bayer > 3) return hipErrorInvalidValue;
+    int cols = 0;
+    for (int k = 0; k < 4; ++k) cols |= gbrg[k ^ phase[bayer]] << (2 * k);
+    const float top = (float)((1u << bit_depth) - 1u);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(gray);
+    const bool vec = (ww & 3) == 0 && (al & 15) == 0;
+    const int64_t work = vec ? (int64_t)n * hh * (ww >> 2) : (int64_t)n * hh * ww;
+    const int64_t blocks = (work + 255) / 256;
+    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    if (vec)
+        hipLaunchKernelGGL(gray_of_rgb_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, rgb, gray, n, hh, ww, cols, top);
+    else
+        hipLaunchKernelGGL(gray_of_rgb_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, rgb, gray, n, hh, ww, cols, top);
+    return hipGetLastError();
+}
+
 // planes of the handle's own buffers (hipMalloc alignment); slots: the ready slots in order (ignored when nready == B)
-hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const float* gray_n, float* I0, float* I1, const int* slots,
-                                int nready, int B, int64_t hw, hipStream_t s) {
+hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const float* gray_n, const float* dgray, uint64_t from_den,
+                                float* I0, float* I1, const int* slots, int nready, int B, int64_t hw, hipStream_t s) {
     SlotList sl{};
     const int all = nready == B;
-    if (!all) {
-        if (nready > 64) return hipErrorInvalidValue;
+    if (B > 64 || (from_den && !dgray)) return hipErrorInvalidValue;      // one bit, one byte per slot
+    if (!all)
         for (int q = 0; q < nready; ++q) sl.slot[q] = (unsigned char)slots[q];
-    }
     const int npairs = nready * (gray_n ? 2 : 1);
     const bool vec = (hw & 3) == 0;
     const int64_t hw4 = vec ? hw / 4 : hw;
     const int gx = (int)((hw4 + 255) / 256 < 256 ? (hw4 + 255) / 256 : 256);
     if (vec)
-        hipLaunchKernelGGL(stream_gather_kernel<f32x4>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, I0, I1, sl, nready, all, hw4);
+        hipLaunchKernelGGL(stream_gather_kernel<f32x4>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, dgray, I0, I1, sl, nready, all,
+                           from_den, hw4);
     else
-        hipLaunchKernelGGL(stream_gather_kernel<float>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, I0, I1, sl, nready, all, hw4);
+        hipLaunchKernelGGL(stream_gather_kernel<float>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, dgray, I0, I1, sl, nready, all,
+                           from_den, hw4);
     return hipGetLastError();
 }
 

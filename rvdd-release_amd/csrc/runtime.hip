@@ -214,8 +214,12 @@ struct rvdd_handle {
         uint64_t pushes = 0;
         std::vector<int> count;      // per slot: frames of its video pushed in a row (0: never started, or idle on the last push)
         std::vector<uint8_t> was_idle;
+        float* dgray = nullptr;      // [B][hh][ww]: gray plane of every slot's last output (option "stream_flow_from_denoised"; allocated by
+                                     // the first push that has the option on)
+        std::vector<uint8_t> dgray_ok;   // per slot: dgray holds the output of the push before this one
     } st;
     bool stream_reset_each = false;  // option "stream_reset_each": every ready step of rvdd_video_push carries the reset mark of every ready slot
+    bool stream_flow_from_denoised = false;  // option "stream_flow_from_denoised": the flow towards the previous frame is matched against the previous output
 
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
@@ -1259,6 +1263,12 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         h->stream_reset_each = value != 0;
         return RVDD_OK;
     }
+    if (std::strcmp(name, "stream_flow_from_denoised") == 0) {
+        // 1 = --val_flow_from_denoised in rvdd_video_push: a slot's flow towards the previous frame is matched against the gray
+        // plane of its previous output (from the second output of a video on)
+        h->stream_flow_from_denoised = value != 0;
+        return RVDD_OK;
+    }
     if (std::strcmp(name, "fuse_pre") == 0) {
         // 0 = preprocessing_layer and EncoderConvs[0][0] as the two convs they are, instead of their composition (the A/B
         // reference: same map up to fp32 rounding of a different summation order)
@@ -1298,7 +1308,7 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         h->split16 = value == 0;
         return RVDD_OK;
     }
-    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, cout_split, small_prestage, bayer_pattern, stream_reset_each)", name);
+    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, cout_split, small_prestage, bayer_pattern, stream_reset_each, stream_flow_from_denoised)", name);
 }
 
 int rvdd_reset(rvdd_t* h) {
@@ -1934,6 +1944,22 @@ int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
     return RVDD_OK;
 }
 
+int rvdd_gray_of_rgb(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t W, int32_t pattern, int32_t bit_depth, float* gray,
+                     void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
+        return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: bit_depth must be 1..16, got %d", bit_depth);
+    if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: H must be even and >= 2, got %d", H);
+    if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: W must be even and >= 2, got %d", W);
+    if (n == 0) return RVDD_OK;
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: n must be >= 0, got %d", n);
+    if (!rgb || !gray) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: rgb and gray are required");
+    ENTER(h);
+    HIPCHK(h, launch_gray_of_rgb(rgb, n, H / 2, W / 2, pattern, bit_depth, gray, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t bit_depth, const uint8_t* ctl, float* out_rgb,
                     uint8_t* valid, void* stream) {
     if (!h) return RVDD_ERR_ARG;
@@ -1958,6 +1984,7 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
         const int depth = 2 + fut, nd = 1 + fut;
         st.count.assign((size_t)B, 0);
         st.was_idle.assign((size_t)B, 0);
+        st.dgray_ok.assign((size_t)B, 0);
         float *pk = nullptr, *gr = nullptr;
         RC(dmalloc(h, reinterpret_cast<void**>(&gr), (size_t)depth * B * hw * sizeof(float)));
         RC(dmalloc(h, reinterpret_cast<void**>(&st.I0), (size_t)nd * B * hw * sizeof(float)));
@@ -1970,6 +1997,9 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
         st.pushes = 0;
         st.packed = pk;      // last: the mark of a complete allocation
     }
+    // option "stream_flow_from_denoised": the gray planes of the outputs, allocated by the first push that has it on
+    const bool from_den = h->stream_flow_from_denoised && !h->no_warp;
+    if (from_den && !st.dgray) RC(dmalloc(h, reinterpret_cast<void**>(&st.dgray), (size_t)B * hw * sizeof(float)));
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
         if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
@@ -1988,6 +2018,7 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
         b = e;
     }
     std::vector<int> ready, fresh;
+    uint64_t den_slots = 0;      // ready slots whose previous push gave an output of the same video, its gray plane in dgray
     for (int b = 0; b < B; ++b) {
         const int c = ctl ? ctl[b] : RVDD_PUSH_NEXT;
         int& n = st.count[(size_t)b];
@@ -1996,6 +2027,8 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
         valid[b] = n >= st.depth;
         if (n >= st.depth) ready.push_back(b);
         if (n == st.depth || (h->stream_reset_each && n >= st.depth)) fresh.push_back(b);
+        if (from_den && n > st.depth && st.dgray_ok[(size_t)b]) den_slots |= 1ull << b;
+        st.dgray_ok[(size_t)b] = 0;
     }
     st.pushes++;
     if (ready.empty()) return RVDD_OK;
@@ -2006,7 +2039,8 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
     auto gray_at = [&](int p) { return st.gray + (size_t)p * B * hw; };
     const float *flow_prev = nullptr, *flow_next = nullptr;
     if (!h->no_warp) {
-        HIPCHK(h, launch_stream_gather(gray_at(pc), gray_at(pp), fut ? gray_at(pos) : nullptr, st.I0, st.I1, ready.data(), nready, B, (int64_t)hw, s));
+        HIPCHK(h, launch_stream_gather(gray_at(pc), gray_at(pp), fut ? gray_at(pos) : nullptr, st.dgray, den_slots, st.I0, st.I1, ready.data(), nready, B,
+                                       (int64_t)hw, s));
         float* u = nready == B ? st.flows : st.u;      // every slot ready: the batch writes the step's flows itself
         const bool was_async = h->tvl1_async;
         h->tvl1_async = true;
@@ -2022,7 +2056,14 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
         for (int b : fresh) mask[(size_t)b] = 1;
         RC(rvdd_reset_slots(h, mask.data()));
     }
-    return rvdd_step_strided(h, packed_at(pp), packed_at(pc), fut ? packed_at(pos) : nullptr, flow_prev, flow_next, 0, 0, out_rgb, stream);
+    RC(rvdd_step_strided(h, packed_at(pp), packed_at(pc), fut ? packed_at(pos) : nullptr, flow_prev, flow_next, 0, 0, out_rgb, stream));
+    if (from_den) {
+        // the plane is taken from the output (with "prev_noisy_frame" lastden holds the noisy demosaic) inside the push that wrote it:
+        // the caller may overwrite out_rgb before the next one
+        HIPCHK(h, launch_gray_of_rgb(out_rgb, B, hh, ww, h->bayer, bit_depth, st.dgray, s));
+        for (int b : ready) st.dgray_ok[(size_t)b] = 1;
+    }
+    return RVDD_OK;
 }
 
 int rvdd_profile_enable(rvdd_t* h, int32_t on) {

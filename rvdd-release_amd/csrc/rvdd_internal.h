@@ -349,10 +349,14 @@ hipError_t launch_srgb_metrics(const uint8_t* a, const uint8_t* b, int n, int H,
 // packed [n][4][hh][ww] = 2 * (dn / (2^bit_depth - 1)) - 1, gray [n][hh][ww] = (((c0 + c1) + c2) + c3) * 0.25 in DN; either nullable
 hipError_t launch_ingest_raw(const void* frames, int dtype, int layout, int n, int hh, int ww, int bit_depth, float* packed, float* gray,
                              hipStream_t s);
+// rgb [n][3][2hh][2ww] in [-1,1] -> gray [n][hh][ww] in DN of its re-mosaic in pattern `bayer` (enum rvdd_bayer): per cell
+// (((dn0 + dn1) + dn2) + dn3) * 0.25 with dn_k = ((v_k + 1) * 0.5) * (2^bit_depth - 1), v_k the pattern's colour at CFA position k
+hipError_t launch_gray_of_rgb(const float* rgb, int n, int hh, int ww, int bayer, int bit_depth, float* gray, hipStream_t s);
 // the flow batch of a push: I0 / I1 [npairs][hw] from the gray planes [B][hw] of the ring positions of the centre, previous and
-// next (nullable: no future frame) frames -- pair q < nready = (centre, previous) of slots[q], pair nready + q = (centre, next)
-hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const float* gray_n, float* I0, float* I1, const int* slots,
-                                int nready, int B, int64_t hw, hipStream_t s);
+// next (nullable: no future frame) frames -- pair q < nready = (centre, previous) of slots[q], pair nready + q = (centre, next).
+// A slot whose bit of from_den is set has its (centre, previous) pair matched against dgray [B][hw] instead of gray_p (B <= 64).
+hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const float* gray_n, const float* dgray, uint64_t from_den,
+                                float* I0, float* I1, const int* slots, int nready, int B, int64_t hw, hipStream_t s);
 // flows [ndir][B][2][hw] of the step from the batch's u [ndir * nready][2][hw]: zero for the slots that are not ready (B <= 64)
 hipError_t launch_stream_scatter(const float* u, float* flows, const int* slots, int nready, int ndir, int B, int64_t hw, hipStream_t s);
 

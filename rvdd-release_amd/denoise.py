@@ -10,7 +10,9 @@ test-time dataset yields (frames 1 .. N-1-future of a video of N frames),
 the file and the output frame runs on the device (`RvddRuntime.video_push`: ingest, TV-L1 flows, the frame-step).
 
 The model flags are the reference's (`--netDenoiser --path2epoch / --checkpoints_dir --feature_rec --future_patch_depth
---no_warp --warp_raw --prev_noisy_frame --bayer_pattern --bit_depth --patch_depth --gpu_ids`; `options.parse`).  Beside them:
+--no_warp --warp_raw --prev_noisy_frame --bayer_pattern --bit_depth --patch_depth --gpu_ids --val_flow_from_denoised`;
+`options.parse`).  `--val_flow_from_denoised`: from a video's second output on, the flow towards the previous frame is matched
+against the re-mosaicked previous OUTPUT instead of the previous noisy frame (option "stream_flow_from_denoised").  Beside them:
   --results_dir DIR   where the frames go (default ./results)
   --batch_size B      B videos advance in lockstep: the videos are dealt to B slots in order, a slot whose video ended
                       takes the next unstarted one, or idles when none is left (`deal_slots`).  Same files, same bytes.
@@ -118,6 +120,7 @@ def main(argv=None) -> dict:
         rt.set_option("warp_raw", int(bool(opt.warp_raw)))
         rt.set_option("bayer_pattern", BAYER_PATTERNS.index(opt.bayer_pattern))
         rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
+        rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
         shape = (B, H, W) if dataset.layout == "mosaic" else (B, H // 2, W // 2, 4)
         out = None
         for step in deal_slots([len(f) for _, f in videos], B):

@@ -182,6 +182,8 @@ class RvddRuntime:
         self._check(self.lib.rvdd_set_option(self.h, name.encode(), int(value)), "rvdd_set_option")
         if name == "no_warp":
             self.no_warp = bool(value)
+        if name == "bayer_pattern":
+            self.bayer_pattern = int(value)
 
     def move_slots(self, pairs):
         """The whole recurrent state of slot `f` replaces that of slot `t` for every (f, t) of `pairs`, one launch
@@ -247,6 +249,25 @@ class RvddRuntime:
         self._check(self.lib.rvdd_ingest_raw(self.h, _ptr(t), dtype, lay, n, hh, ww, int(bit_depth), _ptr(packed), _ptr(gray),
                                              self._stream()), "rvdd_ingest_raw")
         return packed, gray
+
+    def gray_of_rgb(self, rgb: torch.Tensor, bit_depth: int = 12, pattern: Optional[str] = None) -> torch.Tensor:
+        """[n,3,H,W] RGB in [-1,1] -> [n,H/2,W/2]: the gray plane, in DN, of its re-mosaic in `pattern` (one of BAYER_PATTERNS;
+        None = the pattern set_option("bayer_pattern", ...) gave this runtime) -- what `ingest_raw` gives for the sensor frame
+        (rvdd_gray_of_rgb)."""
+        if pattern is None:
+            pat = getattr(self, "bayer_pattern", 0)
+        elif pattern in BAYER_PATTERNS:
+            pat = BAYER_PATTERNS.index(pattern)
+        else:
+            raise ValueError(f"gray_of_rgb: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
+        if not torch.is_tensor(rgb) or rgb.dim() != 4 or rgb.shape[1] != 3:
+            raise RuntimeError(f"gray_of_rgb: rgb is [n,3,H,W], got {tuple(getattr(rgb, 'shape', ()))}")
+        n, _, H, W = rgb.shape
+        rgb = _chk_dev(rgb, rgb.shape, "rgb", self.device)
+        gray = torch.empty(n, H // 2, W // 2, dtype=torch.float32, device=self._tdev)
+        self._check(self.lib.rvdd_gray_of_rgb(self.h, _ptr(rgb), n, H, W, pat, int(bit_depth), _ptr(gray), self._stream()),
+                    "rvdd_gray_of_rgb")
+        return gray
 
     def video_push(self, frames: torch.Tensor, ctl=None, bit_depth: int = 12, layout: str = "mosaic", out=None):
         """Every slot's next sensor frame in, at most one denoised frame per slot out (rvdd_video_push).

@@ -1,0 +1,255 @@
+"""Flows from the previous denoised frame in the stream (option "stream_flow_from_denoised", --val_flow_from_denoised of the
+denoise command line): rvdd_gray_of_rgb against its numpy restatement, rvdd_video_push with the option against the existing
+entry points plus the new op, slot independence, option off against a handle that never saw it, and the command line on disk.
+Every comparison is exact."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import WEIGHTS
+from stream_den_ref import PATTERNS, compose_from_denoised, gray_of_rgb_ref
+from stream_ref import mosaic_of, quantised_dn, to_gpu
+from test_gpu_stream import FIRST, IDLE, NEXT, _runtime, _stream_alone, _tree, _video
+
+pytestmark = pytest.mark.gpu
+
+ON = {"stream_flow_from_denoised": 1}
+
+
+# ---- 1. the op against its restatement -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,W", [(36, 52), (256, 256), (720, 1280)])
+def test_gray_of_rgb_is_the_restatement(H, W):
+    from rvdd_release_amd.util._ops import ops_runtime
+    rt = ops_runtime(0)
+    rng = np.random.default_rng(H + W)
+    for n in (1, 8):
+        x = rng.uniform(-1.2, 1.2, size=(n, 3, H, W)).astype(np.float32)
+        x[0, :, :2, :2], x[-1, :, -2:, -2:] = -1.0, 1.0
+        dev = torch.from_numpy(x).cuda()
+        # the same frames one float off a 16-byte boundary: the one-cell form
+        odd = torch.cat([torch.zeros(1, device="cuda"), dev.reshape(-1)])[1:].view(n, 3, H, W)
+        assert odd.data_ptr() % 16 == 4 and dev.data_ptr() % 16 == 0
+        for pattern in PATTERNS:
+            for bit_depth in (10, 12, 14):
+                want = torch.from_numpy(gray_of_rgb_ref(x, pattern, bit_depth))
+                got = rt.gray_of_rgb(dev, bit_depth, pattern)
+                assert got.shape == (n, H // 2, W // 2) and torch.equal(got.cpu(), want), (n, pattern, bit_depth)
+                assert torch.equal(rt.gray_of_rgb(odd, bit_depth, pattern).cpu(), want), (n, pattern, bit_depth, "unaligned")
+    assert got[0, 0, 0] == 0.0 and got[-1, -1, -1] == 2.0 ** 14 - 1
+
+
+def test_gray_of_rgb_pattern_defaults_to_the_handles():
+    rt = _runtime("convunet", "recurrent-convunet-iso3200", 0, 1, 64, 96)
+    x = torch.rand(2, 3, 64, 96, device="cuda") * 2 - 1
+    assert torch.equal(rt.gray_of_rgb(x), rt.gray_of_rgb(x, 12, "gbrg"))
+    rt.set_option("bayer_pattern", 2)
+    assert torch.equal(rt.gray_of_rgb(x), rt.gray_of_rgb(x, 12, "rggb")) and not torch.equal(rt.gray_of_rgb(x), rt.gray_of_rgb(x, 12, "gbrg"))
+    with pytest.raises(ValueError, match="pattern"):
+        rt.gray_of_rgb(x, 12, "xtrans")
+
+
+def test_gray_of_rgb_bad_arguments():
+    from rvdd_release_amd.util._ops import ops_runtime
+    rt = ops_runtime(0)
+    x = torch.zeros(1, 3, 32, 32, device="cuda")
+    g = torch.full((1, 16, 16), 7.0, device="cuda")
+
+    def call(n=1, H=32, W=32, pattern=0, bit_depth=12):
+        rc = rt.lib.rvdd_gray_of_rgb(rt.h, x.data_ptr(), n, H, W, pattern, bit_depth, g.data_ptr(), None)
+        return rc, rt.lib.rvdd_last_error(rt.h)
+
+    for kw, word in (({"pattern": -1}, b"pattern"), ({"pattern": 4}, b"pattern"), ({"bit_depth": 0}, b"bit_depth"),
+                     ({"bit_depth": 17}, b"bit_depth"), ({"H": 31}, b" H "), ({"W": 31}, b" W "), ({"H": 0}, b" H "), ({"n": -1}, b" n ")):
+        rc, msg = call(**kw)
+        assert rc == -1 and msg.startswith(b"rvdd_gray_of_rgb:") and word in msg, (kw, msg)
+    assert call(n=0)[0] == 0
+    torch.cuda.synchronize()
+    assert bool((g == 7.0).all())                                         # none of these wrote anything
+    with pytest.raises(RuntimeError, match=r"\(-1\).*bit_depth"):
+        rt.gray_of_rgb(x, 0)
+    with pytest.raises(RuntimeError, match="GPU tensor"):
+        rt.gray_of_rgb(x.cpu())
+
+
+# ---- 2. the stream is the composition ------------------------------------------------------------------------------------
+CASES = [
+    ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {}),
+    ("convunet+feat", "recurrent-convunet+feat-future-iso12800", 1, {}),
+    ("next+feat", "recurrent-ConvNeXtUnet+feat-future-iso3200", 1, {}),
+    ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"bayer_pattern": 2}),
+    # the plane is the OUTPUT's: with prev_noisy_frame lastden holds the noisy demosaic, which would be another flow
+    ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"prev_noisy_frame": 1}),
+    ("convunet", "non_recurrent-convunet-iso3200", 0, {"stream_reset_each": 1}),
+    ("convunet", "recurrent-convunet-iso3200", 0, {"no_warp": 1}),
+]
+
+
+@pytest.mark.parametrize("arch,stem,future,options", CASES, ids=[f"{c[1]}-{'-'.join(c[3]) or 'plain'}" for c in CASES])
+def test_stream_from_denoised_is_the_composition(arch, stem, future, options):
+    H, W, T = 64, 96, 6
+    video = _video(T, H, W, seed=31 + future)
+    a = _runtime(arch, stem, future, 1, H, W, **options, **ON)
+    b = _runtime(arch, stem, future, 1, H, W, **{k: v for k, v in options.items() if k != "stream_reset_each"})
+    got, flags = _stream_alone(a, video, future)
+    want = compose_from_denoised(b, video, future, no_warp=bool(options.get("no_warp")), reset_each=bool(options.get("stream_reset_each")))
+    assert flags == [False] * (1 + future) + [True] * (T - 1 - future)
+    assert len(got) == len(want) == T - 1 - future
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert torch.isfinite(g).all() and torch.equal(g, w), (k, float((g - w).abs().max()))
+    a.set_option("tvl1_async", 0)            # the deferred check of the pushes' flow batches: nothing gave up
+    # against the same pushes with the option off: the first output keeps the noisy pair, the later ones do not
+    off, _ = _stream_alone(_runtime(arch, stem, future, 1, H, W, **options), video, future)
+    if options.get("no_warp"):
+        assert all(torch.equal(g, o) for g, o in zip(got, off))           # no flow is computed: nothing changes
+    else:
+        assert torch.equal(off[0], got[0]) and not torch.equal(off[-1], got[-1])
+
+
+def test_option_switched_on_mid_stream_waits_for_its_first_plane():
+    """A push can only match against a plane that the push before it formed: the first push with the option on still takes the
+    noisy pair (and forms the plane), the one after it takes the plane."""
+    H, W, T = 64, 96, 6
+    arch, stem = "convunet+feat", "recurrent-convunet+feat-iso3200"
+    video = _video(T, H, W, seed=33)
+    off, _ = _stream_alone(_runtime(arch, stem, 0, 1, H, W), video, 0)
+    rt = _runtime(arch, stem, 0, 1, H, W)
+    got = []
+    for t in range(T):
+        if t == 3:
+            rt.set_option("stream_flow_from_denoised", 1)
+        out, valid = rt.video_push(to_gpu(video[t:t + 1]), [FIRST if t == 0 else NEXT], 12, "mosaic")
+        if valid[0]:
+            got.append(out.clone())
+    assert all(torch.equal(g, o) for g, o in zip(got[:3], off[:3])) and not torch.equal(got[3], off[3])
+    # ... and that push is the composition: the recurrent state of pushes 1..3, then the flow against the output of push 3
+    ref = _runtime(arch, stem, 0, 1, H, W)
+    pg = [ref.ingest_raw(to_gpu(video[t:t + 1]), 12, "mosaic") for t in range(T)]
+    ref.reset()
+    for c in range(1, 5):
+        prev = pg[c - 1][1] if c < 4 else ref.gray_of_rgb(out_c)
+        out_c = ref.step(pg[c - 1][0], pg[c][0], None, ref.tvl1flow_batch(pg[c][1], prev), None).clone()
+    assert torch.equal(out_c, got[3])
+
+
+# ---- 3. slots stay independent -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("future", [0, 1])
+def test_slots_are_independent_from_denoised(future):
+    from rvdd_release_amd.denoise import deal_slots
+    H, W, B = 64, 96, 3
+    stem = "recurrent-convunet+feat-future-iso12800" if future else "recurrent-convunet+feat-iso3200"
+    lengths = (6, 3, 7, 4, 4)
+    videos = [_video(n, H, W, seed=40 + v) for v, n in enumerate(lengths)]
+    rt = _runtime("convunet+feat", stem, future, B, H, W, **ON)
+    got = {v: [] for v in range(len(lengths))}
+    for step in deal_slots(lengths, B):
+        batch = np.zeros((B, H, W), np.uint16)
+        for b, (c, v, k) in enumerate(step):
+            if c != IDLE:
+                batch[b] = videos[v][k]
+        out, valid = rt.video_push(to_gpu(batch), [c for c, _, _ in step], 12, "mosaic")
+        for b, (c, v, k) in enumerate(step):
+            assert valid[b] == (c != IDLE and k >= 1 + future)
+            if valid[b]:
+                got[v].append(out[b:b + 1].clone())
+        out.fill_(float("nan"))              # the caller owns out_rgb between pushes: the plane was taken inside the push
+    rt.set_option("tvl1_async", 0)
+    alone = _runtime("convunet+feat", stem, future, 1, H, W, **ON)
+    for v, n in enumerate(lengths):
+        want, _ = _stream_alone(alone, videos[v], future)
+        assert len(got[v]) == len(want) == n - 1 - future
+        for k, (g, w) in enumerate(zip(got[v], want)):
+            assert torch.equal(g, w), (v, k, float((g - w).abs().max()))
+
+
+def test_slots_are_independent_from_denoised_720p_batch_8():
+    """The launch shapes the benchmark uses: 720p, B = 8, a future frame; a FIRST mid-stream in one slot."""
+    H, W, B, future, T = 720, 1280, 8, 1, 5
+    stem = "recurrent-convunet+feat-future-iso12800"
+    videos = [_video(T, H, W, seed=50 + v, iso=12800, device="cuda") for v in range(B)]
+    short = _video(3, H, W, seed=70, iso=12800, device="cuda")
+    rt = _runtime("convunet+feat", stem, future, B, H, W, **ON)
+    got = {b: [] for b in range(B)}
+    for t in range(T + 3):
+        batch = np.zeros((B, H, W), np.uint16)
+        ctl = []
+        for b in range(B):
+            # slot 5 holds a video of three frames first, then starts its video of T frames mid-stream; the others idle at the end
+            k = t - 3 if b == 5 else t
+            if b == 5 and t < 3:
+                batch[b], c = short[t], (FIRST if t == 0 else NEXT)
+            elif k < T:
+                batch[b], c = videos[b][k], (FIRST if k == 0 else NEXT)
+            else:
+                c = IDLE
+            ctl.append(c)
+        out, valid = rt.video_push(to_gpu(batch), ctl, 12, "mosaic")
+        for b in range(B):
+            k = t - 3 if b == 5 else t
+            if b == 5 and t < 3:
+                assert valid[b] == (t == 2)
+            else:
+                assert valid[b] == (2 <= k < T)
+                if valid[b]:
+                    got[b].append(out[b:b + 1].clone())
+    rt.set_option("tvl1_async", 0)
+    del rt
+    alone = _runtime("convunet+feat", stem, future, 1, H, W, **ON)
+    for b in (0, 5, 7):
+        want, _ = _stream_alone(alone, videos[b], future)
+        assert len(got[b]) == len(want) == T - 2
+        for g, w in zip(got[b], want):
+            assert torch.equal(g, w), (b, float((g - w).abs().max()))
+
+
+# ---- 4. option off is the push without the option ------------------------------------------------------------------------
+@pytest.mark.parametrize("future", [0, 1])
+def test_option_off_is_the_push_without_it(future):
+    H, W, B, T = 64, 96, 2, 5
+    stem = "recurrent-convunet+feat-future-iso12800" if future else "recurrent-convunet+feat-iso3200"
+    videos = [_video(T, H, W, seed=80 + v) for v in range(B)]
+    a = _runtime("convunet+feat", stem, future, B, H, W)
+    a.set_option("stream_flow_from_denoised", 1)
+    a.set_option("stream_flow_from_denoised", 0)
+    b = _runtime("convunet+feat", stem, future, B, H, W)
+    for t in range(T):
+        frames = to_gpu(np.stack([v[t] for v in videos]))
+        ctl = [FIRST if t == 0 else NEXT] * B
+        oa, va = a.video_push(frames, ctl, 12, "mosaic")
+        ob, vb = b.video_push(frames, ctl, 12, "mosaic")
+        assert va == vb == [t >= 1 + future] * B
+        if va[0]:
+            assert torch.equal(oa, ob), t
+
+
+# ---- 5. on disk ------------------------------------------------------------------------------------------------------------
+def test_denoise_main_with_flows_from_denoised(tmp_path):
+    from rvdd_release_amd import denoise, synth, tiffio
+    H, W = 64, 96
+    name, net = "recurrent-convunet+feat-iso3200", "convunet-mode=fixedfeatures+feat"
+    lengths = (4, 3, 5, 3)
+    root = str(tmp_path / "data")
+    for v, n in enumerate(lengths):
+        d = os.path.join(root, "noisy", "%03d" % v)
+        os.makedirs(d)
+        frames = mosaic_of(quantised_dn(synth.make_sequence(n, H, W, iso=3200, seed=90 + v).raw)).astype(np.uint16)
+        for t in range(n):
+            tiffio.write(os.path.join(d, "%08d.tiff" % (3 * t)), frames[t])
+    flags = ["--netDenoiser", net, "--path2epoch", os.path.join(WEIGHTS, name), "--feature_rec", "--dataroot", root, "--nFolder", "noisy"]
+
+    def run(tag, extra):
+        res = str(tmp_path / tag)
+        stats = denoise.main(flags + ["--results_dir", res] + extra)
+        assert stats["frames"] == sum(n - 1 for n in lengths)
+        return _tree(res)
+
+    on1 = run("on1", ["--val_flow_from_denoised", "--batch_size", "1"])
+    on3 = run("on3", ["--val_flow_from_denoised", "--batch_size", "3"])
+    off = run("off", ["--batch_size", "3"])
+    assert sorted(on1) == sorted(on3) == sorted(off) and len(on1) == sum(n - 1 for n in lengths)
+    assert all(on1[k] == on3[k] for k in on1), [k for k in on1 if on1[k] != on3[k]]
+    firsts = {min(k for k in on1 if os.path.dirname(k) == "%03d" % v) for v in range(len(lengths))}
+    assert len(firsts) == len(lengths)
+    for k in sorted(on1):
+        assert (on1[k] == off[k]) == (k in firsts), k

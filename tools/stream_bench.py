@@ -4,6 +4,7 @@ the device) beside the same handle stepping with the flows computed beforehand (
 synthetic uint16 mosaics.  Two JSON lines: {"mode": "stream"} and {"mode": "step_flows_at_hand"}.
 
 usage (GPU box, repo root):  timeout -k 10 600 python tools/stream_bench.py --config C2 [--batch 8] [--frames 12] [--warmup 3]
+                             [--flow-from-denoised]
 One process, no retries: a failure is the exit status."""
 import argparse
 import json
@@ -27,6 +28,8 @@ ap.add_argument("--batch", type=int, default=None)
 ap.add_argument("--frames", type=int, default=12, help="pushes timed per slot")
 ap.add_argument("--warmup", type=int, default=3, help="pushes before the clock starts (they fill the rings)")
 ap.add_argument("--no-sampler", action="store_true", help="do not sample the shader clock (rocm-smi) beside the loops")
+ap.add_argument("--flow-from-denoised", action="store_true",
+                help="option stream_flow_from_denoised: flows towards the previous frame against the previous output (stream mode only)")
 args = ap.parse_args()
 arch, stem, fut, iso, H, W, _, B0, _ = bench.CONFIGS[args.config]
 B = args.batch or B0
@@ -45,6 +48,7 @@ del raw, dn
 
 rt = RvddRuntime(arch, fut, B, H, W, 0)
 rt.load_state_dict(load_file(os.path.join(REPO, "weights", stem + ".safetensors")))
+rt.set_option("stream_flow_from_denoised", int(args.flow_from_denoised))
 sampler = None if args.no_sampler else bench.GpuSampler(0, 0.05)
 
 
@@ -55,7 +59,8 @@ def clock(t0, t1):
     return {k: w[k] for k in ("sclk_mhz_mean", "sclk_mhz_min", "samples") if k in w}
 
 
-common = {"config": args.config, "arch": arch, "future": fut, "batch": B, "height": H, "width": W, "frames_per_slot": args.frames}
+common = {"config": args.config, "arch": arch, "future": fut, "batch": B, "height": H, "width": W, "frames_per_slot": args.frames,
+          "flow_from_denoised": bool(args.flow_from_denoised)}
 
 # ---- the stream --------------------------------------------------------------------------------------------------------
 out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
