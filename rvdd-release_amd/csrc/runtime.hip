@@ -134,12 +134,10 @@ struct rvdd_handle {
     rvdd_cfg cfg{};
     std::string err;
     bool finalized = false;
-    bool need_init = true;        // every sequence starts a video on the next step (create, rvdd_reset)
-    uint64_t pend_mask = 0;       // rvdd_reset_slots: the sequences that start a video on the next step (B <= 64; never all of them:
-                                  // a full mask is need_init, so that the all-slots step issues the launches it always has)
+    uint64_t reset_marks = 0;     // the sequences that start a video on the next step that covers them: slots_below(batch) = all of them
+                                  // (create, rvdd_reset), some after rvdd_reset_slots (B <= 64; beyond that only none or all occur)
     uint64_t undef_mask = 0;      // rvdd_step_live / rvdd_move_slots: the sequences whose recurrent state is undefined (they sat a step out, or
                                   // were moved away); a step may cover one only together with a reset mark for it
-    int nrun = 0;                 // the sequences the running step launches over: cfg.batch, or n_live inside rvdd_step_live
     bool force_wino = false;      // Winograd at every size (RVDD_CONV=winograd / rvdd_set_option "conv_kernel" 2): tests + measurement
     bool warp_raw = false;        // --warp_raw (rvdd_set_option): warp the re-mosaicked frames at raw resolution, demosaic afterwards
     bool prev_noisy = false;      // --prev_noisy_frame (rvdd_set_option): the next step's "previous frame" is the demosaiced noisy one
@@ -158,9 +156,7 @@ struct rvdd_handle {
     bool next_pool = true;        // ConvNeXt, fused blocks: MaxPool2d(2) from the epilogue of the block in front of a DownConv
     bool next_projfuse = true;    // ConvNeXt, pipelined split-f16 blocks: the 96 -> 48 projection behind a concat as two halves in the epilogues of
                                   // the blocks that form the concatenated maps (RVDD_NEXT_PROJFUSE=0 / option "next_projfuse" 0: proj1x1_kernel)
-    bool netin_proj = false;      // lv[0].t[0] of the running step already holds the first ConvBlock's projection of the network input (run_prologue)
-    bool featw_proj = false;      // `featw` of the running step holds W_f warp(features) + bias (run_prologue, next_pf_pre), not the warped features
-    bool serpentine = false;      // sequence order of the current frame-step (flips every step when seq_major is on)
+    bool serpentine = false;      // sequence order of the next forward (flips with every one when seq_major is on)
     std::map<std::string, HostTensor> staged;
     std::vector<void*> allocs;
 
@@ -187,10 +183,7 @@ struct rvdd_handle {
     float* featw = nullptr;      // NHWC48 warped features
     float* lastfeat = nullptr;   // NHWC48 recurrent features
     unsigned* amax = nullptr;    // [AMAX_SLOTS][B][kAmaxSeqWords] max |x| per map and sequence, zeroed at the start of every forward
-    int step_ctr = 0;            // frame-steps enqueued: picks the regular set (& 1) and the recurrent features' slots (% 3)
-    int amax_base = 0;           // first slot of the regular set the current forward uses
-    int amax_feat_in = 0, amax_post_out = 0;      // absolute slots the current forward reads the old features' words from / writes the new ones to
-    bool amax_zero_pending = false;               // the next netin_bound launch zeroes the step-after-next's set and features slot
+    int step_ctr = 0;            // frame-steps enqueued, mod 6: picks the amax slots of a step (step_amax)
     double* loss_partial = nullptr;
     double* loss_result = nullptr;
     double* loss_batch = nullptr;    // rvdd_psnr_l1_batch: partial sums and results of every slice, grown on demand
@@ -255,6 +248,7 @@ struct rvdd_handle {
 
     bool has_feat() const { return cfg.arch == RVDD_ARCH_CONVUNET_FEAT || cfg.arch == RVDD_ARCH_CONVNEXT_FEAT; }
     bool is_next() const { return cfg.arch == RVDD_ARCH_CONVNEXT || cfg.arch == RVDD_ARCH_CONVNEXT_FEAT; }
+    bool amax_on() const { return bfp && split16 && !is_next(); }      // the convs read amax words (block floating point)
     int cin_real() const { return 3 * (2 + cfg.future); }
 };
 
@@ -269,6 +263,8 @@ int fail(rvdd_t* h, int code, const char* fmt, ...) {
     if (h) h->err = buf; else g_create_error = buf;
     return code;
 }
+
+uint64_t slots_below(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }      // slots [0, n) as a mask (every slot it has, from 64 on)
 
 void drop_graphs(rvdd_t* h) {
     for (auto& kv : h->graphs) {
@@ -622,13 +618,33 @@ const char* conv_name_h(int epi, bool acc) {
 // the amax words (rvdd_internal.h) of map `slot`, from sequence b0 on
 unsigned* amax_words(const rvdd_t* h, int slot, size_t b0 = 0) { return h->amax + ((size_t)slot * h->cfg.batch + b0) * kAmaxSeqWords; }
 constexpr size_t amax_bytes(int B, int nslots) { return (size_t)nslots * B * kAmaxSeqWords * sizeof(unsigned); }
-int amax_layer(const rvdd_t* h, int layer) { return h->amax_base + layer; }
+
+// The amax slots of one forward: the first slot of its regular set, and the absolute slots it reads the old features' words
+// from / writes the new ones to.  A frame-step's follow step_ctr; rvdd_unet_forward has a set of its own, so that the
+// frame-steps' sets and the recurrent slots stay untouched.
+struct AmaxSlots {
+    int base = 0, feat_in = 0, post_out = 0;
+};
+constexpr AmaxSlots step_amax(int ctr) { return {(ctr & 1) * AMAX_NREG, AMAX_FEAT0 + (ctr + 2) % 3, AMAX_FEAT0 + ctr % 3}; }
+constexpr AmaxSlots forward_amax() { return {2 * AMAX_NREG, 2 * AMAX_NREG + AMAX_REL_FWDFEAT, 2 * AMAX_NREG + CU_POST}; }
+
+// One forward of the net, handed down to everything that launches for it: a frame-step (enqueue_step) or a bare
+// rvdd_unet_forward.
+struct StepInputs;
+struct NetRun {
+    int n = 0;                        // the sequences it covers: slots [0, n) of the handle's maps
+    AmaxSlots amax;
+    bool zero_pending = false;        // the first network-input launch zeroes the set and features slot of the step after (run_prologue)
+    bool netin_proj = false;          // lv[0].t[0] already holds the first ConvBlock's projection of the network input (run_prologue)
+    bool featw_proj = false;          // `featw` holds W_f warp(features) + bias (run_prologue, next_pf_pre), not the warped features
+    const StepInputs* in = nullptr;   // what a frame-step does in front of the net (run_prologue); null for rvdd_unet_forward
+};
+int amax_layer(const NetRun& run, int layer) { return run.amax.base + layer; }
 
 struct ConvCall {
     const float* in = nullptr;
     int src = 0;             // which weight slice of the layer
     const float* acc_in = nullptr;
-    bool with_bias = true;   // informational: bias is used iff acc_in == nullptr
     int epi = EPI_RELU;
     const float* res1 = nullptr;
     const float* res2 = nullptr;
@@ -642,8 +658,8 @@ struct ConvCall {
     int amax_out = -1;
 };
 
-bool wino_applies(const rvdd_t* h, int H, int W) {
-    return h->use_wino && (h->force_wino || h->nrun * ((W + 31) / 32) * ((H + 7) / 8) >= 200);
+bool wino_applies(const rvdd_t* h, const NetRun& run, int H, int W) {
+    return h->use_wino && (h->force_wino || run.n * ((W + 31) / 32) * ((H + 7) / 8) >= 200);
 }
 
 // Sequences [b0, b0 + nb) of the batch: the maps of a ConvCall are those of the WHOLE batch, a launch may cover a part.
@@ -658,10 +674,9 @@ struct Sub {
 // more to their tails (3600 units on 256 CUs = 14.06 rounds) and to four filter-bank loads per layer than the cache
 // gives back.  Kept because it is free and pins an invariant the tests use: a launch's batch size does not enter a
 // tile's sums, so both schedules give bit-identical frames.
-bool seq_major_on(const rvdd_t* h) { return h->nrun > 1 && h->seq_major == 1; }
+bool seq_major_on(const rvdd_t* h, int n) { return n > 1 && h->seq_major == 1; }
 
-int run_conv(rvdd_t* h, const Conv3& L, const ConvCall& c, hipStream_t s, Sub sub = Sub{0, -1}) {
-    if (sub.nb < 0) sub.nb = h->nrun;
+int run_conv(rvdd_t* h, const NetRun& run, const Conv3& L, const ConvCall& c, hipStream_t s, Sub sub) {
     const int cin_in = L.cin_pad[c.src];
     const int Ho = c.epi == EPI_POOL ? c.H / 2 : (c.Hout ? c.Hout : c.H), Wo = c.epi == EPI_POOL ? c.W / 2 : (c.Wout ? c.Wout : c.W);
     const size_t px_in = (size_t)sub.b0 * c.H * c.W, px_out = (size_t)sub.b0 * Ho * Wo;
@@ -704,7 +719,7 @@ int run_conv(rvdd_t* h, const Conv3& L, const ConvCall& c, hipStream_t s, Sub su
     a.amax_in = (c.amax_in >= 0 && h->bfp) ? amax_words(h, c.amax_in, sub.b0) : nullptr;
     a.amax_out = (c.amax_out >= 0 && h->bfp) ? amax_words(h, c.amax_out, sub.b0) : nullptr;
     const bool c16_ok = cin != 48 && !c.acc_in && (c.epi == EPI_NONE || c.epi == EPI_RELU);
-    if (c.ups && !(cin == 48 && ((h->split16 && L.wh[c.src]) || (L.wu[c.src] && wino_applies(h, c.H, c.W)))))
+    if (c.ups && !(cin == 48 && ((h->split16 && L.wh[c.src]) || (L.wu[c.src] && wino_applies(h, run, c.H, c.W)))))
         return fail(h, RVDD_ERR_STATE, "run_conv: the fused upsample exists in the split-f16 and the Winograd kernels only");
     if (c.ups) bytes -= px * 4.0 * 36.0;          // reads the quarter-size map
     // the F16 matrix pipe with split operands: every layer of the convunet
@@ -716,7 +731,7 @@ int run_conv(rvdd_t* h, const Conv3& L, const ConvCall& c, hipStream_t s, Sub su
         HIPCHK(h, launch_conv3x3h(a, cin == 48 ? 48 : 16, c.epi, s));
         return RVDD_OK;
     }
-    if ((cin == 48 || c16_ok) && L.wu[c.src] && wino_applies(h, c.H, c.W)) {
+    if ((cin == 48 || c16_ok) && L.wu[c.src] && wino_applies(h, run, c.H, c.W)) {
         a.w = L.wu[c.src];
         Scope sc(h, s, c.ups ? "wino3x3_ups_kernel<1>" : cin == 48 ? wino_name(c.epi, c.acc_in != nullptr)
                                  : (c.epi == EPI_NONE ? "wino3x3_c16_kernel<0>" : "wino3x3_c16_kernel<1>"), flops, bytes);
@@ -730,8 +745,7 @@ int run_conv(rvdd_t* h, const Conv3& L, const ConvCall& c, hipStream_t s, Sub su
 
 
 // The composed 5x5 conv of the network input (compose_pre_enc0) into `part`, and its border fix; sequences of `sub`.
-int run_pre5(rvdd_t* h, const float* netin, float* part, hipStream_t s, Sub sub) {
-    if (sub.nb < 0) sub.nb = h->nrun;
+int run_pre5(rvdd_t* h, const NetRun& run, const float* netin, float* part, hipStream_t s, Sub sub) {
     const int H = h->cfg.height, W = h->cfg.width;
     const size_t px0 = (size_t)sub.b0 * H * W;
     ConvArgs a{};
@@ -743,7 +757,7 @@ int run_pre5(rvdd_t* h, const float* netin, float* part, hipStream_t s, Sub sub)
     a.B = sub.nb;
     a.H = a.Hout = H;
     a.W = a.Wout = W;
-    a.amax_in = h->bfp ? amax_words(h, h->amax_base + AMAX_REL_NETIN, sub.b0) : nullptr;
+    a.amax_in = h->bfp ? amax_words(h, run.amax.base + AMAX_REL_NETIN, sub.b0) : nullptr;
     const double px = (double)sub.nb * H * W;
     {
         Scope sc(h, s, "conv5x5h_kernel<16>", 2.0 * 25.0 * h->cin_real() * 48.0 * px, px * 4.0 * (h->cin_real() + 48.0));
@@ -754,7 +768,7 @@ int run_pre5(rvdd_t* h, const float* netin, float* part, hipStream_t s, Sub sub)
 }
 
 // What rvdd_step does in front of the net (demosaic, warps): the caller's frame and flow pointers of one step.
-// run_convunet calls it per sequence when the full-resolution stages run depth first; null for rvdd_unet_forward.
+// run_convunet calls it per sequence when the full-resolution stages run depth first.
 struct StepInputs {
     const float* raw_prev = nullptr;      // only on the first step of a video (of any sequence)
     unsigned long long latch = 0;         // the sequences that start a video on this step: ~0 = all, else bit b (B <= 64)
@@ -764,56 +778,56 @@ struct StepInputs {
     const float* flow_next = nullptr;
     size_t rawf = 0, flowf = 0;       // floats from one sequence to the next in the caller's raw / flow tensors
 };
-int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s);
+int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s);
 
 // networks/unet.py:544-588 as specialised by UNet_FixedFeatures[_feat] (:595-825).
-int run_convunet(rvdd_t* h, const float* netin, const float* featw, float* feat_dst, float* out_nchw,
-                 float* out_nhwc4, hipStream_t s, const StepInputs* prologue) {
+int run_convunet(rvdd_t* h, NetRun& run, const float* netin, const float* featw, float* feat_dst, float* out_nchw,
+                 float* out_nhwc4, hipStream_t s) {
     const bool feat = h->has_feat();
-    const int B = h->nrun;
+    const int B = run.n;
     Level* lv = h->lv;
     const Conv3* cu = h->cu;
-    // `from` = the amax slot of the input map (L(the layer that wrote it), AMAX_NETIN, h->amax_feat_in); a layer's output slot is L(its id)
+    // `from` = the amax slot of the input map (L(the layer that wrote it), AMAX_NETIN, run.amax.feat_in); a layer's output slot is L(its id)
     auto conv = [&](int layer, const float* in, int from, float* out, int lvl, int epi, Sub sub) {
         ConvCall c;
         c.in = in; c.out = out; c.H = lv[lvl].H; c.W = lv[lvl].W; c.epi = epi;
-        c.amax_in = from; c.amax_out = amax_layer(h, layer);
-        return run_conv(h, cu[layer], c, s, sub);
+        c.amax_in = from; c.amax_out = amax_layer(run, layer);
+        return run_conv(h, run, cu[layer], c, s, sub);
     };
-    const auto L = [&](int layer) { return amax_layer(h, layer); };
-    const int AMAX_NETIN = h->amax_base + AMAX_REL_NETIN;
+    const auto L = [&](int layer) { return amax_layer(run, layer); };
+    const int AMAX_NETIN = run.amax.base + AMAX_REL_NETIN;
     // two-source (virtual concat) conv: pass 1 leaves bias + sum over source A in `part`
     auto conv2 = [&](int layer, const float* inA, int fromA, const float* inB, int fromB, float* out, int lvl, Sub sub) {
         ConvCall c;
         c.in = inA; c.src = 0; c.out = lv[lvl].part; c.H = lv[lvl].H; c.W = lv[lvl].W; c.epi = EPI_NONE;
         c.amax_in = fromA;
-        RC(run_conv(h, cu[layer], c, s, sub));
+        RC(run_conv(h, run, cu[layer], c, s, sub));
         c.in = inB; c.src = 1; c.acc_in = lv[lvl].part; c.out = out; c.epi = EPI_RELU;
-        c.amax_in = fromB; c.amax_out = amax_layer(h, layer);
-        return run_conv(h, cu[layer], c, s, sub);
+        c.amax_in = fromB; c.amax_out = amax_layer(run, layer);
+        return run_conv(h, run, cu[layer], c, s, sub);
     };
     const Sub all{0, B};
     // the full-resolution stages run per sequence when that keeps their maps in the Infinity Cache (seq_major_on),
     // in an order that alternates from frame to frame so that a step begins with the sequence the last one ended on
-    const bool per_seq = seq_major_on(h);
+    const bool per_seq = seq_major_on(h, B);
     const int nsub = per_seq ? B : 1;
     auto sub_at = [&](int k) { return per_seq ? Sub{h->serpentine ? B - 1 - k : k, 1} : all; };
 
     // ---- pre-stages + encoder level 0
     for (int k = 0; k < nsub; ++k) {
         const Sub sb = sub_at(k);
-        if (prologue) RC(run_prologue(h, *prologue, sb, s));
+        if (run.in) RC(run_prologue(h, run, sb, s));
         if (feat && h->fuse_pre && h->split16 && h->pre5_w) {
             // preprocessing_layer (:742, no activation) and the first source of EncoderConvs[0][0] (:743) as ONE 5x5 conv of the
             // network input (compose_pre_enc0), its border ring put right, then the second source (the old features) as before
-            RC(run_pre5(h, netin, lv[0].part, s, sb));
+            RC(run_pre5(h, run, netin, lv[0].part, s, sb));
             ConvCall c;
             c.in = featw; c.src = 1; c.acc_in = lv[0].part; c.out = lv[0].t[1]; c.H = lv[0].H; c.W = lv[0].W; c.epi = EPI_RELU;
-            c.amax_in = h->amax_feat_in; c.amax_out = L(CU_ENC0_0);
-            RC(run_conv(h, cu[CU_ENC0_0], c, s, sb));
+            c.amax_in = run.amax.feat_in; c.amax_out = L(CU_ENC0_0);
+            RC(run_conv(h, run, cu[CU_ENC0_0], c, s, sb));
         } else if (feat) {
             RC(conv(CU_PRE, netin, AMAX_NETIN, lv[0].t[0], 0, EPI_NONE, sb));               // :742 (no activation)
-            RC(conv2(CU_ENC0_0, lv[0].t[0], L(CU_PRE), featw, h->amax_feat_in, lv[0].t[1], 0, sb)); // cat[y, old_features] :743
+            RC(conv2(CU_ENC0_0, lv[0].t[0], L(CU_PRE), featw, run.amax.feat_in, lv[0].t[1], 0, sb)); // cat[y, old_features] :743
         } else {
             RC(conv(CU_ENC0_0, netin, AMAX_NETIN, lv[0].t[1], 0, EPI_RELU, sb));
         }
@@ -834,7 +848,7 @@ int run_convunet(rvdd_t* h, const float* netin, const float* featw, float* feat_
         c.in = lv[3].t[0]; c.out = lv[3].t[1]; c.H = lv[3].H; c.W = lv[3].W;
         c.epi = EPI_RELU_ADD2; c.res1 = e3; c.res2 = lv[3].t[0];
         c.amax_in = L(CU_BOT0); c.amax_out = L(CU_BOT1);
-        RC(run_conv(h, cu[CU_BOT1], c, s));
+        RC(run_conv(h, run, cu[CU_BOT1], c, s, all));
     }
     const float* d = lv[3].t[1];
     int d_from = L(CU_BOT1);
@@ -848,7 +862,7 @@ int run_convunet(rvdd_t* h, const float* netin, const float* featw, float* feat_
             const size_t lo_px = (size_t)sb.b0 * lv[lo].H * lv[lo].W, hi_px = (size_t)sb.b0 * lv[hi].H * lv[hi].W;
             // UpConv: bilinear x2, conv, ReLU (:137-142).  Where the Winograd kernel runs the conv, the interpolation
             // happens in its patch load and the upsampled map is never written; elsewhere it is made first.
-            const bool fused = h->fuse_upsample && (h->split16 || wino_applies(h, uh, uw));
+            const bool fused = h->fuse_upsample && (h->split16 || wino_applies(h, run, uh, uw));
             if (!fused) {
                 Scope sc(h, s, "upsample2x_kernel", 0.0, (double)sb.nb * uh * uw * 192.0 * 1.25);
                 HIPCHK(h, launch_upsample2x(d + lo_px * kF, lv[hi].t[0] + (size_t)sb.b0 * uh * uw * kF, sb.nb, lv[lo].H, lv[lo].W, uh,
@@ -865,24 +879,24 @@ int run_convunet(rvdd_t* h, const float* netin, const float* featw, float* feat_
             c.amax_in = d_from; c.amax_out = L(cu_up(i));
             if (uh != lv[hi].H || uw != lv[hi].W)
                 HIPCHK(h, hipMemsetAsync(lv[hi].t[1] + hi_px * kF, 0, (size_t)sb.nb * lv[hi].H * lv[hi].W * kF * sizeof(float), s));
-            RC(run_conv(h, cu[cu_up(i)], c, s, sb));
+            RC(run_conv(h, run, cu[cu_up(i)], c, s, sb));
             RC(conv2(cu_dec(i, 0), lv[hi].skip, L(cu_enc(hi, 1)), lv[hi].t[1], L(cu_up(i)), lv[hi].t[0], hi, sb));        // cat(skip, dec) :541
             RC(conv(cu_dec(i, 1), lv[hi].t[0], L(cu_dec(i, 0)), lv[hi].t[1], hi, EPI_RELU, sb));
             if (hi > 0) continue;
             // ---- post: hooked 48-ch map = next frame's features (:808-812), then 1x1 -> 3
-            if (h->split16 || wino_applies(h, lv[0].H, lv[0].W)) {
+            if (h->split16 || wino_applies(h, run, lv[0].H, lv[0].W)) {
                 // PostConvs[1] (1x1, 48 -> 3) rides in the epilogue of PostConvs[0]'s kernel (split-f16: at every size; Winograd
                 // f32: where it runs) -- and with it the output frame's share of the words the next step's input bound reads
                 ConvCall pc;
                 pc.in = lv[0].t[1]; pc.out = fdst; pc.H = lv[0].H; pc.W = lv[0].W; pc.epi = EPI_RELU_OUT3;
                 pc.out3_nchw = out_nchw; pc.out3_nhwc4 = out_nhwc4;
-                pc.amax_in = L(cu_dec(2, 1)); pc.amax_out = h->amax_post_out;
-                RC(run_conv(h, cu[CU_POST], pc, s, sb));
+                pc.amax_in = L(cu_dec(2, 1)); pc.amax_out = run.amax.post_out;
+                RC(run_conv(h, run, cu[CU_POST], pc, s, sb));
             } else {
                 ConvCall pc;
                 pc.in = lv[0].t[1]; pc.out = fdst; pc.H = lv[0].H; pc.W = lv[0].W; pc.epi = EPI_RELU;
-                pc.amax_in = L(cu_dec(2, 1)); pc.amax_out = h->amax_post_out;
-                RC(run_conv(h, cu[CU_POST], pc, s, sb));
+                pc.amax_in = L(cu_dec(2, 1)); pc.amax_out = run.amax.post_out;
+                RC(run_conv(h, run, cu[CU_POST], pc, s, sb));
                 const size_t px0 = (size_t)sb.b0 * h->cfg.height * h->cfg.width;
                 const double px = (double)sb.nb * h->cfg.height * h->cfg.width;
                 Scope sc(h, s, "conv1x1_out_kernel", 2.0 * 48 * 3 * px, px * (192.0 + 12.0 + 16.0));
@@ -893,12 +907,8 @@ int run_convunet(rvdd_t* h, const float* netin, const float* featw, float* feat_
         d = lv[hi].t[1];
         d_from = L(cu_dec(i, 1));
     }
-    if (per_seq) h->serpentine = !h->serpentine;
     return RVDD_OK;
 }
-
-int run_net(rvdd_t* h, const float* netin, const float* featw, float* feat_dst, float* out_nchw,
-            float* out_nhwc4, hipStream_t s, const StepInputs* prologue);
 
 int ensure_scratch(rvdd_t* h, size_t bytes) {
     if (h->scratch_bytes >= bytes) return RVDD_OK;
@@ -918,16 +928,11 @@ int ensure_scratch(rvdd_t* h, size_t bytes) {
 #include "runtime_next.inc"
 
 namespace {
-int run_net(rvdd_t* h, const float* netin, const float* featw, float* feat_dst, float* out_nchw,
-            float* out_nhwc4, hipStream_t s, const StepInputs* prologue) {
-    if (!h->is_next()) {
-        return run_convunet(h, netin, featw, feat_dst, out_nchw, out_nhwc4, s, prologue);
-    }
-    const int B = h->nrun;
-    h->featw_proj = false;          // a caller's own features (rvdd_unet_forward) come as they are
-    h->netin_proj = false;          // and so does a caller's own network input
-    if (prologue) RC(run_prologue(h, *prologue, Sub{0, B}, s));
-    return run_convnext(h, netin, featw, feat_dst, out_nchw, out_nhwc4, s, Sub{0, B});
+int run_net(rvdd_t* h, NetRun& run, const float* netin, const float* featw, float* feat_dst, float* out_nchw,
+            float* out_nhwc4, hipStream_t s) {
+    if (!h->is_next()) return run_convunet(h, run, netin, featw, feat_dst, out_nchw, out_nhwc4, s);
+    if (run.in) RC(run_prologue(h, run, Sub{0, run.n}, s));
+    return run_convnext(h, run, netin, featw, feat_dst, out_nchw, out_nhwc4, s);
 }
 }  // namespace
 
@@ -977,7 +982,7 @@ int rvdd_create(const rvdd_cfg* cfg, rvdd_t** out) {
 
     rvdd_t* h = new rvdd_handle();
     h->cfg = *cfg;
-    h->nrun = cfg->batch;
+    h->reset_marks = slots_below(cfg->batch);
     if (const char* sm = std::getenv("RVDD_SEQ_MAJOR")) h->seq_major = std::atoi(sm) != 0;     // measurement switches
     if (const char* fu = std::getenv("RVDD_FUSE_UPSAMPLE")) h->fuse_upsample = std::atoi(fu) != 0;
     if (const char* bf = std::getenv("RVDD_BFP")) h->bfp = std::atoi(bf) != 0;
@@ -1313,7 +1318,7 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
 
 int rvdd_reset(rvdd_t* h) {
     if (!h) return RVDD_ERR_ARG;
-    h->need_init = true;
+    h->reset_marks = slots_below(h->cfg.batch);
     return RVDD_OK;
 }
 
@@ -1324,19 +1329,10 @@ int rvdd_reset_slots(rvdd_t* h, const uint8_t* mask) {
     int count = 0;
     for (int b = 0; b < B; ++b) count += mask[b] != 0;
     if (count == 0) return RVDD_OK;
-    if (count == B) {                 // every slot: exactly rvdd_reset (and its launches)
-        h->need_init = true;
-        return RVDD_OK;
-    }
+    if (count == B) return rvdd_reset(h);      // every slot
     if (B > 64) return fail(h, RVDD_ERR_ARG, "rvdd_reset_slots: a mask of some slots needs batch <= 64 (batch is %d)", B);
-    uint64_t m = h->pend_mask;
     for (int b = 0; b < B; ++b)
-        if (mask[b]) m |= 1ull << b;
-    if (m == (B == 64 ? ~0ull : (1ull << B) - 1)) {
-        h->need_init = true;
-        m = 0;
-    }
-    h->pend_mask = m;
+        if (mask[b]) h->reset_marks |= 1ull << b;
     return RVDD_OK;
 }
 
@@ -1346,7 +1342,8 @@ namespace {
 
 // The stages in front of the net for sequences [sb.b0, sb.b0 + sb.nb): one launch covers them all -- the kernels take
 // the caller's batch strides (channel slices of the reference's wider `n` / `flow` tensors are strided over the batch).
-int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
+int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
+    const StepInputs& in = *run.in;
     const bool nw = h->no_warp;
     const int H = h->cfg.height, W = h->cfg.width;
     const size_t img = (size_t)H * W, npix = (size_t)h->cfg.batch * img;
@@ -1359,15 +1356,15 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
     float* green = h->green + o * img;
     float* netin = h->netin + o * img * kNetInC;
     // amax words of the maps the split-f16 convs read first (block floating point, rvdd_internal.h)
-    const bool bfp = h->bfp && h->split16 && !h->is_next();
-    unsigned* amax_netin = bfp ? amax_words(h, h->amax_base + AMAX_REL_NETIN, o) : nullptr;
+    const bool bfp = h->amax_on();
+    unsigned* amax_netin = bfp ? amax_words(h, run.amax.base + AMAX_REL_NETIN, o) : nullptr;
     // the zeroing for the step after this one rides in the first netin_bound launch of the step; a step without one memsets
-    const int t1 = h->step_ctr + 1;
-    unsigned* zero_a = amax_words(h, (t1 & 1) * AMAX_NREG);
-    unsigned* zero_b = amax_words(h, AMAX_FEAT0 + t1 % 3);
+    const AmaxSlots after = step_amax(h->step_ctr + 1);
+    unsigned* zero_a = amax_words(h, after.base);
+    unsigned* zero_b = amax_words(h, after.post_out);
     const size_t zero_na = amax_bytes(h->cfg.batch, AMAX_NREG) / 4, zero_nb = amax_bytes(h->cfg.batch, 1) / 4;
-    const bool zero_now = bfp && h->amax_zero_pending;
-    h->amax_zero_pending = false;
+    const bool zero_now = bfp && run.zero_pending;
+    run.zero_pending = false;
     // which of these sequences start a video (rvdd_reset_slots): they bound the network input from raw_prev, the others from the
     // words of their previous output -- each sequence gets the words it would get alone
     const unsigned long long latch = in.latch == ~0ull ? ~0ull : (o < 64 ? in.latch >> o : 0ull);
@@ -1412,10 +1409,9 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
         Scope sc(h, s, "netin(ha_green+netin_kernel)", 0.0, (double)n * img * (16.0 + 16.0 + 48.0 + (next4 ? 16.0 : 0.0)));
         // small frames without a future frame: the bound, the green plane and the network input in ONE launch
         if (!h->is_next() && !h->prev_noisy && netin_small_applies(n, H / 2, W / 2, h->cfg.future != 0)) {
-            h->netin_proj = false;
             const float* rp_ = in.raw_prev ? in.raw_prev + o * in.rawf : nullptr;
             HIPCHK(h, launch_netin_small(rc_, rp_, h->lastden4 + o * img * 4, fp_, netin, n, H / 2, W / 2, (int64_t)in.rawf, (int64_t)in.flowf,
-                                         amax_netin && latch != ~0ull ? amax_words(h, h->amax_feat_in, o) : nullptr, amax_netin, s,
+                                         amax_netin && latch != ~0ull ? amax_words(h, run.amax.feat_in, o) : nullptr, amax_netin, s,
                                          zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch, h->bayer));
             goto prologue_features;
         }
@@ -1424,7 +1420,7 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
             // with --prev_noisy_frame the "previous output" is a demosaicked frame whose raw data is gone: its own maximum
             const float* rp_ = in.raw_prev ? in.raw_prev + o * in.rawf : nullptr;
             HIPCHK(h, launch_netin_bound(rc_, rn_, rp_, n, H / 2, W / 2, (int64_t)in.rawf,
-                                         latch == ~0ull ? nullptr : amax_words(h, h->amax_feat_in, o), amax_netin, s,
+                                         latch == ~0ull ? nullptr : amax_words(h, run.amax.feat_in, o), amax_netin, s,
                                          zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch));
             if (h->prev_noisy && latch != ~0ull)      // over the runs of sequences that continue a video (one run without a reset)
                 for (int b = 0; b < n;) {
@@ -1437,16 +1433,16 @@ int run_prologue(rvdd_t* h, const StepInputs& in, Sub sb, hipStream_t s) {
         }
         // ConvNeXtUnet: the input's only reader is the 1x1 projection of the first ConvBlock, which rides in the same kernel
         const NextBlk* first = h->is_next() && h->next_projfuse ? &h->nx[h->has_feat() ? NX_PRE : NX_ENC0_0] : nullptr;
-        h->netin_proj = first != nullptr;
+        run.netin_proj = first != nullptr;
         HIPCHK(h, launch_netin(rc_, green, h->lastden4 + o * img * 4, fp_, next4, fn_, netin, n, H / 2, W / 2, s, (int64_t)in.rawf,
                                (int64_t)in.flowf, first ? first->w.proj_w : nullptr, first ? first->w.proj_b : nullptr,
                                first ? h->lv[0].t[0] + o * img * kF : nullptr, h->bayer));
     }
 prologue_features:
     if (h->has_feat() && !nw) {
-        h->featw_proj = next_pf_pre(h);
-        Scope sc(h, s, "warp48_kernel", h->featw_proj ? 2.0 * 48 * 48 * n * img : 0.0, (double)n * img * (384.0 + 2.0));
-        if (h->featw_proj)
+        run.featw_proj = next_pf_pre(h);
+        Scope sc(h, s, "warp48_kernel", run.featw_proj ? 2.0 * 48 * 48 * n * img : 0.0, (double)n * img * (384.0 + 2.0));
+        if (run.featw_proj)
             HIPCHK(h, launch_warp48_proj(h->lastfeat + o * img * kF, fp_, h->featw + o * img * kF, n, H, W, h->nx[NX_ENC0_0].half[1].frag,
                                          h->nx[NX_ENC0_0].half[1].inv_e, h->nx[NX_ENC0_0].w.proj_b, s, (int64_t)in.flowf));
         else
@@ -1455,27 +1451,38 @@ prologue_features:
     return RVDD_OK;
 }
 
-// Every launch of one frame-step, in order, on stream s.  `init` = first frame of a video.
-int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const float* raw_next, const float* flow_prev,
-                 const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, bool init, uint64_t pend, hipStream_t s) {
-    const bool nw = h->no_warp;
-    const int B = h->nrun, H = h->cfg.height, W = h->cfg.width;      // B: the sequences this step covers (rvdd_step_live: the live ones)
+// One frame-step as step_n planned it: the caller's tensors, the slots it covers and which of them start a video.
+struct StepPlan {
+    int n;                  // slots [0, n): cfg.batch, or the live ones of rvdd_step_live
+    const float *raw_prev, *raw_cur, *raw_next, *flow_prev, *flow_next;
+    int64_t raw_stride, flow_stride;
+    float* out_rgb;
+    bool init;              // every covered slot starts a video
+    uint64_t pend;          // else: the covered slots that do (rvdd_reset_slots)
+};
+
+// Every launch of one frame-step, in order, on stream s.  The handle is read only: commit_step moves it on.
+int enqueue_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
+    const bool nw = h->no_warp, init = p.init;
+    const int B = p.n, H = h->cfg.height, W = h->cfg.width;
     const size_t npix = (size_t)B * H * W;
-    if (init) pend = 0;
+    const uint64_t pend = p.pend;
+    const float *raw_prev = p.raw_prev, *raw_cur = p.raw_cur;
     StepInputs in;
     in.raw_prev = init || pend ? raw_prev : nullptr;
     in.latch = init ? ~0ull : pend;
-    in.raw_cur = raw_cur; in.raw_next = raw_next; in.flow_prev = flow_prev; in.flow_next = flow_next;
-    in.rawf = raw_stride ? (size_t)raw_stride : (size_t)4 * (H / 2) * (W / 2);
-    in.flowf = flow_stride ? (size_t)flow_stride : (size_t)2 * (H / 2) * (W / 2);
+    in.raw_cur = raw_cur; in.raw_next = p.raw_next; in.flow_prev = p.flow_prev; in.flow_next = p.flow_next;
+    in.rawf = p.raw_stride ? (size_t)p.raw_stride : (size_t)4 * (H / 2) * (W / 2);
+    in.flowf = p.flow_stride ? (size_t)p.flow_stride : (size_t)2 * (H / 2) * (W / 2);
+    NetRun run;
+    run.n = B;
+    run.amax = step_amax(h->step_ctr);
+    run.in = &in;
     // amax words: everything but the recurrent features' words this step reads (zero features at the start of a video: zero words)
-    h->amax_base = (h->step_ctr & 1) * AMAX_NREG;
-    h->amax_feat_in = AMAX_FEAT0 + (h->step_ctr + 2) % 3;
-    h->amax_post_out = AMAX_FEAT0 + h->step_ctr % 3;
-    if (h->bfp && h->split16 && !h->is_next()) {
+    if (h->amax_on()) {
         // the first step of a video starts from zero features: zero words; later steps find their set zeroed by the step before
         if (init) HIPCHK(h, hipMemsetAsync(h->amax, 0, amax_bytes(h->cfg.batch, AMAX_SLOTS), s));
-        h->amax_zero_pending = true;
+        run.zero_pending = true;
     }
     if (init) {
         // lastden = n[:, :3] (demosaiced previous noisy frame), features = 0
@@ -1496,13 +1503,12 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
                                       (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf, h->bayer));
             b = e;
         }
-        const bool words = h->bfp && h->split16 && !h->is_next();
-        HIPCHK(h, launch_latch_zero(pend, h->has_feat() ? h->lastfeat : nullptr, (int64_t)img * kF, words ? h->amax : nullptr, AMAX_SLOTS,
+        HIPCHK(h, launch_latch_zero(pend, h->has_feat() ? h->lastfeat : nullptr, (int64_t)img * kF, h->amax_on() ? h->amax : nullptr, AMAX_SLOTS,
                                     h->cfg.batch, s));
     }
     // without warping the previous features are read in place: the net consumes them in its first layer and only
     // its last one writes the new ones
-    const int rc = run_net(h, h->netin, nw ? h->lastfeat : h->featw, h->lastfeat, out_rgb, h->lastden4, s, &in);
+    const int rc = run_net(h, run, h->netin, nw ? h->lastfeat : h->featw, h->lastfeat, p.out_rgb, h->lastden4, s);
     if (rc == RVDD_OK && h->prev_noisy)     // store_frame = the noisy current frame (models/recurrent_model.py:335-337)
         HIPCHK(h, launch_demosaic(raw_cur, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf,
                                   h->bayer));
@@ -1510,28 +1516,6 @@ int enqueue_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const f
 }
 
 constexpr size_t kMaxStepGraphs = 128;      // one per distinct set of caller buffers; least recently used goes first
-
-// The reset marks as one mask of B <= 64 slots (need_init = all of them), and back: a full mask is always stored as need_init.
-uint64_t slots_below(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
-uint64_t reset_marks(const rvdd_t* h) { return h->need_init ? slots_below(h->cfg.batch) : h->pend_mask; }
-void set_reset_marks(rvdd_t* h, uint64_t m) {
-    h->need_init = m == slots_below(h->cfg.batch);
-    h->pend_mask = h->need_init ? 0 : m;
-}
-
-// nrun = n for the launches of one partial step, cfg.batch again when it is over (however it ends)
-struct LiveScope {
-    rvdd_t* h;
-    LiveScope(rvdd_t* h_, int n) : h(h_) { h->nrun = n; }
-    ~LiveScope() { h->nrun = h->cfg.batch; }
-};
-
-int step_n(rvdd_t* h, int n, const float* raw_prev, const float* raw_cur, const float* raw_next, const float* flow_prev,
-           const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, void* stream);
-
-}  // namespace
-
-extern "C" {
 
 // A frame-step is ~30-45 launches.  The schedule is fixed by (configuration, options, first-frame flag) and the six
 // caller pointers, so each distinct pointer set can be captured once into a hipGraph (on a stream of the handle) and
@@ -1541,6 +1525,100 @@ extern "C" {
 // B = 1 2110 vs 2440 frames/s, B = 4 5035 vs 5320; 720p B = 1 398.6 vs 404.5, B = 4 456.9 vs 459.4).  The eager path
 // is not host-bound -- launches are asynchronous and the queue stays full -- and kernel boundaries cost the same
 // either way, so a graph has only its own launch cost to add.  Parity is identical (the GPU suite passes in both modes).
+// Where no graph can be made, this step and every later one of the handle are enqueued launch by launch instead.
+int replay_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
+    rvdd_handle::StepKey key{{p.init ? p.raw_prev : nullptr, p.raw_cur, p.raw_next, p.flow_prev, p.flow_next, p.out_rgb},
+                             {p.raw_stride, p.flow_stride}, (p.init ? 1 : 0) | (h->serpentine ? 2 : 0) | (h->step_ctr << 2)};
+    auto it = h->graphs.find(key);
+    if (it == h->graphs.end()) {
+        hipGraph_t g = nullptr;
+        hipGraphExec_t ex = nullptr;
+        hipError_t e = hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal);
+        int rc = RVDD_OK;
+        if (e == hipSuccess) {
+            rc = enqueue_step(h, p, h->gstream);
+            e = hipStreamEndCapture(h->gstream, &g);
+        }
+        if (e == hipSuccess && rc == RVDD_OK) e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+        if (e != hipSuccess || rc != RVDD_OK) {
+            // no graph for this process: run this step and every later one launch by launch, on the caller's stream
+            // (whatever failed -- the capture, the instantiation or a launch inside the capture -- nothing has run yet)
+            if (g) (void)hipGraphDestroy(g);
+            (void)hipGetLastError();
+            h->use_graphs = 0;
+            return enqueue_step(h, p, s);
+        }
+        if (h->graphs.size() >= kMaxStepGraphs) {
+            auto old = h->graphs.begin();
+            for (auto jt = h->graphs.begin(); jt != h->graphs.end(); ++jt)
+                if (jt->second.last_use < old->second.last_use) old = jt;
+            (void)hipGraphExecDestroy(old->second.exec);
+            (void)hipGraphDestroy(old->second.graph);
+            h->graphs.erase(old);
+        }
+        rvdd_handle::StepGraph sg;
+        sg.graph = g;
+        sg.exec = ex;
+        it = h->graphs.emplace(key, sg).first;
+    }
+    it->second.last_use = ++h->graph_tick;
+    HIPCHK(h, hipEventRecord(h->g_in, s));
+    HIPCHK(h, hipStreamWaitEvent(h->gstream, h->g_in, 0));
+    HIPCHK(h, hipGraphLaunch(it->second.exec, h->gstream));
+    HIPCHK(h, hipEventRecord(h->g_out, h->gstream));
+    HIPCHK(h, hipStreamWaitEvent(s, h->g_out, 0));
+    return RVDD_OK;
+}
+
+// A step over slots [0, n) has been enqueued: their marks are spent (`keep`: those of the others), the slots that sat it
+// out are undefined, the amax words' set and slots (step_amax) and the sequence order move on.  A step that failed half
+// way never gets here: the handle still asks for the first frame of a video (raw_prev, zeroed features), never for a
+// later frame on stale state.
+void commit_step(rvdd_t* h, int n, uint64_t keep) {
+    h->reset_marks = keep;
+    h->undef_mask = slots_below(h->cfg.batch) & ~slots_below(n);
+    h->step_ctr = (h->step_ctr + 1) % 6;
+    if (seq_major_on(h, n)) h->serpentine = !h->serpentine;
+}
+
+// rvdd_step_strided (n = cfg.batch) and rvdd_step_live: validate, plan, enqueue or replay, commit
+int step_n(rvdd_t* h, const int n, const float* raw_prev, const float* raw_cur, const float* raw_next, const float* flow_prev,
+           const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, void* stream) {
+    ENTER(h);
+    if (!h->finalized) return fail(h, RVDD_ERR_STATE, "rvdd_step: weights not finalized");
+    {
+        const int64_t rd = (int64_t)4 * (h->cfg.height / 2) * (h->cfg.width / 2), fd = rd / 2;
+        if ((raw_stride && raw_stride < rd) || (flow_stride && flow_stride < fd))
+            return fail(h, RVDD_ERR_ARG, "rvdd_step_strided: a batch stride must be 0 (dense) or at least one sequence (%lld / %lld floats)",
+                        (long long)rd, (long long)fd);
+    }
+    const bool nw = h->no_warp;
+    if (!raw_cur || (!flow_prev && !nw) || !out_rgb) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_cur, flow_prev and out_rgb are required");
+    if (h->cfg.future && (!raw_next || (!flow_next && !nw))) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_next and flow_next are required when future=1");
+    if (nw) flow_prev = flow_next = nullptr;      // the flows are not looked at (the reference's dataset does not even load them)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the marks of the covered slots are this step's, those of the others stay pending.  Every covered slot marked = the
+    // first step of a handle of n sequences, launch for launch (one demosaic, memsets), not the per-run latch of `pend`.
+    const uint64_t live = slots_below(n), keep = h->reset_marks & ~live;
+    const bool init = (h->reset_marks & live) == live;
+    const uint64_t pend = init ? 0 : h->reset_marks & live;
+    if (const uint64_t bad = h->undef_mask & live & ~(init ? live : pend))
+        return fail(h, RVDD_ERR_STATE, "rvdd_step: the state of slot %d is undefined (it sat out a step of fewer slots, or was moved "
+                    "away): mark it with rvdd_reset_slots, set its state, or move a sequence into it first", __builtin_ctzll(bad));
+    if ((init || pend) && !raw_prev) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_prev is required on the first step of a video");
+    const StepPlan plan{n, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, pend};
+    // never captured: a profiled step, the first step of a handle, a partial reset, a step of some slots
+    const bool replay = h->use_graphs && !h->prof_on && h->ran_eagerly && h->gstream && !pend && n == h->cfg.batch;
+    h->ran_eagerly = true;
+    RC(replay ? replay_step(h, plan, s) : enqueue_step(h, plan, s));
+    commit_step(h, n, keep);
+    return RVDD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int rvdd_step(rvdd_t* h, const float* raw_prev, const float* raw_cur, const float* raw_next,
               const float* flow_prev, const float* flow_next, float* out_rgb, void* stream) {
     return rvdd_step_strided(h, raw_prev, raw_cur, raw_next, flow_prev, flow_next, 0, 0, out_rgb, stream);
@@ -1584,130 +1662,19 @@ int rvdd_move_slots(rvdd_t* h, const int32_t* from, const int32_t* to, int32_t c
     // (disjoint slots below 64: count <= 32 = kMaxMovePairs)
     ENTER(h);
     const size_t img = (size_t)H * W;
-    const bool words = h->bfp && h->split16 && !h->is_next();
     HIPCHK(h, launch_move_slots(from, to, count, h->lastden4, (int64_t)img * 4, h->has_feat() ? h->lastfeat : nullptr, (int64_t)img * kF,
-                                words ? h->amax : nullptr, AMAX_SLOTS, B, static_cast<hipStream_t>(stream)));
+                                h->amax_on() ? h->amax : nullptr, AMAX_SLOTS, B, static_cast<hipStream_t>(stream)));
     // the host-side marks travel with the state; the source is undefined from here on (and has no mark of its own any more)
-    uint64_t marks = reset_marks(h), undef = h->undef_mask;
+    uint64_t marks = h->reset_marks, undef = h->undef_mask;
     for (int k = 0; k < count; ++k) {
         const uint64_t f = 1ull << from[k], t = 1ull << to[k];
         marks = (marks & ~(f | t)) | ((marks & f) ? t : 0);
         undef = (undef & ~t) | ((undef & f) ? t : 0) | f;
     }
-    set_reset_marks(h, marks);
+    h->reset_marks = marks;
     h->undef_mask = undef;
     return RVDD_OK;
 }
-
-}  // extern "C"
-
-namespace {
-
-// rvdd_step_strided (n = cfg.batch) and rvdd_step_live
-int step_n(rvdd_t* h, const int n, const float* raw_prev, const float* raw_cur, const float* raw_next, const float* flow_prev,
-           const float* flow_next, int64_t raw_stride, int64_t flow_stride, float* out_rgb, void* stream) {
-    ENTER(h);
-    if (!h->finalized) return fail(h, RVDD_ERR_STATE, "rvdd_step: weights not finalized");
-    {
-        const int64_t rd = (int64_t)4 * (h->cfg.height / 2) * (h->cfg.width / 2), fd = rd / 2;
-        if ((raw_stride && raw_stride < rd) || (flow_stride && flow_stride < fd))
-            return fail(h, RVDD_ERR_ARG, "rvdd_step_strided: a batch stride must be 0 (dense) or at least one sequence (%lld / %lld floats)",
-                        (long long)rd, (long long)fd);
-    }
-    const bool nw = h->no_warp;
-    if (!raw_cur || (!flow_prev && !nw) || !out_rgb) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_cur, flow_prev and out_rgb are required");
-    if (h->cfg.future && (!raw_next || (!flow_next && !nw))) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_next and flow_next are required when future=1");
-    if (nw) flow_prev = flow_next = nullptr;      // the flows are not looked at (the reference's dataset does not even load them)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // need_init is cleared only once the step has been enqueued: a step that failed half way leaves the handle asking
-    // for the first frame of a video again (raw_prev, zeroed features), never a later frame on stale state
-    const int B = h->cfg.batch;
-    const bool part = n < B;                       // (B <= 64 then: rvdd_step_live)
-    bool init = h->need_init;
-    uint64_t pend = init ? 0 : h->pend_mask, keep = 0;
-    if (part) {
-        // the marks of the live slots are this step's; those of the others stay pending.  Every live slot marked = the first
-        // step of a handle of n sequences, launch for launch.
-        const uint64_t marks = reset_marks(h), live = slots_below(n);
-        keep = marks & ~live;
-        init = (marks & live) == live;
-        pend = init ? 0 : marks & live;
-    }
-    if (h->undef_mask) {
-        const uint64_t covered = slots_below(part ? n : (B < 64 ? B : 64));
-        if (const uint64_t bad = h->undef_mask & covered & ~(init ? covered : pend))
-            return fail(h, RVDD_ERR_STATE, "rvdd_step: the state of slot %d is undefined (it sat out a step of fewer slots, or was moved "
-                        "away): mark it with rvdd_reset_slots, set its state, or move a sequence into it first", __builtin_ctzll(bad));
-    }
-    if ((init || pend) && !raw_prev) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_prev is required on the first step of a video");
-    auto eager = [&]() -> int {
-        LiveScope live(h, n);
-        const int rc = enqueue_step(h, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, pend, s);
-        if (rc == RVDD_OK) {
-            h->need_init = false;
-            h->pend_mask = keep;
-            h->undef_mask = part ? (h->undef_mask & ~slots_below(n)) | (slots_below(B) & ~slots_below(n)) : 0;
-            h->step_ctr = (h->step_ctr + 1) % 6;      // (the amax words' set and slots follow it: & 1, % 3)
-        }
-        return rc;
-    };
-    if (!h->use_graphs || h->prof_on || !h->ran_eagerly || !h->gstream || pend || part) {      // a partial reset and a step of some slots are never captured
-        h->ran_eagerly = true;
-        return eager();
-    }
-    rvdd_handle::StepKey key{{init ? raw_prev : nullptr, raw_cur, raw_next, flow_prev, flow_next, out_rgb},
-                             {raw_stride, flow_stride}, (init ? 1 : 0) | (h->serpentine ? 2 : 0) | (h->step_ctr << 2)};
-    auto it = h->graphs.find(key);
-    if (it == h->graphs.end()) {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t ex = nullptr;
-        hipError_t e = hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal);
-        int rc = RVDD_OK;
-        if (e == hipSuccess) {
-            const bool serp = h->serpentine;
-            rc = enqueue_step(h, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, 0, h->gstream);
-            h->serpentine = serp;                              // the replay below advances it
-            e = hipStreamEndCapture(h->gstream, &g);
-        }
-        if (e == hipSuccess && rc == RVDD_OK) e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-        if (e != hipSuccess || rc != RVDD_OK) {
-            // no graph for this process: run this step and every later one launch by launch, on the caller's stream
-            // (whatever failed -- the capture, the instantiation or a launch inside the capture -- nothing has run yet)
-            if (g) (void)hipGraphDestroy(g);
-            (void)hipGetLastError();
-            h->use_graphs = 0;
-            return eager();
-        }
-        if (h->graphs.size() >= kMaxStepGraphs) {
-            auto old = h->graphs.begin();
-            for (auto jt = h->graphs.begin(); jt != h->graphs.end(); ++jt)
-                if (jt->second.last_use < old->second.last_use) old = jt;
-            (void)hipGraphExecDestroy(old->second.exec);
-            (void)hipGraphDestroy(old->second.graph);
-            h->graphs.erase(old);
-        }
-        rvdd_handle::StepGraph sg;
-        sg.graph = g;
-        sg.exec = ex;
-        it = h->graphs.emplace(key, sg).first;
-    }
-    it->second.last_use = ++h->graph_tick;
-    HIPCHK(h, hipEventRecord(h->g_in, s));
-    HIPCHK(h, hipStreamWaitEvent(h->gstream, h->g_in, 0));
-    HIPCHK(h, hipGraphLaunch(it->second.exec, h->gstream));
-    HIPCHK(h, hipEventRecord(h->g_out, h->gstream));
-    HIPCHK(h, hipStreamWaitEvent(s, h->g_out, 0));
-    h->need_init = false;
-    h->pend_mask = 0;
-    h->undef_mask = 0;
-    h->step_ctr = (h->step_ctr + 1) % 6;
-    if (seq_major_on(h)) h->serpentine = !h->serpentine;
-    return RVDD_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int rvdd_get_state(rvdd_t* h, float* lastden, float* lastfeat, void* stream) {
     if (!h) return RVDD_ERR_ARG;
@@ -1730,15 +1697,14 @@ int rvdd_set_state(rvdd_t* h, const float* lastden, const float* lastfeat, void*
     if (lastfeat && !h->has_feat()) return fail(h, RVDD_ERR_ARG, "rvdd_set_state: this architecture has no recurrent features");
     if (lastden) {
         HIPCHK(h, launch_nchw_to_nhwc(lastden, h->lastden4, B, 3, H, W, 4, s));
-        h->need_init = false;
-        h->pend_mask = 0;
+        h->reset_marks = 0;
         h->undef_mask = 0;
     }
     if (lastfeat) HIPCHK(h, launch_nchw_to_nhwc(lastfeat, h->lastfeat, B, kF, H, W, kF, s));
-    if ((lastden || lastfeat) && h->bfp && h->split16 && !h->is_next()) {
+    if ((lastden || lastfeat) && h->amax_on()) {
         // The words the next step reads as the bound of "the previous output" (block floating point): features and output frame
         // together, as PostConvs leaves them -- rebuilt from the state as it now stands, whichever half the caller replaced
-        unsigned* w = amax_words(h, AMAX_FEAT0 + (h->step_ctr + 2) % 3);
+        unsigned* w = amax_words(h, step_amax(h->step_ctr).feat_in);
         HIPCHK(h, hipMemsetAsync(w, 0, amax_bytes(B, 1), s));
         if (h->has_feat()) HIPCHK(h, launch_amax_reduce(h->lastfeat, B, (int64_t)H * W * kF, w, s));
         HIPCHK(h, launch_amax_reduce(h->lastden4, B, (int64_t)H * W * 4, w, s));
@@ -1807,15 +1773,16 @@ int rvdd_unet_forward(rvdd_t* h, const float* x, const float* feat_in, float* ou
     HIPCHK(h, launch_nchw_to_nhwc(x, h->netin, B, h->cin_real(), H, W, kNetInC, s));
     if (h->has_feat()) HIPCHK(h, launch_nchw_to_nhwc(feat_in, h->featw, B, kF, H, W, kF, s));
     // amax words of the caller's maps (block floating point of the split-f16 convs); the recurrent features' words stay as they are
-    h->amax_base = 2 * AMAX_NREG;              // the set of its own: the frame-steps' sets and the recurrent slots stay untouched
-    h->amax_feat_in = h->amax_base + AMAX_REL_FWDFEAT;
-    h->amax_post_out = amax_layer(h, CU_POST);
-    if (h->bfp && h->split16 && !h->is_next()) {
-        HIPCHK(h, hipMemsetAsync(amax_words(h, h->amax_base), 0, amax_bytes(B, AMAX_NREG), s));
-        HIPCHK(h, launch_amax_reduce(h->netin, B, (int64_t)H * W * kNetInC, amax_words(h, h->amax_base + AMAX_REL_NETIN), s));
-        if (h->has_feat()) HIPCHK(h, launch_amax_reduce(h->featw, B, (int64_t)H * W * kF, amax_words(h, h->amax_feat_in), s));
+    NetRun run;
+    run.n = B;
+    run.amax = forward_amax();
+    if (h->amax_on()) {
+        HIPCHK(h, hipMemsetAsync(amax_words(h, run.amax.base), 0, amax_bytes(B, AMAX_NREG), s));
+        HIPCHK(h, launch_amax_reduce(h->netin, B, (int64_t)H * W * kNetInC, amax_words(h, run.amax.base + AMAX_REL_NETIN), s));
+        if (h->has_feat()) HIPCHK(h, launch_amax_reduce(h->featw, B, (int64_t)H * W * kF, amax_words(h, run.amax.feat_in), s));
     }
-    RC(run_net(h, h->netin, h->featw, h->lv[0].t[2], out, nullptr, s, nullptr));
+    RC(run_net(h, run, h->netin, h->featw, h->lv[0].t[2], out, nullptr, s));
+    if (seq_major_on(h, B) && !h->is_next()) h->serpentine = !h->serpentine;      // the order alternates with every forward
     if (h->has_feat() && feat_out) HIPCHK(h, launch_nhwc_to_nchw(h->lv[0].t[2], feat_out, B, kF, H, W, kF, s));
     return RVDD_OK;
 }
@@ -1908,8 +1875,12 @@ int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, 
     return RVDD_OK;
 }
 
-int rvdd_tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny,
-                        int32_t* iterations, void* stream) {
+}  // extern "C"
+
+namespace {
+// rvdd_tvl1flow_batch; `async`: without iteration counts the batch is enqueued and the call returns (option "tvl1_async")
+int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
+                   void* stream, bool async) {
     if (h && n == 0) return RVDD_OK;
     if (!h || !I0 || !I1 || !u || n < 0 || nx < 16 || ny < 16)
         return fail(h, RVDD_ERR_ARG, "rvdd_tvl1flow_batch: bad argument (images must be >= 16x16)");
@@ -1924,10 +1895,18 @@ int rvdd_tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, i
         HIPCHK(h, tvl1_alloc(&h->tvl1, nx, ny));
     }
     std::vector<int> it((size_t)n, 0);
-    HIPCHK(h, tvl1_run_batch(h->tvl1, I0, I1, u, n, static_cast<hipStream_t>(stream), iterations ? it.data() : nullptr, h->tvl1_async));
+    HIPCHK(h, tvl1_run_batch(h->tvl1, I0, I1, u, n, static_cast<hipStream_t>(stream), iterations ? it.data() : nullptr, async));
     if (iterations)
         for (int i = 0; i < n; ++i) iterations[i] = it[(size_t)i];
     return RVDD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rvdd_tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny,
+                        int32_t* iterations, void* stream) {
+    return tvl1flow_batch(h, I0, I1, u, n, nx, ny, iterations, stream, h && h->tvl1_async);
 }
 
 int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
@@ -2042,11 +2021,7 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
         HIPCHK(h, launch_stream_gather(gray_at(pc), gray_at(pp), fut ? gray_at(pos) : nullptr, st.dgray, den_slots, st.I0, st.I1, ready.data(), nready, B,
                                        (int64_t)hw, s));
         float* u = nready == B ? st.flows : st.u;      // every slot ready: the batch writes the step's flows itself
-        const bool was_async = h->tvl1_async;
-        h->tvl1_async = true;
-        const int rc = rvdd_tvl1flow_batch(h, st.I0, st.I1, u, nready * (1 + fut), ww, hh, nullptr, stream);
-        h->tvl1_async = was_async;
-        RC(rc);
+        RC(tvl1flow_batch(h, st.I0, st.I1, u, nready * (1 + fut), ww, hh, nullptr, stream, true));
         if (nready != B) HIPCHK(h, launch_stream_scatter(st.u, st.flows, ready.data(), nready, 1 + fut, B, (int64_t)hw, s));
         flow_prev = st.flows;
         flow_next = fut ? st.flows + (size_t)B * 2 * hw : nullptr;
@@ -2114,10 +2089,13 @@ int rvdd_debug_conv_bench(rvdd_t* h, int32_t variant, int32_t level, int32_t ite
     ConvCall c;
     c.in = h->lv[level].t[0]; c.out = h->lv[level].t[1]; c.H = h->lv[level].H; c.W = h->lv[level].W; c.epi = EPI_RELU;
     const Conv3& L = h->cu[CU_ENC1_1];
-    int rc = run_conv(h, L, c, s);   // warm-up (also sets the function attribute)
+    NetRun run;
+    run.n = h->cfg.batch;
+    const Sub all{0, run.n};
+    int rc = run_conv(h, run, L, c, s, all);   // warm-up (also sets the function attribute)
     if (rc == RVDD_OK) {
         (void)hipEventRecord(h->t0, s);
-        for (int i = 0; i < iters && rc == RVDD_OK; ++i) rc = run_conv(h, L, c, s);
+        for (int i = 0; i < iters && rc == RVDD_OK; ++i) rc = run_conv(h, run, L, c, s, all);
         (void)hipEventRecord(h->t1, s);
         (void)hipEventSynchronize(h->t1);
         float t = 0.f;

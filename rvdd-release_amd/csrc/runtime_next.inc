@@ -197,17 +197,13 @@ int finalize_convnext(rvdd_t* h) {
     return RVDD_OK;
 }
 
-// Sequences [sb.b0, sb.b0 + sb.nb) of the batch on stream s.
-int run_convnext(rvdd_t* h, const float* netin, const float* featw, float* feat_dst, float* out_nchw,
-                 float* out_nhwc4, hipStream_t s, Sub sb) {
+// The sequences of `run` on stream s.
+int run_convnext(rvdd_t* h, const NetRun& run, const float* netin, const float* featw, float* feat_dst, float* out_nchw,
+                 float* out_nhwc4, hipStream_t s) {
     const bool feat = h->has_feat();
-    const int B = sb.nb;
-    const size_t b0 = (size_t)sb.b0;
+    const int B = run.n;
     Level* lv = h->lv;
     const NextBlk* blocks = h->nx;
-    // The slice of this chain's sequences in a workspace map of level l: always at the level's own batch stride, also
-    // where a chain packs smaller maps ([nb][uh][uw], the upsampled size before zero_pad_features) into it -- the two
-    // chains run concurrently and their slices must never overlap.
     // the fused kernel takes the split-f16 filter fragments unless the option asks for the f32-MFMA form
     auto fused_w = [&](const NextBlk& nb) {
         NextBlockW w = nb.w;
@@ -215,9 +211,8 @@ int run_convnext(rvdd_t* h, const float* netin, const float* featw, float* feat_
         w.pipe = h->next_pipe ? 1 : 0;
         return w;
     };
-    auto at = [&](const float* p, int hh, int ww, int c = kF) { return const_cast<float*>(p) + b0 * hh * ww * c; };
-    auto T = [&](int l, int k) { return at(lv[l].t[k], lv[l].H, lv[l].W); };
-    auto SKIP = [&](int l) { return at(lv[l].skip, lv[l].H, lv[l].W); };
+    auto T = [&](int l, int k) { return lv[l].t[k]; };
+    auto SKIP = [&](int l) { return lv[l].skip; };
     // ConvBlock on an already-projected 48-channel map (new_unet.py:90-103)
     auto block = [&](int bi, const float* x, float* out, int lvl, int Hh, int Ww) -> int {
         const NextBlk& nb = blocks[bi];
@@ -236,8 +231,6 @@ int run_convnext(rvdd_t* h, const float* netin, const float* featw, float* feat_
     };
     const int H0 = lv[0].H, W0 = lv[0].W;
     const int64_t np0 = (int64_t)B * H0 * W0;
-    netin = at(netin, H0, W0, kNetInC);
-    if (featw) featw = at(featw, H0, W0);
 
     // The 96 -> 48 projection of decoder_convs[i].blocks[0] (cat((x_dec, x_enc)), :321-329) as two halves in the epilogues of the
     // blocks that form x_enc (the last block of encoder level hi = 2 - i) and x_dec (decoder_ups[i]): where the upsampled map has the
@@ -258,18 +251,18 @@ int run_convnext(rvdd_t* h, const float* netin, const float* featw, float* feat_
     // ---- preprocessing + encoder level 0
     const float* e0 = T(0, 0);          // the projected input of encoder_convs[0].blocks[0], and the map that block writes
     float* e1 = T(0, 1);
-    if (feat && h->featw_proj) {
-        if (!h->netin_proj) RC(proj(NX_PRE, netin, nullptr, T(0, 0), np0));
+    if (feat && run.featw_proj) {
+        if (!run.netin_proj) RC(proj(NX_PRE, netin, nullptr, T(0, 0), np0));
         NextProj pj = blocks[NX_ENC0_0].half[0];
         pj.add = featw;                                                                  // W_f warp(features) + bias
         RC(block_proj(NX_PRE, T(0, 0), T(0, 1), nullptr, pj, H0, W0));
         e0 = T(0, 1);
         e1 = T(0, 0);
     } else if (feat) {
-        if (!h->netin_proj) RC(proj(NX_PRE, netin, nullptr, T(0, 0), np0));
+        if (!run.netin_proj) RC(proj(NX_PRE, netin, nullptr, T(0, 0), np0));
         RC(block(NX_PRE, T(0, 0), T(0, 1), 0, H0, W0));
         RC(proj(NX_ENC0_0, T(0, 1), featw, T(0, 0), np0));                              // cat[y, old_features] :381-382
-    } else if (!h->netin_proj) {
+    } else if (!run.netin_proj) {
         RC(proj(NX_ENC0_0, netin, nullptr, T(0, 0), np0));
     }
     // the last block of an encoder level feeds MaxPool2d(2) (DownConv, :200-204): the fused kernel pools in its epilogue
@@ -335,9 +328,7 @@ int run_convnext(rvdd_t* h, const float* netin, const float* featw, float* feat_
         d = T(hi, 0);
     }
     // ---- post-processing: two blocks (the second one is the hooked feature map :414-417), 1x1 -> 3
-    float* fdst = at(feat_dst ? feat_dst : lv[0].t[2], H0, W0);
-    float* o_nchw = out_nchw ? out_nchw + b0 * 3 * H0 * W0 : nullptr;
-    float* o_nhwc4 = out_nhwc4 ? out_nhwc4 + b0 * 4 * H0 * W0 : nullptr;
+    float* fdst = feat_dst ? feat_dst : lv[0].t[2];
     float* p0 = d == T(0, 1) ? T(0, 0) : T(0, 1);
     RC(block(NX_POST0, d, p0, 0, H0, W0));
     {
@@ -345,7 +336,7 @@ int run_convnext(rvdd_t* h, const float* netin, const float* featw, float* feat_
         const NextBlk& nb = blocks[NX_POST1];
         const double px = (double)np0;
         Scope sc(h, s, "convblock_kernel", (2.0 * 49 * 48 + 2.0 * 2 * 48 * 192 + 2.0 * 48 * 3) * px, px * (384.0 + 12.0 + 16.0));
-        HIPCHK(h, launch_next_block_out3(p0, fdst, fused_w(nb), B, H0, W0, h->w_out, h->b_out, o_nchw, o_nhwc4, s));
+        HIPCHK(h, launch_next_block_out3(p0, fdst, fused_w(nb), B, H0, W0, h->w_out, h->b_out, out_nchw, out_nhwc4, s));
     }
     return RVDD_OK;
 }
