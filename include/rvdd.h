@@ -390,6 +390,11 @@ int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, 
  *               input plus a fix of the border ring, where the zero padding between the two layers matters (default 1, the
  *               feature-recurrent convunet on the split-f16 path; the A/B reference: the same linear map, summed in another
  *               order, a few 1e-7 apart).
+ *   "pre5_cin8": 0 = the composed first layer ("fuse_pre") multiplies all 16 channels of the network input's pixel, 25 taps x 2
+ *               eight-channel groups = 13 chunks of K, also where at most 8 of them are real.  Default 1: a network without a
+ *               future frame (6 real channels) multiplies the first eight only, 25 groups = 7 chunks -- the other group of every
+ *               tap is zero filters on zero input; half the halo loads, splits and staging stores as well.  The same linear map
+ *               with K grouped differently (a few 1e-6 apart).  Inert with a future frame (9 channels).  Per handle.
  *   "block_fp": 0 = the split-f16 convs split their operands without the per-map power of two (the A/B reference of the block
  *               floating point; right only while every activation stays within 2^-14 .. 65504).  Default 1.
  *   "bayer_pattern": enum rvdd_bayer of the packed raw frames rvdd_step is handed (--bayer_pattern): every demosaic and

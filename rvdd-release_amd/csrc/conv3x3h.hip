@@ -23,7 +23,8 @@
 //
 // Orientation as conv3x3.hip: D[cout][pixel] += W[cout][k] X[k][pixel]; lane l holds pixel l & 15 and, per MFMA, the
 // eight consecutive k of group l >> 4.  k runs (tap, channel): 8-channel group G = 4 chunk + (l >> 4) is channels
-// 8 (G % 6) .. +7 of tap G / 6 (CIN = 48: 54 groups, 14 chunks of 32, the last two groups zero filters).
+// 8 (G % 6) .. +7 of tap G / 6 (CIN = 48: 54 groups, 14 chunks of 32, the last two groups zero filters).  The composed 5x5 first layer
+// (KS = 5): CIN = 16, two groups per tap, 13 chunks; CIN = 8 (at most 8 real channels: no future frame), one group per tap, 7 chunks.
 //
 // Work: a persistent workgroup of 8 waves per CU walks 16x16-pixel tiles.  The 18x18 halo tile is fetched as f32 into
 // registers one tile ahead (buffer loads, out-of-image pixels zero-filled by out-of-range offsets = padding 1), split
@@ -50,6 +51,11 @@ typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int TW = 16;
 constexpr int NTHREADS = 512;
+// LDS bytes per pixel of the two planes of the 8-channel first layer (HGeo CIN = 8: ONE group per tap, so the four groups of a B
+// fragment sit at four PIXELS).  16: with the 20-pixel halo row two taps in a row of the K order are 1 or 16 pixels apart, and a 16-lane
+// group of ds_read_b128 (lanes n of one tap with lanes n' of the next) then meets the SAME 16 bytes or another bank -- conflict-free
+// (tools/lds_b128_bench.hip, the "c8 5x5" patterns); 32, the 16-channel pitch with its second half unused, is two-way everywhere.
+constexpr int C8_PITCH = 16;
 
 // NGRP = 1 (the library): the eight waves of a workgroup share one 16x16-pixel tile.  NGRP = 2 (round 4, the harness only):
 // two GROUPS of four waves, one wave of each per SIMD, each group with its own 8x16-pixel tile, halo planes and barrier (an
@@ -73,15 +79,19 @@ struct HGeo {
     static constexpr int IW = TW + KS - 1;
     static constexpr int NT = NTHREADS / NGRP;               // threads of a group
     static constexpr int WPG = NT / 64;                      // waves of a group
+    static constexpr int CMEM = CIN == 8 ? 16 : CIN;         // floats of one input pixel IN MEMORY; CIN = the channels staged and multiplied.
+                                                             // CIN = 8: the first 8 channels of the NHWC16 network input, whose other 8 are
+                                                             // zero without a future frame (6 real channels) -- half the halo loads, splits
+                                                             // and staging stores per pixel, and one group per tap
     static constexpr int GPT = CIN / 8;                      // 8-channel groups per tap
     static constexpr int NG = KS * KS * GPT;                 // groups of the whole filter
     static constexpr int NCH = (NG + 3) / 4;                 // K chunks of 32 (one MFMA deep)
     static constexpr int HI = CIN * 2;                       // bytes of one pixel's hi half
-    static constexpr int S = HI;                             // LDS bytes per pixel in EACH of the two planes (hi, lo): 96 / 32, an odd multiple of
+    static constexpr int S = CIN == 8 ? C8_PITCH : HI;       // LDS bytes per pixel in EACH of the two planes (hi, lo): 96 / 32, an odd multiple of
                                                              // 32 -- every fragment pattern of the kernel is conflict-free
                                                              // (tools/lds_b128_bench.hip; 192 or 208 are 2-way), and 10 KiB less than one
                                                              // interleaved [hi | lo | pad] image of 224 B per pixel
-    static constexpr int PLANE = IH * IW * HI;
+    static constexpr int PLANE = IH * IW * S;
     static constexpr int W_BYTES = NCH * MT * 2 * 1024;
     static constexpr int I_BYTES = 2 * PLANE;                // one group's two planes
     static constexpr int P_FLOATS = 48 + 3 * 48 + 4 + 8 + 4; // bias, PostConvs[1] weights and bias, one word per wave (amax reduction), the groups' barrier counters
@@ -168,6 +178,7 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
 #endif
     const int mt0 = MT == 3 ? 0 : (int)blockIdx.y;      // first 16-channel output block of this workgroup
     constexpr int TH = G::TH, IH = G::IH, IW = G::IW, PAD = G::PAD;
+    constexpr int PXB = G::CMEM * 4;                    // bytes of one input pixel in memory
     static_assert(KS == 3 || (!UPS && !ACC_IN), "the 5x5 form exists for the composed first layer only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef __attribute__((address_space(3))) unsigned char lds_u8;
@@ -271,7 +282,7 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
     const int hx = rem / G::SEG;
     const int part = rem - hx * G::SEG;
     const bool ld_thread = rp < G::RPR;
-    const int g_lane = (rp * a.W + hx) * (CIN * 4) + part * 16;           // byte offset inside the image, relative to the halo origin
+    const int g_lane = (rp * a.W + hx) * PXB + part * 16;           // byte offset inside the image, relative to the halo origin
     const unsigned l_lane = plane0 + (unsigned)((rp * IW + hx) * G::S + part * 8);
     // One round = one 16-B load per thread (RPR halo rows).  The rounds of the NEXT tile are issued one per chunk inside
     // this tile's MFMA loop (a CU's texture path moves 64 B per clock: the 72 KiB of a halo tile are 1100 cycles of it, and
@@ -291,21 +302,21 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
     auto source = [&](const TilePos& p, bool live) {
         Src q;
         const int ih = UPS ? a.H >> 1 : a.H, iw = UPS ? a.W >> 1 : a.W;
-        q.r = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)(live ? p.b : 0) * ih * iw * CIN), 0,
-                                                live ? (unsigned)(ih * iw * CIN * 4) : 0, 0x00020000);
+        q.r = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)(live ? p.b : 0) * ih * iw * G::CMEM), 0,
+                                                live ? (unsigned)(ih * iw * PXB) : 0, 0x00020000);
         const bool xok = ld_thread && (unsigned)(p.x0 - PAD + hx) < (unsigned)a.W;
-        q.base = xok ? (unsigned)(g_lane + ((p.y0 - PAD) * a.W + (p.x0 - PAD)) * (CIN * 4)) : 0x80000000u;
+        q.base = xok ? (unsigned)(g_lane + ((p.y0 - PAD) * a.W + (p.x0 - PAD)) * PXB) : 0x80000000u;
         q.y0 = p.y0;
         q.x0 = p.x0;
         q.soff = -1;
         if constexpr (UPS) {
-            if (p.y0 >= 16 && p.y0 + IH <= a.H && p.x0 >= 16 && p.x0 + IW <= a.W) q.soff = (((p.y0 >> 1) - 1) * iw + (p.x0 >> 1) - 1) * (CIN * 4);
+            if (p.y0 >= 16 && p.y0 + IH <= a.H && p.x0 >= 16 && p.x0 + IW <= a.W) q.soff = (((p.y0 >> 1) - 1) * iw + (p.x0 >> 1) - 1) * PXB;
         }
         return q;
     };
     // (one v_add per round; the image's rows above and below come out of the buffer's range check, see Src::base.  Rows of the
     // last round beyond the halo, CIN = 16, are loaded and not stored.)
-    auto fetch_round = [&](const Src& q, int r0) { pre[r0] = bload(q.r, q.base + (unsigned)(r0 * G::RPR * a.W * (CIN * 4))); };
+    auto fetch_round = [&](const Src& q, int r0) { pre[r0] = bload(q.r, q.base + (unsigned)(r0 * G::RPR * a.W * PXB)); };
     // ---- UPS: the halo tile in 2x2 blocks.  Upsampled rows 2i+1, 2i+2 interpolate between the SAME two source rows
     // (i, i+1, clamped as ATen clamps them), columns alike, and a tile's halo starts at an odd row and column: its 18x18
     // pixels are 9x9 such blocks, each from four source pixels.  One work item = one block x one 16-B channel piece: four
@@ -355,15 +366,15 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
     int u_off00[UNR];
 #pragma unroll
     for (int r0 = 0; r0 < UNR; ++r0)
-        u_off00[r0] = U_OK(r0) ? ((U_BY(r0) * (a.W >> 1) + U_BX(r0)) * (CIN * 4) + U_PART(r0) * 16) : (int)0x80000000;
+        u_off00[r0] = U_OK(r0) ? ((U_BY(r0) * (a.W >> 1) + U_BX(r0)) * PXB + U_PART(r0) * 16) : (int)0x80000000;
     auto fetch_ups = [&](const Src& q, int r0) {
         const int ih = a.H >> 1, iw = a.W >> 1;
         if (q.soff >= 0) {
-            const int soff0 = q.soff, soff1 = soff0 + iw * (CIN * 4);
+            const int soff0 = q.soff, soff1 = soff0 + iw * PXB;
             ulo[r0][0] = bload(q.r, (unsigned)u_off00[r0], soff0);
-            ulo[r0][1] = bload(q.r, (unsigned)u_off00[r0] + (unsigned)(CIN * 4), soff0);
+            ulo[r0][1] = bload(q.r, (unsigned)u_off00[r0] + (unsigned)PXB, soff0);
             ulo[r0][2] = bload(q.r, (unsigned)u_off00[r0], soff1);
-            ulo[r0][3] = bload(q.r, (unsigned)u_off00[r0] + (unsigned)(CIN * 4), soff1);
+            ulo[r0][3] = bload(q.r, (unsigned)u_off00[r0] + (unsigned)PXB, soff1);
             return;
         }
         const int i = (q.y0 >> 1) - 1 + U_BY(r0), jx = (q.x0 >> 1) - 1 + U_BX(r0);
@@ -374,10 +385,10 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
         const bool any = U_OK(r0) && ((unsigned)Y0 < (unsigned)a.H || (unsigned)(Y0 + 1) < (unsigned)a.H) &&
                          ((unsigned)X0 < (unsigned)a.W || (unsigned)(X0 + 1) < (unsigned)a.W);
         const unsigned p16 = (unsigned)(U_PART(r0) * 16);
-        ulo[r0][0] = bload(q.r, any ? (unsigned)((rr0 * iw + cc0) * (CIN * 4)) + p16 : 0x80000000u);
-        ulo[r0][1] = bload(q.r, any ? (unsigned)((rr0 * iw + cc1) * (CIN * 4)) + p16 : 0x80000000u);
-        ulo[r0][2] = bload(q.r, any ? (unsigned)((rr1 * iw + cc0) * (CIN * 4)) + p16 : 0x80000000u);
-        ulo[r0][3] = bload(q.r, any ? (unsigned)((rr1 * iw + cc1) * (CIN * 4)) + p16 : 0x80000000u);
+        ulo[r0][0] = bload(q.r, any ? (unsigned)((rr0 * iw + cc0) * PXB) + p16 : 0x80000000u);
+        ulo[r0][1] = bload(q.r, any ? (unsigned)((rr0 * iw + cc1) * PXB) + p16 : 0x80000000u);
+        ulo[r0][2] = bload(q.r, any ? (unsigned)((rr1 * iw + cc0) * PXB) + p16 : 0x80000000u);
+        ulo[r0][3] = bload(q.r, any ? (unsigned)((rr1 * iw + cc1) * PXB) + p16 : 0x80000000u);
     };
     // vertical pass, then horizontal, each "a * wa, then one fused multiply-add": upsample2x_kernel's expressions in its order
     auto interp_ups = [&](const Src& q, int r0, float sc_st, auto scaled_tag) {
@@ -469,7 +480,10 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
     };
 
     const unsigned map_bytes = (unsigned)(a.H * a.W * kF * 4);
-    const unsigned out_bytes = (unsigned)(a.Hout * a.Wout * kF * 4);
+    // (CIN = 8, launch_conv5x5h_c8: the output map has the input's size and no offset -- four kernel arguments fewer held in
+    // scalar registers across the tile loop, which this instantiation then keeps without a spill)
+    constexpr bool SAME_OUT = CIN == 8;
+    const unsigned out_bytes = SAME_OUT ? map_bytes : (unsigned)(a.Hout * a.Wout * kF * 4);
 
     float sc_nxt = 1.f, inv_cur = 1.f, inv_nxt = 1.f;
     float amx = 0.f;        // max |x| of what this wave has stored for sequence amx_b
@@ -580,7 +594,7 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
             for (int nt = 0; nt < 2; ++nt) {
                 const bool ok = yy0 + nt < a.H && xx < a.W;
                 po[nt] = ok ? (unsigned)((((yy0 + nt) * a.W + xx) * kF + 4 * g) * 4) : 0x80000000u;
-                so[nt] = ok ? (unsigned)((((yy0 + nt + a.oy) * a.Wout + xx + a.ox) * kF + 4 * g) * 4) : 0x80000000u;
+                so[nt] = SAME_OUT ? po[nt] : ok ? (unsigned)((((yy0 + nt + a.oy) * a.Wout + xx + a.ox) * kF + 4 * g) * 4) : 0x80000000u;
             }
             if constexpr (EPI == EPI_POOL) {
                 const int pr_ = (cur.y0 >> 1) + gw, pc = xx >> 1;
@@ -755,7 +769,8 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
         }
         so_prev[0] = so[0];
         so_prev[1] = so[1];
-        orr_prev = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)cur.b * a.Hout * a.Wout * kF), 0, out_bytes, 0x00020000);
+        orr_prev = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)cur.b * (SAME_OUT ? a.H : a.Hout) * (SAME_OUT ? a.W : a.Wout) * kF), 0, out_bytes,
+                                                     0x00020000);
         STAMP(4);
         gsync();               // every wave of the group has read its last fragment of this tile: the next one may be staged
         STAMP(5);
@@ -831,7 +846,7 @@ hipError_t launch_h(const ConvArgs& a, hipStream_t s) {
 }  // namespace
 
 size_t conv3x3h_weight_bytes(int cin) { return cin == 48 ? HGeo<48, 1>::W_BYTES : HGeo<16, 1>::W_BYTES; }
-size_t conv5x5h_weight_bytes() { return HGeo<16, 1, 5>::W_BYTES; }
+size_t conv5x5h_weight_bytes(int cin) { return cin == 8 ? HGeo<8, 1, 5>::W_BYTES : HGeo<16, 1, 5>::W_BYTES; }
 
 // the composed 5x5 conv of the 16-channel network input (see HGeo): a.w = the bank arranged by arrange_conv3x3h(.., ks = 5), no
 // activation, a.bias = the composed bias; a.out = the partial sums the second source's pass starts from
@@ -839,6 +854,14 @@ hipError_t launch_conv5x5h_c16(const ConvArgs& a, hipStream_t s) {
     if (a.B <= 0 || a.H <= 0 || a.W <= 0) return hipSuccess;
     if ((size_t)a.H * a.W * kF * 4 >= 0x80000000ull || a.acc_in || a.ups) return hipErrorInvalidValue;
     return launch_g<16, EPI_NONE, false, false, 1, 5>(a, s);
+}
+// the same conv over the first 8 channels of the 16-channel pixel (a network input of at most 8 real channels): a.w = the bank
+// arranged by arrange_conv3x3h(.., cin_pad = 8, ks = 5), one group per tap, 7 chunks instead of 13
+hipError_t launch_conv5x5h_c8(const ConvArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.H <= 0 || a.W <= 0) return hipSuccess;
+    if ((size_t)a.H * a.W * kF * 4 >= 0x80000000ull || a.acc_in || a.ups) return hipErrorInvalidValue;
+    if (a.Hout != a.H || a.Wout != a.W || a.oy || a.ox) return hipErrorInvalidValue;      // (the kernel's SAME_OUT)
+    return launch_g<8, EPI_NONE, false, false, 1, 5>(a, s);
 }
 void conv3x3h_set_groups(int g) { g_conv3x3h_groups = g == 1 ? 1 : 2; }
 void conv3x3h_set_cout_split(bool on) { g_conv3x3h_cout_split = on; }

@@ -166,6 +166,9 @@ struct rvdd_handle {
     float* pre5_w = nullptr;  // the composed 5x5 bank (split f16)
     float pre5_inv = 1.f;
     float* pre5_b = nullptr;  // [48] composed bias
+    float* pre5_w8 = nullptr; // the same bank over the first 8 input channels only (7 chunks instead of 13): at most 8 real channels, else null
+    float pre5_inv8 = 1.f;
+    bool pre5_cin8 = true;    // option "pre5_cin8" 0: the 13-chunk bank also where the 7-chunk one exists (A/B reference)
     float* pre_w1 = nullptr;  // [9][16][48]: preprocessing_layer weight, tap-major, input channel, its output channel m (border fix)
     float* pre_b1 = nullptr;  // [48]
     float* pre_w2 = nullptr;  // [9][48 m][48 o]: EncoderConvs[0][0] weight over the preprocessing layer's channels (border fix)
@@ -388,7 +391,7 @@ std::vector<float> arrange_conv3x3h(const HostTensor& t, int c0, float* inv_scal
     const float sc = std::ldexp(1.0f, sft);
     *inv_scale = std::ldexp(1.0f, -sft);
     const size_t halves = (size_t)nch * 3 * 2 * 512;
-    if (halves * 2 != (ks == 5 ? conv5x5h_weight_bytes() : conv3x3h_weight_bytes(cin_pad))) return {};
+    if (halves * 2 != (ks == 5 ? conv5x5h_weight_bytes(cin_pad) : conv3x3h_weight_bytes(cin_pad))) return {};
     std::vector<uint16_t> bank(halves, 0);
     for (int G = 0; G < ng; ++G) {
         const int j = G / 4, g = G % 4, tap = G / gpt, cg = (G % gpt) * 8;
@@ -445,6 +448,10 @@ int compose_pre_enc0(rvdd_t* h) {
         bc[o] = (float)(b + (double)h->staged.at("EncoderConvs.0.blocks.0.0.bias").data[o]);      // + the layer's own bias (pass 1 adds it)
     }
     RC(upload(h, &h->pre5_w, arrange_conv3x3h(wc, 0, &h->pre5_inv, 16, 5)));
+    // without a future frame (6 real channels) the second 8-channel group of every tap is zero filters on zero input: the bank of
+    // the first groups alone, 25 groups in 7 chunks.  Both banks are kept, "pre5_cin8" chooses per launch.
+    h->pre5_w8 = nullptr;
+    if (h->cin_real() <= 8) RC(upload(h, &h->pre5_w8, arrange_conv3x3h(wc, 0, &h->pre5_inv8, 8, 5)));
     RC(upload(h, &h->pre5_b, bc));
     std::vector<float> a1((size_t)9 * 16 * 48, 0.f), a2((size_t)9 * 48 * 48);
     for (int e = 0; e < 9; ++e)
@@ -750,8 +757,9 @@ int run_pre5(rvdd_t* h, const NetRun& run, const float* netin, float* part, hipS
     const size_t px0 = (size_t)sub.b0 * H * W;
     ConvArgs a{};
     a.in = netin + px0 * kNetInC;
-    a.w = h->pre5_w;
-    a.wscale = h->pre5_inv;
+    const bool c8 = h->pre5_cin8 && h->pre5_w8;      // at most 8 real channels: only the first 8 of the 16-channel pixel are multiplied
+    a.w = c8 ? h->pre5_w8 : h->pre5_w;
+    a.wscale = c8 ? h->pre5_inv8 : h->pre5_inv;
     a.bias = h->pre5_b;
     a.out = part + px0 * kF;
     a.B = sub.nb;
@@ -760,8 +768,8 @@ int run_pre5(rvdd_t* h, const NetRun& run, const float* netin, float* part, hipS
     a.amax_in = h->bfp ? amax_words(h, run.amax.base + AMAX_REL_NETIN, sub.b0) : nullptr;
     const double px = (double)sub.nb * H * W;
     {
-        Scope sc(h, s, "conv5x5h_kernel<16>", 2.0 * 25.0 * h->cin_real() * 48.0 * px, px * 4.0 * (h->cin_real() + 48.0));
-        HIPCHK(h, launch_conv5x5h_c16(a, s));
+        Scope sc(h, s, c8 ? "conv5x5h_kernel<8>" : "conv5x5h_kernel<16>", 2.0 * 25.0 * h->cin_real() * 48.0 * px, px * 4.0 * (h->cin_real() + 48.0));
+        HIPCHK(h, c8 ? launch_conv5x5h_c8(a, s) : launch_conv5x5h_c16(a, s));
     }
     HIPCHK(h, launch_pre_border_fix(a.in, h->pre_w1, h->pre_b1, h->pre_w2, a.out, sub.nb, H, W, s));
     return RVDD_OK;
@@ -1280,6 +1288,12 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         h->fuse_pre = value != 0;
         return RVDD_OK;
     }
+    if (std::strcmp(name, "pre5_cin8") == 0) {
+        // 0 = the composed first layer multiplies all 16 channels of the network input's pixel (13 chunks) also where at most 8 are
+        // real and the 7-chunk bank exists (the A/B reference: the same map, K grouped differently)
+        h->pre5_cin8 = value != 0;
+        return RVDD_OK;
+    }
     if (std::strcmp(name, "block_fp") == 0) {
         // 0 = the split-f16 convs split their operands as they are (no per-map power of two): the round-3 behaviour, right only
         // while every activation stays inside 2^-14 .. 65504 -- kept as the A/B reference of the block floating point
@@ -1313,7 +1327,7 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         h->split16 = value == 0;
         return RVDD_OK;
     }
-    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, cout_split, small_prestage, bayer_pattern, stream_reset_each, stream_flow_from_denoised)", name);
+    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, pre5_cin8, cout_split, small_prestage, bayer_pattern, stream_reset_each, stream_flow_from_denoised)", name);
 }
 
 int rvdd_reset(rvdd_t* h) {

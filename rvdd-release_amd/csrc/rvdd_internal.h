@@ -198,7 +198,9 @@ size_t conv3x3h_weight_bytes(int cin);
 // (conv3x3h.hip HGeo KS = 5; runtime.hip compose_pre_enc0), and the fix of its border ring: part -= sum over the 3x3 taps d
 // whose pixel q = p + d - 1 lies OUTSIDE the image of W2[d] (b1 + sum over taps e inside the image of W1[e] x(q + e - 1))
 hipError_t launch_conv5x5h_c16(const ConvArgs& a, hipStream_t s);
-size_t conv5x5h_weight_bytes();
+// ... over the first 8 channels only (at most 8 real channels, i.e. no future frame): 25 groups in 7 chunks instead of 50 in 13
+hipError_t launch_conv5x5h_c8(const ConvArgs& a, hipStream_t s);
+size_t conv5x5h_weight_bytes(int cin);      // cin = 8 or 16: the channels multiplied
 hipError_t launch_pre_border_fix(const float* netin, const float* w1, const float* b1, const float* w2, float* part, int B, int H, int W,
                                  hipStream_t s);
 void conv3x3h_set_cout_split(bool on);   // false: no launch takes the output-channel split of small launches (conv3x3h.hip MT = 1); process-wide

@@ -54,6 +54,15 @@ int main() {
         pats.push_back({S, {0, 16, S, S + 16}, "groups 0,1 of two neighbouring pixels"});
         pats.push_back({S, {0, S, 2 * S, 18 * S}, "group 0 of four taps"});
     }
+    // the 8-channel 5x5 first layer (HGeo<8, 1, 5>): ONE group per tap, so the four groups of a chunk sit at four PIXELS, tap t at halo
+    // pixel 20 (t / 5) + t % 5 of a 20-pixel row: its seven chunks at a pixel pitch of 16 B (compact), 32 B (the 16-channel pitch with
+    // the second half unused) and 48 B
+    for (int S : {16, 32, 48}) {
+        const int px[7][4] = {{0, 1, 2, 3}, {4, 20, 21, 22}, {23, 24, 40, 41}, {42, 43, 44, 60}, {61, 62, 63, 64}, {80, 81, 82, 83}, {84, 84, 84, 84}};
+        static const char* what[7] = {"c8 5x5 chunk 0: taps 0-3",   "c8 5x5 chunk 1: taps 4-7",   "c8 5x5 chunk 2: taps 8-11", "c8 5x5 chunk 3: taps 12-15",
+                                      "c8 5x5 chunk 4: taps 16-19", "c8 5x5 chunk 5: taps 20-23", "c8 5x5 chunk 6: tap 24 four times"};
+        for (int j = 0; j < 7; ++j) pats.push_back({S, {px[j][0] * S, px[j][1] * S, px[j][2] * S, px[j][3] * S}, what[j]});
+    }
     for (int threads : {512})
         for (const P& p : pats) {
             hipMemset(dcyc, 0, 256 * 8 * 8);
