@@ -262,8 +262,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_kernel(ConvArgs a) {
     }
 }
 
-int g_variant = 0;   // A/B switch for the measurement hook (rvdd_debug_conv_bench)
-
 template <int CIN, int EPI, bool ACC_IN, int VARIANT>
 hipError_t launch_v(const ConvArgs& a, hipStream_t s) {
     static std::atomic<uint64_t> attr_done{0};
@@ -276,41 +274,40 @@ hipError_t launch_v(const ConvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// variant: A/B forms of the plain 48 -> 48 layer for the measurement hook (rvdd_debug_conv_bench); 0 everywhere else
 template <int CIN, int EPI, bool ACC_IN>
-hipError_t launch_t(const ConvArgs& a, hipStream_t s) {
+hipError_t launch_t(const ConvArgs& a, hipStream_t s, int variant) {
     if constexpr (CIN == 48 && EPI == EPI_RELU && !ACC_IN) {
-        if (g_variant == 1) return launch_v<CIN, EPI, ACC_IN, 1>(a, s);
-        if (g_variant == 2) return launch_v<CIN, EPI, ACC_IN, 2>(a, s);
+        if (variant == 1) return launch_v<CIN, EPI, ACC_IN, 1>(a, s);
+        if (variant == 2) return launch_v<CIN, EPI, ACC_IN, 2>(a, s);
     }
     return launch_v<CIN, EPI, ACC_IN, 0>(a, s);
 }
 
 template <int CIN>
-hipError_t launch_c(const ConvArgs& a, int epi, hipStream_t s) {
+hipError_t launch_c(const ConvArgs& a, int epi, hipStream_t s, int variant) {
     const bool acc = a.acc_in != nullptr;
     switch (epi) {
         case EPI_NONE:
-            return acc ? launch_t<CIN, EPI_NONE, true>(a, s) : launch_t<CIN, EPI_NONE, false>(a, s);
+            return acc ? launch_t<CIN, EPI_NONE, true>(a, s, variant) : launch_t<CIN, EPI_NONE, false>(a, s, variant);
         case EPI_RELU:
-            return acc ? launch_t<CIN, EPI_RELU, true>(a, s) : launch_t<CIN, EPI_RELU, false>(a, s);
+            return acc ? launch_t<CIN, EPI_RELU, true>(a, s, variant) : launch_t<CIN, EPI_RELU, false>(a, s, variant);
         case EPI_POOL:
-            return acc ? hipErrorInvalidValue : launch_t<CIN, EPI_POOL, false>(a, s);
+            return acc ? hipErrorInvalidValue : launch_t<CIN, EPI_POOL, false>(a, s, variant);
         case EPI_RELU_ADD2:
-            return acc ? hipErrorInvalidValue : launch_t<CIN, EPI_RELU_ADD2, false>(a, s);
+            return acc ? hipErrorInvalidValue : launch_t<CIN, EPI_RELU_ADD2, false>(a, s, variant);
     }
     return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-void conv3x3_set_variant(int v) { g_variant = v; }
-
 size_t conv3x3_weight_floats(int cin) { return (size_t)9 * (cin / 16) * 48 * 16; }
 
-hipError_t launch_conv3x3(const ConvArgs& a, int cin, int epi, hipStream_t s) {
+hipError_t launch_conv3x3(const ConvArgs& a, int cin, int epi, hipStream_t s, int variant) {
     if (a.ntiles <= 0) return hipSuccess;
     if ((size_t)a.H * a.W * cin * 4 >= 0x80000000ull) return hipErrorInvalidValue;   // 32-bit buffer offsets
-    if (cin == 48) return launch_c<48>(a, epi, s);
-    if (cin == 16) return launch_c<16>(a, epi, s);
+    if (cin == 48) return launch_c<48>(a, epi, s, variant);
+    if (cin == 16) return launch_c<16>(a, epi, s, variant);
     return hipErrorInvalidValue;
 }

@@ -805,7 +805,6 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {
     else tile_loop(std::false_type{});
 }
 
-bool g_conv3x3h_cout_split = true;      // conv3x3h_set_cout_split: false = every launch forms all 48 output channels per workgroup (A/B, tests)
 template <int CIN, int EPI, bool ACC_IN, bool UPS, int NGRP, int KS = 3, int MT = 3>
 hipError_t launch_g(const ConvArgs& a0, hipStream_t s) {
     static std::atomic<uint64_t> attr_done{0};
@@ -826,19 +825,19 @@ hipError_t launch_g(const ConvArgs& a0, hipStream_t s) {
 // Does a launch of this many 16x16 tiles take the output-channel split (MT = 1)?  At most a third of a tile per CU, i.e. every
 // workgroup of the split launch has ONE tile and a CU of its own.  (Measured, profiles/r05y_c1_cout_split.txt: up to one tile per
 // CU -- 85 walkers of three tiles each at 256 tiles -- loses what the coarse levels gain: the halo fetch of a tile does not shrink
-// with the output channels.)
-bool cout_split_applies(const ConvArgs& a) {
+// with the output channels.)  enabled = false: never (option "cout_split" 0, the A/B reference).
+bool cout_split_applies(const ConvArgs& a, bool enabled) {
     const int ntiles = a.B * ((a.W + TW - 1) / TW) * ((a.H + 15) / 16);
-    return g_conv3x3h_cout_split && 3 * ntiles <= current_device_cus();
+    return enabled && 3 * ntiles <= current_device_cus();
 }
 int g_conv3x3h_groups = 1;
 template <int CIN, int EPI, bool ACC_IN, bool UPS = false>
-hipError_t launch_h(const ConvArgs& a, hipStream_t s) {
+hipError_t launch_h(const ConvArgs& a, hipStream_t s, bool cout_split) {
 #ifdef RVDD_CONV_GROUPS2
     if (g_conv3x3h_groups == 2) return launch_g<CIN, EPI, ACC_IN, UPS, 2>(a, s);
 #endif
     if constexpr (CIN == 48 && EPI != EPI_RELU_OUT3) {
-        if (cout_split_applies(a)) return launch_g<CIN, EPI, ACC_IN, UPS, 1, 3, 1>(a, s);
+        if (cout_split_applies(a, cout_split)) return launch_g<CIN, EPI, ACC_IN, UPS, 1, 3, 1>(a, s);
     }
     return launch_g<CIN, EPI, ACC_IN, UPS, 1>(a, s);
 }
@@ -864,35 +863,34 @@ hipError_t launch_conv5x5h_c8(const ConvArgs& a, hipStream_t s) {
     return launch_g<8, EPI_NONE, false, false, 1, 5>(a, s);
 }
 void conv3x3h_set_groups(int g) { g_conv3x3h_groups = g == 1 ? 1 : 2; }
-void conv3x3h_set_cout_split(bool on) { g_conv3x3h_cout_split = on; }
 
-hipError_t launch_conv3x3h(const ConvArgs& a, int cin, int epi, hipStream_t s) {
+hipError_t launch_conv3x3h(const ConvArgs& a, int cin, int epi, hipStream_t s, bool cout_split) {
     if (a.B <= 0 || a.H <= 0 || a.W <= 0) return hipSuccess;
     // every map is addressed with one 32-bit byte offset per image whose out-of-image sentinel is 2^31
     if ((size_t)a.H * a.W * kF * 4 >= 0x80000000ull || (size_t)a.Hout * a.Wout * kF * 4 >= 0x80000000ull) return hipErrorInvalidValue;
     const bool acc = a.acc_in != nullptr;
     if (cin == 16) {      // the zero-padded network input (6 or 9 real channels)
         if (acc || a.ups) return hipErrorInvalidValue;
-        if (epi == EPI_NONE) return launch_h<16, EPI_NONE, false>(a, s);
-        if (epi == EPI_RELU) return launch_h<16, EPI_RELU, false>(a, s);
+        if (epi == EPI_NONE) return launch_h<16, EPI_NONE, false>(a, s, cout_split);
+        if (epi == EPI_RELU) return launch_h<16, EPI_RELU, false>(a, s, cout_split);
         return hipErrorInvalidValue;
     }
     if (cin != 48) return hipErrorInvalidValue;
     if (a.ups) {          // a.in = the map to upsample, [B][H/2][W/2][48]
         if (acc || epi != EPI_RELU || (a.H & 1) || (a.W & 1)) return hipErrorInvalidValue;
-        return launch_h<48, EPI_RELU, false, true>(a, s);
+        return launch_h<48, EPI_RELU, false, true>(a, s, cout_split);
     }
     switch (epi) {
         case EPI_NONE:
-            return acc ? launch_h<48, EPI_NONE, true>(a, s) : launch_h<48, EPI_NONE, false>(a, s);
+            return acc ? launch_h<48, EPI_NONE, true>(a, s, cout_split) : launch_h<48, EPI_NONE, false>(a, s, cout_split);
         case EPI_RELU:
-            return acc ? launch_h<48, EPI_RELU, true>(a, s) : launch_h<48, EPI_RELU, false>(a, s);
+            return acc ? launch_h<48, EPI_RELU, true>(a, s, cout_split) : launch_h<48, EPI_RELU, false>(a, s, cout_split);
         case EPI_POOL:
-            return acc ? hipErrorInvalidValue : launch_h<48, EPI_POOL, false>(a, s);
+            return acc ? hipErrorInvalidValue : launch_h<48, EPI_POOL, false>(a, s, cout_split);
         case EPI_RELU_ADD2:
-            return acc ? hipErrorInvalidValue : launch_h<48, EPI_RELU_ADD2, false>(a, s);
+            return acc ? hipErrorInvalidValue : launch_h<48, EPI_RELU_ADD2, false>(a, s, cout_split);
         case EPI_RELU_OUT3:
-            return acc ? hipErrorInvalidValue : launch_h<48, EPI_RELU_OUT3, false>(a, s);
+            return acc ? hipErrorInvalidValue : launch_h<48, EPI_RELU_OUT3, false>(a, s, cout_split);
     }
     return hipErrorInvalidValue;
 }

@@ -1100,12 +1100,11 @@ hipError_t launch_netin_bound(const float* raw_a, const float* raw_b, const floa
     return hipGetLastError();
 }
 
-bool g_small_prestage = true;      // prestage_set_small: false = the three pre-stage kernels at every size (A/B reference, tests)
-void prestage_set_small(bool on) { g_small_prestage = on; }
 // Can a frame-step of this size take the one-kernel pre-stage (netin_small_kernel)?  No future frame, at most 1024 tiles of 16x16.
-bool netin_small_applies(int B, int h, int w, bool future) {
+// enabled = false: never (option "small_prestage" 0: the three pre-stage kernels at every size, the A/B reference).
+bool netin_small_applies(int B, int h, int w, bool future, bool enabled) {
     const long tiles = (long)B * ((2 * h + 15) / 16) * ((2 * w + 15) / 16);
-    return g_small_prestage && !future && h >= 1 && w >= 1 && tiles <= 1024;
+    return enabled && !future && h >= 1 && w >= 1 && tiles <= 1024;
 }
 hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const float* prev4, const float* flow_prev, float* netin, int B,
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,

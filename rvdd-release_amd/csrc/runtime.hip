@@ -128,6 +128,45 @@ struct Level {
     float* part = nullptr;
 };
 
+// Which kernel runs the convunet's 3x3 convs: the values of option "conv_kernel".
+enum ConvSel {
+    CONV_SPLIT16 = 0,   // the default: the F16 matrix pipe with split f32 operands (conv3x3h.hip) wherever a layer has that bank
+    CONV_DIRECT = 1,    // the direct f32 kernel everywhere
+    CONV_WINO = 2,      // the Winograd f32 kernel everywhere, also where it is the slower choice (tests, A/B measurements)
+    CONV_F32 = 4        // f32 kernels, direct or Winograd by launch size (wino_applies)
+};
+
+// Everything rvdd_set_option sets, per handle; one row of RVDD_OPTIONS each (include/rvdd.h describes them).  All int: a row
+// names its field by one kind of member pointer; flags hold 0 or 1.
+struct Options {
+    int no_warp = 0;          // --no_warp: previous output / features / next frame enter the net unwarped
+    int warp_raw = 0;         // --warp_raw: warp the re-mosaicked frames at raw resolution, demosaic afterwards
+    int prev_noisy = 0;       // --prev_noisy_frame: the next step's "previous frame" is the demosaiced noisy one
+    int bayer = 0;            // enum rvdd_bayer of the packed raw frames: every demosaic and re-mosaic of a step
+    int conv = CONV_SPLIT16;  // enum ConvSel
+    int bfp = 1;              // block floating point of the split-f16 convs (amax words per map and sequence); 0: operands split as
+                              // they are, the round-3 behaviour with its 2^-14 .. 65504 domain -- A/B reference only
+    int seq_major = 0;        // 1 = full-resolution stages one sequence at a time (see seq_major_on)
+    int fuse_upsample = 1;    // UpConv's bilinear x2 inside the patch load of the conv behind it (0: separate kernel)
+    int cout_split = 1;       // split-f16 convs: small launches give a tile to three workgroups of 16 output channels (conv3x3h.hip MT = 1)
+    int small_prestage = 1;   // the three pre-stage kernels of a small frame-step without a future frame as one (netin_small_kernel)
+    int fuse_pre = 1;         // feat nets: preprocessing_layer and EncoderConvs[0][0] composed (0: one after the other, A/B reference)
+    int pre5_cin8 = 1;        // 0: the 13-chunk bank of that composition also where the 7-chunk one exists (A/B reference)
+    int next_split = 1;       // ConvNeXt, fused blocks: the two 1x1 convs on the F16 matrix pipe with split f32 operands (0: f32 MFMA)
+    int next_pipe = 1;        // ConvNeXt, fused split-f16 blocks as a front / back pipeline over tiles (0: convblock_kernel's phases)
+    int next_pool = 1;        // ConvNeXt, fused blocks: MaxPool2d(2) from the epilogue of the block in front of a DownConv
+    int next_projfuse = 1;    // ConvNeXt, pipelined split-f16 blocks: the 96 -> 48 projection behind a concat as two halves in the
+                              // epilogues of the blocks that form the concatenated maps (0: proj1x1_kernel)
+    int tvl1_async = 0;       // rvdd_tvl1flow_batch without iteration counts enqueues and returns
+    int stream_reset_each = 0;            // every ready step of rvdd_video_push carries the reset mark of every ready slot
+    int stream_flow_from_denoised = 0;    // rvdd_video_push: the flow towards the previous frame is matched against the previous output
+    int use_graphs = 0;       // replay captured frame-steps (measured slower, off)
+
+    bool split16() const { return conv == CONV_SPLIT16; }
+    bool wino_allowed() const { return conv != CONV_DIRECT; }
+    bool wino_forced() const { return conv == CONV_WINO; }
+};
+
 }  // namespace
 
 struct rvdd_handle {
@@ -138,24 +177,7 @@ struct rvdd_handle {
                                   // (create, rvdd_reset), some after rvdd_reset_slots (B <= 64; beyond that only none or all occur)
     uint64_t undef_mask = 0;      // rvdd_step_live / rvdd_move_slots: the sequences whose recurrent state is undefined (they sat a step out, or
                                   // were moved away); a step may cover one only together with a reset mark for it
-    bool force_wino = false;      // Winograd at every size (RVDD_CONV=winograd / rvdd_set_option "conv_kernel" 2): tests + measurement
-    bool warp_raw = false;        // --warp_raw (rvdd_set_option): warp the re-mosaicked frames at raw resolution, demosaic afterwards
-    bool prev_noisy = false;      // --prev_noisy_frame (rvdd_set_option): the next step's "previous frame" is the demosaiced noisy one
-    bool no_warp = false;         // --no_warp (rvdd_set_option): previous output / features / next frame enter the net unwarped
-    int bayer = 0;                // enum rvdd_bayer of the packed raw frames (rvdd_set_option "bayer_pattern"): every demosaic and
-                                  // re-mosaic of a step
-    bool use_wino = true;         // 48->48 3x3 convs: Winograd F(2x2,3x3) (RVDD_CONV=direct selects the direct kernel)
-    bool split16 = true;          // 48->48 3x3 convs on the F16 matrix pipe with split f32 operands (conv3x3h.hip); RVDD_CONV=f32 | direct |
-                                  // winograd / "conv_kernel" 1, 2, 4 select the f32-MFMA kernels (the A/B reference)
-    bool bfp = true;              // block floating point of the split-f16 convs (amax words per map and sequence; RVDD_BFP=0 / option "block_fp" 0:
-                                  // operands split as they are, the round-3 behaviour with its 2^-14 .. 65504 domain -- A/B reference only)
-    int seq_major = 0;            // 1 = full-resolution stages one sequence at a time (see seq_major_on)
-    bool fuse_upsample = true;    // UpConv's bilinear x2 inside the Winograd patch load (RVDD_FUSE_UPSAMPLE=0: separate kernel)
-    bool next_split = true;       // ConvNeXt, fused blocks: the two 1x1 convs on the F16 matrix pipe with split f32 operands (RVDD_NEXT_SPLIT=0: f32 MFMA)
-    bool next_pipe = true;        // ConvNeXt, fused split-f16 blocks as a front / back pipeline over tiles (convblock_pipe_kernel; RVDD_NEXT_PIPE=0: convblock_kernel's phases)
-    bool next_pool = true;        // ConvNeXt, fused blocks: MaxPool2d(2) from the epilogue of the block in front of a DownConv
-    bool next_projfuse = true;    // ConvNeXt, pipelined split-f16 blocks: the 96 -> 48 projection behind a concat as two halves in the epilogues of
-                                  // the blocks that form the concatenated maps (RVDD_NEXT_PROJFUSE=0 / option "next_projfuse" 0: proj1x1_kernel)
+    Options opt;                  // what rvdd_set_option sets (kOptions)
     bool serpentine = false;      // sequence order of the next forward (flips with every one when seq_major is on)
     std::map<std::string, HostTensor> staged;
     std::vector<void*> allocs;
@@ -168,11 +190,9 @@ struct rvdd_handle {
     float* pre5_b = nullptr;  // [48] composed bias
     float* pre5_w8 = nullptr; // the same bank over the first 8 input channels only (7 chunks instead of 13): at most 8 real channels, else null
     float pre5_inv8 = 1.f;
-    bool pre5_cin8 = true;    // option "pre5_cin8" 0: the 13-chunk bank also where the 7-chunk one exists (A/B reference)
     float* pre_w1 = nullptr;  // [9][16][48]: preprocessing_layer weight, tap-major, input channel, its output channel m (border fix)
     float* pre_b1 = nullptr;  // [48]
     float* pre_w2 = nullptr;  // [9][48 m][48 o]: EncoderConvs[0][0] weight over the preprocessing layer's channels (border fix)
-    bool fuse_pre = true;     // RVDD_FUSE_PRE=0 / option "fuse_pre" 0: the two layers one after the other (A/B reference)
     float* w_out = nullptr;   // [3][48]
     float* b_out = nullptr;   // [3]
     NextBlk nx[NX_COUNT];     // ConvNeXt blocks in schedule order (NxBlock)
@@ -194,7 +214,6 @@ struct rvdd_handle {
     float* scratch = nullptr;
     size_t scratch_bytes = 0;
     Tvl1Workspace* tvl1 = nullptr;   // cached for the last (nx, ny)
-    bool tvl1_async = false;         // option "tvl1_async": rvdd_tvl1flow_batch without iteration counts enqueues and returns (see rvdd.h)
 
     // rvdd_video_push: the last 2 + future ingested frames of every slot, allocated by the first push.  The slots share ONE
     // ring position per push (push k writes position k % depth of every slot that gets a frame), so the centre, previous and
@@ -214,8 +233,6 @@ struct rvdd_handle {
                                      // the first push that has the option on)
         std::vector<uint8_t> dgray_ok;   // per slot: dgray holds the output of the push before this one
     } st;
-    bool stream_reset_each = false;  // option "stream_reset_each": every ready step of rvdd_video_push carries the reset mark of every ready slot
-    bool stream_flow_from_denoised = false;  // option "stream_flow_from_denoised": the flow towards the previous frame is matched against the previous output
 
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
@@ -235,7 +252,6 @@ struct rvdd_handle {
     };
     std::map<StepKey, StepGraph> graphs;
     uint64_t graph_tick = 0;
-    int use_graphs = 0;             // RVDD_GRAPH=1 / rvdd_set_option "graphs" 1: replay captured frame-steps (measured slower, off)
     bool ran_eagerly = false;       // the first step of a handle is never captured (it sets the kernels' attributes)
     hipStream_t gstream = nullptr;  // the stream the graphs are captured on and replayed in
     hipEvent_t g_in = nullptr, g_out = nullptr;
@@ -251,7 +267,7 @@ struct rvdd_handle {
 
     bool has_feat() const { return cfg.arch == RVDD_ARCH_CONVUNET_FEAT || cfg.arch == RVDD_ARCH_CONVNEXT_FEAT; }
     bool is_next() const { return cfg.arch == RVDD_ARCH_CONVNEXT || cfg.arch == RVDD_ARCH_CONVNEXT_FEAT; }
-    bool amax_on() const { return bfp && split16 && !is_next(); }      // the convs read amax words (block floating point)
+    bool amax_on() const { return opt.bfp && opt.split16() && !is_next(); }      // the convs read amax words (block floating point)
     int cin_real() const { return 3 * (2 + cfg.future); }
 };
 
@@ -265,6 +281,70 @@ int fail(rvdd_t* h, int code, const char* fmt, ...) {
     va_end(ap);
     if (h) h->err = buf; else g_create_error = buf;
     return code;
+}
+
+// One row per option: ABI name | environment variable read at rvdd_create (nullptr: none) | field of Options | accepted range
+// lo .. hi | message of a value outside it (nullptr: a flag, any value counts as value != 0) | hook that does the storing itself
+// (nullptr: plain store).  F is the first row, X every other: the table and the unknown-option message expand this one list.
+int opt_graphs(rvdd_t* h, int32_t value);
+int opt_warp_raw(rvdd_t* h, int32_t value);
+int opt_tvl1_async(rvdd_t* h, int32_t value);
+int opt_block_fp(rvdd_t* h, int32_t value);
+int opt_conv_kernel(rvdd_t* h, int32_t value);
+#define CONV_KERNEL_RANGE "rvdd_set_option: conv_kernel must be 0 (default), 1 (direct f32), 2 (winograd f32) or 4 (f32 by size)"
+#define RVDD_OPTIONS(F, X)                                                                                                       \
+    F("no_warp", nullptr, no_warp, 0, 1, nullptr, nullptr)                                                                       \
+    X("warp_raw", nullptr, warp_raw, 0, 1, nullptr, opt_warp_raw)                                                                \
+    X("prev_noisy_frame", nullptr, prev_noisy, 0, 1, nullptr, nullptr)                                                           \
+    X("conv_kernel", "RVDD_CONV", conv, 0, 4, CONV_KERNEL_RANGE, opt_conv_kernel)                                                \
+    X("seq_major", "RVDD_SEQ_MAJOR", seq_major, 0, 1, "rvdd_set_option: seq_major must be 0 or 1", nullptr)                      \
+    X("graphs", "RVDD_GRAPH", use_graphs, 0, 1, nullptr, opt_graphs)                                                             \
+    X("fuse_upsample", "RVDD_FUSE_UPSAMPLE", fuse_upsample, 0, 1, nullptr, nullptr)                                              \
+    X("next_split", "RVDD_NEXT_SPLIT", next_split, 0, 1, nullptr, nullptr)                                                       \
+    X("next_pipe", "RVDD_NEXT_PIPE", next_pipe, 0, 1, nullptr, nullptr)                                                          \
+    X("next_pool", "RVDD_NEXT_POOL", next_pool, 0, 1, nullptr, nullptr)                                                          \
+    X("next_projfuse", "RVDD_NEXT_PROJFUSE", next_projfuse, 0, 1, nullptr, nullptr)                                              \
+    X("tvl1_async", nullptr, tvl1_async, 0, 1, nullptr, opt_tvl1_async)                                                          \
+    X("block_fp", "RVDD_BFP", bfp, 0, 1, nullptr, opt_block_fp)                                                                  \
+    X("fuse_pre", "RVDD_FUSE_PRE", fuse_pre, 0, 1, nullptr, nullptr)                                                             \
+    X("pre5_cin8", nullptr, pre5_cin8, 0, 1, nullptr, nullptr)                                                                   \
+    X("cout_split", "RVDD_COUT_SPLIT", cout_split, 0, 1, nullptr, nullptr)                                                       \
+    X("small_prestage", "RVDD_SMALL_PRESTAGE", small_prestage, 0, 1, nullptr, nullptr)                                           \
+    X("bayer_pattern", nullptr, bayer, RVDD_BAYER_GBRG, RVDD_BAYER_BGGR,                                                         \
+      "rvdd_set_option: bayer_pattern must be 0 (GBRG), 1 (GRBG), 2 (RGGB) or 3 (BGGR)", nullptr)                                \
+    X("stream_reset_each", nullptr, stream_reset_each, 0, 1, nullptr, nullptr)                                                   \
+    X("stream_flow_from_denoised", nullptr, stream_flow_from_denoised, 0, 1, nullptr, nullptr)
+struct OptRow {
+    const char* name;
+    const char* env;
+    int Options::*field;
+    int lo, hi;
+    const char* range_msg;
+    int (*hook)(rvdd_t*, int32_t);
+};
+#define OPT_ROW(name, env, field, lo, hi, msg, hook) {name, env, &Options::field, lo, hi, msg, hook},
+const OptRow kOptions[] = {RVDD_OPTIONS(OPT_ROW, OPT_ROW)};
+#define OPT_NAME_FIRST(name, ...) name
+#define OPT_NAME(name, ...) ", " name
+const char kUnknownOption[] = "rvdd_set_option: unknown option '%s' (known: " RVDD_OPTIONS(OPT_NAME_FIRST, OPT_NAME) ")";
+
+// The one decoder of the conv selector: option "conv_kernel"'s integer (word == nullptr; -1: not a selector), or RVDD_CONV's
+// word -- direct | winograd | f32, anything else = the default.
+int conv_decode(const char* word, int32_t value) {
+    static const struct { int sel; const char* word; } known[] = {
+        {CONV_SPLIT16, nullptr}, {CONV_DIRECT, "direct"}, {CONV_WINO, "winograd"}, {CONV_F32, "f32"}};
+    for (const auto& k : known)
+        if (word ? (k.word && std::strcmp(word, k.word) == 0) : value == k.sel) return k.sel;
+    return word ? CONV_SPLIT16 : -1;
+}
+
+// range check, then the row's hook or a plain store
+int set_option_row(rvdd_t* h, const OptRow& row, int32_t value) {
+    if (!row.range_msg) value = value != 0;
+    else if (value < row.lo || value > row.hi) return fail(h, RVDD_ERR_ARG, "%s", row.range_msg);
+    if (row.hook) return row.hook(h, value);
+    h->opt.*row.field = value;
+    return RVDD_OK;
 }
 
 uint64_t slots_below(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }      // slots [0, n) as a mask (every slot it has, from 64 on)
@@ -663,10 +743,13 @@ struct ConvCall {
     bool ups = false;        // `in` is the half-resolution map whose bilinear x2 upsample the conv reads (UpConv)
     int amax_in = -1;        // amax slot of `in` (-1: no scaling) and of `out` (-1: no split kernel reads it)
     int amax_out = -1;
+    int variant = 0;         // launch_conv3x3's A/B forms (rvdd_debug_conv_bench only)
 };
 
+// Winograd needs enough 8x32-pixel units to fill the chip (its 144 KiB filter bank is loaded once
+// per workgroup); the 1/8-resolution level of a single 720p sequence (60 units) runs faster direct
 bool wino_applies(const rvdd_t* h, const NetRun& run, int H, int W) {
-    return h->use_wino && (h->force_wino || run.n * ((W + 31) / 32) * ((H + 7) / 8) >= 200);
+    return h->opt.wino_allowed() && (h->opt.wino_forced() || run.n * ((W + 31) / 32) * ((H + 7) / 8) >= 200);
 }
 
 // Sequences [b0, b0 + nb) of the batch: the maps of a ConvCall are those of the WHOLE batch, a launch may cover a part.
@@ -681,14 +764,14 @@ struct Sub {
 // more to their tails (3600 units on 256 CUs = 14.06 rounds) and to four filter-bank loads per layer than the cache
 // gives back.  Kept because it is free and pins an invariant the tests use: a launch's batch size does not enter a
 // tile's sums, so both schedules give bit-identical frames.
-bool seq_major_on(const rvdd_t* h, int n) { return n > 1 && h->seq_major == 1; }
+bool seq_major_on(const rvdd_t* h, int n) { return n > 1 && h->opt.seq_major == 1; }
 
 int run_conv(rvdd_t* h, const NetRun& run, const Conv3& L, const ConvCall& c, hipStream_t s, Sub sub) {
-    const int cin_in = L.cin_pad[c.src];
+    const int cin = L.cin_pad[c.src];
     const int Ho = c.epi == EPI_POOL ? c.H / 2 : (c.Hout ? c.Hout : c.H), Wo = c.epi == EPI_POOL ? c.W / 2 : (c.Wout ? c.Wout : c.W);
     const size_t px_in = (size_t)sub.b0 * c.H * c.W, px_out = (size_t)sub.b0 * Ho * Wo;
     ConvArgs a{};
-    a.in = c.in + (c.ups ? px_in / 4 : px_in) * cin_in;
+    a.in = c.in + (c.ups ? px_in / 4 : px_in) * cin;
     a.ups = c.ups ? 1 : 0;
     a.w = L.w[c.src];
     a.bias = L.bias;
@@ -699,43 +782,35 @@ int run_conv(rvdd_t* h, const NetRun& run, const Conv3& L, const ConvCall& c, hi
     a.B = sub.nb;
     a.H = c.H;
     a.W = c.W;
-    if (c.epi == EPI_POOL) {
-        a.Hout = c.H / 2;
-        a.Wout = c.W / 2;
-    } else {
-        a.Hout = c.Hout ? c.Hout : c.H;
-        a.Wout = c.Wout ? c.Wout : c.W;
-    }
+    a.Hout = Ho;
+    a.Wout = Wo;
     a.oy = c.oy;
     a.ox = c.ox;
     a.tiles_x = (c.W + 15) / 16;
     a.tiles_y = (c.H + 7) / 8;
     a.ntiles = a.B * a.tiles_x * a.tiles_y;
-    const int cin = L.cin_pad[c.src];
     const double px = (double)a.B * c.H * c.W;
     const double flops = 2.0 * 9.0 * L.cin_real[c.src] * 48.0 * px;
     double bytes = px * 4.0 * (L.cin_real[c.src] + (c.epi == EPI_POOL ? 12.0 : 48.0));
     if (c.acc_in) bytes += px * 192.0;
     if (c.epi == EPI_RELU_ADD2) bytes += px * 384.0;
-    // Winograd needs enough 8x32-pixel units to fill the chip (its 144 KiB filter bank is loaded once
-    // per workgroup); the 1/8-resolution level of a single 720p sequence (60 units) runs faster direct
     a.w3 = h->w_out;
     a.b3 = h->b_out;
     a.out3_nchw = c.out3_nchw ? c.out3_nchw + px_in * 3 : nullptr;
     a.out3_nhwc4 = c.out3_nhwc4 ? c.out3_nhwc4 + px_in * 4 : nullptr;
-    a.amax_in = (c.amax_in >= 0 && h->bfp) ? amax_words(h, c.amax_in, sub.b0) : nullptr;
-    a.amax_out = (c.amax_out >= 0 && h->bfp) ? amax_words(h, c.amax_out, sub.b0) : nullptr;
+    a.amax_in = (c.amax_in >= 0 && h->opt.bfp) ? amax_words(h, c.amax_in, sub.b0) : nullptr;
+    a.amax_out = (c.amax_out >= 0 && h->opt.bfp) ? amax_words(h, c.amax_out, sub.b0) : nullptr;
     const bool c16_ok = cin != 48 && !c.acc_in && (c.epi == EPI_NONE || c.epi == EPI_RELU);
-    if (c.ups && !(cin == 48 && ((h->split16 && L.wh[c.src]) || (L.wu[c.src] && wino_applies(h, run, c.H, c.W)))))
+    if (c.ups && !(cin == 48 && ((h->opt.split16() && L.wh[c.src]) || (L.wu[c.src] && wino_applies(h, run, c.H, c.W)))))
         return fail(h, RVDD_ERR_STATE, "run_conv: the fused upsample exists in the split-f16 and the Winograd kernels only");
     if (c.ups) bytes -= px * 4.0 * 36.0;          // reads the quarter-size map
     // the F16 matrix pipe with split operands: every layer of the convunet
-    if (h->split16 && L.wh[c.src] && (cin == 48 || c16_ok)) {
+    if (h->opt.split16() && L.wh[c.src] && (cin == 48 || c16_ok)) {
         a.w = L.wh[c.src];
         a.wscale = L.wh_inv[c.src];
         Scope sc(h, s, c.ups ? "conv3x3h_kernel<48, 1, false, true>" : cin == 48 ? conv_name_h(c.epi, c.acc_in != nullptr)
                            : (c.epi == EPI_NONE ? "conv3x3h_kernel<16, 0, false, false>" : "conv3x3h_kernel<16, 1, false, false>"), flops, bytes);
-        HIPCHK(h, launch_conv3x3h(a, cin == 48 ? 48 : 16, c.epi, s));
+        HIPCHK(h, launch_conv3x3h(a, cin == 48 ? 48 : 16, c.epi, s, h->opt.cout_split));
         return RVDD_OK;
     }
     if ((cin == 48 || c16_ok) && L.wu[c.src] && wino_applies(h, run, c.H, c.W)) {
@@ -746,7 +821,7 @@ int run_conv(rvdd_t* h, const NetRun& run, const Conv3& L, const ConvCall& c, hi
         return RVDD_OK;
     }
     Scope sc(h, s, conv_name(cin, c.epi, c.acc_in != nullptr), flops, bytes);
-    HIPCHK(h, launch_conv3x3(a, cin, c.epi, s));
+    HIPCHK(h, launch_conv3x3(a, cin, c.epi, s, c.variant));
     return RVDD_OK;
 }
 
@@ -757,7 +832,7 @@ int run_pre5(rvdd_t* h, const NetRun& run, const float* netin, float* part, hipS
     const size_t px0 = (size_t)sub.b0 * H * W;
     ConvArgs a{};
     a.in = netin + px0 * kNetInC;
-    const bool c8 = h->pre5_cin8 && h->pre5_w8;      // at most 8 real channels: only the first 8 of the 16-channel pixel are multiplied
+    const bool c8 = h->opt.pre5_cin8 && h->pre5_w8;      // at most 8 real channels: only the first 8 of the 16-channel pixel are multiplied
     a.w = c8 ? h->pre5_w8 : h->pre5_w;
     a.wscale = c8 ? h->pre5_inv8 : h->pre5_inv;
     a.bias = h->pre5_b;
@@ -765,7 +840,7 @@ int run_pre5(rvdd_t* h, const NetRun& run, const float* netin, float* part, hipS
     a.B = sub.nb;
     a.H = a.Hout = H;
     a.W = a.Wout = W;
-    a.amax_in = h->bfp ? amax_words(h, run.amax.base + AMAX_REL_NETIN, sub.b0) : nullptr;
+    a.amax_in = h->opt.bfp ? amax_words(h, run.amax.base + AMAX_REL_NETIN, sub.b0) : nullptr;
     const double px = (double)sub.nb * H * W;
     {
         Scope sc(h, s, c8 ? "conv5x5h_kernel<8>" : "conv5x5h_kernel<16>", 2.0 * 25.0 * h->cin_real() * 48.0 * px, px * 4.0 * (h->cin_real() + 48.0));
@@ -825,7 +900,7 @@ int run_convunet(rvdd_t* h, NetRun& run, const float* netin, const float* featw,
     for (int k = 0; k < nsub; ++k) {
         const Sub sb = sub_at(k);
         if (run.in) RC(run_prologue(h, run, sb, s));
-        if (feat && h->fuse_pre && h->split16 && h->pre5_w) {
+        if (feat && h->opt.fuse_pre && h->opt.split16() && h->pre5_w) {
             // preprocessing_layer (:742, no activation) and the first source of EncoderConvs[0][0] (:743) as ONE 5x5 conv of the
             // network input (compose_pre_enc0), its border ring put right, then the second source (the old features) as before
             RC(run_pre5(h, run, netin, lv[0].part, s, sb));
@@ -870,7 +945,7 @@ int run_convunet(rvdd_t* h, NetRun& run, const float* netin, const float* featw,
             const size_t lo_px = (size_t)sb.b0 * lv[lo].H * lv[lo].W, hi_px = (size_t)sb.b0 * lv[hi].H * lv[hi].W;
             // UpConv: bilinear x2, conv, ReLU (:137-142).  Where the Winograd kernel runs the conv, the interpolation
             // happens in its patch load and the upsampled map is never written; elsewhere it is made first.
-            const bool fused = h->fuse_upsample && (h->split16 || wino_applies(h, run, uh, uw));
+            const bool fused = h->opt.fuse_upsample && (h->opt.split16() || wino_applies(h, run, uh, uw));
             if (!fused) {
                 Scope sc(h, s, "upsample2x_kernel", 0.0, (double)sb.nb * uh * uw * 192.0 * 1.25);
                 HIPCHK(h, launch_upsample2x(d + lo_px * kF, lv[hi].t[0] + (size_t)sb.b0 * uh * uw * kF, sb.nb, lv[lo].H, lv[lo].W, uh,
@@ -892,7 +967,7 @@ int run_convunet(rvdd_t* h, NetRun& run, const float* netin, const float* featw,
             RC(conv(cu_dec(i, 1), lv[hi].t[0], L(cu_dec(i, 0)), lv[hi].t[1], hi, EPI_RELU, sb));
             if (hi > 0) continue;
             // ---- post: hooked 48-ch map = next frame's features (:808-812), then 1x1 -> 3
-            if (h->split16 || wino_applies(h, run, lv[0].H, lv[0].W)) {
+            if (h->opt.split16() || wino_applies(h, run, lv[0].H, lv[0].W)) {
                 // PostConvs[1] (1x1, 48 -> 3) rides in the epilogue of PostConvs[0]'s kernel (split-f16: at every size; Winograd
                 // f32: where it runs) -- and with it the output frame's share of the words the next step's input bound reads
                 ConvCall pc;
@@ -964,6 +1039,42 @@ bool graph_stream(rvdd_t* h) {
     }
     return true;
 }
+
+// ---- the options that do more than store a value (kOptions)
+int opt_graphs(rvdd_t* h, int32_t value) {        // the capture stream on demand (see rvdd_create)
+    h->opt.use_graphs = value && graph_stream(h);
+    return RVDD_OK;
+}
+int opt_warp_raw(rvdd_t* h, int32_t value) {
+    // the reference warps the full-resolution features with the raw-resolution flow in this mode and fails on the shapes
+    if (value && h->has_feat()) return fail(h, RVDD_ERR_ARG, "rvdd_set_option: warp_raw is not defined with feature recurrence (the reference fails there too)");
+    h->opt.warp_raw = value;
+    return RVDD_OK;
+}
+int opt_tvl1_async(rvdd_t* h, int32_t value) {    // 0 switches back and reports what is pending now (the control word, see rvdd.h)
+    if (!value && h->tvl1) {
+        ENTER(h);
+        HIPCHK(h, hipDeviceSynchronize());
+        if (hipError_t e = tvl1_check(h->tvl1, nullptr); e != hipSuccess)
+            return fail(h, RVDD_ERR_HIP, "rvdd_set_option(tvl1_async, 0): a pending asynchronous flow batch failed: %s", hipGetErrorString(e));
+    }
+    h->opt.tvl1_async = value;
+    return RVDD_OK;
+}
+int opt_block_fp(rvdd_t* h, int32_t value) {
+    h->opt.bfp = value;
+    if (h->amax) {
+        ENTER(h);
+        HIPCHK(h, hipMemset(h->amax, 0, amax_bytes(h->cfg.batch, AMAX_SLOTS)));      // no stale words across the switch
+    }
+    return RVDD_OK;
+}
+int opt_conv_kernel(rvdd_t* h, int32_t value) {
+    const int sel = conv_decode(nullptr, value);
+    if (sel < 0) return fail(h, RVDD_ERR_ARG, "%s", CONV_KERNEL_RANGE);
+    h->opt.conv = sel;
+    return RVDD_OK;
+}
 }  // namespace
 
 int rvdd_create(const rvdd_cfg* cfg, rvdd_t** out) {
@@ -991,21 +1102,6 @@ int rvdd_create(const rvdd_cfg* cfg, rvdd_t** out) {
     rvdd_t* h = new rvdd_handle();
     h->cfg = *cfg;
     h->reset_marks = slots_below(cfg->batch);
-    if (const char* sm = std::getenv("RVDD_SEQ_MAJOR")) h->seq_major = std::atoi(sm) != 0;     // measurement switches
-    if (const char* fu = std::getenv("RVDD_FUSE_UPSAMPLE")) h->fuse_upsample = std::atoi(fu) != 0;
-    if (const char* bf = std::getenv("RVDD_BFP")) h->bfp = std::atoi(bf) != 0;
-    if (const char* fp = std::getenv("RVDD_FUSE_PRE")) h->fuse_pre = std::atoi(fp) != 0;
-    if (const char* np = std::getenv("RVDD_NEXT_POOL")) h->next_pool = std::atoi(np) != 0;
-    if (const char* nsp = std::getenv("RVDD_NEXT_SPLIT")) h->next_split = std::atoi(nsp) != 0;
-    if (const char* npp = std::getenv("RVDD_NEXT_PIPE")) h->next_pipe = std::atoi(npp) != 0;
-    if (const char* npf = std::getenv("RVDD_NEXT_PROJFUSE")) h->next_projfuse = std::atoi(npf) != 0;
-    if (const char* cv = std::getenv("RVDD_CONV")) {
-        // f32 (the f32-MFMA kernels, direct or Winograd by launch size) | direct | winograd (that f32 kernel at every size) |
-        // anything else = the default: split-f16 kernel for the 48-channel layers, f32 kernels by size for the rest
-        h->use_wino = std::strcmp(cv, "direct") != 0;
-        h->force_wino = std::strcmp(cv, "winograd") == 0;
-        h->split16 = std::strcmp(cv, "direct") != 0 && std::strcmp(cv, "winograd") != 0 && std::strcmp(cv, "f32") != 0;
-    }
     const int B = cfg->batch, H = cfg->height, W = cfg->width;
     int rc = RVDD_OK;
     auto A = [&](float** p, size_t floats) {
@@ -1045,9 +1141,13 @@ int rvdd_create(const rvdd_cfg* cfg, rvdd_t** out) {
     // hardware queue the device's scheduler keeps mapped, and a handle that merely EXISTED beside another one -- with the two idle
     // streams every handle used to create -- made that one's cooperative TV-L1 launches and the kernels behind them 20 % slower
     // (profiles/r05k_online_flow_two_handles.txt)
-    if (const char* cs = std::getenv("RVDD_COUT_SPLIT")) conv3x3h_set_cout_split(std::atoi(cs) != 0);      // process-wide A/B switch
-    if (const char* sp = std::getenv("RVDD_SMALL_PRESTAGE")) prestage_set_small(std::atoi(sp) != 0);       // likewise
-    if (const char* gv = std::getenv("RVDD_GRAPH")) h->use_graphs = std::atoi(gv) != 0 && graph_stream(h);
+    // The measurement switches of the environment: a number (0 = off), RVDD_CONV a word.  They go the way of rvdd_set_option, hooks
+    // included: RVDD_GRAPH makes the capture stream, RVDD_BFP clears the amax words once more, RVDD_CONV's word comes back from
+    // conv_decode as a selector that opt_conv_kernel accepts.  Last in create, so that a hook finds the handle complete; a hook's
+    // failure does not fail create, its message stays in the handle's error string.
+    for (const OptRow& row : kOptions)
+        if (const char* v = row.env ? std::getenv(row.env) : nullptr)
+            (void)set_option_row(h, row, row.field == &Options::conv ? conv_decode(v, 0) : std::atoi(v) != 0);
     *out = h;
     return RVDD_OK;
 }
@@ -1203,131 +1303,9 @@ int rvdd_set_option(rvdd_t* h, const char* name, int32_t value) {
         (void)hipDeviceSynchronize();
         drop_graphs(h);            // a captured step has the options it was captured with
     }
-    if (std::strcmp(name, "graphs") == 0) {
-        h->use_graphs = value != 0 && graph_stream(h);
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "no_warp") == 0) {
-        h->no_warp = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "warp_raw") == 0) {
-        // the reference warps the full-resolution features with the raw-resolution flow in this mode and fails on the shapes
-        if (value && h->has_feat()) return fail(h, RVDD_ERR_ARG, "rvdd_set_option: warp_raw is not defined with feature recurrence (the reference fails there too)");
-        h->warp_raw = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "prev_noisy_frame") == 0) {
-        h->prev_noisy = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "fuse_upsample") == 0) {
-        // 0 = UpConv's bilinear x2 always as its own kernel (A/B reference of the fused Winograd patch load)
-        h->fuse_upsample = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "next_split") == 0) {
-        // 0 = the fused ConvBlock's two 1x1 convs on the f32 matrix pipe (exact-f32 products: the A/B reference of the split-f16 form)
-        h->next_split = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "next_pipe") == 0) {
-        // 0 = the fused ConvBlock's phases one after the other in all eight waves (convblock_kernel) instead of the pipeline over
-        // tiles (depth-wise + LayerNorm of tile t + 1 on waves 0-3 beside the MLP of tile t on waves 4-7); same bits
-        h->next_pipe = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "next_pool") == 0) {
-        // 0 = MaxPool2d(2) as its own kernel behind the fused block (A/B reference of the pooling epilogue; same bits)
-        h->next_pool = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "next_projfuse") == 0) {
-        // 0 = the 96 -> 48 projection behind a concat as its own kernel (A/B reference of the projection halves in the epilogues of
-        // the blocks that form the two concatenated maps)
-        h->next_projfuse = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "cout_split") == 0) {
-        // 0 = every launch of the split-f16 conv kernel forms all 48 output channels per workgroup (A/B reference of the
-        // output-channel split that launches of at most a third of a tile per CU take; same bits).  Process-wide.
-        conv3x3h_set_cout_split(value != 0);
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "small_prestage") == 0) {
-        // 0 = the pre-stage of a frame-step as its three kernels (input bound, green plane, network input) at every size: the A/B
-        // reference of the one-kernel form that small launches without a future frame take (same bits).  Process-wide.
-        prestage_set_small(value != 0);
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "tvl1_async") == 0) {
-        // 1 = rvdd_tvl1flow_batch without iteration counts enqueues its launches and returns; its control word is read by the next
-        // synchronising call.  0 switches back and reports what is pending now.
-        if (!value && h->tvl1) {
-            HIPCHK(h, hipDeviceSynchronize());
-            if (hipError_t e = tvl1_check(h->tvl1, nullptr); e != hipSuccess)
-                return fail(h, RVDD_ERR_HIP, "rvdd_set_option(tvl1_async, 0): a pending asynchronous flow batch failed: %s", hipGetErrorString(e));
-        }
-        h->tvl1_async = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "stream_reset_each") == 0) {
-        // 1 = non-recurrent checkpoints (training_unrollings == 1: recurrentModel.forward resets before every step)
-        h->stream_reset_each = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "stream_flow_from_denoised") == 0) {
-        // 1 = --val_flow_from_denoised in rvdd_video_push: a slot's flow towards the previous frame is matched against the gray
-        // plane of its previous output (from the second output of a video on)
-        h->stream_flow_from_denoised = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "fuse_pre") == 0) {
-        // 0 = preprocessing_layer and EncoderConvs[0][0] as the two convs they are, instead of their composition (the A/B
-        // reference: same map up to fp32 rounding of a different summation order)
-        h->fuse_pre = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "pre5_cin8") == 0) {
-        // 0 = the composed first layer multiplies all 16 channels of the network input's pixel (13 chunks) also where at most 8 are
-        // real and the 7-chunk bank exists (the A/B reference: the same map, K grouped differently)
-        h->pre5_cin8 = value != 0;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "block_fp") == 0) {
-        // 0 = the split-f16 convs split their operands as they are (no per-map power of two): the round-3 behaviour, right only
-        // while every activation stays inside 2^-14 .. 65504 -- kept as the A/B reference of the block floating point
-        h->bfp = value != 0;
-        if (h->amax) {
-            ENTER(h);
-            HIPCHK(h, hipMemset(h->amax, 0, amax_bytes(h->cfg.batch, AMAX_SLOTS)));      // no stale words across the switch
-        }
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "seq_major") == 0) {
-        // 1 = the full-resolution stages of the convunet run one sequence at a time (measured slower: see seq_major_on)
-        if (value < 0 || value > 1) return fail(h, RVDD_ERR_ARG, "rvdd_set_option: seq_major must be 0 or 1");
-        h->seq_major = value;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "bayer_pattern") == 0) {
-        // enum rvdd_bayer of the packed raw frames rvdd_step is handed: every demosaic and re-mosaic of a step follows it
-        if (value < RVDD_BAYER_GBRG || value > RVDD_BAYER_BGGR)
-            return fail(h, RVDD_ERR_ARG, "rvdd_set_option: bayer_pattern must be 0 (GBRG), 1 (GRBG), 2 (RGGB) or 3 (BGGR)");
-        h->bayer = value;
-        return RVDD_OK;
-    }
-    if (std::strcmp(name, "conv_kernel") == 0) {
-        // which kernel runs the 3x3 convs: 0 = the default (48-channel layers on the split-f16 kernel, the others on an f32
-        // kernel chosen by launch size), 1 = the direct f32 kernel everywhere, 2 = the Winograd f32 kernel everywhere (also
-        // where it is the slower choice: tests and A/B measurements), 4 = f32 kernels chosen by launch size
-        if (value < 0 || value > 4 || value == 3) return fail(h, RVDD_ERR_ARG, "rvdd_set_option: conv_kernel must be 0 (default), 1 (direct f32), 2 (winograd f32) or 4 (f32 by size)");
-        h->use_wino = value != 1;
-        h->force_wino = value == 2;
-        h->split16 = value == 0;
-        return RVDD_OK;
-    }
-    return fail(h, RVDD_ERR_ARG, "rvdd_set_option: unknown option '%s' (known: no_warp, warp_raw, prev_noisy_frame, conv_kernel, seq_major, graphs, fuse_upsample, next_split, next_pipe, next_pool, next_projfuse, tvl1_async, block_fp, fuse_pre, pre5_cin8, cout_split, small_prestage, bayer_pattern, stream_reset_each, stream_flow_from_denoised)", name);
+    for (const OptRow& row : kOptions)
+        if (std::strcmp(name, row.name) == 0) return set_option_row(h, row, value);
+    return fail(h, RVDD_ERR_ARG, kUnknownOption, name);
 }
 
 int rvdd_reset(rvdd_t* h) {
@@ -1358,7 +1336,7 @@ namespace {
 // the caller's batch strides (channel slices of the reference's wider `n` / `flow` tensors are strided over the batch).
 int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
     const StepInputs& in = *run.in;
-    const bool nw = h->no_warp;
+    const bool nw = h->opt.no_warp;
     const int H = h->cfg.height, W = h->cfg.width;
     const size_t img = (size_t)H * W, npix = (size_t)h->cfg.batch * img;
     const size_t o = (size_t)sb.b0;
@@ -1382,7 +1360,7 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
     // which of these sequences start a video (rvdd_reset_slots): they bound the network input from raw_prev, the others from the
     // words of their previous output -- each sequence gets the words it would get alone
     const unsigned long long latch = in.latch == ~0ull ? ~0ull : (o < 64 ? in.latch >> o : 0ull);
-    if (h->warp_raw && !nw) {
+    if (h->opt.warp_raw && !nw) {
         // warp_frame with --warp_raw (models/recurrent_model.py:149-152): HA(warp(remosaick(frame), raw-resolution flow)).
         // remosaick(HA(raw)) is raw itself, so the next frame is warped as it came.  next4 is free in this mode: its
         // first quarter holds the re-mosaicked previous output, the second the warped planes.  The generic NCHW warp
@@ -1391,20 +1369,20 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
         {
             Scope sc(h, s, "demosaic(ha_green+ha_rb)", 0.0, (double)n * img * 16.0);
             HIPCHK(h, launch_demosaic(rc_, green, netin + 3, n, H / 2, W / 2, (int64_t)H * W * kNetInC, kNetInC, 1, s, (int64_t)in.rawf,
-                                      h->bayer));
+                                      h->opt.bayer));
         }
         for (int b = 0; b < n; b += dense ? n : 1) {
             const int nb = dense ? n : 1;
             float* packed = h->next4 + (o + b) * img;
             float* warped = h->next4 + npix + (o + b) * img;
-            HIPCHK(h, launch_remosaick4(h->lastden4 + (o + b) * img * 4, packed, nb, H, W, s, h->bayer));
+            HIPCHK(h, launch_remosaick4(h->lastden4 + (o + b) * img * 4, packed, nb, H, W, s, h->opt.bayer));
             HIPCHK(h, launch_warp_nchw(packed, fp_ + b * in.flowf, warped, nb, 4, H / 2, W / 2, s));
             HIPCHK(h, launch_demosaic(warped, green + b * img, netin + b * img * kNetInC + 0, nb, H / 2, W / 2, (int64_t)H * W * kNetInC,
-                                      kNetInC, 1, s, 0, h->bayer));
+                                      kNetInC, 1, s, 0, h->opt.bayer));
             if (h->cfg.future) {
                 HIPCHK(h, launch_warp_nchw(rn_ + b * in.rawf, fn_ + b * in.flowf, warped, nb, 4, H / 2, W / 2, s));
                 HIPCHK(h, launch_demosaic(warped, green + b * img, netin + b * img * kNetInC + 6, nb, H / 2, W / 2,
-                                          (int64_t)H * W * kNetInC, kNetInC, 1, s, 0, h->bayer));
+                                          (int64_t)H * W * kNetInC, kNetInC, 1, s, 0, h->opt.bayer));
             }
         }
         if (amax_netin) HIPCHK(h, launch_amax_reduce(netin, n, (int64_t)img * kNetInC, amax_netin, s));
@@ -1418,15 +1396,15 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
         float* next4 = nullptr;
         if (h->cfg.future) {
             next4 = h->next4 + o * img * 4;
-            HIPCHK(h, launch_demosaic(rn_, green, next4, n, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf, h->bayer));
+            HIPCHK(h, launch_demosaic(rn_, green, next4, n, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf, h->opt.bayer));
         }
         Scope sc(h, s, "netin(ha_green+netin_kernel)", 0.0, (double)n * img * (16.0 + 16.0 + 48.0 + (next4 ? 16.0 : 0.0)));
         // small frames without a future frame: the bound, the green plane and the network input in ONE launch
-        if (!h->is_next() && !h->prev_noisy && netin_small_applies(n, H / 2, W / 2, h->cfg.future != 0)) {
+        if (!h->is_next() && !h->opt.prev_noisy && netin_small_applies(n, H / 2, W / 2, h->cfg.future != 0, h->opt.small_prestage)) {
             const float* rp_ = in.raw_prev ? in.raw_prev + o * in.rawf : nullptr;
             HIPCHK(h, launch_netin_small(rc_, rp_, h->lastden4 + o * img * 4, fp_, netin, n, H / 2, W / 2, (int64_t)in.rawf, (int64_t)in.flowf,
                                          amax_netin && latch != ~0ull ? amax_words(h, run.amax.feat_in, o) : nullptr, amax_netin, s,
-                                         zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch, h->bayer));
+                                         zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch, h->opt.bayer));
             goto prologue_features;
         }
         if (amax_netin) {
@@ -1436,7 +1414,7 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
             HIPCHK(h, launch_netin_bound(rc_, rn_, rp_, n, H / 2, W / 2, (int64_t)in.rawf,
                                          latch == ~0ull ? nullptr : amax_words(h, run.amax.feat_in, o), amax_netin, s,
                                          zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch));
-            if (h->prev_noisy && latch != ~0ull)      // over the runs of sequences that continue a video (one run without a reset)
+            if (h->opt.prev_noisy && latch != ~0ull)      // over the runs of sequences that continue a video (one run without a reset)
                 for (int b = 0; b < n;) {
                     if ((latch >> b) & 1ull) { ++b; continue; }
                     int e = b + 1;
@@ -1446,11 +1424,11 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
                 }
         }
         // ConvNeXtUnet: the input's only reader is the 1x1 projection of the first ConvBlock, which rides in the same kernel
-        const NextBlk* first = h->is_next() && h->next_projfuse ? &h->nx[h->has_feat() ? NX_PRE : NX_ENC0_0] : nullptr;
+        const NextBlk* first = h->is_next() && h->opt.next_projfuse ? &h->nx[h->has_feat() ? NX_PRE : NX_ENC0_0] : nullptr;
         run.netin_proj = first != nullptr;
         HIPCHK(h, launch_netin(rc_, green, h->lastden4 + o * img * 4, fp_, next4, fn_, netin, n, H / 2, W / 2, s, (int64_t)in.rawf,
                                (int64_t)in.flowf, first ? first->w.proj_w : nullptr, first ? first->w.proj_b : nullptr,
-                               first ? h->lv[0].t[0] + o * img * kF : nullptr, h->bayer));
+                               first ? h->lv[0].t[0] + o * img * kF : nullptr, h->opt.bayer));
     }
 prologue_features:
     if (h->has_feat() && !nw) {
@@ -1477,7 +1455,7 @@ struct StepPlan {
 
 // Every launch of one frame-step, in order, on stream s.  The handle is read only: commit_step moves it on.
 int enqueue_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
-    const bool nw = h->no_warp, init = p.init;
+    const bool nw = h->opt.no_warp, init = p.init;
     const int B = p.n, H = h->cfg.height, W = h->cfg.width;
     const size_t npix = (size_t)B * H * W;
     const uint64_t pend = p.pend;
@@ -1502,7 +1480,7 @@ int enqueue_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
         // lastden = n[:, :3] (demosaiced previous noisy frame), features = 0
         // (models/recurrent_model.py:233-245)
         HIPCHK(h, launch_demosaic(raw_prev, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf,
-                                  h->bayer));
+                                  h->opt.bayer));
         if (h->has_feat()) HIPCHK(h, hipMemsetAsync(h->lastfeat, 0, npix * kF * sizeof(float), s));
     } else if (pend) {
         // some sequences start a video (rvdd_reset_slots): the same latch for them alone -- the demosaic over each run of
@@ -1514,7 +1492,7 @@ int enqueue_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
             int e = b + 1;
             while (e < B && ((pend >> e) & 1u)) ++e;
             HIPCHK(h, launch_demosaic(raw_prev + b * in.rawf, h->green + b * img, h->lastden4 + b * img * 4, e - b, H / 2, W / 2,
-                                      (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf, h->bayer));
+                                      (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf, h->opt.bayer));
             b = e;
         }
         HIPCHK(h, launch_latch_zero(pend, h->has_feat() ? h->lastfeat : nullptr, (int64_t)img * kF, h->amax_on() ? h->amax : nullptr, AMAX_SLOTS,
@@ -1523,9 +1501,9 @@ int enqueue_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
     // without warping the previous features are read in place: the net consumes them in its first layer and only
     // its last one writes the new ones
     const int rc = run_net(h, run, h->netin, nw ? h->lastfeat : h->featw, h->lastfeat, p.out_rgb, h->lastden4, s);
-    if (rc == RVDD_OK && h->prev_noisy)     // store_frame = the noisy current frame (models/recurrent_model.py:335-337)
+    if (rc == RVDD_OK && h->opt.prev_noisy)     // store_frame = the noisy current frame (models/recurrent_model.py:335-337)
         HIPCHK(h, launch_demosaic(raw_cur, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf,
-                                  h->bayer));
+                                  h->opt.bayer));
     return rc;
 }
 
@@ -1559,7 +1537,7 @@ int replay_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
             // (whatever failed -- the capture, the instantiation or a launch inside the capture -- nothing has run yet)
             if (g) (void)hipGraphDestroy(g);
             (void)hipGetLastError();
-            h->use_graphs = 0;
+            h->opt.use_graphs = 0;
             return enqueue_step(h, p, s);
         }
         if (h->graphs.size() >= kMaxStepGraphs) {
@@ -1606,7 +1584,7 @@ int step_n(rvdd_t* h, const int n, const float* raw_prev, const float* raw_cur, 
             return fail(h, RVDD_ERR_ARG, "rvdd_step_strided: a batch stride must be 0 (dense) or at least one sequence (%lld / %lld floats)",
                         (long long)rd, (long long)fd);
     }
-    const bool nw = h->no_warp;
+    const bool nw = h->opt.no_warp;
     if (!raw_cur || (!flow_prev && !nw) || !out_rgb) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_cur, flow_prev and out_rgb are required");
     if (h->cfg.future && (!raw_next || (!flow_next && !nw))) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_next and flow_next are required when future=1");
     if (nw) flow_prev = flow_next = nullptr;      // the flows are not looked at (the reference's dataset does not even load them)
@@ -1622,7 +1600,7 @@ int step_n(rvdd_t* h, const int n, const float* raw_prev, const float* raw_cur, 
     if ((init || pend) && !raw_prev) return fail(h, RVDD_ERR_ARG, "rvdd_step: raw_prev is required on the first step of a video");
     const StepPlan plan{n, raw_prev, raw_cur, raw_next, flow_prev, flow_next, raw_stride, flow_stride, out_rgb, init, pend};
     // never captured: a profiled step, the first step of a handle, a partial reset, a step of some slots
-    const bool replay = h->use_graphs && !h->prof_on && h->ran_eagerly && h->gstream && !pend && n == h->cfg.batch;
+    const bool replay = h->opt.use_graphs && !h->prof_on && h->ran_eagerly && h->gstream && !pend && n == h->cfg.batch;
     h->ran_eagerly = true;
     RC(replay ? replay_step(h, plan, s) : enqueue_step(h, plan, s));
     commit_step(h, n, keep);
@@ -1920,7 +1898,7 @@ extern "C" {
 
 int rvdd_tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny,
                         int32_t* iterations, void* stream) {
-    return tvl1flow_batch(h, I0, I1, u, n, nx, ny, iterations, stream, h && h->tvl1_async);
+    return tvl1flow_batch(h, I0, I1, u, n, nx, ny, iterations, stream, h && h->opt.tvl1_async);
 }
 
 int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
@@ -1971,7 +1949,7 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!st.packed) {      // the first push
         if (B > 64) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: needs batch <= 64, as the partial reset marks of rvdd_reset_slots do (batch is %d)", B);
-        if (!h->no_warp && (hh < 16 || ww < 16 || !tvl1_size_ok(ww, hh)))
+        if (!h->opt.no_warp && (hh < 16 || ww < 16 || !tvl1_size_ok(ww, hh)))
             return fail(h, RVDD_ERR_ARG, "rvdd_video_push: raw frames of %d x %d cells are not a size rvdd_tvl1flow_batch accepts (at least 16 x 16 and not too "
                         "skinny for the flow's pyramid); only option no_warp streams this size", ww, hh);
         const int depth = 2 + fut, nd = 1 + fut;
@@ -1991,7 +1969,7 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
         st.packed = pk;      // last: the mark of a complete allocation
     }
     // option "stream_flow_from_denoised": the gray planes of the outputs, allocated by the first push that has it on
-    const bool from_den = h->stream_flow_from_denoised && !h->no_warp;
+    const bool from_den = h->opt.stream_flow_from_denoised && !h->opt.no_warp;
     if (from_den && !st.dgray) RC(dmalloc(h, reinterpret_cast<void**>(&st.dgray), (size_t)B * hw * sizeof(float)));
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
@@ -2019,7 +1997,7 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
         st.was_idle[(size_t)b] = c == RVDD_PUSH_IDLE;
         valid[b] = n >= st.depth;
         if (n >= st.depth) ready.push_back(b);
-        if (n == st.depth || (h->stream_reset_each && n >= st.depth)) fresh.push_back(b);
+        if (n == st.depth || (h->opt.stream_reset_each && n >= st.depth)) fresh.push_back(b);
         if (from_den && n > st.depth && st.dgray_ok[(size_t)b]) den_slots |= 1ull << b;
         st.dgray_ok[(size_t)b] = 0;
     }
@@ -2031,7 +2009,7 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
     auto packed_at = [&](int p) { return st.packed + (size_t)p * B * 4 * hw; };
     auto gray_at = [&](int p) { return st.gray + (size_t)p * B * hw; };
     const float *flow_prev = nullptr, *flow_next = nullptr;
-    if (!h->no_warp) {
+    if (!h->opt.no_warp) {
         HIPCHK(h, launch_stream_gather(gray_at(pc), gray_at(pp), fut ? gray_at(pos) : nullptr, st.dgray, den_slots, st.I0, st.I1, ready.data(), nready, B,
                                        (int64_t)hw, s));
         float* u = nready == B ? st.flows : st.u;      // every slot ready: the batch writes the step's flows itself
@@ -2049,7 +2027,7 @@ int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
     if (from_den) {
         // the plane is taken from the output (with "prev_noisy_frame" lastden holds the noisy demosaic) inside the push that wrote it:
         // the caller may overwrite out_rgb before the next one
-        HIPCHK(h, launch_gray_of_rgb(out_rgb, B, hh, ww, h->bayer, bit_depth, st.dgray, s));
+        HIPCHK(h, launch_gray_of_rgb(out_rgb, B, hh, ww, h->opt.bayer, bit_depth, st.dgray, s));
         for (int b : ready) st.dgray_ok[(size_t)b] = 1;
     }
     return RVDD_OK;
@@ -2095,14 +2073,16 @@ int rvdd_debug_conv_bench(rvdd_t* h, int32_t variant, int32_t level, int32_t ite
     ENTER(h);
     if (!h->finalized || h->is_next()) return fail(h, RVDD_ERR_STATE, "rvdd_debug_conv_bench: needs a finalized convunet handle");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool was = h->prof_on, was_wino = h->use_wino, was_split = h->split16;
+    const bool was = h->prof_on;
+    const int was_conv = h->opt.conv;
     h->prof_on = false;
-    h->use_wino = h->force_wino = variant == 3;   // variant 3 = Winograd kernel, 4 = split-f16 kernel, 0..2 = direct kernel variants
-    h->split16 = variant == 4;
-    conv3x3_set_variant(variant >= 3 ? 0 : variant);
-    ConvCall c;
-    c.in = h->lv[level].t[0]; c.out = h->lv[level].t[1]; c.H = h->lv[level].H; c.W = h->lv[level].W; c.epi = EPI_RELU;
     const Conv3& L = h->cu[CU_ENC1_1];
+    ConvCall c;
+    // variant 3 = Winograd kernel, 4 = split-f16 kernel (the direct one where the layer has no split bank, never one by size),
+    // 0..2 = direct kernel variants
+    h->opt.conv = variant == 3 ? CONV_WINO : variant == 4 && L.wh[c.src] ? CONV_SPLIT16 : CONV_DIRECT;
+    c.variant = variant >= 3 ? 0 : variant;
+    c.in = h->lv[level].t[0]; c.out = h->lv[level].t[1]; c.H = h->lv[level].H; c.W = h->lv[level].W; c.epi = EPI_RELU;
     NetRun run;
     run.n = h->cfg.batch;
     const Sub all{0, run.n};
@@ -2116,11 +2096,8 @@ int rvdd_debug_conv_bench(rvdd_t* h, int32_t variant, int32_t level, int32_t ite
         (void)hipEventElapsedTime(&t, h->t0, h->t1);
         *ms = t / iters;
     }
-    conv3x3_set_variant(0);
     h->prof_on = was;
-    h->use_wino = was_wino;
-    h->force_wino = false;
-    h->split16 = was_split;
+    h->opt.conv = was_conv;
     return rc;
 }
 

@@ -4,7 +4,7 @@ namespace {
 // encoder_convs[0].blocks[0] projects cat[y, warped features] 96 -> 48 (new_unet.py:381-382): the features' half in the feature
 // warp (prestage.hip warp48_proj_kernel: `featw` then holds W_f warp(f) + bias), y's half in the epilogue of the block that forms y
 bool next_pf_pre(const rvdd_t* h) {
-    return h->is_next() && h->has_feat() && !h->no_warp && h->next_projfuse && h->next_split && h->next_pipe &&
+    return h->is_next() && h->has_feat() && !h->opt.no_warp && h->opt.next_projfuse && h->opt.next_split && h->opt.next_pipe &&
            h->nx[NX_PRE].w.fc1_h && h->nx[NX_ENC0_0].half[0].frag && h->nx[NX_ENC0_0].half[1].frag;
 }
 
@@ -207,8 +207,8 @@ int run_convnext(rvdd_t* h, const NetRun& run, const float* netin, const float* 
     // the fused kernel takes the split-f16 filter fragments unless the option asks for the f32-MFMA form
     auto fused_w = [&](const NextBlk& nb) {
         NextBlockW w = nb.w;
-        if (!h->next_split) w.fc1_h = nullptr;
-        w.pipe = h->next_pipe ? 1 : 0;
+        if (!h->opt.next_split) w.fc1_h = nullptr;
+        w.pipe = h->opt.next_pipe ? 1 : 0;
         return w;
     };
     auto T = [&](int l, int k) { return lv[l].t[k]; };
@@ -235,7 +235,7 @@ int run_convnext(rvdd_t* h, const NetRun& run, const float* netin, const float* 
     // The 96 -> 48 projection of decoder_convs[i].blocks[0] (cat((x_dec, x_enc)), :321-329) as two halves in the epilogues of the
     // blocks that form x_enc (the last block of encoder level hi = 2 - i) and x_dec (decoder_ups[i]): where the upsampled map has the
     // skip's size (no zero_pad_features in between) and every kernel involved is the pipelined split-f16 block
-    const bool pf_ok = h->next_projfuse && h->next_split && h->next_pipe && h->next_pool;
+    const bool pf_ok = h->opt.next_projfuse && h->opt.next_split && h->opt.next_pipe && h->opt.next_pool;
     auto pf_level = [&](int hi) {
         const int i = 2 - hi;
         return pf_ok && 2 * lv[hi + 1].H == lv[hi].H && 2 * lv[hi + 1].W == lv[hi].W && blocks[nx_enc(hi, 1)].w.fc1_h &&
@@ -268,7 +268,7 @@ int run_convnext(rvdd_t* h, const NetRun& run, const float* netin, const float* 
     // the last block of an encoder level feeds MaxPool2d(2) (DownConv, :200-204): the fused kernel pools in its epilogue
     auto block_pool = [&](int bi, const float* x, float* out, float* pooled, int lvl) -> int {
         if (pf_level(lvl)) return block_proj(bi, x, out, pooled, blocks[nx_dec(2 - lvl, 0)].half[1], lv[lvl].H, lv[lvl].W);
-        if (!h->next_pool) {
+        if (!h->opt.next_pool) {
             RC(block(bi, x, out, lvl, lv[lvl].H, lv[lvl].W));
             Scope sc(h, s, "maxpool2_kernel", 0.0, (double)B * lv[lvl].H * lv[lvl].W * 192.0 * 1.25);
             HIPCHK(h, launch_maxpool2(out, pooled, B, lv[lvl].H, lv[lvl].W, s));

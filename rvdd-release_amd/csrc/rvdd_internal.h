@@ -183,8 +183,8 @@ __device__ __forceinline__ bool seq_latched(unsigned long long mask, int b) {
 hipError_t launch_amax_reduce(const float* map, int B, int64_t hw_c, unsigned* words, hipStream_t s, int up = 0);
 
 
-// cin = 16 or 48.  Returns hipGetLastError().
-hipError_t launch_conv3x3(const ConvArgs& a, int cin, int epi, hipStream_t s);
+// cin = 16 or 48.  Returns hipGetLastError().  variant 1, 2: A/B forms of the plain 48 -> 48 ReLU layer (rvdd_debug_conv_bench only)
+hipError_t launch_conv3x3(const ConvArgs& a, int cin, int epi, hipStream_t s, int variant = 0);
 size_t conv3x3_weight_floats(int cin);
 // Winograd F(2x2,3x3) variant for 48 -> 48 layers; a.w = bank arranged by arrange_wino3x3 (runtime.hip)
 hipError_t launch_wino3x3(const ConvArgs& a, int cin, int epi, hipStream_t s);   // cin: 48, or 16 = the zero-padded network input
@@ -192,7 +192,8 @@ size_t wino3x3_weight_floats();
 // the same layers on the F16 matrix pipe with split f32 operands (conv3x3h.hip); a.w = the split bank arranged by
 // arrange_conv3x3h (runtime.hip), a.wscale its scale; cin 48 (every epilogue, with or without a.acc_in, with a.ups for
 // UpConv's fused upsample) or 16 (the zero-padded network input): every 3x3 conv of the convunet by default
-hipError_t launch_conv3x3h(const ConvArgs& a, int cin, int epi, hipStream_t s);
+// cout_split = false: no launch takes the output-channel split of small launches (conv3x3h.hip MT = 1; option "cout_split" 0)
+hipError_t launch_conv3x3h(const ConvArgs& a, int cin, int epi, hipStream_t s, bool cout_split = true);
 size_t conv3x3h_weight_bytes(int cin);
 // preprocessing_layer composed with the first source of EncoderConvs[0][0]: one 5x5 conv of the 16-channel network input
 // (conv3x3h.hip HGeo KS = 5; runtime.hip compose_pre_enc0), and the fix of its border ring: part -= sum over the 3x3 taps d
@@ -203,9 +204,7 @@ hipError_t launch_conv5x5h_c8(const ConvArgs& a, hipStream_t s);
 size_t conv5x5h_weight_bytes(int cin);      // cin = 8 or 16: the channels multiplied
 hipError_t launch_pre_border_fix(const float* netin, const float* w1, const float* b1, const float* w2, float* part, int B, int H, int W,
                                  hipStream_t s);
-void conv3x3h_set_cout_split(bool on);   // false: no launch takes the output-channel split of small launches (conv3x3h.hip MT = 1); process-wide
 void conv3x3h_set_groups(int g);   // stand-alone harness (-DRVDD_CONV_GROUPS2): 2 = two groups of four waves with an 8x16 tile each
-void conv3x3_set_variant(int v);   // A/B switch used by rvdd_debug_conv_bench only
 
 // -------------------------------------------------------------- pre-stages --
 // Hamilton-Adams: raw [n][4][h][w] -> green plane scratch [n][2h][2w] -> RGB
@@ -237,13 +236,13 @@ hipError_t launch_netin_bound(const float* raw_a, const float* raw_b, const floa
                               unsigned* zero_b = nullptr, size_t zero_nb = 0, unsigned long long latch = ~0ull);
 // src NHWC48 -> dst NHWC48.
 // the three pre-stage kernels of a small frame-step without a future frame in one launch (prestage.hip netin_small_kernel); same bits
-bool netin_small_applies(int B, int h, int w, bool future);
+// (enabled = false: never -- option "small_prestage" 0)
+bool netin_small_applies(int B, int h, int w, bool future, bool enabled = true);
 // (raw_prev: the first step of a video, whose bound also covers the previous raw frame -- prev_words is null then)
 hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const float* prev4, const float* flow_prev, float* netin, int B,
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,
                               hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb,
                               unsigned long long latch, int bayer);
-void prestage_set_small(bool on);      // false: never; process-wide
 hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W,
                          hipStream_t s, int64_t flow_bstride = 0);
 // the same, and a 48 -> 48 projection of every warped pixel: dst = W warp(src) + bias; frag / inv_e = the projection as a

@@ -164,7 +164,7 @@ def test_one_kernel_and_three_kernel_prestage_agree_under_a_pattern():
             rt.set_option("small_prestage", small)
             outs.append(_run(rt, [seq], T, 0))
         finally:
-            rt.set_option("small_prestage", 1)          # process-wide: back to the default
+            rt.set_option("small_prestage", 1)          # harmless: the option is per handle
             rt.close()
     assert torch.equal(outs[0], outs[1]), float((outs[0] - outs[1]).abs().max())
 

@@ -1121,7 +1121,7 @@ def test_conv_output_channel_split_same_bits(arch, stem, fut):
                 rt.close()
         finally:
             from rvdd_release_amd.util._ops import ops_runtime
-            ops_runtime(0).set_option("cout_split", 1)          # process-wide switch: back to the default
+            ops_runtime(0).set_option("cout_split", 1)          # harmless: the option is per handle
         for a, b in zip(outs[0][0], outs[1][0]):
             assert torch.equal(a, b), (arch, B, H, W, float((a - b).abs().max()))
         if outs[0][1] is not None:
