@@ -313,6 +313,49 @@ int rvdd_video_push(rvdd_t* h, const void* frames /* [B, one frame each] */, int
                     int32_t bit_depth, const uint8_t* ctl /* HOST [B], NULL = all NEXT */,
                     float* out_rgb /* [B,3,H,W] */, uint8_t* valid /* HOST [B] */, void* stream);
 
+/* ---- raw datasets from sRGB video ------------------------------------------- */
+
+/* dataset/generate_raw_from_RGB.py (:45-127 single_image_rgb2raw, :168-189 the 12-bit range, the percentile matching to CRVD
+ * and the noise) in one pointwise kernel: sRGB frames -> the four images the reference writes per frame, all HWC.
+ * Per pixel and channel, every operation rounded to f32 on its own and both divisions correctly rounded:
+ *   v   = clamp(((float)srgb + dither) / 266, 0, 1)
+ *   p   = pow(max(0.5 - sin(asin(1 - 2 v) / 3), 1e-8), 2.2)                 inverse smoothstep, gamma expansion
+ *   cam[k] = (p[0] M[k][0] + p[1] M[k][1]) + p[2] M[k][2]                   the CRVD rgb2cam matrix (:101)
+ *   y   = clamp(cam[k] * g[k], 0, 1),  g = ((1 / red_gain) / rgb_gain, 1 / rgb_gain, (1 / blue_gain) / rgb_gain) formed in
+ *         f32 on the host from the gains rounded to f32 (:77)
+ *   lin = y * 3855 + 240;  lin = A * (lin - 245) / 2060 + B,  (A, B) = (3344, 266) at ISO 3200, (3807, 268) at ISO 12800
+ * Outputs (each may be NULL; with all four NULL nothing is launched):
+ *   lin_f32 [n,H,W,3]      lin -- what rvdd_ppipe(bit_depth 12, HWC strides) takes to make gt_RGB;
+ *   lin_u16 [n,H,W,3]      clip(rint(lin), 0, 4095): gt_raw_linear_RGB;
+ *   gt_raw  [n,H/2,W/2,4]  the mosaic of lin in `pattern` (enum rvdd_bayer; GBRG is the reference's mosaic()): channel k is
+ *                          CFA position (k >> 1, k & 1) of a 2x2 cell -- RVDD_RAW_PACKED_HWC in f32, which rvdd_ingest_raw and
+ *                          rvdd_video_push read as it lies;
+ *   noisy   [n,H/2,W/2,4]  m + sqrt(max(ka * m - kb, 0)) * z of the mosaic m: (ka, kb) = (8.0034, 2043.51144) at ISO 3200,
+ *                          (28.3015, 6307.62081) at ISO 12800.
+ * The draws.  dither [n,H,W,3] (the reference's uniform quantisation noise in [-0.5, 0.5)) and normal [n,H/2,W/2,4] (z) may be
+ * handed in; where one is NULL the kernel draws it with Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments
+ * 0x9E3779B9 / 0xBB67AE85): key = (low, high) 32 bits of `seed`, counter = (element, stream, low, high 32 bits of frame0 + i)
+ * for image i of the call, output words w_0..w_3.
+ *   stream 0, element = pixel y * W + x: dither of channel c = (w_c >> 8) * 2^-24 - 0.5 (exact in f32);
+ *   stream 1, element = cell y * (W/2) + x: u = ((w_0 >> 8) + 1) * 2^-24, v = (w_1 >> 8) * 2^-24, r = sqrt(-2 ln u),
+ *             (z_0, z_1) = (r cos 2 pi v, r sin 2 pi v), (z_2, z_3) the same from (w_2, w_3); z_k goes to CFA position k.
+ * The 24-bit uniforms end the normal's tail at sqrt(48 ln 2) = 5.77 sigma.  A draw depends on (seed, frame, element) alone, so:
+ *   - rvdd_unprocess with NULL planes is bit for bit rvdd_unprocess fed the planes rvdd_unprocess_draws writes for the same
+ *     (seed, frame0, n, H, W);
+ *   - a call of n frames is bit for bit n calls of one frame at frame0 + i.
+ * iso other than 3200 / 12800, odd H or W, pattern outside 0..3, H * W >= 2^32, n < 0 or a zero gain: RVDD_ERR_ARG (the message
+ * names the argument).  n = 0 does nothing.  Asynchronous and stream-ordered; nothing is read back.  With (W/2) % 4 == 0 and
+ * 16-byte aligned pointers a thread takes two cells with 16-byte stores; same bits either way. */
+int rvdd_unprocess(rvdd_t* h, const uint8_t* srgb /* [n,H,W,3] */, int32_t n, int32_t H, int32_t W,
+                   double rgb_gain, double red_gain, double blue_gain, int32_t iso, int32_t pattern /* enum rvdd_bayer */,
+                   const float* dither /* nullable */, const float* normal /* nullable */, uint64_t seed, int64_t frame0,
+                   float* lin_f32, uint16_t* lin_u16, float* gt_raw, float* noisy, void* stream);
+
+/* The two planes rvdd_unprocess draws for (seed, frame0 .. frame0 + n - 1), alone: dither [n,H,W,3], normal [n,H/2,W/2,4];
+ * either may be NULL.  Shape errors as rvdd_unprocess.  Asynchronous and stream-ordered. */
+int rvdd_unprocess_draws(rvdd_t* h, uint64_t seed, int64_t frame0, int32_t n, int32_t H, int32_t W,
+                         float* dither, float* normal, void* stream);
+
 /* dataset/fwd_ppipe.py `ppipe(im, rgb_gain, red_gain, blue_gain, iso)` (:48-77) fused with the range
  * normalisation in front of it (:131-137) and the uint8 conversion behind it (:141): linear camera RGB ->
  * display sRGB (inverse percentile matching per ISO, black level, white-balance gains, inverse CCM,

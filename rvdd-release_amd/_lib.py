@@ -57,6 +57,9 @@ _PROTOS = {
     "rvdd_ingest_raw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "rvdd_gray_of_rgb": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                 _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),
+    "rvdd_unprocess_draws": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "rvdd_ppipe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                              C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P]),
     "rvdd_srgb_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double),

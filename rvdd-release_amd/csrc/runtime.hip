@@ -1931,6 +1931,45 @@ int rvdd_gray_of_rgb(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t 
     return RVDD_OK;
 }
 
+// the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine
+static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int32_t W) {
+    if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);
+    if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "%s: W must be even and >= 2, got %d", fn, W);
+    if ((int64_t)H * W >= (1ll << 32)) return fail(h, RVDD_ERR_ARG, "%s: H * W must be below 2^32 (the draws count a frame's pixels in 32 bits), got %d x %d", fn, H, W);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    return RVDD_OK;
+}
+
+int rvdd_unprocess(rvdd_t* h, const uint8_t* srgb, int32_t n, int32_t H, int32_t W, double rgb_gain, double red_gain, double blue_gain,
+                   int32_t iso, int32_t pattern, const float* dither, const float* normal, uint64_t seed, int64_t frame0, float* lin_f32,
+                   uint16_t* lin_u16, float* gt_raw, float* noisy, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (iso != 3200 && iso != 12800) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: iso must be 3200 or 12800, got %d", iso);
+    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
+        return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    RC(unprocess_shape(h, "rvdd_unprocess", n, H, W));
+    if (n == 0) return RVDD_OK;
+    if (!srgb) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: srgb is required");
+    if (!(rgb_gain != 0.0) || !(red_gain != 0.0) || !(blue_gain != 0.0)) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: zero gain (rgb_gain, red_gain, blue_gain)");
+    ENTER(h);
+    // generate_raw_from_RGB.py:77: float32 tensors -- (1 / red_gain, 1, 1 / blue_gain) / rgb_gain, each quotient rounded to f32
+    const float rgb = (float)rgb_gain;
+    const float g[3] = {(1.0f / (float)red_gain) / rgb, 1.0f / rgb, (1.0f / (float)blue_gain) / rgb};
+    HIPCHK(h, launch_unprocess(srgb, n, H / 2, W / 2, g, iso, pattern, dither, normal, seed, frame0, lin_f32, lin_u16, gt_raw, noisy,
+                               static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_unprocess_draws(rvdd_t* h, uint64_t seed, int64_t frame0, int32_t n, int32_t H, int32_t W, float* dither, float* normal,
+                         void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    RC(unprocess_shape(h, "rvdd_unprocess_draws", n, H, W));
+    if (n == 0) return RVDD_OK;
+    ENTER(h);
+    HIPCHK(h, launch_unprocess_draws(seed, frame0, n, H / 2, W / 2, dither, normal, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t bit_depth, const uint8_t* ctl, float* out_rgb,
                     uint8_t* valid, void* stream) {
     if (!h) return RVDD_ERR_ARG;

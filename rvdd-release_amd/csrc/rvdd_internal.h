@@ -361,6 +361,14 @@ hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const 
 // flows [ndir][B][2][hw] of the step from the batch's u [ndir * nready][2][hw]: zero for the slots that are not ready (B <= 64)
 hipError_t launch_stream_scatter(const float* u, float* flows, const int* slots, int nready, int ndir, int B, int64_t hw, hipStream_t s);
 
+// unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
+// srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from
+// (seed, frame0 + image) then); lin_f32 / lin_u16 [n][2hh][2ww][3], gt_raw / noisy [n][hh][ww][4], each nullable
+hipError_t launch_unprocess(const uint8_t* srgb, int n, int hh, int ww, const float g[3], int iso, int bayer, const float* dither,
+                            const float* normal, uint64_t seed, int64_t frame0, float* lin_f32, uint16_t* lin_u16, float* gt_raw, float* noisy,
+                            hipStream_t s);
+hipError_t launch_unprocess_draws(uint64_t seed, int64_t frame0, int n, int hh, int ww, float* dither, float* normal, hipStream_t s);
+
 // ------------------------------------------------------------------ TV-L1 --
 struct Tvl1Workspace;
 hipError_t tvl1_alloc(Tvl1Workspace** out, int nx, int ny);

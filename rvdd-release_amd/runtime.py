@@ -426,6 +426,64 @@ class RvddRuntime:
                                         self._stream()), "rvdd_ppipe")
         return (u8, f32) if want_float else u8
 
+    # -- raw datasets from sRGB video -------------------------------------------
+    UNPROCESS_OUTPUTS = ("lin_f32", "lin_u16", "gt_raw", "noisy")
+
+    def _unprocess_plane(self, t, shape, name):
+        if t is None:
+            return None
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"unprocess: {name} must be a GPU tensor (rvdd has no CPU path)")
+        return _chk_dev(t, shape, name, self.device)
+
+    def unprocess(self, srgb: torch.Tensor, rgb_gain: float, red_gain: float, blue_gain: float, iso: int,
+                  pattern: str = "gbrg", dither: Optional[torch.Tensor] = None, normal: Optional[torch.Tensor] = None,
+                  seed: int = 0, frame0: int = 0, want=UNPROCESS_OUTPUTS) -> Dict[str, torch.Tensor]:
+        """dataset/generate_raw_from_RGB.py:45-127, :168-189 (rvdd_unprocess).  srgb: uint8 [n,H,W,3] GPU tensor, H and W even.
+        -> the outputs named in `want`: lin_f32 [n,H,W,3] float32 (what `ppipe(..., bit_depth=12, layout="hwc")` takes),
+        lin_u16 [n,H,W,3] uint16, gt_raw and noisy [n,H/2,W/2,4] float32 in `pattern` (one of BAYER_PATTERNS), the packed HWC
+        layout `ingest_raw` / `video_push` read.  dither [n,H,W,3] / normal [n,H/2,W/2,4]: the random planes; where None the
+        kernel draws them from (seed, frame0 + i) for image i (`unprocess_draws` gives the same planes)."""
+        if pattern not in BAYER_PATTERNS:
+            raise ValueError(f"unprocess: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
+        unknown = [w for w in want if w not in self.UNPROCESS_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unprocess: unknown outputs {unknown}; known: {', '.join(self.UNPROCESS_OUTPUTS)}")
+        if not torch.is_tensor(srgb) or not srgb.is_cuda:
+            raise RuntimeError("unprocess: srgb must be a GPU tensor (rvdd has no CPU path)")
+        if srgb.device.index != self.device:
+            raise RuntimeError(f"unprocess: srgb lives on cuda:{srgb.device.index} but this runtime drives cuda:{self.device}")
+        if srgb.dtype != torch.uint8 or srgb.dim() != 4 or srgb.shape[3] != 3:
+            raise RuntimeError(f"unprocess: srgb is uint8 [n,H,W,3], got {srgb.dtype} {tuple(srgb.shape)}")
+        n, H, W, _ = srgb.shape
+        if H % 2 or W % 2:
+            raise RuntimeError(f"unprocess: H and W must be even (crop the frame as the reference does), got {H} x {W}")
+        srgb = srgb if srgb.is_contiguous() else srgb.contiguous()
+        dither = self._unprocess_plane(dither, (n, H, W, 3), "dither")
+        normal = self._unprocess_plane(normal, (n, H // 2, W // 2, 4), "normal")
+        out = {}
+        for name, shape, dt in (("lin_f32", (n, H, W, 3), torch.float32), ("lin_u16", (n, H, W, 3), torch.uint16),
+                                ("gt_raw", (n, H // 2, W // 2, 4), torch.float32), ("noisy", (n, H // 2, W // 2, 4), torch.float32)):
+            if name in want:
+                out[name] = torch.empty(shape, dtype=dt, device=self._tdev)
+        self._check(self.lib.rvdd_unprocess(self.h, _ptr(srgb), n, H, W, float(rgb_gain), float(red_gain), float(blue_gain), int(iso),
+                                            BAYER_PATTERNS.index(pattern), _ptr(dither), _ptr(normal), int(seed) & (2 ** 64 - 1),
+                                            int(frame0), _ptr(out.get("lin_f32")), _ptr(out.get("lin_u16")), _ptr(out.get("gt_raw")),
+                                            _ptr(out.get("noisy")), self._stream()), "rvdd_unprocess")
+        return out
+
+    def unprocess_draws(self, seed: int, frame0: int, n: int, H: int, W: int, want_dither: bool = True, want_normal: bool = True):
+        """-> (dither [n,H,W,3], normal [n,H/2,W/2,4]), None for one not wanted: the planes `unprocess` draws for
+        (seed, frame0 .. frame0 + n - 1) (rvdd_unprocess_draws)."""
+        n, H, W = int(n), int(H), int(W)
+        if n < 0 or H < 2 or W < 2 or H % 2 or W % 2:
+            raise RuntimeError(f"unprocess_draws: n >= 0 and even H, W >= 2, got n = {n}, {H} x {W}")
+        dither = torch.empty(n, H, W, 3, dtype=torch.float32, device=self._tdev) if want_dither else None
+        normal = torch.empty(n, H // 2, W // 2, 4, dtype=torch.float32, device=self._tdev) if want_normal else None
+        self._check(self.lib.rvdd_unprocess_draws(self.h, int(seed) & (2 ** 64 - 1), int(frame0), n, H, W, _ptr(dither), _ptr(normal),
+                                                  self._stream()), "rvdd_unprocess_draws")
+        return dither, normal
+
     def srgb_metrics(self, a: torch.Tensor, b: torch.Tensor):
         """dataset/fwd_ppipe.py:79-86 on uint8 [n,H,W,3] images -> (psnr[n], ssim[n]) Python floats."""
         if a.shape != b.shape:
