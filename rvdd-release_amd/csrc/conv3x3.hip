@@ -26,7 +26,7 @@
 // reads channels 16j+4g..+3 of its pixel with ONE ds_read_b128; MFMA number i
 // of that chunk consumes element i, i.e. k-slot g of MFMA i is channel
 // 16j+4g+i.  The weights are pre-arranged on the host (arrange_conv3x3,
-// runtime.hip) as [tap][j][m][lane = 16g + cout&15][i] so that the matching A
+// net_convunet.hip) as [tap][j][m][lane = 16g + cout&15][i] so that the matching A
 // fragment is one ds_read_b128 too, lane-linear: each of the four 16-lane groups
 // the read is served in covers one whole 256-B bank row (conflict-free).
 // Fragments for group n+1 are read while the 24 MFMAs of group n issue.

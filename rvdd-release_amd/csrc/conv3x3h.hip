@@ -65,7 +65,7 @@ constexpr int C8_PITCH = 16;
 // issues besides the MFMAs (profiles/r04_conv3x3h_tile_loop_parts.txt), and the 8-row tile's halo is 1.41x its pixels.
 // KS = 3: the convunet's 3x3 convs.  KS = 5, CIN = 16: preprocessing_layer (3x3, no activation, unet.py:742) composed with the
 // first source of EncoderConvs[0][0] (3x3) into ONE 5x5 conv of the network input -- two linear maps in a row are one linear
-// map (runtime.hip: compose_pre_enc0); what the zero padding BETWEEN the two does at the image border is put right by
+// map (net_convunet.hip: compose_pre_enc0); what the zero padding BETWEEN the two does at the image border is put right by
 // pre_border_fix_kernel below.
 // MT = 3 (every launch with enough tiles): a workgroup forms all 48 output channels of its tiles.  MT = 1 (launches with at most a
 // third of a tile per CU -- the coarse levels of one small sequence): a workgroup forms ONE block of 16 output channels

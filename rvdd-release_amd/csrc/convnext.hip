@@ -345,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void convblock_kernel(const float* __restri
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // ---- tiles: as dwln_kernel (persistent, the workgroups of one XCD walk one contiguous band)
+    // ---- tiles: persistent workgroups, those of one XCD walk one contiguous band of the tile list
     const int per_xcd = (ntiles + 7) >> 3;
     const int band_end = min(((int)(blockIdx.x & 7) + 1) * per_xcd, ntiles);
     const int stride = (int)(gridDim.x >> 3);
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(512, 2) void convblock_kernel(const float* __restri
         return p;
     };
 
-    // ---- depth-wise phase: lane -> (row of the wave's four rows, quad of four pixels, channel group), see dwln_kernel
+    // ---- depth-wise phase: lane -> (row of the wave's four rows, quad of four pixels, channel group g = four of a chunk's 16 channels)
     const int g = lane & 3;
     const int idx = lane >> 2;
     const int quad = idx & 3;
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(512, 2) void convblock_kernel(const float* __restri
 #pragma unroll
         for (int d = 0; d < 4; ++d) rd0[c][d] = (row * 6 + quad) * 64 + ((d ^ ((t0 + c) & 3)) * 4 + g) * 4;
 
-    // ---- MLP phase: lane -> (pixel lr of a 16-pixel group = one tile row, channel group kk), see mlp_kernel.  Its lane
+    // ---- MLP phase: lane -> (pixel lr of a 16-pixel group = one tile row, channel group kk: the MFMA operand layout).  Its lane
     // constants (fragment pointers, row offsets, exchange addresses) are derived INSIDE the tile loop from an opaque copy
     // of the lane index: as loop invariants they would stay alive through the depth-wise phase, which has no register to
     // spare (the kernel is capped at 256 registers so that the MFMA results stay in VGPRs, where the GELU reads them).

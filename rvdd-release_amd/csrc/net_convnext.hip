@@ -1,5 +1,5 @@
-// ConvNeXtUnet schedule (networks/new_unet.py:332-362, 365-430) -- included by runtime.hip.
-namespace {
+// The ConvNeXt net: weight banks of its ConvBlocks and the schedule of one forward (networks/new_unet.py:332-362, 365-430).
+#include "runtime_internal.h"
 
 // encoder_convs[0].blocks[0] projects cat[y, warped features] 96 -> 48 (new_unet.py:381-382): the features' half in the feature
 // warp (prestage.hip warp48_proj_kernel: `featw` then holds W_f warp(f) + bias), y's half in the epilogue of the block that forms y
@@ -340,5 +340,3 @@ int run_convnext(rvdd_t* h, const NetRun& run, const float* netin, const float* 
     }
     return RVDD_OK;
 }
-
-}  // namespace

@@ -1,0 +1,224 @@
+// The stand-alone operators of the ABI: each one validates, selects the handle's device and launches.
+#include "runtime_internal.h"
+
+namespace {
+// rvdd_psnr_l1_batch as `fn`, the entry point the caller used (rvdd_psnr_l1: one slice)
+int psnr_l1_n(rvdd_t* h, const char* fn, const float* den, const float* gt, int32_t n, int64_t count, float* out, void* stream) {
+    if (h && n == 0) return RVDD_OK;
+    if (!h || !den || !gt || !out || n < 0 || count <= 0) return fail(h, RVDD_ERR_ARG, "%s: bad argument", fn);
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int nblk = (int)((count + 256 * 16 - 1) / (256 * 16));      // the partition of every slice
+    if (nblk > 1024) nblk = 1024;
+    RC(ensure_loss_batch(h, (size_t)n * (2 * nblk + 2)));
+    double* res = h->loss_batch + (size_t)n * 2 * nblk;
+    HIPCHK(h, launch_loss_reduce_batch(den, gt, n, count, h->loss_batch, nblk, res, s));
+    std::vector<double> r((size_t)2 * n);
+    HIPCHK(h, hipMemcpyAsync(r.data(), res, r.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (hipError_t e = tvl1_check(h->tvl1, s); e != hipSuccess)       // an asynchronous flow batch in front of the frames just measured
+        return fail(h, RVDD_ERR_HIP, "%s: an asynchronous rvdd_tvl1flow_batch before this call failed: %s", fn, hipGetErrorString(e));
+    for (int i = 0; i < n; ++i) {
+        out[2 * i] = (float)(100.0 * r[2 * i] / (double)count);
+        out[2 * i + 1] = (float)(10.0 * std::log10(4.0 / (r[2 * i + 1] / (double)count)));
+    }
+    return RVDD_OK;
+}
+}  // namespace
+
+// rvdd_tvl1flow_batch; `async`: without iteration counts the batch is enqueued and the call returns (option "tvl1_async")
+int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
+                   void* stream, bool async) {
+    if (h && n == 0) return RVDD_OK;
+    if (!h || !I0 || !I1 || !u || n < 0 || nx < 16 || ny < 16)
+        return fail(h, RVDD_ERR_ARG, "rvdd_tvl1flow_batch: bad argument (images must be >= 16x16)");
+    ENTER(h);
+    if (!tvl1_size_ok(nx, ny))
+        return fail(h, RVDD_ERR_ARG, "rvdd_tvl1flow_batch: image too skinny for its pyramid (the reference reads out of bounds at this size)");
+    if (!h->tvl1 || tvl1_ws_nx(h->tvl1) != nx || tvl1_ws_ny(h->tvl1) != ny) {
+        HIPCHK(h, hipDeviceSynchronize());
+        HIPCHK(h, tvl1_check(h->tvl1, static_cast<hipStream_t>(stream)));      // what an asynchronous batch on the old workspace left unread
+        tvl1_free(h->tvl1);
+        h->tvl1 = nullptr;
+        HIPCHK(h, tvl1_alloc(&h->tvl1, nx, ny));
+    }
+    std::vector<int> it((size_t)n, 0);
+    HIPCHK(h, tvl1_run_batch(h->tvl1, I0, I1, u, n, static_cast<hipStream_t>(stream), iterations ? it.data() : nullptr, async));
+    if (iterations)
+        for (int i = 0; i < n; ++i) iterations[i] = it[(size_t)i];
+    return RVDD_OK;
+}
+
+extern "C" {
+
+int rvdd_psnr_l1(rvdd_t* h, const float* den, const float* gt, int64_t count, float* out2, void* stream) {
+    return psnr_l1_n(h, "rvdd_psnr_l1", den, gt, 1, count, out2, stream);
+}
+
+int rvdd_psnr_l1_batch(rvdd_t* h, const float* den, const float* gt, int32_t n, int64_t count, float* out, void* stream) {
+    return psnr_l1_n(h, "rvdd_psnr_l1_batch", den, gt, n, count, out, stream);
+}
+
+int rvdd_demosaic_ha_bayer(rvdd_t* h, const float* raw, int32_t n, int32_t hh, int32_t ww, int32_t pattern, float* rgb, void* stream) {
+    if (h && (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR))
+        return fail(h, RVDD_ERR_ARG, "rvdd_demosaic_ha_bayer: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    if (h && n == 0) return RVDD_OK;       // an empty batch is valid and launches nothing
+    if (!h || !raw || !rgb || n < 0 || hh < 1 || ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_demosaic_ha_bayer: bad argument");
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RC(ensure_scratch(h, (size_t)n * 4 * hh * ww * sizeof(float)));
+    const int64_t hw = (int64_t)4 * hh * ww;
+    HIPCHK(h, launch_demosaic(raw, h->scratch, rgb, n, hh, ww, 3 * hw, 1, (int)hw, s, 0, pattern));
+    return RVDD_OK;
+}
+
+int rvdd_demosaic_ha(rvdd_t* h, const float* raw, int32_t n, int32_t hh, int32_t ww, float* rgb, void* stream) {
+    return rvdd_demosaic_ha_bayer(h, raw, n, hh, ww, RVDD_BAYER_GBRG, rgb, stream);
+}
+
+int rvdd_warp_bicubic(rvdd_t* h, const float* x, const float* flow, int32_t n, int32_t c, int32_t H, int32_t W,
+                      float* y, void* stream) {
+    if (h && n == 0) return RVDD_OK;
+    if (!h || !x || !flow || !y || n < 0 || c < 1 || H < 2 || W < 2) return fail(h, RVDD_ERR_ARG, "rvdd_warp_bicubic: bad argument");
+    ENTER(h);
+    HIPCHK(h, launch_warp_nchw(x, flow, y, n, c, H, W, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_upsample_factor_2(rvdd_t* h, const float* t, int32_t n, int32_t c, int32_t hh, int32_t ww,
+                           float multiply_by, float* out, void* stream) {
+    if (h && n == 0) return RVDD_OK;
+    if (!h || !t || !out || n < 0 || c < 1 || hh < 1 || ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_upsample_factor_2: bad argument");
+    ENTER(h);
+    HIPCHK(h, launch_upsample_flow(t, out, n * c, hh, ww, multiply_by, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_tvl1flow(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t nx, int32_t ny, int32_t* iterations,
+                  void* stream) {
+    if (!h || !I0 || !I1 || !u || nx < 16 || ny < 16) return fail(h, RVDD_ERR_ARG, "rvdd_tvl1flow: bad argument (images must be >= 16x16)");
+    ENTER(h);
+    if (!tvl1_size_ok(nx, ny))
+        return fail(h, RVDD_ERR_ARG, "rvdd_tvl1flow: image too skinny for its pyramid (the reference reads out of bounds at this size)");
+    if (!h->tvl1 || tvl1_ws_nx(h->tvl1) != nx || tvl1_ws_ny(h->tvl1) != ny) {
+        HIPCHK(h, hipDeviceSynchronize());
+        HIPCHK(h, tvl1_check(h->tvl1, static_cast<hipStream_t>(stream)));      // what an asynchronous batch on the old workspace left unread
+        tvl1_free(h->tvl1);
+        h->tvl1 = nullptr;
+        HIPCHK(h, tvl1_alloc(&h->tvl1, nx, ny));
+    }
+    int it = 0;
+    HIPCHK(h, tvl1_run(h->tvl1, I0, I1, u, static_cast<hipStream_t>(stream), iterations ? &it : nullptr));
+    if (iterations) *iterations = it;
+    return RVDD_OK;
+}
+
+int rvdd_ppipe(rvdd_t* h, const float* img, int32_t n, int32_t H, int32_t W, int64_t sn, int64_t sc, int64_t sy, int64_t sx,
+               int32_t bit_depth, double rgb_gain, double red_gain, double blue_gain, int32_t iso, uint8_t* out_u8,
+               float* out_f32, void* stream) {
+    if (h && n == 0) return RVDD_OK;
+    if (!h || !img || !out_u8 || n < 0 || H < 1 || W < 1) return fail(h, RVDD_ERR_ARG, "rvdd_ppipe: bad argument");
+    ENTER(h);
+    if (!(rgb_gain != 0.0) || !(red_gain != 0.0) || !(blue_gain != 0.0)) return fail(h, RVDD_ERR_ARG, "rvdd_ppipe: zero gain");
+    // fwd_ppipe.py:29: a float32 tensor of Python-double quotients
+    const float gains[3] = {(float)(1.0 / (red_gain * rgb_gain)), (float)(1.0 / rgb_gain), (float)(1.0 / (blue_gain * rgb_gain))};
+    HIPCHK(h, launch_ppipe(img, n, H, W, sn, sc, sy, sx, bit_depth, gains, iso, out_u8, out_f32, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, int32_t H, int32_t W, double* psnr,
+                      double* ssim, void* stream) {
+    if (!h || !a || !b || n < 1) return fail(h, RVDD_ERR_ARG, "rvdd_srgb_metrics: bad argument");
+    ENTER(h);
+    if (H < 7 || W < 7) return fail(h, RVDD_ERR_ARG, "rvdd_srgb_metrics: win_size exceeds image extent (images must be >= 7x7)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RC(ensure_scratch(h, srgb_metrics_workspace(n, H, W)));
+    HIPCHK(h, launch_srgb_metrics(a, b, n, H, W, h->scratch, s));
+    std::vector<unsigned long long> ssd(n);
+    std::vector<double> sums(n);
+    HIPCHK(h, hipMemcpyAsync(ssd.data(), h->scratch, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(sums.data(), reinterpret_cast<char*>(h->scratch) + (size_t)n * 8, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) {
+        // mean((a/255 - b/255)^2) = SSD / 255^2 / count; 10 log10(1 / 0) = inf as in numpy
+        if (psnr) psnr[i] = 10.0 * std::log10(1.0 / ((double)ssd[i] / (255.0 * 255.0) / ((double)H * W * 3)));
+        if (ssim) ssim[i] = sums[i] / (3.0 * (double)(H - 6) * (double)(W - 6));
+    }
+    return RVDD_OK;
+}
+
+int rvdd_tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny,
+                        int32_t* iterations, void* stream) {
+    return tvl1flow_batch(h, I0, I1, u, n, nx, ny, iterations, stream, h && h->opt.tvl1_async);
+}
+
+int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+                    float* packed, float* gray, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (dtype != RVDD_RAW_U16 && dtype != RVDD_RAW_F32) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: dtype must be 0 (u16) or 1 (f32), got %d", dtype);
+    if (layout != RVDD_RAW_MOSAIC && layout != RVDD_RAW_PACKED_HWC)
+        return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: layout must be 0 (mosaic) or 1 (packed HWC), got %d", layout);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: bit_depth must be 1..16, got %d", bit_depth);
+    if (n == 0) return RVDD_OK;
+    if (!frames || n < 0 || hh < 1 || ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: bad argument (frames, n >= 0, hh, ww >= 1)");
+    ENTER(h);
+    HIPCHK(h, launch_ingest_raw(frames, dtype, layout, n, hh, ww, bit_depth, packed, gray, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_gray_of_rgb(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t W, int32_t pattern, int32_t bit_depth, float* gray,
+                     void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
+        return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: bit_depth must be 1..16, got %d", bit_depth);
+    if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: H must be even and >= 2, got %d", H);
+    if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: W must be even and >= 2, got %d", W);
+    if (n == 0) return RVDD_OK;
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: n must be >= 0, got %d", n);
+    if (!rgb || !gray) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: rgb and gray are required");
+    ENTER(h);
+    HIPCHK(h, launch_gray_of_rgb(rgb, n, H / 2, W / 2, pattern, bit_depth, gray, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+// the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine
+static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int32_t W) {
+    if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);
+    if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "%s: W must be even and >= 2, got %d", fn, W);
+    if ((int64_t)H * W >= (1ll << 32)) return fail(h, RVDD_ERR_ARG, "%s: H * W must be below 2^32 (the draws count a frame's pixels in 32 bits), got %d x %d", fn, H, W);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    return RVDD_OK;
+}
+
+int rvdd_unprocess(rvdd_t* h, const uint8_t* srgb, int32_t n, int32_t H, int32_t W, double rgb_gain, double red_gain, double blue_gain,
+                   int32_t iso, int32_t pattern, const float* dither, const float* normal, uint64_t seed, int64_t frame0, float* lin_f32,
+                   uint16_t* lin_u16, float* gt_raw, float* noisy, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (iso != 3200 && iso != 12800) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: iso must be 3200 or 12800, got %d", iso);
+    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
+        return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    RC(unprocess_shape(h, "rvdd_unprocess", n, H, W));
+    if (n == 0) return RVDD_OK;
+    if (!srgb) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: srgb is required");
+    if (!(rgb_gain != 0.0) || !(red_gain != 0.0) || !(blue_gain != 0.0)) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: zero gain (rgb_gain, red_gain, blue_gain)");
+    ENTER(h);
+    // generate_raw_from_RGB.py:77: float32 tensors -- (1 / red_gain, 1, 1 / blue_gain) / rgb_gain, each quotient rounded to f32
+    const float rgb = (float)rgb_gain;
+    const float g[3] = {(1.0f / (float)red_gain) / rgb, 1.0f / rgb, (1.0f / (float)blue_gain) / rgb};
+    HIPCHK(h, launch_unprocess(srgb, n, H / 2, W / 2, g, iso, pattern, dither, normal, seed, frame0, lin_f32, lin_u16, gt_raw, noisy,
+                               static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_unprocess_draws(rvdd_t* h, uint64_t seed, int64_t frame0, int32_t n, int32_t H, int32_t W, float* dither, float* normal,
+                         void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    RC(unprocess_shape(h, "rvdd_unprocess_draws", n, H, W));
+    if (n == 0) return RVDD_OK;
+    ENTER(h);
+    HIPCHK(h, launch_unprocess_draws(seed, frame0, n, H / 2, W / 2, dither, normal, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+}  // extern "C"

@@ -655,7 +655,7 @@ __global__ __launch_bounds__(192) void warp48_kernel(const float* __restrict__ s
 // The 32 warped pixels of the workgroup change lanes through LDS (pixel pitch 52 floats: the 16 lanes of a ds_read_b128 group
 // on 16 distinct bank quads); waves 0 and 1 then project one 16-pixel group each on the F16 matrix pipe exactly as convnext.hip's
 // PROJ epilogue does: per-pixel power of two (the features have no a-priori bound), split into f16 halves, fc1's five-MFMA
-// pattern on the three 16-row blocks of 2^s W (frag: runtime_next.inc's half[1] fragments, 9 KiB, copied to LDS once per
+// pattern on the three 16-row blocks of 2^s W (frag: net_convnext.hip's half[1] fragments, 9 KiB, copied to LDS once per
 // workgroup), one fma back.  (The first form multiplied f32 on v_mfma_f32_16x16x4_f32: 72 per workgroup at 32 cycles each ON the
 // vector lanes the gather's FMAs need -- 1 247 us against warp48_kernel's 899.)
 typedef _Float16 wp_h8 __attribute__((ext_vector_type(8)));
@@ -1164,7 +1164,7 @@ hipError_t launch_amax_reduce(const float* map, int B, int64_t hw_c, unsigned* w
     return hipGetLastError();
 }
 
-// The border ring of the composed first layer (runtime.hip compose_pre_enc0).  The composition treats the preprocessing
+// The border ring of the composed first layer (net_convunet.hip compose_pre_enc0).  The composition treats the preprocessing
 // layer's output y as if it existed outside the image (b1 + partial windows of the zero-extended input); the reference pads it
 // with ZEROS (networks/unet.py:742-743, padding=1 on both convs).  For a border pixel p the composed sum therefore carries
 // sum over the taps d with q = p + d - 1 outside the image of W2[d] y~(q), y~(q) = b1 + sum over taps e with q + e - 1 inside of
@@ -1260,13 +1260,6 @@ hipError_t launch_conv1x1_out(const float* feat, const float* w3x48, const float
     const size_t n = (size_t)B * H * W;
     hipLaunchKernelGGL(conv1x1_out_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, feat, w3x48, b3, out_nchw,
                        out_nhwc4, B, H, W);
-    return hipGetLastError();
-}
-
-hipError_t launch_loss_reduce(const float* a, const float* b, int64_t n, double* partial, int nblk,
-                              double* result2, hipStream_t s) {
-    hipLaunchKernelGGL(loss_partial_kernel, dim3(nblk), dim3(256), 0, s, a, b, n, partial);
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, s, partial, nblk, result2);
     return hipGetLastError();
 }
 

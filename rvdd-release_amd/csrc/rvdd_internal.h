@@ -44,7 +44,7 @@ enum ConvEpi { EPI_NONE = 0, EPI_RELU = 1, EPI_POOL = 2, EPI_RELU_ADD2 = 3, EPI_
 
 struct ConvArgs {
     const float* in;      // NHWC [B][H][W][CIN]
-    const float* w;       // arranged [9][CIN/16][3][64 lanes][4] (see arrange_conv3x3 / arrange_wino3x3 in runtime.hip)
+    const float* w;       // arranged [9][CIN/16][3][64 lanes][4] (see arrange_conv3x3 / arrange_wino3x3 in net_convunet.hip)
     const float* bias;    // [48]   (ignored when acc_in != nullptr)
     const float* acc_in;  // NHWC48 [B][H][W] partial sums to start from, or nullptr
     const float* res1;    // EPI_RELU_ADD2: out = relu(conv) + res1 + res2
@@ -186,17 +186,17 @@ hipError_t launch_amax_reduce(const float* map, int B, int64_t hw_c, unsigned* w
 // cin = 16 or 48.  Returns hipGetLastError().  variant 1, 2: A/B forms of the plain 48 -> 48 ReLU layer (rvdd_debug_conv_bench only)
 hipError_t launch_conv3x3(const ConvArgs& a, int cin, int epi, hipStream_t s, int variant = 0);
 size_t conv3x3_weight_floats(int cin);
-// Winograd F(2x2,3x3) variant for 48 -> 48 layers; a.w = bank arranged by arrange_wino3x3 (runtime.hip)
+// Winograd F(2x2,3x3) variant for 48 -> 48 layers; a.w = bank arranged by arrange_wino3x3 (net_convunet.hip)
 hipError_t launch_wino3x3(const ConvArgs& a, int cin, int epi, hipStream_t s);   // cin: 48, or 16 = the zero-padded network input
 size_t wino3x3_weight_floats();
 // the same layers on the F16 matrix pipe with split f32 operands (conv3x3h.hip); a.w = the split bank arranged by
-// arrange_conv3x3h (runtime.hip), a.wscale its scale; cin 48 (every epilogue, with or without a.acc_in, with a.ups for
+// arrange_conv3x3h (net_convunet.hip), a.wscale its scale; cin 48 (every epilogue, with or without a.acc_in, with a.ups for
 // UpConv's fused upsample) or 16 (the zero-padded network input): every 3x3 conv of the convunet by default
 // cout_split = false: no launch takes the output-channel split of small launches (conv3x3h.hip MT = 1; option "cout_split" 0)
 hipError_t launch_conv3x3h(const ConvArgs& a, int cin, int epi, hipStream_t s, bool cout_split = true);
 size_t conv3x3h_weight_bytes(int cin);
 // preprocessing_layer composed with the first source of EncoderConvs[0][0]: one 5x5 conv of the 16-channel network input
-// (conv3x3h.hip HGeo KS = 5; runtime.hip compose_pre_enc0), and the fix of its border ring: part -= sum over the 3x3 taps d
+// (conv3x3h.hip HGeo KS = 5; net_convunet.hip compose_pre_enc0), and the fix of its border ring: part -= sum over the 3x3 taps d
 // whose pixel q = p + d - 1 lies OUTSIDE the image of W2[d] (b1 + sum over taps e inside the image of W1[e] x(q + e - 1))
 hipError_t launch_conv5x5h_c16(const ConvArgs& a, hipStream_t s);
 // ... over the first 8 channels only (at most 8 real channels, i.e. no future frame): 25 groups in 7 chunks instead of 50 in 13
@@ -230,7 +230,7 @@ hipError_t launch_netin(const float* raw_cur, float* green_scratch, const float*
                         int bayer);
 // amax words of that network input (block floating point of the split-f16 convs, below): an upper bound from the packed raw
 // frames it is made of (up to three, each nullable) and from `prev_words`, words that bound the previous output (nullable)
-// (zero_a / zero_b, nullable: word ranges the kernel also clears -- the next step's amax words, runtime.hip)
+// (zero_a / zero_b, nullable: word ranges the kernel also clears -- the next step's amax words, step.hip)
 hipError_t launch_netin_bound(const float* raw_a, const float* raw_b, const float* raw_c, int B, int h, int w, int64_t raw_bstride,
                               const unsigned* prev_words, unsigned* words, hipStream_t s, unsigned* zero_a = nullptr, size_t zero_na = 0,
                               unsigned* zero_b = nullptr, size_t zero_nb = 0, unsigned long long latch = ~0ull);
@@ -246,7 +246,7 @@ hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const
 hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W,
                          hipStream_t s, int64_t flow_bstride = 0);
 // the same, and a 48 -> 48 projection of every warped pixel: dst = W warp(src) + bias; frag / inv_e = the projection as a
-// NextProj's split-f16 fragments and scale (runtime_next.inc), applied per pixel in block floating point (prestage.hip)
+// NextProj's split-f16 fragments and scale (net_convnext.hip), applied per pixel in block floating point (prestage.hip)
 hipError_t launch_warp48_proj(const float* src, const float* flow_raw, float* dst, int B, int H, int W, const float* frag,
                               int inv_e, const float* bias, hipStream_t s, int64_t flow_bstride = 0);
 // generic NCHW warp with a full-resolution flow (util.flow_utils.warp).
@@ -271,11 +271,8 @@ hipError_t launch_nhwc_to_nchw(const float* in, float* out, int B, int C, int H,
 // final 1x1 conv 48->3: feat NHWC48 -> out NCHW [B][3][H][W] (+ NHWC4 copy for the next warp)
 hipError_t launch_conv1x1_out(const float* feat, const float* w3x48, const float* b3, float* out_nchw,
                               float* out_nhwc4, int B, int H, int W, hipStream_t s);
-// partial[2*nblk] doubles scratch; result2 device floats {sum|d|, sum d^2} as doubles -> host math
-hipError_t launch_loss_reduce(const float* a, const float* b, int64_t n, double* partial, int nblk,
-                              double* result2, hipStream_t s);
-// the same for `nslices` dense slices of n elements: partial[nslices][2*nblk], result2[nslices][2]; each slice's two sums are
-// bit for bit what launch_loss_reduce gives for it alone
+// {sum|d|, sum d^2} as doubles -> host math, for `nslices` dense slices of n elements: partial[nslices][2*nblk] doubles scratch,
+// result2[nslices][2]; each slice's two sums are bit for bit what a launch of that slice alone gives
 hipError_t launch_loss_reduce_batch(const float* a, const float* b, int nslices, int64_t n, double* partial, int nblk,
                                     double* result2, hipStream_t s);
 // rvdd_reset_slots' latch: zero the features (feat_per_seq floats per sequence) and the amax words of every set (nsets, layout
@@ -297,13 +294,13 @@ struct NextBlockW {          // device pointers, one ConvBlock (networks/new_une
     const float* dw_b;       // [48]
     const float* ln_w;       // [48]
     const float* ln_b;       // [48]
-    const float* fc1_w;      // arranged for MFMA, see runtime.hip
+    const float* fc1_w;      // arranged for MFMA, see net_convnext.hip
     const float* fc1_b;      // [192]
     const float* fc2_w;
     const float* fc2_b;      // [48]
     const float* ls;         // [48]
     // the fused kernel's split-f16 MLP (convnext.hip SPLIT): filter fragments of 2^s fc1 / 2^s' fc2 as f16 hi, lo halves
-    // (arranged in runtime_next.inc), the scales and their inverses; fc1_h null = the f32-MFMA form
+    // (arranged in net_convnext.hip), the scales and their inverses; fc1_h null = the f32-MFMA form
     const float* fc1_h;
     const float* fc2_h;
     float fc1_scale, fc1_inv, fc2_scale, fc2_inv;
@@ -315,7 +312,7 @@ struct NextBlockW {          // device pointers, one ConvBlock (networks/new_une
 // A 48 -> 48 projection applied to a fused block's OUTPUT in its epilogue (convblock_pipe_kernel PROJ): one half of the
 // 96 -> 48 projection behind a concat, proj(cat(a, b)) = Wa a + Wb b + bias (networks/new_unet.py:85-88, 321-329)
 struct NextProj {
-    const float* frag;       // split-f16 fragments of 2^s W [48][48] (runtime_next.inc arrange_proj_half), 9 KiB
+    const float* frag;       // split-f16 fragments of 2^s W [48][48] (net_convnext.hip finalize_convnext), 9 KiB
     const float* bias;       // [48] or null; used when `add` is null
     const float* add;        // NHWC48 map of the block's output size added to the projection (the other half, with the bias), or null
     int inv_e;               // -s: added to a float's exponent field it multiplies by 2^-s

@@ -1,0 +1,101 @@
+// rvdd_video_push: raw frames in, denoised frames out -- ingest, flows and the step of every slot that has its frames.
+#include "runtime_internal.h"
+
+extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t bit_depth, const uint8_t* ctl, float* out_rgb,
+                    uint8_t* valid, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (dtype != RVDD_RAW_U16 && dtype != RVDD_RAW_F32) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: dtype must be 0 (u16) or 1 (f32), got %d", dtype);
+    if (layout != RVDD_RAW_MOSAIC && layout != RVDD_RAW_PACKED_HWC)
+        return fail(h, RVDD_ERR_ARG, "rvdd_video_push: layout must be 0 (mosaic) or 1 (packed HWC), got %d", layout);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: bit_depth must be 1..16, got %d", bit_depth);
+    if (!frames || !out_rgb || !valid) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: frames, out_rgb and valid are required");
+    if (!h->finalized) return fail(h, RVDD_ERR_STATE, "rvdd_video_push: weights not finalized");
+    const int B = h->cfg.batch, hh = h->cfg.height / 2, ww = h->cfg.width / 2, fut = h->cfg.future;
+    const size_t hw = (size_t)hh * ww;
+    auto& st = h->st;
+    for (int b = 0; b < B; ++b)
+        if (ctl && ctl[b] > RVDD_PUSH_IDLE) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: ctl[%d] = %d is not 0 (NEXT), 1 (FIRST) or 2 (IDLE)", b, ctl[b]);
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!st.packed) {      // the first push
+        if (B > 64) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: needs batch <= 64, as the partial reset marks of rvdd_reset_slots do (batch is %d)", B);
+        if (!h->opt.no_warp && (hh < 16 || ww < 16 || !tvl1_size_ok(ww, hh)))
+            return fail(h, RVDD_ERR_ARG, "rvdd_video_push: raw frames of %d x %d cells are not a size rvdd_tvl1flow_batch accepts (at least 16 x 16 and not too "
+                        "skinny for the flow's pyramid); only option no_warp streams this size", ww, hh);
+        const int depth = 2 + fut, nd = 1 + fut;
+        st.count.assign((size_t)B, 0);
+        st.was_idle.assign((size_t)B, 0);
+        st.dgray_ok.assign((size_t)B, 0);
+        float *pk = nullptr, *gr = nullptr;
+        RC(dmalloc(h, reinterpret_cast<void**>(&gr), (size_t)depth * B * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&st.I0), (size_t)nd * B * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&st.I1), (size_t)nd * B * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&st.u), (size_t)nd * B * 2 * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&st.flows), (size_t)nd * B * 2 * hw * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&pk), (size_t)depth * B * 4 * hw * sizeof(float)));
+        st.gray = gr;
+        st.depth = depth;
+        st.pushes = 0;
+        st.packed = pk;      // last: the mark of a complete allocation
+    }
+    // option "stream_flow_from_denoised": the gray planes of the outputs, allocated by the first push that has it on
+    const bool from_den = h->opt.stream_flow_from_denoised && !h->opt.no_warp;
+    if (from_den && !st.dgray) RC(dmalloc(h, reinterpret_cast<void**>(&st.dgray), (size_t)B * hw * sizeof(float)));
+    // the whole ctl is judged before anything changes
+    for (int b = 0; b < B; ++b)
+        if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
+            return st.was_idle[(size_t)b]
+                       ? fail(h, RVDD_ERR_STATE, "rvdd_video_push: slot %d was idle on the last push: it goes on with FIRST or IDLE, not NEXT", b)
+                       : fail(h, RVDD_ERR_STATE, "rvdd_video_push: slot %d has no video yet: its first frame is pushed with FIRST", b);
+    // ingest: one launch per run of slots that get a frame
+    const int pos = (int)(st.pushes % (uint64_t)st.depth);
+    const size_t esz = dtype == RVDD_RAW_U16 ? 2 : 4;
+    RC(for_each_run(B, [&](int b) { return !(ctl && ctl[b] == RVDD_PUSH_IDLE); }, [&](int b, int e) -> int {
+        HIPCHK(h, launch_ingest_raw(static_cast<const char*>(frames) + (size_t)b * 4 * hw * esz, dtype, layout, e - b, hh, ww, bit_depth,
+                                    st.packed + ((size_t)pos * B + b) * 4 * hw, st.gray + ((size_t)pos * B + b) * hw, s));
+        return RVDD_OK;
+    }));
+    std::vector<int> ready, fresh;
+    uint64_t den_slots = 0;      // ready slots whose previous push gave an output of the same video, its gray plane in dgray
+    for (int b = 0; b < B; ++b) {
+        const int c = ctl ? ctl[b] : RVDD_PUSH_NEXT;
+        int& n = st.count[(size_t)b];
+        n = c == RVDD_PUSH_IDLE ? 0 : c == RVDD_PUSH_FIRST ? 1 : (n < (1 << 30) ? n + 1 : n);
+        st.was_idle[(size_t)b] = c == RVDD_PUSH_IDLE;
+        valid[b] = n >= st.depth;
+        if (n >= st.depth) ready.push_back(b);
+        if (n == st.depth || (h->opt.stream_reset_each && n >= st.depth)) fresh.push_back(b);
+        if (from_den && n > st.depth && st.dgray_ok[(size_t)b]) den_slots |= 1ull << b;
+        st.dgray_ok[(size_t)b] = 0;
+    }
+    st.pushes++;
+    if (ready.empty()) return RVDD_OK;
+    const int nready = (int)ready.size();
+    // ring positions: with a future frame the centre is the frame of the push before
+    const int pc = (pos + st.depth - fut) % st.depth, pp = (pc + st.depth - 1) % st.depth;
+    auto packed_at = [&](int p) { return st.packed + (size_t)p * B * 4 * hw; };
+    auto gray_at = [&](int p) { return st.gray + (size_t)p * B * hw; };
+    const float *flow_prev = nullptr, *flow_next = nullptr;
+    if (!h->opt.no_warp) {
+        HIPCHK(h, launch_stream_gather(gray_at(pc), gray_at(pp), fut ? gray_at(pos) : nullptr, st.dgray, den_slots, st.I0, st.I1, ready.data(), nready, B,
+                                       (int64_t)hw, s));
+        float* u = nready == B ? st.flows : st.u;      // every slot ready: the batch writes the step's flows itself
+        RC(tvl1flow_batch(h, st.I0, st.I1, u, nready * (1 + fut), ww, hh, nullptr, stream, true));
+        if (nready != B) HIPCHK(h, launch_stream_scatter(st.u, st.flows, ready.data(), nready, 1 + fut, B, (int64_t)hw, s));
+        flow_prev = st.flows;
+        flow_next = fut ? st.flows + (size_t)B * 2 * hw : nullptr;
+    }
+    if (!fresh.empty()) {
+        std::vector<uint8_t> mask((size_t)B, 0);
+        for (int b : fresh) mask[(size_t)b] = 1;
+        RC(rvdd_reset_slots(h, mask.data()));
+    }
+    RC(rvdd_step_strided(h, packed_at(pp), packed_at(pc), fut ? packed_at(pos) : nullptr, flow_prev, flow_next, 0, 0, out_rgb, stream));
+    if (from_den) {
+        // the plane is taken from the output (with "prev_noisy_frame" lastden holds the noisy demosaic) inside the push that wrote it:
+        // the caller may overwrite out_rgb before the next one
+        HIPCHK(h, launch_gray_of_rgb(out_rgb, B, hh, ww, h->opt.bayer, bit_depth, st.dgray, s));
+        for (int b : ready) st.dgray_ok[(size_t)b] = 1;
+    }
+    return RVDD_OK;
+}

@@ -1021,7 +1021,7 @@ dim3 grid2(int nx, int ny) { return dim3((nx + 255) / 256, ny); }
 
 }  // namespace
 
-// Workspace: every buffer the pyramid needs for one (nx, ny), per lane; owned by the caller (runtime.hip).
+// Workspace: every buffer the pyramid needs for one (nx, ny), per lane; owned by the caller (the handle: ops.hip).
 struct Tvl1LaneBufs {
     std::vector<Scale> sc;
     IterBufs it{};

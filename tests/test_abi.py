@@ -30,8 +30,11 @@ def test_library_exports_every_declared_symbol():
     for name in declared_functions():
         assert hasattr(lib, name), name
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = set(re.findall(r"\sT\s+(rvdd_[a-z0-9_]+)", out))
-    assert exported == set(declared_functions())
+    # every defined dynamic symbol, not only the rvdd_ ones: launchers, kernel handles, template instantiations and the handle's
+    # constructor stay inside the library (csrc/rvdd.map)
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    assert exported == set(declared_functions()), sorted(exported ^ set(declared_functions()))
+    assert set(re.findall(r"\sT\s+(rvdd_[a-z0-9_]+)", out)) == exported
     assert b"gfx950" in lib.rvdd_version()
 
 

@@ -1,4 +1,4 @@
-"""rvdd_set_option: every option is a field of the handle it is set on (one table in runtime.hip), the measurement hook
+"""rvdd_set_option: every option is a field of the handle it is set on (one table in handle.hip), the measurement hook
 leaves the handle's conv selection as it found it, and every documented name is known with its range."""
 import os
 import re

@@ -221,6 +221,16 @@ def test_psnr_l1_batch_equals_single(size):
     got = rt.psnr_l1_batch(den, gt)
     want = [rt.psnr_l1(den[b:b + 1], gt[b:b + 1]) for b in range(B)]
     assert got == want
+    # both calls share one path in the library: anchor them to the CPU.  d in float32 as the kernel forms it, both sums in float64;
+    # the library accumulates in double and rounds its two results to float32 once (6e-8 relative), so 1e-6 has an order of
+    # magnitude to spare and still catches a wrong count, slice offset or partition
+    d = (den - gt).cpu().reshape(B, -1)
+    n = d.shape[1]
+    for b in range(B):
+        d64 = d[b].double()
+        ref = (100.0 * float(d64.abs().sum()) / n, 10.0 * math.log10(4.0 / (float((d64 * d64).sum()) / n)))
+        for g, r in zip(got[b], ref):
+            assert abs(g - r) <= 1e-6 * abs(r), (b, got[b], ref)
     assert rt.psnr_l1_batch(den[:0], gt[:0]) == []
     rt.close()
 

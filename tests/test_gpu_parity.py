@@ -665,7 +665,7 @@ def test_4k_frame_next_batch_of_two():
 
 def test_all_twenty_checkpoints_load_strictly_and_run():
     """Every checkpoint of the reference's trained-nets/ passes the runtime's strict key/shape table
-    (runtime.hip expected_keys) under the architecture its name states and produces a finite frame."""
+    (handle.hip expected_keys) under the architecture its name states and produces a finite frame."""
     import glob
     from rvdd_release_amd import synth
     from rvdd_release_amd.runtime import RvddRuntime

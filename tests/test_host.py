@@ -96,7 +96,7 @@ def test_load_networks_reads_pth_and_safetensors(tmp_path):
 
 
 def test_every_shipped_checkpoint_matches_its_key_table():
-    """The key/shape table the runtime enforces (runtime.hip expected_keys) is the
+    """The key/shape table the runtime enforces (handle.hip expected_keys) is the
     reference's: count tensors and parameters."""
     fam = {"convunet": (48, 522243), "convunet-future": (48, 523539), "convunet+feat": (50, 563763),
            "convunet+feat-future": (50, 565059), "ConvNeXtUnet": (226, 523635), "ConvNeXtUnet+feat-future": (237, 549651)}

@@ -10,9 +10,11 @@ if [ "$1" = build ]; then
   mkdir -p tools/scratch
   python3 tools/convblock_xp_patch.py tools/scratch/convnext_xp.hip > /dev/null || exit 1
   make -C $C > /dev/null || exit 1
+  # the library's objects (csrc/Makefile print-objs) with convnext.o replaced by the variant
+  OBJS=$(for o in $(make -s -C $C print-objs); do [ $o = convnext.o ] || echo $C/$o; done)
   for xp in $2; do
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-value -DRVDD_XP=$xp -I$C -c tools/scratch/convnext_xp.hip -o tools/scratch/convnext_xp$xp.o || exit 1
-    hipcc --offload-arch=gfx950 -shared -fPIC $C/conv3x3.o $C/conv3x3h.o $C/wino3x3.o tools/scratch/convnext_xp$xp.o $C/prestage.o $C/tvl1.o $C/srgb.o $C/runtime.o \
+    hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--version-script=$C/rvdd.map $OBJS tools/scratch/convnext_xp$xp.o \
           -o rvdd-release_amd/librvdd_hip_xp$xp.so || exit 1
     echo built xp$xp
   done

@@ -9,9 +9,11 @@ pads=${@:-0 1 2 3 5 8 16}
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
 if [ "$mode" = build ]; then
   mkdir -p tools/scratch
+  # the library's objects (csrc/Makefile print-objs) with conv3x3h.o replaced by the variant
+  objs=$(make -s -C rvdd-release_amd/csrc print-objs | tr ' ' '\n' | grep -vx conv3x3h.o | tr '\n' ' ')
   for k in $pads; do
     (cd rvdd-release_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -DRVDD_UPS_PAD=$k -c conv3x3h.hip -o ../../tools/scratch/conv3x3h_pad$k.o &&
-      hipcc --offload-arch=gfx950 -shared -fPIC conv3x3.o ../../tools/scratch/conv3x3h_pad$k.o wino3x3.o convnext.o prestage.o tvl1.o srgb.o runtime.o -o ../librvdd_hip_pad$k.so) && echo "built pad $k"
+      hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--version-script=rvdd.map $objs ../../tools/scratch/conv3x3h_pad$k.o -o ../librvdd_hip_pad$k.so) && echo "built pad $k"
   done
 else
   cp rvdd-release_amd/librvdd_hip.so /tmp/keep_layout.so
