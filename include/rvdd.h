@@ -276,6 +276,41 @@ int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
 int rvdd_gray_of_rgb(rvdd_t* h, const float* rgb /* [n,3,H,W] in [-1,1] */, int32_t n, int32_t H, int32_t W,
                      int32_t pattern /* enum rvdd_bayer */, int32_t bit_depth, float* gray /* [n,H/2,W/2] */, void* stream);
 
+enum rvdd_out_layout { RVDD_OUT_RGB_HWC = 0,     /* [n,H,W,3]                                   */
+                       RVDD_OUT_MOSAIC = 1,      /* [n,H,W]: one plane, as a sensor writes it    */
+                       RVDD_OUT_PACKED_HWC = 2 };/* [n,H/2,W/2,4]: the reference dataset's TIFF  */
+
+/* Denoised frames out, in the containers a raw pipeline reads: the inverse direction of rvdd_ingest_raw.  With
+ * top = (float)(2^bit_depth - 1), every operation rounded to f32 on its own,
+ *   dn  = ((v + 1.0f) * 0.5f) * top                            (the dn_k of rvdd_gray_of_rgb)
+ *   out = dn                                                   RVDD_RAW_F32: neither rounded nor clamped
+ *   out = (uint16) min(max(rint(dn), 0), top)                  RVDD_RAW_U16: rint rounds half to even; NaN -> 0, -inf -> 0, +inf -> top
+ * of the sample
+ *   RVDD_OUT_RGB_HWC     out[i][y][x][c]                      = rgb[i][c][y][x]
+ *   RVDD_OUT_PACKED_HWC  out[i][y][x][k]                      = rgb[i][col(k)][2y + (k >> 1)][2x + (k & 1)]
+ *   RVDD_OUT_MOSAIC      out[i][2y + (k >> 1)][2x + (k & 1)]  = the same sample
+ * where col(k) is the colour `pattern` has at CFA position k (HamiltonAdam(pattern).remosaick, as rvdd_gray_of_rgb).
+ * What that gives:
+ *   - RGB_HWC, F32, bit_depth 8 is bit for bit util.tensor2im of the frame -- (x.transpose(1,2,0) + 1) / 2.0 * 255.0 in f32 -- the
+ *     image validate / denoise write as <frame>_denoised.tif;
+ *   - MOSAIC / PACKED_HWC, F32: (((c0 + c1) + c2) + c3) * 0.25f of a cell's four outputs is bit for bit rvdd_gray_of_rgb for the
+ *     same pattern and bit_depth;
+ *   - the round trip: for uint16 frames with values in 0 .. 2^bit_depth - 1, rvdd_ingest_raw -> rvdd_demosaic_ha_bayer(pattern) ->
+ *     rvdd_egress(U16, the same layout, pattern and bit_depth) returns the frames exactly (the demosaic keeps a site's own
+ *     sample, and rint(dn_of(packed(dn))) == dn for every dn of every bit_depth: the worst deviation is 9.8e-4 DN, at 16 bits).
+ * No black level or white balance is applied: ingest leaves both in the data, and so does this.
+ * layout outside 0..2, dtype outside 0..1, bit_depth outside 1..16, H or W < 1, n < 0, NULL rgb / out with n > 0, a launch of
+ * more than 2^31 - 1 blocks, and for the two mosaic layouts pattern outside 0..3 or an odd H or W: RVDD_ERR_ARG (the message
+ * names the argument) and nothing is launched.  RGB_HWC takes any H, W and ignores pattern.  n = 0 does nothing.
+ * Asynchronous and stream-ordered; nothing is read back: after rvdd_video_push, call it on the push's stream.
+ * The wide form (every access 16 bytes) needs `rgb` and `out` 16-byte aligned and, for the mosaic layouts, (W/2) % 4 == 0 (a
+ * thread owns four cells of a cell row); for RGB_HWC, H * W % 8 == 0 (U16) or H * W % 4 == 0 (F32): a thread owns that many
+ * consecutive pixels and stores 3 x 16 bytes.  Every other shape takes the one-cell / one-pixel form; same bits either way. */
+int rvdd_egress(rvdd_t* h, const float* rgb /* [n,3,H,W] in [-1,1] */, int32_t n, int32_t H, int32_t W,
+                int32_t layout /* enum rvdd_out_layout */, int32_t dtype /* enum rvdd_raw_dtype */,
+                int32_t bit_depth, int32_t pattern /* enum rvdd_bayer; ignored for RGB_HWC */,
+                void* out, void* stream);
+
 enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
 
 /* The stream: one call hands every batch slot its next sensor frame (`frames`: cfg.batch frames of H/2 x W/2 cells, one

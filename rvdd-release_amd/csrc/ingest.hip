@@ -1,6 +1,6 @@
 // Sensor frames -> the inputs of a frame-step (packed raw in [-1, 1]) and of TV-L1 (gray plane in DN), the same gray plane of
-// an output frame's re-mosaic (rvdd_gray_of_rgb), and the two small
-// copy kernels rvdd_video_push composes its flow batch with.  Compiled -ffp-contract=off: every operation below is rounded
+// an output frame's re-mosaic (rvdd_gray_of_rgb), the way back -- an output frame as sensor frames (rvdd_egress) -- and the two
+// small copy kernels rvdd_video_push composes its flow batch with.  Compiled -ffp-contract=off: every operation below is rounded
 // to f32 on its own, which is what makes the outputs the bits of the reference's loader (library.py load_image + the
 // dataset's transform) and of library._gray on integer-valued frames.
 //
@@ -177,6 +177,140 @@ __global__ void __launch_bounds__(256) gray_of_rgb_kernel(const float* __restric
     }
 }
 
+// ---- rvdd_egress: a denoised frame in the containers a sensor pipeline reads ----------------------------------------------
+// The inverse direction of ingest: dn = dn_of(v), written as it is (f32) or rounded half-to-even and clamped to 0 .. top (u16;
+// the comparisons send NaN and -inf to 0, +inf to top), as interleaved RGB [n][H][W][3] (LAYOUT 0), as the re-mosaic in one
+// plane [n][H][W] (1) or packed [n][H/2][W/2][4] (2).  Pure streaming: 12 B read per pixel for RGB, 4 B used (8 B fetched: the
+// other half of every 16-B vector is another colour's site) for the mosaic layouts.  The wide form makes every access 16 B:
+// RGB gives a thread 8 (u16) / 4 (f32) consecutive pixels of an image -- the planes and the interleaved output are both flat
+// in the pixel index, so rows do not matter -- and its store is 3 x 16 B; the mosaic layouts give it four cells of a cell row,
+// loaded as gray_of_rgb_kernel<true> loads them, and store one (u16) / two (f32) vectors per sensor row, twice that per packed
+// run.  Both forms compute every sample with the same operations: same bits.
+template <typename T>
+__device__ __forceinline__ T out_of(float dn, float top) {
+    if constexpr (sizeof(T) == 4) {
+        return dn;
+    } else {
+        float r = rintf(dn);
+        r = r > 0.0f ? r : 0.0f;
+        r = r < top ? r : top;
+        return (unsigned short)r;
+    }
+}
+
+// N consecutive outputs as N * sizeof(T) / 16 vectors of 16 B (dst 16-B aligned)
+template <typename T, int N>
+__device__ __forceinline__ void store_run(T* __restrict__ dst, const float (&dn)[N], float top) {
+    constexpr int PER = 16 / sizeof(T);
+    typedef T vec_t __attribute__((ext_vector_type(PER)));
+#pragma unroll
+    for (int j = 0; j < N / PER; ++j) {
+        vec_t v;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) v[i] = out_of<T>(dn[j * PER + i], top);
+        *reinterpret_cast<vec_t*>(dst + j * PER) = v;
+    }
+}
+
+template <int LAYOUT, typename T, bool WIDE>
+__global__ void __launch_bounds__(256) egress_kernel(const float* __restrict__ rgb, T* __restrict__ out, int n, int H, int W, int cols,
+                                                     float top) {
+    const int64_t HW = (int64_t)H * W;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (LAYOUT == 0) {
+        constexpr int P = WIDE ? 16 / (int)sizeof(T) : 1;      // pixels per thread
+        const int64_t q = HW / P;
+        if (t >= (int64_t)n * q) return;
+        const int64_t img = t / q, p = (t % q) * P;
+        float dn[3 * P];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* src = rgb + (img * 3 + c) * HW + p;
+            if constexpr (WIDE) {
+#pragma unroll
+                for (int j = 0; j < P / 4; ++j) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * j);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) dn[(4 * j + i) * 3 + c] = dn_of(v[i], top);
+                }
+            } else {
+                dn[c] = dn_of(src[0], top);
+            }
+        }
+        T* dst = out + (img * HW + p) * 3;
+        if constexpr (WIDE) {
+            store_run<T, 3 * P>(dst, dn, top);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dst[c] = out_of<T>(dn[c], top);
+        }
+    } else {
+        constexpr int NC = WIDE ? 4 : 1;                 // cells per thread
+        const int hh = H >> 1, ww = W >> 1, wq = ww / NC;
+        if (t >= (int64_t)n * hh * wq) return;
+        const int x = NC * (int)(t % wq);
+        const int64_t row = t / wq;                      // img * hh + y
+        const int y = (int)(row % hh);
+        const int64_t img = row / hh;
+        float c[NC][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float* p = rgb + (img * 3 + ((cols >> (2 * k)) & 3)) * HW + (2 * (int64_t)y + (k >> 1)) * W + 2 * x + (k & 1);
+            if constexpr (WIDE) {
+                const float* a = p - (k & 1);            // the 16-B aligned run of eight pixels; position k takes its even / odd ones
+                const f32x4 v0 = *reinterpret_cast<const f32x4*>(a), v1 = *reinterpret_cast<const f32x4*>(a + 4);
+                c[0][k] = dn_of(v0[k & 1], top); c[1][k] = dn_of(v0[2 + (k & 1)], top);
+                c[2][k] = dn_of(v1[k & 1], top); c[3][k] = dn_of(v1[2 + (k & 1)], top);
+            } else {
+                c[0][k] = dn_of(p[0], top);
+            }
+        }
+        if constexpr (LAYOUT == 1) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                float run[2 * NC];                       // sensor row 2y + r, sites 2x .. 2x + 2 NC - 1
+#pragma unroll
+                for (int i = 0; i < NC; ++i) { run[2 * i] = c[i][2 * r]; run[2 * i + 1] = c[i][2 * r + 1]; }
+                T* dst = out + (img * H + 2 * (int64_t)y + r) * W + 2 * x;
+                if constexpr (WIDE) {
+                    store_run<T, 2 * NC>(dst, run, top);
+                } else {
+                    dst[0] = out_of<T>(run[0], top); dst[1] = out_of<T>(run[1], top);
+                }
+            }
+        } else {
+            float run[4 * NC];
+#pragma unroll
+            for (int i = 0; i < NC; ++i)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) run[4 * i + k] = c[i][k];
+            T* dst = out + ((img * hh + y) * (int64_t)ww + x) * 4;
+            if constexpr (WIDE) {
+                store_run<T, 4 * NC>(dst, run, top);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) dst[k] = out_of<T>(run[k], top);
+            }
+        }
+    }
+}
+
+template <int LAYOUT, typename T>
+hipError_t launch_egress_t(const float* rgb, int n, int H, int W, int cols, float top, T* out, bool wide, int64_t blocks, hipStream_t s) {
+    if (wide)
+        hipLaunchKernelGGL((egress_kernel<LAYOUT, T, true>), dim3((unsigned)blocks), dim3(256), 0, s, rgb, out, n, H, W, cols, top);
+    else
+        hipLaunchKernelGGL((egress_kernel<LAYOUT, T, false>), dim3((unsigned)blocks), dim3(256), 0, s, rgb, out, n, H, W, cols, top);
+    return hipGetLastError();
+}
+
+template <int LAYOUT>
+hipError_t launch_egress_l(const float* rgb, int n, int H, int W, int cols, float top, int dtype, void* out, bool wide, int64_t blocks,
+                           hipStream_t s) {
+    return dtype == 0 ? launch_egress_t<LAYOUT>(rgb, n, H, W, cols, top, static_cast<unsigned short*>(out), wide, blocks, s)
+                      : launch_egress_t<LAYOUT>(rgb, n, H, W, cols, top, static_cast<float*>(out), wide, blocks, s);
+}
+
 // ---- rvdd_video_push: the flow batch's operands and results ------------------------------------------------------------
 // The ready slots of a push, one byte each (B <= 64 on a partial set; the full set needs no list)
 struct SlotList {
@@ -238,12 +372,8 @@ hipError_t launch_ingest_raw(const void* frames, int dtype, int layout, int n, i
 
 hipError_t launch_gray_of_rgb(const float* rgb, int n, int hh, int ww, int bayer, int bit_depth, float* gray, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    // RGB plane of each GBRG site -- G(e,e), B(e,o), R(o,e), G(o,o) -- and the phase (py << 1) | px of the pattern: CFA position k
-    // of the pattern is the GBRG site k ^ phase (prestage.hip's bayer_phase)
-    constexpr int gbrg[4] = {1, 2, 0, 1}, phase[4] = {0, 3, 2, 1};
     if (bayer < 0 || bayer > 3) return hipErrorInvalidValue;
-    int cols = 0;
-    for (int k = 0; k < 4; ++k) cols |= gbrg[k ^ phase[bayer]] << (2 * k);
+    const int cols = bayer_cols(bayer);
     const float top = (float)((1u << bit_depth) - 1u);
     const uintptr_t al = reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(gray);
     const bool vec = (ww & 3) == 0 && (al & 15) == 0;
@@ -255,6 +385,37 @@ hipError_t launch_gray_of_rgb(const float* rgb, int n, int hh, int ww, int bayer
     else
         hipLaunchKernelGGL(gray_of_rgb_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, rgb, gray, n, hh, ww, cols, top);
     return hipGetLastError();
+}
+
+int64_t egress_blocks(const float* rgb, int n, int H, int W, int layout, int dtype, const void* out, bool* wide) {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(out);
+    const int64_t hw = (int64_t)H * W;
+    int64_t per;                                         // threads per image
+    if (layout == 0) {
+        const int P = dtype == 0 ? 8 : 4;
+        *wide = hw % P == 0 && (al & 15) == 0;
+        per = *wide ? hw / P : hw;
+    } else {
+        *wide = ((W >> 1) & 3) == 0 && (al & 15) == 0;
+        per = (int64_t)(H >> 1) * (*wide ? W >> 3 : W >> 1);
+    }
+    constexpr int64_t most = 0x7fffffffll * 256;         // threads of the largest grid
+    if (per > most || n > most / per) return -1;
+    return (n * per + 255) / 256;
+}
+
+hipError_t launch_egress(const float* rgb, int n, int H, int W, int layout, int dtype, int bit_depth, int bayer, void* out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (layout < 0 || layout > 2 || dtype < 0 || dtype > 1 || H < 1 || W < 1) return hipErrorInvalidValue;
+    if (layout != 0 && (bayer < 0 || bayer > 3 || ((H | W) & 1))) return hipErrorInvalidValue;
+    bool wide;
+    const int64_t blocks = egress_blocks(rgb, n, H, W, layout, dtype, out, &wide);
+    if (blocks < 0) return hipErrorInvalidValue;
+    const int cols = layout == 0 ? 0 : bayer_cols(bayer);
+    const float top = (float)((1u << bit_depth) - 1u);
+    return layout == 0   ? launch_egress_l<0>(rgb, n, H, W, cols, top, dtype, out, wide, blocks, s)
+           : layout == 1 ? launch_egress_l<1>(rgb, n, H, W, cols, top, dtype, out, wide, blocks, s)
+                         : launch_egress_l<2>(rgb, n, H, W, cols, top, dtype, out, wide, blocks, s);
 }
 
 // planes of the handle's own buffers (hipMalloc alignment); slots: the ready slots in order (ignored when nready == B)

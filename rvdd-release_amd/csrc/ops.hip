@@ -182,6 +182,29 @@ int rvdd_gray_of_rgb(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t 
     return RVDD_OK;
 }
 
+int rvdd_egress(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t dtype, int32_t bit_depth,
+                int32_t pattern, void* out, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (layout < RVDD_OUT_RGB_HWC || layout > RVDD_OUT_PACKED_HWC)
+        return fail(h, RVDD_ERR_ARG, "rvdd_egress: layout must be 0 (RGB HWC), 1 (mosaic) or 2 (packed HWC), got %d", layout);
+    if (dtype != RVDD_RAW_U16 && dtype != RVDD_RAW_F32) return fail(h, RVDD_ERR_ARG, "rvdd_egress: dtype must be 0 (u16) or 1 (f32), got %d", dtype);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_egress: bit_depth must be 1..16, got %d", bit_depth);
+    const bool cfa = layout != RVDD_OUT_RGB_HWC;
+    if (cfa && (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR))
+        return fail(h, RVDD_ERR_ARG, "rvdd_egress: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    if (H < 1 || (cfa && (H & 1))) return fail(h, RVDD_ERR_ARG, "rvdd_egress: H must be >= 1, and even for the mosaic layouts, got %d", H);
+    if (W < 1 || (cfa && (W & 1))) return fail(h, RVDD_ERR_ARG, "rvdd_egress: W must be >= 1, and even for the mosaic layouts, got %d", W);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_egress: n must be >= 0, got %d", n);
+    if (n == 0) return RVDD_OK;
+    if (!rgb || !out) return fail(h, RVDD_ERR_ARG, "rvdd_egress: rgb and out are required");
+    bool wide;
+    if (egress_blocks(rgb, n, H, W, layout, dtype, out, &wide) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_egress: n * H * W = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, H, W);
+    ENTER(h);
+    HIPCHK(h, launch_egress(rgb, n, H, W, layout, dtype, bit_depth, pattern, out, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 // the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine
 static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int32_t W) {
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);

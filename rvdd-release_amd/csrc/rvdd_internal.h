@@ -350,6 +350,21 @@ hipError_t launch_ingest_raw(const void* frames, int dtype, int layout, int n, i
 // rgb [n][3][2hh][2ww] in [-1,1] -> gray [n][hh][ww] in DN of its re-mosaic in pattern `bayer` (enum rvdd_bayer): per cell
 // (((dn0 + dn1) + dn2) + dn3) * 0.25 with dn_k = ((v_k + 1) * 0.5) * (2^bit_depth - 1), v_k the pattern's colour at CFA position k
 hipError_t launch_gray_of_rgb(const float* rgb, int n, int hh, int ww, int bayer, int bit_depth, float* gray, hipStream_t s);
+// The re-mosaic's colour table, the one copy of it: the RGB plane of each GBRG site -- G(e,e), B(e,o), R(o,e), G(o,o) -- and the
+// phase (py << 1) | px of the pattern; CFA position k of pattern `bayer` (enum rvdd_bayer, 0..3) is the GBRG site k ^ phase
+// (prestage.hip's bayer_phase).  -> the four plane indices, two bits each: col(k) = (cols >> 2k) & 3.
+inline int bayer_cols(int bayer) {
+    constexpr int gbrg[4] = {1, 2, 0, 1}, phase[4] = {0, 3, 2, 1};
+    int cols = 0;
+    for (int k = 0; k < 4; ++k) cols |= gbrg[k ^ phase[bayer]] << (2 * k);
+    return cols;
+}
+// a denoised frame in the containers a sensor pipeline reads (rvdd_egress).  rgb [n][3][H][W] in [-1,1]; layout enum
+// rvdd_out_layout (0 [n][H][W][3], 1 the mosaic [n][H][W], 2 packed [n][H/2][W/2][4]; H, W even for 1 and 2), dtype 0 = u16
+// (rint, clamped to 0 .. 2^bit_depth - 1) / 1 = f32 (DN as computed), bayer ignored for layout 0
+hipError_t launch_egress(const float* rgb, int n, int H, int W, int layout, int dtype, int bit_depth, int bayer, void* out, hipStream_t s);
+// the grid of that launch (n, H, W >= 1) and whether it takes the wide form; -1 = more than 2^31 - 1 blocks
+int64_t egress_blocks(const float* rgb, int n, int H, int W, int layout, int dtype, const void* out, bool* wide);
 // the flow batch of a push: I0 / I1 [npairs][hw] from the gray planes [B][hw] of the ring positions of the centre, previous and
 // next (nullable: no future frame) frames -- pair q < nready = (centre, previous) of slots[q], pair nready + q = (centre, next).
 // A slot whose bit of from_den is set has its (centre, previous) pair matched against dgray [B][hw] instead of gray_p (B <= 64).

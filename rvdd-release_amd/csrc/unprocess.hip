@@ -297,13 +297,11 @@ hipError_t launch_unprocess(const uint8_t* srgb, int n, int hh, int ww, const fl
                             hipStream_t s) {
     if (n <= 0 || (!lin_f32 && !lin_u16 && !gt_raw && !noisy)) return hipSuccess;
     if (bayer < 0 || bayer > 3 || (iso != 3200 && iso != 12800)) return hipErrorInvalidValue;
-    // RGB plane of each GBRG site and the pattern's phase, as launch_gray_of_rgb (ingest.hip)
-    constexpr int gbrg[4] = {1, 2, 0, 1}, phase[4] = {0, 3, 2, 1};
     UnprocessArgs a{};
     a.srgb = srgb; a.dither = dither; a.normal = normal;
     a.lin_f32 = lin_f32; a.lin_u16 = lin_u16; a.gt_raw = gt_raw; a.noisy = noisy;
     a.n = n; a.hh = hh; a.ww = ww;
-    for (int k = 0; k < 4; ++k) a.cols |= gbrg[k ^ phase[bayer]] << (2 * k);
+    a.cols = bayer_cols(bayer);
     for (int k = 0; k < 3; ++k) a.g[k] = g[k];
     a.A = iso == 3200 ? 3344.0f : 3807.0f;
     a.B = iso == 3200 ? 266.0f : 268.0f;

@@ -7,7 +7,8 @@ test-time dataset yields (frames 1 .. N-1-future of a video of N frames),
     <results_dir>/<video>/<frame>_denoised.tif
 
 -- the float32 [H,W,3] image `validate.py` writes for that frame (`util.visualizer.save_images`).  Everything between
-the file and the output frame runs on the device (`RvddRuntime.video_push`: ingest, TV-L1 flows, the frame-step).
+the file and the output frame runs on the device (`RvddRuntime.video_push`: ingest, TV-L1 flows, the frame-step;
+`RvddRuntime.egress`: the file's samples, one call per push over all slots and one copy to the host).
 
 The model flags are the reference's (`--netDenoiser --path2epoch / --checkpoints_dir --feature_rec --future_patch_depth
 --no_warp --warp_raw --prev_noisy_frame --bayer_pattern --bit_depth --patch_depth --gpu_ids --val_flow_from_denoised`;
@@ -18,6 +19,11 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       takes the next unstarted one, or idles when none is left (`deal_slots`).  Same files, same bytes.
   --srgb ISO,n,red_gain,blue_gain   also write <frame>_srgb.png: the display image of dataset/fwd_ppipe.py for that ISO and
                       white balance (rgb_gain = 1/n), `rvdd_ppipe` on the network output.
+  --out_format F      f32 (default): the file above.  rgb16 / mosaic16 / packed16: <results_dir>/<video>/<frame>.tif under the
+                      input frame's own base name, uint16 digital numbers as [H,W,3] linear RGB / the [H,W] mosaic in
+                      --bayer_pattern / the packed [H/2,W/2,4] frame (`rvdd_egress`) -- the results directory is then itself a
+                      --dataroot/--nFolder tree that `--dataset_mode rawvideo` reads (mosaic16, packed16).
+  --out_bit_depth N   the digital numbers' bit depth (default: --bit_depth)
 Videos of different frame sizes are grouped by size and run one group after the other, one runtime per size.
 """
 from __future__ import annotations
@@ -35,6 +41,9 @@ from . import _lib
 from .runtime import BAYER_PATTERNS, raw_frames_to_device
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
+# --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
+OUT_FORMATS = {"f32": ("rgb_hwc", torch.float32, "_denoised.tif"), "rgb16": ("rgb_hwc", torch.int16, ".tif"),
+               "mosaic16": ("mosaic", torch.int16, ".tif"), "packed16": ("packed_hwc", torch.int16, ".tif")}
 
 
 def deal_slots(lengths: Sequence[int], slots: int) -> List[List[Tuple[int, int, int]]]:
@@ -73,9 +82,16 @@ def _parse(argv):
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--results_dir', type=str, default='./results')
     p.add_argument('--srgb', type=str, default=None, help='ISO,n,red_gain,blue_gain: also write <frame>_srgb.png')
+    p.add_argument('--out_format', type=str, default='f32', help=', '.join(OUT_FORMATS))
+    p.add_argument('--out_bit_depth', type=int, default=None, help='bit depth of the sensor formats (default: --bit_depth)')
     own, rest = p.parse_known_args(argv)
+    if own.out_format not in OUT_FORMATS:
+        raise SystemExit("--out_format %r is not one of %s" % (own.out_format, ', '.join(OUT_FORMATS)))
     opt = parse(rest)
-    opt.results_dir, opt.srgb = own.results_dir, own.srgb
+    opt.results_dir, opt.srgb, opt.out_format = own.results_dir, own.srgb, own.out_format
+    opt.out_bit_depth = int(opt.bit_depth) if own.out_bit_depth is None else own.out_bit_depth
+    if not 1 <= opt.out_bit_depth <= 16:
+        raise SystemExit("--out_bit_depth must be 1..16, got %d" % opt.out_bit_depth)
     if not any(a == '--dataset_mode' or a.startswith('--dataset_mode=') for a in rest):
         opt.dataset_mode = 'rawvideo'
     if opt.srgb is not None:
@@ -95,8 +111,10 @@ def main(argv=None) -> dict:
     from .data import create_dataset
     from .library import iio_write
     from .models import create_model
-    from .util.visualizer import save_images
+    from .util import util
     opt = _parse(argv)
+    layout, sample, suffix = OUT_FORMATS[opt.out_format]
+    depth = 8 if opt.out_format == "f32" else opt.out_bit_depth
     v = copy.deepcopy(opt)
     v.max_dataset_size, v.num_threads, v.batch_size, v.serial_batches = float("inf"), 0, 1, True
     dataset = create_dataset(v).dataset
@@ -122,7 +140,7 @@ def main(argv=None) -> dict:
         rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
         rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
         shape = (B, H, W) if dataset.layout == "mosaic" else (B, H // 2, W // 2, 4)
-        out = None
+        out = files = None
         for step in deal_slots([len(f) for _, f in videos], B):
             batch = np.zeros(shape, dtype=dataset.dtype)
             for b, (c, vid, k) in enumerate(step):
@@ -130,6 +148,11 @@ def main(argv=None) -> dict:
                     batch[b] = dataset.read_frame(videos[vid][1][k])
             out, valid = rt.video_push(raw_frames_to_device(batch, dev), [c for c, _, _ in step], int(opt.bit_depth),
                                        dataset.layout, out)
+            host = None
+            if any(valid):                               # the files' samples of all slots: one kernel, one copy
+                files = rt.egress(out, layout, sample, depth, out=files)
+                host = files.cpu().numpy()
+                host = host.view(np.uint16) if host.dtype == np.int16 else host
             ended = False
             for b, (c, vid, k) in enumerate(step):
                 if c == IDLE:
@@ -139,11 +162,12 @@ def main(argv=None) -> dict:
                 if not valid[b]:
                     continue
                 path = frames[k - fut]                  # the centre frame
-                save_images(opt.results_dir, {'denoised': out[b:b + 1]}, [os.path.basename(path)], subfolder=key)
+                stem = os.path.splitext(os.path.basename(path))[0]
+                util.mkdir(os.path.join(opt.results_dir, key))
+                iio_write(host[b], os.path.join(opt.results_dir, key, stem + suffix))
                 if opt.srgb is not None:
                     iso, n, red, blue = opt.srgb
                     png = rt.ppipe(out[b:b + 1], 1.0 / n, red, blue, iso, _lib.PPIPE_FROM_NET, "nchw")
-                    stem = os.path.splitext(os.path.basename(path))[0]
                     iio_write(png[0].cpu().numpy(), os.path.join(opt.results_dir, key, stem + '_srgb.png'))
                 written += 1
             if ended:

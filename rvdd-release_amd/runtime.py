@@ -26,6 +26,8 @@ BAYER_PATTERNS = ("gbrg", "grbg", "rggb", "bggr")
 
 # enum rvdd_raw_layout by name (rvdd_ingest_raw, rvdd_video_push)
 RAW_LAYOUTS = {"mosaic": _lib.RAW_MOSAIC, "packed_hwc": _lib.RAW_PACKED_HWC}
+# enum rvdd_out_layout by name (rvdd_egress)
+OUT_LAYOUTS = {"rgb_hwc": _lib.OUT_RGB_HWC, "mosaic": _lib.OUT_MOSAIC, "packed_hwc": _lib.OUT_PACKED_HWC}
 
 
 def raw_frames_to_device(frames, device) -> torch.Tensor:
@@ -268,6 +270,46 @@ class RvddRuntime:
         self._check(self.lib.rvdd_gray_of_rgb(self.h, _ptr(rgb), n, H, W, pat, int(bit_depth), _ptr(gray), self._stream()),
                     "rvdd_gray_of_rgb")
         return gray
+
+    def egress(self, rgb: torch.Tensor, layout: str = "rgb_hwc", dtype: torch.dtype = getattr(torch, "uint16", torch.int16),
+               bit_depth: int = 12, pattern: Optional[str] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[n,3,H,W] RGB in [-1,1] -> the frames in a sensor container (rvdd_egress): digital numbers of `bit_depth` bits as
+        [n,H,W,3] ("rgb_hwc"), the re-mosaic in `pattern` as one plane [n,H,W] ("mosaic") or as [n,H/2,W/2,4] ("packed_hwc").
+        dtype torch.uint16 (rounded half to even, clamped to 0 .. 2^bit_depth - 1; torch.int16 gives the same 16 bits as the
+        view `ingest_raw` reads) or torch.float32 (neither rounded nor clamped).  pattern: one of BAYER_PATTERNS, None = the
+        pattern set_option("bayer_pattern", ...) gave this runtime.  out: a tensor of that shape and dtype to write into."""
+        if layout not in OUT_LAYOUTS:
+            raise ValueError(f"egress: layout {layout!r} is not one of {', '.join(OUT_LAYOUTS)}")
+        if pattern is None:
+            pat = getattr(self, "bayer_pattern", 0)
+        elif pattern in BAYER_PATTERNS:
+            pat = BAYER_PATTERNS.index(pattern)
+        else:
+            raise ValueError(f"egress: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
+        if dtype == torch.float32:
+            dt = _lib.RAW_F32
+        elif dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            dt = _lib.RAW_U16
+        else:
+            raise RuntimeError(f"egress: dtype must be torch.uint16 (or torch.int16, its view) or torch.float32, got {dtype}")
+        if not torch.is_tensor(rgb) or rgb.dim() != 4 or rgb.shape[1] != 3:
+            raise RuntimeError(f"egress: rgb is [n,3,H,W], got {tuple(getattr(rgb, 'shape', ()))}")
+        n, _, H, W = rgb.shape
+        rgb = _chk_dev(rgb, rgb.shape, "rgb", self.device)
+        shape = {"rgb_hwc": (n, H, W, 3), "mosaic": (n, H, W), "packed_hwc": (n, H // 2, W // 2, 4)}[layout]
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self._tdev)
+        else:
+            if not torch.is_tensor(out) or not out.is_cuda:
+                raise RuntimeError("egress: out must be a GPU tensor (rvdd has no CPU path)")
+            if out.device.index != self.device:
+                raise RuntimeError(f"egress: out lives on cuda:{out.device.index} but this runtime drives cuda:{self.device}")
+            if tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+                raise RuntimeError(f"egress: out must be a contiguous {dtype} tensor of shape {shape}, got {out.dtype} "
+                                   f"{tuple(out.shape)}")
+        self._check(self.lib.rvdd_egress(self.h, _ptr(rgb), n, H, W, OUT_LAYOUTS[layout], dt, int(bit_depth), pat, _ptr(out),
+                                         self._stream()), "rvdd_egress")
+        return out
 
     def video_push(self, frames: torch.Tensor, ctl=None, bit_depth: int = 12, layout: str = "mosaic", out=None):
         """Every slot's next sensor frame in, at most one denoised frame per slot out (rvdd_video_push).
