@@ -323,8 +323,33 @@ enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
  *   valid (HOST [cfg.batch]): 1 for the slots that are READY -- that hold 2 + future frames of their video -- and out_rgb[b]
  *       [cfg.batch,3,H,W] then holds the denoised CENTRE frame: with future = 0 the frame just pushed, with future = 1 the
  *       frame pushed one call earlier.  The outputs of a video of N frames are its frames 1 .. N-1-future, the frames
- *       data/infer4rec_dataset.py yields; frame 0 and, with a future frame, the last frame are never output (no flush).
- *       out_rgb[b] of a slot that is not ready is unspecified.
+ *       data/infer4rec_dataset.py yields; option "stream_all_frames" adds frame 0 and, with a future frame, the last frame:
+ *       valid[b] is 1 exactly where out_rgb[b] holds an output -- with that option also on a FIRST push (future = 0) and on
+ *       an IDLE push (a tail) -- and the frame is the oldest frame of the slot's video not yet output.
+ *       out_rgb[b] of a slot without an output is unspecified.
+ *   Option "stream_all_frames" (default 0: the paragraph above, the same launches, nothing more allocated).  Let n be the
+ *       frames of the slot's video pushed so far, this push included.  A push that carries a frame gives an output iff
+ *       n >= 1 + future (not 2 + future), the centre being frame c = n - 1 - future:
+ *         c == 0, the HEAD: no previous frame exists, so the step's raw_prev of the slot is frame 0 itself and its flow_prev
+ *           all zeros -- by definition: no TV-L1 pair is formed for that direction -- and the step carries the slot's reset
+ *           mark.  raw_next / flow_next with a future frame are the ordinary ones (frame 1, TV-L1 of (gray[0], gray[1]); the
+ *           noisy pair also under "stream_flow_from_denoised").
+ *         c == 1: exactly the first output without the option, its reset mark included: the head's step leaves no trace, and
+ *           every output with c >= 1 is bit for bit what the same pushes give with the option off.  Under
+ *           "stream_flow_from_denoised" this push keeps the noisy pair: the head's output is not matched against.
+ *         c > 1: as without the option.
+ *       IDLE on a slot with future = 1 whose previous push carried a frame is the TAIL: it outputs the video's last frame,
+ *       c = n - 1 (the slot gets no frame, its slice of `frames` is not read), with raw_next a copy of frame c itself and
+ *       flow_next all zeros (no pair); raw_prev / flow_prev are the ordinary ones (under "stream_flow_from_denoised" matched
+ *       against the previous output wherever an ordinary push at that position would be).  The recurrence carries on: no
+ *       reset mark, except at c == 1 (the video's first regular output) and c == 0 (a one-frame video: head and tail in one
+ *       step, previous = next = the frame, both flows zero).  Afterwards the slot is idle as after any IDLE: FIRST or IDLE.
+ *       FIRST straight after a video's last frame DROPS that video's tail, as without the option: a caller that wants it
+ *       puts one IDLE between two videos of a slot.  With future = 0 there is no tail and IDLE is what it always is.  With
+ *       "stream_reset_each" every output carries the reset mark, head and tail included; with "no_warp" no flow exists and
+ *       head and tail are just the substituted frames.  A video whose FIRST was pushed with the option off has no head.
+ *       The substituted frames are copied inside the slot's ring (one small launch per push that has a FIRST or a tail); a
+ *       push whose outputs have no TV-L1 pair at all runs no TV-L1, its step reads a zeroed flow tensor.
  * The handle keeps the last 2 + future ingested frames of every slot (packed and gray) on the device: allocated by the
  * first push, freed with the handle (20 (2 + future) + 24 (1 + future) bytes per raw cell and slot with the flow batch's
  * buffers; 4 more with option "stream_flow_from_denoised", allocated by the first push that has it on).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
@@ -492,6 +517,11 @@ int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, 
  *               taken from out_rgb inside the push that wrote it, so the caller may overwrite out_rgb between pushes.  Still one
  *               asynchronous rvdd_tvl1flow_batch per push.  Default 0: exactly the launches of a push without it.  Acts on
  *               rvdd_video_push only.  Per handle.
+ *   "stream_all_frames": 1 = rvdd_video_push outputs EVERY frame of a video, not only frames 1 .. N-1-future: the first frame on the
+ *               push that completes 1 + future frames (previous frame = itself, zero flow towards it, reset mark), and with a future
+ *               frame the last one on an IDLE pushed straight after it (next frame = itself, zero flow towards it); the contract is
+ *               with rvdd_video_push.  Every other output keeps its bits.  Default 0: exactly the launches of a push without it, and
+ *               nothing more allocated.  Acts on rvdd_video_push only.  Per handle.
  * Every option belongs to the handle it is set on: no option changes what another handle of the process does.
  * Unknown names are an error. */
 int rvdd_set_option(rvdd_t* h, const char* name, int32_t value);

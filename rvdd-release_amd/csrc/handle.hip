@@ -98,7 +98,8 @@ int opt_conv_kernel(rvdd_t* h, int32_t value) {
     X("bayer_pattern", nullptr, bayer, RVDD_BAYER_GBRG, RVDD_BAYER_BGGR,                                                         \
       "rvdd_set_option: bayer_pattern must be 0 (GBRG), 1 (GRBG), 2 (RGGB) or 3 (BGGR)", nullptr)                                \
     X("stream_reset_each", nullptr, stream_reset_each, 0, 1, nullptr, nullptr)                                                   \
-    X("stream_flow_from_denoised", nullptr, stream_flow_from_denoised, 0, 1, nullptr, nullptr)
+    X("stream_flow_from_denoised", nullptr, stream_flow_from_denoised, 0, 1, nullptr, nullptr)                                   \
+    X("stream_all_frames", nullptr, stream_all_frames, 0, 1, nullptr, nullptr)
 struct OptRow {
     const char* name;
     const char* env;

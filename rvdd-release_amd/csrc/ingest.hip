@@ -1,6 +1,6 @@
 // Sensor frames -> the inputs of a frame-step (packed raw in [-1, 1]) and of TV-L1 (gray plane in DN), the same gray plane of
-// an output frame's re-mosaic (rvdd_gray_of_rgb), the way back -- an output frame as sensor frames (rvdd_egress) -- and the two
-// small copy kernels rvdd_video_push composes its flow batch with.  Compiled -ffp-contract=off: every operation below is rounded
+// an output frame's re-mosaic (rvdd_gray_of_rgb), the way back -- an output frame as sensor frames (rvdd_egress) -- and the
+// small copy kernels rvdd_video_push composes its flow batch and its substituted frames with.  Compiled -ffp-contract=off: every operation below is rounded
 // to f32 on its own, which is what makes the outputs the bits of the reference's loader (library.py load_image + the
 // dataset's transform) and of library._gray on integer-valued frames.
 //
@@ -311,27 +311,31 @@ hipError_t launch_egress_l(const float* rgb, int n, int H, int W, int cols, floa
                       : launch_egress_t<LAYOUT>(rgb, n, H, W, cols, top, static_cast<float*>(out), wide, blocks, s);
 }
 
-// ---- rvdd_video_push: the flow batch's operands and results ------------------------------------------------------------
-// The ready slots of a push, one byte each (B <= 64 on a partial set; the full set needs no list)
+// ---- rvdd_video_push: the flow batch's operands and results, and the substituted frames of the ring ------------------------
+// One byte per entry, handed to the kernel by value (B <= 64 slots, two directions)
 struct SlotList {
     unsigned char slot[64];
 };
+struct PairList {
+    unsigned char e[128];
+};
 
 // (V = f32x4 where a plane is a whole number of 16-B vectors, float otherwise; hw4 / hw2_4 count V's)
-// I0[q] / I1[q], q < npairs: pair q < nready = (centre, previous) of ready slot q, pair nready + q = (centre, next).
+// I0[q] / I1[q], q < npairs: pair q is (centre, previous) of slot b for the entry b, (centre, next) for the entry 64 | b; with
+// `all` -- every slot has every pair, no list -- pair q is slot q % B, direction q / B.
 // gray_c / gray_p / gray_n: the [B][hw] planes of the ring positions that hold the centre, previous and next frames.
 // dgray [B][hw]: the gray planes of the slots' previous OUTPUTS; slot b's pair towards the previous frame is matched against
 // it where bit b of from_den is set (option "stream_flow_from_denoised"), against gray_p elsewhere.
 template <typename V>
 __global__ void __launch_bounds__(256) stream_gather_kernel(const float* __restrict__ gray_c, const float* __restrict__ gray_p,
                                                             const float* __restrict__ gray_n, const float* __restrict__ dgray,
-                                                            float* __restrict__ I0, float* __restrict__ I1, SlotList sl, int nready, int all,
+                                                            float* __restrict__ I0, float* __restrict__ I1, PairList pl, int B, int all,
                                                             uint64_t from_den, int64_t hw4) {
     const int q = blockIdx.y;
-    const int r = q < nready ? q : q - nready;
-    const int b = all ? r : sl.slot[r];
+    const int b = all ? q % B : pl.e[q] & 63;
+    const int dir = all ? q / B : pl.e[q] >> 6;
     const V* c = reinterpret_cast<const V*>(gray_c) + (int64_t)b * hw4;
-    const float* other = q >= nready ? gray_n : ((from_den >> b) & 1) ? dgray : gray_p;
+    const float* other = dir ? gray_n : ((from_den >> b) & 1) ? dgray : gray_p;
     const V* o = reinterpret_cast<const V*>(other) + (int64_t)b * hw4;
     V* d0 = reinterpret_cast<V*>(I0) + (int64_t)q * hw4;
     V* d1 = reinterpret_cast<V*>(I1) + (int64_t)q * hw4;
@@ -341,18 +345,30 @@ __global__ void __launch_bounds__(256) stream_gather_kernel(const float* __restr
     }
 }
 
-// flows [ndir][B][2][hw] of a step from the batch's u [ndir * nready][2][hw]: the flow of a ready slot, zero for the others.
-// rank[b] = position of slot b among the ready ones, 255 = not ready.
+// flows [ndir][B][2][hw] of a step from the batch's u [npairs][2][hw]: the flow of a (slot, direction) that has a pair, zero
+// for the others.  rank.e[dir * B + b] = position of that pair in the batch, 255 = none.
 template <typename V>
-__global__ void __launch_bounds__(256) stream_scatter_kernel(const float* __restrict__ u, float* __restrict__ flows, SlotList rank, int nready,
-                                                             int B, int64_t hw2_4) {
-    const int b = blockIdx.y % B, dir = blockIdx.y / B;
-    const int r = rank.slot[b];
-    V* d = reinterpret_cast<V*>(flows) + ((int64_t)dir * B + b) * hw2_4;
-    const V* src = r == 255 ? nullptr : reinterpret_cast<const V*>(u) + ((int64_t)dir * nready + r) * hw2_4;
+__global__ void __launch_bounds__(256) stream_scatter_kernel(const float* __restrict__ u, float* __restrict__ flows, PairList rank,
+                                                             int64_t hw2_4) {
+    const int r = rank.e[blockIdx.y];
+    V* d = reinterpret_cast<V*>(flows) + (int64_t)blockIdx.y * hw2_4;
+    const V* src = r == 255 ? nullptr : reinterpret_cast<const V*>(u) + (int64_t)r * hw2_4;
     const V zero = {};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw2_4; i += (int64_t)gridDim.x * blockDim.x)
         d[i] = src ? src[i] : zero;
+}
+
+// option "stream_all_frames": the packed frame of every listed slot from one ring position to its neighbour -- ring_prev / ring_pos
+// [B][4][hw] are the positions before this push's and this push's; bit b of to_pos set: previous -> this push's (a tail: the last
+// frame stands in for the missing next one), clear: this push's -> previous (a FIRST: frame 0 stands in for the missing previous
+// one).  A packed frame is hw vectors of 16 B on a 16-B boundary whatever hw is.
+__global__ void __launch_bounds__(256) stream_dup_kernel(float* __restrict__ ring_prev, float* __restrict__ ring_pos, SlotList sl,
+                                                         uint64_t to_pos, int64_t hw) {
+    const int b = sl.slot[blockIdx.y];
+    const bool fwd = (to_pos >> b) & 1;
+    const f32x4* src = reinterpret_cast<const f32x4*>(fwd ? ring_prev : ring_pos) + (int64_t)b * hw;
+    f32x4* dst = reinterpret_cast<f32x4*>(fwd ? ring_pos : ring_prev) + (int64_t)b * hw;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
 }  // namespace
@@ -418,38 +434,57 @@ hipError_t launch_egress(const float* rgb, int n, int H, int W, int layout, int 
                          : launch_egress_l<2>(rgb, n, H, W, cols, top, dtype, out, wide, blocks, s);
 }
 
-// planes of the handle's own buffers (hipMalloc alignment); slots: the ready slots in order (ignored when nready == B)
+// planes of the handle's own buffers (hipMalloc alignment); pairs: slot | direction << 6 of every pair in batch order (ignored
+// when every slot has every pair)
 hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const float* gray_n, const float* dgray, uint64_t from_den,
-                                float* I0, float* I1, const int* slots, int nready, int B, int64_t hw, hipStream_t s) {
-    SlotList sl{};
-    const int all = nready == B;
-    if (B > 64 || (from_den && !dgray)) return hipErrorInvalidValue;      // one bit, one byte per slot
+                                float* I0, float* I1, const uint8_t* pairs, int npairs, int B, int64_t hw, hipStream_t s) {
+    PairList pl{};
+    const int all = npairs == B * (gray_n ? 2 : 1);
+    if (B > 64 || npairs < 1 || npairs > B * (gray_n ? 2 : 1) || (from_den && !dgray)) return hipErrorInvalidValue;      // one bit per slot
     if (!all)
-        for (int q = 0; q < nready; ++q) sl.slot[q] = (unsigned char)slots[q];
-    const int npairs = nready * (gray_n ? 2 : 1);
+        for (int q = 0; q < npairs; ++q) {
+            if ((pairs[q] & 63) >= B || (pairs[q] >> 6) > (gray_n ? 1 : 0)) return hipErrorInvalidValue;
+            pl.e[q] = pairs[q];
+        }
     const bool vec = (hw & 3) == 0;
     const int64_t hw4 = vec ? hw / 4 : hw;
     const int gx = (int)((hw4 + 255) / 256 < 256 ? (hw4 + 255) / 256 : 256);
     if (vec)
-        hipLaunchKernelGGL(stream_gather_kernel<f32x4>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, dgray, I0, I1, sl, nready, all,
+        hipLaunchKernelGGL(stream_gather_kernel<f32x4>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, dgray, I0, I1, pl, B, all,
                            from_den, hw4);
     else
-        hipLaunchKernelGGL(stream_gather_kernel<float>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, dgray, I0, I1, sl, nready, all,
+        hipLaunchKernelGGL(stream_gather_kernel<float>, dim3(gx, npairs), dim3(256), 0, s, gray_c, gray_p, gray_n, dgray, I0, I1, pl, B, all,
                            from_den, hw4);
     return hipGetLastError();
 }
 
-hipError_t launch_stream_scatter(const float* u, float* flows, const int* slots, int nready, int ndir, int B, int64_t hw, hipStream_t s) {
-    if (B > 64) return hipErrorInvalidValue;
-    SlotList rank;
-    for (int b = 0; b < 64; ++b) rank.slot[b] = 255;
-    for (int q = 0; q < nready; ++q) rank.slot[slots[q]] = (unsigned char)q;
+hipError_t launch_stream_scatter(const float* u, float* flows, const uint8_t* pairs, int npairs, int ndir, int B, int64_t hw, hipStream_t s) {
+    if (B > 64 || ndir < 1 || ndir > 2 || npairs < 0 || npairs > ndir * B) return hipErrorInvalidValue;
+    PairList rank;
+    for (int i = 0; i < 128; ++i) rank.e[i] = 255;
+    for (int q = 0; q < npairs; ++q) {
+        if ((pairs[q] & 63) >= B || (pairs[q] >> 6) >= ndir) return hipErrorInvalidValue;
+        rank.e[(pairs[q] >> 6) * B + (pairs[q] & 63)] = (unsigned char)q;
+    }
     const bool vec = (hw & 1) == 0;
     const int64_t n4 = vec ? 2 * hw / 4 : 2 * hw;
     const int gx = (int)((n4 + 255) / 256 < 256 ? (n4 + 255) / 256 : 256);
     if (vec)
-        hipLaunchKernelGGL(stream_scatter_kernel<f32x4>, dim3(gx, ndir * B), dim3(256), 0, s, u, flows, rank, nready, B, n4);
+        hipLaunchKernelGGL(stream_scatter_kernel<f32x4>, dim3(gx, ndir * B), dim3(256), 0, s, u, flows, rank, n4);
     else
-        hipLaunchKernelGGL(stream_scatter_kernel<float>, dim3(gx, ndir * B), dim3(256), 0, s, u, flows, rank, nready, B, n4);
+        hipLaunchKernelGGL(stream_scatter_kernel<float>, dim3(gx, ndir * B), dim3(256), 0, s, u, flows, rank, n4);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_dup(float* ring_prev, float* ring_pos, const int* slots, int nslots, uint64_t to_pos, int B, int64_t hw, hipStream_t s) {
+    if (nslots <= 0) return hipSuccess;
+    if (B > 64 || nslots > B) return hipErrorInvalidValue;
+    SlotList sl{};
+    for (int q = 0; q < nslots; ++q) {
+        if (slots[q] < 0 || slots[q] >= B) return hipErrorInvalidValue;
+        sl.slot[q] = (unsigned char)slots[q];
+    }
+    const int gx = (int)((hw + 255) / 256 < 256 ? (hw + 255) / 256 : 256);
+    hipLaunchKernelGGL(stream_dup_kernel, dim3(gx, nslots), dim3(256), 0, s, ring_prev, ring_pos, sl, to_pos, hw);
     return hipGetLastError();
 }

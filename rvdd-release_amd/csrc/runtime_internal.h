@@ -158,6 +158,7 @@ struct Options {
     int tvl1_async = 0;       // rvdd_tvl1flow_batch without iteration counts enqueues and returns
     int stream_reset_each = 0;            // every ready step of rvdd_video_push carries the reset mark of every ready slot
     int stream_flow_from_denoised = 0;    // rvdd_video_push: the flow towards the previous frame is matched against the previous output
+    int stream_all_frames = 0;            // rvdd_video_push: also a video's first frame and, on an IDLE behind its last frame, that frame
     int use_graphs = 0;       // replay captured frame-steps (measured slower, off)
 
     bool split16() const { return conv == CONV_SPLIT16; }
@@ -223,6 +224,8 @@ struct rvdd_handle {
         uint64_t pushes = 0;
         std::vector<int> count;      // per slot: frames of its video pushed in a row (0: never started, or idle on the last push)
         std::vector<uint8_t> was_idle;
+        std::vector<uint8_t> head;   // per slot: its video's FIRST came under option "stream_all_frames" and left frame 0 also in the ring
+                                     // position before its own, where a head's step reads the previous frame
         float* dgray = nullptr;      // [B][hh][ww]: gray plane of every slot's last output (option "stream_flow_from_denoised"; allocated by
                                      // the first push that has the option on)
         std::vector<uint8_t> dgray_ok;   // per slot: dgray holds the output of the push before this one

@@ -342,7 +342,7 @@ hipError_t launch_ppipe(const float* img, int n, int H, int W, int64_t sn, int64
 size_t srgb_metrics_workspace(int n, int H, int W);
 hipError_t launch_srgb_metrics(const uint8_t* a, const uint8_t* b, int n, int H, int W, void* ws, hipStream_t s);
 
-// ingest.hip -- sensor frames to the inputs of a step and of TV-L1 (rvdd_ingest_raw), and rvdd_video_push's two copy kernels
+// ingest.hip -- sensor frames to the inputs of a step and of TV-L1 (rvdd_ingest_raw), and rvdd_video_push's copy kernels
 // frames: n frames, dtype 0 = u16 / 1 = f32, layout 0 = mosaic [n][2hh][2ww] / 1 = packed HWC [n][hh][ww][4];
 // packed [n][4][hh][ww] = 2 * (dn / (2^bit_depth - 1)) - 1, gray [n][hh][ww] = (((c0 + c1) + c2) + c3) * 0.25 in DN; either nullable
 hipError_t launch_ingest_raw(const void* frames, int dtype, int layout, int n, int hh, int ww, int bit_depth, float* packed, float* gray,
@@ -366,12 +366,17 @@ hipError_t launch_egress(const float* rgb, int n, int H, int W, int layout, int 
 // the grid of that launch (n, H, W >= 1) and whether it takes the wide form; -1 = more than 2^31 - 1 blocks
 int64_t egress_blocks(const float* rgb, int n, int H, int W, int layout, int dtype, const void* out, bool* wide);
 // the flow batch of a push: I0 / I1 [npairs][hw] from the gray planes [B][hw] of the ring positions of the centre, previous and
-// next (nullable: no future frame) frames -- pair q < nready = (centre, previous) of slots[q], pair nready + q = (centre, next).
+// next (nullable: no future frame) frames.  pairs[q] = slot | direction << 6 of pair q (direction 0: (centre, previous), 1: (centre,
+// next)); with npairs = B * directions -- every slot has every pair -- pair q is slot q % B, direction q / B, and pairs is not read.
 // A slot whose bit of from_den is set has its (centre, previous) pair matched against dgray [B][hw] instead of gray_p (B <= 64).
 hipError_t launch_stream_gather(const float* gray_c, const float* gray_p, const float* gray_n, const float* dgray, uint64_t from_den,
-                                float* I0, float* I1, const int* slots, int nready, int B, int64_t hw, hipStream_t s);
-// flows [ndir][B][2][hw] of the step from the batch's u [ndir * nready][2][hw]: zero for the slots that are not ready (B <= 64)
-hipError_t launch_stream_scatter(const float* u, float* flows, const int* slots, int nready, int ndir, int B, int64_t hw, hipStream_t s);
+                                float* I0, float* I1, const uint8_t* pairs, int npairs, int B, int64_t hw, hipStream_t s);
+// flows [ndir][B][2][hw] of the step from the batch's u [npairs][2][hw]: zero for every (slot, direction) without a pair (B <= 64;
+// npairs = 0 zeroes them all and does not read u)
+hipError_t launch_stream_scatter(const float* u, float* flows, const uint8_t* pairs, int npairs, int ndir, int B, int64_t hw, hipStream_t s);
+// option "stream_all_frames": the packed frame [4][hw] of every listed slot copied between ring_prev and ring_pos [B][4][hw], the ring
+// positions before this push's and this push's: previous -> this push's where bit slot of to_pos is set, the other way elsewhere
+hipError_t launch_stream_dup(float* ring_prev, float* ring_pos, const int* slots, int nslots, uint64_t to_pos, int B, int64_t hw, hipStream_t s);
 
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from

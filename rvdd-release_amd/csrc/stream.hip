@@ -26,6 +26,7 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         st.count.assign((size_t)B, 0);
         st.was_idle.assign((size_t)B, 0);
         st.dgray_ok.assign((size_t)B, 0);
+        st.head.assign((size_t)B, 0);
         float *pk = nullptr, *gr = nullptr;
         RC(dmalloc(h, reinterpret_cast<void**>(&gr), (size_t)depth * B * hw * sizeof(float)));
         RC(dmalloc(h, reinterpret_cast<void**>(&st.I0), (size_t)nd * B * hw * sizeof(float)));
@@ -55,33 +56,65 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
                                     st.packed + ((size_t)pos * B + b) * 4 * hw, st.gray + ((size_t)pos * B + b) * hw, s));
         return RVDD_OK;
     }));
-    std::vector<int> ready, fresh;
-    uint64_t den_slots = 0;      // ready slots whose previous push gave an output of the same video, its gray plane in dgray
+    // Per slot: which frame of its video this push outputs (centre; -1: none).  The plain rule is centre = n - 1 - future >= 1.  Option
+    // "stream_all_frames" adds the HEAD, centre 0 -- frame 0 stands in for the missing previous frame, the flow towards it is zero by
+    // definition -- and, with a future frame, the TAIL: an IDLE straight after the video's last frame outputs that frame, centre n - 1,
+    // with itself as the next frame and a zero flow towards it.  The substituted frames lie in the slot's own ring positions (dup).
+    const bool all_frames = h->opt.stream_all_frames;
+    std::vector<int> ready, fresh, dup, centre((size_t)B, -1);
+    std::vector<uint8_t> pairs, next_pairs;      // slot | direction << 6 of every TV-L1 pair: the pairs towards the previous frames first
+    uint64_t den_slots = 0;      // slots whose pair towards the previous frame is matched against the previous output, its gray plane in dgray
+    uint64_t tails = 0;
     for (int b = 0; b < B; ++b) {
         const int c = ctl ? ctl[b] : RVDD_PUSH_NEXT;
         int& n = st.count[(size_t)b];
-        n = c == RVDD_PUSH_IDLE ? 0 : c == RVDD_PUSH_FIRST ? 1 : (n < (1 << 30) ? n + 1 : n);
+        // a tail needs the frame in front of the centre in the ring: frame n - 2, or the copy a FIRST under the option left
+        const bool tail = all_frames && fut && c == RVDD_PUSH_IDLE && n >= 1 && (n >= 2 || st.head[(size_t)b]);
+        int& ctr = centre[(size_t)b];
+        if (tail) {
+            ctr = n - 1;
+            tails |= 1ull << b;
+            dup.push_back(b);
+        } else {
+            n = c == RVDD_PUSH_IDLE ? 0 : c == RVDD_PUSH_FIRST ? 1 : (n < (1 << 30) ? n + 1 : n);
+            if (c == RVDD_PUSH_FIRST) {
+                st.head[(size_t)b] = all_frames;
+                if (all_frames) dup.push_back(b);
+            }
+            if (c != RVDD_PUSH_IDLE) ctr = n - 1 - fut;
+            if (ctr < 0 || (ctr == 0 && !(all_frames && st.head[(size_t)b]))) ctr = -1;
+        }
         st.was_idle[(size_t)b] = c == RVDD_PUSH_IDLE;
-        valid[b] = n >= st.depth;
-        if (n >= st.depth) ready.push_back(b);
-        if (n == st.depth || (h->opt.stream_reset_each && n >= st.depth)) fresh.push_back(b);
-        if (from_den && n > st.depth && st.dgray_ok[(size_t)b]) den_slots |= 1ull << b;
+        valid[b] = ctr >= 0;
+        if (ctr >= 0) {
+            ready.push_back(b);
+            if (ctr <= 1 || h->opt.stream_reset_each) fresh.push_back(b);
+            if (ctr >= 1) pairs.push_back((uint8_t)b);
+            if (fut && !tail) next_pairs.push_back((uint8_t)(64 | b));
+            if (from_den && ctr >= 2 && st.dgray_ok[(size_t)b]) den_slots |= 1ull << b;
+        }
         st.dgray_ok[(size_t)b] = 0;
+        if (tail) n = 0;      // idle from here on, as after any IDLE
     }
     st.pushes++;
-    if (ready.empty()) return RVDD_OK;
-    const int nready = (int)ready.size();
-    // ring positions: with a future frame the centre is the frame of the push before
-    const int pc = (pos + st.depth - fut) % st.depth, pp = (pc + st.depth - 1) % st.depth;
     auto packed_at = [&](int p) { return st.packed + (size_t)p * B * 4 * hw; };
     auto gray_at = [&](int p) { return st.gray + (size_t)p * B * hw; };
+    if (!dup.empty())
+        HIPCHK(h, launch_stream_dup(packed_at((pos + st.depth - 1) % st.depth), packed_at(pos), dup.data(), (int)dup.size(), tails, B, (int64_t)hw, s));
+    if (ready.empty()) return RVDD_OK;
+    // ring positions: with a future frame the centre is the frame of the push before
+    const int pc = (pos + st.depth - fut) % st.depth, pp = (pc + st.depth - 1) % st.depth;
     const float *flow_prev = nullptr, *flow_next = nullptr;
     if (!h->opt.no_warp) {
-        HIPCHK(h, launch_stream_gather(gray_at(pc), gray_at(pp), fut ? gray_at(pos) : nullptr, st.dgray, den_slots, st.I0, st.I1, ready.data(), nready, B,
-                                       (int64_t)hw, s));
-        float* u = nready == B ? st.flows : st.u;      // every slot ready: the batch writes the step's flows itself
-        RC(tvl1flow_batch(h, st.I0, st.I1, u, nready * (1 + fut), ww, hh, nullptr, stream, true));
-        if (nready != B) HIPCHK(h, launch_stream_scatter(st.u, st.flows, ready.data(), nready, 1 + fut, B, (int64_t)hw, s));
+        pairs.insert(pairs.end(), next_pairs.begin(), next_pairs.end());
+        const int npairs = (int)pairs.size();
+        const bool whole = npairs == B * (1 + fut);      // every slot has every pair: the batch writes the step's flows itself
+        if (npairs) {
+            HIPCHK(h, launch_stream_gather(gray_at(pc), gray_at(pp), fut ? gray_at(pos) : nullptr, st.dgray, den_slots, st.I0, st.I1, pairs.data(), npairs, B,
+                                           (int64_t)hw, s));
+            RC(tvl1flow_batch(h, st.I0, st.I1, whole ? st.flows : st.u, npairs, ww, hh, nullptr, stream, true));
+        }
+        if (!whole) HIPCHK(h, launch_stream_scatter(st.u, st.flows, pairs.data(), npairs, 1 + fut, B, (int64_t)hw, s));
         flow_prev = st.flows;
         flow_next = fut ? st.flows + (size_t)B * 2 * hw : nullptr;
     }
@@ -95,7 +128,7 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         // the plane is taken from the output (with "prev_noisy_frame" lastden holds the noisy demosaic) inside the push that wrote it:
         // the caller may overwrite out_rgb before the next one
         HIPCHK(h, launch_gray_of_rgb(out_rgb, B, hh, ww, h->opt.bayer, bit_depth, st.dgray, s));
-        for (int b : ready) st.dgray_ok[(size_t)b] = 1;
+        for (int b : ready) st.dgray_ok[(size_t)b] = centre[(size_t)b] >= 1 && st.count[(size_t)b] > 0;      // not a head's, not a tail's
     }
     return RVDD_OK;
 }

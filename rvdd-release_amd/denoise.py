@@ -2,7 +2,7 @@
 
 Reads `<dataroot>/<nFolder>/<video>/<frame>.tif` (`--dataset_mode rawvideo`: sensor frames as 1-channel mosaics or
 4-channel packed frames, uint16 or float32; no ground truth, no flow folder) and writes, for every frame the reference's
-test-time dataset yields (frames 1 .. N-1-future of a video of N frames),
+test-time dataset yields (frames 1 .. N-1-future of a video of N frames; every frame with --all_frames),
 
     <results_dir>/<video>/<frame>_denoised.tif
 
@@ -24,6 +24,9 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       --bayer_pattern / the packed [H/2,W/2,4] frame (`rvdd_egress`) -- the results directory is then itself a
                       --dataroot/--nFolder tree that `--dataset_mode rawvideo` reads (mosaic16, packed16).
   --out_bit_depth N   the digital numbers' bit depth (default: --bit_depth)
+  --all_frames        write EVERY input frame (option "stream_all_frames"): also frame 0 of a video -- denoised with itself as the
+                      previous frame, a zero flow and a fresh recurrence; frame 1 then starts as always -- and, with a future frame,
+                      the last frame, with itself as the next frame.  The files of frames 1 .. N-1-future keep their bytes.
 Videos of different frame sizes are grouped by size and run one group after the other, one runtime per size.
 """
 from __future__ import annotations
@@ -46,11 +49,13 @@ OUT_FORMATS = {"f32": ("rgb_hwc", torch.float32, "_denoised.tif"), "rgb16": ("rg
                "mosaic16": ("mosaic", torch.int16, ".tif"), "packed16": ("packed_hwc", torch.int16, ".tif")}
 
 
-def deal_slots(lengths: Sequence[int], slots: int) -> List[List[Tuple[int, int, int]]]:
+def deal_slots(lengths: Sequence[int], slots: int, tail: int = 0) -> List[List[Tuple[int, int, int]]]:
     """The pushes of videos of `lengths` frames on `slots` batch slots: a list of steps, each a list of one
     (ctl, video, frame) per slot.  The videos are dealt in order; a slot whose video ended takes the next unstarted
     video (FIRST on its frame 0), or goes IDLE -- (IDLE, -1, -1) -- when none is left; the list ends with the last step
-    that carries a frame.  Every frame of every video appears once, in order, and NEXT never follows IDLE."""
+    that carries a frame.  Every frame of every video appears once, in order, and NEXT never follows IDLE.
+    tail=1 (option "stream_all_frames" with a future frame): a slot whose video v of N frames has ended first sits out one
+    step, returned as (IDLE, v, N) -- the push that outputs the video's last frame -- and the list ends with the last such step."""
     if slots < 1:
         raise ValueError("deal_slots: at least one slot")
     if any(n < 1 for n in lengths):
@@ -65,6 +70,9 @@ def deal_slots(lengths: Sequence[int], slots: int) -> List[List[Tuple[int, int, 
             if v >= 0 and k < lengths[v]:
                 step.append((NEXT, v, k))
                 cur[b] = (v, k + 1)
+            elif v >= 0 and tail:
+                step.append((IDLE, v, k))
+                cur[b] = (-1, 0)
             elif nxt < len(lengths):
                 step.append((FIRST, nxt, 0))
                 cur[b] = (nxt, 1)
@@ -72,7 +80,7 @@ def deal_slots(lengths: Sequence[int], slots: int) -> List[List[Tuple[int, int, 
             else:
                 step.append((IDLE, -1, -1))
                 cur[b] = (-1, 0)
-        if all(c == IDLE for c, _, _ in step):
+        if all(v < 0 for _, v, _ in step):
             return steps
         steps.append(step)
 
@@ -84,11 +92,12 @@ def _parse(argv):
     p.add_argument('--srgb', type=str, default=None, help='ISO,n,red_gain,blue_gain: also write <frame>_srgb.png')
     p.add_argument('--out_format', type=str, default='f32', help=', '.join(OUT_FORMATS))
     p.add_argument('--out_bit_depth', type=int, default=None, help='bit depth of the sensor formats (default: --bit_depth)')
+    p.add_argument('--all_frames', action='store_true', help='write every input frame, the first and the last of a video too')
     own, rest = p.parse_known_args(argv)
     if own.out_format not in OUT_FORMATS:
         raise SystemExit("--out_format %r is not one of %s" % (own.out_format, ', '.join(OUT_FORMATS)))
     opt = parse(rest)
-    opt.results_dir, opt.srgb, opt.out_format = own.results_dir, own.srgb, own.out_format
+    opt.results_dir, opt.srgb, opt.out_format, opt.all_frames = own.results_dir, own.srgb, own.out_format, own.all_frames
     opt.out_bit_depth = int(opt.bit_depth) if own.out_bit_depth is None else own.out_bit_depth
     if not 1 <= opt.out_bit_depth <= 16:
         raise SystemExit("--out_bit_depth must be 1..16, got %d" % opt.out_bit_depth)
@@ -139,9 +148,11 @@ def main(argv=None) -> dict:
         rt.set_option("bayer_pattern", BAYER_PATTERNS.index(opt.bayer_pattern))
         rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
         rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
+        rt.set_option("stream_all_frames", int(opt.all_frames))
         shape = (B, H, W) if dataset.layout == "mosaic" else (B, H // 2, W // 2, 4)
         out = files = None
-        for step in deal_slots([len(f) for _, f in videos], B):
+        # --all_frames with a future frame: the step behind a video's last frame (k = N) is the IDLE that outputs that frame
+        for step in deal_slots([len(f) for _, f in videos], B, tail=fut if opt.all_frames else 0):
             batch = np.zeros(shape, dtype=dataset.dtype)
             for b, (c, vid, k) in enumerate(step):
                 if c != IDLE:
@@ -155,10 +166,10 @@ def main(argv=None) -> dict:
                 host = host.view(np.uint16) if host.dtype == np.int16 else host
             ended = False
             for b, (c, vid, k) in enumerate(step):
-                if c == IDLE:
+                if vid < 0:
                     continue
                 key, frames = videos[vid]
-                ended = ended or k == len(frames) - 1
+                ended = ended or k == len(frames) - (0 if opt.all_frames and fut else 1)      # the step that ends the video
                 if not valid[b]:
                     continue
                 path = frames[k - fut]                  # the centre frame

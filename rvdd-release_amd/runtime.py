@@ -315,7 +315,11 @@ class RvddRuntime:
         """Every slot's next sensor frame in, at most one denoised frame per slot out (rvdd_video_push).
         frames: [B,2hh,2ww] / [B,hh,ww,4] as `ingest_raw` takes them; ctl: None (every slot continues its video) or B
         values of _lib.PUSH_NEXT / PUSH_FIRST / PUSH_IDLE.  -> (out [B,3,H,W], valid: B bools); out[b] is the denoised
-        centre frame of slot b where valid[b], unspecified elsewhere.  Nothing is synchronised."""
+        centre frame of slot b where valid[b], unspecified elsewhere.  Nothing is synchronised.
+        A video of N frames gives its frames 1 .. N-1-future.  With option "stream_all_frames" it gives every frame: frame 0 on
+        the push that completes 1 + future frames, and with a future frame the last one on a PUSH_IDLE straight after it (a
+        PUSH_FIRST there drops it); valid[b] is then also set on such a FIRST / IDLE push, and out[b] is the oldest frame of
+        the slot's video not yet output."""
         t, dtype, lay, n, hh, ww = _raw_frames(frames, layout, "video_push", self.device)
         B, H, W = self.B, self.H, self.W
         if (n, 2 * hh, 2 * ww) != (B, H, W):

@@ -4,7 +4,7 @@ the device) beside the same handle stepping with the flows computed beforehand (
 synthetic uint16 mosaics.  Two JSON lines: {"mode": "stream"} and {"mode": "step_flows_at_hand"}.
 
 usage (GPU box, repo root):  timeout -k 10 600 python tools/stream_bench.py --config C2 [--batch 8] [--frames 12] [--warmup 3]
-                             [--flow-from-denoised]
+                             [--flow-from-denoised] [--all-frames] [--video-len N]
 One process, no retries: a failure is the exit status."""
 import argparse
 import json
@@ -30,6 +30,12 @@ ap.add_argument("--warmup", type=int, default=3, help="pushes before the clock s
 ap.add_argument("--no-sampler", action="store_true", help="do not sample the shader clock (rocm-smi) beside the loops")
 ap.add_argument("--flow-from-denoised", action="store_true",
                 help="option stream_flow_from_denoised: flows towards the previous frame against the previous output (stream mode only)")
+ap.add_argument("--all-frames", action="store_true",
+                help="option stream_all_frames: every frame of a video is output; with a future frame each video ends with one IDLE push "
+                     "(stream mode only)")
+ap.add_argument("--video-len", type=int, default=None,
+                help="frames per video: every slot streams its warmup + frames frames as videos of this length, one after the other "
+                     "(default: one video)")
 args = ap.parse_args()
 arch, stem, fut, iso, H, W, _, B0, _ = bench.CONFIGS[args.config]
 B = args.batch or B0
@@ -49,6 +55,7 @@ del raw, dn
 rt = RvddRuntime(arch, fut, B, H, W, 0)
 rt.load_state_dict(load_file(os.path.join(REPO, "weights", stem + ".safetensors")))
 rt.set_option("stream_flow_from_denoised", int(args.flow_from_denoised))
+rt.set_option("stream_all_frames", int(args.all_frames))
 sampler = None if args.no_sampler else bench.GpuSampler(0, 0.05)
 
 
@@ -61,24 +68,36 @@ def clock(t0, t1):
 
 common = {"config": args.config, "arch": arch, "future": fut, "batch": B, "height": H, "width": W, "frames_per_slot": args.frames,
           "flow_from_denoised": bool(args.flow_from_denoised)}
+V = args.video_len or T
+assert V >= 1
+# the pushes of a slot: (ctl, frame); with --all-frames and a future frame every video is followed by the IDLE that outputs its last frame
+pushes = []
+for t in range(T):
+    pushes.append((_lib.PUSH_FIRST if t % V == 0 else _lib.PUSH_NEXT, t))
+    if args.all_frames and fut and (t % V == V - 1 or t == T - 1):
+        pushes.append((_lib.PUSH_IDLE, t))
 
 # ---- the stream --------------------------------------------------------------------------------------------------------
 out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
-outputs = 0
-for t in range(T):
-    if t == args.warmup:
+outputs = timed = 0
+for i, (c, t) in enumerate(pushes):
+    if i == args.warmup:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         rt.timer_start()
-    _, valid = rt.video_push(frames[t], [_lib.PUSH_FIRST if t == 0 else _lib.PUSH_NEXT] * B, 12, "mosaic", out)
-    if t >= args.warmup:
+    _, valid = rt.video_push(frames[t], [c] * B, 12, "mosaic", out)
+    if i >= args.warmup:
         outputs += sum(valid)
+        timed += 1
 ms = rt.timer_stop_ms()
 t1 = time.perf_counter()
 rt.set_option("tvl1_async", 0)              # the deferred check of every flow batch above
-assert outputs == B * args.frames
-print(json.dumps(dict(common, mode="stream", fps=round(outputs / (ms * 1e-3), 2), ms_per_push=round(ms / args.frames, 3), **clock(t0, t1))))
+if V == T and not args.all_frames:
+    assert outputs == B * args.frames
+print(json.dumps(dict(common, mode="stream", all_frames=bool(args.all_frames), video_len=V, pushes=timed, outputs=outputs,
+                      fps=round(outputs / (ms * 1e-3), 2), ms_per_push=round(ms / timed, 3), **clock(t0, t1))))
 sys.stdout.flush()
+rt.set_option("stream_all_frames", 0)
 
 # ---- the same handle, flows at hand ----------------------------------------------------------------------------------------
 packed = torch.empty(T, B, 4, H // 2, W // 2, dtype=torch.float32, device=dev)
