@@ -272,6 +272,7 @@ int run_pre5(rvdd_t* h, const NetRun& run, const float* netin, float* part, hipS
 // gives back.  Kept because it is free and pins an invariant the tests use: a launch's batch size does not enter a
 // tile's sums, so both schedules give bit-identical frames.
 bool seq_major_on(const rvdd_t* h, int n) { return n > 1 && h->opt.seq_major == 1; }
+bool pre5_fused(const rvdd_t* h) { return !h->is_next() && h->has_feat() && h->opt.fuse_pre && h->opt.split16() && h->pre5_w; }
 
 int finalize_convunet(rvdd_t* h) {
     for (const auto& n : convunet_conv_names(h->has_feat())) {
@@ -342,14 +343,23 @@ int run_convunet(rvdd_t* h, NetRun& run, const float* netin, const float* featw,
     for (int k = 0; k < nsub; ++k) {
         const Sub sb = sub_at(k);
         if (run.in) RC(run_prologue(h, run, sb, s));
-        if (feat && h->opt.fuse_pre && h->opt.split16() && h->pre5_w) {
+        if (pre5_fused(h)) {
             // preprocessing_layer (:742, no activation) and the first source of EncoderConvs[0][0] (:743) as ONE 5x5 conv of the
             // network input (compose_pre_enc0), its border ring put right, then the second source (the old features) as before
             RC(run_pre5(h, run, netin, lv[0].part, s, sb));
-            ConvCall c;
-            c.in = featw; c.src = 1; c.acc_in = lv[0].part; c.out = lv[0].t[1]; c.H = lv[0].H; c.W = lv[0].W; c.epi = EPI_RELU;
-            c.amax_in = run.amax.feat_in; c.amax_out = L(CU_ENC0_0);
-            RC(run_conv(h, run, cu[CU_ENC0_0], c, s, sb));
+            if (run.zero_feat) {
+                // the first step of a video: the second source is all +0, its pass adds +0 to `part` and applies the ReLU
+                const size_t px0 = (size_t)sb.b0 * lv[0].H * lv[0].W;
+                const double px = (double)sb.nb * lv[0].H * lv[0].W;
+                Scope sc(h, s, "relu_part_kernel", 0.0, px * 384.0);
+                HIPCHK(h, launch_relu_part(lv[0].part + px0 * kF, lv[0].t[1] + px0 * kF, sb.nb, (int64_t)lv[0].H * lv[0].W * kF,
+                                           h->opt.bfp ? amax_words(h, L(CU_ENC0_0), sb.b0) : nullptr, s));
+            } else {
+                ConvCall c;
+                c.in = featw; c.src = 1; c.acc_in = lv[0].part; c.out = lv[0].t[1]; c.H = lv[0].H; c.W = lv[0].W; c.epi = EPI_RELU;
+                c.amax_in = run.amax.feat_in; c.amax_out = L(CU_ENC0_0);
+                RC(run_conv(h, run, cu[CU_ENC0_0], c, s, sb));
+            }
         } else if (feat) {
             RC(conv(CU_PRE, netin, AMAX_NETIN, lv[0].t[0], 0, EPI_NONE, sb));               // :742 (no activation)
             RC(conv2(CU_ENC0_0, lv[0].t[0], L(CU_PRE), featw, run.amax.feat_in, lv[0].t[1], 0, sb)); // cat[y, old_features] :743

@@ -58,15 +58,22 @@ __global__ void ha_green_kernel(const float* __restrict__ raw, float* __restrict
     Cfa c{raw + (size_t)b * rbs, h, w, H, W};
     green[idx] = ha_green_at<PH>(c, y, x);
 }
+// (`at`: the replicate-padded CFA as a function of the coordinates -- the frame in memory, or a copy of a tile of it in LDS)
+template <int PH, class At>
+__device__ __forceinline__ float ha_green_from(At at, int y, int x);
 template <int PH>
 __device__ __forceinline__ float ha_green_at(const Cfa& c, int y, int x) {
-    const float cc = c.at(y, x);
+    return ha_green_from<PH>([&](int yy, int xx) { return c.at(yy, xx); }, y, x);
+}
+template <int PH, class At>
+__device__ __forceinline__ float ha_green_from(At at, int y, int x) {
+    const float cc = at(y, x);
     float gval;
     if (((y ^ x ^ (PH >> 1) ^ PH) & 1) == 0) {      // y ^ x ^ py ^ px even: GBRG / GRBG's green diagonal, RGGB / BGGR's other one
         gval = cc;  // measured green
     } else {
-        const float l1 = c.at(y, x - 1), r1 = c.at(y, x + 1), l2 = c.at(y, x - 2), r2 = c.at(y, x + 2);
-        const float u1 = c.at(y - 1, x), d1 = c.at(y + 1, x), u2 = c.at(y - 2, x), d2 = c.at(y + 2, x);
+        const float l1 = at(y, x - 1), r1 = at(y, x + 1), l2 = at(y, x - 2), r2 = at(y, x + 2);
+        const float u1 = at(y - 1, x), d1 = at(y + 1, x), u2 = at(y - 2, x), d2 = at(y + 2, x);
         const float Kh = 0.5f * l1 + 0.5f * r1;
         const float Kv = 0.5f * u1 + 0.5f * d1;
         const float Dh = (l2 + (-2.f) * cc) + r2;
@@ -483,19 +490,32 @@ __global__ __launch_bounds__(256) void netin_bound_kernel(const float* __restric
 // 14.7 us of ~270).  A block owns a 16x16 tile: the green plane of the 18x18 pixels around it goes to LDS (ha_green_at at the
 // clamped coordinates, i.e. what the green kernel wrote and netin_kernel read back through a clamped index), then netin_pixel's
 // sequence per pixel with the ring's greens from LDS, then netin_bound_kernel's tail: every raw sample of the current frame is some
-// thread's own CFA sample.  Same operations on the same values: same bits as the three kernels.  Only where the launch is small: one
-// atomic per block on the amax words costs 100 us at 28 800 blocks (720p, round 4) -- launch_netin_small refuses above 1024 blocks.
+// thread's own CFA sample.  Same operations on the same values: same bits as the three kernels.  The tail only where the launch is
+// small: one atomic per block on the amax words costs 100 us at 28 800 blocks (720p, round 4).  Above 1024 blocks the bound stays in
+// netin_bound_kernel (14 us), which also keeps the housekeeping, and this kernel (words == nullptr) replaces ha_green_kernel and
+// netin_kernel: the green plane, written to memory and read back nine times per pixel through the address path that bounds
+// netin_kernel, stays in LDS.
 template <int PH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void netin_small_kernel(
     NetinArgs a, float* __restrict__ netin, const float* __restrict__ raw_prev, const unsigned* __restrict__ prev_words,
     unsigned* __restrict__ words, unsigned* __restrict__ zero_a, size_t zero_na, unsigned* __restrict__ zero_b, size_t zero_nb, int tiles_x,
-    unsigned long long latch) {
+    unsigned long long latch, int xcd_walk) {
+    __shared__ float cs[22][24];     // the replicate-padded CFA at (y0 - 3 + r, x0 - 3 + c): what the 18x18 greens and the rings read
     __shared__ float gs[18][20];
     __shared__ unsigned red[4];
     const int H = 2 * a.h, W = 2 * a.w;
-    const int b = blockIdx.y, t = threadIdx.x;
+    const int t = threadIdx.x;
+    // (sequence, tile) of this block.  xcd_walk (the large launches): workgroups go to the eight XCDs in turn in the order
+    // x, then y, of the grid; each XCD takes a contiguous eighth of the (sequence, tile) pairs, i.e. a band of tile rows, instead
+    // (xcd_contiguous_block for a two-dimensional grid)
+    unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
+    if (xcd_walk) {
+        const unsigned per = (gridDim.x * gridDim.y) >> 3;
+        if (lin < 8u * per) lin = (lin & 7u) * per + (lin >> 3);
+    }
+    const int b = (int)(lin / gridDim.x), tile = (int)(lin - (unsigned)b * gridDim.x);
     const bool lat = raw_prev && seq_latched(latch, b);      // netin_bound_kernel's choice of bound
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int y0 = ty * 16, x0 = tx * 16;
     {   // housekeeping for the step AFTER this one (netin_bound_kernel's)
         const size_t me = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + t, all = (size_t)gridDim.x * gridDim.y * 256;
@@ -503,28 +523,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         if (zero_b) for (size_t i = me; i < zero_nb; i += all) zero_b[i] = 0u;
     }
     Cfa c{a.raw_cur + (size_t)b * a.rbs, a.h, a.w, H, W};
-    for (int i = t; i < 18 * 18; i += 256) {
-        const int r = i / 18, cc = i - r * 18;
-        gs[r][cc] = ha_green_at<PH>(c, clampi(y0 - 1 + r, 0, H - 1), clampi(x0 - 1 + cc, 0, W - 1));
+    // Every CFA sample the tile needs, once: 22x22 loads per 256 pixels.  (Each green formed from memory -- up to nine loads --
+    // and each pixel's ring -- nine more -- went through the address path that bounds this kernel: 301 us against netin_kernel's
+    // 253 at 720p B = 8.)  The greens' stencils reach two samples beyond their 18x18 clamped positions, all inside the 22x22.
+    for (int i = t; i < 22 * 22; i += 256) {
+        const int r = i / 22, cc = i - r * 22;
+        cs[r][cc] = c.at(y0 - 3 + r, x0 - 3 + cc);
     }
     const int ly = t >> 4, lx = t & 15, y = y0 + ly, x = x0 + lx;
     const bool inside = y < H && x < W;
-    // flow vectors and the CFA ring while the greens are being formed
+    // flow vectors while the samples arrive
     FlowQ fq;
     Ring q;
     const bool warp_p = a.flow_prev != nullptr;
     const f32x4* sp = reinterpret_cast<const f32x4*>(a.prev4) + (size_t)b * H * W;
-    if (inside) {
-        if (warp_p) flow_fetch(a.flow_prev + (size_t)b * a.fbs, a.h, a.w, H, W, y, x, fq);
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const int yy = clampi(y + dy - 1, 0, H - 1), xx = clampi(x + dx - 1, 0, W - 1);
-                const int st = ((yy & 1) << 1) | (xx & 1);
-                q.site[dy][dx] = st ^ PH;
-                q.r[dy][dx] = c.raw[((size_t)st * c.h + (yy >> 1)) * c.w + (xx >> 1)];
-            }
+    if (inside && warp_p) flow_fetch(a.flow_prev + (size_t)b * a.fbs, a.h, a.w, H, W, y, x, fq);
+    __syncthreads();
+    const auto cfa = [&](int yy, int xx) { return cs[yy - (y0 - 3)][xx - (x0 - 3)]; };
+    for (int i = t; i < 18 * 18; i += 256) {
+        const int r = i / 18, cc = i - r * 18;
+        gs[r][cc] = ha_green_from<PH>(cfa, clampi(y0 - 1 + r, 0, H - 1), clampi(x0 - 1 + cc, 0, W - 1));
     }
     __syncthreads();
     float m = 0.f;
@@ -532,7 +550,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx) q.g[dy][dx] = gs[ly + dy][lx + dx];
+            for (int dx = 0; dx < 3; ++dx) {
+                const int yy = clampi(y + dy - 1, 0, H - 1), xx = clampi(x + dx - 1, 0, W - 1);
+                q.site[dy][dx] = (((yy & 1) << 1) | (xx & 1)) ^ PH;
+                q.r[dy][dx] = cfa(yy, xx);
+                q.g[dy][dx] = gs[ly + dy][lx + dx];
+            }
         Taps tp;
         f32x4 vt[16];
         f32x4 p;
@@ -558,10 +581,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     }
     if (words) {      // netin_bound_kernel's tail
         unsigned bits = __float_as_uint(m);
-        if (blockIdx.x == 0 && prev_words && !lat && t < kAmaxLines) bits = max(bits, prev_words[(size_t)b * kAmaxSeqWords + t * kAmaxLineWords]);
+        if (tile == 0 && prev_words && !lat && t < kAmaxLines) bits = max(bits, prev_words[(size_t)b * kAmaxSeqWords + t * kAmaxLineWords]);
         const unsigned e = (bits >> 23) & 0xffu;
         if (e >= 1 && e < 250) bits += 4u << 23;
-        amax_commit_block(words, b, blockIdx.x, __uint_as_float(bits), red);
+        amax_commit_block(words, b, tile, __uint_as_float(bits), red);
     }
 }
 
@@ -1102,10 +1125,14 @@ hipError_t launch_netin_bound(const float* raw_a, const float* raw_b, const floa
 
 // Can a frame-step of this size take the one-kernel pre-stage (netin_small_kernel)?  No future frame, at most 1024 tiles of 16x16.
 // enabled = false: never (option "small_prestage" 0: the three pre-stage kernels at every size, the A/B reference).
+constexpr long kNetinSmallTiles = 1024;
+static long netin_tiles(int B, int h, int w) { return (long)B * ((2 * h + 15) / 16) * ((2 * w + 15) / 16); }
 bool netin_small_applies(int B, int h, int w, bool future, bool enabled) {
-    const long tiles = (long)B * ((2 * h + 15) / 16) * ((2 * w + 15) / 16);
-    return enabled && !future && h >= 1 && w >= 1 && tiles <= 1024;
+    return netin_tiled_applies(h, w, future, enabled) && netin_tiles(B, h, w) <= kNetinSmallTiles;
 }
+// ... and the tiled kernel for the network input alone (words == nullptr, nothing to clear) at every size: the bound stays in
+// netin_bound_kernel above 1024 tiles, the green plane never goes to memory.
+bool netin_tiled_applies(int h, int w, bool future, bool enabled) { return enabled && !future && h >= 1 && w >= 1; }
 hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const float* prev4, const float* flow_prev, float* netin, int B,
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,
                               hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb, unsigned long long latch,
@@ -1114,8 +1141,11 @@ hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const
     const int tiles_x = (2 * w + 15) / 16, tiles_y = (2 * h + 15) / 16;
     const int64_t rbs = raw_bstride ? raw_bstride : (int64_t)4 * h * w, fbs = flow_bstride ? flow_bstride : (int64_t)2 * h * w;
     const NetinArgs a{raw_cur, nullptr, prev4, flow_prev, nullptr, nullptr, B, h, w, bayer, rbs, fbs};
+    const bool large = netin_tiles(B, h, w) > kNetinSmallTiles;
+    if (large && (words || zero_a || zero_b)) return hipErrorInvalidValue;      // one atomic per block: launch_netin_bound's work there
+    if ((long)tiles_x * tiles_y * B >= 0x100000000l) return hipErrorInvalidValue;
     RVDD_BAYER_DISPATCH(a.bayer, netin_small_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, s, a, netin, raw_prev, prev_words, words,
-                        zero_a, zero_na, zero_b, zero_nb, tiles_x, latch);
+                        zero_a, zero_na, zero_b, zero_nb, tiles_x, latch, large ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -1168,46 +1198,172 @@ hipError_t launch_amax_reduce(const float* map, int B, int64_t hw_c, unsigned* w
 // layer's output y as if it existed outside the image (b1 + partial windows of the zero-extended input); the reference pads it
 // with ZEROS (networks/unet.py:742-743, padding=1 on both convs).  For a border pixel p the composed sum therefore carries
 // sum over the taps d with q = p + d - 1 outside the image of W2[d] y~(q), y~(q) = b1 + sum over taps e with q + e - 1 inside of
-// W1[e] x(q + e - 1): subtracted here.  One 64-thread block per border pixel (2 W + 2 (H - 2) of them per sequence), thread = channel.
+// W1[e] x(q + e - 1): subtracted here.
 // netin NHWC16, w1 [9][16][48 m], w2 [9][48 m][48 o], part NHWC48.
-__global__ __launch_bounds__(64) void pre_border_fix_kernel(const float* __restrict__ netin, const float* __restrict__ w1,
+// One 256-thread block per RUN of up to 16 consecutive ring pixels of one side of one sequence (the top and bottom rows whole,
+// corners included; the left and right columns between them), wave = a share of the run, lane = channel.  (One 64-thread block
+// per ring pixel -- 32 000 of them at 720p B = 8 -- formed every outside y~(q) again in each of the up to three pixels that touch
+// it, one dependent round trip after another: 83 us per frame-step for 4 000 pixels per sequence.)  The run's outside positions
+// -- the 18 next to it in the row or column beyond the edge, and beside a corner the two in the column beyond the side edge --
+// are formed ONCE into LDS, each by the chain of the one-pixel kernel (b1, taps e ascending, channels c ascending); then every
+// pixel's corr by its chain (outside taps d ascending, m = 0..47) and the subtraction last: the same bits.  The four pixels of a
+// wave share each w2 row they need (a 192-B coalesced load) and run their chains side by side.
+constexpr int kFixRun = 16;                  // ring pixels per block
+constexpr int kFixSlots = kFixRun + 2 + 4;   // outside positions of a run: the line beyond the edge, two per corner
+__global__ __launch_bounds__(256) void pre_border_fix_kernel(const float* __restrict__ netin, const float* __restrict__ w1,
                                                             const float* __restrict__ b1, const float* __restrict__ w2,
                                                             float* __restrict__ part, int H, int W) {
-    __shared__ float ys[48];
-    const int b = blockIdx.y, t = threadIdx.x;
-    int i = blockIdx.x, py, px;
-    if (i < W) { py = 0; px = i; }
-    else if (i < 2 * W) { py = H - 1; px = i - W; }
-    else if (i < 2 * W + H - 2) { py = i - 2 * W + 1; px = 0; }
-    else { py = i - 2 * W - (H - 2) + 1; px = W - 1; }
-    const float* x = netin + (size_t)b * H * W * kNetInC;
-    float corr = 0.f;
-    for (int d = 0; d < 9; ++d) {
-        const int qy = py + d / 3 - 1, qx = px + d % 3 - 1;
-        if ((unsigned)qy < (unsigned)H && (unsigned)qx < (unsigned)W) continue;      // q inside: the composition is right
-        float y = 0.f;
-        if (t < 48) {
-            y = b1[t];
-            for (int e = 0; e < 9; ++e) {
-                const int ry = qy + e / 3 - 1, rx = qx + e % 3 - 1;
-                if ((unsigned)ry >= (unsigned)H || (unsigned)rx >= (unsigned)W) continue;
-                const float* xp = x + ((size_t)ry * W + rx) * kNetInC;
-                for (int c = 0; c < kNetInC; ++c) y = fmaf(w1[(e * kNetInC + c) * 48 + t], xp[c], y);
-            }
-            ys[t] = y;
-        }
-        __syncthreads();
-        if (t < 48)
-            for (int m = 0; m < 48; ++m) corr = fmaf(w2[((size_t)d * 48 + m) * 48 + t], ys[m], corr);
-        __syncthreads();
+    __shared__ float ys[kFixSlots][48];
+    const int b = blockIdx.y, t = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int nxr = (W + kFixRun - 1) / kFixRun, nyr = (H - 2 + kFixRun - 1) / kFixRun;
+    // the run: `horiz` along row py0 from column px0, else along column px0 from row py0; n pixels; (oy, ox) the line beyond the edge
+    int i = blockIdx.x, py0, px0, n;
+    const bool horiz = i < 2 * nxr;
+    if (horiz) {
+        py0 = i < nxr ? 0 : H - 1;
+        px0 = (i < nxr ? i : i - nxr) * kFixRun;
+        n = min(kFixRun, W - px0);
+    } else {
+        i -= 2 * nxr;
+        px0 = i < nyr ? 0 : W - 1;
+        py0 = 1 + (i < nyr ? i : i - nyr) * kFixRun;
+        n = min(kFixRun, H - 1 - py0);
     }
-    if (t < 48) part[((size_t)b * H * W + (size_t)py * W + px) * kF + t] -= corr;
+    const int oy = py0 == 0 ? -1 : H, ox = px0 == 0 ? -1 : W;      // (horiz: oy; else: ox)
+    const int iny = py0 == 0 ? 1 : H - 2;                          // horiz: the row next to the run's, towards the inside
+    const bool c_lo = horiz && px0 == 0, c_hi = horiz && px0 + n == W;
+    const float* x = netin + (size_t)b * H * W * kNetInC;
+    // ---- y~(q) of every outside position the run touches: slots 0 .. n + 1 along the line beyond the edge, kFixRun + 2 .. + 5
+    // the positions (py0, -1), (iny, -1), (py0, W), (iny, W) beside the corners
+#pragma unroll 1
+    for (int sl = g; sl < kFixSlots; sl += 4) {
+        int qy, qx;
+        if (sl < kFixRun + 2) {
+            if (sl > n + 1) continue;
+            qy = horiz ? oy : py0 - 1 + sl;
+            qx = horiz ? px0 - 1 + sl : ox;
+        } else {
+            const int k = sl - (kFixRun + 2);
+            if (!(k < 2 ? c_lo : c_hi)) continue;
+            qy = (k & 1) ? iny : py0;
+            qx = k < 2 ? -1 : W;
+        }
+        // the taps e whose pixel q + e - 1 lies inside: at most three (q is one step outside in a row or in a column), ascending;
+        // their loads all together, then the chain
+        int ek[3];
+        {
+            int e = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                while (e < 9 && ((unsigned)(qy + e / 3 - 1) >= (unsigned)H || (unsigned)(qx + e % 3 - 1) >= (unsigned)W)) ++e;
+                ek[k] = e;
+                e = e < 9 ? e + 1 : 9;
+            }
+        }
+        if (t < 48) {
+            float xv[3][kNetInC], wv[3][kNetInC];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (ek[k] >= 9) continue;
+                // (the same pixel for every lane: a scalar offset, the 16 channels from the scalar cache)
+                const int off = __builtin_amdgcn_readfirstlane(((qy + ek[k] / 3 - 1) * W + (qx + ek[k] % 3 - 1)) * kNetInC);
+#pragma unroll
+                for (int c = 0; c < kNetInC; ++c) xv[k][c] = x[off + c];
+#pragma unroll
+                for (int c = 0; c < kNetInC; ++c) wv[k][c] = w1[(ek[k] * kNetInC + c) * 48 + t];
+            }
+            float y = b1[t];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (ek[k] >= 9) continue;
+#pragma unroll
+                for (int c = 0; c < kNetInC; ++c) y = fmaf(wv[k][c], xv[k][c], y);
+            }
+            ys[sl][t] = y;
+        }
+    }
+    __syncthreads();
+    // ---- pixels 4 g .. 4 g + 3 of the run
+    if (t >= 48) return;
+    int py[4], px[4];
+    bool live[4];
+    float corr[4] = {0.f, 0.f, 0.f, 0.f}, pv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = 4 * g + k;
+        live[k] = j < n;
+        py[k] = horiz ? py0 : py0 + j;
+        px[k] = horiz ? px0 + j : px0;
+        pv[k] = live[k] ? part[((size_t)b * H * W + (size_t)py[k] * W + px[k]) * kF + t] : 0.f;      // (on its way under the chains)
+    }
+#pragma unroll 1
+    for (int d = 0; d < 9; ++d) {
+        int slot[4];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int qy = py[k] + d / 3 - 1, qx = px[k] + d % 3 - 1;
+            slot[k] = -1;
+            if (!live[k] || ((unsigned)qy < (unsigned)H && (unsigned)qx < (unsigned)W)) continue;      // q inside: the composition is right
+            if (!horiz) slot[k] = qy - (py0 - 1);
+            else if (qy == oy) slot[k] = qx - (px0 - 1);
+            else slot[k] = kFixRun + 2 + (qx < 0 ? 0 : 2) + (qy == py0 ? 0 : 1);
+            any = true;
+        }
+        if (!any) continue;
+        const float* wd = w2 + (size_t)d * 48 * 48 + t;
+        float wv[48];
+#pragma unroll
+        for (int m = 0; m < 48; ++m) wv[m] = wd[m * 48];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (slot[k] < 0) continue;
+#pragma unroll
+            for (int m = 0; m < 48; ++m) corr[k] = fmaf(wv[m], ys[slot[k]][m], corr[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (live[k]) part[((size_t)b * H * W + (size_t)py[k] * W + px[k]) * kF + t] = pv[k] - corr[k];
 }
 
 hipError_t launch_pre_border_fix(const float* netin, const float* w1, const float* b1, const float* w2, float* part, int B, int H, int W,
                                  hipStream_t s) {
     if (B <= 0 || H < 2 || W < 2) return hipSuccess;
-    hipLaunchKernelGGL(pre_border_fix_kernel, dim3(2 * W + 2 * (H - 2), B), dim3(64), 0, s, netin, w1, b1, w2, part, H, W);
+    const int nxr = (W + kFixRun - 1) / kFixRun, nyr = (H - 2 + kFixRun - 1) / kFixRun;
+    hipLaunchKernelGGL(pre_border_fix_kernel, dim3(2 * nxr + 2 * nyr, B), dim3(256), 0, s, netin, w1, b1, w2, part, H, W);
+    return hipGetLastError();
+}
+
+// The second pass of EncoderConvs[0][0] on the first step of a video.  Its source, the warped recurrent features, is all +0
+// there (a bicubic gather of +0 sums +0 products from +0), so the pass of conv3x3h_kernel<48, EPI_RELU, ACC_IN> computes
+// fma(acc, ws, part) with acc = +0 (an MFMA chain from +0 over +-0 products) and ws finite: part + 0 -- which is part, with -0
+// made +0 -- then its one-instruction ReLU, and commits max |out| per sequence to the layer's amax words (every reader takes the
+// maximum over a sequence's lines: which line a workgroup's maximum lands on is free).  The same here without the 1.4 GB of
+// zeros read: 16-B loads and stores, grid (blocks, B), grid-stride inside a sequence.
+__global__ __launch_bounds__(256) void relu_part_kernel(const float* __restrict__ part, float* __restrict__ out, int64_t n4,
+                                                        unsigned* __restrict__ words) {
+    __shared__ unsigned red[4];
+    const int b = blockIdx.y;
+    const f32x4* p = reinterpret_cast<const f32x4*>(part) + (size_t)b * n4;
+    f32x4* o = reinterpret_cast<f32x4*>(out) + (size_t)b * n4;
+    float m = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        f32x4 x = p[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = __builtin_amdgcn_fmed3f(x[e] + 0.0f, 0.f, __builtin_inff());
+        o[i] = x;
+        m = fmaxf(fmaxf(m, fmaxf(fabsf(x[0]), fabsf(x[1]))), fmaxf(fabsf(x[2]), fabsf(x[3])));
+    }
+    if (words) amax_commit_block(words, b, blockIdx.x, m, red);
+}
+
+hipError_t launch_relu_part(const float* part, float* out, int B, int64_t n, unsigned* words, hipStream_t s) {
+    if (B <= 0 || n <= 0) return hipSuccess;
+    if (n & 3) return hipErrorInvalidValue;
+    int64_t nblk = (n / 4 + 256 * 4 - 1) / (256 * 4);        // four 16-B loads and stores per thread, at most 2048 blocks per sequence
+    nblk = nblk < 1 ? 1 : (nblk > 2048 ? 2048 : nblk);
+    hipLaunchKernelGGL(relu_part_kernel, dim3((unsigned)nblk, B), dim3(256), 0, s, part, out, n / 4, words);
     return hipGetLastError();
 }
 

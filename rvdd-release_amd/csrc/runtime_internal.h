@@ -323,6 +323,8 @@ struct NetRun {
     bool zero_pending = false;        // the first network-input launch zeroes the set and features slot of the step after (run_prologue)
     bool netin_proj = false;          // lv[0].t[0] already holds the first ConvBlock's projection of the network input (run_prologue)
     bool featw_proj = false;          // `featw` holds W_f warp(features) + bias (run_prologue, next_pf_pre), not the warped features
+    bool zero_feat = false;           // the first step of a video for every sequence, composed first layer: the recurrent features are
+                                      // zero, nobody warps or convolves them (enqueue_step, run_convunet) -- `featw` is not written
     const StepInputs* in = nullptr;   // what a frame-step does in front of the net (run_prologue); null for rvdd_unet_forward
 };
 inline int amax_layer(const NetRun& run, int layer) { return run.amax.base + layer; }
@@ -405,6 +407,7 @@ int next_proj_cin(const rvdd_t* h, const std::string& blk);
 // ---- net_convunet.hip
 int finalize_convunet(rvdd_t* h);
 bool seq_major_on(const rvdd_t* h, int n);
+bool pre5_fused(const rvdd_t* h);      // EncoderConvs[0][0]'s first source runs as the composed 5x5 conv of the network input
 int run_convunet(rvdd_t* h, NetRun& run, const float* netin, const float* featw, float* feat_dst, float* out_nchw, float* out_nhwc4,
                  hipStream_t s);
 // ---- net_convnext.hip

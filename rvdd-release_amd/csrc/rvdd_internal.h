@@ -204,6 +204,9 @@ hipError_t launch_conv5x5h_c8(const ConvArgs& a, hipStream_t s);
 size_t conv5x5h_weight_bytes(int cin);      // cin = 8 or 16: the channels multiplied
 hipError_t launch_pre_border_fix(const float* netin, const float* w1, const float* b1, const float* w2, float* part, int B, int H, int W,
                                  hipStream_t s);
+// What the second pass of a two-source conv (ACC_IN, EPI_RELU) leaves when its source map is all +0: out = relu(part + 0), and
+// the amax words of `out` (nullable) per sequence; n = floats per sequence (a multiple of 4), part / out 16-B aligned
+hipError_t launch_relu_part(const float* part, float* out, int B, int64_t n, unsigned* words, hipStream_t s);
 void conv3x3h_set_groups(int g);   // stand-alone harness (-DRVDD_CONV_GROUPS2): 2 = two groups of four waves with an 8x16 tile each
 
 // -------------------------------------------------------------- pre-stages --
@@ -238,6 +241,9 @@ hipError_t launch_netin_bound(const float* raw_a, const float* raw_b, const floa
 // the three pre-stage kernels of a small frame-step without a future frame in one launch (prestage.hip netin_small_kernel); same bits
 // (enabled = false: never -- option "small_prestage" 0)
 bool netin_small_applies(int B, int h, int w, bool future, bool enabled = true);
+// ... at most 1024 tiles of 16x16.  Above that the same kernel forms the network input alone (words, zero_a, zero_b null: the
+// bound and the clearing stay with launch_netin_bound) -- no green plane in memory; any size without a future frame
+bool netin_tiled_applies(int h, int w, bool future, bool enabled = true);
 // (raw_prev: the first step of a video, whose bound also covers the previous raw frame -- prev_words is null then)
 hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const float* prev4, const float* flow_prev, float* netin, int B,
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,

@@ -79,6 +79,8 @@ int prologue_netin(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
                                          zero_now ? zero_a : nullptr, zero_na, zero_now ? zero_b : nullptr, zero_nb, latch, h->opt.bayer));
             return RVDD_OK;
         }
+        // larger ones: the bound (and the zeroing) in its own small launch, the green plane and the network input tiled
+        const bool tiled = !h->is_next() && !h->opt.prev_noisy && netin_tiled_applies(H / 2, W / 2, h->cfg.future != 0, h->opt.small_prestage);
         if (amax_netin) {
             // (block floating point) a bound of max |netin| from the raw frames and from the words PostConvs wrote last step;
             // with --prev_noisy_frame the "previous output" is a demosaicked frame whose raw data is gone: its own maximum
@@ -95,6 +97,11 @@ int prologue_netin(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
         // ConvNeXtUnet: the input's only reader is the 1x1 projection of the first ConvBlock, which rides in the same kernel
         const NextBlk* first = h->is_next() && h->opt.next_projfuse ? &h->nx[h->has_feat() ? NX_PRE : NX_ENC0_0] : nullptr;
         run.netin_proj = first != nullptr;
+        if (tiled) {
+            HIPCHK(h, launch_netin_small(rc_, nullptr, h->lastden4 + o * img * 4, fp_, netin, n, H / 2, W / 2, (int64_t)in.rawf, (int64_t)in.flowf,
+                                         nullptr, nullptr, s, nullptr, 0, nullptr, 0, latch, h->opt.bayer));
+            return RVDD_OK;
+        }
         HIPCHK(h, launch_netin(rc_, green, h->lastden4 + o * img * 4, fp_, next4, fn_, netin, n, H / 2, W / 2, s, (int64_t)in.rawf,
                                (int64_t)in.flowf, first ? first->w.proj_w : nullptr, first ? first->w.proj_b : nullptr,
                                first ? h->lv[0].t[0] + o * img * kF : nullptr, h->opt.bayer));
@@ -104,7 +111,7 @@ int prologue_netin(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
 
 // The feature warp of the same sequences (feature recurrence, unless --no_warp)
 int prologue_features(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s) {
-    if (!h->has_feat() || h->opt.no_warp) return RVDD_OK;
+    if (!h->has_feat() || h->opt.no_warp || run.zero_feat) return RVDD_OK;
     const int H = h->cfg.height, W = h->cfg.width, n = sb.nb;
     const size_t img = (size_t)H * W, o = (size_t)sb.b0;
     const StepInputs& in = *run.in;
@@ -153,6 +160,10 @@ int enqueue_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
     run.n = B;
     run.amax = step_amax(h->step_ctr);
     run.in = &in;
+    // every covered slot starts a video and the first layer is the composed one: the features are zero, and instead of a map of
+    // zeros written, warped and convolved (a memset of 1.4 GB at 720p B = 8, warp48_kernel over it, the second pass of
+    // EncoderConvs[0][0] over the result: +0 added to every partial sum) run_convunet applies the layer's ReLU to the partial sums
+    run.zero_feat = init && !nw && pre5_fused(h);
     // amax words: everything but the recurrent features' words this step reads (zero features at the start of a video: zero words)
     if (h->amax_on()) {
         // the first step of a video starts from zero features: zero words; later steps find their set zeroed by the step before
@@ -164,7 +175,8 @@ int enqueue_step(rvdd_t* h, const StepPlan& p, hipStream_t s) {
         // (models/recurrent_model.py:233-245)
         HIPCHK(h, launch_demosaic(raw_prev, h->green, h->lastden4, B, H / 2, W / 2, (int64_t)H * W * 4, 4, 1, s, (int64_t)in.rawf,
                                   h->opt.bayer));
-        if (h->has_feat()) HIPCHK(h, hipMemsetAsync(h->lastfeat, 0, npix * kF * sizeof(float), s));
+        // (zero_feat: the features have no reader in this step, and PostConvs[0] writes the whole map at its end)
+        if (h->has_feat() && !run.zero_feat) HIPCHK(h, hipMemsetAsync(h->lastfeat, 0, npix * kF * sizeof(float), s));
     } else if (pend) {
         // some sequences start a video (rvdd_reset_slots): the same latch for them alone -- the demosaic over each run of
         // them, then ONE launch that zeroes their features and their words in every set (the rotation of the sets by step_ctr
