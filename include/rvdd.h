@@ -311,6 +311,46 @@ int rvdd_egress(rvdd_t* h, const float* rgb /* [n,3,H,W] in [-1,1] */, int32_t n
                 int32_t bit_depth, int32_t pattern /* enum rvdd_bayer; ignored for RGB_HWC */,
                 void* out, void* stream);
 
+/* Frames of packed 10 / 12 / 14-bit samples, as a sensor or a raw recorder leaves them: a mosaic plane [n,2hh,2ww] whose rows are
+ * bit-packed.  Rows are tight and frames are tight -- frame i starts at byte i * 2hh * row_bytes -- and nothing is assumed about
+ * alignment; row_bytes may be odd.  With b = bit_depth:
+ *   RVDD_BITS_MIPI  MIPI CSI-2 RAW10 / RAW12 / RAW14.  Pixels in groups of G = 4 (b = 10, 14) or 2 (b = 12): G bytes P_k >> (b - 8),
+ *                   then G (b - 8) / 8 bytes holding L = sum_k (P_k & (2^(b-8) - 1)) << (k (b - 8)), least significant byte first.
+ *                   row_bytes = 2ww b / 8.  2ww must be a multiple of G: ww even for b = 10 and 14.
+ *   RVDD_BITS_MSB   TIFF 6.0 with FillOrder 1 / uncompressed DNG.  A row is its samples, b bits each with the most significant bit
+ *                   first, as one bit string cut into bytes most significant bit first and zero-padded to a whole byte:
+ *                   row_bytes = ceil(2ww b / 8).  Any ww.
+ *   e.g. b = 10, pixels 3FF 000 155 2AA: MIPI FF 00 55 AA 93, MSB FF C0 05 56 AA;  b = 12, pixels ABC 123: MIPI AB 12 3C, MSB AB C1 23. */
+enum rvdd_bits_order { RVDD_BITS_MIPI = 0, RVDD_BITS_MSB = 1 };
+
+/* rvdd_ingest_raw(RVDD_RAW_U16, RVDD_RAW_MOSAIC, bit_depth) of the frames those bytes hold, in one kernel: `packed` and `gray` are
+ * bit for bit what it writes for the unpacked uint16 frames, and no unpacked plane ever exists in memory.  Pad bits (MSB, odd ww)
+ * are not read as data, and no byte beyond n * 2hh * row_bytes is read.  Either output may be NULL.
+ * order outside 0..1, bit_depth other than 10 / 12 / 14, hh or ww < 1, an odd ww with MIPI at 10 / 14 bits, n < 0, NULL frames with
+ * n > 0, a launch of more than 2^31 - 1 blocks: RVDD_ERR_ARG (the message names the argument) and nothing is launched.  n = 0 does
+ * nothing.  Asynchronous and stream-ordered; nothing is read back.
+ * With ww % 8 == 0, `frames` 4-byte aligned and the outputs 16-byte aligned a thread owns 16 pixels of both sensor rows of a
+ * cell row -- 20 / 24 / 28 bytes per row, read as dwords, 16-byte stores; every other case moves single bytes, two cells per
+ * thread.  Same bits either way. */
+int rvdd_ingest_bits(rvdd_t* h, const uint8_t* frames, int32_t order /* enum rvdd_bits_order */, int32_t n, int32_t hh, int32_t ww,
+                     int32_t bit_depth, float* packed /* [n,4,hh,ww], nullable */, float* gray /* [n,hh,ww], nullable */,
+                     void* stream);
+
+/* rvdd_egress(RVDD_OUT_MOSAIC, RVDD_RAW_U16, bit_depth, pattern) written as packed bits: the samples are exactly the uint16 values it
+ * writes (the same rint and clamp, NaN -> 0, -inf -> 0, +inf -> 2^bit_depth - 1), packed in `order`, pad bits zero.  Every byte of
+ * out[0 .. n * H * row_bytes) is written -- row_bytes of W samples, as above -- and nothing outside it.
+ * The round trip: for frames with values in 0 .. 2^bit_depth - 1, rvdd_ingest_bits -> rvdd_demosaic_ha_bayer(pattern) ->
+ * rvdd_egress_bits(the same order, bit_depth and pattern) returns the input bytes exactly (the uint16 round trip of rvdd_egress;
+ * for MSB frames with zero pad bits).
+ * order outside 0..1, bit_depth other than 10 / 12 / 14, H or W odd or < 2, W / 2 odd with MIPI at 10 / 14 bits (the message names
+ * ww = W / 2), pattern outside 0..3, n < 0, NULL rgb / out with n > 0, a launch of more than 2^31 - 1 blocks: RVDD_ERR_ARG (the message
+ * names the argument) and nothing is launched.  n = 0 does nothing.  Asynchronous and stream-ordered; nothing is read back.
+ * With W % 16 == 0, `rgb` 16-byte and `out` 4-byte aligned a thread owns 16 pixels of both sensor rows (16-byte loads, dword
+ * stores); every other case stores single bytes, two cells per thread.  Same bits either way. */
+int rvdd_egress_bits(rvdd_t* h, const float* rgb /* [n,3,H,W] in [-1,1] */, int32_t n, int32_t H, int32_t W,
+                     int32_t order /* enum rvdd_bits_order */, int32_t bit_depth, int32_t pattern /* enum rvdd_bayer */,
+                     uint8_t* out /* [n,H,row_bytes] */, void* stream);
+
 enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
 
 /* The stream: one call hands every batch slot its next sensor frame (`frames`: cfg.batch frames of H/2 x W/2 cells, one
@@ -523,6 +563,13 @@ int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, 
  *               frame the last one on an IDLE pushed straight after it (next frame = itself, zero flow towards it); the contract is
  *               with rvdd_video_push.  Every other output keeps its bits.  Default 0: exactly the launches of a push without it, and
  *               nothing more allocated.  Acts on rvdd_video_push only.  Per handle.
+ *   "stream_container": 1 / 2 = the `frames` of rvdd_video_push are packed bits in RVDD_BITS_MIPI / RVDD_BITS_MSB (the value is the
+ *               enum rvdd_bits_order plus one): slot b's frame is the H * row_bytes bytes at byte b * H * row_bytes, read by
+ *               rvdd_ingest_bits' kernel instead of rvdd_ingest_raw's; an IDLE slot's slice is not read.  The push must then say
+ *               dtype RVDD_RAW_U16 (the samples' type), layout RVDD_RAW_MOSAIC and bit_depth 10 / 12 / 14, and MIPI at 10 / 14 bits
+ *               needs an even W / 2: RVDD_ERR_ARG otherwise, and nothing is changed.  out_rgb and valid are bit for bit those of
+ *               the same pushes with the unpacked uint16 frames, under every other stream option.  Default 0: exactly the
+ *               launches of a push without it.  Any other value than 0..2 is RVDD_ERR_ARG.  Acts on rvdd_video_push only.  Per handle.
  * Every option belongs to the handle it is set on: no option changes what another handle of the process does.
  * Unknown names are an error. */
 int rvdd_set_option(rvdd_t* h, const char* name, int32_t value);

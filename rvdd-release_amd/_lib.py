@@ -20,6 +20,8 @@ RAW_MOSAIC, RAW_PACKED_HWC = 0, 1
 PUSH_NEXT, PUSH_FIRST, PUSH_IDLE = 0, 1, 2
 # enum rvdd_out_layout (rvdd_egress)
 OUT_RGB_HWC, OUT_MOSAIC, OUT_PACKED_HWC = 0, 1, 2
+# enum rvdd_bits_order (rvdd_ingest_bits, rvdd_egress_bits; option "stream_container" is the value plus one)
+BITS_MIPI, BITS_MSB = 0, 1
 PPIPE_FROM_NET = -1      # RVDD_PPIPE_FROM_NET: rvdd_ppipe's bit_depth for a network output in [-1,1]
 
 
@@ -59,6 +61,8 @@ _PROTOS = {
     "rvdd_ingest_raw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "rvdd_gray_of_rgb": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_egress": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rvdd_ingest_bits": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "rvdd_egress_bits": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                  _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),

@@ -99,7 +99,9 @@ int opt_conv_kernel(rvdd_t* h, int32_t value) {
       "rvdd_set_option: bayer_pattern must be 0 (GBRG), 1 (GRBG), 2 (RGGB) or 3 (BGGR)", nullptr)                                \
     X("stream_reset_each", nullptr, stream_reset_each, 0, 1, nullptr, nullptr)                                                   \
     X("stream_flow_from_denoised", nullptr, stream_flow_from_denoised, 0, 1, nullptr, nullptr)                                   \
-    X("stream_all_frames", nullptr, stream_all_frames, 0, 1, nullptr, nullptr)
+    X("stream_all_frames", nullptr, stream_all_frames, 0, 1, nullptr, nullptr)                                                   \
+    X("stream_container", nullptr, stream_container, 0, 2,                                                                       \
+      "rvdd_set_option: stream_container must be 0 (one number per sample), 1 (MIPI CSI-2) or 2 (MSB first)", nullptr)
 struct OptRow {
     const char* name;
     const char* env;

@@ -1,5 +1,6 @@
 // Sensor frames -> the inputs of a frame-step (packed raw in [-1, 1]) and of TV-L1 (gray plane in DN), the same gray plane of
-// an output frame's re-mosaic (rvdd_gray_of_rgb), the way back -- an output frame as sensor frames (rvdd_egress) -- and the
+// an output frame's re-mosaic (rvdd_gray_of_rgb), the way back -- an output frame as sensor frames (rvdd_egress) --, both
+// directions on frames of bit-packed 10 / 12 / 14-bit samples (rvdd_ingest_bits, rvdd_egress_bits), and the
 // small copy kernels rvdd_video_push composes its flow batch and its substituted frames with.  Compiled -ffp-contract=off: every operation below is rounded
 // to f32 on its own, which is what makes the outputs the bits of the reference's loader (library.py load_image + the
 // dataset's transform) and of library._gray on integer-valued frames.
@@ -311,6 +312,236 @@ hipError_t launch_egress_l(const float* rgb, int n, int H, int W, int cols, floa
                       : launch_egress_t<LAYOUT>(rgb, n, H, W, cols, top, static_cast<float*>(out), wide, blocks, s);
 }
 
+// ---- rvdd_ingest_bits / rvdd_egress_bits: the same two directions on frames of packed 10 / 12 / 14-bit samples ----------------
+// ORDER 0 (RVDD_BITS_MIPI, CSI-2 RAW10 / RAW12 / RAW14): groups of G = 4 (2 at 12 bits) pixels, G bytes of the samples' upper
+// eight bits, then G (b - 8) / 8 bytes of their lower bits, pixel 0's lowest.  ORDER 1 (RVDD_BITS_MSB, TIFF FillOrder 1): the
+// samples b bits each, most significant bit first, as one bit string per row.  In both, 4 pixels are b / 2 whole bytes (5 / 6 / 7)
+// and 16 pixels 2 b bytes (20 / 24 / 28), a whole number of dwords.
+// A thread takes NC cells of a cell row: from each of the two sensor rows it holds the NC * 2 * b / 8 bytes of its 2 NC pixels as
+// a WINDOW of dwords in registers, byte i at bits 8 (i & 3) of word i >> 2 -- the little-endian image of the bytes.  The
+// general form (NC = 2) moves the window byte by byte and touches no byte at or beyond row_bytes (an odd ww ends a row inside
+// the last window: the missing samples are not written on the way in and are zero -- the pad bits -- on the way out); the fast
+// form (NC = 8, ww % 8 == 0, rows on dword boundaries) moves it as 5 / 6 / 7 dwords, so a wave reads or writes one run of 1280 /
+// 1536 / 1792 bytes per sensor row.  Between window and samples both forms run the same code with every index a constant after
+// unrolling (registers only: no LDS, no scratch); the per-sample arithmetic is ingest_raw_kernel's and egress_kernel's own.
+template <int NW>
+__device__ __forceinline__ unsigned window_byte(const unsigned (&w)[NW], int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
+
+// sample j of the window, j = 0 .. NS - 1
+template <int BITS, int ORDER, int NS, int NW>
+__device__ __forceinline__ void unpack_window(const unsigned (&w)[NW], unsigned (&s)[NS]) {
+    constexpr int LOW = BITS - 8;
+    if constexpr (ORDER == 0) {
+        constexpr int G = BITS == 12 ? 2 : 4, GB = G * BITS / 8;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int base = (j / G) * GB, k = j % G;
+            const int q = 8 * (base + G) + k * LOW;      // where the sample's lower bits start, counted in the little-endian window
+            unsigned lo = w[q >> 5] >> (q & 31);
+            if ((q & 31) + LOW > 32) lo |= w[(q >> 5) + 1] << (32 - (q & 31));
+            s[j] = (window_byte(w, base + k) << LOW) | (lo & ((1u << LOW) - 1u));
+        }
+    } else {
+        unsigned m[NW];                                  // the same bytes as big-endian words: bit q of the row's string is bit 31 - (q & 31)
+#pragma unroll
+        for (int i = 0; i < NW; ++i) m[i] = __builtin_bswap32(w[i]);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int q = j * BITS, sh = q & 31;
+            unsigned v = m[q >> 5] << sh;
+            if (sh + BITS > 32) v |= m[(q >> 5) + 1] >> (32 - sh);
+            s[j] = v >> (32 - BITS);
+        }
+    }
+}
+
+// the window of NS samples (each < 2^BITS); every bit no sample owns is zero
+template <int BITS, int ORDER, int NS, int NW>
+__device__ __forceinline__ void pack_window(const unsigned (&s)[NS], unsigned (&w)[NW]) {
+    constexpr int LOW = BITS - 8;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = 0u;
+    if constexpr (ORDER == 0) {
+        constexpr int G = BITS == 12 ? 2 : 4, GB = G * BITS / 8;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int base = (j / G) * GB, k = j % G;
+            const int q = 8 * (base + G) + k * LOW;
+            const unsigned lo = s[j] & ((1u << LOW) - 1u);
+            w[(base + k) >> 2] |= (s[j] >> LOW) << (8 * ((base + k) & 3));
+            w[q >> 5] |= lo << (q & 31);
+            if ((q & 31) + LOW > 32) w[(q >> 5) + 1] |= lo >> (32 - (q & 31));
+        }
+    } else {
+        unsigned m[NW];
+#pragma unroll
+        for (int i = 0; i < NW; ++i) m[i] = 0u;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int q = j * BITS, sh = q & 31;
+            if (sh + BITS <= 32) {
+                m[q >> 5] |= s[j] << (32 - sh - BITS);
+            } else {
+                m[q >> 5] |= s[j] >> (sh + BITS - 32);
+                m[(q >> 5) + 1] |= s[j] << (64 - sh - BITS);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NW; ++i) w[i] = __builtin_bswap32(m[i]);
+    }
+}
+
+template <int BITS, bool FAST>
+struct BitsWindow {
+    static constexpr int NC = FAST ? 8 : 2;              // cells per thread
+    static constexpr int NS = 2 * NC;                    // samples of one sensor row
+    static constexpr int NB = NS * BITS / 8;             // their bytes
+    static constexpr int NW = (NB + 3) / 4;              // the window's dwords
+};
+
+template <int BITS, int ORDER, bool FAST>
+__global__ void __launch_bounds__(256) ingest_bits_kernel(const uint8_t* __restrict__ frames, float* __restrict__ packed,
+                                                          float* __restrict__ gray, int n, int hh, int ww, int64_t row_bytes, float maxv) {
+    typedef BitsWindow<BITS, FAST> Wn;
+    constexpr int NC = Wn::NC, NS = Wn::NS, NB = Wn::NB, NW = Wn::NW;
+    const int64_t hw = (int64_t)hh * ww;
+    const int wq = (ww + NC - 1) / NC;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)n * hh * wq) return;
+    const int xq = (int)(t % wq);
+    const int64_t row = t / wq;                          // img * hh + y
+    const int y = (int)(row % hh);
+    const int64_t img = row / hh;
+    const int64_t at = (int64_t)xq * NB;                 // the window's first byte in its row
+    const uint8_t* r0 = frames + (img * 2 * hh + 2 * (int64_t)y) * row_bytes + at;
+    const int left = (int)(row_bytes - at < NB ? row_bytes - at : NB);      // the window's bytes that lie in the row
+    unsigned s[2][NS];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const uint8_t* p = r0 + r * row_bytes;
+        unsigned w[NW];
+        if constexpr (FAST) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) w[i] = reinterpret_cast<const unsigned*>(p)[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) w[i] = 0u;
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+                if (i < left) w[i >> 2] |= (unsigned)p[i] << (8 * (i & 3));
+        }
+        unpack_window<BITS, ORDER>(w, s[r]);
+    }
+    float c[NC][4];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        c[i][0] = (float)s[0][2 * i]; c[i][1] = (float)s[0][2 * i + 1];
+        c[i][2] = (float)s[1][2 * i]; c[i][3] = (float)s[1][2 * i + 1];
+    }
+    const int x = NC * xq;
+    const int64_t o = (int64_t)y * ww + x;
+    if constexpr (FAST) {
+        if (packed) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int j = 0; j < NC / 4; ++j) {
+                    f32x4 v;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = norm_dn(c[4 * j + i][k], maxv);
+                    *reinterpret_cast<f32x4*>(packed + (img * 4 + k) * hw + o + 4 * j) = v;
+                }
+        }
+        if (gray) {
+#pragma unroll
+            for (int j = 0; j < NC / 4; ++j) {
+                f32x4 g;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) g[i] = gray_dn(c[4 * j + i]);
+                *reinterpret_cast<f32x4*>(gray + img * hw + o + 4 * j) = g;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            if (x + i >= ww) break;                      // an odd ww: the row ends inside this window
+            if (packed) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) packed[(img * 4 + k) * hw + o + i] = norm_dn(c[i][k], maxv);
+            }
+            if (gray) gray[img * hw + o + i] = gray_dn(c[i]);
+        }
+    }
+}
+
+template <int BITS, int ORDER, bool FAST>
+__global__ void __launch_bounds__(256) egress_bits_kernel(const float* __restrict__ rgb, uint8_t* __restrict__ out, int n, int H, int W,
+                                                          int64_t row_bytes, int cols, float top) {
+    typedef BitsWindow<BITS, FAST> Wn;
+    constexpr int NC = Wn::NC, NS = Wn::NS, NB = Wn::NB, NW = Wn::NW;
+    const int64_t HW = (int64_t)H * W;
+    const int hh = H >> 1, ww = W >> 1, wq = (ww + NC - 1) / NC;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)n * hh * wq) return;
+    const int xq = (int)(t % wq);
+    const int x = NC * xq;
+    const int64_t row = t / wq;                          // img * hh + y
+    const int y = (int)(row % hh);
+    const int64_t img = row / hh;
+    unsigned s[2][NS];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float* p = rgb + (img * 3 + ((cols >> (2 * k)) & 3)) * HW + (2 * (int64_t)y + (k >> 1)) * W + 2 * x + (k & 1);
+        if constexpr (FAST) {
+            const float* a = p - (k & 1);                // the 16-B aligned run of sixteen pixels; position k takes its even / odd ones
+#pragma unroll
+            for (int j = 0; j < NC / 2; ++j) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(a + 4 * j);
+                s[k >> 1][4 * j + (k & 1)] = out_of<unsigned short>(dn_of(v[k & 1], top), top);
+                s[k >> 1][4 * j + 2 + (k & 1)] = out_of<unsigned short>(dn_of(v[2 + (k & 1)], top), top);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) s[k >> 1][2 * i + (k & 1)] = x + i < ww ? out_of<unsigned short>(dn_of(p[2 * i], top), top) : 0u;
+        }
+    }
+    const int64_t at = (int64_t)xq * NB;
+    uint8_t* r0 = out + (img * H + 2 * (int64_t)y) * row_bytes + at;
+    const int left = (int)(row_bytes - at < NB ? row_bytes - at : NB);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        uint8_t* p = r0 + r * row_bytes;
+        unsigned w[NW];
+        pack_window<BITS, ORDER>(s[r], w);
+        if constexpr (FAST) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) reinterpret_cast<unsigned*>(p)[i] = w[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+                if (i < left) p[i] = (uint8_t)window_byte(w, i);
+        }
+    }
+}
+
+// one launch of kernel K<BITS, ORDER, FAST> chosen by the run-time (bit_depth, order, fast); bit_depth is 10, 12 or 14
+#define BITS_DISPATCH(K, bits, order, fast, ...)                                                      \
+    do {                                                                                              \
+        if (bits == 10) BITS_DISPATCH_O(K, 10, order, fast, __VA_ARGS__);                             \
+        else if (bits == 12) BITS_DISPATCH_O(K, 12, order, fast, __VA_ARGS__);                        \
+        else BITS_DISPATCH_O(K, 14, order, fast, __VA_ARGS__);                                        \
+    } while (0)
+#define BITS_DISPATCH_O(K, B, order, fast, ...)                                                       \
+    do {                                                                                              \
+        if (order == 0) BITS_DISPATCH_F(K, B, 0, fast, __VA_ARGS__);                                  \
+        else BITS_DISPATCH_F(K, B, 1, fast, __VA_ARGS__);                                             \
+    } while (0)
+#define BITS_DISPATCH_F(K, B, O, fast, ...)                                                           \
+    do {                                                                                              \
+        if (fast) hipLaunchKernelGGL((K<B, O, true>), dim3((unsigned)blocks), dim3(256), 0, s, __VA_ARGS__);  \
+        else hipLaunchKernelGGL((K<B, O, false>), dim3((unsigned)blocks), dim3(256), 0, s, __VA_ARGS__);      \
+    } while (0)
+
 // ---- rvdd_video_push: the flow batch's operands and results, and the substituted frames of the ring ------------------------
 // One byte per entry, handed to the kernel by value (B <= 64 slots, two directions)
 struct SlotList {
@@ -432,6 +663,50 @@ hipError_t launch_egress(const float* rgb, int n, int H, int W, int layout, int 
     return layout == 0   ? launch_egress_l<0>(rgb, n, H, W, cols, top, dtype, out, wide, blocks, s)
            : layout == 1 ? launch_egress_l<1>(rgb, n, H, W, cols, top, dtype, out, wide, blocks, s)
                          : launch_egress_l<2>(rgb, n, H, W, cols, top, dtype, out, wide, blocks, s);
+}
+
+int64_t bits_blocks(int n, int hh, int ww, bool fast) {
+    const int64_t per = (int64_t)hh * (fast ? ww >> 3 : (ww + 1) >> 1);      // threads per image
+    constexpr int64_t most = 0x7fffffffll * 256;
+    if (per > most || (per > 0 && n > most / per)) return -1;
+    return (n * per + 255) / 256;
+}
+
+bool ingest_bits_fast(const uint8_t* frames, int ww, const float* packed, const float* gray) {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(gray);
+    return (ww & 7) == 0 && (reinterpret_cast<uintptr_t>(frames) & 3) == 0 && (al & 15) == 0;
+}
+
+bool egress_bits_fast(const float* rgb, int W, const uint8_t* out) {
+    return (W & 15) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+}
+
+hipError_t launch_ingest_bits(const uint8_t* frames, int order, int n, int hh, int ww, int bit_depth, float* packed, float* gray, hipStream_t s) {
+    if (n <= 0 || (!packed && !gray)) return hipSuccess;
+    if (order < 0 || order > 1 || (bit_depth != 10 && bit_depth != 12 && bit_depth != 14) || hh < 1 || ww < 1) return hipErrorInvalidValue;
+    if (order == 0 && bit_depth != 12 && (ww & 1)) return hipErrorInvalidValue;
+    const bool fast = ingest_bits_fast(frames, ww, packed, gray);
+    const int64_t blocks = bits_blocks(n, hh, ww, fast);
+    if (blocks < 0) return hipErrorInvalidValue;
+    const int64_t row_bytes = bits_row_bytes(ww, bit_depth);
+    const float maxv = (float)((1u << bit_depth) - 1u);
+    BITS_DISPATCH(ingest_bits_kernel, bit_depth, order, fast, frames, packed, gray, n, hh, ww, row_bytes, maxv);
+    return hipGetLastError();
+}
+
+hipError_t launch_egress_bits(const float* rgb, int n, int H, int W, int order, int bit_depth, int bayer, uint8_t* out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (order < 0 || order > 1 || (bit_depth != 10 && bit_depth != 12 && bit_depth != 14) || H < 2 || W < 2 || ((H | W) & 1) || bayer < 0 || bayer > 3)
+        return hipErrorInvalidValue;
+    if (order == 0 && bit_depth != 12 && (W & 3)) return hipErrorInvalidValue;
+    const bool fast = egress_bits_fast(rgb, W, out);
+    const int64_t blocks = bits_blocks(n, H >> 1, W >> 1, fast);
+    if (blocks < 0) return hipErrorInvalidValue;
+    const int64_t row_bytes = bits_row_bytes(W >> 1, bit_depth);
+    const int cols = bayer_cols(bayer);
+    const float top = (float)((1u << bit_depth) - 1u);
+    BITS_DISPATCH(egress_bits_kernel, bit_depth, order, fast, rgb, out, n, H, W, row_bytes, cols, top);
+    return hipGetLastError();
 }
 
 // planes of the handle's own buffers (hipMalloc alignment); pairs: slot | direction << 6 of every pair in batch order (ignored

@@ -205,6 +205,49 @@ int rvdd_egress(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t W, in
     return RVDD_OK;
 }
 
+// the checks rvdd_ingest_bits and rvdd_egress_bits share (ww in cells); 0 = fine
+static int bits_args(rvdd_t* h, const char* fn, int32_t order, int32_t bit_depth, int32_t ww) {
+    if (order != RVDD_BITS_MIPI && order != RVDD_BITS_MSB) return fail(h, RVDD_ERR_ARG, "%s: order must be 0 (MIPI CSI-2) or 1 (MSB first), got %d", fn, order);
+    if (bit_depth != 10 && bit_depth != 12 && bit_depth != 14) return fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 10, 12 or 14, got %d", fn, bit_depth);
+    if (order == RVDD_BITS_MIPI && bit_depth != 12 && (ww & 1))
+        return fail(h, RVDD_ERR_ARG, "%s: ww must be even for MIPI RAW%d (groups of four pixels), got ww = %d", fn, bit_depth, ww);
+    return RVDD_OK;
+}
+
+int rvdd_ingest_bits(rvdd_t* h, const uint8_t* frames, int32_t order, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, float* packed,
+                     float* gray, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (hh < 1) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: hh must be >= 1, got %d", hh);
+    if (ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: ww must be >= 1, got %d", ww);
+    RC(bits_args(h, "rvdd_ingest_bits", order, bit_depth, ww));
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: n must be >= 0, got %d", n);
+    if (n == 0) return RVDD_OK;
+    if (!frames) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: frames is required");
+    if (bits_blocks(n, hh, ww, ingest_bits_fast(frames, ww, packed, gray)) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
+    ENTER(h);
+    HIPCHK(h, launch_ingest_bits(frames, order, n, hh, ww, bit_depth, packed, gray, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_egress_bits(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t W, int32_t order, int32_t bit_depth, int32_t pattern,
+                     uint8_t* out, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: H must be even and >= 2, got %d", H);
+    if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: W must be even and >= 2, got %d", W);
+    RC(bits_args(h, "rvdd_egress_bits", order, bit_depth, W / 2));
+    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
+        return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: n must be >= 0, got %d", n);
+    if (n == 0) return RVDD_OK;
+    if (!rgb || !out) return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: rgb and out are required");
+    if (bits_blocks(n, H / 2, W / 2, egress_bits_fast(rgb, W, out)) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: n * H * W = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, H, W);
+    ENTER(h);
+    HIPCHK(h, launch_egress_bits(rgb, n, H, W, order, bit_depth, pattern, out, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 // the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine
 static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int32_t W) {
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);

@@ -159,6 +159,7 @@ struct Options {
     int stream_reset_each = 0;            // every ready step of rvdd_video_push carries the reset mark of every ready slot
     int stream_flow_from_denoised = 0;    // rvdd_video_push: the flow towards the previous frame is matched against the previous output
     int stream_all_frames = 0;            // rvdd_video_push: also a video's first frame and, on an IDLE behind its last frame, that frame
+    int stream_container = 0;             // rvdd_video_push: the frames are packed 10 / 12 / 14-bit samples, 1 = MIPI CSI-2, 2 = MSB first (0: one number each)
     int use_graphs = 0;       // replay captured frame-steps (measured slower, off)
 
     bool split16() const { return conv == CONV_SPLIT16; }

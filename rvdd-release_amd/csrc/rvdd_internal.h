@@ -371,6 +371,16 @@ inline int bayer_cols(int bayer) {
 hipError_t launch_egress(const float* rgb, int n, int H, int W, int layout, int dtype, int bit_depth, int bayer, void* out, hipStream_t s);
 // the grid of that launch (n, H, W >= 1) and whether it takes the wide form; -1 = more than 2^31 - 1 blocks
 int64_t egress_blocks(const float* rgb, int n, int H, int W, int layout, int dtype, const void* out, bool* wide);
+// The same two directions on frames of packed bit_depth = 10 / 12 / 14-bit samples (rvdd_ingest_bits, rvdd_egress_bits): order enum
+// rvdd_bits_order (0 MIPI CSI-2 groups, 1 MSB-first bit string per row), rows and frames tight.  A row of 2ww samples:
+inline int64_t bits_row_bytes(int ww, int bit_depth) { return (2 * (int64_t)ww * bit_depth + 7) / 8; }
+// packed / gray / the u16 samples are those of launch_ingest_raw(u16 mosaic) / launch_egress(mosaic, u16) on the unpacked frames
+hipError_t launch_ingest_bits(const uint8_t* frames, int order, int n, int hh, int ww, int bit_depth, float* packed, float* gray, hipStream_t s);
+hipError_t launch_egress_bits(const float* rgb, int n, int H, int W, int order, int bit_depth, int bayer, uint8_t* out, hipStream_t s);
+// whether those launches take the dword form (a thread owns 16 pixels of both sensor rows), and their grid; -1 = more than 2^31 - 1 blocks
+bool ingest_bits_fast(const uint8_t* frames, int ww, const float* packed, const float* gray);
+bool egress_bits_fast(const float* rgb, int W, const uint8_t* out);
+int64_t bits_blocks(int n, int hh, int ww, bool fast);
 // the flow batch of a push: I0 / I1 [npairs][hw] from the gray planes [B][hw] of the ring positions of the centre, previous and
 // next (nullable: no future frame) frames.  pairs[q] = slot | direction << 6 of pair q (direction 0: (centre, previous), 1: (centre,
 // next)); with npairs = B * directions -- every slot has every pair -- pair q is slot q % B, direction q / B, and pairs is not read.

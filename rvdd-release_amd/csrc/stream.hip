@@ -9,8 +9,18 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         return fail(h, RVDD_ERR_ARG, "rvdd_video_push: layout must be 0 (mosaic) or 1 (packed HWC), got %d", layout);
     if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: bit_depth must be 1..16, got %d", bit_depth);
     if (!frames || !out_rgb || !valid) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: frames, out_rgb and valid are required");
-    if (!h->finalized) return fail(h, RVDD_ERR_STATE, "rvdd_video_push: weights not finalized");
     const int B = h->cfg.batch, hh = h->cfg.height / 2, ww = h->cfg.width / 2, fut = h->cfg.future;
+    // option "stream_container": the frames are packed bits, order container - 1 of enum rvdd_bits_order
+    const int container = h->opt.stream_container;
+    if (container) {
+        if (dtype != RVDD_RAW_U16) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with option stream_container dtype must be 0 (u16: the samples' type), got %d", dtype);
+        if (layout != RVDD_RAW_MOSAIC) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with option stream_container layout must be 0 (mosaic), got %d", layout);
+        if (bit_depth != 10 && bit_depth != 12 && bit_depth != 14)
+            return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with option stream_container bit_depth must be 10, 12 or 14, got %d", bit_depth);
+        if (container - 1 == RVDD_BITS_MIPI && bit_depth != 12 && (ww & 1))
+            return fail(h, RVDD_ERR_ARG, "rvdd_video_push: ww must be even for MIPI RAW%d (groups of four pixels), got ww = %d", bit_depth, ww);
+    }
+    if (!h->finalized) return fail(h, RVDD_ERR_STATE, "rvdd_video_push: weights not finalized");
     const size_t hw = (size_t)hh * ww;
     auto& st = h->st;
     for (int b = 0; b < B; ++b)
@@ -51,7 +61,13 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     // ingest: one launch per run of slots that get a frame
     const int pos = (int)(st.pushes % (uint64_t)st.depth);
     const size_t esz = dtype == RVDD_RAW_U16 ? 2 : 4;
+    const size_t frame_bytes = container ? 2 * (size_t)hh * (size_t)bits_row_bytes(ww, bit_depth) : 0;
     RC(for_each_run(B, [&](int b) { return !(ctl && ctl[b] == RVDD_PUSH_IDLE); }, [&](int b, int e) -> int {
+        if (container) {
+            HIPCHK(h, launch_ingest_bits(static_cast<const uint8_t*>(frames) + (size_t)b * frame_bytes, container - 1, e - b, hh, ww, bit_depth,
+                                         st.packed + ((size_t)pos * B + b) * 4 * hw, st.gray + ((size_t)pos * B + b) * hw, s));
+            return RVDD_OK;
+        }
         HIPCHK(h, launch_ingest_raw(static_cast<const char*>(frames) + (size_t)b * 4 * hw * esz, dtype, layout, e - b, hh, ww, bit_depth,
                                     st.packed + ((size_t)pos * B + b) * 4 * hw, st.gray + ((size_t)pos * B + b) * hw, s));
         return RVDD_OK;

@@ -1,7 +1,9 @@
 """Denoise raw footage: `python -m rvdd_release_amd.denoise --dataroot D --nFolder noisy --results_dir R <model flags>`.
 
 Reads `<dataroot>/<nFolder>/<video>/<frame>.tif` (`--dataset_mode rawvideo`: sensor frames as 1-channel mosaics or
-4-channel packed frames, uint16 or float32; no ground truth, no flow folder) and writes, for every frame the reference's
+4-channel packed frames, uint16 or float32; no ground truth, no flow folder) -- or frames of packed 10 / 12 / 14-bit samples,
+which go to the device as they lie (`RvddRuntime.video_push(container=...)`): TIFFs with BitsPerSample = --bit_depth, or with
+`--raw_container mipi --raw_size WxH` headerless `<frame>.raw` files of MIPI CSI-2 RAW<bit_depth> rows -- and writes, for every frame the reference's
 test-time dataset yields (frames 1 .. N-1-future of a video of N frames; every frame with --all_frames),
 
     <results_dir>/<video>/<frame>_denoised.tif
@@ -23,6 +25,9 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       input frame's own base name, uint16 digital numbers as [H,W,3] linear RGB / the [H,W] mosaic in
                       --bayer_pattern / the packed [H/2,W/2,4] frame (`rvdd_egress`) -- the results directory is then itself a
                       --dataroot/--nFolder tree that `--dataset_mode rawvideo` reads (mosaic16, packed16).
+                      mosaic_msb: that mosaic as <frame>.tif with BitsPerSample = --out_bit_depth (10 / 12 / 14), the samples
+                      bit-packed as TIFF stores them (`rvdd_egress_bits`) -- again a tree `denoise` reads; mosaic_mipi: the same
+                      samples as headerless <frame>.raw of MIPI CSI-2 RAW10 / 12 / 14 rows (read back with --raw_container mipi).
   --out_bit_depth N   the digital numbers' bit depth (default: --bit_depth)
   --all_frames        write EVERY input frame (option "stream_all_frames"): also frame 0 of a video -- denoised with itself as the
                       previous frame, a zero flow and a fresh recurrence; frame 1 then starts as always -- and, with a future frame,
@@ -41,12 +46,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from .runtime import BAYER_PATTERNS, raw_frames_to_device
+from . import tiffio
+from .runtime import BAYER_PATTERNS, BITS_DEPTHS, bits_row_bytes, raw_frames_to_device
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
 # --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
 OUT_FORMATS = {"f32": ("rgb_hwc", torch.float32, "_denoised.tif"), "rgb16": ("rgb_hwc", torch.int16, ".tif"),
-               "mosaic16": ("mosaic", torch.int16, ".tif"), "packed16": ("packed_hwc", torch.int16, ".tif")}
+               "mosaic16": ("mosaic", torch.int16, ".tif"), "packed16": ("packed_hwc", torch.int16, ".tif"),
+               # the mosaic's samples bit-packed (RvddRuntime.egress_bits): layout "bits", the order in the sample type's place
+               "mosaic_msb": ("bits", "msb", ".tif"), "mosaic_mipi": ("bits", "mipi", ".raw")}
 
 
 def deal_slots(lengths: Sequence[int], slots: int, tail: int = 0) -> List[List[Tuple[int, int, int]]]:
@@ -101,6 +109,15 @@ def _parse(argv):
     opt.out_bit_depth = int(opt.bit_depth) if own.out_bit_depth is None else own.out_bit_depth
     if not 1 <= opt.out_bit_depth <= 16:
         raise SystemExit("--out_bit_depth must be 1..16, got %d" % opt.out_bit_depth)
+    if OUT_FORMATS[opt.out_format][0] == "bits" and opt.out_bit_depth not in BITS_DEPTHS:
+        raise SystemExit("--out_format %s needs --out_bit_depth (default: --bit_depth) 10, 12 or 14, got %d" % (opt.out_format, opt.out_bit_depth))
+    if opt.raw_container is not None:
+        if opt.raw_container != 'mipi':
+            raise SystemExit("--raw_container %r: headerless frames are 'mipi' (packed TIFFs are recognised by themselves)" % opt.raw_container)
+        if opt.raw_size is None:
+            raise SystemExit("--raw_container mipi needs --raw_size WxH")
+        if int(opt.bit_depth) not in BITS_DEPTHS:
+            raise SystemExit("--raw_container mipi needs --bit_depth 10, 12 or 14, got %d" % int(opt.bit_depth))
     if not any(a == '--dataset_mode' or a.startswith('--dataset_mode=') for a in rest):
         opt.dataset_mode = 'rawvideo'
     if opt.srgb is not None:
@@ -109,11 +126,6 @@ def _parse(argv):
             raise SystemExit("--srgb takes ISO,n,red_gain,blue_gain")
         opt.srgb = (int(f[0]), float(f[1]), float(f[2]), float(f[3]))
     return opt
-
-
-def _frame_size(dataset, path):
-    a = dataset.read_frame(path)
-    return (a.shape[0], a.shape[1]) if dataset.layout == "mosaic" else (2 * a.shape[0], 2 * a.shape[1])
 
 
 def main(argv=None) -> dict:
@@ -136,7 +148,7 @@ def main(argv=None) -> dict:
 
     groups = {}                                   # frame size -> its videos, in dataset order
     for key, frames in dataset.videos:
-        groups.setdefault(_frame_size(dataset, frames[0]), []).append((key, frames))
+        groups.setdefault(dataset.frame_size(frames[0]), []).append((key, frames))
     written = 0
     t0 = time.time()
     for (H, W), videos in groups.items():
@@ -149,7 +161,13 @@ def main(argv=None) -> dict:
         rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
         rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
         rt.set_option("stream_all_frames", int(opt.all_frames))
-        shape = (B, H, W) if dataset.layout == "mosaic" else (B, H // 2, W // 2, 4)
+        container = dataset.container               # None, or "msb" / "mipi": the frames stay bit-packed up to the device
+        if layout == "bits" and sample == "mipi" and W % (2 if depth == 12 else 4):
+            raise SystemExit("--out_format mosaic_mipi: a RAW%d row is groups of %d pixels, the frames are %d wide" % (depth, 2 if depth == 12 else 4, W))
+        if container is not None:
+            shape = (B, H, bits_row_bytes(W, int(opt.bit_depth), container))
+        else:
+            shape = (B, H, W) if dataset.layout == "mosaic" else (B, H // 2, W // 2, 4)
         out = files = None
         # --all_frames with a future frame: the step behind a video's last frame (k = N) is the IDLE that outputs that frame
         for step in deal_slots([len(f) for _, f in videos], B, tail=fut if opt.all_frames else 0):
@@ -157,11 +175,11 @@ def main(argv=None) -> dict:
             for b, (c, vid, k) in enumerate(step):
                 if c != IDLE:
                     batch[b] = dataset.read_frame(videos[vid][1][k])
-            out, valid = rt.video_push(raw_frames_to_device(batch, dev), [c for c, _, _ in step], int(opt.bit_depth),
-                                       dataset.layout, out)
+            frames_dev = raw_frames_to_device(batch, dev) if container is None else torch.from_numpy(batch).to(dev)
+            out, valid = rt.video_push(frames_dev, [c for c, _, _ in step], int(opt.bit_depth), dataset.layout, out, container=container)
             host = None
             if any(valid):                               # the files' samples of all slots: one kernel, one copy
-                files = rt.egress(out, layout, sample, depth, out=files)
+                files = rt.egress_bits(out, sample, depth, out=files) if layout == "bits" else rt.egress(out, layout, sample, depth, out=files)
                 host = files.cpu().numpy()
                 host = host.view(np.uint16) if host.dtype == np.int16 else host
             ended = False
@@ -175,7 +193,12 @@ def main(argv=None) -> dict:
                 path = frames[k - fut]                  # the centre frame
                 stem = os.path.splitext(os.path.basename(path))[0]
                 util.mkdir(os.path.join(opt.results_dir, key))
-                iio_write(host[b], os.path.join(opt.results_dir, key, stem + suffix))
+                if layout != "bits":
+                    iio_write(host[b], os.path.join(opt.results_dir, key, stem + suffix))
+                elif sample == "msb":
+                    tiffio.write_packed(os.path.join(opt.results_dir, key, stem + suffix), host[b], W, depth)
+                else:
+                    host[b].tofile(os.path.join(opt.results_dir, key, stem + suffix))
                 if opt.srgb is not None:
                     iso, n, red, blue = opt.srgb
                     png = rt.ppipe(out[b:b + 1], 1.0 / n, red, blue, iso, _lib.PPIPE_FROM_NET, "nchw")

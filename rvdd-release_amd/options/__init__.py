@@ -31,6 +31,8 @@ def make_opt(**overrides) -> Namespace:
         crop_data=None, warpeddata=False,
         val_batch_size=1,                    # validation: videos packed into this many batch slots (data/packed.py); 1 = one frame per step
         val_compact_slots=False,             # with val_batch_size > 1: step only the live slots once no video is left to refill one (no tail)
+        raw_container=None,                  # rawvideo: 'mipi' = the frames are headerless <frame>.raw files of CSI-2 RAW<bit_depth> rows
+        raw_size=None,                       # rawvideo, with raw_container: the frames' size in pixels, 'WxH'
     )
     for k, v in overrides.items():
         if not hasattr(opt, k):

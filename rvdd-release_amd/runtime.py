@@ -28,6 +28,15 @@ BAYER_PATTERNS = ("gbrg", "grbg", "rggb", "bggr")
 RAW_LAYOUTS = {"mosaic": _lib.RAW_MOSAIC, "packed_hwc": _lib.RAW_PACKED_HWC}
 # enum rvdd_out_layout by name (rvdd_egress)
 OUT_LAYOUTS = {"rgb_hwc": _lib.OUT_RGB_HWC, "mosaic": _lib.OUT_MOSAIC, "packed_hwc": _lib.OUT_PACKED_HWC}
+# enum rvdd_bits_order by name (rvdd_ingest_bits, rvdd_egress_bits; option "stream_container" is the value plus one)
+BITS_ORDERS = {"mipi": _lib.BITS_MIPI, "msb": _lib.BITS_MSB}
+BITS_DEPTHS = (10, 12, 14)
+
+
+def bits_row_bytes(width: int, bit_depth: int, order: str = "msb") -> int:
+    """Bytes of one row of `width` packed samples of `bit_depth` bits: width * bit_depth / 8, for "msb" rounded up to a whole
+    byte (zero pad bits); a "mipi" row is whole groups of 4 pixels (2 at 12 bits), which the library checks."""
+    return (int(width) * int(bit_depth) + 7) // 8
 
 
 def raw_frames_to_device(frames, device) -> torch.Tensor:
@@ -186,6 +195,8 @@ class RvddRuntime:
             self.no_warp = bool(value)
         if name == "bayer_pattern":
             self.bayer_pattern = int(value)
+        if name == "stream_container":
+            self.stream_container = int(value)
 
     def move_slots(self, pairs):
         """The whole recurrent state of slot `f` replaces that of slot `t` for every (f, t) of `pairs`, one launch
@@ -311,17 +322,95 @@ class RvddRuntime:
                                          self._stream()), "rvdd_egress")
         return out
 
-    def video_push(self, frames: torch.Tensor, ctl=None, bit_depth: int = 12, layout: str = "mosaic", out=None):
+    def _bits_frames(self, frames: torch.Tensor, order: str, bit_depth: int, n: int, hh: int, ww: int, name: str) -> torch.Tensor:
+        """the uint8 GPU tensor of n tight frames of 2hh rows of bits_row_bytes(2ww, bit_depth, order) bytes, checked"""
+        if order not in BITS_ORDERS:
+            raise ValueError(f"{name}: order {order!r} is not one of {', '.join(BITS_ORDERS)}")
+        if not torch.is_tensor(frames) or not frames.is_cuda:
+            raise RuntimeError(f"{name}: frames must be a GPU tensor (rvdd has no CPU path)")
+        if frames.device.index != self.device:
+            raise RuntimeError(f"{name}: frames live on cuda:{frames.device.index} but this runtime drives cuda:{self.device}")
+        if frames.dtype != torch.uint8 or not frames.is_contiguous():
+            raise RuntimeError(f"{name}: packed frames are a contiguous uint8 tensor, got {frames.dtype}")
+        rb = bits_row_bytes(2 * ww, bit_depth, order)
+        if frames.numel() != n * 2 * hh * rb:
+            raise RuntimeError(f"{name}: {n} frames of {2 * hh} rows of {rb} bytes ({2 * ww} samples of {bit_depth} bits, {order}) are "
+                               f"{n * 2 * hh * rb} bytes, got {frames.numel()}")
+        return frames
+
+    def ingest_bits(self, frames: torch.Tensor, order: str, bit_depth: int, hh: int, ww: int, n: Optional[int] = None,
+                    want_packed: bool = True, want_gray: bool = True):
+        """Frames of packed 10 / 12 / 14-bit samples -> (packed [n,4,hh,ww], gray [n,hh,ww]) exactly as `ingest_raw` gives them for
+        the unpacked uint16 mosaic (rvdd_ingest_bits).  frames: contiguous uint8 GPU tensor, n tight frames of 2hh rows of
+        bits_row_bytes(2ww, bit_depth, order) bytes ([n,2hh,row_bytes], or flat); order "mipi" (CSI-2 RAW10 / 12 / 14) or "msb"
+        (TIFF FillOrder 1).  n: None = frames.shape[0]."""
+        hh, ww = int(hh), int(ww)
+        if n is None:
+            n = frames.shape[0] if torch.is_tensor(frames) and frames.dim() == 3 else 1
+        t = self._bits_frames(frames, order, int(bit_depth), int(n), hh, ww, "ingest_bits")
+        packed = torch.empty(n, 4, hh, ww, dtype=torch.float32, device=self._tdev) if want_packed else None
+        gray = torch.empty(n, hh, ww, dtype=torch.float32, device=self._tdev) if want_gray else None
+        self._check(self.lib.rvdd_ingest_bits(self.h, _ptr(t), BITS_ORDERS[order], n, hh, ww, int(bit_depth), _ptr(packed), _ptr(gray),
+                                              self._stream()), "rvdd_ingest_bits")
+        return packed, gray
+
+    def egress_bits(self, rgb: torch.Tensor, order: str, bit_depth: int, pattern: Optional[str] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[n,3,H,W] RGB in [-1,1] -> uint8 [n,H,row_bytes]: the uint16 mosaic `egress` writes, its samples packed `bit_depth` = 10 /
+        12 / 14 bits each in `order` ("mipi" / "msb"), pad bits zero (rvdd_egress_bits).  pattern: one of BAYER_PATTERNS, None =
+        the pattern set_option("bayer_pattern", ...) gave this runtime.  out: a contiguous uint8 GPU tensor of n * H * row_bytes
+        elements to write into."""
+        if order not in BITS_ORDERS:
+            raise ValueError(f"egress_bits: order {order!r} is not one of {', '.join(BITS_ORDERS)}")
+        if pattern is None:
+            pat = getattr(self, "bayer_pattern", 0)
+        elif pattern in BAYER_PATTERNS:
+            pat = BAYER_PATTERNS.index(pattern)
+        else:
+            raise ValueError(f"egress_bits: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
+        if not torch.is_tensor(rgb) or rgb.dim() != 4 or rgb.shape[1] != 3:
+            raise RuntimeError(f"egress_bits: rgb is [n,3,H,W], got {tuple(getattr(rgb, 'shape', ()))}")
+        n, _, H, W = rgb.shape
+        rgb = _chk_dev(rgb, rgb.shape, "rgb", self.device)
+        rb = bits_row_bytes(W, int(bit_depth), order)
+        if out is None:
+            out = torch.empty(n, H, rb, dtype=torch.uint8, device=self._tdev)
+        else:
+            if not torch.is_tensor(out) or not out.is_cuda or out.device.index != self.device:
+                raise RuntimeError(f"egress_bits: out must be a GPU tensor on cuda:{self.device} (rvdd has no CPU path)")
+            if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n * H * rb:
+                raise RuntimeError(f"egress_bits: out must be a contiguous uint8 tensor of {n * H * rb} elements, got {out.dtype} "
+                                   f"{tuple(out.shape)}")
+        self._check(self.lib.rvdd_egress_bits(self.h, _ptr(rgb), n, H, W, BITS_ORDERS[order], int(bit_depth), pat, _ptr(out),
+                                              self._stream()), "rvdd_egress_bits")
+        return out
+
+    def video_push(self, frames: torch.Tensor, ctl=None, bit_depth: int = 12, layout: str = "mosaic", out=None,
+                   container: Optional[str] = None):
         """Every slot's next sensor frame in, at most one denoised frame per slot out (rvdd_video_push).
         frames: [B,2hh,2ww] / [B,hh,ww,4] as `ingest_raw` takes them; ctl: None (every slot continues its video) or B
         values of _lib.PUSH_NEXT / PUSH_FIRST / PUSH_IDLE.  -> (out [B,3,H,W], valid: B bools); out[b] is the denoised
         centre frame of slot b where valid[b], unspecified elsewhere.  Nothing is synchronised.
+        container "mipi" / "msb" (option "stream_container", set here; None sets it back to 0): frames is a uint8 tensor of B tight
+        frames of packed `bit_depth` = 10 / 12 / 14-bit samples as `ingest_bits` takes them, and the outputs are those of the
+        same pushes with the unpacked uint16 frames.
         A video of N frames gives its frames 1 .. N-1-future.  With option "stream_all_frames" it gives every frame: frame 0 on
         the push that completes 1 + future frames, and with a future frame the last one on a PUSH_IDLE straight after it (a
         PUSH_FIRST there drops it); valid[b] is then also set on such a FIRST / IDLE push, and out[b] is the oldest frame of
         the slot's video not yet output."""
-        t, dtype, lay, n, hh, ww = _raw_frames(frames, layout, "video_push", self.device)
         B, H, W = self.B, self.H, self.W
+        if container is not None and container not in BITS_ORDERS:
+            raise ValueError(f"video_push: container {container!r} is not None or one of {', '.join(BITS_ORDERS)}")
+        want = 0 if container is None else 1 + BITS_ORDERS[container]
+        if container is None:
+            t, dtype, lay, n, hh, ww = _raw_frames(frames, layout, "video_push", self.device)
+        else:
+            if layout != "mosaic":
+                raise ValueError(f"video_push: packed frames ({container}) are a mosaic, got layout {layout!r}")
+            dtype, lay, n, hh, ww = _lib.RAW_U16, _lib.RAW_MOSAIC, B, H // 2, W // 2
+            t = self._bits_frames(frames, container, int(bit_depth), n, hh, ww, "video_push")
+        if getattr(self, "stream_container", 0) != want:
+            self.set_option("stream_container", want)
         if (n, 2 * hh, 2 * ww) != (B, H, W):
             raise RuntimeError(f"video_push: frames of {n} x {2 * hh} x {2 * ww} sites for a runtime of {B} slots of {H} x {W}")
         c = None

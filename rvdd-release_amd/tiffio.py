@@ -147,7 +147,8 @@ def _undo_predictor(block: np.ndarray, predictor: int, dtype: np.dtype, rows: in
     raise TiffError(f"unsupported TIFF predictor {predictor}")
 
 
-def read(path: str) -> np.ndarray:
+def _read_tags(path: str):
+    """-> (the file's bytes, its byte order "<" / ">", {tag: values} of its first IFD)"""
     with open(path, "rb") as f:
         buf = f.read()
     if len(buf) < 8:
@@ -178,6 +179,11 @@ def read(path: str) -> np.ndarray:
             (off,) = struct.unpack(bo + ("Q" if big else "I"), buf[off:off + val_sz])
         vals = struct.unpack(bo + fmt * count if len(fmt) == 1 else bo + fmt * count, buf[off:off + nbytes])
         tags[tag] = vals
+    return buf, bo, tags
+
+
+def read(path: str) -> np.ndarray:
+    buf, bo, tags = _read_tags(path)
     try:
         W, H = int(tags[256][0]), int(tags[257][0])
     except KeyError:
@@ -268,6 +274,11 @@ def write(path: str, arr) -> None:
     if extra > 0:
         add(338, 3, (0,) * extra)                       # EXTRASAMPLE_UNSPECIFIED
     add(339, 3, (fmt,) * C)
+    _emit(path, data, entries)
+
+
+def _emit(path: str, data: bytes, entries) -> None:
+    """one strip `data` at byte 8, then the IFD of `entries` (tag, type, count, values; in tag order; StripOffsets patched)"""
     if 8 + len(data) + 2 + 12 * len(entries) + 4 + 64 >= 2 ** 32:
         raise TiffError("write: image too large for classic TIFF")
     data_off = 8
@@ -294,3 +305,71 @@ def write(path: str, arr) -> None:
             f.write(b"\0")
         f.write(ifd)
         f.write(tail)
+
+
+PACKED_BITS = (10, 12, 14)
+
+
+def packed_row_bytes(width: int, bits: int) -> int:
+    """bytes of a row of `width` samples of `bits` bits as TIFF stores them: one bit string, padded to a whole byte"""
+    return (width * bits + 7) // 8
+
+
+def read_packed(path: str):
+    """A 1-sample, unsigned, uncompressed, stripped TIFF with BitsPerSample 10 / 12 / 14 (FillOrder 1) -> (rows, W, bits): rows
+    uint8 [H, row_bytes], the file's bit-packed rows as they lie -- each sample `bits` wide, most significant bit first, the row
+    zero-padded to a whole byte: RVDD_BITS_MSB of include/rvdd.h -- with the strips (whole rows each) concatenated.  Nothing is
+    unpacked.  Anything else raises TiffError."""
+    buf, bo, tags = _read_tags(path)
+    try:
+        W, H = int(tags[256][0]), int(tags[257][0])
+    except KeyError:
+        raise TiffError(f"{path}: missing ImageWidth/ImageLength")
+    spp = int(tags.get(277, (1,))[0])
+    bits = tags.get(258, (1,))
+    fmt = int(tags.get(339, (1,))[0])
+    if spp != 1 or len(bits) != 1 or int(bits[0]) not in PACKED_BITS or fmt not in (1, 4):
+        raise TiffError(f"{path}: not a packed raw frame (one unsigned sample of 10, 12 or 14 bits), got SamplesPerPixel {spp}, "
+                        f"BitsPerSample {tuple(bits)}, SampleFormat {fmt}")
+    bits = int(bits[0])
+    if int(tags.get(259, (1,))[0]) != 1:
+        raise TiffError(f"{path}: packed raw frames are read uncompressed only, got Compression {tags[259][0]}")
+    if int(tags.get(266, (1,))[0]) != 1:
+        raise TiffError(f"{path}: FillOrder {tags[266][0]} is not supported (1: most significant bit first)")
+    if 322 in tags:
+        raise TiffError(f"{path}: tiled packed raw frames are not supported")
+    offs = tags.get(273)
+    if offs is None:
+        raise TiffError(f"{path}: missing StripOffsets")
+    rb = packed_row_bytes(W, bits)
+    rps = min(int(tags.get(278, (H,))[0]), H)
+    if H < 1 or W < 1 or rps < 1:
+        raise TiffError(f"{path}: empty image")
+    nstrips = (H + rps - 1) // rps
+    cnts = tags.get(279) or tuple(min(rps, H - s * rps) * rb for s in range(nstrips))
+    if len(offs) != nstrips or len(cnts) != nstrips:
+        raise TiffError(f"{path}: {len(offs)} strip offsets / {len(cnts)} byte counts for {nstrips} strips")
+    rows = np.empty((H, rb), np.uint8)
+    for s in range(nstrips):
+        nr = min(rps, H - s * rps)
+        raw = buf[offs[s]:offs[s] + cnts[s]]
+        if len(raw) < nr * rb:
+            raise TiffError(f"{path}: strip {s} is truncated")
+        rows[s * rps:s * rps + nr] = np.frombuffer(raw, np.uint8, nr * rb).reshape(nr, rb)
+    return rows, W, bits
+
+
+def write_packed(path: str, rows_u8, W: int, bits: int) -> None:
+    """uint8 [H, row_bytes] bit-packed rows (RVDD_BITS_MSB: what `read_packed` returns, what rvdd_egress_bits writes) -> an
+    uncompressed one-strip TIFF of one unsigned sample with BitsPerSample = bits (10 / 12 / 14), FillOrder 1."""
+    a = np.asarray(rows_u8)
+    if bits not in PACKED_BITS:
+        raise TiffError(f"write_packed: bits must be 10, 12 or 14, got {bits}")
+    if a.dtype != np.uint8 or a.ndim != 2 or W < 1 or a.shape[1] != packed_row_bytes(W, bits):
+        raise TiffError(f"write_packed: rows must be uint8 [H, {packed_row_bytes(max(W, 0), bits)}] for {W} samples of {bits} bits, got "
+                        f"{a.dtype} {a.shape}")
+    data = np.ascontiguousarray(a).tobytes()
+    entries = [(256, 4, 1, (W,)), (257, 4, 1, (a.shape[0],)), (258, 3, 1, (bits,)), (259, 3, 1, (1,)), (262, 3, 1, (1,)),
+               (266, 3, 1, (1,)), (273, 4, 1, (0,)), (277, 3, 1, (1,)), (278, 4, 1, (a.shape[0],)), (279, 4, 1, (len(data),)),
+               (284, 3, 1, (1,)), (339, 3, 1, (1,))]
+    _emit(path, data, entries)
