@@ -351,6 +351,41 @@ int rvdd_egress_bits(rvdd_t* h, const float* rgb /* [n,3,H,W] in [-1,1] */, int3
                      int32_t order /* enum rvdd_bits_order */, int32_t bit_depth, int32_t pattern /* enum rvdd_bayer */,
                      uint8_t* out /* [n,H,row_bytes] */, void* stream);
 
+/* Dynamic defective-pixel correction (DPC) of packed raw frames: hot and stuck samples replaced by the median of their eight
+ * same-colour neighbours, on the planes rvdd_ingest_raw / rvdd_ingest_bits write -- packed [n,4,hh,ww] in [-1,1], channel k = CFA
+ * position (k >> 1, k & 1).  Inside one channel plane the +-1 neighbours are the same-colour +-2 neighbours of the mosaic, so the
+ * rule needs neither the Bayer pattern nor the container.  Every operation is rounded to f32 on its own (no fused multiply-add, no
+ * square root): the result is reproducible bit for bit in NumPy f32 (tests/dpc_ref.py).  With top = (float)(2^bit_depth - 1):
+ *   dn(v) = ((v + 1) * 0.5) * top                       the dn_k of rvdd_gray_of_rgb
+ *   c     = dn(p[k][y][x]); the eight neighbours dn(p[k][y+dy][x+dx]), dy, dx in {-1, 0, 1} not both zero, an index outside the
+ *           plane mirrored about the site (-1 -> +1, n -> n - 2: hence hh, ww >= 2)
+ *   lo, hi  the smallest and largest neighbour;  m = (s3 + s4) * 0.5, s3 / s4 the 4th / 5th of the eight in ascending order
+ *   var   = fmaxf(noise_a * m - noise_b, var_floor)     the noise curve in DN of this bit depth
+ *   hot:  k_hot  > 0, d = c - hi > 0 and d * d > (k_hot * k_hot) * var
+ *   dead: k_dead > 0, d = lo - c > 0 and d * d > (k_dead * k_dead) * var
+ * packed_out: a flagged sample is 2 * (m / top) - 1 (the division correctly rounded: rvdd_ingest_raw's own function), every other
+ *   sample a copy of its bits.  A frame in which nothing is flagged is a bit copy.
+ * gray [n,hh,ww] (nullable, patched IN PLACE): at a cell in which at least one of the four planes was flagged,
+ *   (((d0 + d1) + d2) + d3) * 0.25 with d_k = m_k for a flagged plane (the median in DN, no round trip through the packed value)
+ *   and dn(p[k][y][x]) for the others; a cell without a flag is not written.
+ * counts (DEVICE uint32 [n,2], nullable): the flags of frame i are ADDED to counts[i][0] (hot) and counts[i][1] (dead).
+ * The median of eight tolerates up to three bad neighbours; larger clusters of one colour are out of its reach.  Inputs are assumed
+ * finite: with NaN or inf the result is unspecified, but nothing outside the tensors is read or written.
+ * RVDD_ERR_ARG (the message names the argument) and nothing launched: NULL cfg; k_hot / k_dead negative or not finite; noise_a /
+ * noise_b not finite; var_floor not > 0 (or not finite); bit_depth outside 1..16; hh or ww < 2; n < 0; NULL packed_in / packed_out
+ * with n > 0; a launch of more than 2^31 - 1 blocks; packed_out overlapping packed_in.  k_hot = 0 / k_dead = 0 switches that side
+ * off.  n = 0 does nothing.  Asynchronous and stream-ordered; nothing is read back.
+ * With ww % 4 == 0 and all pointers 16-byte aligned a thread owns four neighbouring cells (16-byte loads and stores); every other
+ * case one cell.  Same bits either way. */
+typedef struct rvdd_dpc_cfg {
+    float k_hot, k_dead;      /* thresholds in standard deviations of the noise curve; 0 = that side off */
+    float noise_a, noise_b;   /* var(m) = noise_a * m - noise_b, in DN of the frames' bit depth */
+    float var_floor;          /* the least variance assumed, > 0 */
+} rvdd_dpc_cfg;
+int rvdd_dpc(rvdd_t* h, const float* packed_in /* [n,4,hh,ww] */, float* packed_out /* [n,4,hh,ww] */,
+             float* gray /* [n,hh,ww], nullable, patched in place */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+             const rvdd_dpc_cfg* cfg, uint32_t* counts /* DEVICE [n,2], nullable, accumulated */, void* stream);
+
 enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
 
 /* The stream: one call hands every batch slot its next sensor frame (`frames`: cfg.batch frames of H/2 x W/2 cells, one
@@ -392,7 +427,7 @@ enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
  *       push whose outputs have no TV-L1 pair at all runs no TV-L1, its step reads a zeroed flow tensor.
  * The handle keeps the last 2 + future ingested frames of every slot (packed and gray) on the device: allocated by the
  * first push, freed with the handle (20 (2 + future) + 24 (1 + future) bytes per raw cell and slot with the flow batch's
- * buffers; 4 more with option "stream_flow_from_denoised", allocated by the first push that has it on).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
+ * buffers; 4 more with option "stream_flow_from_denoised", 16 more with rvdd_set_dpc, each allocated by the first push that has it on).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
  * I1 = gray[previous]) and, with a future frame, (gray[centre], gray[next]) for all of them in ONE batch call in the form of
  * option "tvl1_async" 1 (whatever the option says), then one rvdd_step_strided on the kept packed frames and those flows.  A
  * slot's first ready push carries its reset mark (rvdd_reset_slots; raw_prev = its oldest frame), so every output is bit for
@@ -412,6 +447,24 @@ enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
 int rvdd_video_push(rvdd_t* h, const void* frames /* [B, one frame each] */, int32_t dtype, int32_t layout,
                     int32_t bit_depth, const uint8_t* ctl /* HOST [B], NULL = all NEXT */,
                     float* out_rgb /* [B,3,H,W] */, uint8_t* valid /* HOST [B] */, void* stream);
+
+/* Defective-pixel correction inside rvdd_video_push: cfg = the parameters of rvdd_dpc (checked as there: RVDD_ERR_ARG, the message
+ * names the field, and nothing changes), NULL = off, the default.  Its own call and not an rvdd_set_option name because its
+ * parameters are floats.  Per handle; acts on rvdd_video_push only; synchronises the device, as rvdd_set_option does.
+ * With the stage on a push ingests the packed planes of the slots that get a frame into a scratch tensor [cfg.batch,4,hh,ww]
+ * (allocated by the first push that has the stage on: 16 bytes per raw cell and slot, freed with the handle) and their gray planes
+ * straight into the ring, then runs rvdd_dpc's kernel from the scratch tensor into the ring's packed frames, patching the ring's
+ * gray planes, with the push's bit_depth -- one launch per run of slots that got a frame, as the ingest.  Everything downstream
+ * reads the ring as before, so the corrected frames are what TV-L1 matches, what the step denoises and what option
+ * "stream_all_frames" copies for a head or a tail (copies of corrected frames: not counted again), under every
+ * "stream_container".  With the stage off a push makes exactly the launches it made before and allocates nothing more; a frame in
+ * which nothing is flagged leaves the ring bit for bit what a push without the stage leaves. */
+int rvdd_set_dpc(rvdd_t* h, const rvdd_dpc_cfg* cfg /* NULL = off, the default */);
+
+/* The samples the stage corrected, per batch slot, since rvdd_set_dpc last switched it ON (off -> on; a call that only changes the
+ * parameters keeps the totals): hot_dead[b][0] hot, hot_dead[b][1] dead.  Copies the device's counters to the host on `stream` and
+ * synchronises it: call it where the loop synchronises anyway.  All zeros on a handle that never had the stage on. */
+int rvdd_dpc_counts(rvdd_t* h, uint64_t* hot_dead /* HOST [cfg.batch,2] */, void* stream /* synchronised */);
 
 /* ---- raw datasets from sRGB video ------------------------------------------- */
 

@@ -30,6 +30,12 @@ class RvddCfg(C.Structure):
                 ("height", C.c_int32), ("width", C.c_int32), ("device", C.c_int32)]
 
 
+class RvddDpcCfg(C.Structure):
+    """struct rvdd_dpc_cfg (rvdd_dpc, rvdd_set_dpc)"""
+    _fields_ = [("k_hot", C.c_float), ("k_dead", C.c_float), ("noise_a", C.c_float), ("noise_b", C.c_float),
+                ("var_floor", C.c_float)]
+
+
 # symbol -> (restype, argtypes); exactly the functions include/rvdd.h declares
 _P = C.c_void_p
 _PROTOS = {
@@ -63,6 +69,9 @@ _PROTOS = {
     "rvdd_egress": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_ingest_bits": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "rvdd_egress_bits": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rvdd_dpc": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddDpcCfg), _P, _P]),
+    "rvdd_set_dpc": (C.c_int, [_P, C.POINTER(RvddDpcCfg)]),
+    "rvdd_dpc_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), _P]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                  _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),

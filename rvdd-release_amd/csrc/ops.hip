@@ -49,6 +49,19 @@ int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_
     return RVDD_OK;
 }
 
+int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* out) {
+    if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
+    if (!(cfg->k_hot >= 0.0f) || !std::isfinite(cfg->k_hot)) return fail(h, RVDD_ERR_ARG, "%s: k_hot must be finite and >= 0 (0 = off), got %g", fn, cfg->k_hot);
+    if (!(cfg->k_dead >= 0.0f) || !std::isfinite(cfg->k_dead)) return fail(h, RVDD_ERR_ARG, "%s: k_dead must be finite and >= 0 (0 = off), got %g", fn, cfg->k_dead);
+    if (!std::isfinite(cfg->noise_a)) return fail(h, RVDD_ERR_ARG, "%s: noise_a must be finite, got %g", fn, cfg->noise_a);
+    if (!std::isfinite(cfg->noise_b)) return fail(h, RVDD_ERR_ARG, "%s: noise_b must be finite, got %g", fn, cfg->noise_b);
+    if (!(cfg->var_floor > 0.0f) || !std::isfinite(cfg->var_floor)) return fail(h, RVDD_ERR_ARG, "%s: var_floor must be finite and > 0, got %g", fn, cfg->var_floor);
+    // the squares rounded to f32 once, here (1e18 squared is +inf: such a side can never flag)
+    const float k2h = cfg->k_hot * cfg->k_hot, k2d = cfg->k_dead * cfg->k_dead;
+    *out = DpcParams{cfg->k_hot, cfg->k_dead, k2h, k2d, cfg->noise_a, cfg->noise_b, cfg->var_floor, 0.0f};
+    return RVDD_OK;
+}
+
 extern "C" {
 
 int rvdd_psnr_l1(rvdd_t* h, const float* den, const float* gt, int64_t count, float* out2, void* stream) {
@@ -245,6 +258,28 @@ int rvdd_egress_bits(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t 
         return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: n * H * W = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, H, W);
     ENTER(h);
     HIPCHK(h, launch_egress_bits(rgb, n, H, W, order, bit_depth, pattern, out, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_dpc(rvdd_t* h, const float* packed_in, float* packed_out, float* gray, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+             const rvdd_dpc_cfg* cfg, uint32_t* counts, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    DpcParams p;
+    RC(dpc_params(h, "rvdd_dpc", cfg, &p));
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: bit_depth must be 1..16, got %d", bit_depth);
+    if (hh < 2) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: hh must be >= 2 (the neighbours are mirrored about the site), got %d", hh);
+    if (ww < 2) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: ww must be >= 2 (the neighbours are mirrored about the site), got %d", ww);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: n must be >= 0, got %d", n);
+    if (n == 0) return RVDD_OK;
+    if (!packed_in || !packed_out) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: packed_in and packed_out are required");
+    if (dpc_blocks(n, hh, ww, dpc_wide(packed_in, packed_out, gray, ww), nullptr) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_dpc: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
+    // a thread reads the neighbours other threads write: in place is a race, and so is any other overlap
+    const uintptr_t a = reinterpret_cast<uintptr_t>(packed_in), b = reinterpret_cast<uintptr_t>(packed_out);
+    const uintptr_t bytes = (uintptr_t)n * 4 * (uintptr_t)hh * (uintptr_t)ww * sizeof(float);
+    if (a < b + bytes && b < a + bytes) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: packed_out must not overlap packed_in (%d frames of 4 x %d x %d floats each)", n, hh, ww);
+    ENTER(h);
+    HIPCHK(h, launch_dpc(packed_in, packed_out, gray, n, hh, ww, bit_depth, p, counts, static_cast<hipStream_t>(stream)));
     return RVDD_OK;
 }
 

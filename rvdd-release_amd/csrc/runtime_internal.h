@@ -232,6 +232,15 @@ struct rvdd_handle {
         std::vector<uint8_t> dgray_ok;   // per slot: dgray holds the output of the push before this one
     } st;
 
+    // rvdd_set_dpc: defective-pixel correction between the ingest and the ring of rvdd_video_push
+    struct Dpc {
+        bool on = false;
+        DpcParams p{};                   // the checked parameters (dpc_params)
+        float* in = nullptr;             // [B][4][hh][ww]: where a push with the stage on ingests the packed planes (allocated by the first)
+        unsigned* counts = nullptr;      // DEVICE [B][2]: hot / dead flags per slot since rvdd_dpc_counts last folded them into `total`
+        std::vector<uint64_t> total;     // [B][2] since the stage was last switched on
+    } dpc;
+
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
         const void* p[6];
@@ -419,5 +428,7 @@ int run_convnext(rvdd_t* h, const NetRun& run, const float* netin, const float* 
 // ---- step.hip
 int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s);
 // ---- ops.hip
+// the checks rvdd_dpc and rvdd_set_dpc share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
+int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* out);
 int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
                    void* stream, bool async);

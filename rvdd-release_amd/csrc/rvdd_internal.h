@@ -394,6 +394,20 @@ hipError_t launch_stream_scatter(const float* u, float* flows, const uint8_t* pa
 // positions before this push's and this push's: previous -> this push's where bit slot of to_pos is set, the other way elsewhere
 hipError_t launch_stream_dup(float* ring_prev, float* ring_pos, const int* slots, int nslots, uint64_t to_pos, int B, int64_t hw, hipStream_t s);
 
+// dpc.hip -- dynamic defective-pixel correction of packed frames (rvdd_dpc, the stage of rvdd_video_push behind rvdd_set_dpc)
+// k2_* = k_* * k_* rounded to f32 (formed once on the host); a side whose k_* is 0 is off; top is filled in by the launch
+struct DpcParams {
+    float k_hot, k_dead, k2_hot, k2_dead, a, b, floor, top;
+};
+// pin [n][4][hh][ww] -> pout (no overlap), flagged samples replaced by the median of their eight same-plane neighbours; gray [n][hh][ww]
+// (nullable) re-formed at the cells with a flag; counts [n][2] u32 (nullable): hot / dead flags per frame, added.  hh, ww >= 2.
+hipError_t launch_dpc(const float* pin, float* pout, float* gray, int n, int hh, int ww, int bit_depth, const DpcParams& p, unsigned* counts,
+                      hipStream_t s);
+// whether that launch takes the wide form (a thread owns four cells), and its grid (*per_frame: the blocks of one frame); -1 = more
+// than 2^31 - 1 blocks
+bool dpc_wide(const float* pin, const float* pout, const float* gray, int ww);
+int64_t dpc_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame);
+
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from
 // (seed, frame0 + image) then); lin_f32 / lin_u16 [n][2hh][2ww][3], gt_raw / noisy [n][hh][ww][4], each nullable

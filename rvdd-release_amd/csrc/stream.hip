@@ -52,6 +52,13 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     // option "stream_flow_from_denoised": the gray planes of the outputs, allocated by the first push that has it on
     const bool from_den = h->opt.stream_flow_from_denoised && !h->opt.no_warp;
     if (from_den && !st.dgray) RC(dmalloc(h, reinterpret_cast<void**>(&st.dgray), (size_t)B * hw * sizeof(float)));
+    // rvdd_set_dpc: the packed planes are ingested beside the ring and corrected into it; allocated by the first push that has the stage on
+    auto& dpc = h->dpc;
+    if (dpc.on && (hh < 2 || ww < 2)) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with rvdd_set_dpc hh and ww must be >= 2, got %d x %d cells", hh, ww);
+    if (dpc.on && !dpc.in) {
+        RC(dmalloc(h, reinterpret_cast<void**>(&dpc.counts), (size_t)B * 2 * sizeof(unsigned)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&dpc.in), (size_t)B * 4 * hw * sizeof(float)));
+    }
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
         if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
@@ -63,13 +70,16 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     const size_t esz = dtype == RVDD_RAW_U16 ? 2 : 4;
     const size_t frame_bytes = container ? 2 * (size_t)hh * (size_t)bits_row_bytes(ww, bit_depth) : 0;
     RC(for_each_run(B, [&](int b) { return !(ctl && ctl[b] == RVDD_PUSH_IDLE); }, [&](int b, int e) -> int {
-        if (container) {
+        float* ring_packed = st.packed + ((size_t)pos * B + b) * 4 * hw;
+        float* ring_gray = st.gray + ((size_t)pos * B + b) * hw;
+        float* packed = dpc.on ? dpc.in + (size_t)b * 4 * hw : ring_packed;
+        if (container)
             HIPCHK(h, launch_ingest_bits(static_cast<const uint8_t*>(frames) + (size_t)b * frame_bytes, container - 1, e - b, hh, ww, bit_depth,
-                                         st.packed + ((size_t)pos * B + b) * 4 * hw, st.gray + ((size_t)pos * B + b) * hw, s));
-            return RVDD_OK;
-        }
-        HIPCHK(h, launch_ingest_raw(static_cast<const char*>(frames) + (size_t)b * 4 * hw * esz, dtype, layout, e - b, hh, ww, bit_depth,
-                                    st.packed + ((size_t)pos * B + b) * 4 * hw, st.gray + ((size_t)pos * B + b) * hw, s));
+                                         packed, ring_gray, s));
+        else
+            HIPCHK(h, launch_ingest_raw(static_cast<const char*>(frames) + (size_t)b * 4 * hw * esz, dtype, layout, e - b, hh, ww, bit_depth,
+                                        packed, ring_gray, s));
+        if (dpc.on) HIPCHK(h, launch_dpc(packed, ring_packed, ring_gray, e - b, hh, ww, bit_depth, dpc.p, dpc.counts + 2 * (size_t)b, s));
         return RVDD_OK;
     }));
     // Per slot: which frame of its video this push outputs (centre; -1: none).  The plain rule is centre = n - 1 - future >= 1.  Option
@@ -146,5 +156,42 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         HIPCHK(h, launch_gray_of_rgb(out_rgb, B, hh, ww, h->opt.bayer, bit_depth, st.dgray, s));
         for (int b : ready) st.dgray_ok[(size_t)b] = centre[(size_t)b] >= 1 && st.count[(size_t)b] > 0;      // not a head's, not a tail's
     }
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_set_dpc(rvdd_t* h, const rvdd_dpc_cfg* cfg) {
+    if (!h) return RVDD_ERR_ARG;
+    DpcParams p{};
+    if (cfg) RC(dpc_params(h, "rvdd_set_dpc", cfg, &p));
+    ENTER(h);
+    HIPCHK(h, hipDeviceSynchronize());      // pushes in flight keep the parameters they were enqueued with anyway; the counters must be at rest
+    auto& dpc = h->dpc;
+    if (cfg && !dpc.on) {                   // switched on: the totals start again
+        dpc.total.assign((size_t)h->cfg.batch * 2, 0);
+        if (dpc.counts) HIPCHK(h, hipMemset(dpc.counts, 0, (size_t)h->cfg.batch * 2 * sizeof(unsigned)));
+    }
+    dpc.on = cfg != nullptr;
+    if (cfg) dpc.p = p;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_dpc_counts(rvdd_t* h, uint64_t* hot_dead, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (!hot_dead) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_counts: hot_dead is required");
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto& dpc = h->dpc;
+    const size_t n = (size_t)h->cfg.batch * 2;
+    dpc.total.resize(n, 0);
+    if (dpc.counts) {                       // fold what the device counted since the last call into the totals, and start it at zero
+        std::vector<unsigned> got(n, 0);
+        HIPCHK(h, hipMemcpyAsync(got.data(), dpc.counts, n * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemsetAsync(dpc.counts, 0, n * sizeof(unsigned), s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        for (size_t i = 0; i < n; ++i) dpc.total[i] += got[i];
+    } else {
+        HIPCHK(h, hipStreamSynchronize(s));
+    }
+    for (size_t i = 0; i < n; ++i) hot_dead[i] = dpc.total[i];
     return RVDD_OK;
 }

@@ -32,6 +32,16 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
   --all_frames        write EVERY input frame (option "stream_all_frames"): also frame 0 of a video -- denoised with itself as the
                       previous frame, a zero flow and a fresh recurrence; frame 1 then starts as always -- and, with a future frame,
                       the last frame, with itself as the next frame.  The files of frames 1 .. N-1-future keep their bytes.
+  --dpc K             defective-pixel correction on the device, between the ingest and the frames the stream keeps (`rvdd_set_dpc`):
+                      a sample that lies above the largest (hot) or below the smallest (dead, stuck low) of its eight same-colour
+                      neighbours by more than K standard deviations of the noise at their median is replaced by that median; TV-L1
+                      and the network see the corrected frames.  K = 4 flags about 1e-5 of the samples of defect-free noise
+                      (DESIGN.md 4.14).  Needs exactly one of
+  --dpc_iso ISO       the reference's noise curve of ISO 3200 / 12800, rescaled from 12 bits to --bit_depth, or
+  --dpc_noise a,b[,floor]   the curve var = a * m - b in DN of the frames' own bit depth, and the least variance (default 1).
+  --dpc_dead K        another threshold for the dead side; 0 switches that side off.
+                      Prints, per video, `dpc: <hot> hot, <dead> dead samples corrected in <frames> frames`.  Without --dpc the
+                      output files keep their bytes.
 Videos of different frame sizes are grouped by size and run one group after the other, one runtime per size.
 """
 from __future__ import annotations
@@ -47,7 +57,7 @@ import torch
 
 from . import _lib
 from . import tiffio
-from .runtime import BAYER_PATTERNS, BITS_DEPTHS, bits_row_bytes, raw_frames_to_device
+from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, dpc_iso_curve, raw_frames_to_device
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
 # --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
@@ -93,6 +103,37 @@ def deal_slots(lengths: Sequence[int], slots: int, tail: int = 0) -> List[List[T
         steps.append(step)
 
 
+def dpc_arguments(dpc, dpc_dead, dpc_iso, dpc_noise, bit_depth):
+    """--dpc / --dpc_dead / --dpc_iso / --dpc_noise -> None (no --dpc) or (k_hot, k_dead, noise_a, noise_b, var_floor) as Python
+    doubles (`runtime.dpc_cfg` rounds each to f32 once); SystemExit where the flags do not fit together."""
+    if dpc is None:
+        if dpc_dead is not None or dpc_iso is not None or dpc_noise is not None:
+            raise SystemExit("--dpc_dead, --dpc_iso and --dpc_noise belong to --dpc K")
+        return None
+    if (dpc_iso is None) == (dpc_noise is None):
+        raise SystemExit("--dpc needs exactly one of --dpc_iso {%s} and --dpc_noise a,b[,floor]" % ','.join(str(k) for k in DPC_ISO_CURVES))
+    k_dead = dpc if dpc_dead is None else dpc_dead
+    if not (dpc >= 0 and k_dead >= 0 and dpc < float("inf") and k_dead < float("inf")):
+        raise SystemExit("--dpc and --dpc_dead are thresholds >= 0, got %r and %r" % (dpc, k_dead))
+    floor = 1.0
+    if dpc_iso is not None:
+        if dpc_iso not in DPC_ISO_CURVES:
+            raise SystemExit("--dpc_iso must be one of %s, got %r" % (', '.join(str(k) for k in DPC_ISO_CURVES), dpc_iso))
+        a, b = dpc_iso_curve(dpc_iso, bit_depth)
+    else:
+        f = dpc_noise.split(',')
+        if len(f) not in (2, 3):
+            raise SystemExit("--dpc_noise takes a,b or a,b,floor")
+        try:
+            a, b = float(f[0]), float(f[1])
+            floor = float(f[2]) if len(f) == 3 else 1.0
+        except ValueError:
+            raise SystemExit("--dpc_noise takes numbers a,b[,floor], got %r" % dpc_noise)
+        if not floor > 0:
+            raise SystemExit("--dpc_noise: the floor must be > 0, got %r" % floor)
+    return (float(dpc), float(k_dead), a, b, floor)
+
+
 def _parse(argv):
     from .options import parse
     p = argparse.ArgumentParser(add_help=False)
@@ -101,6 +142,10 @@ def _parse(argv):
     p.add_argument('--out_format', type=str, default='f32', help=', '.join(OUT_FORMATS))
     p.add_argument('--out_bit_depth', type=int, default=None, help='bit depth of the sensor formats (default: --bit_depth)')
     p.add_argument('--all_frames', action='store_true', help='write every input frame, the first and the last of a video too')
+    p.add_argument('--dpc', type=float, default=None, help='defective-pixel correction: threshold K in standard deviations (both sides)')
+    p.add_argument('--dpc_dead', type=float, default=None, help='threshold of the dead side (default: --dpc; 0 = off)')
+    p.add_argument('--dpc_iso', type=int, default=None, help='the noise curve of ISO 3200 / 12800, rescaled to --bit_depth')
+    p.add_argument('--dpc_noise', type=str, default=None, help='a,b[,floor]: var = a * m - b in DN of the frames, the least variance')
     own, rest = p.parse_known_args(argv)
     if own.out_format not in OUT_FORMATS:
         raise SystemExit("--out_format %r is not one of %s" % (own.out_format, ', '.join(OUT_FORMATS)))
@@ -111,6 +156,7 @@ def _parse(argv):
         raise SystemExit("--out_bit_depth must be 1..16, got %d" % opt.out_bit_depth)
     if OUT_FORMATS[opt.out_format][0] == "bits" and opt.out_bit_depth not in BITS_DEPTHS:
         raise SystemExit("--out_format %s needs --out_bit_depth (default: --bit_depth) 10, 12 or 14, got %d" % (opt.out_format, opt.out_bit_depth))
+    opt.dpc = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth))
     if opt.raw_container is not None:
         if opt.raw_container != 'mipi':
             raise SystemExit("--raw_container %r: headerless frames are 'mipi' (packed TIFFs are recognised by themselves)" % opt.raw_container)
@@ -161,6 +207,9 @@ def main(argv=None) -> dict:
         rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
         rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
         rt.set_option("stream_all_frames", int(opt.all_frames))
+        rt.set_dpc(None if opt.dpc is None else dpc_cfg(*opt.dpc))
+        dpc_seen = rt.dpc_counts() if opt.dpc is not None else None      # rvdd_dpc_counts at the end of the slot's last video
+        dpc_frames = [0] * B                        # frames the slot's video has pushed
         container = dataset.container               # None, or "msb" / "mipi": the frames stay bit-packed up to the device
         if layout == "bits" and sample == "mipi" and W % (2 if depth == 12 else 4):
             raise SystemExit("--out_format mosaic_mipi: a RAW%d row is groups of %d pixels, the frames are %d wide" % (depth, 2 if depth == 12 else 4, W))
@@ -182,12 +231,16 @@ def main(argv=None) -> dict:
                 files = rt.egress_bits(out, sample, depth, out=files) if layout == "bits" else rt.egress(out, layout, sample, depth, out=files)
                 host = files.cpu().numpy()
                 host = host.view(np.uint16) if host.dtype == np.int16 else host
-            ended = False
+            ended, ends = False, []
             for b, (c, vid, k) in enumerate(step):
                 if vid < 0:
                     continue
                 key, frames = videos[vid]
-                ended = ended or k == len(frames) - (0 if opt.all_frames and fut else 1)      # the step that ends the video
+                last = k == len(frames) - (0 if opt.all_frames and fut else 1)      # the step that ends the video
+                ended = ended or last
+                dpc_frames[b] = min(k + 1, len(frames))
+                if last:
+                    ends.append((b, key))
                 if not valid[b]:
                     continue
                 path = frames[k - fut]                  # the centre frame
@@ -206,6 +259,12 @@ def main(argv=None) -> dict:
                 written += 1
             if ended:
                 rt.set_option("tvl1_async", 0)          # synchronises: reports a TV-L1 exchange of this video's pushes that gave up
+                if opt.dpc is not None:                 # ... and before the slot's next FIRST push: the difference is this video's
+                    now = rt.dpc_counts()
+                    for b, key in ends:
+                        print('dpc: %d hot, %d dead samples corrected in %d frames (%s)'
+                              % (now[b][0] - dpc_seen[b][0], now[b][1] - dpc_seen[b][1], dpc_frames[b], key))
+                        dpc_seen[b] = now[b]
         rt.set_option("tvl1_async", 0)
     torch.cuda.synchronize(dev)
     dt = time.time() - t0

@@ -39,6 +39,25 @@ def bits_row_bytes(width: int, bit_depth: int, order: str = "msb") -> int:
     return (int(width) * int(bit_depth) + 7) // 8
 
 
+# the reference's noise curves var(m) = ka * m - kb in 12-bit DN (dataset/generate_raw_from_RGB.py; rvdd_unprocess draws with them)
+DPC_ISO_CURVES = {3200: (8.0034, 2043.51144), 12800: (28.3015, 6307.62081)}
+
+
+def dpc_iso_curve(iso: int, bit_depth: int = 12) -> Tuple[float, float]:
+    """The reference's noise curve of `iso` (3200 / 12800) in DN of `bit_depth`: with s = (2^bit_depth - 1) / 4095 a sample scales by s
+    and its variance by s^2, so a = s * ka and b = s^2 * kb -- formed in double; the C ABI rounds them to f32 once."""
+    if iso not in DPC_ISO_CURVES:
+        raise ValueError(f"dpc_iso_curve: iso {iso!r} is not one of {', '.join(str(k) for k in DPC_ISO_CURVES)}")
+    ka, kb = DPC_ISO_CURVES[iso]
+    s = (2 ** int(bit_depth) - 1) / 4095.0
+    return s * ka, s * s * kb
+
+
+def dpc_cfg(k_hot: float, k_dead: float, noise_a: float, noise_b: float, var_floor: float = 1.0) -> "_lib.RvddDpcCfg":
+    """struct rvdd_dpc_cfg of Python doubles, each rounded to f32 once"""
+    return _lib.RvddDpcCfg(float(k_hot), float(k_dead), float(noise_a), float(noise_b), float(var_floor))
+
+
 def raw_frames_to_device(frames, device) -> torch.Tensor:
     """Host sensor frames (a numpy array or CPU tensor of uint16 / int16 / float32) -> a tensor on `device` that
     `ingest_raw` / `video_push` accept.  uint16 arrays travel as their int16 view: the bytes are what crosses the ABI."""
@@ -384,6 +403,44 @@ class RvddRuntime:
         self._check(self.lib.rvdd_egress_bits(self.h, _ptr(rgb), n, H, W, BITS_ORDERS[order], int(bit_depth), pat, _ptr(out),
                                               self._stream()), "rvdd_egress_bits")
         return out
+
+    # -- defective-pixel correction -----------------------------------------------
+    def dpc(self, packed: torch.Tensor, cfg, bit_depth: int = 12, gray: Optional[torch.Tensor] = None,
+            counts: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Hot and stuck samples of packed frames [n,4,hh,ww] (as `ingest_raw` writes them) replaced by the median of their eight
+        same-colour neighbours (rvdd_dpc; `cfg`: `dpc_cfg(k_hot, k_dead, noise_a, noise_b, var_floor)`, the curve in DN of
+        `bit_depth`).  -> the corrected frames (`out`, or a new tensor; never `packed` itself).  gray [n,hh,ww]: patched in place at
+        the cells with a flag; counts: int32 / uint32 [n,2] on the device, the hot / dead flags of every frame are added to it."""
+        if not torch.is_tensor(packed) or packed.dim() != 4 or packed.shape[1] != 4:
+            raise RuntimeError(f"dpc: packed is [n,4,hh,ww], got {tuple(getattr(packed, 'shape', ()))}")
+        n, _, hh, ww = packed.shape
+        packed = _chk_dev(packed, packed.shape, "packed", self.device)
+        if out is None:
+            out = torch.empty_like(packed)
+        else:
+            _chk_dev(out, packed.shape, "out", self.device)
+            assert out.is_contiguous()
+        if gray is not None:
+            _chk_dev(gray, (n, hh, ww), "gray", self.device)
+            assert gray.is_contiguous()
+        if counts is not None:
+            if not counts.is_cuda or counts.device.index != self.device or counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) \
+                    or tuple(counts.shape) != (n, 2) or not counts.is_contiguous():
+                raise RuntimeError(f"dpc: counts is a contiguous int32 / uint32 tensor [{n},2] on cuda:{self.device}")
+        self._check(self.lib.rvdd_dpc(self.h, _ptr(packed), _ptr(out), _ptr(gray), n, hh, ww, int(bit_depth), C.byref(cfg), _ptr(counts),
+                                      self._stream()), "rvdd_dpc")
+        return out
+
+    def set_dpc(self, cfg=None):
+        """The correction as a stage of `video_push`, between the ingest and the kept frames (rvdd_set_dpc): cfg = `dpc_cfg(...)`,
+        None = off (the default)."""
+        self._check(self.lib.rvdd_set_dpc(self.h, None if cfg is None else C.byref(cfg)), "rvdd_set_dpc")
+
+    def dpc_counts(self) -> List[Tuple[int, int]]:
+        """[(hot, dead)] * B: the samples the stage corrected per slot since it was last switched on (rvdd_dpc_counts; synchronises)."""
+        out = (C.c_uint64 * (2 * self.B))()
+        self._check(self.lib.rvdd_dpc_counts(self.h, out, self._stream()), "rvdd_dpc_counts")
+        return [(int(out[2 * b]), int(out[2 * b + 1])) for b in range(self.B)]
 
     def video_push(self, frames: torch.Tensor, ctl=None, bit_depth: int = 12, layout: str = "mosaic", out=None,
                    container: Optional[str] = None):

@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""Time of rvdd_dpc alone on 1280x720 frames (640 x 360 cells, the wide form), n = 8, beside rvdd_ingest_raw (a u16 mosaic in, both
+outputs) -- the kernel it follows inside rvdd_video_push -- in the same process.  rvdd_timer_start / rvdd_timer_stop_ms over
+LAUNCHES launches after a warm-up.  The frames: a flat 12-bit scene with the noise of the ISO 3200 curve and one hot sample in 10^4.
+Prints one line per kernel and appends them to profiles/dpc_kernel.txt (or the file named by DPC_BENCH_OUT).
+
+Per line: microseconds per frame, and the bytes per raw cell over that time: the stage reads 16 and writes 16 (the neighbours come
+from the cache), the ingest reads 8 and writes 20."""
+import os
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tools"))
+import kernel_resources  # noqa: E402
+from rvdd_release_amd import _lib  # noqa: E402
+from rvdd_release_amd.runtime import dpc_cfg, dpc_iso_curve  # noqa: E402
+from rvdd_release_amd.util._ops import ops_runtime  # noqa: E402
+
+N, H, W = int(os.environ.get("BATCH", "8")), 720, 1280
+LAUNCHES, WARMUP = int(os.environ.get("LAUNCHES", "200")), 20
+
+
+def main():
+    assert torch.cuda.is_available(), "dpc_bench needs a GPU"
+    rt = ops_runtime(0)
+    hh, ww = H // 2, W // 2
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    a, b = dpc_iso_curve(3200, 12)
+    m = 0.45 * 4095
+    dn = (m + (a * m - b) ** 0.5 * torch.randn(N, H, W, device="cuda", generator=gen)).round().clamp(0, 4095)
+    dn[torch.rand(N, H, W, device="cuda", generator=gen) < 1e-4] = 4095
+    mosaic = dn.to(torch.int16)
+    packed, gray = rt.ingest_raw(mosaic, 12, "mosaic")
+    out = torch.empty_like(packed)
+    counts = torch.zeros(N, 2, dtype=torch.int32, device="cuda")
+    cfg = dpc_cfg(4, 4, a, b)
+    vgpr = {r["name"]: r.get("vgpr_count", 0) for r in kernel_resources.kernel_table(_lib.LIB_PATH)}
+
+    def timed(fn):
+        for _ in range(WARMUP):
+            fn()
+        rt.timer_start()
+        for _ in range(LAUNCHES):
+            fn()
+        return rt.timer_stop_ms() * 1e3 / LAUNCHES        # us per launch
+
+    def ingest():
+        rc = rt.lib.rvdd_ingest_raw(rt.h, mosaic.data_ptr(), _lib.RAW_U16, _lib.RAW_MOSAIC, N, hh, ww, 12, packed.data_ptr(), gray.data_ptr(), rt._stream())
+        assert rc == 0, rt.lib.rvdd_last_error(rt.h)
+
+    def dpc():
+        rc = rt.lib.rvdd_dpc(rt.h, packed.data_ptr(), out.data_ptr(), gray.data_ptr(), N, hh, ww, 12, cfg, counts.data_ptr(), rt._stream())
+        assert rc == 0, rt.lib.rvdd_last_error(rt.h)
+
+    lines = []
+    for name, fn, cell_bytes, kernel in (("rvdd_ingest_raw (u16 mosaic -> packed + gray)", ingest, 8 + 20, "ingest_raw_kernel<unsigned short, 0, true>"),
+                                         ("rvdd_dpc (packed -> packed, gray patched, counts)", dpc, 16 + 16, "dpc_kernel<4>")):
+        us = timed(fn)
+        lines.append("%-52s %8.2f us/frame  %8.1f us/launch of %d frames  %7.1f GB/s of %d B/cell  %s vgpr"
+                     % (name, us / N, us, N, N * hh * ww * cell_bytes / us / 1e3, cell_bytes, vgpr.get(kernel)))
+    torch.cuda.synchronize()
+    flagged = counts.sum(dim=0).tolist()
+    lines.append("flags per launch: %.1f hot, %.1f dead in %d samples" % (flagged[0] / (LAUNCHES + WARMUP), flagged[1] / (LAUNCHES + WARMUP), N * H * W))
+    path = os.environ.get("DPC_BENCH_OUT", os.path.join(REPO, "profiles", "dpc_kernel.txt"))
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "a") as f:
+        for ln in lines:
+            print(ln)
+            f.write(ln + "\n")
+
+
+if __name__ == "__main__":
+    main()
