@@ -466,6 +466,67 @@ int rvdd_set_dpc(rvdd_t* h, const rvdd_dpc_cfg* cfg /* NULL = off, the default *
  * synchronises it: call it where the loop synchronises anyway.  All zeros on a handle that never had the stage on. */
 int rvdd_dpc_counts(rvdd_t* h, uint64_t* hot_dead /* HOST [cfg.batch,2] */, void* stream /* synchronised */);
 
+/* The sensor's noise curve var(m) = a * m - b (what rvdd_dpc_cfg's noise_a / noise_b ask for) estimated from the footage itself:
+ * rvdd_noise_hist gathers block statistics of packed frames into a histogram on the device, rvdd_noise_fit fits the curve to a host
+ * copy of it.  The rule, on packed [n,4,hh,ww] in [-1,1] as rvdd_ingest_raw / rvdd_ingest_bits / rvdd_dpc write it, with
+ * top = (float)(2^bit_depth - 1) and dn(v) = ((v + 1) * 0.5) * top as in rvdd_dpc, every operation rounded to f32 on its own (no fused
+ * multiply-add), so that every integer below is reproducible in NumPy (tests/noise_ref.py):
+ *   blocks  each channel plane is cut into 8 x 8 blocks anchored at (0, 0): hh / 8 x ww / 8 whole blocks; rows and columns beyond
+ *           the last whole block are ignored; hh < 8 or ww < 8 gives zero blocks, which is valid.
+ *   per block, x[r][c] = dn(sample):
+ *     rs_r = ((((((x[r][0] + x[r][1]) + x[r][2]) + ...) + x[r][7]);  s = ((rs_0 + rs_1) + ...) + rs_7;  m = s * (1/64)
+ *     d    = x[r][c] - (x[r][c-1] + x[r][c+1]) * 0.5 for c = 1..6: a horizontal second difference, which cancels linear ramps and
+ *            has variance 1.5 sigma^2;  rq_r = the sum of d * d over c = 1..6 in that order, from 0;  q = ((rq_0 + rq_1) + ...) + rq_7
+ *     v    = q * (float)(1.0 / 72.0)                          the block's variance estimate
+ *   a block is CLIPPED if any of its 64 samples is <= 0 or >= top in DN, DEGENERATE if it is not clipped and v == 0; neither enters
+ *   the histogram.  Every other block adds one to hist[i][j] and (int64)rint(m * 16) to msum[i]:
+ *     i = (int)(m * (64 / 2^bit_depth))                       the mean bin, 0..63 (the scale is a power of two)
+ *     j = clamp((bits(v) >> 19) - ((127 - 6) << 4), 0, 511)   the exponent and the top four mantissa bits of v: 16 sub-bins per
+ *                                                             octave from 2^-6 to 2^26, integer work only
+ *   counters = { blocks seen, clipped, degenerate, 0 }.
+ * Every add is an integer atomic, so the totals do not depend on the order of arrival: two runs give the same bits, and a batch in
+ * one call gives what its halves give in two.  Inputs are assumed finite: which counts a block with a NaN or an inf adds to is
+ * unspecified, but both keys are clamped, and nothing outside the tensors is read or written whatever the input. */
+typedef struct rvdd_noise_acc {
+    uint32_t hist[64][512];   /* [mean bin][variance sub-bin] */
+    uint64_t msum[64];        /* sum of (int64)rint(m * 16) over the blocks of the mean bin */
+    uint64_t counters[4];     /* blocks seen, clipped, degenerate, reserved (0) */
+} rvdd_noise_acc;
+
+/* Adds the blocks of `packed` to *acc (DEVICE, 131616 bytes, 8-byte aligned; the caller zeroes it once and may accumulate any
+ * number of calls, frame sizes and videos of one bit depth into it).  One kernel, a lane per block; equal keys are combined in a
+ * table in the workgroup's LDS, so that a flat scene, whose blocks all share a handful of keys, issues one atomic per distinct key
+ * and workgroup.  With ww % 4 == 0 and `packed` 16-byte aligned a row of a block is two 16-byte loads, single floats otherwise:
+ * same integers either way.
+ * RVDD_ERR_ARG (the message names the argument) and nothing launched: NULL acc, or one not 8-byte aligned; bit_depth outside 1..16; n, hh or ww < 0; NULL packed
+ * with n > 0 and at least one block; a launch of more than 2^31 - 1 workgroups.  n = 0 or zero blocks does nothing.  Asynchronous
+ * and stream-ordered; nothing is read back. */
+int rvdd_noise_hist(rvdd_t* h, const float* packed /* [n,4,hh,ww] */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+                    rvdd_noise_acc* acc /* DEVICE, accumulated; caller zeroes */, void* stream);
+
+/* The fit, in f64 on the host; needs neither a device nor a handle (errors go where rvdd_create's go: rvdd_last_error(NULL)).
+ *   usable bins: the mean bins i with count_i = sum_j hist[i][j] >= 16;  m_i = msum[i] / 16 / count_i
+ *   v_i = the lower quartile of row i of the histogram / C_Q: the first sub-bin j at which the cumulative count reaches
+ *         0.25 * count_i, interpolated linearly inside it between its edges -- the edge of sub-bin j is the f32 whose bits are
+ *         (j + ((127 - 6) << 4)) << 19 -- and divided by C_Q = 0.8051, the lower quartile of the rule's v on unit white Gaussian samples
+ *         (tools/noise_cq.py).  The lower quartile and not the mean or the median because texture only ever raises v: with a third
+ *         of the blocks textured the predicted sigma comes out a few per cent high, about half of what the median gives; an
+ *         over-estimate is the safe side for rvdd_dpc.
+ *   a, b: weighted least squares of v = a * m - b over the usable bins with weights count_i / v_i^2
+ *   rms = sqrt(sum_i count_i ((v_i - (a m_i - b)) / v_i)^2 / sum_i count_i)
+ * RVDD_ERR_ARG: NULL acc_host / out, bit_depth outside 1..16.  RVDD_ERR_STATE, *out untouched, when fewer than 4 bins are usable or
+ * their means span less than 2^bit_depth / 16: the message says which (the footage has too little tonal range, or too few frames).
+ * The estimate assumes one camera setting -- one gain, one curve -- for everything accumulated. */
+typedef struct rvdd_noise_curve {
+    double a, b;              /* var(m) = a * m - b in DN of bit_depth */
+    double m_min, m_max;      /* the smallest and largest bin mean used, DN */
+    double rms;               /* weighted RMS of the relative residuals */
+    uint64_t blocks;          /* blocks in the usable bins */
+    int32_t bins;             /* usable bins */
+    int32_t reserved;         /* 0 */
+} rvdd_noise_curve;
+int rvdd_noise_fit(const rvdd_noise_acc* acc_host /* HOST copy */, int32_t bit_depth, rvdd_noise_curve* out);
+
 /* ---- raw datasets from sRGB video ------------------------------------------- */
 
 /* dataset/generate_raw_from_RGB.py (:45-127 single_image_rgb2raw, :168-189 the 12-bit range, the percentile matching to CRVD

@@ -36,6 +36,17 @@ class RvddDpcCfg(C.Structure):
                 ("var_floor", C.c_float)]
 
 
+class RvddNoiseAcc(C.Structure):
+    """struct rvdd_noise_acc (rvdd_noise_hist, rvdd_noise_fit): 131616 bytes"""
+    _fields_ = [("hist", (C.c_uint32 * 512) * 64), ("msum", C.c_uint64 * 64), ("counters", C.c_uint64 * 4)]
+
+
+class RvddNoiseCurve(C.Structure):
+    """struct rvdd_noise_curve (rvdd_noise_fit)"""
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("m_min", C.c_double), ("m_max", C.c_double), ("rms", C.c_double),
+                ("blocks", C.c_uint64), ("bins", C.c_int32), ("reserved", C.c_int32)]
+
+
 # symbol -> (restype, argtypes); exactly the functions include/rvdd.h declares
 _P = C.c_void_p
 _PROTOS = {
@@ -72,6 +83,8 @@ _PROTOS = {
     "rvdd_dpc": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddDpcCfg), _P, _P]),
     "rvdd_set_dpc": (C.c_int, [_P, C.POINTER(RvddDpcCfg)]),
     "rvdd_dpc_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), _P]),
+    "rvdd_noise_hist": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rvdd_noise_fit": (C.c_int, [C.POINTER(RvddNoiseAcc), C.c_int32, C.POINTER(RvddNoiseCurve)]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                  _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),

@@ -1,0 +1,89 @@
+// rvdd_noise_fit: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
+// Host code only, f64, no device and no handle; compiled -ffp-contract=off so that tests/noise_ref.py, which runs the same sums in
+// the same order in Python doubles, gets the same numbers.
+#include "runtime_internal.h"
+
+namespace {
+
+// the lower quartile of the rule's block variance on unit white Gaussian samples; tools/noise_cq.py (seed 20261019, 4194304 blocks):
+//   "mean 1.000094  C_Q (lower quartile) 0.805112  C_MED (median) 0.972282  (standard error about 1.4e-04)"
+constexpr double kCQ = 0.8051;
+constexpr int kMinCount = 16, kMinBins = 4;
+
+// the lower edge of variance sub-bin j
+double noise_edge(int j) {
+    const uint32_t bits = (uint32_t)(j + ((127 - 6) << 4)) << 19;
+    float f;
+    std::memcpy(&f, &bits, sizeof f);
+    return (double)f;
+}
+
+// the value at which the cumulative count of a histogram row of `count` > 0 blocks reaches q * count, linear inside its sub-bin
+double noise_quantile(const uint32_t* row, uint64_t count, double q) {
+    const double target = q * (double)count;
+    uint64_t cum = 0;
+    for (int j = 0; j < 512; ++j) {
+        const uint64_t c = row[j];
+        if (c > 0 && (double)(cum + c) >= target) {
+            const double lo = noise_edge(j), hi = noise_edge(j + 1);
+            return lo + ((target - (double)cum) / (double)c) * (hi - lo);
+        }
+        cum += c;
+    }
+    return noise_edge(512);      // not reached: the counts add up to `count`
+}
+
+}  // namespace
+
+extern "C" int rvdd_noise_fit(const rvdd_noise_acc* acc, int32_t bit_depth, rvdd_noise_curve* out) {
+    if (!acc) return fail(nullptr, RVDD_ERR_ARG, "rvdd_noise_fit: acc_host is required");
+    if (!out) return fail(nullptr, RVDD_ERR_ARG, "rvdd_noise_fit: out is required");
+    if (bit_depth < 1 || bit_depth > 16) return fail(nullptr, RVDD_ERR_ARG, "rvdd_noise_fit: bit_depth must be 1..16, got %d", bit_depth);
+    double ms[64], vs[64], ns[64];
+    int bins = 0;
+    uint64_t blocks = 0;
+    for (int i = 0; i < 64; ++i) {
+        uint64_t count = 0;
+        for (int j = 0; j < 512; ++j) count += acc->hist[i][j];
+        if (count < (uint64_t)kMinCount) continue;
+        ms[bins] = (double)acc->msum[i] / 16.0 / (double)count;
+        vs[bins] = noise_quantile(acc->hist[i], count, 0.25) / kCQ;
+        ns[bins] = (double)count;
+        blocks += count;
+        ++bins;
+    }
+    if (bins < kMinBins)
+        return fail(nullptr, RVDD_ERR_STATE, "rvdd_noise_fit: %d usable mean bins (of %d blocks or more), at least %d are needed: too few frames, or "
+                    "footage that is clipped or constant almost everywhere (%llu blocks seen, %llu clipped, %llu constant)", bins, kMinCount,
+                    kMinBins, (unsigned long long)acc->counters[0], (unsigned long long)acc->counters[1], (unsigned long long)acc->counters[2]);
+    double m_min = ms[0], m_max = ms[0];
+    for (int k = 1; k < bins; ++k) {
+        m_min = ms[k] < m_min ? ms[k] : m_min;
+        m_max = ms[k] > m_max ? ms[k] : m_max;
+    }
+    const double range = (double)(1u << bit_depth);
+    if (m_max - m_min < range / 16.0)
+        return fail(nullptr, RVDD_ERR_STATE, "rvdd_noise_fit: the footage has too little tonal range: the %d usable bin means span %.1f DN (%.1f .. "
+                    "%.1f), a curve needs %.0f (1/16 of 2^%d)", bins, m_max - m_min, m_min, m_max, range / 16.0, bit_depth);
+    double ws[64], sw = 0.0, swm = 0.0, swv = 0.0;
+    for (int k = 0; k < bins; ++k) {
+        ws[k] = ns[k] / (vs[k] * vs[k]);
+        sw += ws[k];
+        swm += ws[k] * ms[k];
+        swv += ws[k] * vs[k];
+    }
+    const double mbar = swm / sw, vbar = swv / sw;      // centred: the normal equations lose no digits to the means' offset
+    double smm = 0.0, smv = 0.0;
+    for (int k = 0; k < bins; ++k) {
+        smm += ws[k] * ((ms[k] - mbar) * (ms[k] - mbar));
+        smv += ws[k] * ((ms[k] - mbar) * (vs[k] - vbar));
+    }
+    const double a = smv / smm, b = a * mbar - vbar;
+    double sr = 0.0;
+    for (int k = 0; k < bins; ++k) {
+        const double r = (vs[k] - (a * ms[k] - b)) / vs[k];
+        sr += ns[k] * (r * r);
+    }
+    *out = rvdd_noise_curve{a, b, m_min, m_max, std::sqrt(sr / (double)blocks), blocks, bins, 0};
+    return RVDD_OK;
+}

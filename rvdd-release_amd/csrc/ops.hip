@@ -283,6 +283,24 @@ int rvdd_dpc(rvdd_t* h, const float* packed_in, float* packed_out, float* gray, 
     return RVDD_OK;
 }
 
+int rvdd_noise_hist(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, rvdd_noise_acc* acc, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (!acc) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: acc is required");
+    if (reinterpret_cast<uintptr_t>(acc) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: acc must be 8-byte aligned (its sums are 64-bit atomics)");
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: bit_depth must be 1..16, got %d", bit_depth);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: n must be >= 0, got %d", n);
+    if (hh < 0) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: hh must be >= 0, got %d", hh);
+    if (ww < 0) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: ww must be >= 0, got %d", ww);
+    const int64_t groups = noise_groups(n, hh, ww, nullptr);
+    if (groups < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 workgroups", n, hh, ww);
+    if (groups == 0) return RVDD_OK;       // no frame, or frames smaller than one block
+    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: packed is required");
+    ENTER(h);
+    HIPCHK(h, launch_noise_hist(packed, n, hh, ww, bit_depth, acc, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 // the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine
 static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int32_t W) {
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);

@@ -408,6 +408,16 @@ hipError_t launch_dpc(const float* pin, float* pout, float* gray, int n, int hh,
 bool dpc_wide(const float* pin, const float* pout, const float* gray, int ww);
 int64_t dpc_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame);
 
+// noise.hip -- block statistics of packed frames for the noise-curve estimate (rvdd_noise_hist)
+struct rvdd_noise_acc;
+typedef rvdd_noise_acc NoiseAcc;      // include/rvdd.h: u32 hist[64][512], u64 msum[64], u64 counters[4]
+// the 8 x 8 blocks of packed [n][4][hh][ww] added to *acc (DEVICE), a lane per block; zero blocks launches nothing
+hipError_t launch_noise_hist(const float* packed, int n, int hh, int ww, int bit_depth, NoiseAcc* acc, hipStream_t s);
+// whether that launch takes the wide form (two 16-byte loads per block row), and its grid (*blocks: the blocks of the call; n, hh, ww
+// >= 0); -1 = more than 2^31 - 1 workgroups
+bool noise_wide(const float* packed, int ww);
+int64_t noise_groups(int n, int hh, int ww, int64_t* blocks);
+
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from
 // (seed, frame0 + image) then); lin_f32 / lin_u16 [n][2hh][2ww][3], gt_raw / noisy [n][hh][ww][4], each nullable

@@ -39,6 +39,12 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       (DESIGN.md 4.14).  Needs exactly one of
   --dpc_iso ISO       the reference's noise curve of ISO 3200 / 12800, rescaled from 12 bits to --bit_depth, or
   --dpc_noise a,b[,floor]   the curve var = a * m - b in DN of the frames' own bit depth, and the least variance (default 1).
+  --dpc_noise auto[,floor]  the curve estimated from the run's own footage before streaming starts (`rvdd_noise_hist`, `rvdd_noise_fit`;
+                      python -m rvdd_release_amd.noise is the same estimate on its own): the first --dpc_noise_frames K (default 4)
+                      frames of up to 16 of the videos.  Prints `noise: {"a": ..., "b": ..., ...}` -- a and b with 17 digits, so that
+                      --dpc_noise a,b repeats the run exactly -- and which checkpoint family's curve lies nearest.
+                      Assumes ONE camera setting (one gain) for all videos of the run; footage with too little tonal range is
+                      refused: pass a,b then.
   --dpc_dead K        another threshold for the dead side; 0 switches that side off.
                       Prints, per video, `dpc: <hot> hot, <dead> dead samples corrected in <frames> frames`.  Without --dpc the
                       output files keep their bytes.
@@ -103,13 +109,19 @@ def deal_slots(lengths: Sequence[int], slots: int, tail: int = 0) -> List[List[T
         steps.append(step)
 
 
-def dpc_arguments(dpc, dpc_dead, dpc_iso, dpc_noise, bit_depth):
+def dpc_arguments(dpc, dpc_dead, dpc_iso, dpc_noise, bit_depth, dpc_noise_frames=None):
     """--dpc / --dpc_dead / --dpc_iso / --dpc_noise -> None (no --dpc) or (k_hot, k_dead, noise_a, noise_b, var_floor) as Python
-    doubles (`runtime.dpc_cfg` rounds each to f32 once); SystemExit where the flags do not fit together."""
+    doubles (`runtime.dpc_cfg` rounds each to f32 once); SystemExit where the flags do not fit together.  --dpc_noise auto[,floor]:
+    noise_a and noise_b are None, for `main` to estimate from the footage."""
     if dpc is None:
-        if dpc_dead is not None or dpc_iso is not None or dpc_noise is not None:
+        if dpc_dead is not None or dpc_iso is not None or dpc_noise is not None or dpc_noise_frames is not None:
             raise SystemExit("--dpc_dead, --dpc_iso and --dpc_noise belong to --dpc K")
         return None
+    auto = dpc_noise is not None and dpc_noise.split(',')[0] == 'auto'
+    if dpc_noise_frames is not None and not auto:
+        raise SystemExit("--dpc_noise_frames belongs to --dpc_noise auto")
+    if dpc_noise_frames is not None and dpc_noise_frames < 1:
+        raise SystemExit("--dpc_noise_frames must be >= 1, got %d" % dpc_noise_frames)
     if (dpc_iso is None) == (dpc_noise is None):
         raise SystemExit("--dpc needs exactly one of --dpc_iso {%s} and --dpc_noise a,b[,floor]" % ','.join(str(k) for k in DPC_ISO_CURVES))
     k_dead = dpc if dpc_dead is None else dpc_dead
@@ -122,16 +134,32 @@ def dpc_arguments(dpc, dpc_dead, dpc_iso, dpc_noise, bit_depth):
         a, b = dpc_iso_curve(dpc_iso, bit_depth)
     else:
         f = dpc_noise.split(',')
+        if auto:
+            f = [None] + f                         # auto[,floor]: a and b come from the footage
         if len(f) not in (2, 3):
-            raise SystemExit("--dpc_noise takes a,b or a,b,floor")
+            raise SystemExit("--dpc_noise takes a,b, a,b,floor or auto[,floor]")
         try:
-            a, b = float(f[0]), float(f[1])
+            a, b = (None, None) if auto else (float(f[0]), float(f[1]))
             floor = float(f[2]) if len(f) == 3 else 1.0
         except ValueError:
-            raise SystemExit("--dpc_noise takes numbers a,b[,floor], got %r" % dpc_noise)
+            raise SystemExit("--dpc_noise takes numbers a,b[,floor] or auto[,floor], got %r" % dpc_noise)
         if not floor > 0:
             raise SystemExit("--dpc_noise: the floor must be > 0, got %r" % floor)
     return (float(dpc), float(k_dead), a, b, floor)
+
+
+def estimate_noise(dataset, dev, bit_depth, frames):
+    """--dpc_noise auto: (a, b) of `noise.estimate` on the run's videos, the line `python -m rvdd_release_amd.noise` prints sent to
+    the log; SystemExit with the fit's message where it refuses."""
+    from . import noise
+    from .util._ops import ops_runtime
+    acc, read = noise.estimate(ops_runtime(dev.index or 0), dataset, bit_depth, frames)
+    try:
+        r = noise.report(acc, bit_depth, read)
+    except RuntimeError as err:
+        raise SystemExit("--dpc_noise auto: %s -- pass the curve as --dpc_noise a,b" % err)
+    print('noise: ' + noise.format_line(r))
+    return (r["a"], r["b"])
 
 
 def _parse(argv):
@@ -145,7 +173,9 @@ def _parse(argv):
     p.add_argument('--dpc', type=float, default=None, help='defective-pixel correction: threshold K in standard deviations (both sides)')
     p.add_argument('--dpc_dead', type=float, default=None, help='threshold of the dead side (default: --dpc; 0 = off)')
     p.add_argument('--dpc_iso', type=int, default=None, help='the noise curve of ISO 3200 / 12800, rescaled to --bit_depth')
-    p.add_argument('--dpc_noise', type=str, default=None, help='a,b[,floor]: var = a * m - b in DN of the frames, the least variance')
+    p.add_argument('--dpc_noise', type=str, default=None, help='a,b[,floor]: var = a * m - b in DN of the frames, the least variance; '
+                   'auto[,floor]: estimated from the footage (assumes one camera setting for the whole run)')
+    p.add_argument('--dpc_noise_frames', type=int, default=None, help='with --dpc_noise auto: frames read per video (default 4)')
     own, rest = p.parse_known_args(argv)
     if own.out_format not in OUT_FORMATS:
         raise SystemExit("--out_format %r is not one of %s" % (own.out_format, ', '.join(OUT_FORMATS)))
@@ -156,7 +186,8 @@ def _parse(argv):
         raise SystemExit("--out_bit_depth must be 1..16, got %d" % opt.out_bit_depth)
     if OUT_FORMATS[opt.out_format][0] == "bits" and opt.out_bit_depth not in BITS_DEPTHS:
         raise SystemExit("--out_format %s needs --out_bit_depth (default: --bit_depth) 10, 12 or 14, got %d" % (opt.out_format, opt.out_bit_depth))
-    opt.dpc = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth))
+    opt.dpc = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth), own.dpc_noise_frames)
+    opt.dpc_noise_frames = 4 if own.dpc_noise_frames is None else own.dpc_noise_frames
     if opt.raw_container is not None:
         if opt.raw_container != 'mipi':
             raise SystemExit("--raw_container %r: headerless frames are 'mipi' (packed TIFFs are recognised by themselves)" % opt.raw_container)
@@ -191,6 +222,8 @@ def main(argv=None) -> dict:
     model.setup(opt)
     net, dev = model._netDenoise, model.device
     fut = int(opt.future_patch_depth)
+    if opt.dpc is not None and opt.dpc[2] is None:      # --dpc_noise auto: the curve of the run's own footage, before any push
+        opt.dpc = opt.dpc[:2] + estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames) + opt.dpc[4:]
 
     groups = {}                                   # frame size -> its videos, in dataset order
     for key, frames in dataset.videos:

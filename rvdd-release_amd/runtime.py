@@ -58,6 +58,59 @@ def dpc_cfg(k_hot: float, k_dead: float, noise_a: float, noise_b: float, var_flo
     return _lib.RvddDpcCfg(float(k_hot), float(k_dead), float(noise_a), float(noise_b), float(var_floor))
 
 
+NOISE_ACC_BYTES = C.sizeof(_lib.RvddNoiseAcc)      # struct rvdd_noise_acc: u32 hist[64][512], u64 msum[64], u64 counters[4]
+
+
+def noise_acc_arrays(acc):
+    """struct rvdd_noise_acc as numpy arrays (copies on the host): {"hist": int64 [64,512], "msum": int64 [64], "counters": int64 [4]}
+    of an accumulator `RvddRuntime.noise_hist` returned (any tensor or array of its 131616 bytes)."""
+    import numpy as np
+    raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy() if torch.is_tensor(acc) else np.frombuffer(bytes(acc), np.uint8)
+    if raw.size != NOISE_ACC_BYTES:
+        raise RuntimeError(f"a noise accumulator is {NOISE_ACC_BYTES} bytes (struct rvdd_noise_acc), got {raw.size}")
+    raw = raw.tobytes()
+    return {"hist": np.frombuffer(raw, np.uint32, 64 * 512).reshape(64, 512).astype(np.int64),
+            "msum": np.frombuffer(raw, np.uint64, 64, 64 * 512 * 4).astype(np.int64),
+            "counters": np.frombuffer(raw, np.uint64, 4, 64 * 512 * 4 + 64 * 8).astype(np.int64)}
+
+
+def noise_fit(acc, bit_depth: int) -> Dict[str, float]:
+    """The noise curve var(m) = a * m - b, in DN of `bit_depth`, from an accumulator of `RvddRuntime.noise_hist` (rvdd_noise_fit: on
+    the host, no GPU needed; a device tensor is copied, which synchronises).  acc: the tensor, or any array / bytes of struct
+    rvdd_noise_acc.  -> {"a", "b", "bins", "blocks", "m_min", "m_max", "rms"}; RuntimeError with the library's message where the
+    fit refuses (fewer than 4 usable mean bins, or too little tonal range)."""
+    lib = _lib.load()
+    if isinstance(acc, _lib.RvddNoiseAcc):
+        host = acc
+    else:
+        raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes() if torch.is_tensor(acc) else bytes(acc)
+        if len(raw) != NOISE_ACC_BYTES:
+            raise RuntimeError(f"noise_fit: an accumulator is {NOISE_ACC_BYTES} bytes (struct rvdd_noise_acc), got {len(raw)}")
+        host = _lib.RvddNoiseAcc.from_buffer_copy(raw)
+    out = _lib.RvddNoiseCurve()
+    rc = lib.rvdd_noise_fit(C.byref(host), int(bit_depth), C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"rvdd_noise_fit failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    return {"a": out.a, "b": out.b, "bins": int(out.bins), "blocks": int(out.blocks), "m_min": out.m_min, "m_max": out.m_max,
+            "rms": out.rms}
+
+
+def nearest_iso(a: float, b: float, bit_depth: int = 12, levels=(0.20, 0.45, 0.80)):
+    """Which of DPC_ISO_CURVES lies closest to the curve (a, b) in DN of `bit_depth`: -> (iso, ratios), the ISO whose predicted
+    standard deviation at 20 %, 45 % and 80 % of 2^bit_depth - 1 is nearest in the log (the largest |log ratio| over the levels is
+    the distance), and the ratios sigma(a, b) / sigma(iso) at those levels."""
+    import math
+    top = 2 ** int(bit_depth) - 1
+    best = None
+    for iso in DPC_ISO_CURVES:
+        ia, ib = dpc_iso_curve(iso, bit_depth)
+        ratios = [math.sqrt(max(a * l * top - b, 0.0) / (ia * l * top - ib)) for l in levels]
+        dist = max(abs(math.log(max(r, 1e-300))) for r in ratios)
+        if best is None or dist < best[0]:
+            best = (dist, iso, ratios)
+    return best[1], best[2]
+
+
 def raw_frames_to_device(frames, device) -> torch.Tensor:
     """Host sensor frames (a numpy array or CPU tensor of uint16 / int16 / float32) -> a tensor on `device` that
     `ingest_raw` / `video_push` accept.  uint16 arrays travel as their int16 view: the bytes are what crosses the ABI."""
@@ -430,6 +483,24 @@ class RvddRuntime:
         self._check(self.lib.rvdd_dpc(self.h, _ptr(packed), _ptr(out), _ptr(gray), n, hh, ww, int(bit_depth), C.byref(cfg), _ptr(counts),
                                       self._stream()), "rvdd_dpc")
         return out
+
+    # -- the noise curve from the footage ---------------------------------------------
+    def noise_hist(self, packed: torch.Tensor, bit_depth: int = 12, acc: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The 8 x 8 block statistics of packed frames [n,4,hh,ww] (as `ingest_raw` / `ingest_bits` / `dpc` write them) added to `acc`
+        (rvdd_noise_hist): a device tensor holding struct rvdd_noise_acc -- int32 [32904]; None = a new zeroed one -- which is
+        returned.  Accumulate any number of calls of one bit depth, then `noise_fit(acc, bit_depth)`; `noise_acc_arrays(acc)` gives
+        the histogram, the sums of means and the counters.  Nothing is synchronised."""
+        if not torch.is_tensor(packed) or packed.dim() != 4 or packed.shape[1] != 4:
+            raise RuntimeError(f"noise_hist: packed is [n,4,hh,ww], got {tuple(getattr(packed, 'shape', ()))}")
+        n, _, hh, ww = packed.shape
+        packed = _chk_dev(packed, packed.shape, "packed", self.device)
+        if acc is None:
+            acc = torch.zeros(NOISE_ACC_BYTES // 4, dtype=torch.int32, device=self._tdev)
+        elif not torch.is_tensor(acc) or not acc.is_cuda or acc.device.index != self.device or not acc.is_contiguous() \
+                or acc.numel() * acc.element_size() != NOISE_ACC_BYTES:
+            raise RuntimeError(f"noise_hist: acc is a contiguous tensor of {NOISE_ACC_BYTES} bytes on cuda:{self.device} (what noise_hist returned)")
+        self._check(self.lib.rvdd_noise_hist(self.h, _ptr(packed), n, hh, ww, int(bit_depth), _ptr(acc), self._stream()), "rvdd_noise_hist")
+        return acc
 
     def set_dpc(self, cfg=None):
         """The correction as a stage of `video_push`, between the ingest and the kept frames (rvdd_set_dpc): cfg = `dpc_cfg(...)`,
