@@ -164,7 +164,7 @@ __device__ unsigned long long g_stamps[8 * 8];      // [wave][phase 0..6, tiles]
 
 // UPS (UpConv, networks/unet.py:88-147): `a.in` is the half-resolution map [B][H/2][W/2][48] and the conv input is its
 // bilinear x2 upsample (align_corners=False), interpolated in the halo fetch (2x2 blocks of halo pixels from four source
-// pixels each) with the expressions of upsample2x_kernel (prestage.hip) in the same order: the same bits as "upsample,
+// pixels each) with the expressions of upsample2x_kernel (maps.hip) in the same order: the same bits as "upsample,
 // then conv", the upsampled map is never written.
 template <int CIN, int EPI, bool ACC_IN, bool UPS = false, int NGRP = 2, int KS = 3, int MT = 3>
 __global__ __launch_bounds__(NTHREADS) void conv3x3h_kernel(ConvArgs a) {

@@ -2,7 +2,7 @@
 #include "runtime_internal.h"
 
 // encoder_convs[0].blocks[0] projects cat[y, warped features] 96 -> 48 (new_unet.py:381-382): the features' half in the feature
-// warp (prestage.hip warp48_proj_kernel: `featw` then holds W_f warp(f) + bias), y's half in the epilogue of the block that forms y
+// warp (warp.hip warp48_proj_kernel: `featw` then holds W_f warp(f) + bias), y's half in the epilogue of the block that forms y
 bool next_pf_pre(const rvdd_t* h) {
     return h->is_next() && h->has_feat() && !h->opt.no_warp && h->opt.next_projfuse && h->opt.next_split && h->opt.next_pipe &&
            h->nx[NX_PRE].w.fc1_h && h->nx[NX_ENC0_0].half[0].frag && h->nx[NX_ENC0_0].half[1].frag;

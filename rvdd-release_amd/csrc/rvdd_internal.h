@@ -37,6 +37,7 @@ inline int current_device_cus() {
     cache[dev & 63].store(cus, std::memory_order_relaxed);
     return cus;
 }
+inline unsigned nblocks(size_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }      // blocks of bs threads for n of them
 
 // ---------------------------------------------------------------- conv3x3 --
 // EPI_RELU_OUT3 (Winograd kernel only): ReLU, store the 48-channel map AND apply the final 1x1 conv 48->3
@@ -173,15 +174,15 @@ __device__ __forceinline__ void amax_commit_block(unsigned* words, int b, unsign
         if (t) atomicMax(words + (size_t)b * kAmaxSeqWords + (spread % kAmaxLines) * kAmaxLineWords, t);
     }
 }
+__device__ __forceinline__ float absmax4(float m, f32x4 v) {      // max(m, |v[0]| .. |v[3]|): a lane's running maximum over 16-B loads
+    return fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+}
 // Does sequence b start a video on this step?  `mask`: ~0 = every sequence (a first step, any B); otherwise bit b (B <= 64:
 // rvdd_reset_slots) of the launch's own sequences.
 __device__ __forceinline__ bool seq_latched(unsigned long long mask, int b) {
     return mask == ~0ull || (b < 64 && ((mask >> b) & 1ull));
 }
 #endif
-// amax words of a dense NHWC map [B][HW][C] (the maps no split kernel's producer wrote: caller-supplied inputs and states)
-hipError_t launch_amax_reduce(const float* map, int B, int64_t hw_c, unsigned* words, hipStream_t s, int up = 0);
-
 
 // cin = 16 or 48.  Returns hipGetLastError().  variant 1, 2: A/B forms of the plain 48 -> 48 ReLU layer (rvdd_debug_conv_bench only)
 hipError_t launch_conv3x3(const ConvArgs& a, int cin, int epi, hipStream_t s, int variant = 0);
@@ -196,50 +197,64 @@ size_t wino3x3_weight_floats();
 hipError_t launch_conv3x3h(const ConvArgs& a, int cin, int epi, hipStream_t s, bool cout_split = true);
 size_t conv3x3h_weight_bytes(int cin);
 // preprocessing_layer composed with the first source of EncoderConvs[0][0]: one 5x5 conv of the 16-channel network input
-// (conv3x3h.hip HGeo KS = 5; net_convunet.hip compose_pre_enc0), and the fix of its border ring: part -= sum over the 3x3 taps d
-// whose pixel q = p + d - 1 lies OUTSIDE the image of W2[d] (b1 + sum over taps e inside the image of W1[e] x(q + e - 1))
+// (conv3x3h.hip HGeo KS = 5; net_convunet.hip compose_pre_enc0); the fix of its border ring is launch_pre_border_fix
 hipError_t launch_conv5x5h_c16(const ConvArgs& a, hipStream_t s);
 // ... over the first 8 channels only (at most 8 real channels, i.e. no future frame): 25 groups in 7 chunks instead of 50 in 13
 hipError_t launch_conv5x5h_c8(const ConvArgs& a, hipStream_t s);
 size_t conv5x5h_weight_bytes(int cin);      // cin = 8 or 16: the channels multiplied
+void conv3x3h_set_groups(int g);   // stand-alone harness (-DRVDD_CONV_GROUPS2): 2 = two groups of four waves with an 8x16 tile each
+
+// ---- prologue.hip -- the composed first layer's border fix and zero-source pass, amax words of maps handed in
+// the border ring of launch_conv5x5h_*'s output: part -= sum over the 3x3 taps d whose pixel q = p + d - 1 lies OUTSIDE the
+// image of W2[d] (b1 + sum over taps e inside the image of W1[e] x(q + e - 1))
 hipError_t launch_pre_border_fix(const float* netin, const float* w1, const float* b1, const float* w2, float* part, int B, int H, int W,
                                  hipStream_t s);
 // What the second pass of a two-source conv (ACC_IN, EPI_RELU) leaves when its source map is all +0: out = relu(part + 0), and
 // the amax words of `out` (nullable) per sequence; n = floats per sequence (a multiple of 4), part / out 16-B aligned
 hipError_t launch_relu_part(const float* part, float* out, int B, int64_t n, unsigned* words, hipStream_t s);
-void conv3x3h_set_groups(int g);   // stand-alone harness (-DRVDD_CONV_GROUPS2): 2 = two groups of four waves with an 8x16 tile each
+// amax words of a dense NHWC map [B][HW][C] (the maps no split kernel's producer wrote: caller-supplied inputs and states)
+hipError_t launch_amax_reduce(const float* map, int B, int64_t hw_c, unsigned* words, hipStream_t s, int up = 0);
 
-// -------------------------------------------------------------- pre-stages --
-// Hamilton-Adams: raw [n][4][h][w] -> green plane scratch [n][2h][2w] -> RGB
-// written at out[b*bstride + (y*W+x)*pstride + c*cstride].  raw_bstride: floats between the raw frames of consecutive
-// sequences (0 = dense, 4hw): the caller's raw frames may be channel slices of a wider [B][4k][h][w] tensor.
-// `bayer` (every launcher that demosaics or re-mosaics): enum rvdd_bayer of the packed raw frames (channel k = CFA position
-// (k >> 1, k & 1) of each 2x2 cell, whatever the pattern); hipErrorInvalidValue for any other value.
+// ---- demosaic.hip -- Hamilton-Adams demosaic of packed raw frames and its inverse, the re-mosaic
+// raw [n][4][h][w] -> green plane scratch [n][2h][2w] -> RGB written at out[b*bstride + (y*W+x)*pstride + c*cstride].  raw_bstride: floats
+// between the raw frames of consecutive sequences (0 = dense, 4hw): the caller's raw frames may be channel slices of a wider
+// [B][4k][h][w] tensor.  `bayer` (every launcher that demosaics or re-mosaics): enum rvdd_bayer of the packed raw frames (channel k =
+// CFA position (k >> 1, k & 1) of each 2x2 cell, whatever the pattern); hipErrorInvalidValue for any other value.
 hipError_t launch_demosaic(const float* raw, float* green_scratch, float* out, int n, int h, int w,
                            int64_t bstride, int pstride, int cstride, hipStream_t s, int64_t raw_bstride, int bayer);
+// its first half alone, for launch_netin: the green plane [n][2h][2w] (n, h, w >= 1; rbs = the raw frames' stride, never 0)
+hipError_t launch_ha_green(const float* raw, float* green, int n, int h, int w, int64_t rbs, hipStream_t s, int bayer);
+// HamiltonAdam(pattern).remosaick of an NHWC4 frame: the packed planes of the pattern (the inverse of its packing)
+hipError_t launch_remosaick4(const float* rgb4, float* raw, int B, int H, int W, hipStream_t s, int bayer);
 
-// bicubic backward warp with the raw-resolution flow (x2 bilinear upsample,
-// align_corners=True, times 2, fused).  src NHWC4 -> dst[(b*H*W + p)*dpstride + c], c<3.
-hipError_t launch_warp3(const float* src4, const float* flow_raw, float* dst, int dpstride, int B,
-                        int H, int W, hipStream_t s);
-// The NHWC16 network input of a step in one pass: warp3 of prev4 | demosaic of raw_cur | warp3 of next4 (or zeros when
-// next4 == nullptr); flows nullptr = --no_warp.  [B][4][h][w] raw, [B][2][h][w] flows, dense inside a sequence, with
-// raw_bstride / flow_bstride floats from one sequence to the next (0 = dense); green_scratch [B][2h][2w].
-// proj_w16 set (ConvNeXtUnet): the 16-channel map is not written; `proj_out` NHWC48 receives its 1x1 projection
-// proj_w16 / proj_b (launch_proj1x1's (16, 0) arrangement) instead (prestage.hip netin_proj_kernel)
-hipError_t launch_netin(const float* raw_cur, float* green_scratch, const float* prev4, const float* flow_prev,
-                        const float* next4, const float* flow_next, float* netin, int B, int h, int w, hipStream_t s,
-                        int64_t raw_bstride, int64_t flow_bstride, const float* proj_w16, const float* proj_b, float* proj_out,
-                        int bayer);
+// ---- warp.hip -- bicubic backward warps with the raw-resolution flow (x2 bilinear upsample, align_corners=True, times 2, fused)
+// src NHWC4 -> dst[(b*H*W + p)*dpstride + c], c<3.
+hipError_t launch_warp3(const float* src4, const float* flow_raw, float* dst, int dpstride, int B, int H, int W, hipStream_t s);
+// src NHWC48 -> dst NHWC48.
+hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W, hipStream_t s, int64_t flow_bstride = 0);
+// the same, and a 48 -> 48 projection of every warped pixel: dst = W warp(src) + bias; frag / inv_e = the projection as a
+// NextProj's split-f16 fragments and scale (net_convnext.hip), applied per pixel in block floating point (warp48_proj_kernel)
+hipError_t launch_warp48_proj(const float* src, const float* flow_raw, float* dst, int B, int H, int W, const float* frag,
+                              int inv_e, const float* bias, hipStream_t s, int64_t flow_bstride = 0);
+// generic NCHW warp with a full-resolution flow (util.flow_utils.warp), and that flow from the raw-resolution one (times mul)
+hipError_t launch_warp_nchw(const float* x, const float* flow, float* y, int n, int c, int H, int W, hipStream_t s);
+hipError_t launch_upsample_flow(const float* t, float* out, int nc, int h, int w, float mul, hipStream_t s);
+
+// ---- netin.hip -- the network input of a frame-step and the bound of its maximum
+// The NHWC16 network input of a step in one pass: warp3 of prev4 | demosaic of raw_cur | warp3 of next4 (or zeros when next4 == nullptr);
+// flows nullptr = --no_warp.  [B][4][h][w] raw, [B][2][h][w] flows, dense inside a sequence, with raw_bstride / flow_bstride floats
+// from one sequence to the next (0 = dense); green_scratch [B][2h][2w].  proj_w16 set (ConvNeXtUnet): the 16-channel map is not
+// written; `proj_out` NHWC48 receives its 1x1 projection proj_w16 / proj_b (launch_proj1x1's (16, 0) arrangement) instead (netin_proj_kernel)
+hipError_t launch_netin(const float* raw_cur, float* green_scratch, const float* prev4, const float* flow_prev, const float* next4,
+                        const float* flow_next, float* netin, int B, int h, int w, hipStream_t s, int64_t raw_bstride,
+                        int64_t flow_bstride, const float* proj_w16, const float* proj_b, float* proj_out, int bayer);
 // amax words of that network input (block floating point of the split-f16 convs, below): an upper bound from the packed raw
 // frames it is made of (up to three, each nullable) and from `prev_words`, words that bound the previous output (nullable)
 // (zero_a / zero_b, nullable: word ranges the kernel also clears -- the next step's amax words, step.hip)
 hipError_t launch_netin_bound(const float* raw_a, const float* raw_b, const float* raw_c, int B, int h, int w, int64_t raw_bstride,
                               const unsigned* prev_words, unsigned* words, hipStream_t s, unsigned* zero_a = nullptr, size_t zero_na = 0,
                               unsigned* zero_b = nullptr, size_t zero_nb = 0, unsigned long long latch = ~0ull);
-// src NHWC48 -> dst NHWC48.
-// the three pre-stage kernels of a small frame-step without a future frame in one launch (prestage.hip netin_small_kernel); same bits
-// (enabled = false: never -- option "small_prestage" 0)
+// the three pre-stage kernels of a small frame-step without a future frame in one launch, same bits (enabled: option "small_prestage")
 bool netin_small_applies(int B, int h, int w, bool future, bool enabled = true);
 // ... at most 1024 tiles of 16x16.  Above that the same kernel forms the network input alone (words, zero_a, zero_b null: the
 // bound and the clearing stay with launch_netin_bound) -- no green plane in memory; any size without a future frame
@@ -249,31 +264,14 @@ hipError_t launch_netin_small(const float* raw_cur, const float* raw_prev, const
                               int h, int w, int64_t raw_bstride, int64_t flow_bstride, const unsigned* prev_words, unsigned* words,
                               hipStream_t s, unsigned* zero_a, size_t zero_na, unsigned* zero_b, size_t zero_nb,
                               unsigned long long latch, int bayer);
-hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W,
-                         hipStream_t s, int64_t flow_bstride = 0);
-// the same, and a 48 -> 48 projection of every warped pixel: dst = W warp(src) + bias; frag / inv_e = the projection as a
-// NextProj's split-f16 fragments and scale (net_convnext.hip), applied per pixel in block floating point (prestage.hip)
-hipError_t launch_warp48_proj(const float* src, const float* flow_raw, float* dst, int B, int H, int W, const float* frag,
-                              int inv_e, const float* bias, hipStream_t s, int64_t flow_bstride = 0);
-// generic NCHW warp with a full-resolution flow (util.flow_utils.warp).
-// HamiltonAdam(pattern).remosaick of an NHWC4 frame: the packed planes of the pattern (the inverse of its packing)
-hipError_t launch_remosaick4(const float* rgb4, float* raw, int B, int H, int W, hipStream_t s, int bayer);
-hipError_t launch_warp_nchw(const float* x, const float* flow, float* y, int n, int c, int H, int W,
-                            hipStream_t s);
-hipError_t launch_upsample_flow(const float* t, float* out, int nc, int h, int w, float mul,
-                                hipStream_t s);
 
-// ---------------------------------------------------------- map reshaping --
-// bilinear x2 of a NHWC48 map [B][h][w] into [B][Hout][Wout] at offset (oy,ox);
-// pixels outside the 2h x 2w window are zero.  align_corners selects
-// nn.Upsample(align_corners=...) semantics.
-hipError_t launch_upsample2x(const float* in, float* out, int B, int h, int w, int Hout, int Wout,
-                             int oy, int ox, bool align_corners, hipStream_t s);
+// ---- maps.hip -- the map primitives of the nets and the loss reduction
+// bilinear x2 of a NHWC48 map [B][h][w] into [B][Hout][Wout] at offset (oy,ox); pixels outside the 2h x 2w window are zero.
+// align_corners selects nn.Upsample(align_corners=...) semantics.
+hipError_t launch_upsample2x(const float* in, float* out, int B, int h, int w, int Hout, int Wout, int oy, int ox, bool align_corners, hipStream_t s);
 hipError_t launch_maxpool2(const float* in, float* out, int B, int H, int W, hipStream_t s);
-hipError_t launch_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, int Cpad,
-                               hipStream_t s);
-hipError_t launch_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, int Cpad,
-                               hipStream_t s);
+hipError_t launch_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, int Cpad, hipStream_t s);
+hipError_t launch_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, int Cpad, hipStream_t s);
 // final 1x1 conv 48->3: feat NHWC48 -> out NCHW [B][3][H][W] (+ NHWC4 copy for the next warp)
 hipError_t launch_conv1x1_out(const float* feat, const float* w3x48, const float* b3, float* out_nchw,
                               float* out_nhwc4, int B, int H, int W, hipStream_t s);
@@ -281,6 +279,8 @@ hipError_t launch_conv1x1_out(const float* feat, const float* w3x48, const float
 // result2[nslices][2]; each slice's two sums are bit for bit what a launch of that slice alone gives
 hipError_t launch_loss_reduce_batch(const float* a, const float* b, int nslices, int64_t n, double* partial, int nblk,
                                     double* result2, hipStream_t s);
+
+// ---- state.hip -- the recurrent state of single sequences of a batch: reset and moved
 // rvdd_reset_slots' latch: zero the features (feat_per_seq floats per sequence) and the amax words of every set (nsets, layout
 // [nsets][B][kAmaxSeqWords]) of the sequences in `mask` (B <= 64); either pointer nullable
 hipError_t launch_latch_zero(unsigned long long mask, float* feat, int64_t feat_per_seq, unsigned* words, int nsets, int B, hipStream_t s);
@@ -358,7 +358,7 @@ hipError_t launch_ingest_raw(const void* frames, int dtype, int layout, int n, i
 hipError_t launch_gray_of_rgb(const float* rgb, int n, int hh, int ww, int bayer, int bit_depth, float* gray, hipStream_t s);
 // The re-mosaic's colour table, the one copy of it: the RGB plane of each GBRG site -- G(e,e), B(e,o), R(o,e), G(o,o) -- and the
 // phase (py << 1) | px of the pattern; CFA position k of pattern `bayer` (enum rvdd_bayer, 0..3) is the GBRG site k ^ phase
-// (prestage.hip's bayer_phase).  -> the four plane indices, two bits each: col(k) = (cols >> 2k) & 3.
+// (demosaic.h's bayer_phase).  -> the four plane indices, two bits each: col(k) = (cols >> 2k) & 3.
 inline int bayer_cols(int bayer) {
     constexpr int gbrg[4] = {1, 2, 0, 1}, phase[4] = {0, 3, 2, 1};
     int cols = 0;

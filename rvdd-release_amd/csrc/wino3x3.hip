@@ -55,7 +55,7 @@ __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
 }
 
 // a * s + c with ONE rounding (the interpolation of the fused upsample: the same expression, written the same way, in
-// upsample2x_kernel of prestage.hip, so that both produce the same bits)
+// upsample2x_kernel of maps.hip, so that both produce the same bits)
 __device__ __forceinline__ f32x4 fma4(f32x4 a, float s, f32x4 c) {
     return __builtin_elementwise_fma(a, f32x4{s, s, s, s}, c);
 }
@@ -190,7 +190,7 @@ __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     //   pr 1: 0.25 d[i-1] + 0.75 d[i]   (d[i] alone when ty = 0: the source index is clamped at 0 with weight 1)
     //   pr 2: 0.75 d[i]   + 0.25 d[i+1]
     //   pr 3: 0.25 d[i]   + 0.75 d[i+1] (zero padding when ty is the last row)
-    // the same along x; vertical pass first, then horizontal, as upsample2x_kernel (prestage.hip) evaluates it, so
+    // the same along x; vertical pass first, then horizontal, as upsample2x_kernel (maps.hip) evaluates it, so
     // the fused conv and "upsample, then conv" see the same bits.
     auto interp = [&](f32x4 (&p)[16], const UnitPos& u) {
         const int hl = a.H >> 1, wl = a.W >> 1;

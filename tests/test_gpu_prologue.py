@@ -1,5 +1,5 @@
 """The stages of a frame-step in front of the 3x3 convs, after their rewrite for speed: the border ring of the composed first
-layer by runs of 16 pixels (prestage.hip pre_border_fix_kernel), the tiled network input above 1024 tiles (netin_small_kernel
+layer by runs of 16 pixels (prologue.hip pre_border_fix_kernel), the tiled network input above 1024 tiles (netin_small_kernel
 without its bound) and the first step of a video without work on zero features (step.hip enqueue_step zero_feat).  All three
 promise the bits of what they replace.  Needs a real MI355X: -m gpu.
 

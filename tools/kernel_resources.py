@@ -29,23 +29,28 @@ def _demangle(names):
     return [re.sub(r"\(.*$", "", n.replace("void ", "", 1).replace("(anonymous namespace)::", "")) for n in out.splitlines()]
 
 
+def code_objects(lib, tmp):
+    """The gfx950 code objects of the library, one per translation unit with kernels, as ELF files under `tmp`."""
+    fat = os.path.join(tmp, "fat.bin")
+    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
+    blob = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
+    for i, st in enumerate(starts):
+        piece = os.path.join(tmp, f"bundle{i}.bin")
+        open(piece, "wb").write(blob[st:starts[i + 1] if i + 1 < len(starts) else len(blob)])
+        co = os.path.join(tmp, f"co{i}.o")
+        r = subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={piece}",
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], capture_output=True, text=True)
+        if r.returncode == 0 and os.path.exists(co) and os.path.getsize(co) > 0:
+            yield co
+
+
 def kernel_table(lib=LIB):
     """-> list of dicts {name, vgpr_count, agpr_count, sgpr_count, vgpr_spill_count, sgpr_spill_count,
     private_segment_fixed_size, group_segment_fixed_size, max_flat_workgroup_size}, one per kernel of the library."""
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        fat = os.path.join(tmp, "fat.bin")
-        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-        for i, st in enumerate(starts):
-            piece = os.path.join(tmp, f"bundle{i}.bin")
-            open(piece, "wb").write(blob[st:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-            co = os.path.join(tmp, f"co{i}.o")
-            r = subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={piece}",
-                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], capture_output=True, text=True)
-            if r.returncode != 0 or not os.path.exists(co) or os.path.getsize(co) == 0:
-                continue
+        for co in code_objects(lib, tmp):
             notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True).stdout
             cur = None
             for ln in notes.splitlines():
