@@ -19,6 +19,10 @@ against the REFERENCE's stored frames and per-frame PSNR.  Schemes:
                patches and filters are what is split)
 
 Also prints the largest |operand| any dense conv saw (f16 overflows at 65504).
+
+The device itself under dense random weights, against the oracle in f64: tests/test_gpu_random_weights.py (its docstring has what
+that found: with both operands' hi halves toward zero, as f16x2p3 here and in the library, the dropped lo.lo terms all have
+their product's sign and add up over the layers of a net).
 """
 import os
 import sys
