@@ -527,6 +527,66 @@ typedef struct rvdd_noise_curve {
 } rvdd_noise_curve;
 int rvdd_noise_fit(const rvdd_noise_acc* acc_host /* HOST copy */, int32_t bit_depth, rvdd_noise_curve* out);
 
+/* ---- footage matched to the checkpoint's noise curve ------------------------- */
+
+/* The checkpoints were trained on two noise curves of one synthetic camera (in 12-bit DN: ISO 3200 var = 8.0034 m - 2043.51144, ISO
+ * 12800 var = 28.3015 m - 6307.62081).  An affine curve maps onto any other affine curve by an affine map of the samples: with
+ * x' = s x + t the variance of x' is s^2 (a x - b) = (s a) x' - (s a t + s^2 b), so s = a_ref / a and t = (b_ref - s^2 b) / a_ref give
+ * exactly the curve (a_ref, b_ref), and the black level comes along, since b is about a * black.  On samples in [-1,1], where
+ * x = ((v + 1) / 2) * 4095 in 12-bit DN whatever the bit depth, that map is
+ *   v' = scale * v + offset,   scale = s,   offset = s - 1 + 2 t / 4095.
+ * Pointwise, no weights; the network sees footage with the statistics it was trained on, its output is mapped back.
+ * Footage NOISIER than the checkpoint's curve (s < 1) is compressed into the trained range: the case the map is for.  Footage CLEANER than
+ * the curve (s > 1) is stretched by s beyond the trained range and can lose quality (DESIGN.md 4.16 has the measured table). */
+typedef struct rvdd_match_cfg {
+    float scale, offset;      /* v' = scale * v + offset on samples in [-1,1]; scale finite and > 0, offset finite */
+} rvdd_match_cfg;
+
+/* The coefficients, in f64 on the host; needs neither a device nor a handle (errors go where rvdd_noise_fit's go:
+ * rvdd_last_error(NULL)).  a, b: the footage's curve in DN of bit_depth, what rvdd_noise_fit returns; a_ref, b_ref: the checkpoint's
+ * curve in 12-bit DN.  Each operation as written, in this order:
+ *   k = 4095 / (2^bit_depth - 1);  a12 = k * a;  b12 = (k * k) * b;  s = a_ref / a12;  t = (b_ref - (s * s) * b12) / a_ref
+ *   out->scale = (float)s;  out->offset = (float)((s - 1) + (2 * t) / 4095)
+ * s_t (nullable): { s, t } with t in 12-bit DN.  A reference curve matched onto itself at 12 bits gives scale = 1, offset = 0 exactly.
+ * RVDD_ERR_ARG and *out untouched: NULL out; a or a_ref not finite or not > 0; b or b_ref not finite; bit_depth outside 1..16;
+ * coefficients that are not finite (or a scale that is not > 0) once rounded to f32. */
+int rvdd_match_coeffs(double a, double b, int32_t bit_depth, double a_ref, double b_ref, rvdd_match_cfg* out,
+                      double* s_t /* HOST [2], nullable */);
+
+/* The map on packed frames [n,4,hh,ww] (as rvdd_ingest_raw / rvdd_ingest_bits / rvdd_dpc write them): out = (scale * v) + offset,
+ * two f32 operations each rounded on its own (no fused multiply-add), reproducible bit for bit in NumPy f32 (tests/match_ref.py).
+ * packed_out == packed_in (in place) is allowed; any other overlap is RVDD_ERR_ARG.  Gray planes are not this call's business: TV-L1
+ * keeps matching the sensor's own planes.
+ * With both pointers 16-byte aligned and the element count a multiple of 4 a thread owns four samples (16-byte loads and stores),
+ * every other case one sample.  Same bits either way.
+ * RVDD_ERR_ARG (the message names the argument) and nothing launched: NULL cfg; scale not finite or not > 0; offset not finite;
+ * n < 0; hh or ww < 1; NULL packed_in / packed_out with n > 0; a launch of more than 2^31 - 1 blocks; a partial overlap.  n = 0 does
+ * nothing.  Asynchronous and stream-ordered; nothing is read back. */
+int rvdd_match_raw(rvdd_t* h, const float* packed_in /* [n,4,hh,ww] */, float* packed_out /* [n,4,hh,ww], may be packed_in */,
+                   int32_t n, int32_t hh, int32_t ww, const rvdd_match_cfg* cfg, void* stream);
+
+/* The way back on network outputs [n,3,H,W]: out = (v - offset) * r with r = (float)(1.0 / (double)scale) formed once on the host;
+ * the difference and the product each rounded to f32 on their own.  In place, forms, errors (H or W < 1) and semantics as
+ * rvdd_match_raw.  A sample of an integer DN of up to 16 bits that goes through rvdd_match_raw and back lands within a small
+ * fraction of a DN of itself, so rvdd_egress's rounding returns the DN (tests/test_match_host.py walks every DN). */
+int rvdd_unmatch_rgb(rvdd_t* h, const float* rgb_in /* [n,3,H,W] */, float* rgb_out /* [n,3,H,W], may be rgb_in */, int32_t n,
+                     int32_t H, int32_t W, const rvdd_match_cfg* cfg, void* stream);
+
+/* The map as a stage of rvdd_video_push: cfg = the coefficients (checked as rvdd_match_raw checks them: RVDD_ERR_ARG, the message
+ * names the field, and nothing changes), NULL = off, the default.  Its own call like rvdd_set_dpc, because its parameters are floats.
+ * Per handle; acts on rvdd_video_push only; synchronises the device.  With the stage on a push
+ *   - maps the ring's packed frames of the slots that got a frame, in place, after the ingest and after rvdd_set_dpc's correction (which
+ *     keeps working in the sensor's domain with the sensor's curve): one launch per run of slots, as the ingest.  The gray planes stay
+ *     the sensor's, so TV-L1 matches what it matches without the stage.  The copies option "stream_all_frames" makes for a head or a
+ *     tail are copies of mapped frames and are not mapped again;
+ *   - maps out_rgb back in place after the step, all cfg.batch slots in one launch, BEFORE option "stream_flow_from_denoised" takes its
+ *     gray plane from it: that plane is in the sensor's domain like the ring's gray planes it is paired with.
+ * The recurrent state stays in the mapped domain: it is the network's own.  out_rgb is in the sensor's domain, so rvdd_egress and
+ * everything behind it need nothing new.  Every output is bit for bit rvdd_ingest_raw -> rvdd_match_raw -> the flows of the un-mapped
+ * gray planes -> rvdd_step -> rvdd_unmatch_rgb on a handle of batch 1.  The stage allocates nothing; with it off a push makes exactly the
+ * launches it made before.  Switch it between videos: frames mapped with other coefficients stay in the ring as they are. */
+int rvdd_set_match(rvdd_t* h, const rvdd_match_cfg* cfg /* NULL = off, the default */);
+
 /* ---- raw datasets from sRGB video ------------------------------------------- */
 
 /* dataset/generate_raw_from_RGB.py (:45-127 single_image_rgb2raw, :168-189 the 12-bit range, the percentile matching to CRVD

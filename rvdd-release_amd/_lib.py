@@ -36,6 +36,11 @@ class RvddDpcCfg(C.Structure):
                 ("var_floor", C.c_float)]
 
 
+class RvddMatchCfg(C.Structure):
+    """struct rvdd_match_cfg (rvdd_match_coeffs, rvdd_match_raw, rvdd_unmatch_rgb, rvdd_set_match)"""
+    _fields_ = [("scale", C.c_float), ("offset", C.c_float)]
+
+
 class RvddNoiseAcc(C.Structure):
     """struct rvdd_noise_acc (rvdd_noise_hist, rvdd_noise_fit): 131616 bytes"""
     _fields_ = [("hist", (C.c_uint32 * 512) * 64), ("msum", C.c_uint64 * 64), ("counters", C.c_uint64 * 4)]
@@ -85,6 +90,11 @@ _PROTOS = {
     "rvdd_dpc_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), _P]),
     "rvdd_noise_hist": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_noise_fit": (C.c_int, [C.POINTER(RvddNoiseAcc), C.c_int32, C.POINTER(RvddNoiseCurve)]),
+    "rvdd_match_coeffs": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(RvddMatchCfg),
+                                    C.POINTER(C.c_double)]),
+    "rvdd_match_raw": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddMatchCfg), _P]),
+    "rvdd_unmatch_rgb": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddMatchCfg), _P]),
+    "rvdd_set_match": (C.c_int, [_P, C.POINTER(RvddMatchCfg)]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                  _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),

@@ -1,4 +1,4 @@
-// rvdd_noise_fit: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
+// rvdd_noise_fit and rvdd_match_coeffs: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
 // Host code only, f64, no device and no handle; compiled -ffp-contract=off so that tests/noise_ref.py, which runs the same sums in
 // the same order in Python doubles, gets the same numbers.
 #include "runtime_internal.h"
@@ -85,5 +85,31 @@ extern "C" int rvdd_noise_fit(const rvdd_noise_acc* acc, int32_t bit_depth, rvdd
         sr += ns[k] * (r * r);
     }
     *out = rvdd_noise_curve{a, b, m_min, m_max, std::sqrt(sr / (double)blocks), blocks, bins, 0};
+    return RVDD_OK;
+}
+
+// The affine map of the samples that takes the footage's curve onto the checkpoint's (the derivation is in include/rvdd.h): f64, each
+// operation as written, so that the same formulas in Python doubles give the same numbers.
+extern "C" int rvdd_match_coeffs(double a, double b, int32_t bit_depth, double a_ref, double b_ref, rvdd_match_cfg* out, double* s_t) {
+    if (!out) return fail(nullptr, RVDD_ERR_ARG, "rvdd_match_coeffs: out is required");
+    if (!(a > 0.0) || !std::isfinite(a)) return fail(nullptr, RVDD_ERR_ARG, "rvdd_match_coeffs: a must be finite and > 0, got %g", a);
+    if (!std::isfinite(b)) return fail(nullptr, RVDD_ERR_ARG, "rvdd_match_coeffs: b must be finite, got %g", b);
+    if (bit_depth < 1 || bit_depth > 16) return fail(nullptr, RVDD_ERR_ARG, "rvdd_match_coeffs: bit_depth must be 1..16, got %d", bit_depth);
+    if (!(a_ref > 0.0) || !std::isfinite(a_ref)) return fail(nullptr, RVDD_ERR_ARG, "rvdd_match_coeffs: a_ref must be finite and > 0, got %g", a_ref);
+    if (!std::isfinite(b_ref)) return fail(nullptr, RVDD_ERR_ARG, "rvdd_match_coeffs: b_ref must be finite, got %g", b_ref);
+    const double k = 4095.0 / (double)((1u << bit_depth) - 1u);
+    const double a12 = k * a, b12 = (k * k) * b;
+    const double s = a_ref / a12;
+    const double t = (b_ref - (s * s) * b12) / a_ref;
+    const rvdd_match_cfg cfg = {(float)s, (float)((s - 1.0) + (2.0 * t) / 4095.0)};
+    // a curve so far from the checkpoint's that the f32 coefficients leave the range rvdd_match_raw accepts
+    if (!(cfg.scale > 0.0f) || !std::isfinite(cfg.scale) || !std::isfinite(cfg.offset))
+        return fail(nullptr, RVDD_ERR_ARG, "rvdd_match_coeffs: a = %g, b = %g against a_ref = %g, b_ref = %g gives scale %g, offset %g, which no f32 "
+                    "map can carry", a, b, a_ref, b_ref, (double)cfg.scale, (double)cfg.offset);
+    *out = cfg;
+    if (s_t) {
+        s_t[0] = s;
+        s_t[1] = t;
+    }
     return RVDD_OK;
 }

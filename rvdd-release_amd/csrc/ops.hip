@@ -62,7 +62,51 @@ int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* ou
     return RVDD_OK;
 }
 
+int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg) {
+    if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
+    if (!(cfg->scale > 0.0f) || !std::isfinite(cfg->scale)) return fail(h, RVDD_ERR_ARG, "%s: scale must be finite and > 0, got %g", fn, cfg->scale);
+    if (!std::isfinite(cfg->offset)) return fail(h, RVDD_ERR_ARG, "%s: offset must be finite, got %g", fn, cfg->offset);
+    return RVDD_OK;
+}
+
+namespace {
+// rvdd_match_raw (c = 4, inverse = false) and rvdd_unmatch_rgb (c = 3, inverse = true) as `fn`: [n][c][d0][d1] floats, `in_name` /
+// `out_name` and `d0_name` / `d1_name` the caller's words for them
+int match_call(rvdd_t* h, const char* fn, const char* in_name, const char* out_name, const char* d0_name, const char* d1_name, const float* in,
+               float* out, int32_t n, int c, int32_t d0, int32_t d1, const rvdd_match_cfg* cfg, bool inverse, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    RC(match_params(h, fn, cfg));
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    if (d0 < 1) return fail(h, RVDD_ERR_ARG, "%s: %s must be >= 1, got %d", fn, d0_name, d0);
+    if (d1 < 1) return fail(h, RVDD_ERR_ARG, "%s: %s must be >= 1, got %d", fn, d1_name, d1);
+    if (n == 0) return RVDD_OK;
+    if (!in) return fail(h, RVDD_ERR_ARG, "%s: %s is required", fn, in_name);
+    if (!out) return fail(h, RVDD_ERR_ARG, "%s: %s is required", fn, out_name);
+    const int64_t count = (int64_t)n * c * d0 * d1;      // below 2^63: three 31-bit factors and c <= 4
+    if (match_blocks(count, match_wide(in, out, count)) < 0)
+        return fail(h, RVDD_ERR_ARG, "%s: n * %s * %s = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, d0_name, d1_name, n, d0, d1);
+    // a thread reads its own samples and then writes them: the same tensor is fine, a shifted one is a race
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t bytes = (uintptr_t)count * sizeof(float);
+    if (a != b && a < b + bytes && b < a + bytes)
+        return fail(h, RVDD_ERR_ARG, "%s: %s must be %s itself (in place) or not overlap it (%d frames of %d x %d x %d floats each)", fn, out_name,
+                    in_name, n, c, d0, d1);
+    ENTER(h);
+    HIPCHK(h, launch_match(in, out, count, cfg->scale, cfg->offset, inverse, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+}  // namespace
+
 extern "C" {
+
+int rvdd_match_raw(rvdd_t* h, const float* packed_in, float* packed_out, int32_t n, int32_t hh, int32_t ww, const rvdd_match_cfg* cfg,
+                   void* stream) {
+    return match_call(h, "rvdd_match_raw", "packed_in", "packed_out", "hh", "ww", packed_in, packed_out, n, 4, hh, ww, cfg, false, stream);
+}
+
+int rvdd_unmatch_rgb(rvdd_t* h, const float* rgb_in, float* rgb_out, int32_t n, int32_t H, int32_t W, const rvdd_match_cfg* cfg, void* stream) {
+    return match_call(h, "rvdd_unmatch_rgb", "rgb_in", "rgb_out", "H", "W", rgb_in, rgb_out, n, 3, H, W, cfg, true, stream);
+}
 
 int rvdd_psnr_l1(rvdd_t* h, const float* den, const float* gt, int64_t count, float* out2, void* stream) {
     return psnr_l1_n(h, "rvdd_psnr_l1", den, gt, 1, count, out2, stream);

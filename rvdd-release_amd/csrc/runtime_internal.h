@@ -241,6 +241,12 @@ struct rvdd_handle {
         std::vector<uint64_t> total;     // [B][2] since the stage was last switched on
     } dpc;
 
+    // rvdd_set_match: the ring's packed frames mapped onto the checkpoint's noise curve, out_rgb mapped back (rvdd_video_push)
+    struct Match {
+        bool on = false;
+        rvdd_match_cfg cfg{};            // the checked coefficients (match_params)
+    } match;
+
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
         const void* p[6];
@@ -430,5 +436,7 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s);
 // ---- ops.hip
 // the checks rvdd_dpc and rvdd_set_dpc share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
 int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* out);
+// the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
+int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg);
 int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
                    void* stream, bool async);

@@ -408,6 +408,14 @@ hipError_t launch_dpc(const float* pin, float* pout, float* gray, int n, int hh,
 bool dpc_wide(const float* pin, const float* pout, const float* gray, int ww);
 int64_t dpc_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame);
 
+// match.hip -- footage matched to the checkpoint's noise curve (rvdd_match_raw, rvdd_unmatch_rgb, the stage behind rvdd_set_match)
+// `count` dense floats in -> out (the same pointer, or no overlap): (scale * v) + offset, or with `inverse` (v - offset) * r with
+// r = (float)(1.0 / (double)scale) formed here; each operation rounded to f32 on its own.  scale finite and > 0, offset finite.
+hipError_t launch_match(const float* in, float* out, int64_t count, float scale, float offset, bool inverse, hipStream_t s);
+// whether that launch takes the wide form (a thread owns four samples), and its grid; -1 = more than 2^31 - 1 blocks
+bool match_wide(const float* in, const float* out, int64_t count);
+int64_t match_blocks(int64_t count, bool wide);
+
 // noise.hip -- block statistics of packed frames for the noise-curve estimate (rvdd_noise_hist)
 struct rvdd_noise_acc;
 typedef rvdd_noise_acc NoiseAcc;      // include/rvdd.h: u32 hist[64][512], u64 msum[64], u64 counters[4]

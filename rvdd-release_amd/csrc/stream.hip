@@ -59,6 +59,8 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         RC(dmalloc(h, reinterpret_cast<void**>(&dpc.counts), (size_t)B * 2 * sizeof(unsigned)));
         RC(dmalloc(h, reinterpret_cast<void**>(&dpc.in), (size_t)B * 4 * hw * sizeof(float)));
     }
+    // rvdd_set_match: the ring's packed frames are mapped in place behind the ingest (and the correction), out_rgb is mapped back
+    const auto match = h->match;
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
         if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
@@ -80,6 +82,8 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
             HIPCHK(h, launch_ingest_raw(static_cast<const char*>(frames) + (size_t)b * 4 * hw * esz, dtype, layout, e - b, hh, ww, bit_depth,
                                         packed, ring_gray, s));
         if (dpc.on) HIPCHK(h, launch_dpc(packed, ring_packed, ring_gray, e - b, hh, ww, bit_depth, dpc.p, dpc.counts + 2 * (size_t)b, s));
+        // the gray planes stay the sensor's: TV-L1 matches what it always matched
+        if (match.on) HIPCHK(h, launch_match(ring_packed, ring_packed, (int64_t)(e - b) * 4 * (int64_t)hw, match.cfg.scale, match.cfg.offset, false, s));
         return RVDD_OK;
     }));
     // Per slot: which frame of its video this push outputs (centre; -1: none).  The plain rule is centre = n - 1 - future >= 1.  Option
@@ -150,6 +154,8 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         RC(rvdd_reset_slots(h, mask.data()));
     }
     RC(rvdd_step_strided(h, packed_at(pp), packed_at(pc), fut ? packed_at(pos) : nullptr, flow_prev, flow_next, 0, 0, out_rgb, stream));
+    // every slot, ready or not: one launch; the recurrent state stays in the network's own domain
+    if (match.on) HIPCHK(h, launch_match(out_rgb, out_rgb, (int64_t)B * 12 * (int64_t)hw, match.cfg.scale, match.cfg.offset, true, s));
     if (from_den) {
         // the plane is taken from the output (with "prev_noisy_frame" lastden holds the noisy demosaic) inside the push that wrote it:
         // the caller may overwrite out_rgb before the next one
@@ -172,6 +178,16 @@ extern "C" int rvdd_set_dpc(rvdd_t* h, const rvdd_dpc_cfg* cfg) {
     }
     dpc.on = cfg != nullptr;
     if (cfg) dpc.p = p;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_set_match(rvdd_t* h, const rvdd_match_cfg* cfg) {
+    if (!h) return RVDD_ERR_ARG;
+    if (cfg) RC(match_params(h, "rvdd_set_match", cfg));
+    ENTER(h);
+    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight keep the coefficients they were enqueued with
+    h->match.on = cfg != nullptr;
+    if (cfg) h->match.cfg = *cfg;
     return RVDD_OK;
 }
 

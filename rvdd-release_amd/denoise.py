@@ -48,6 +48,17 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
   --dpc_dead K        another threshold for the dead side; 0 switches that side off.
                       Prints, per video, `dpc: <hot> hot, <dead> dead samples corrected in <frames> frames`.  Without --dpc the
                       output files keep their bytes.
+  --match_noise a,b   map the footage onto the checkpoint's noise curve (`rvdd_set_match`): a,b is the footage's curve var = a * m - b in
+                      DN of --bit_depth.  The kept frames are mapped by x' = s x + t with s = a_ref / a (in 12-bit DN) behind the ingest
+                      and the correction of --dpc, which keeps the sensor's curve; the outputs are mapped back, so every output format
+                      stays in the sensor's range; flows are matched on the sensor's own planes.  Needs
+  --match_iso ISO     the checkpoint's family, 3200 or 12800: the curve it was trained on.  Either flag without the other is an error.
+  --match_noise auto  the curve estimated from the footage as --dpc_noise auto estimates it (--dpc_noise_frames frames per video,
+                      default 4); with both on auto one estimate and one `noise:` line serve both.
+                      Prints `match: {"scale": ..., "offset": ..., "s": ..., "t_dn12": ..., "iso": ...}` with 17 digits.  Footage
+                      noisier than the curve (s < 1, low light) is what the map is for: +3.5 to +4.6 dB on the synthetic camera.
+                      Footage cleaner than the curve (s > 1) is stretched beyond the trained range and can LOSE quality: a warning
+                      says so (DESIGN.md 4.16 has the table).  Without the flags the output files keep their bytes.
 Videos of different frame sizes are grouped by size and run one group after the other, one runtime per size.
 """
 from __future__ import annotations
@@ -63,7 +74,8 @@ import torch
 
 from . import _lib
 from . import tiffio
-from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, dpc_iso_curve, raw_frames_to_device
+from .runtime import (BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, dpc_iso_curve, match_coeffs,
+                      raw_frames_to_device)
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
 # --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
@@ -148,8 +160,49 @@ def dpc_arguments(dpc, dpc_dead, dpc_iso, dpc_noise, bit_depth, dpc_noise_frames
     return (float(dpc), float(k_dead), a, b, floor)
 
 
-def estimate_noise(dataset, dev, bit_depth, frames):
-    """--dpc_noise auto: (a, b) of `noise.estimate` on the run's videos, the line `python -m rvdd_release_amd.noise` prints sent to
+def match_arguments(match_noise, match_iso):
+    """--match_noise / --match_iso -> None (neither) or (a, b, iso), a and b Python doubles in DN of --bit_depth -- None with
+    --match_noise auto, for `main` to estimate from the footage; SystemExit where the flags do not fit together."""
+    if match_noise is None and match_iso is None:
+        return None
+    isos = ', '.join(str(k) for k in DPC_ISO_CURVES)
+    if match_iso is None:
+        raise SystemExit("--match_noise needs --match_iso {%s}: the checkpoint family whose curve the footage is mapped onto" % isos)
+    if match_noise is None:
+        raise SystemExit("--match_iso belongs to --match_noise a,b or --match_noise auto")
+    if match_iso not in DPC_ISO_CURVES:
+        raise SystemExit("--match_iso must be one of %s, got %r" % (isos, match_iso))
+    if match_noise == 'auto':
+        return (None, None, match_iso)
+    f = match_noise.split(',')
+    if len(f) != 2:
+        raise SystemExit("--match_noise takes a,b or auto, got %r" % match_noise)
+    try:
+        a, b = float(f[0]), float(f[1])
+    except ValueError:
+        raise SystemExit("--match_noise takes numbers a,b or auto, got %r" % match_noise)
+    if not (0 < a < float("inf")) or not abs(b) < float("inf"):
+        raise SystemExit("--match_noise: a must be finite and > 0 and b finite, got %r" % match_noise)
+    return (a, b, match_iso)
+
+
+def match_report(a, b, bit_depth, iso):
+    """The coefficients of --match_noise a,b --match_iso iso (`runtime.match_coeffs`), the `match:` line sent to the log, and the
+    warning where the footage is cleaner than the checkpoint's curve.  -> struct rvdd_match_cfg"""
+    from . import noise
+    try:
+        cfg, s, t = match_coeffs(a, b, bit_depth, iso)
+    except RuntimeError as err:
+        raise SystemExit("--match_noise: %s" % err)
+    print('match: ' + noise.format_match_line(cfg, s, t, iso))
+    if s > 1.0:
+        print('match: WARNING: the footage is cleaner than the ISO %d checkpoints\' noise curve: matching stretches it by s = %.3f beyond '
+              'the range the network was trained on, which can lose quality (DESIGN.md 4.16: the table of measured gains and losses)' % (iso, s))
+    return cfg
+
+
+def estimate_noise(dataset, dev, bit_depth, frames, flag='--dpc_noise'):
+    """--dpc_noise auto / --match_noise auto: (a, b) of `noise.estimate` on the run's videos, the line `python -m rvdd_release_amd.noise` prints sent to
     the log; SystemExit with the fit's message where it refuses."""
     from . import noise
     from .util._ops import ops_runtime
@@ -157,7 +210,7 @@ def estimate_noise(dataset, dev, bit_depth, frames):
     try:
         r = noise.report(acc, bit_depth, read)
     except RuntimeError as err:
-        raise SystemExit("--dpc_noise auto: %s -- pass the curve as --dpc_noise a,b" % err)
+        raise SystemExit("%s auto: %s -- pass the curve as %s a,b" % (flag, err, flag))
     print('noise: ' + noise.format_line(r))
     return (r["a"], r["b"])
 
@@ -176,6 +229,9 @@ def _parse(argv):
     p.add_argument('--dpc_noise', type=str, default=None, help='a,b[,floor]: var = a * m - b in DN of the frames, the least variance; '
                    'auto[,floor]: estimated from the footage (assumes one camera setting for the whole run)')
     p.add_argument('--dpc_noise_frames', type=int, default=None, help='with --dpc_noise auto: frames read per video (default 4)')
+    p.add_argument('--match_noise', type=str, default=None, help="a,b: the footage's curve var = a * m - b in DN of the frames, mapped onto "
+                   'the curve of --match_iso; auto: estimated from the footage')
+    p.add_argument('--match_iso', type=int, default=None, help="the checkpoint family's noise curve: 3200 or 12800")
     own, rest = p.parse_known_args(argv)
     if own.out_format not in OUT_FORMATS:
         raise SystemExit("--out_format %r is not one of %s" % (own.out_format, ', '.join(OUT_FORMATS)))
@@ -188,6 +244,7 @@ def _parse(argv):
         raise SystemExit("--out_format %s needs --out_bit_depth (default: --bit_depth) 10, 12 or 14, got %d" % (opt.out_format, opt.out_bit_depth))
     opt.dpc = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth), own.dpc_noise_frames)
     opt.dpc_noise_frames = 4 if own.dpc_noise_frames is None else own.dpc_noise_frames
+    opt.match = match_arguments(own.match_noise, own.match_iso)
     if opt.raw_container is not None:
         if opt.raw_container != 'mipi':
             raise SystemExit("--raw_container %r: headerless frames are 'mipi' (packed TIFFs are recognised by themselves)" % opt.raw_container)
@@ -222,8 +279,16 @@ def main(argv=None) -> dict:
     model.setup(opt)
     net, dev = model._netDenoise, model.device
     fut = int(opt.future_patch_depth)
-    if opt.dpc is not None and opt.dpc[2] is None:      # --dpc_noise auto: the curve of the run's own footage, before any push
-        opt.dpc = opt.dpc[:2] + estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames) + opt.dpc[4:]
+    curve = None                                  # --dpc_noise auto / --match_noise auto: ONE estimate of the run's own footage, before any push
+    if opt.dpc is not None and opt.dpc[2] is None:
+        curve = estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames)
+        opt.dpc = opt.dpc[:2] + curve + opt.dpc[4:]
+    match = None
+    if opt.match is not None:
+        if opt.match[0] is None:
+            curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--match_noise')
+            opt.match = curve + opt.match[2:]
+        match = match_report(opt.match[0], opt.match[1], int(opt.bit_depth), opt.match[2])
 
     groups = {}                                   # frame size -> its videos, in dataset order
     for key, frames in dataset.videos:
@@ -241,6 +306,7 @@ def main(argv=None) -> dict:
         rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
         rt.set_option("stream_all_frames", int(opt.all_frames))
         rt.set_dpc(None if opt.dpc is None else dpc_cfg(*opt.dpc))
+        rt.set_match(match)
         dpc_seen = rt.dpc_counts() if opt.dpc is not None else None      # rvdd_dpc_counts at the end of the slot's last video
         dpc_frames = [0] * B                        # frames the slot's video has pushed
         container = dataset.container               # None, or "msb" / "mipi": the frames stay bit-packed up to the device

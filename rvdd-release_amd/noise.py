@@ -1,5 +1,5 @@
 """The sensor's noise curve from the footage itself:
-`python -m rvdd_release_amd.noise --dataroot D --nFolder noisy --bit_depth 12 [--frames K] [container flags of denoise]`.
+`python -m rvdd_release_amd.noise --dataroot D --nFolder noisy --bit_depth 12 [--frames K] [--match_iso ISO] [container flags of denoise]`.
 
 Reads the tree `denoise` reads (`--dataset_mode rawvideo`: uint16 / float32 mosaics or packed frames, TIFFs of packed 10 / 12 / 14-bit
 samples, or with `--raw_container mipi --raw_size WxH` headerless MIPI CSI-2 frames), ingests the first K frames (default 4) of up
@@ -15,6 +15,14 @@ clipped: the share of the blocks seen that touch 0 or the top of the range; rms:
 fit; nearest_iso: which of the two checkpoint families' curves (ISO 3200 / 12800 of the reference's synthetic camera, rescaled to
 --bit_depth) predicts the closest standard deviation at 20 / 45 / 80 % of the range, and the ratios estimate / that curve there.
 
+With `--match_iso ISO` (3200 / 12800) a second line follows, the one `denoise --match_noise a,b --match_iso ISO` prints:
+
+    match: {"scale": ..., "offset": ..., "s": ..., "t_dn12": ..., "iso": ...}
+
+the affine map v' = scale * v + offset on samples in [-1,1] that takes the estimated curve onto that checkpoint family's
+(`rvdd_match_coeffs`; x' = s x + t_dn12 in 12-bit DN), every number with 17 digits.  s > 1: the footage is cleaner than the curve and
+the map stretches it beyond the trained range.
+
 The estimate assumes ONE camera setting -- one gain, one curve -- for everything it reads: footage of several gains in one tree gives
 a curve of none of them.  Texture only ever raises a block's variance and the fit reads the lower quartile, so a busy scene comes out
 a few per cent high in sigma, the safe side for --dpc.  Footage with too little tonal range is refused with the
@@ -28,7 +36,7 @@ import copy
 import numpy as np
 import torch
 
-from .runtime import NOISE_ACC_BYTES, nearest_iso, noise_acc_arrays, noise_fit, raw_frames_to_device
+from .runtime import DPC_ISO_CURVES, NOISE_ACC_BYTES, match_coeffs, nearest_iso, noise_acc_arrays, noise_fit, raw_frames_to_device
 
 MAX_VIDEOS = 16
 
@@ -70,15 +78,23 @@ def format_line(r: dict) -> str:
                ", ".join("%.4f" % v for v in r["ratios"])))
 
 
+def format_match_line(cfg, s: float, t: float, iso: int) -> str:
+    """the JSON of the `match:` line: what `runtime.match_coeffs` returned, every number as %.17g"""
+    return '{"scale": %.17g, "offset": %.17g, "s": %.17g, "t_dn12": %.17g, "iso": %d}' % (cfg.scale, cfg.offset, s, t, iso)
+
+
 def main(argv=None) -> dict:
     from .data import create_dataset
     from .options import parse
     from .util._ops import ops_runtime
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--frames', type=int, default=4, help='frames read per video (the first ones)')
+    p.add_argument('--match_iso', type=int, default=None, help="also print the map onto this checkpoint family's curve (3200 / 12800)")
     own, rest = p.parse_known_args(argv)
     if own.frames < 1:
         raise SystemExit("--frames must be >= 1, got %d" % own.frames)
+    if own.match_iso is not None and own.match_iso not in DPC_ISO_CURVES:
+        raise SystemExit("--match_iso must be one of %s, got %r" % (', '.join(str(k) for k in DPC_ISO_CURVES), own.match_iso))
     opt = parse(rest)
     if not any(a == '--dataset_mode' or a.startswith('--dataset_mode=') for a in rest):
         opt.dataset_mode = 'rawvideo'
@@ -94,6 +110,13 @@ def main(argv=None) -> dict:
     except RuntimeError as err:
         raise SystemExit(str(err))
     print(format_line(r))
+    if own.match_iso is not None:
+        try:
+            cfg, s, t = match_coeffs(r["a"], r["b"], int(opt.bit_depth), own.match_iso)
+        except RuntimeError as err:
+            raise SystemExit(str(err))
+        print('match: ' + format_match_line(cfg, s, t, own.match_iso))
+        r["match"] = {"scale": cfg.scale, "offset": cfg.offset, "s": s, "t_dn12": t, "iso": own.match_iso}
     return r
 
 

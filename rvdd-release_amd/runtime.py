@@ -111,6 +111,33 @@ def nearest_iso(a: float, b: float, bit_depth: int = 12, levels=(0.20, 0.45, 0.8
     return best[1], best[2]
 
 
+def match_cfg(scale: float, offset: float) -> "_lib.RvddMatchCfg":
+    """struct rvdd_match_cfg of Python doubles, each rounded to f32 once"""
+    return _lib.RvddMatchCfg(float(scale), float(offset))
+
+
+def match_coeffs(a: float, b: float, bit_depth: int, iso_or_curve):
+    """The affine map that takes footage of the noise curve var(m) = a * m - b, in DN of `bit_depth` (what `noise_fit` returns), onto a
+    checkpoint's curve (rvdd_match_coeffs: on the host, no GPU needed).  iso_or_curve: 3200 / 12800, a key of DPC_ISO_CURVES, or the
+    curve itself as (a_ref, b_ref) in 12-bit DN.  -> (cfg, s, t): cfg the struct `match_raw` / `unmatch_rgb` / `set_match` take
+    (v' = cfg.scale * v + cfg.offset on samples in [-1,1]), s and t the map x' = s * x + t in 12-bit DN.  s > 1 means footage cleaner
+    than the checkpoint's curve: the map stretches it beyond the trained range."""
+    lib = _lib.load()
+    if isinstance(iso_or_curve, (tuple, list)):
+        if len(iso_or_curve) != 2:
+            raise ValueError(f"match_coeffs: a curve is (a_ref, b_ref) in 12-bit DN, got {iso_or_curve!r}")
+        a_ref, b_ref = (float(v) for v in iso_or_curve)
+    elif iso_or_curve in DPC_ISO_CURVES:
+        a_ref, b_ref = DPC_ISO_CURVES[iso_or_curve]
+    else:
+        raise ValueError(f"match_coeffs: {iso_or_curve!r} is not one of {', '.join(str(k) for k in DPC_ISO_CURVES)} or a curve (a_ref, b_ref)")
+    cfg, st = _lib.RvddMatchCfg(), (C.c_double * 2)()
+    rc = lib.rvdd_match_coeffs(float(a), float(b), int(bit_depth), a_ref, b_ref, C.byref(cfg), st)
+    if rc != 0:
+        raise RuntimeError(f"rvdd_match_coeffs failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    return cfg, float(st[0]), float(st[1])
+
+
 def raw_frames_to_device(frames, device) -> torch.Tensor:
     """Host sensor frames (a numpy array or CPU tensor of uint16 / int16 / float32) -> a tensor on `device` that
     `ingest_raw` / `video_push` accept.  uint16 arrays travel as their int16 view: the bytes are what crosses the ABI."""
@@ -501,6 +528,37 @@ class RvddRuntime:
             raise RuntimeError(f"noise_hist: acc is a contiguous tensor of {NOISE_ACC_BYTES} bytes on cuda:{self.device} (what noise_hist returned)")
         self._check(self.lib.rvdd_noise_hist(self.h, _ptr(packed), n, hh, ww, int(bit_depth), _ptr(acc), self._stream()), "rvdd_noise_hist")
         return acc
+
+    # -- footage matched to the checkpoint's noise curve ---------------------------------
+    def _match(self, fn, name: str, t: torch.Tensor, c: int, cfg, out: Optional[torch.Tensor]) -> torch.Tensor:
+        if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != c:
+            raise RuntimeError(f"{name}: the frames are [n,{c},h,w], got {tuple(getattr(t, 'shape', ()))}")
+        n, _, d0, d1 = t.shape
+        t = _chk_dev(t, t.shape, "frames", self.device)
+        if out is None:
+            out = torch.empty_like(t)
+        else:
+            _chk_dev(out, t.shape, "out", self.device)
+            assert out.is_contiguous()
+        self._check(fn(self.h, _ptr(t), _ptr(out), n, d0, d1, None if cfg is None else C.byref(cfg), self._stream()), "rvdd_" + name)
+        return out
+
+    def match_raw(self, packed: torch.Tensor, cfg, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Packed frames [n,4,hh,ww] mapped onto the checkpoint's noise curve: (cfg.scale * v) + cfg.offset (rvdd_match_raw; cfg:
+        `match_cfg(scale, offset)` or the first item `match_coeffs` returns).  -> `out`, or a new tensor; out = packed maps in place.
+        Nothing is synchronised."""
+        return self._match(self.lib.rvdd_match_raw, "match_raw", packed, 4, cfg, out)
+
+    def unmatch_rgb(self, rgb: torch.Tensor, cfg, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Network outputs [n,3,H,W] mapped back to the sensor's domain: (v - cfg.offset) * (1 / cfg.scale) (rvdd_unmatch_rgb).
+        -> `out`, or a new tensor; out = rgb maps in place.  Nothing is synchronised."""
+        return self._match(self.lib.rvdd_unmatch_rgb, "unmatch_rgb", rgb, 3, cfg, out)
+
+    def set_match(self, cfg=None):
+        """The map as a stage of `video_push` (rvdd_set_match): the kept packed frames are mapped behind the ingest (and the
+        correction of `set_dpc`), the outputs mapped back; flows are still matched on the sensor's own gray planes.
+        cfg = `match_cfg(...)`, None = off (the default)."""
+        self._check(self.lib.rvdd_set_match(self.h, None if cfg is None else C.byref(cfg)), "rvdd_set_match")
 
     def set_dpc(self, cfg=None):
         """The correction as a stage of `video_push`, between the ingest and the kept frames (rvdd_set_dpc): cfg = `dpc_cfg(...)`,
