@@ -527,6 +527,50 @@ typedef struct rvdd_noise_curve {
 } rvdd_noise_curve;
 int rvdd_noise_fit(const rvdd_noise_acc* acc_host /* HOST copy */, int32_t bit_depth, rvdd_noise_curve* out);
 
+/* ---- scene cuts: one small integer signature per frame ------------------------ */
+
+/* Where one shot ends and the next begins, so that a reel can be streamed shot by shot (RVDD_PUSH_FIRST at every cut) and the recurrence
+ * never aligns two unrelated images: rvdd_frame_sigs measures every frame on the device, rvdd_cut_score compares two measurements on the
+ * host.  The rule, on gray [n,hh,ww] -- the plane rvdd_ingest_raw / rvdd_ingest_bits write: f32, in DN of bit_depth -- with
+ * top = (float)(2^bit_depth - 1), every operation rounded to f32 on its own (no fused multiply-add), so that every integer below is
+ * reproducible in NumPy (tests/cuts_ref.py).  Per cell g = gray[i][y][x]:
+ *   c  = fminf(fmaxf(g, 0), top)
+ *   q  = (uint32) rintf(c * 4.0f)                    0 .. 4 * top, exact: gray is a mean of four DN; ties round to even
+ *   j  = min((int)(c * (64 / 2^bit_depth)), 63)      the level bin (the scale is a power of two, as rvdd_noise_hist's mean bin)
+ *   by = (16 * y) / hh,  bx = (16 * x) / ww          integer division (in 64 bits): 16 bands of rows x 16 columns; hh, ww >= 16, so
+ *                                                    that every band and every column holds at least one cell
+ *   hist[by][j] += 1;   sum[by][bx] += q
+ * Integer sums only, so the result does not depend on the order of summation: two runs give the same bits, and a batch gives what
+ * its frames give one at a time.  With NaN or inf in the input the counts are unspecified (as it happens fmaxf / fminf put NaN at 0
+ * and inf at an end of the range), but nothing outside the tensors is read or written. */
+typedef struct rvdd_frame_sig {   /* 6144 bytes */
+    uint32_t hist[16][64];        /* [band][level bin]: cells */
+    uint64_t sum[16][16];         /* [band][column]: sum of q */
+} rvdd_frame_sig;
+
+/* sig[i] = the signature of gray[i], every word of it OVERWRITTEN (the caller need not clear anything; nothing beyond sig[n - 1] is
+ * touched).  One kernel, one workgroup per (frame, band): every word of the struct has exactly one owner, which reads its band's rows
+ * -- a contiguous run of the plane --, counts in its LDS and writes its 64 + 16 words with plain stores.  No global atomics.  With
+ * ww % 4 == 0 and `gray` 16-byte aligned the rows are read with 16-byte loads, single floats otherwise: same integers either way.
+ * RVDD_ERR_ARG (the message names the argument) and nothing launched: bit_depth outside 1..16; hh or ww < 16; n < 0; NULL gray or
+ * sig with n > 0; sig not 8-byte aligned; a launch of more than 2^31 - 1 blocks (16 n).  n = 0 does nothing.  Asynchronous and
+ * stream-ordered; nothing is read back. */
+int rvdd_frame_sigs(rvdd_t* h, const float* gray /* [n,hh,ww] */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+                    rvdd_frame_sig* sig /* DEVICE [n], 8-byte aligned, OVERWRITTEN */, void* stream);
+
+/* How far two frames of hh x ww cells lie apart, from HOST copies of their signatures; f64 on the host, needs neither a device nor a
+ * handle (errors go where rvdd_noise_fit's go: rvdd_last_error(NULL)).  With H_a[j] = sum over the bands of a.hist[band][j] and
+ * N = hh * ww:
+ *   out2[0] = d_hist = sum_j |H_a[j] - H_b[j]| / (2 N)                                        in [0,1]: how much of the level histogram moved
+ *   out2[1] = d_grid = sum_blocks |a.sum - b.sum| / max(1, sum_blocks max(a.sum, b.sum))      in [0,1]: how much of the 16 x 16 layout moved
+ * Numerators and denominators are integer sums, converted to f64 once each: the same formulas on Python integers give the same bits.
+ * RVDD_ERR_ARG and *out2 untouched: NULL a / b / out2; hh or ww < 16; sum_j H[j] != N for either signature (the message says which:
+ * signatures of another frame size).
+ * A caller declares a cut where d_hist or d_grid exceeds a threshold (python -m rvdd_release_amd.cuts: 0.10 and 0.12; DESIGN.md 4.17
+ * says what those rest on, and that none of it is measured on real footage). */
+int rvdd_cut_score(const rvdd_frame_sig* a /* HOST */, const rvdd_frame_sig* b /* HOST */, int32_t hh, int32_t ww,
+                   double* out2 /* HOST { d_hist, d_grid } */);
+
 /* ---- footage matched to the checkpoint's noise curve ------------------------- */
 
 /* The checkpoints were trained on two noise curves of one synthetic camera (in 12-bit DN: ISO 3200 var = 8.0034 m - 2043.51144, ISO

@@ -52,6 +52,11 @@ class RvddNoiseCurve(C.Structure):
                 ("blocks", C.c_uint64), ("bins", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RvddFrameSig(C.Structure):
+    """struct rvdd_frame_sig (rvdd_frame_sigs, rvdd_cut_score): 6144 bytes"""
+    _fields_ = [("hist", (C.c_uint32 * 64) * 16), ("sum", (C.c_uint64 * 16) * 16)]
+
+
 # symbol -> (restype, argtypes); exactly the functions include/rvdd.h declares
 _P = C.c_void_p
 _PROTOS = {
@@ -90,6 +95,8 @@ _PROTOS = {
     "rvdd_dpc_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), _P]),
     "rvdd_noise_hist": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_noise_fit": (C.c_int, [C.POINTER(RvddNoiseAcc), C.c_int32, C.POINTER(RvddNoiseCurve)]),
+    "rvdd_frame_sigs": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rvdd_cut_score": (C.c_int, [C.POINTER(RvddFrameSig), C.POINTER(RvddFrameSig), C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "rvdd_match_coeffs": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(RvddMatchCfg),
                                     C.POINTER(C.c_double)]),
     "rvdd_match_raw": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddMatchCfg), _P]),

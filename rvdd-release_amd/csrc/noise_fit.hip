@@ -1,4 +1,4 @@
-// rvdd_noise_fit and rvdd_match_coeffs: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
+// rvdd_noise_fit, rvdd_cut_score and rvdd_match_coeffs: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
 // Host code only, f64, no device and no handle; compiled -ffp-contract=off so that tests/noise_ref.py, which runs the same sums in
 // the same order in Python doubles, gets the same numbers.
 #include "runtime_internal.h"
@@ -85,6 +85,44 @@ extern "C" int rvdd_noise_fit(const rvdd_noise_acc* acc, int32_t bit_depth, rvdd
         sr += ns[k] * (r * r);
     }
     *out = rvdd_noise_curve{a, b, m_min, m_max, std::sqrt(sr / (double)blocks), blocks, bins, 0};
+    return RVDD_OK;
+}
+
+// rvdd_cut_score: the distance of two frame signatures (rvdd_frame_sigs; the rule is in include/rvdd.h).  Integer sums, each converted to
+// f64 once, one division each: the same formulas on Python integers give the same bits (tests/cuts_ref.py).
+extern "C" int rvdd_cut_score(const rvdd_frame_sig* a, const rvdd_frame_sig* b, int32_t hh, int32_t ww, double* out2) {
+    if (!a) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cut_score: a is required");
+    if (!b) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cut_score: b is required");
+    if (!out2) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cut_score: out2 is required");
+    if (hh < 16) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cut_score: hh must be >= 16, got %d", hh);
+    if (ww < 16) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cut_score: ww must be >= 16, got %d", ww);
+    const uint64_t cells = (uint64_t)hh * (uint64_t)ww;
+    uint64_t ha[64], hb[64], na = 0, nb = 0, dh = 0;
+    for (int j = 0; j < 64; ++j) {
+        ha[j] = hb[j] = 0;
+        for (int band = 0; band < 16; ++band) {
+            ha[j] += a->hist[band][j];
+            hb[j] += b->hist[band][j];
+        }
+        na += ha[j];
+        nb += hb[j];
+        dh += ha[j] > hb[j] ? ha[j] - hb[j] : hb[j] - ha[j];
+    }
+    if (na != cells)
+        return fail(nullptr, RVDD_ERR_ARG, "rvdd_cut_score: a counts %llu cells, a frame of hh x ww = %d x %d has %llu: a signature of another frame size",
+                    (unsigned long long)na, hh, ww, (unsigned long long)cells);
+    if (nb != cells)
+        return fail(nullptr, RVDD_ERR_ARG, "rvdd_cut_score: b counts %llu cells, a frame of hh x ww = %d x %d has %llu: a signature of another frame size",
+                    (unsigned long long)nb, hh, ww, (unsigned long long)cells);
+    unsigned __int128 dg = 0, mg = 0;          // 256 sums of up to 2^62 cells x 2^18 each
+    for (int band = 0; band < 16; ++band)
+        for (int col = 0; col < 16; ++col) {
+            const uint64_t sa = a->sum[band][col], sb = b->sum[band][col];
+            dg += sa > sb ? sa - sb : sb - sa;
+            mg += sa > sb ? sa : sb;
+        }
+    out2[0] = (double)dh / (double)(2 * (unsigned __int128)cells);
+    out2[1] = (double)dg / (mg ? (double)mg : 1.0);
     return RVDD_OK;
 }
 

@@ -345,6 +345,22 @@ int rvdd_noise_hist(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32
     return RVDD_OK;
 }
 
+int rvdd_frame_sigs(rvdd_t* h, const float* gray, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, rvdd_frame_sig* sig, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: bit_depth must be 1..16, got %d", bit_depth);
+    if (hh < 16) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: hh must be >= 16 (16 bands of at least one row), got %d", hh);
+    if (ww < 16) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: ww must be >= 16 (16 columns of at least one cell), got %d", ww);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: n must be >= 0, got %d", n);
+    if (n == 0) return RVDD_OK;
+    if (!gray) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: gray is required");
+    if (!sig) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: sig is required");
+    if (reinterpret_cast<uintptr_t>(sig) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: sig must be 8-byte aligned (its sums are 64-bit words)");
+    if (n > 0x7fffffff / 16) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: n = %d needs a launch of more than 2^31 - 1 blocks (16 per frame)", n);
+    ENTER(h);
+    HIPCHK(h, launch_frame_sigs(gray, n, hh, ww, bit_depth, sig, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 // the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine
 static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int32_t W) {
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);

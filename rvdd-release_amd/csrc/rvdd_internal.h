@@ -426,6 +426,14 @@ hipError_t launch_noise_hist(const float* packed, int n, int hh, int ww, int bit
 bool noise_wide(const float* packed, int ww);
 int64_t noise_groups(int n, int hh, int ww, int64_t* blocks);
 
+// cuts.hip -- one integer signature per frame for scene-cut detection (rvdd_frame_sigs)
+struct rvdd_frame_sig;
+// sig[i] (DEVICE, every word overwritten) = the signature of gray [n][hh][ww], one workgroup per (frame, band); n = 0 launches nothing;
+// hh, ww >= 16, n <= (2^31 - 1) / 16
+hipError_t launch_frame_sigs(const float* gray, int n, int hh, int ww, int bit_depth, rvdd_frame_sig* sig, hipStream_t s);
+// whether that launch takes the wide form (16-byte loads)
+bool frame_sig_wide(const float* gray, int ww);
+
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from
 // (seed, frame0 + image) then); lin_f32 / lin_u16 [n][2hh][2ww][3], gt_raw / noisy [n][hh][ww][4], each nullable

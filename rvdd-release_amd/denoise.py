@@ -59,12 +59,28 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       noisier than the curve (s < 1, low light) is what the map is for: +3.5 to +4.6 dB on the synthetic camera.
                       Footage cleaner than the curve (s > 1) is stretched beyond the trained range and can LOSE quality: a warning
                       says so (DESIGN.md 4.16 has the table).  Without the flags the output files keep their bytes.
+  --cuts auto         a folder need not be one shot: before the first push every frame of the run is measured on the device (one 6 KiB
+                      integer signature per frame, `rvdd_frame_sigs`; python -m rvdd_release_amd.cuts is the same pass on its own) and
+                      every video is split where consecutive frames differ by more than --cut_hist T (default 0.10: the share of cells
+                      whose level bin changed) or --cut_grid T (default 0.12: the share of the 16 x 16 layout that moved).  Each shot is
+                      then streamed as a video of its own under the SAME key: a fresh recurrence and no flow across the cut, the files in
+                      the same folder under the frames' own names -- byte for byte the run on a tree in which every shot is its own
+                      folder.  --cut_min_len L (default 4, at least 2 + future): cuts that would leave a shorter shot are dropped.
+                      Prints `cuts: <key>: N frames, shots at [0, k1, ...]` per video; `dpc:` lines are then per shot and name its first
+                      frame.  Without --all_frames the first frame and the last `future` frames of every SHOT are not written, as for
+                      any video: pass --all_frames with --cuts.  The pass reads every frame a second time;
+  --cuts FILE         reads the lines python -m rvdd_release_amd.cuts printed (`{"video": key, "frames": N, "cuts": [k, ...]}`) instead.
+                      A key that is not in the run, or a cut outside 1 .. N-1, is an error that names it.
+                      The thresholds rest on synthetic scenes of 128 x 192 cells and more; NOTHING is measured on
+                      real footage.  Look-alike shots and fades are not found, which leaves today's behaviour.  --dpc_noise auto still
+                      reads the first frames of every FOLDER.  Without --cuts no new call is made and the output files keep their bytes.
 Videos of different frame sizes are grouped by size and run one group after the other, one runtime per size.
 """
 from __future__ import annotations
 
 import argparse
 import copy
+import json
 import os
 import time
 from typing import List, Sequence, Tuple
@@ -215,9 +231,96 @@ def estimate_noise(dataset, dev, bit_depth, frames, flag='--dpc_noise'):
     return (r["a"], r["b"])
 
 
+def cuts_arguments(cuts, own, future):
+    """--cuts / --cut_hist / --cut_grid / --cut_min_len -> None (no --cuts), ("auto", t_hist, t_grid, min_len) or ("file", path);
+    SystemExit where the flags do not fit together.  min_len is at least 2 + future: a shot that yields a frame."""
+    from . import cuts as C
+    given = [f for f in ("cut_hist", "cut_grid", "cut_min_len") if getattr(own, f) is not None]
+    if cuts is None:
+        if given:
+            raise SystemExit("--cut_hist, --cut_grid and --cut_min_len belong to --cuts auto")
+        return None
+    if cuts == "auto":
+        return ("auto",) + C.thresholds(own, 2 + int(future))
+    if given:
+        raise SystemExit("--%s belongs to --cuts auto: --cuts %s reads cuts that are already decided" % (given[0], cuts))
+    return ("file", cuts)
+
+
+def read_cuts_file(path):
+    """The lines `python -m rvdd_release_amd.cuts` printed -> {video key: [k, ...]}; other lines of a log are skipped; SystemExit for a
+    file that cannot be read or a line that starts like one of them and is not."""
+    found = {}
+    try:
+        with open(path) as f:
+            lines = f.read().splitlines()
+    except OSError as err:
+        raise SystemExit("--cuts %s: %s" % (path, err))
+    for no, line in enumerate(lines, 1):
+        line = line.strip()
+        if not line.startswith('{"video"'):
+            continue
+        try:
+            rec = json.loads(line)
+            key, cuts = rec["video"], [int(k) for k in rec["cuts"]]
+            if not isinstance(key, str) or any(k != v for k, v in zip(cuts, rec["cuts"])):
+                raise ValueError("a video is a string and a cut an integer")
+        except (ValueError, KeyError, TypeError) as err:
+            raise SystemExit('--cuts %s, line %d: not a {"video": ..., "frames": ..., "cuts": [...]} line (%s)' % (path, no, err))
+        if key in found:
+            raise SystemExit("--cuts %s, line %d: video %r appears twice" % (path, no, key))
+        found[key] = cuts
+    return found
+
+
+def split_shots(videos, cuts_by_key):
+    """videos [(key, [paths])] and {key: [k, ...]} -> the shots [(key, [paths of the shot])], in order: every video cut in front of its
+    frames k -- each shot a video of its own under the SAME key, so that its files land in the video's folder under the frames' own
+    names.  A video without an entry stays whole.  SystemExit that names it for a key that is not among the videos, and for an index
+    outside 1 .. N-1."""
+    keys = {key for key, _ in videos}
+    for key in cuts_by_key:
+        if key not in keys:
+            raise SystemExit("--cuts: video %r is not in this run (its videos: %s)" % (key, ', '.join(sorted(keys))))
+    shots = []
+    for key, frames in videos:
+        starts = [0]
+        for k in sorted(set(cuts_by_key.get(key, ()))):
+            if not 1 <= k <= len(frames) - 1:
+                raise SystemExit("--cuts: video %r: cut %d is outside 1 .. %d (the video has %d frames)" % (key, k, len(frames) - 1, len(frames)))
+            starts.append(k)
+        for a, b in zip(starts, starts[1:] + [len(frames)]):
+            shots.append((key, frames[a:b]))
+    return shots
+
+
+def find_shots(dataset, dev, opt):
+    """--cuts: the run's videos as their shots (`split_shots`), one `cuts: <key>: N frames, shots at [0, k1, ...]` line per video sent to
+    the log.  auto: `cuts.detect` on the run's own videos, before any push."""
+    if opt.cuts[0] == "auto":
+        from . import cuts as C
+        from .util._ops import ops_runtime
+        _, t_hist, t_grid, min_len = opt.cuts
+        t0 = time.time()
+        found = C.detect(ops_runtime(dev.index or 0), dataset, dataset.videos, int(opt.bit_depth), t_hist, t_grid, min_len)
+        by_key = {key: cuts for key, _, cuts, _ in found}
+        print('cuts: measured %d frames in %.3f s (--cuts FILE with the lines of python -m rvdd_release_amd.cuts saves the pass)'
+              % (sum(n for _, n, _, _ in found), time.time() - t0))
+    else:
+        by_key = read_cuts_file(opt.cuts[1])
+    shots = split_shots(dataset.videos, by_key)
+    for key, frames in dataset.videos:
+        print('cuts: %s: %d frames, shots at [%s]' % (key, len(frames), ', '.join(str(k) for k in [0] + sorted(set(by_key.get(key, ()))))))
+    return shots
+
+
 def _parse(argv):
+    from . import cuts as C
     from .options import parse
     p = argparse.ArgumentParser(add_help=False)
+    p.add_argument('--cuts', type=str, default=None, help='auto: split every video at its scene cuts, found on the device before streaming '
+                   'starts; FILE: at the cuts of the lines python -m rvdd_release_amd.cuts printed')
+    C.add_arguments(p)
     p.add_argument('--results_dir', type=str, default='./results')
     p.add_argument('--srgb', type=str, default=None, help='ISO,n,red_gain,blue_gain: also write <frame>_srgb.png')
     p.add_argument('--out_format', type=str, default='f32', help=', '.join(OUT_FORMATS))
@@ -245,6 +348,7 @@ def _parse(argv):
     opt.dpc = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth), own.dpc_noise_frames)
     opt.dpc_noise_frames = 4 if own.dpc_noise_frames is None else own.dpc_noise_frames
     opt.match = match_arguments(own.match_noise, own.match_iso)
+    opt.cuts = cuts_arguments(own.cuts, own, opt.future_patch_depth)
     if opt.raw_container is not None:
         if opt.raw_container != 'mipi':
             raise SystemExit("--raw_container %r: headerless frames are 'mipi' (packed TIFFs are recognised by themselves)" % opt.raw_container)
@@ -290,8 +394,10 @@ def main(argv=None) -> dict:
             opt.match = curve + opt.match[2:]
         match = match_report(opt.match[0], opt.match[1], int(opt.bit_depth), opt.match[2])
 
+    # --cuts: every shot is a video of its own from here on, under its video's key
+    shots = dataset.videos if opt.cuts is None else find_shots(dataset, dev, opt)
     groups = {}                                   # frame size -> its videos, in dataset order
-    for key, frames in dataset.videos:
+    for key, frames in shots:
         groups.setdefault(dataset.frame_size(frames[0]), []).append((key, frames))
     written = 0
     t0 = time.time()
@@ -338,8 +444,8 @@ def main(argv=None) -> dict:
                 last = k == len(frames) - (0 if opt.all_frames and fut else 1)      # the step that ends the video
                 ended = ended or last
                 dpc_frames[b] = min(k + 1, len(frames))
-                if last:
-                    ends.append((b, key))
+                if last:                                # --cuts: several shots share a key; the line names the shot's first frame
+                    ends.append((b, key if opt.cuts is None else '%s from %s' % (key, os.path.basename(frames[0]))))
                 if not valid[b]:
                     continue
                 path = frames[k - fut]                  # the centre frame

@@ -95,6 +95,50 @@ def noise_fit(acc, bit_depth: int) -> Dict[str, float]:
             "rms": out.rms}
 
 
+FRAME_SIG_BYTES = C.sizeof(_lib.RvddFrameSig)      # struct rvdd_frame_sig: u32 hist[16][64], u64 sum[16][16]
+
+
+def _frame_sig_bytes(sig, what: str):
+    """the bytes of n whole structs rvdd_frame_sig as a C-contiguous uint8 array [n,6144] on the host (a device tensor is copied)"""
+    import numpy as np
+    if torch.is_tensor(sig):
+        raw = sig.detach().cpu().contiguous().view(torch.uint8).numpy()
+    elif isinstance(sig, np.ndarray):
+        raw = np.ascontiguousarray(sig).view(np.uint8)
+    else:
+        raw = np.frombuffer(bytes(sig), np.uint8)
+    if raw.size % FRAME_SIG_BYTES:
+        raise RuntimeError(f"{what}: a frame signature is {FRAME_SIG_BYTES} bytes (struct rvdd_frame_sig), got {raw.size}")
+    return raw.reshape(-1, FRAME_SIG_BYTES)
+
+
+def frame_sig_arrays(sig):
+    """Signatures of `RvddRuntime.frame_sigs` (the tensor [n,6144], or any array / bytes of n structs rvdd_frame_sig) as NumPy views of
+    ONE host copy: {"hist": uint32 [n,16,64] (cells per band and level bin), "sum": uint64 [n,16,16] (sum of q per band and column)}."""
+    import numpy as np
+    raw = _frame_sig_bytes(sig, "frame_sig_arrays")
+    rec = raw.reshape(-1).view(np.dtype([("hist", np.uint32, (16, 64)), ("sum", np.uint64, (16, 16))]))
+    return {"hist": rec["hist"], "sum": rec["sum"]}
+
+
+def cut_score(a, b, hh: int, ww: int) -> Tuple[float, float]:
+    """(d_hist, d_grid) of two frames of hh x ww cells from their signatures (rvdd_cut_score: on the host, no GPU needed).  a, b: one
+    struct rvdd_frame_sig each -- a row of the tensor `RvddRuntime.frame_sigs` returned (a device tensor is copied, which
+    synchronises), an array or bytes of its 6144 bytes.  RuntimeError with the library's message for signatures of another frame size."""
+    lib = _lib.load()
+    host = []
+    for s, name in ((a, "a"), (b, "b")):
+        raw = _frame_sig_bytes(s, "cut_score")
+        if raw.shape[0] != 1:
+            raise RuntimeError(f"cut_score: {name} is ONE signature of {FRAME_SIG_BYTES} bytes, got {raw.shape[0]}")
+        host.append(_lib.RvddFrameSig.from_buffer_copy(raw.tobytes()))
+    out = (C.c_double * 2)()
+    rc = lib.rvdd_cut_score(C.byref(host[0]), C.byref(host[1]), int(hh), int(ww), out)
+    if rc != 0:
+        raise RuntimeError(f"rvdd_cut_score failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    return float(out[0]), float(out[1])
+
+
 def nearest_iso(a: float, b: float, bit_depth: int = 12, levels=(0.20, 0.45, 0.80)):
     """Which of DPC_ISO_CURVES lies closest to the curve (a, b) in DN of `bit_depth`: -> (iso, ratios), the ISO whose predicted
     standard deviation at 20 %, 45 % and 80 % of 2^bit_depth - 1 is nearest in the log (the largest |log ratio| over the levels is
@@ -528,6 +572,24 @@ class RvddRuntime:
             raise RuntimeError(f"noise_hist: acc is a contiguous tensor of {NOISE_ACC_BYTES} bytes on cuda:{self.device} (what noise_hist returned)")
         self._check(self.lib.rvdd_noise_hist(self.h, _ptr(packed), n, hh, ww, int(bit_depth), _ptr(acc), self._stream()), "rvdd_noise_hist")
         return acc
+
+    # -- scene cuts: one signature per frame ----------------------------------------------
+    def frame_sigs(self, gray: torch.Tensor, bit_depth: int = 12, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The signatures of gray planes [n,hh,ww] (f32, in DN: what `ingest_raw` / `ingest_bits` return) as a device uint8 tensor
+        [n,6144], one struct rvdd_frame_sig per frame (rvdd_frame_sigs).  out: a contiguous uint8 tensor of that shape on this device to
+        overwrite.  `frame_sig_arrays` gives the counts and sums, `cut_score(sig[k - 1], sig[k], hh, ww)` the distance of two frames.
+        Nothing is synchronised."""
+        if not torch.is_tensor(gray) or gray.dim() != 3:
+            raise RuntimeError(f"frame_sigs: gray is [n,hh,ww], got {tuple(getattr(gray, 'shape', ()))}")
+        n, hh, ww = gray.shape
+        gray = _chk_dev(gray, gray.shape, "gray", self.device)
+        if out is None:
+            out = torch.empty(n, FRAME_SIG_BYTES, dtype=torch.uint8, device=self._tdev)
+        elif not torch.is_tensor(out) or not out.is_cuda or out.device.index != self.device or out.dtype != torch.uint8 \
+                or tuple(out.shape) != (n, FRAME_SIG_BYTES) or not out.is_contiguous():
+            raise RuntimeError(f"frame_sigs: out is a contiguous uint8 tensor [{n},{FRAME_SIG_BYTES}] on cuda:{self.device}")
+        self._check(self.lib.rvdd_frame_sigs(self.h, _ptr(gray), n, hh, ww, int(bit_depth), _ptr(out), self._stream()), "rvdd_frame_sigs")
+        return out
 
     # -- footage matched to the checkpoint's noise curve ---------------------------------
     def _match(self, fn, name: str, t: torch.Tensor, c: int, cfg, out: Optional[torch.Tensor]) -> torch.Tensor:
