@@ -466,6 +466,77 @@ int rvdd_set_dpc(rvdd_t* h, const rvdd_dpc_cfg* cfg /* NULL = off, the default *
  * synchronises it: call it where the loop synchronises anyway.  All zeros on a handle that never had the stage on. */
 int rvdd_dpc_counts(rvdd_t* h, uint64_t* hot_dead /* HOST [cfg.batch,2] */, void* stream /* synchronised */);
 
+/* The static defect map: the sites of persistent defects found once, then those sites and only those corrected.  A real defect sits
+ * at the same site in every frame while scene detail moves, so rvdd_dpc's rule is COUNTED per site over frames spread across the
+ * footage (rvdd_dpc_detect), the counts are thresholded on the host into a map, and the map is applied by rvdd_dpc_map_apply or as a
+ * stage of rvdd_video_push (rvdd_set_dpc_map).  dn(v), top, norm_dn(d) = 2 * (d / top) - 1 and the mirroring of the eight neighbours
+ * are rvdd_dpc's; every operation is rounded to f32 on its own, so every integer and every written value is reproducible bit for bit
+ * in NumPy (tests/dpc_map_ref.py).
+ *
+ * rvdd_dpc_detect.  Per sample of packed [n,4,hh,ww]: the eight neighbours of rvdd_dpc in ascending order s0 .. s7,
+ * m = (s3 + s4) * 0.5, var = fmaxf(noise_a * m - noise_b, var_floor) with the fields of cfg->rule, and with t = cfg->tolerate (0..3):
+ *   hot:  k_hot  > 0, d = c - s[7 - t] > 0 and d * d > (k_hot * k_hot) * var
+ *   dead: k_dead > 0, d = s[t] - c > 0 and d * d > (k_dead * k_dead) * var
+ * t = 0 is exactly rvdd_dpc's decision.  t > 0 also finds the members of clusters with at most t other defects among a site's eight
+ * same-colour neighbours (the median bears three).  It is meant for flat or dark calibration footage: on texture t > 0 flags edges
+ * and thin lines, where a sample legitimately stands above all but t of its neighbours.
+ * hits (DEVICE uint32 [4,hh,ww], the caller zeroes it before the first call): hits[k][y][x] holds the site's hot frames in its low 16
+ * bits and its dead frames in its high 16; the n frames of a call are ADDED, each half on its own, saturating at 65535.  One thread
+ * owns a site across the n frames and updates its word with a plain load, add and store -- no atomics -- and calls are
+ * stream-ordered, so the totals do not depend on how the frames are split over calls.
+ * RVDD_ERR_ARG (the message names the argument) and nothing launched: NULL cfg; the fields of cfg->rule as in rvdd_dpc; tolerate
+ * outside 0..3; reserved != 0; bit_depth outside 1..16; hh or ww < 2; n < 0; NULL hits; NULL packed with n > 0; a launch of more than
+ * 2^31 - 1 blocks.  n = 0 does nothing.  Asynchronous and stream-ordered; nothing is read back.
+ * With ww % 4 == 0 and both pointers 16-byte aligned a thread owns four neighbouring sites (16-byte loads and stores); every other
+ * case one site.  Same integers either way. */
+typedef struct rvdd_dpc_detect_cfg {
+    rvdd_dpc_cfg rule;        /* the thresholds and the noise curve, as rvdd_dpc takes them */
+    int32_t tolerate;         /* 0..3: other defects among the eight neighbours a site may have and still be found */
+    int32_t reserved;         /* 0 */
+} rvdd_dpc_detect_cfg;
+int rvdd_dpc_detect(rvdd_t* h, const float* packed /* [n,4,hh,ww] */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+                    const rvdd_dpc_detect_cfg* cfg, uint32_t* hits /* DEVICE [4,hh,ww], accumulated; caller zeroes */, void* stream);
+
+/* The map.  cellmask, uint8 [hh,ww]: bit k (0..3) is set where plane k of the cell -- CFA position (k >> 1, k & 1) -- is defective;
+ * bits 4..7 must be zero.  (On disk it is a one-sample uint8 image of the mosaic [2hh,2ww], nonzero = defective, whatever the Bayer
+ * pattern: python -m rvdd_release_amd.dpc_map writes it.)
+ * The correction of a defective sample of plane k at (y, x).  An index that leaves the plane is reflected about its edge (-i -> i,
+ * n - 1 + i -> n - 1 - i; for ring 1 that is rvdd_dpc's mirroring), hence hh, ww >= 3.  Ring 1 is the eight neighbours, ring 2 the
+ * sixteen sites of the border of the 5 x 5 window, dy outer and dx inner, ascending.  A site is GOOD iff bit k of cellmask at its
+ * reflected index is clear.  Of the first ring that has a good site, with q good values in DN in ascending order s0 .. s(q-1):
+ *   rep = (s[(q - 1) / 2] + s[q / 2]) * 0.5, and the sample becomes norm_dn(rep).
+ * If neither ring has a good site the sample is UNFIXABLE: it keeps its bits.
+ * gray (nullable), at every cell of the map: (((d0 + d1) + d2) + d3) * 0.25 with d_k = rep for a corrected plane and dn(p[k][y][x])
+ * for every other one (rvdd_dpc's convention); cells outside the map are not written.
+ *
+ * rvdd_dpc_map_stats: out3 = {defective samples, defective cells, unfixable samples} of a map, by the rule above, on the host -- it
+ * needs neither a handle nor a device (the error string is rvdd_last_error(NULL)'s).  RVDD_ERR_ARG: NULL cellmask / out3, hh or
+ * ww < 3, a bit above bit 3. */
+int rvdd_dpc_map_stats(const uint8_t* cellmask /* HOST [hh,ww] */, int32_t hh, int32_t ww,
+                       int64_t* out3 /* samples, cells, unfixable samples */);
+
+/* The handle's map: uploads the mask and the ascending list of its defective cells (device memory owned by the handle: hh * ww bytes
+ * and 4 bytes per defective cell, freed by the next call and with the handle).  NULL = off, the default.  An empty map is valid.
+ * Synchronises the device, as rvdd_set_dpc does.  RVDD_ERR_ARG and the map stays what it was: hh or ww < 3, hh * ww >= 2^31, a bit
+ * above bit 3.
+ * As a stage of rvdd_video_push: with a map set, the frames of every run of slots that got a frame are corrected in place right
+ * behind their ingest -- without rvdd_set_dpc in the ring, with rvdd_set_dpc in its scratch tensor (the gray planes in the ring)
+ * BEFORE rvdd_dpc's kernel, so that the dynamic rule sees cleaned neighbours; rvdd_set_match's map comes after both.  Every output
+ * is bit for bit rvdd_ingest_raw -> rvdd_dpc_map_apply -> (rvdd_dpc) -> flows -> rvdd_step on a handle of batch 1, under every
+ * "stream_container" and under "stream_all_frames" (copies of corrected frames).  A push of another frame size than the map's is
+ * RVDD_ERR_ARG.  With the map off -- or empty -- a push makes exactly the launches it made before, and nothing more is allocated. */
+int rvdd_set_dpc_map(rvdd_t* h, const uint8_t* cellmask /* HOST [hh,ww]; NULL = off, the default */, int32_t hh, int32_t ww);
+
+/* The handle's map applied to packed frames IN PLACE (and to their gray planes, nullable).  Only good sites are read and only
+ * defective ones written, so there is no scratch tensor and no race, and applying the map twice gives the bits of applying it
+ * once.  One thread per (frame, defective cell), the only owner of the cell's four planes and its gray value: the cost follows the
+ * number of defects, not the frame size.  An empty map, or n = 0, launches nothing.
+ * RVDD_ERR_ARG (the message names the argument), nothing launched: bit_depth outside 1..16, hh or ww < 3, n < 0, NULL packed with
+ * n > 0, a launch of more than 2^31 - 1 blocks.  RVDD_ERR_STATE: no map set, or a map of another hh x ww.  Asynchronous and
+ * stream-ordered; nothing is read back. */
+int rvdd_dpc_map_apply(rvdd_t* h, float* packed /* [n,4,hh,ww], IN PLACE */, float* gray /* [n,hh,ww], nullable, in place */,
+                       int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream);
+
 /* The sensor's noise curve var(m) = a * m - b (what rvdd_dpc_cfg's noise_a / noise_b ask for) estimated from the footage itself:
  * rvdd_noise_hist gathers block statistics of packed frames into a histogram on the device, rvdd_noise_fit fits the curve to a host
  * copy of it.  The rule, on packed [n,4,hh,ww] in [-1,1] as rvdd_ingest_raw / rvdd_ingest_bits / rvdd_dpc write it, with

@@ -36,6 +36,11 @@ class RvddDpcCfg(C.Structure):
                 ("var_floor", C.c_float)]
 
 
+class RvddDpcDetectCfg(C.Structure):
+    """struct rvdd_dpc_detect_cfg (rvdd_dpc_detect)"""
+    _fields_ = [("rule", RvddDpcCfg), ("tolerate", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RvddMatchCfg(C.Structure):
     """struct rvdd_match_cfg (rvdd_match_coeffs, rvdd_match_raw, rvdd_unmatch_rgb, rvdd_set_match)"""
     _fields_ = [("scale", C.c_float), ("offset", C.c_float)]
@@ -93,6 +98,10 @@ _PROTOS = {
     "rvdd_dpc": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddDpcCfg), _P, _P]),
     "rvdd_set_dpc": (C.c_int, [_P, C.POINTER(RvddDpcCfg)]),
     "rvdd_dpc_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), _P]),
+    "rvdd_dpc_detect": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddDpcDetectCfg), _P, _P]),
+    "rvdd_dpc_map_stats": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "rvdd_set_dpc_map": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
+    "rvdd_dpc_map_apply": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "rvdd_noise_hist": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_noise_fit": (C.c_int, [C.POINTER(RvddNoiseAcc), C.c_int32, C.POINTER(RvddNoiseCurve)]),
     "rvdd_frame_sigs": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

@@ -327,6 +327,78 @@ int rvdd_dpc(rvdd_t* h, const float* packed_in, float* packed_out, float* gray, 
     return RVDD_OK;
 }
 
+int rvdd_dpc_detect(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, const rvdd_dpc_detect_cfg* cfg,
+                    uint32_t* hits, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (!cfg) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: cfg is required");
+    DpcParams p;
+    RC(dpc_params(h, "rvdd_dpc_detect", &cfg->rule, &p));
+    if (cfg->tolerate < 0 || cfg->tolerate > 3) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: tolerate must be 0..3 (the median of eight bears three), got %d", cfg->tolerate);
+    if (cfg->reserved != 0) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: reserved must be 0, got %d", cfg->reserved);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: bit_depth must be 1..16, got %d", bit_depth);
+    if (hh < 2) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: hh must be >= 2 (the neighbours are mirrored about the site), got %d", hh);
+    if (ww < 2) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: ww must be >= 2 (the neighbours are mirrored about the site), got %d", ww);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: n must be >= 0, got %d", n);
+    if (!hits) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: hits is required");
+    if (reinterpret_cast<uintptr_t>(hits) & 3) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: hits must be 4-byte aligned (32-bit words)");
+    if (n == 0) return RVDD_OK;
+    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: packed is required");
+    if (dpc_detect_blocks(hh, ww, dpc_detect_wide(packed, hits, ww)) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: hh * ww = %d * %d needs a launch of more than 2^31 - 1 blocks", hh, ww);
+    ENTER(h);
+    HIPCHK(h, launch_dpc_detect(packed, n, hh, ww, bit_depth, p, cfg->tolerate, hits, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_dpc_map_stats(const uint8_t* cellmask, int32_t hh, int32_t ww, int64_t* out3) {
+    if (!cellmask) return fail(nullptr, RVDD_ERR_ARG, "rvdd_dpc_map_stats: cellmask is required");
+    if (!out3) return fail(nullptr, RVDD_ERR_ARG, "rvdd_dpc_map_stats: out3 is required");
+    if (hh < 3) return fail(nullptr, RVDD_ERR_ARG, "rvdd_dpc_map_stats: hh must be >= 3 (the second ring is reflected about the edge), got %d", hh);
+    if (ww < 3) return fail(nullptr, RVDD_ERR_ARG, "rvdd_dpc_map_stats: ww must be >= 3 (the second ring is reflected about the edge), got %d", ww);
+    const auto reflect = [](int i, int n) { return i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i; };
+    int64_t samples = 0, cells = 0, unfixable = 0;
+    for (int y = 0; y < hh; ++y)
+        for (int x = 0; x < ww; ++x) {
+            const unsigned bits = cellmask[(size_t)y * ww + x];
+            if (bits & 0xf0u)
+                return fail(nullptr, RVDD_ERR_ARG, "rvdd_dpc_map_stats: cellmask[%d][%d] = 0x%02x has a bit above the four planes' set", y, x, bits);
+            if (!bits) continue;
+            ++cells;
+            for (int k = 0; k < 4; ++k) {
+                if (!((bits >> k) & 1u)) continue;
+                ++samples;
+                bool good = false;      // a site of the 5 x 5 window, either ring, whose bit k is clear (the centre's is set)
+                for (int dy = -2; dy <= 2 && !good; ++dy)
+                    for (int dx = -2; dx <= 2 && !good; ++dx)
+                        good = !((cellmask[(size_t)reflect(y + dy, hh) * ww + reflect(x + dx, ww)] >> k) & 1u);
+                unfixable += !good;
+            }
+        }
+    out3[0] = samples;
+    out3[1] = cells;
+    out3[2] = unfixable;
+    return RVDD_OK;
+}
+
+int rvdd_dpc_map_apply(rvdd_t* h, float* packed, float* gray, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: bit_depth must be 1..16, got %d", bit_depth);
+    if (hh < 3) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: hh must be >= 3 (the second ring is reflected about the edge), got %d", hh);
+    if (ww < 3) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: ww must be >= 3 (the second ring is reflected about the edge), got %d", ww);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: n must be >= 0, got %d", n);
+    if (n > 0 && !packed) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: packed is required");
+    const auto& m = h->dmap;
+    if (!m.on) return fail(h, RVDD_ERR_STATE, "rvdd_dpc_map_apply: no map is set (rvdd_set_dpc_map)");
+    if (m.hh != hh || m.ww != ww)
+        return fail(h, RVDD_ERR_STATE, "rvdd_dpc_map_apply: the map is one of %d x %d cells, the frames have %d x %d", m.hh, m.ww, hh, ww);
+    if (dpc_map_blocks(n, m.ncells) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: n = %d frames of %lld defective cells need a launch of more than 2^31 - 1 blocks", n, (long long)m.ncells);
+    if (n == 0 || m.ncells == 0) return RVDD_OK;
+    ENTER(h);
+    HIPCHK(h, launch_dpc_map_apply(packed, gray, n, hh, ww, bit_depth, m.mask, m.cells, m.ncells, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 int rvdd_noise_hist(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, rvdd_noise_acc* acc, void* stream) {
     if (!h) return RVDD_ERR_ARG;
     if (!acc) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: acc is required");

@@ -241,6 +241,15 @@ struct rvdd_handle {
         std::vector<uint64_t> total;     // [B][2] since the stage was last switched on
     } dpc;
 
+    // rvdd_set_dpc_map: the static defect map rvdd_dpc_map_apply corrects by, and the stage of rvdd_video_push behind the ingest
+    struct DpcMap {
+        bool on = false;
+        int hh = 0, ww = 0;              // the map's size in cells
+        uint8_t* mask = nullptr;         // DEVICE [hh][ww]: bit k = plane k of the cell is defective (freed by rvdd_set_dpc_map / rvdd_destroy)
+        int* cells = nullptr;            // DEVICE [ncells]: the indices y * ww + x of the defective cells, ascending
+        int64_t ncells = 0;
+    } dmap;
+
     // rvdd_set_match: the ring's packed frames mapped onto the checkpoint's noise curve, out_rgb mapped back (rvdd_video_push)
     struct Match {
         bool on = false;

@@ -408,6 +408,24 @@ hipError_t launch_dpc(const float* pin, float* pout, float* gray, int n, int hh,
 bool dpc_wide(const float* pin, const float* pout, const float* gray, int ww);
 int64_t dpc_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame);
 
+// dpc_map.hip -- the static defect map: persistence counts per site (rvdd_dpc_detect) and the correction by map (rvdd_dpc_map_apply,
+// the stage of rvdd_video_push behind rvdd_set_dpc_map)
+// hits [4][hh][ww] u32 (hot frames | dead frames << 16, each half added to and saturating at 65535) of packed [n][4][hh][ww] under
+// launch_dpc's rule with the (tolerate + 1)-th largest / smallest neighbour (tolerate 0..3) in place of hi / lo; a thread owns its
+// sites across the n frames: plain load, add and store.  hh, ww >= 2; n <= 0 launches nothing.
+hipError_t launch_dpc_detect(const float* packed, int n, int hh, int ww, int bit_depth, const DpcParams& p, int tolerate, unsigned* hits,
+                             hipStream_t s);
+// whether that launch takes the wide form (a thread owns four sites of a row), and its grid; -1 = more than 2^31 - 1 blocks
+bool dpc_detect_wide(const float* packed, const unsigned* hits, int ww);
+int64_t dpc_detect_blocks(int hh, int ww, bool wide);
+// packed [n][4][hh][ww] IN PLACE, gray [n][hh][ww] (nullable) in place: the defective samples of the `ncells` cells listed in `cells`
+// (DEVICE, indices y * ww + x; mask: DEVICE [hh][ww], bit k = plane k of the cell is defective) replaced by the middle of the good
+// sites of the first ring that has one, the cells' gray values re-formed; one thread per (frame, cell).  hh, ww >= 3; no cell or no
+// frame launches nothing.
+hipError_t launch_dpc_map_apply(float* packed, float* gray, int n, int hh, int ww, int bit_depth, const uint8_t* mask, const int* cells,
+                                int64_t ncells, hipStream_t s);
+int64_t dpc_map_blocks(int n, int64_t ncells);      // the grid of that launch; -1 = more than 2^31 - 1 blocks
+
 // match.hip -- footage matched to the checkpoint's noise curve (rvdd_match_raw, rvdd_unmatch_rgb, the stage behind rvdd_set_match)
 // `count` dense floats in -> out (the same pointer, or no overlap): (scale * v) + offset, or with `inverse` (v - offset) * r with
 // r = (float)(1.0 / (double)scale) formed here; each operation rounded to f32 on its own.  scale finite and > 0, offset finite.

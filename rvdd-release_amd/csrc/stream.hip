@@ -59,6 +59,10 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         RC(dmalloc(h, reinterpret_cast<void**>(&dpc.counts), (size_t)B * 2 * sizeof(unsigned)));
         RC(dmalloc(h, reinterpret_cast<void**>(&dpc.in), (size_t)B * 4 * hw * sizeof(float)));
     }
+    // rvdd_set_dpc_map: the frames just ingested are corrected by the map in place, in front of rvdd_set_dpc's rule
+    const auto& dmap = h->dmap;
+    if (dmap.on && (dmap.hh != hh || dmap.ww != ww))
+        return fail(h, RVDD_ERR_ARG, "rvdd_video_push: the map of rvdd_set_dpc_map is one of %d x %d cells, the frames have %d x %d", dmap.hh, dmap.ww, hh, ww);
     // rvdd_set_match: the ring's packed frames are mapped in place behind the ingest (and the correction), out_rgb is mapped back
     const auto match = h->match;
     // the whole ctl is judged before anything changes
@@ -81,6 +85,8 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         else
             HIPCHK(h, launch_ingest_raw(static_cast<const char*>(frames) + (size_t)b * 4 * hw * esz, dtype, layout, e - b, hh, ww, bit_depth,
                                         packed, ring_gray, s));
+        if (dmap.on && dmap.ncells)
+            HIPCHK(h, launch_dpc_map_apply(packed, ring_gray, e - b, hh, ww, bit_depth, dmap.mask, dmap.cells, dmap.ncells, s));
         if (dpc.on) HIPCHK(h, launch_dpc(packed, ring_packed, ring_gray, e - b, hh, ww, bit_depth, dpc.p, dpc.counts + 2 * (size_t)b, s));
         // the gray planes stay the sensor's: TV-L1 matches what it always matched
         if (match.on) HIPCHK(h, launch_match(ring_packed, ring_packed, (int64_t)(e - b) * 4 * (int64_t)hw, match.cfg.scale, match.cfg.offset, false, s));
@@ -178,6 +184,45 @@ extern "C" int rvdd_set_dpc(rvdd_t* h, const rvdd_dpc_cfg* cfg) {
     }
     dpc.on = cfg != nullptr;
     if (cfg) dpc.p = p;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_set_dpc_map(rvdd_t* h, const uint8_t* cellmask, int32_t hh, int32_t ww) {
+    if (!h) return RVDD_ERR_ARG;
+    std::vector<int> cells;
+    if (cellmask) {
+        if (hh < 3) return fail(h, RVDD_ERR_ARG, "rvdd_set_dpc_map: hh must be >= 3 (the second ring is reflected about the edge), got %d", hh);
+        if (ww < 3) return fail(h, RVDD_ERR_ARG, "rvdd_set_dpc_map: ww must be >= 3 (the second ring is reflected about the edge), got %d", ww);
+        if ((int64_t)hh * ww > 0x7fffffffll) return fail(h, RVDD_ERR_ARG, "rvdd_set_dpc_map: hh * ww = %d * %d must be below 2^31 (cell indices are 32-bit)", hh, ww);
+        const size_t hw = (size_t)hh * ww;
+        for (size_t i = 0; i < hw; ++i) {
+            if (cellmask[i] & 0xf0u)
+                return fail(h, RVDD_ERR_ARG, "rvdd_set_dpc_map: cellmask[%d][%d] = 0x%02x has a bit above the four planes' set", (int)(i / ww), (int)(i % ww),
+                            cellmask[i]);
+            if (cellmask[i]) cells.push_back((int)i);
+        }
+    }
+    ENTER(h);
+    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight read the map they were enqueued with
+    auto& m = h->dmap;
+    if (m.mask) HIPCHK(h, hipFree(m.mask));
+    m.mask = nullptr;
+    if (m.cells) HIPCHK(h, hipFree(m.cells));
+    m.cells = nullptr;
+    m.on = false;
+    m.ncells = 0;
+    if (!cellmask) return RVDD_OK;
+    if (!cells.empty()) {                   // an empty map is valid and owns nothing
+        const size_t hw = (size_t)hh * ww;
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&m.mask), hw));
+        HIPCHK(h, hipMemcpy(m.mask, cellmask, hw, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&m.cells), cells.size() * sizeof(int)));
+        HIPCHK(h, hipMemcpy(m.cells, cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    m.hh = hh;
+    m.ww = ww;
+    m.ncells = (int64_t)cells.size();
+    m.on = true;
     return RVDD_OK;
 }
 

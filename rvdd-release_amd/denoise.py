@@ -48,6 +48,20 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
   --dpc_dead K        another threshold for the dead side; 0 switches that side off.
                       Prints, per video, `dpc: <hot> hot, <dead> dead samples corrected in <frames> frames`.  Without --dpc the
                       output files keep their bytes.
+  --dpc_map FILE      correct the persistent defects of the sensor by a static map (`rvdd_set_dpc_map`): a one-sample image of the mosaic,
+                      nonzero = defective (python -m rvdd_release_amd.dpc_map writes one; a camera's own calibration serves as well).
+                      Every ingested frame has the map's samples, and only those, replaced by the middle value of their good same-colour
+                      neighbours, clusters of any shape included; scene highlights are not touched.  Needs no --dpc; with --dpc the map
+                      is applied first and the dynamic rule sees cleaned neighbours.
+  --dpc_map auto      the map found in the run's own footage before streaming starts (`rvdd_dpc_detect`; python -m rvdd_release_amd.dpc_map
+                      is the same pass on its own): --dpc_map_frames K (default 16) frames spread evenly over each of up to 16 videos,
+                      a sample being defective where the rule of --dpc fired in at least --dpc_map_share (default 0.5) of them;
+                      --dpc_map_tolerate t (0..3, default 0) for clusters in flat calibration footage.
+  --dpc_static_only   with --dpc_map auto: --dpc only names the detection rule, the dynamic stage stays off.
+                      Prints `dpc_map: N samples in M cells, U unfixable, from F frames` (or `from FILE`).  Limits: a tripod shot of a
+                      static scene gives the map the dynamic rule's false alarms, since nothing moves -- no worse than --dpc; one
+                      camera (one frame size, one map) per run; NOTHING is measured on real footage.  Without the
+                      flags no new call is made and the output files keep their bytes.
   --match_noise a,b   map the footage onto the checkpoint's noise curve (`rvdd_set_match`): a,b is the footage's curve var = a * m - b in
                       DN of --bit_depth.  The kept frames are mapped by x' = s x + t with s = a_ref / a (in 12-bit DN) behind the ingest
                       and the correction of --dpc, which keeps the sensor's curve; the outputs are mapped back, so every output format
@@ -174,6 +188,48 @@ def dpc_arguments(dpc, dpc_dead, dpc_iso, dpc_noise, bit_depth, dpc_noise_frames
         if not floor > 0:
             raise SystemExit("--dpc_noise: the floor must be > 0, got %r" % floor)
     return (float(dpc), float(k_dead), a, b, floor)
+
+
+def dpc_map_arguments(dpc_map, frames, share, tolerate, static_only, have_dpc):
+    """--dpc_map / --dpc_map_frames / --dpc_map_share / --dpc_map_tolerate / --dpc_static_only -> None (no --dpc_map), ("file", path)
+    or ("auto", frames, share, tolerate); `have_dpc`: --dpc K was given.  SystemExit where the flags do not fit together."""
+    from .dpc_map import check_detect_flags
+    given = [n for n, v in (("dpc_map_frames", frames), ("dpc_map_share", share), ("dpc_map_tolerate", tolerate)) if v is not None]
+    if dpc_map is None:
+        if given or static_only:
+            raise SystemExit("--dpc_map_frames, --dpc_map_share, --dpc_map_tolerate and --dpc_static_only belong to --dpc_map auto")
+        return None
+    if dpc_map != "auto":
+        if given:
+            raise SystemExit("--%s belongs to --dpc_map auto: --dpc_map %s reads a map that is already made" % (given[0], dpc_map))
+        if static_only:
+            raise SystemExit("--dpc_static_only belongs to --dpc_map auto: with --dpc_map FILE leave --dpc away to keep the dynamic stage off")
+        return ("file", dpc_map)
+    if not have_dpc:
+        raise SystemExit("--dpc_map auto needs --dpc K with --dpc_iso ISO or --dpc_noise a,b / auto: the rule whose persistence is counted "
+                         "(--dpc_static_only keeps the dynamic stage itself off)")
+    frames, share, tolerate = 16 if frames is None else frames, 0.5 if share is None else share, 0 if tolerate is None else tolerate
+    check_detect_flags(frames, share, tolerate, "--dpc_map_")
+    return ("auto", int(frames), float(share), int(tolerate))
+
+
+def find_dpc_map(dataset, dev, opt):
+    """--dpc_map: the run's map as a cellmask uint8 [hh,ww], its `dpc_map: N samples in M cells, U unfixable, from ...` line sent to the
+    log.  auto: `dpc_map.detect` on the run's own videos with the rule of --dpc, before any push."""
+    from . import dpc_map as M
+    from .util._ops import ops_runtime
+    try:
+        if opt.dpc_map[0] == "file":
+            mask = M.read_map(opt.dpc_map[1])
+            print(M.summary_line(mask, opt.dpc_map[1]))
+            return mask
+        _, frames, share, tolerate = opt.dpc_map
+        hits, read = M.detect(ops_runtime(dev.index or 0), dataset, int(opt.bit_depth), dpc_cfg(*opt.dpc), frames, tolerate)
+        mask, _ = M.report(hits, read, share, tolerate)
+    except (RuntimeError, tiffio.TiffError, OSError) as err:
+        raise SystemExit("--dpc_map %s: %s" % (opt.dpc_map[0] if opt.dpc_map[0] == "auto" else opt.dpc_map[1], err))
+    print(M.summary_line(mask, '%d frames' % read))
+    return mask
 
 
 def match_arguments(match_noise, match_iso):
@@ -332,6 +388,12 @@ def _parse(argv):
     p.add_argument('--dpc_noise', type=str, default=None, help='a,b[,floor]: var = a * m - b in DN of the frames, the least variance; '
                    'auto[,floor]: estimated from the footage (assumes one camera setting for the whole run)')
     p.add_argument('--dpc_noise_frames', type=int, default=None, help='with --dpc_noise auto: frames read per video (default 4)')
+    p.add_argument('--dpc_map', type=str, default=None, help='FILE: correct the sites of this defect map (python -m rvdd_release_amd.dpc_map '
+                   'writes one); auto: find the map in the footage before streaming starts, with the rule of --dpc')
+    p.add_argument('--dpc_map_frames', type=int, default=None, help='with --dpc_map auto: frames read per video, spread over it (default 16)')
+    p.add_argument('--dpc_map_share', type=float, default=None, help='with --dpc_map auto: the share of those frames a defect fires in (default 0.5)')
+    p.add_argument('--dpc_map_tolerate', type=int, default=None, help='with --dpc_map auto: 0..3 other defects among the neighbours (default 0)')
+    p.add_argument('--dpc_static_only', action='store_true', help='with --dpc_map auto: --dpc only names the detection rule, the dynamic stage stays off')
     p.add_argument('--match_noise', type=str, default=None, help="a,b: the footage's curve var = a * m - b in DN of the frames, mapped onto "
                    'the curve of --match_iso; auto: estimated from the footage')
     p.add_argument('--match_iso', type=int, default=None, help="the checkpoint family's noise curve: 3200 or 12800")
@@ -347,6 +409,9 @@ def _parse(argv):
         raise SystemExit("--out_format %s needs --out_bit_depth (default: --bit_depth) 10, 12 or 14, got %d" % (opt.out_format, opt.out_bit_depth))
     opt.dpc = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth), own.dpc_noise_frames)
     opt.dpc_noise_frames = 4 if own.dpc_noise_frames is None else own.dpc_noise_frames
+    opt.dpc_map = dpc_map_arguments(own.dpc_map, own.dpc_map_frames, own.dpc_map_share, own.dpc_map_tolerate, own.dpc_static_only,
+                                    opt.dpc is not None)
+    opt.dpc_static_only = own.dpc_static_only
     opt.match = match_arguments(own.match_noise, own.match_iso)
     opt.cuts = cuts_arguments(own.cuts, own, opt.future_patch_depth)
     if opt.raw_container is not None:
@@ -387,6 +452,10 @@ def main(argv=None) -> dict:
     if opt.dpc is not None and opt.dpc[2] is None:
         curve = estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames)
         opt.dpc = opt.dpc[:2] + curve + opt.dpc[4:]
+    # --dpc_map: ONE map for the run, read or found before any push; --dpc_static_only: --dpc has named the rule and is done
+    dmap = None if opt.dpc_map is None else find_dpc_map(dataset, dev, opt)
+    if opt.dpc_static_only:
+        opt.dpc = None
     match = None
     if opt.match is not None:
         if opt.match[0] is None:
@@ -412,6 +481,11 @@ def main(argv=None) -> dict:
         rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
         rt.set_option("stream_all_frames", int(opt.all_frames))
         rt.set_dpc(None if opt.dpc is None else dpc_cfg(*opt.dpc))
+        if dmap is not None and dmap.shape != (H // 2, W // 2):
+            raise SystemExit("--dpc_map: the map is one of a %d x %d mosaic, video %r has frames of %d x %d (one camera per run)"
+                             % (2 * dmap.shape[1], 2 * dmap.shape[0], videos[0][0], W, H))
+        if dmap is not None:
+            rt.set_dpc_map(dmap)
         rt.set_match(match)
         dpc_seen = rt.dpc_counts() if opt.dpc is not None else None      # rvdd_dpc_counts at the end of the slot's last video
         dpc_frames = [0] * B                        # frames the slot's video has pushed

@@ -58,7 +58,74 @@ def dpc_cfg(k_hot: float, k_dead: float, noise_a: float, noise_b: float, var_flo
     return _lib.RvddDpcCfg(float(k_hot), float(k_dead), float(noise_a), float(noise_b), float(var_floor))
 
 
-NOISE_ACC_BYTES = C.sizeof(_lib.RvddNoiseAcc)      # struct rvdd_noise_acc: u32 hist[64][512], u64 msum[64], u64 counters[4]
+def dpc_detect_cfg(rule, tolerate: int = 0) -> "_lib.RvddDpcDetectCfg":
+    """struct rvdd_dpc_detect_cfg: `rule` = `dpc_cfg(...)`, tolerate 0..3 (the library checks the range)"""
+    return _lib.RvddDpcDetectCfg(rule, int(tolerate), 0)
+
+
+def dpc_map_from_hits(hits, frames: int, share: float = 0.5):
+    """The map of persistence counts: hits = what `RvddRuntime.dpc_detect` accumulated over `frames` frames (a tensor or array of
+    32-bit words [4,hh,ww]: hot frames in the low 16 bits, dead frames in the high 16).  A sample is defective iff it was hot, or
+    dead, in at least ceil(share * frames) of them.  -> (cellmask uint8 [hh,ww] with bit k = plane k, hot bool [4,hh,ww], dead bool
+    [4,hh,ww]), NumPy arrays on the host (a device tensor is copied, which synchronises)."""
+    import math
+    import numpy as np
+    if torch.is_tensor(hits):
+        hits = hits.detach().cpu().contiguous().numpy()
+    w = np.ascontiguousarray(hits).view(np.uint32)
+    if w.ndim != 3 or w.shape[0] != 4:
+        raise RuntimeError(f"dpc_map_from_hits: hits is [4,hh,ww] 32-bit words, got {w.shape}")
+    if int(frames) < 1 or not 0.0 < float(share) <= 1.0:
+        raise ValueError(f"dpc_map_from_hits: frames >= 1 and 0 < share <= 1, got frames = {frames}, share = {share}")
+    need = max(1, math.ceil(float(share) * int(frames)))
+    hot, dead = (w & 0xffff) >= need, (w >> 16) >= need
+    bad = hot | dead
+    mask = np.zeros(w.shape[1:], np.uint8)
+    for k in range(4):
+        mask |= bad[k].astype(np.uint8) << k
+    return mask, hot, dead
+
+
+def dpc_map_to_mosaic(cellmask):
+    """cellmask uint8 [hh,ww] -> the file form: uint8 [2hh,2ww], sample (2y + (k >> 1), 2x + (k & 1)) = 255 where bit k is set, else 0"""
+    import numpy as np
+    m = np.asarray(cellmask)
+    if m.ndim != 2 or m.dtype != np.uint8 or (m & 0xf0).any():
+        raise RuntimeError("dpc_map_to_mosaic: cellmask is uint8 [hh,ww] with bits 0..3 only")
+    out = np.zeros((2 * m.shape[0], 2 * m.shape[1]), np.uint8)
+    for k in range(4):
+        out[k >> 1::2, k & 1::2] = ((m >> k) & 1) * 255
+    return out
+
+
+def dpc_map_from_mosaic(plane):
+    """The file form back: a one-sample image of the mosaic [2hh,2ww] (any integer or bool type, nonzero = defective) -> cellmask"""
+    import numpy as np
+    p = np.asarray(plane)
+    if p.ndim != 2 or p.shape[0] % 2 or p.shape[1] % 2 or p.shape[0] < 2 or p.shape[1] < 2:
+        raise RuntimeError(f"dpc_map_from_mosaic: a map is a one-sample image of the mosaic [2hh,2ww], got {p.shape}")
+    m = np.zeros((p.shape[0] // 2, p.shape[1] // 2), np.uint8)
+    for k in range(4):
+        m |= (p[k >> 1::2, k & 1::2] != 0).astype(np.uint8) << k
+    return m
+
+
+def dpc_map_stats(cellmask) -> Dict[str, int]:
+    """{"samples", "cells", "unfixable"} of a map uint8 [hh,ww] (rvdd_dpc_map_stats: on the host, no GPU needed): its defective
+    samples and cells, and the samples no ring of which has a good site -- `dpc_map_apply` leaves those as they are."""
+    import numpy as np
+    lib = _lib.load()
+    m = np.ascontiguousarray(cellmask)
+    if m.ndim != 2 or m.dtype != np.uint8:
+        raise RuntimeError(f"dpc_map_stats: cellmask is uint8 [hh,ww], got {m.dtype} {m.shape}")
+    out = (C.c_int64 * 3)()
+    rc = lib.rvdd_dpc_map_stats(m.ctypes.data, m.shape[0], m.shape[1], out)
+    if rc != 0:
+        raise RuntimeError(f"rvdd_dpc_map_stats failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    return {"samples": int(out[0]), "cells": int(out[1]), "unfixable": int(out[2])}
+
+
+NOISE_ACC_BYTES = C.sizeof(_lib.RvddNoiseAcc)     # struct rvdd_noise_acc: u32 hist[64][512], u64 msum[64], u64 counters[4]
 
 
 def noise_acc_arrays(acc):
@@ -554,6 +621,52 @@ class RvddRuntime:
         self._check(self.lib.rvdd_dpc(self.h, _ptr(packed), _ptr(out), _ptr(gray), n, hh, ww, int(bit_depth), C.byref(cfg), _ptr(counts),
                                       self._stream()), "rvdd_dpc")
         return out
+
+    # -- the static defect map -----------------------------------------------------------
+    def dpc_detect(self, packed: torch.Tensor, cfg, bit_depth: int = 12, hits: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The hot and dead frames of every site of packed frames [n,4,hh,ww] added to `hits` (rvdd_dpc_detect; cfg:
+        `dpc_detect_cfg(dpc_cfg(...), tolerate)`): a device int32 tensor [4,hh,ww] -- None = a new zeroed one -- which is returned;
+        hot frames in the low 16 bits, dead frames in the high 16, each saturating at 65535.  Accumulate any number of calls, then
+        `dpc_map_from_hits(hits, frames, share)`.  Nothing is synchronised."""
+        if not torch.is_tensor(packed) or packed.dim() != 4 or packed.shape[1] != 4:
+            raise RuntimeError(f"dpc_detect: packed is [n,4,hh,ww], got {tuple(getattr(packed, 'shape', ()))}")
+        n, _, hh, ww = packed.shape
+        packed = _chk_dev(packed, packed.shape, "packed", self.device)
+        if hits is None:
+            hits = torch.zeros(4, hh, ww, dtype=torch.int32, device=self._tdev)
+        elif not torch.is_tensor(hits) or not hits.is_cuda or hits.device.index != self.device or not hits.is_contiguous() \
+                or hits.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(hits.shape) != (4, hh, ww):
+            raise RuntimeError(f"dpc_detect: hits is a contiguous int32 / uint32 tensor [4,{hh},{ww}] on cuda:{self.device}")
+        self._check(self.lib.rvdd_dpc_detect(self.h, _ptr(packed), n, hh, ww, int(bit_depth), C.byref(cfg), _ptr(hits), self._stream()),
+                    "rvdd_dpc_detect")
+        return hits
+
+    def set_dpc_map(self, cellmask=None):
+        """The handle's defect map (rvdd_set_dpc_map): cellmask uint8 [hh,ww] on the host (a NumPy array or CPU tensor; bit k = plane k
+        of the cell is defective), None = off (the default).  `dpc_map_apply` corrects by it, and `video_push` corrects every
+        ingested frame by it, in front of `set_dpc`'s rule.  Synchronises the device."""
+        if cellmask is None:
+            self._check(self.lib.rvdd_set_dpc_map(self.h, None, 0, 0), "rvdd_set_dpc_map")
+            return
+        import numpy as np
+        m = np.ascontiguousarray(cellmask.cpu().numpy() if torch.is_tensor(cellmask) else cellmask)
+        if m.ndim != 2 or m.dtype != np.uint8:
+            raise RuntimeError(f"set_dpc_map: cellmask is uint8 [hh,ww], got {m.dtype} {m.shape}")
+        self._check(self.lib.rvdd_set_dpc_map(self.h, m.ctypes.data, m.shape[0], m.shape[1]), "rvdd_set_dpc_map")
+
+    def dpc_map_apply(self, packed: torch.Tensor, bit_depth: int = 12, gray: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Packed frames [n,4,hh,ww] corrected by the handle's map IN PLACE (rvdd_dpc_map_apply), gray [n,hh,ww] re-formed at the
+        map's cells.  -> packed.  Both must be contiguous: they are written where they lie.  Nothing is synchronised."""
+        if not torch.is_tensor(packed) or packed.dim() != 4 or packed.shape[1] != 4:
+            raise RuntimeError(f"dpc_map_apply: packed is [n,4,hh,ww], got {tuple(getattr(packed, 'shape', ()))}")
+        n, _, hh, ww = packed.shape
+        if _chk_dev(packed, packed.shape, "packed", self.device) is not packed:
+            raise RuntimeError("dpc_map_apply: packed must be contiguous (it is corrected in place)")
+        if gray is not None and _chk_dev(gray, (n, hh, ww), "gray", self.device) is not gray:
+            raise RuntimeError("dpc_map_apply: gray must be contiguous (it is patched in place)")
+        self._check(self.lib.rvdd_dpc_map_apply(self.h, _ptr(packed), _ptr(gray), n, hh, ww, int(bit_depth), self._stream()),
+                    "rvdd_dpc_map_apply")
+        return packed
 
     # -- the noise curve from the footage ---------------------------------------------
     def noise_hist(self, packed: torch.Tensor, bit_depth: int = 12, acc: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -1,0 +1,408 @@
+"""The static defect map on the device: rvdd_dpc_detect and rvdd_dpc_map_apply against their NumPy restatements
+(tests/dpc_map_ref.py) bit for bit, the identities the header promises (tolerate 0 is rvdd_dpc's decision, the split of the frames
+over calls does not matter, applying twice is applying once), the argument errors, and the stage inside rvdd_video_push
+(rvdd_set_dpc_map) against the same schedule made by hand from the stand-alone entry points, and `python -m rvdd_release_amd.dpc_map` /
+`denoise --dpc_map` end to end on a small tree.  Every comparison is exact."""
+import ctypes as C
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import dpc_map_ref as M
+import dpc_ref as R
+from stream_ref import to_gpu
+from test_gpu_dpc import H, W, _bits, _cfg, _offset, _push_all, _rt, _runtime, _same, _videos
+
+pytestmark = pytest.mark.gpu
+
+DETECT_SHAPES = [(1, 2, 2), (1, 3, 5), (3, 16, 20), (2, 18, 17), (1, 16, 24)]
+APPLY_SHAPES = [(1, 3, 3), (1, 3, 5), (3, 16, 20), (2, 18, 17), (1, 16, 24)]
+
+
+def _dcfg(k_hot, k_dead, a, b, tolerate, floor=1.0):
+    from rvdd_release_amd.runtime import dpc_detect_cfg
+    return dpc_detect_cfg(_cfg(k_hot, k_dead, a, b, floor), tolerate)
+
+
+def _hits0(hh, ww, seed):
+    """counts that do not start at zero, some of them a few frames below saturation in either half"""
+    rng = np.random.default_rng(seed)
+    h = (rng.integers(0, 9, (4, hh, ww)) | rng.integers(0, 9, (4, hh, ww)) << 16).astype(np.uint32)
+    h[0, 0, 0] = 65534 | (65535 << 16)
+    h[1, 0, ww - 1] = 2 | (65534 << 16)
+    return h
+
+
+def _up(a, offset=False):
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint32:
+        a = a.view(np.int32)
+    return _offset(a) if offset else torch.from_numpy(a).cuda()
+
+
+# ---- 1. detection -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,hh,ww", DETECT_SHAPES, ids=["%dx%dx%d" % s for s in DETECT_SHAPES])
+def test_detect_is_the_restatement(n, hh, ww):
+    rt = _rt()
+    for bits in (10, 12, 14, 16):
+        packed, _, sites, _ = M.make_static_case(n, hh, ww, bits, 3200, seed=7 * bits + hh)
+        a, b = R.iso_curve(3200, bits)
+        start = _hits0(hh, ww, bits)
+        dev = _up(packed)
+        for t in range(4):
+            want, hot, dead = M.detect_ref(packed, bits, 4, 4, a, b, 1.0, t, hits=start)
+            what = (n, hh, ww, bits, t)
+            if t == 0 and hh >= 3:                                # a parity test on frames where nothing fires proves nothing
+                assert hot.any() and dead.any(), what
+            assert want[0, 0, 0] == 65535 | (65535 << 16), what   # the corner is hot in every frame, and its count was one below the top
+            got = rt.dpc_detect(dev, _dcfg(4, 4, a, b, t), bits, _up(start))
+            assert np.array_equal(_bits(got), want), (what, int((_bits(got) != want).sum()))
+            if (hh, ww) == (16, 24):
+                # every pointer 4 bytes off a 16-byte boundary: the one-site form on a shape the wide form takes -- the same integers
+                off = rt.dpc_detect(_up(packed, True), _dcfg(4, 4, a, b, t), bits, _up(start, True))
+                assert np.array_equal(_bits(off), want), what
+        assert np.array_equal(_bits(dev), packed.view(np.uint32))
+
+
+def test_detect_batch_is_its_frames_one_call_at_a_time():
+    rt = _rt()
+    n, hh, ww = 3, 16, 20
+    packed, _, _, _ = M.make_static_case(n, hh, ww, 12, 3200, seed=5)
+    a, b = R.iso_curve(3200, 12)
+    dev = _up(packed)
+    for t in (0, 2):
+        whole = rt.dpc_detect(dev, _dcfg(4, 4, a, b, t), 12)
+        parts = None
+        for i in (2, 0, 1):                                       # any order: the totals are sums
+            parts = rt.dpc_detect(dev[i:i + 1], _dcfg(4, 4, a, b, t), 12, parts)
+        assert torch.equal(whole, parts) and int(whole.sum()) > 0
+
+
+@pytest.mark.parametrize("n,hh,ww", [(3, 16, 20), (2, 18, 17), (1, 16, 24)])
+def test_tolerate_0_is_rvdd_dpc(n, hh, ww):
+    """the sums of the low and high halves are the `counts` of rvdd_dpc on the same frames, and the sites are the ones it changes"""
+    rt = _rt()
+    packed, _, _, _ = M.make_static_case(n, hh, ww, 12, 3200, seed=3)
+    a, b = R.iso_curve(3200, 12)
+    dev = _up(packed)
+    counts = torch.zeros(n, 2, dtype=torch.int32, device="cuda")
+    out = rt.dpc(dev, _cfg(4, 4, a, b), 12, counts=counts)
+    hits = _bits(rt.dpc_detect(dev, _dcfg(4, 4, a, b, 0), 12))
+    c = counts.cpu().numpy()
+    assert int((hits & 0xffff).sum()) == int(c[:, 0].sum()) > 0 and int((hits >> 16).sum()) == int(c[:, 1].sum()) > 0
+    changed = (_bits(out) != packed.view(np.uint32)).sum(axis=0)
+    assert np.array_equal(changed, (hits & 0xffff) + (hits >> 16))
+
+
+# ---- 2. correction ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,hh,ww", APPLY_SHAPES, ids=["%dx%dx%d" % s for s in APPLY_SHAPES])
+def test_apply_is_the_restatement(n, hh, ww):
+    rt = _rt()
+    for bits in (10, 12, 14, 16):
+        packed, gray, sites, mask = M.make_static_case(n, hh, ww, bits, 3200, seed=11 * bits + ww)
+        want_p, want_g, kinds = M.apply_ref(packed, gray, mask, bits)
+        what = (n, hh, ww, bits)
+        # every class of site is in the case: a full first ring, a first ring with bad sites in it, the second ring, unfixable
+        rings = {r for r, q in kinds.values()}
+        assert rings == {0, 1, 2}, (what, rings)
+        assert any(r == 1 and q < 8 for r, q in kinds.values()), what
+        if hh >= 16:
+            assert any(r == 1 and q == 8 for r, q in kinds.values()) and any(r == 2 and q < 16 for r, q in kinds.values()), what
+            assert {s[0] for s in sites} == {"corner", "edge", "pair", "triple", "block2", "block5"}
+        bad = np.broadcast_to(M.planes_of(mask), packed.shape)
+        # ... and every fixable one changes its sample in every frame (a defect is 0 or the top, the replacement a noisy mid-grey)
+        assert (want_p.view(np.uint32) != packed.view(np.uint32))[bad].sum() == n * sum(r != 0 for r, _ in kinds.values()), what
+        rt.set_dpc_map(mask)
+        p, g = _up(packed), _up(gray)
+        assert rt.dpc_map_apply(p, bits, gray=g) is p
+        assert np.array_equal(_bits(p), want_p.view(np.uint32)), (what, int((_bits(p) != want_p.view(np.uint32)).sum()))
+        assert np.array_equal(_bits(g), want_g.view(np.uint32)), what
+        # nothing outside the map changes its bits; the unfixable samples keep theirs
+        assert np.array_equal(_bits(p)[~bad], packed.view(np.uint32)[~bad])
+        assert np.array_equal(_bits(g)[:, mask == 0], gray.view(np.uint32)[:, mask == 0])
+        for (k, y, x), (r, q) in kinds.items():
+            if r == 0:
+                assert np.array_equal(_bits(p)[:, k, y, x], packed.view(np.uint32)[:, k, y, x]), (what, k, y, x)
+        # applying twice is applying once
+        rt.dpc_map_apply(p, bits, gray=g)
+        assert np.array_equal(_bits(p), want_p.view(np.uint32)) and np.array_equal(_bits(g), want_g.view(np.uint32)), what
+        # gray is optional
+        p2 = _up(packed)
+        rt.dpc_map_apply(p2, bits)
+        assert np.array_equal(_bits(p2), want_p.view(np.uint32)), what
+    rt.set_dpc_map(None)
+
+
+def test_empty_map_and_empty_batch():
+    rt = _rt()
+    n, hh, ww = 2, 18, 17
+    packed, gray, _, mask = M.make_static_case(n, hh, ww, 12, 3200, seed=1)
+    p, g = _up(packed), _up(gray)
+    rt.set_dpc_map(np.zeros((hh, ww), np.uint8))                  # valid, launches nothing
+    rt.dpc_map_apply(p, 12, gray=g)
+    assert np.array_equal(_bits(p), packed.view(np.uint32)) and np.array_equal(_bits(g), gray.view(np.uint32))
+    rt.set_dpc_map(mask)
+    rt.dpc_map_apply(p[:0], 12, gray=g[:0])
+    assert rt.lib.rvdd_dpc_map_apply(rt.h, None, None, 0, hh, ww, 12, None) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(_bits(p), packed.view(np.uint32)) and np.array_equal(_bits(g), gray.view(np.uint32))
+    hits = torch.full((4, hh, ww), 7, dtype=torch.int32, device="cuda")
+    a, b = R.iso_curve(3200, 12)
+    rt.dpc_detect(p[:0], _dcfg(4, 4, a, b, 0), 12, hits)
+    assert (hits == 7).all()
+    rt.set_dpc_map(None)
+
+
+# ---- 3. argument errors -----------------------------------------------------------------------------------------------------
+def test_argument_errors_launch_nothing():
+    from rvdd_release_amd import _lib
+    rt = _rt()
+    n, hh, ww = 1, 16, 20
+    p = torch.full((n, 4, hh, ww), 0.25, device="cuda")
+    gray = torch.full((n, hh, ww), 7.0, device="cuda")
+    hits = torch.full((4, hh, ww), 7, dtype=torch.int32, device="cuda")
+    a, b = R.iso_curve(3200, 12)
+    good = dict(k_hot=4.0, k_dead=4.0, noise_a=a, noise_b=b, var_floor=1.0)
+    nan, inf = float("nan"), float("inf")
+
+    def detect(packed=p.data_ptr(), n_=n, hh_=hh, ww_=ww, bits=12, rule=good, tolerate=0, reserved=0, cfg=True, hits_=hits.data_ptr()):
+        c = None
+        if cfg:
+            c = C.byref(_lib.RvddDpcDetectCfg(_lib.RvddDpcCfg(*(float(rule[f]) for f, _ in _lib.RvddDpcCfg._fields_)), tolerate, reserved))
+        rc = rt.lib.rvdd_dpc_detect(rt.h, packed, n_, hh_, ww_, bits, c, hits_, None)
+        return rc, rt.lib.rvdd_last_error(rt.h).decode()
+
+    bad = [(dict(tolerate=4), "tolerate"), (dict(tolerate=-1), "tolerate"), (dict(reserved=1), "reserved"), (dict(hits_=None), "hits"),
+           (dict(cfg=False), "cfg"), (dict(hh_=1), "hh"), (dict(ww_=1), "ww"), (dict(bits=0), "bit_depth"), (dict(bits=17), "bit_depth"),
+           (dict(n_=-1), r"\bn\b"), (dict(packed=None), "packed"), (dict(hh_=2 ** 31 - 1, ww_=2 ** 31 - 1), "blocks")]
+    for field, values in (("k_hot", (-1.0, nan, inf)), ("k_dead", (-0.5, nan)), ("noise_a", (nan, inf)), ("noise_b", (nan, -inf)),
+                          ("var_floor", (0.0, nan))):
+        bad += [(dict(rule=dict(good, **{field: v})), field) for v in values]
+    for kwargs, name in bad:
+        rc, msg = detect(**kwargs)
+        assert rc == -1 and msg.startswith("rvdd_dpc_detect:") and re.search(name, msg), (kwargs, rc, msg)
+    assert detect(n_=0)[0] == 0
+    torch.cuda.synchronize()
+    assert (hits == 7).all() and (p == 0.25).all()
+
+    def apply(packed=p.data_ptr(), n_=n, hh_=hh, ww_=ww, bits=12):
+        rc = rt.lib.rvdd_dpc_map_apply(rt.h, packed, gray.data_ptr(), n_, hh_, ww_, bits, None)
+        return rc, rt.lib.rvdd_last_error(rt.h).decode()
+
+    def set_map(m, hh_, ww_):
+        rc = rt.lib.rvdd_set_dpc_map(rt.h, m.ctypes.data, hh_, ww_)
+        return rc, rt.lib.rvdd_last_error(rt.h).decode()
+
+    rt.set_dpc_map(None)
+    rc, msg = apply()
+    assert rc == -2 and msg.startswith("rvdd_dpc_map_apply:") and "no map" in msg      # RVDD_ERR_STATE
+    mask = np.zeros((hh, ww), np.uint8)
+    mask[3, 4] = 0b0110
+    rt.set_dpc_map(mask)
+    for kwargs, name in ((dict(bits=0), "bit_depth"), (dict(bits=17), "bit_depth"), (dict(hh_=2), "hh"), (dict(ww_=2), "ww"), (dict(n_=-1), r"\bn\b"),
+                         (dict(packed=None), "packed")):
+        rc, msg = apply(**kwargs)
+        assert rc == -1 and msg.startswith("rvdd_dpc_map_apply:") and re.search(name, msg), (kwargs, rc, msg)
+    for kwargs in (dict(hh_=hh + 1), dict(ww_=ww - 4), dict(hh_=ww, ww_=hh)):
+        rc, msg = apply(**kwargs)
+        assert rc == -2 and msg.startswith("rvdd_dpc_map_apply:") and "%d x %d" % (hh, ww) in msg, (kwargs, rc, msg)
+    # a refused rvdd_set_dpc_map leaves the map what it was
+    for m, hh_, ww_, name in ((mask, 2, ww, "hh"), (mask, hh, 2, "ww"), (np.full((hh, ww), 16, np.uint8), hh, ww, "bit")):
+        rc, msg = set_map(m, hh_, ww_)
+        assert rc == -1 and msg.startswith("rvdd_set_dpc_map:") and name in msg, (name, rc, msg)
+    torch.cuda.synchronize()
+    assert (p == 0.25).all() and (gray == 7).all()
+    assert apply()[0] == 0                                        # the map of before is still set: its cell is corrected
+    torch.cuda.synchronize()
+    assert (gray[0, 3, 4] != 7) and int((gray != 7).sum()) == 1
+    rt.set_dpc_map(None)
+    with pytest.raises(RuntimeError, match="dpc_map_apply: packed is"):
+        rt.dpc_map_apply(torch.zeros(1, 3, 4, 4, device="cuda"))
+    with pytest.raises(RuntimeError, match="set_dpc_map: cellmask is uint8"):
+        rt.set_dpc_map(np.zeros((4, 4), np.int32))
+
+
+# ---- 4. the stage inside the stream -----------------------------------------------------------------------------------------
+STATIC = [(0, 0, 0, "hot"), (1, 3, 4, "hot"), (2, 10, 2, "dead"), (0, 6, 6, "hot"), (0, 6, 7, "hot"), (3, 15, 15, "dead"), (3, 0, 9, "hot")]
+
+
+def _static_videos(bits=12):
+    """test_gpu_dpc's three videos without its moving defects, with the same static defects in every frame of every video: singles in
+    every plane, at a corner and on an edge, and an equal hot pair.  -> (videos, cellmask [16,16])"""
+    videos = _videos(bits=bits, defects=False)
+    mask = np.zeros((H // 2, W // 2), np.uint8)
+    for k, y, x, kind in STATIC:
+        mask[y, x] |= 1 << k
+        for m in videos:
+            m[:, 2 * y + (k >> 1), 2 * x + (k & 1)] = 2 ** bits - 1 if kind == "hot" else 0
+    return videos, mask
+
+
+def _compose(rt, video, future, all_frames, bits=12, dpc=None, match=None):
+    """The outputs of one video by hand on a batch-1 handle that HAS the map and no stage: rvdd_ingest_raw -> rvdd_dpc_map_apply
+    (packed and gray in place) -> (rvdd_dpc) -> (rvdd_match_raw) -> rvdd_tvl1flow_batch on the gray planes -> reset at c <= 1 -> step
+    (-> rvdd_unmatch_rgb); heads and tails of "stream_all_frames" as tests/test_gpu_dpc.py composes them."""
+    N = video.shape[0]
+    pg = []
+    for t in range(N):
+        p, g = rt.ingest_raw(to_gpu(video[t:t + 1]), bits, "mosaic")
+        rt.dpc_map_apply(p, bits, gray=g)
+        if dpc is not None:
+            p = rt.dpc(p, dpc, bits, gray=g)
+        if match is not None:
+            p = rt.match_raw(p, match)
+        pg.append((p, g))
+    zeros = torch.zeros(1, 2, H // 2, W // 2, device="cuda")
+    outs = []
+    for c in (range(N) if all_frames else range(1, N - future)):
+        head, tail = c == 0, bool(future) and c == N - 1
+        prev = pg[c] if head else pg[c - 1]
+        nxt = (pg[c] if tail else pg[c + 1]) if future else None
+        fp = zeros if head else rt.tvl1flow_batch(pg[c][1], pg[c - 1][1])
+        fn = (zeros if tail else rt.tvl1flow_batch(pg[c][1], pg[c + 1][1])) if future else None
+        if c <= 1:
+            rt.reset()
+        out = rt.step(prev[0], pg[c][0], nxt[0] if future else None, fp, fn)
+        outs.append(rt.unmatch_rgb(out, match) if match is not None else out.clone())
+    return outs
+
+
+@pytest.mark.parametrize("future,all_frames,stage", [(0, 0, "map"), (1, 1, "map+dpc"), (0, 1, "map+match")])
+def test_stream_with_the_map_is_the_composition(future, all_frames, stage):
+    from rvdd_release_amd.runtime import match_cfg
+    videos, mask = _static_videos()
+    a, b = R.iso_curve(3200, 12)
+    dpc = _cfg(4, 4, a, b) if stage == "map+dpc" else None
+    match = match_cfg(0.75, -0.125) if stage == "map+match" else None
+    rt = _runtime(future, 2, stream_all_frames=all_frames)
+    rt.set_dpc_map(mask)
+    rt.set_dpc(dpc)
+    rt.set_match(match)
+    got = _push_all(rt, videos)
+    alone = _runtime(future, 1)
+    alone.set_dpc_map(mask)
+    want = [_compose(alone, v, future, all_frames, dpc=dpc, match=match) for v in videos]
+    _same(got[0], want[0] + want[2], "slot 0")
+    _same(got[1], want[1], "slot 1")
+    if dpc is not None:
+        # the dynamic rule saw cleaned neighbours: behind the map the static hot samples are gone, it has nothing of theirs to count
+        plain = _runtime(future, 2, stream_all_frames=all_frames)
+        plain.set_dpc(dpc)
+        _push_all(plain, videos)
+        assert sum(h for h, _ in rt.dpc_counts()) < sum(h for h, _ in plain.dpc_counts())
+    # the map matters on these frames; switched off again, the outputs are those of a handle that never had one
+    rt.set_dpc_map(None)
+    off = _push_all(rt, videos)
+    assert not torch.equal(off[0][0], got[0][0])
+    never = _runtime(future, 2, stream_all_frames=all_frames)
+    never.set_dpc(dpc)
+    never.set_match(match)
+    plain = _push_all(never, videos)
+    for s in range(2):
+        _same(off[s], plain[s], "off, slot %d" % s)
+
+
+def test_map_on_mipi_raw10_is_the_map_on_the_unpacked_frames():
+    videos, mask = _static_videos(bits=10)
+    plain = _runtime(1, 2, stream_all_frames=1)
+    plain.set_dpc_map(mask)
+    want = _push_all(plain, videos, bits=10)
+    mipi = _runtime(1, 2, stream_all_frames=1)
+    mipi.set_dpc_map(mask)
+    got = _push_all(mipi, videos, bits=10, container="mipi")
+    alone = _runtime(1, 1)
+    alone.set_dpc_map(mask)
+    by_hand = [_compose(alone, v, 1, 1, bits=10) for v in videos]
+    for s in range(2):
+        _same(got[s], want[s], s)
+    _same(got[0], by_hand[0] + by_hand[2], "slot 0 by hand")
+
+
+def test_push_of_another_frame_size_than_the_maps_is_refused():
+    videos, mask = _static_videos()
+    rt = _runtime(0, 2)
+    rt.set_dpc_map(np.zeros((H // 2 + 1, W // 2), np.uint8))
+    with pytest.raises(RuntimeError, match=r"rvdd_video_push failed \(-1\).*rvdd_set_dpc_map"):
+        rt.video_push(to_gpu(np.zeros((2, H, W), np.uint16)), [1, 1], 12, "mosaic")
+    rt.set_dpc_map(mask)
+    rt.video_push(to_gpu(np.zeros((2, H, W), np.uint16)), [1, 1], 12, "mosaic")
+    torch.cuda.synchronize()
+
+
+# ---- 5. the command lines ---------------------------------------------------------------------------------------------------
+T, Hc, Wc = 8, 32, 48
+TREE_SITES = [(0, 0, 0, "hot"), (1, 5, 7, "hot"), (2, 20, 30, "dead"), (3, 31, 47, "hot"), (0, 12, 40, "dead"), (3, 16, 0, "hot")]
+
+
+@pytest.fixture(scope="module")
+def tree(tmp_path_factory):
+    """2 videos of 8 frames of 32 x 48 cells: dpc_map_ref's speckled texture moving (3, 2) cells per frame under the noise of ISO 3200,
+    uint16 TIFFs, with the same static hot and dead samples in every frame of both.  -> (root, the cells of both videos, the sites' map)"""
+    from rvdd_release_amd import tiffio
+    from stream_ref import mosaic_of
+    root = tmp_path_factory.mktemp("dpc_map_tree")
+    mask = np.zeros((Hc, Wc), np.uint8)
+    cells = []
+    for v in range(2):
+        c = M.speckle_frames(T, Hc, Wc, 12, 3200, seed=60 + v)
+        for k, y, x, kind in TREE_SITES:
+            c[:, y, x, k] = 4095 if kind == "hot" else 0
+            mask[y, x] |= 1 << k
+        cells.append(c)
+        m = mosaic_of(c).astype(np.uint16)
+        os.makedirs(root / "u16" / ("%03d" % v))
+        for t in range(T):
+            tiffio.write(str(root / "u16" / ("%03d/%08d.tif" % (v, t))), m[t])
+    return root, cells, mask
+
+
+def test_map_command_is_the_restatement_and_denoise_takes_its_file(tree, tmp_path, capsys):
+    from conftest import WEIGHTS
+    from rvdd_release_amd import denoise, dpc_map
+    from test_gpu_match import _files
+    root, cells, truth = tree
+    a, b = R.iso_curve(3200, 12)
+    path = str(tmp_path / "map.tif")
+    capsys.readouterr()
+    rule = ["--dpc", "4", "--dpc_iso", "3200"]
+    r = dpc_map.main(["--dataroot", str(root), "--nFolder", "u16", "--bit_depth", "12", "--frames", str(T), "--out", path] + rule)
+    line = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(line) == 1 and json.loads(line[0]) == r
+    # the restatement on the same frames: every frame of both videos, one total
+    hits = None
+    for c in cells:
+        hits = M.detect_ref(R.ingest(c, 12)[0], 12, 4, 4, a, b, 1.0, 0, hits=hits)[0]
+    want, hot, dead = M.map_from_hits(hits, 2 * T, 0.5)
+    got = dpc_map.read_map(path)
+    assert np.array_equal(got, want)
+    assert (got & truth == truth).all() and int(M.planes_of(got & ~truth).sum()) <= 2       # every injected site; the moving texture leaves next to nothing
+    s = M.stats_ref(got)
+    assert r == {"frames": 2 * T, "share": 0.5, "tolerate": 0, "samples": s[0], "hot": int(hot.sum()), "dead": int(dead.sum()), "cells": s[1],
+                 "planes": [int(((got >> k) & 1).sum()) for k in range(4)], "unfixable": s[2]}
+    flags = ["--netDenoiser", "convunet-mode=fixedfeatures+feat", "--path2epoch", os.path.join(WEIGHTS, "recurrent-convunet+feat-iso3200"),
+             "--feature_rec", "--bit_depth", "12", "--dataroot", str(root), "--nFolder", "u16"]
+
+    def run(name, *more):
+        capsys.readouterr()
+        res = str(tmp_path / name)
+        stats = denoise.main(flags + ["--results_dir", res] + list(more))
+        out = capsys.readouterr().out.splitlines()
+        assert stats["frames"] == 2 * (T - 1)
+        return _files(res), [ln for ln in out if ln.startswith("dpc_map: ")], [ln for ln in out if ln.startswith("dpc: ")]
+
+    told = "dpc_map: %d samples in %d cells, %d unfixable, from " % s
+    by_file, line, dyn = run("file", "--dpc_map", path, "--batch_size", "2")
+    assert line == [told + path] and dyn == []
+    auto, line, dyn = run("auto", "--dpc_map", "auto", "--dpc_map_frames", str(T), "--dpc_static_only", "--batch_size", "1", *rule)
+    assert line == [told + "%d frames" % (2 * T)] and dyn == [] and auto == by_file
+    plain, line, dyn = run("plain", "--batch_size", "2")
+    assert line == [] and sorted(plain) == sorted(by_file) and plain != by_file
+    both, line, dyn = run("both", "--dpc_map", "auto", "--dpc_map_frames", str(T), "--batch_size", "2", *rule)
+    assert line == [told + "%d frames" % (2 * T)] and len(dyn) == 2 and both != by_file      # the dynamic stage runs as well
+    dpc_map.write_map(path, np.zeros((Hc + 1, Wc), np.uint8))
+    with pytest.raises(SystemExit, match="one camera per run"):
+        denoise.main(flags + ["--results_dir", str(tmp_path / "bad"), "--dpc_map", path])
