@@ -15,30 +15,9 @@
 // stores one 16-B vector per plane; the one-cell form (NC = 1) serves every other shape.  Both run the same arithmetic per sample:
 // same bits.  No LDS: a workgroup is ONE wave, so the reduction of the flag counts inside the wave is the workgroup's, and lane 0
 // adds them to the frame's two counters with one atomic each (none where the count is zero).  A workgroup lies inside one frame.
-#include "rvdd_internal.h"
+#include "dpc_rule.h"
 
 namespace {
-
-__device__ __forceinline__ float dpc_dn_of(float v, float top) { return ((v + 1.0f) * 0.5f) * top; }         // ingest.hip dn_of
-__device__ __forceinline__ float dpc_norm_dn(float dn, float maxv) { return 2.0f * __fdiv_rn(dn, maxv) - 1.0f; }      // ingest.hip norm_dn
-
-__device__ __forceinline__ void cex(float& a, float& b) {
-    const float lo = fminf(a, b), hi = fmaxf(a, b);
-    a = lo;
-    b = hi;
-}
-
-// the eight neighbours in any order -> smallest, 4th, 5th, largest: the 19 compare-exchanges of the optimal 8-input sorting network;
-// the last layer's two exchanges nobody reads fall away
-__device__ __forceinline__ void order8(float v[8], float& lo, float& s3, float& s4, float& hi) {
-    cex(v[0], v[2]); cex(v[1], v[3]); cex(v[4], v[6]); cex(v[5], v[7]);
-    cex(v[0], v[4]); cex(v[1], v[5]); cex(v[2], v[6]); cex(v[3], v[7]);
-    cex(v[0], v[1]); cex(v[2], v[3]); cex(v[4], v[5]); cex(v[6], v[7]);
-    cex(v[2], v[4]); cex(v[3], v[5]);
-    cex(v[1], v[4]); cex(v[3], v[6]);
-    cex(v[3], v[4]);
-    lo = v[0]; s3 = v[3]; s4 = v[4]; hi = v[7];
-}
 
 template <int NC>
 __global__ void __launch_bounds__(64) dpc_kernel(const float* __restrict__ pin, float* __restrict__ pout, float* __restrict__ gray,
@@ -50,8 +29,8 @@ __global__ void __launch_bounds__(64) dpc_kernel(const float* __restrict__ pin, 
     unsigned found = 0;                                  // hot samples | dead samples << 16 of this thread (at most 16 each)
     if (t < (int64_t)hh * wq) {
         const int x = NC * (int)(t % wq), y = (int)(t / wq);
-        const int yr[3] = {y > 0 ? y - 1 : 1, y, y + 1 < hh ? y + 1 : hh - 2};
-        const int xl = x > 0 ? x - 1 : 1, xr = x + NC < ww ? x + NC : ww - 2;      // the columns left and right of the thread's cells
+        const int yr[3] = {mirror_below(y), y, mirror_above(y + 1, hh)};
+        const int xl = mirror_below(x), xr = mirror_above(x + NC, ww);      // the columns left and right of the thread's cells
         float g[NC];                                     // the cell's gray: its DN per plane (the median where flagged) summed in plane order
         unsigned any = 0;                                // bit i: cell i has a flag in some plane
 #pragma unroll 1
@@ -60,39 +39,26 @@ __global__ void __launch_bounds__(64) dpc_kernel(const float* __restrict__ pin, 
             float raw[NC], w[3][NC + 2];
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
-                const float* row = plane + (int64_t)yr[r] * ww;
                 float c[NC];
-                if constexpr (NC == 4) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(row + x);
-                    c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
-                } else {
-                    c[0] = row[x];
-                }
-                w[r][0] = dpc_dn_of(row[xl], P.top);
-                w[r][NC + 1] = dpc_dn_of(row[xr], P.top);
+                dpc_window_row<NC>(plane + (int64_t)yr[r] * ww, x, xl, xr, P.top, w[r], c);
 #pragma unroll
-                for (int i = 0; i < NC; ++i) {
-                    w[r][i + 1] = dpc_dn_of(c[i], P.top);
+                for (int i = 0; i < NC; ++i)
                     if (r == 1) raw[i] = c[i];
-                }
             }
             float o[NC];
 #pragma unroll
             for (int i = 0; i < NC; ++i) {
-                float nb[8] = {w[0][i], w[0][i + 1], w[0][i + 2], w[1][i], w[1][i + 2], w[2][i], w[2][i + 1], w[2][i + 2]};
-                float lo, s3, s4, hi;
-                order8(nb, lo, s3, s4, hi);
-                const float c = w[1][i + 1];
-                const float m = (s3 + s4) * 0.5f;
+                float s[8];
+                const float m = dpc_neighbours<NC>(w, i, s), c = w[1][i + 1];
                 const float var = fmaxf(P.a * m - P.b, P.floor);
-                const float dh = c - hi, dl = lo - c;
+                const float dh = c - s[7], dl = s[0] - c;
                 const bool hot = P.k_hot > 0.0f && dh > 0.0f && dh * dh > P.k2_hot * var;
                 const bool dead = P.k_dead > 0.0f && dl > 0.0f && dl * dl > P.k2_dead * var;
                 found += (hot ? 1u : 0u) + (dead ? 0x10000u : 0u);
                 any |= hot || dead ? 1u << i : 0u;
                 const float dk = hot || dead ? m : c;
                 g[i] = k ? g[i] + dk : dk;
-                o[i] = hot || dead ? dpc_norm_dn(m, P.top) : raw[i];
+                o[i] = hot || dead ? norm_dn(m, P.top) : raw[i];
             }
             float* dst = pout + ((int64_t)img * 4 + k) * hw + (int64_t)y * ww + x;
             if constexpr (NC == 4) {

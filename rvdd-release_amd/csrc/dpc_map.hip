@@ -1,11 +1,11 @@
 // The static defect map (rvdd_dpc_detect, rvdd_dpc_map_apply; the stage rvdd_set_dpc_map puts behind the ingest of rvdd_video_push).
 // Compiled -ffp-contract=off like dpc.hip: every operation below is rounded to f32 on its own, so that the counts and the written
-// values are the bits of the NumPy restatement (tests/dpc_map_ref.py).  dn(v), norm_dn, top and the mirroring of the eight
-// neighbours are those of dpc.hip.
+// values are the bits of the NumPy restatement (tests/dpc_map_ref.py).  dn_of, norm_dn, the mirroring, the window and the sorted eight
+// neighbours are dpc_rule.h's, the text dpc.hip uses.
 //
 // Detection: rvdd_dpc's rule per sample, with the largest / smallest neighbour replaced by the (tolerate + 1)-th largest / smallest, so
 // the whole order of the eight is needed: all 19 exchanges of the sorting network.  A thread owns NC sites of one row of ONE plane
-// across all n frames of the call -- window as in dpc_kernel, the wide form (NC = 4) with 16-byte loads -- counts its sites' hot and
+// across all n frames of the call -- the window of dpc_rule.h, the wide form (NC = 4) with 16-byte loads -- counts its sites' hot and
 // dead frames in registers and folds them into `hits` once, with a plain load, add and store: nobody else touches those words, and
 // launches are stream-ordered, so the totals do not depend on how the frames are split over calls.  No atomics, no LDS.
 //
@@ -13,30 +13,11 @@
 // good sites only (mask bit clear) and writes defective ones only: in place without a race, and a second application finds the same
 // good values.  The order statistics of the q good values of a ring come from rank counting over the ring padded with +inf -- fully
 // unrolled, no register array is indexed with a runtime value, nothing goes to scratch.
-#include "rvdd_internal.h"
+#include "dpc_rule.h"
 
 namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float dm_dn_of(float v, float top) { return ((v + 1.0f) * 0.5f) * top; }                 // ingest.hip dn_of
-__device__ __forceinline__ float dm_norm_dn(float dn, float maxv) { return 2.0f * __fdiv_rn(dn, maxv) - 1.0f; }     // ingest.hip norm_dn
-
-__device__ __forceinline__ void cex(float& a, float& b) {
-    const float lo = fminf(a, b), hi = fmaxf(a, b);
-    a = lo;
-    b = hi;
-}
-
-// the eight neighbours in any order -> ascending: the 19 compare-exchanges of the optimal 8-input sorting network
-__device__ __forceinline__ void sort8(float v[8]) {
-    cex(v[0], v[2]); cex(v[1], v[3]); cex(v[4], v[6]); cex(v[5], v[7]);
-    cex(v[0], v[4]); cex(v[1], v[5]); cex(v[2], v[6]); cex(v[3], v[7]);
-    cex(v[0], v[1]); cex(v[2], v[3]); cex(v[4], v[5]); cex(v[6], v[7]);
-    cex(v[2], v[4]); cex(v[3], v[5]);
-    cex(v[1], v[4]); cex(v[3], v[6]);
-    cex(v[1], v[2]); cex(v[3], v[4]); cex(v[5], v[6]);
-}
 
 __device__ __forceinline__ unsigned fold_hits(unsigned old, unsigned hot, unsigned dead) {      // both halves saturate at 65535
     const unsigned lo = min((old & 0xffffu) + min(hot, 0xffffu), 0xffffu), hi = min((old >> 16) + min(dead, 0xffffu), 0xffffu);
@@ -53,8 +34,8 @@ __global__ void __launch_bounds__(64) dpc_detect_kernel(const float* __restrict_
     const int k = (int)(t / per);
     const int64_t r = t % per;
     const int x = NC * (int)(r % wq), y = (int)(r / wq);
-    const int yr[3] = {y > 0 ? y - 1 : 1, y, y + 1 < hh ? y + 1 : hh - 2};
-    const int xl = x > 0 ? x - 1 : 1, xr = x + NC < ww ? x + NC : ww - 2;      // the columns left and right of the thread's sites
+    const int yr[3] = {mirror_below(y), y, mirror_above(y + 1, hh)};
+    const int xl = mirror_below(x), xr = mirror_above(x + NC, ww);      // the columns left and right of the thread's sites
     unsigned hot[NC], dead[NC];
 #pragma unroll
     for (int i = 0; i < NC; ++i) hot[i] = dead[i] = 0;
@@ -64,30 +45,18 @@ __global__ void __launch_bounds__(64) dpc_detect_kernel(const float* __restrict_
         float w[3][NC + 2];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const float* row = plane + (int64_t)yr[q] * ww;
             float c[NC];
-            if constexpr (NC == 4) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(row + x);
-                c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
-            } else {
-                c[0] = row[x];
-            }
-            w[q][0] = dm_dn_of(row[xl], P.top);
-            w[q][NC + 1] = dm_dn_of(row[xr], P.top);
-#pragma unroll
-            for (int i = 0; i < NC; ++i) w[q][i + 1] = dm_dn_of(c[i], P.top);
+            dpc_window_row<NC>(plane + (int64_t)yr[q] * ww, x, xl, xr, P.top, w[q], c);
         }
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
-            float s[8] = {w[0][i], w[0][i + 1], w[0][i + 2], w[1][i], w[1][i + 2], w[2][i], w[2][i + 1], w[2][i + 2]};
-            sort8(s);
-            const float c = w[1][i + 1];
-            const float m = (s[3] + s[4]) * 0.5f;
+            float s[8];
+            const float m = dpc_neighbours<NC>(w, i, s), c = w[1][i + 1];
             const float var = fmaxf(P.a * m - P.b, P.floor);
             const float hi = tol == 0 ? s[7] : tol == 1 ? s[6] : tol == 2 ? s[5] : s[4];      // s[7 - tol], tol wave-uniform
             const float lo = tol == 0 ? s[0] : tol == 1 ? s[1] : tol == 2 ? s[2] : s[3];      // s[tol]
             const float dh = c - hi, dl = lo - c;
-            hot[i] += P.k_hot > 0.0f && dh > 0.0f && dh * dh > P.k2_hot * var ? 1u : 0u;
+            hot[i] += P.k_hot > 0.0f && dh > 0.0f && dh * dh > P.k2_hot * var ? 1u : 0u;       // dpc_kernel's two tests, hi / lo for s[7] / s[0]
             dead[i] += P.k_dead > 0.0f && dl > 0.0f && dl * dl > P.k2_dead * var ? 1u : 0u;
         }
     }
@@ -167,12 +136,12 @@ __global__ void __launch_bounds__(64) dpc_map_apply_kernel(float* __restrict__ p
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const bool good = !((m1[j] >> k) & 1u);
-                v1[j] = good ? dm_dn_of(plane[at1[j]], top) : inf;
+                v1[j] = good ? dn_of(plane[at1[j]], top) : inf;
                 q += good ? 1 : 0;
             }
             if (q) {
                 d = middle_of<8>(v1, q);
-                *own = dm_norm_dn(d, top);
+                *own = norm_dn(d, top);
             } else {
                 float v2[16];
                 i = 0;
@@ -183,18 +152,18 @@ __global__ void __launch_bounds__(64) dpc_map_apply_kernel(float* __restrict__ p
                         if (dy > 0 && dy < 4 && dx > 0 && dx < 4) continue;
                         const int64_t at = (int64_t)ys[dy] * ww + xs[dx];
                         const bool good = !((mask[at] >> k) & 1u);
-                        v2[i++] = good ? dm_dn_of(plane[at], top) : inf;
+                        v2[i++] = good ? dn_of(plane[at], top) : inf;
                         q += good ? 1 : 0;
                     }
                 if (q) {
                     d = middle_of<16>(v2, q);
-                    *own = dm_norm_dn(d, top);
+                    *own = norm_dn(d, top);
                 } else {
-                    d = dm_dn_of(*own, top);         // unfixable: the sample keeps its bits
+                    d = dn_of(*own, top);         // unfixable: the sample keeps its bits
                 }
             }
         } else {
-            d = dm_dn_of(*own, top);
+            d = dn_of(*own, top);
         }
         g = k ? g + d : d;
     }

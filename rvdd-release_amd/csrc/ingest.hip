@@ -10,7 +10,7 @@
 // the two sensor rows, for the packed HWC layout 2 x 16 B (u16) / 4 x 16 B (f32) of one row, and writes one 16-B vector per
 // packed channel and one for the gray plane -- so the 64 lanes of a wave read 1 KiB runs of each sensor row and write 1 KiB
 // runs of each output plane.  It needs ww % 4 == 0 and 16-B aligned pointers; any other shape takes the one-cell form.
-#include "rvdd_internal.h"
+#include "dpc_rule.h"      // dn_of, norm_dn
 
 namespace {
 
@@ -69,8 +69,6 @@ __device__ __forceinline__ void load_cells4(const T* __restrict__ f, int64_t img
     }
 }
 
-// packed = 2 * (dn / maxv) - 1: the division correctly rounded, then the product, then the difference
-__device__ __forceinline__ float norm_dn(float dn, float maxv) { return 2.0f * __fdiv_rn(dn, maxv) - 1.0f; }
 // library._gray of a 4-channel frame: the f32 sum in channel order, left to right, times 0.25
 __device__ __forceinline__ float gray_dn(const float c[4]) { return (((c[0] + c[1]) + c[2]) + c[3]) * 0.25f; }
 
@@ -140,7 +138,6 @@ hipError_t launch_ingest_t(const T* frames, int n, int hh, int ww, float maxv, f
 // `cols` carries those four plane indices, two bits each.  Per cell: dn_k = ((v_k + 1) * 0.5) * top, then ingest's gray_dn.
 // Of the six plane-rows of a pair of pixel rows four are read (one colour per position), half of each used.  The wide form
 // gives a thread four neighbouring cells of a cell row: 2 x 16 B from each of the four plane-rows, one 16-B store.
-__device__ __forceinline__ float dn_of(float v, float top) { return ((v + 1.0f) * 0.5f) * top; }
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) gray_of_rgb_kernel(const float* __restrict__ rgb, float* __restrict__ gray, int n, int hh, int ww,

@@ -12,7 +12,7 @@
 // the sums of means in 64 LDS words of 64 bits and the three counters in three more, and goes to global memory once per distinct
 // key, touched mean bin and non-zero counter -- integer vector atomics, so the totals do not depend on the order of arrival.
 #include "../../include/rvdd.h"
-#include "rvdd_internal.h"
+#include "dpc_rule.h"      // dn_of
 
 namespace {
 
@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(kNoiseThreads) noise_hist_kernel(const float* 
             }
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                x[c] = ((x[c] + 1.0f) * 0.5f) * top;                            // dpc.hip dpc_dn_of
+                x[c] = dn_of(x[c], top);
                 margin = fminf(fminf(margin, x[c]), top - x[c]);                // top - x is exact enough: it is 0 only where x == top
             }
             float rs = x[0] + x[1];

@@ -23,14 +23,13 @@ flash) costs a few frames of fresh recurrence and nothing else.
 from __future__ import annotations
 
 import argparse
-import copy
 import json
 from typing import List, Sequence, Tuple
 
 import numpy as np
-import torch
 
-from .runtime import FRAME_SIG_BYTES, cut_score, raw_frames_to_device
+from .footage import ingest_frames, open_rawvideo
+from .runtime import FRAME_SIG_BYTES, cut_score
 
 T_HIST, T_GRID, MIN_LEN = 0.10, 0.12, 4
 
@@ -39,17 +38,10 @@ def signatures(rt, dataset, paths: Sequence[str], bit_depth: int, batch: int = 1
     """The signatures of the frames at `paths` (one video: one frame size) of a rawvideo dataset as a host uint8 array [N,6144], one
     struct rvdd_frame_sig per frame: read, ingested on `rt`'s device as `video_push` ingests them (gray only) and measured `batch`
     frames at a time, one copy to the host per batch."""
-    dev = rt._tdev
     out = np.empty((len(paths), FRAME_SIG_BYTES), np.uint8)
     for k in range(0, len(paths), max(1, int(batch))):
         part = paths[k:k + max(1, int(batch))]
-        H, W = dataset.frame_size(part[0])
-        frames = np.stack([dataset.read_frame(p) for p in part])
-        if dataset.container is not None:
-            _, gray = rt.ingest_bits(torch.from_numpy(frames).to(dev), dataset.container, int(bit_depth), H // 2, W // 2, n=len(part),
-                                     want_packed=False)
-        else:
-            _, gray = rt.ingest_raw(raw_frames_to_device(frames, dev), int(bit_depth), dataset.layout, want_packed=False)
+        _, gray = ingest_frames(rt, dataset, np.stack([dataset.read_frame(p) for p in part]), bit_depth, want_packed=False)
         out[k:k + len(part)] = rt.frame_sigs(gray, int(bit_depth)).cpu().numpy()
     return out
 
@@ -118,7 +110,6 @@ def detect(rt, dataset, videos, bit_depth: int, t_hist: float, t_grid: float, mi
 
 
 def main(argv=None) -> list:
-    from .data import create_dataset
     from .options import parse
     from .util._ops import ops_runtime
     p = argparse.ArgumentParser(add_help=False)
@@ -127,13 +118,7 @@ def main(argv=None) -> list:
     own, rest = p.parse_known_args(argv)
     t_hist, t_grid, min_len = thresholds(own, 1)
     opt = parse(rest)
-    if not any(a == '--dataset_mode' or a.startswith('--dataset_mode=') for a in rest):
-        opt.dataset_mode = 'rawvideo'
-    v = copy.deepcopy(opt)
-    v.max_dataset_size, v.num_threads, v.batch_size, v.serial_batches = float("inf"), 0, 1, True
-    dataset = create_dataset(v).dataset
-    if not hasattr(dataset, "read_frame"):
-        raise SystemExit("cuts reads --dataset_mode rawvideo")
+    dataset = open_rawvideo(opt, rest, "cuts")
     rt = ops_runtime(opt.gpu_ids[0] if opt.gpu_ids else 0)
     found = detect(rt, dataset, dataset.videos, int(opt.bit_depth), t_hist, t_grid, min_len)
     for key, frames, cuts, scores in found:

@@ -93,7 +93,6 @@ Videos of different frame sizes are grouped by size and run one group after the 
 from __future__ import annotations
 
 import argparse
-import copy
 import json
 import os
 import time
@@ -104,8 +103,8 @@ import torch
 
 from . import _lib
 from . import tiffio
-from .runtime import (BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, dpc_iso_curve, match_coeffs,
-                      raw_frames_to_device)
+from .footage import add_dpc_arguments, dpc_arguments, estimate_noise, open_rawvideo, to_device
+from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, match_coeffs
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
 # --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
@@ -149,45 +148,6 @@ def deal_slots(lengths: Sequence[int], slots: int, tail: int = 0) -> List[List[T
         if all(v < 0 for _, v, _ in step):
             return steps
         steps.append(step)
-
-
-def dpc_arguments(dpc, dpc_dead, dpc_iso, dpc_noise, bit_depth, dpc_noise_frames=None):
-    """--dpc / --dpc_dead / --dpc_iso / --dpc_noise -> None (no --dpc) or (k_hot, k_dead, noise_a, noise_b, var_floor) as Python
-    doubles (`runtime.dpc_cfg` rounds each to f32 once); SystemExit where the flags do not fit together.  --dpc_noise auto[,floor]:
-    noise_a and noise_b are None, for `main` to estimate from the footage."""
-    if dpc is None:
-        if dpc_dead is not None or dpc_iso is not None or dpc_noise is not None or dpc_noise_frames is not None:
-            raise SystemExit("--dpc_dead, --dpc_iso and --dpc_noise belong to --dpc K")
-        return None
-    auto = dpc_noise is not None and dpc_noise.split(',')[0] == 'auto'
-    if dpc_noise_frames is not None and not auto:
-        raise SystemExit("--dpc_noise_frames belongs to --dpc_noise auto")
-    if dpc_noise_frames is not None and dpc_noise_frames < 1:
-        raise SystemExit("--dpc_noise_frames must be >= 1, got %d" % dpc_noise_frames)
-    if (dpc_iso is None) == (dpc_noise is None):
-        raise SystemExit("--dpc needs exactly one of --dpc_iso {%s} and --dpc_noise a,b[,floor]" % ','.join(str(k) for k in DPC_ISO_CURVES))
-    k_dead = dpc if dpc_dead is None else dpc_dead
-    if not (dpc >= 0 and k_dead >= 0 and dpc < float("inf") and k_dead < float("inf")):
-        raise SystemExit("--dpc and --dpc_dead are thresholds >= 0, got %r and %r" % (dpc, k_dead))
-    floor = 1.0
-    if dpc_iso is not None:
-        if dpc_iso not in DPC_ISO_CURVES:
-            raise SystemExit("--dpc_iso must be one of %s, got %r" % (', '.join(str(k) for k in DPC_ISO_CURVES), dpc_iso))
-        a, b = dpc_iso_curve(dpc_iso, bit_depth)
-    else:
-        f = dpc_noise.split(',')
-        if auto:
-            f = [None] + f                         # auto[,floor]: a and b come from the footage
-        if len(f) not in (2, 3):
-            raise SystemExit("--dpc_noise takes a,b, a,b,floor or auto[,floor]")
-        try:
-            a, b = (None, None) if auto else (float(f[0]), float(f[1]))
-            floor = float(f[2]) if len(f) == 3 else 1.0
-        except ValueError:
-            raise SystemExit("--dpc_noise takes numbers a,b[,floor] or auto[,floor], got %r" % dpc_noise)
-        if not floor > 0:
-            raise SystemExit("--dpc_noise: the floor must be > 0, got %r" % floor)
-    return (float(dpc), float(k_dead), a, b, floor)
 
 
 def dpc_map_arguments(dpc_map, frames, share, tolerate, static_only, have_dpc):
@@ -271,20 +231,6 @@ def match_report(a, b, bit_depth, iso):
         print('match: WARNING: the footage is cleaner than the ISO %d checkpoints\' noise curve: matching stretches it by s = %.3f beyond '
               'the range the network was trained on, which can lose quality (DESIGN.md 4.16: the table of measured gains and losses)' % (iso, s))
     return cfg
-
-
-def estimate_noise(dataset, dev, bit_depth, frames, flag='--dpc_noise'):
-    """--dpc_noise auto / --match_noise auto: (a, b) of `noise.estimate` on the run's videos, the line `python -m rvdd_release_amd.noise` prints sent to
-    the log; SystemExit with the fit's message where it refuses."""
-    from . import noise
-    from .util._ops import ops_runtime
-    acc, read = noise.estimate(ops_runtime(dev.index or 0), dataset, bit_depth, frames)
-    try:
-        r = noise.report(acc, bit_depth, read)
-    except RuntimeError as err:
-        raise SystemExit("%s auto: %s -- pass the curve as %s a,b" % (flag, err, flag))
-    print('noise: ' + noise.format_line(r))
-    return (r["a"], r["b"])
 
 
 def cuts_arguments(cuts, own, future):
@@ -382,12 +328,7 @@ def _parse(argv):
     p.add_argument('--out_format', type=str, default='f32', help=', '.join(OUT_FORMATS))
     p.add_argument('--out_bit_depth', type=int, default=None, help='bit depth of the sensor formats (default: --bit_depth)')
     p.add_argument('--all_frames', action='store_true', help='write every input frame, the first and the last of a video too')
-    p.add_argument('--dpc', type=float, default=None, help='defective-pixel correction: threshold K in standard deviations (both sides)')
-    p.add_argument('--dpc_dead', type=float, default=None, help='threshold of the dead side (default: --dpc; 0 = off)')
-    p.add_argument('--dpc_iso', type=int, default=None, help='the noise curve of ISO 3200 / 12800, rescaled to --bit_depth')
-    p.add_argument('--dpc_noise', type=str, default=None, help='a,b[,floor]: var = a * m - b in DN of the frames, the least variance; '
-                   'auto[,floor]: estimated from the footage (assumes one camera setting for the whole run)')
-    p.add_argument('--dpc_noise_frames', type=int, default=None, help='with --dpc_noise auto: frames read per video (default 4)')
+    add_dpc_arguments(p)
     p.add_argument('--dpc_map', type=str, default=None, help='FILE: correct the sites of this defect map (python -m rvdd_release_amd.dpc_map '
                    'writes one); auto: find the map in the footage before streaming starts, with the rule of --dpc')
     p.add_argument('--dpc_map_frames', type=int, default=None, help='with --dpc_map auto: frames read per video, spread over it (default 16)')
@@ -431,24 +372,11 @@ def _parse(argv):
     return opt
 
 
-def main(argv=None) -> dict:
-    from .data import create_dataset
-    from .library import iio_write
-    from .models import create_model
-    from .util import util
-    opt = _parse(argv)
-    layout, sample, suffix = OUT_FORMATS[opt.out_format]
-    depth = 8 if opt.out_format == "f32" else opt.out_bit_depth
-    v = copy.deepcopy(opt)
-    v.max_dataset_size, v.num_threads, v.batch_size, v.serial_batches = float("inf"), 0, 1, True
-    dataset = create_dataset(v).dataset
-    if not hasattr(dataset, "read_frame"):
-        raise SystemExit("denoise reads --dataset_mode rawvideo")
-    model = create_model(opt)
-    model.setup(opt)
-    net, dev = model._netDenoise, model.device
-    fut = int(opt.future_patch_depth)
-    curve = None                                  # --dpc_noise auto / --match_noise auto: ONE estimate of the run's own footage, before any push
+def prepasses(opt, dataset, dev):
+    """What is decided on the run's own footage before any push, in this order: the noise curve of --dpc_noise auto / --match_noise auto
+    (ONE estimate for both), the defect map, the match coefficients, the shots.  Completes opt.dpc and opt.match; -> (dmap: the cellmask
+    or None, match: struct rvdd_match_cfg or None, shots [(key, [paths])])."""
+    curve = None
     if opt.dpc is not None and opt.dpc[2] is None:
         curve = estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames)
         opt.dpc = opt.dpc[:2] + curve + opt.dpc[4:]
@@ -462,90 +390,118 @@ def main(argv=None) -> dict:
             curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--match_noise')
             opt.match = curve + opt.match[2:]
         match = match_report(opt.match[0], opt.match[1], int(opt.bit_depth), opt.match[2])
-
     # --cuts: every shot is a video of its own from here on, under its video's key
     shots = dataset.videos if opt.cuts is None else find_shots(dataset, dev, opt)
+    return dmap, match, shots
+
+
+def write_frame(opt, rt, out_b, host_b, key, path, W):
+    """One output frame to <results_dir>/<key>/: the file of --out_format from `host_b`, the frame's samples on the host, under the base
+    name of `path`, and with --srgb the display image of `out_b`, the network output [1,3,H,W] on the device."""
+    from .library import iio_write
+    from .util import util
+    layout, sample, suffix = OUT_FORMATS[opt.out_format]
+    stem = os.path.splitext(os.path.basename(path))[0]
+    util.mkdir(os.path.join(opt.results_dir, key))
+    if layout != "bits":
+        iio_write(host_b, os.path.join(opt.results_dir, key, stem + suffix))
+    elif sample == "msb":
+        tiffio.write_packed(os.path.join(opt.results_dir, key, stem + suffix), host_b, W, opt.out_bit_depth)
+    else:
+        host_b.tofile(os.path.join(opt.results_dir, key, stem + suffix))
+    if opt.srgb is not None:
+        iso, n, red, blue = opt.srgb
+        png = rt.ppipe(out_b, 1.0 / n, red, blue, iso, _lib.PPIPE_FROM_NET, "nchw")
+        iio_write(png[0].cpu().numpy(), os.path.join(opt.results_dir, key, stem + '_srgb.png'))
+
+
+def run_group(opt, model, dataset, videos, H, W, dmap, match) -> int:
+    """The videos [(key, [paths])] of one frame size H x W through one runtime: its options and stages set, the videos dealt to the
+    slots (`deal_slots`), every step pushed, its valid outputs taken to the host in one egress and written (`write_frame`), and the
+    `dpc:` line of every video that ended.  -> the frames written."""
+    layout, sample, _ = OUT_FORMATS[opt.out_format]
+    depth = 8 if opt.out_format == "f32" else opt.out_bit_depth
+    dev, fut = model.device, int(opt.future_patch_depth)
+    B = max(1, min(int(opt.batch_size), len(videos)))
+    rt = model._netDenoise.runtime_for(B, H, W, pin=True)
+    rt.set_option("no_warp", int(bool(opt.no_warp)))
+    rt.set_option("prev_noisy_frame", int(bool(opt.prev_noisy_frame)))
+    rt.set_option("warp_raw", int(bool(opt.warp_raw)))
+    rt.set_option("bayer_pattern", BAYER_PATTERNS.index(opt.bayer_pattern))
+    rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
+    rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
+    rt.set_option("stream_all_frames", int(opt.all_frames))
+    rt.set_dpc(None if opt.dpc is None else dpc_cfg(*opt.dpc))
+    if dmap is not None and dmap.shape != (H // 2, W // 2):
+        raise SystemExit("--dpc_map: the map is one of a %d x %d mosaic, video %r has frames of %d x %d (one camera per run)"
+                         % (2 * dmap.shape[1], 2 * dmap.shape[0], videos[0][0], W, H))
+    if dmap is not None:
+        rt.set_dpc_map(dmap)
+    rt.set_match(match)
+    dpc_seen = rt.dpc_counts() if opt.dpc is not None else None      # rvdd_dpc_counts at the end of the slot's last video
+    dpc_frames = [0] * B                        # frames the slot's video has pushed
+    container = dataset.container               # None, or "msb" / "mipi": the frames stay bit-packed up to the device
+    if layout == "bits" and sample == "mipi" and W % (2 if depth == 12 else 4):
+        raise SystemExit("--out_format mosaic_mipi: a RAW%d row is groups of %d pixels, the frames are %d wide" % (depth, 2 if depth == 12 else 4, W))
+    if container is not None:
+        shape = (B, H, bits_row_bytes(W, int(opt.bit_depth), container))
+    else:
+        shape = (B, H, W) if dataset.layout == "mosaic" else (B, H // 2, W // 2, 4)
+    out = files = None
+    written = 0
+    # --all_frames with a future frame: the step behind a video's last frame (k = N) is the IDLE that outputs that frame
+    for step in deal_slots([len(f) for _, f in videos], B, tail=fut if opt.all_frames else 0):
+        batch = np.zeros(shape, dtype=dataset.dtype)
+        for b, (c, vid, k) in enumerate(step):
+            if c != IDLE:
+                batch[b] = dataset.read_frame(videos[vid][1][k])
+        out, valid = rt.video_push(to_device(dataset, batch, dev), [c for c, _, _ in step], int(opt.bit_depth), dataset.layout, out,
+                                   container=container)
+        host = None
+        if any(valid):                               # the files' samples of all slots: one kernel, one copy
+            files = rt.egress_bits(out, sample, depth, out=files) if layout == "bits" else rt.egress(out, layout, sample, depth, out=files)
+            host = files.cpu().numpy()
+            host = host.view(np.uint16) if host.dtype == np.int16 else host
+        ended, ends = False, []
+        for b, (c, vid, k) in enumerate(step):
+            if vid < 0:
+                continue
+            key, frames = videos[vid]
+            last = k == len(frames) - (0 if opt.all_frames and fut else 1)      # the step that ends the video
+            ended = ended or last
+            dpc_frames[b] = min(k + 1, len(frames))
+            if last:                                # --cuts: several shots share a key; the line names the shot's first frame
+                ends.append((b, key if opt.cuts is None else '%s from %s' % (key, os.path.basename(frames[0]))))
+            if valid[b]:
+                write_frame(opt, rt, out[b:b + 1], host[b], key, frames[k - fut], W)      # the centre frame
+                written += 1
+        if ended:
+            rt.set_option("tvl1_async", 0)          # synchronises: reports a TV-L1 exchange of this video's pushes that gave up
+            if opt.dpc is not None:                 # ... and before the slot's next FIRST push: the difference is this video's
+                now = rt.dpc_counts()
+                for b, key in ends:
+                    print('dpc: %d hot, %d dead samples corrected in %d frames (%s)'
+                          % (now[b][0] - dpc_seen[b][0], now[b][1] - dpc_seen[b][1], dpc_frames[b], key))
+                    dpc_seen[b] = now[b]
+    rt.set_option("tvl1_async", 0)
+    return written
+
+
+def main(argv=None) -> dict:
+    from .models import create_model
+    opt = _parse(argv)
+    dataset = open_rawvideo(opt, None, "denoise")          # _parse has settled --dataset_mode
+    model = create_model(opt)
+    model.setup(opt)
+    dmap, match, shots = prepasses(opt, dataset, model.device)
     groups = {}                                   # frame size -> its videos, in dataset order
     for key, frames in shots:
         groups.setdefault(dataset.frame_size(frames[0]), []).append((key, frames))
     written = 0
     t0 = time.time()
     for (H, W), videos in groups.items():
-        B = max(1, min(int(opt.batch_size), len(videos)))
-        rt = net.runtime_for(B, H, W, pin=True)
-        rt.set_option("no_warp", int(bool(opt.no_warp)))
-        rt.set_option("prev_noisy_frame", int(bool(opt.prev_noisy_frame)))
-        rt.set_option("warp_raw", int(bool(opt.warp_raw)))
-        rt.set_option("bayer_pattern", BAYER_PATTERNS.index(opt.bayer_pattern))
-        rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
-        rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
-        rt.set_option("stream_all_frames", int(opt.all_frames))
-        rt.set_dpc(None if opt.dpc is None else dpc_cfg(*opt.dpc))
-        if dmap is not None and dmap.shape != (H // 2, W // 2):
-            raise SystemExit("--dpc_map: the map is one of a %d x %d mosaic, video %r has frames of %d x %d (one camera per run)"
-                             % (2 * dmap.shape[1], 2 * dmap.shape[0], videos[0][0], W, H))
-        if dmap is not None:
-            rt.set_dpc_map(dmap)
-        rt.set_match(match)
-        dpc_seen = rt.dpc_counts() if opt.dpc is not None else None      # rvdd_dpc_counts at the end of the slot's last video
-        dpc_frames = [0] * B                        # frames the slot's video has pushed
-        container = dataset.container               # None, or "msb" / "mipi": the frames stay bit-packed up to the device
-        if layout == "bits" and sample == "mipi" and W % (2 if depth == 12 else 4):
-            raise SystemExit("--out_format mosaic_mipi: a RAW%d row is groups of %d pixels, the frames are %d wide" % (depth, 2 if depth == 12 else 4, W))
-        if container is not None:
-            shape = (B, H, bits_row_bytes(W, int(opt.bit_depth), container))
-        else:
-            shape = (B, H, W) if dataset.layout == "mosaic" else (B, H // 2, W // 2, 4)
-        out = files = None
-        # --all_frames with a future frame: the step behind a video's last frame (k = N) is the IDLE that outputs that frame
-        for step in deal_slots([len(f) for _, f in videos], B, tail=fut if opt.all_frames else 0):
-            batch = np.zeros(shape, dtype=dataset.dtype)
-            for b, (c, vid, k) in enumerate(step):
-                if c != IDLE:
-                    batch[b] = dataset.read_frame(videos[vid][1][k])
-            frames_dev = raw_frames_to_device(batch, dev) if container is None else torch.from_numpy(batch).to(dev)
-            out, valid = rt.video_push(frames_dev, [c for c, _, _ in step], int(opt.bit_depth), dataset.layout, out, container=container)
-            host = None
-            if any(valid):                               # the files' samples of all slots: one kernel, one copy
-                files = rt.egress_bits(out, sample, depth, out=files) if layout == "bits" else rt.egress(out, layout, sample, depth, out=files)
-                host = files.cpu().numpy()
-                host = host.view(np.uint16) if host.dtype == np.int16 else host
-            ended, ends = False, []
-            for b, (c, vid, k) in enumerate(step):
-                if vid < 0:
-                    continue
-                key, frames = videos[vid]
-                last = k == len(frames) - (0 if opt.all_frames and fut else 1)      # the step that ends the video
-                ended = ended or last
-                dpc_frames[b] = min(k + 1, len(frames))
-                if last:                                # --cuts: several shots share a key; the line names the shot's first frame
-                    ends.append((b, key if opt.cuts is None else '%s from %s' % (key, os.path.basename(frames[0]))))
-                if not valid[b]:
-                    continue
-                path = frames[k - fut]                  # the centre frame
-                stem = os.path.splitext(os.path.basename(path))[0]
-                util.mkdir(os.path.join(opt.results_dir, key))
-                if layout != "bits":
-                    iio_write(host[b], os.path.join(opt.results_dir, key, stem + suffix))
-                elif sample == "msb":
-                    tiffio.write_packed(os.path.join(opt.results_dir, key, stem + suffix), host[b], W, depth)
-                else:
-                    host[b].tofile(os.path.join(opt.results_dir, key, stem + suffix))
-                if opt.srgb is not None:
-                    iso, n, red, blue = opt.srgb
-                    png = rt.ppipe(out[b:b + 1], 1.0 / n, red, blue, iso, _lib.PPIPE_FROM_NET, "nchw")
-                    iio_write(png[0].cpu().numpy(), os.path.join(opt.results_dir, key, stem + '_srgb.png'))
-                written += 1
-            if ended:
-                rt.set_option("tvl1_async", 0)          # synchronises: reports a TV-L1 exchange of this video's pushes that gave up
-                if opt.dpc is not None:                 # ... and before the slot's next FIRST push: the difference is this video's
-                    now = rt.dpc_counts()
-                    for b, key in ends:
-                        print('dpc: %d hot, %d dead samples corrected in %d frames (%s)'
-                              % (now[b][0] - dpc_seen[b][0], now[b][1] - dpc_seen[b][1], dpc_frames[b], key))
-                        dpc_seen[b] = now[b]
-        rt.set_option("tvl1_async", 0)
-    torch.cuda.synchronize(dev)
+        written += run_group(opt, model, dataset, videos, H, W, dmap, match)
+    torch.cuda.synchronize(model.device)
     dt = time.time() - t0
     print('(denoise, %d frames, %.3f s, %.2f frames/s)' % (written, dt, written / max(dt, 1e-9)))
     return {'frames': written, 'seconds': dt, 'fps': written / max(dt, 1e-9)}

@@ -26,15 +26,14 @@ none.  The rule is tested on synthetic frames only; NOTHING is 
 from __future__ import annotations
 
 import argparse
-import copy
 import math
 
 import numpy as np
 import torch
 
 from . import tiffio
-from .runtime import (dpc_cfg, dpc_detect_cfg, dpc_map_from_hits, dpc_map_from_mosaic, dpc_map_stats, dpc_map_to_mosaic,
-                      raw_frames_to_device)
+from .footage import add_dpc_arguments, dpc_arguments, estimate_noise, ingest_frames, open_rawvideo
+from .runtime import dpc_cfg, dpc_detect_cfg, dpc_map_from_hits, dpc_map_from_mosaic, dpc_map_stats, dpc_map_to_mosaic
 
 MAX_VIDEOS = 16
 
@@ -51,7 +50,6 @@ def detect(rt, dataset, bit_depth: int, rule, frames: int = 16, tolerate: int = 
     """The persistence counts (a device tensor [4,hh,ww], `RvddRuntime.dpc_detect`) of `frames` frames spread over each of the first
     `max_videos` videos of a rawvideo dataset, ingested on `rt`'s device as `video_push` ingests them; rule = `dpc_cfg(...)`.
     -> (hits, frames read).  RuntimeError where the videos differ in frame size.  Nothing is synchronised."""
-    dev = rt._tdev
     cfg = dpc_detect_cfg(rule, tolerate)
     hits, read, size = None, 0, None
     for key, paths in dataset.videos[:max_videos]:
@@ -61,11 +59,7 @@ def detect(rt, dataset, bit_depth: int, rule, frames: int = 16, tolerate: int = 
             raise RuntimeError("a defect map is one sensor's: video %r has frames of %d x %d, the videos before it %d x %d" % (key, W, H, size[1], size[0]))
         size = (H, W)
         for p in paths:                               # one frame per call: the totals do not depend on the split, the memory does
-            batch = dataset.read_frame(p)[None]
-            if dataset.container is not None:
-                packed, _ = rt.ingest_bits(torch.from_numpy(batch).to(dev), dataset.container, int(bit_depth), H // 2, W // 2, n=1, want_gray=False)
-            else:
-                packed, _ = rt.ingest_raw(raw_frames_to_device(batch, dev), int(bit_depth), dataset.layout, want_gray=False)
+            packed, _ = ingest_frames(rt, dataset, dataset.read_frame(p)[None], bit_depth, want_gray=False)
             hits = rt.dpc_detect(packed, cfg, int(bit_depth), hits)
             read += 1
     if hits is None:
@@ -121,8 +115,6 @@ def check_detect_flags(frames, share, tolerate, prefix="--"):
 
 
 def main(argv=None) -> dict:
-    from .data import create_dataset
-    from .denoise import dpc_arguments, estimate_noise
     from .options import parse
     from .util._ops import ops_runtime
     p = argparse.ArgumentParser(add_help=False)
@@ -130,11 +122,7 @@ def main(argv=None) -> dict:
     p.add_argument('--share', type=float, default=0.5, help='a site is defective where the rule fired in at least this share of the frames')
     p.add_argument('--tolerate', type=int, default=0, help='0..3 other defects among the eight neighbours (for flat calibration footage)')
     p.add_argument('--out', type=str, default=None, help='the map: a one-sample uint8 TIFF of the mosaic')
-    p.add_argument('--dpc', type=float, default=None)
-    p.add_argument('--dpc_dead', type=float, default=None)
-    p.add_argument('--dpc_iso', type=int, default=None)
-    p.add_argument('--dpc_noise', type=str, default=None)
-    p.add_argument('--dpc_noise_frames', type=int, default=None)
+    add_dpc_arguments(p)
     own, rest = p.parse_known_args(argv)
     if own.out is None:
         raise SystemExit("--out FILE is required: where the map goes")
@@ -143,13 +131,7 @@ def main(argv=None) -> dict:
     check_detect_flags(own.frames, own.share, own.tolerate)
     opt = parse(rest)
     rule = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth), own.dpc_noise_frames)
-    if not any(a == '--dataset_mode' or a.startswith('--dataset_mode=') for a in rest):
-        opt.dataset_mode = 'rawvideo'
-    v = copy.deepcopy(opt)
-    v.max_dataset_size, v.num_threads, v.batch_size, v.serial_batches = float("inf"), 0, 1, True
-    dataset = create_dataset(v).dataset
-    if not hasattr(dataset, "read_frame"):
-        raise SystemExit("dpc_map reads --dataset_mode rawvideo")
+    dataset = open_rawvideo(opt, rest, "dpc_map")
     dev = torch.device("cuda", opt.gpu_ids[0] if opt.gpu_ids else 0)
     if rule[2] is None:
         rule = rule[:2] + estimate_noise(dataset, dev, int(opt.bit_depth), 4 if own.dpc_noise_frames is None else own.dpc_noise_frames) + rule[4:]

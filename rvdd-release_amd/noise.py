@@ -31,12 +31,12 @@ fit's message.
 from __future__ import annotations
 
 import argparse
-import copy
 
 import numpy as np
 import torch
 
-from .runtime import DPC_ISO_CURVES, NOISE_ACC_BYTES, match_coeffs, nearest_iso, noise_acc_arrays, noise_fit, raw_frames_to_device
+from .footage import ingest_frames, open_rawvideo
+from .runtime import DPC_ISO_CURVES, NOISE_ACC_BYTES, match_coeffs, nearest_iso, noise_acc_arrays, noise_fit
 
 MAX_VIDEOS = 16
 
@@ -44,18 +44,11 @@ MAX_VIDEOS = 16
 def estimate(rt, dataset, bit_depth: int, frames: int = 4, max_videos: int = MAX_VIDEOS):
     """The accumulator (a device tensor, `RvddRuntime.noise_hist`) of the first `frames` frames of the first `max_videos` videos of a
     rawvideo dataset, ingested on `rt`'s device as `video_push` ingests them.  -> (acc, frames read).  Nothing is synchronised."""
-    dev = rt._tdev
-    acc = torch.zeros(NOISE_ACC_BYTES // 4, dtype=torch.int32, device=dev)
+    acc = torch.zeros(NOISE_ACC_BYTES // 4, dtype=torch.int32, device=rt._tdev)
     read = 0
     for _, paths in dataset.videos[:max_videos]:
         paths = paths[:max(1, int(frames))]
-        H, W = dataset.frame_size(paths[0])
-        batch = np.stack([dataset.read_frame(p) for p in paths])
-        if dataset.container is not None:
-            packed, _ = rt.ingest_bits(torch.from_numpy(batch).to(dev), dataset.container, int(bit_depth), H // 2, W // 2, n=len(paths),
-                                       want_gray=False)
-        else:
-            packed, _ = rt.ingest_raw(raw_frames_to_device(batch, dev), int(bit_depth), dataset.layout, want_gray=False)
+        packed, _ = ingest_frames(rt, dataset, np.stack([dataset.read_frame(p) for p in paths]), bit_depth, want_gray=False)
         rt.noise_hist(packed, int(bit_depth), acc)
         read += len(paths)
     return acc, read
@@ -84,7 +77,6 @@ def format_match_line(cfg, s: float, t: float, iso: int) -> str:
 
 
 def main(argv=None) -> dict:
-    from .data import create_dataset
     from .options import parse
     from .util._ops import ops_runtime
     p = argparse.ArgumentParser(add_help=False)
@@ -96,13 +88,7 @@ def main(argv=None) -> dict:
     if own.match_iso is not None and own.match_iso not in DPC_ISO_CURVES:
         raise SystemExit("--match_iso must be one of %s, got %r" % (', '.join(str(k) for k in DPC_ISO_CURVES), own.match_iso))
     opt = parse(rest)
-    if not any(a == '--dataset_mode' or a.startswith('--dataset_mode=') for a in rest):
-        opt.dataset_mode = 'rawvideo'
-    v = copy.deepcopy(opt)
-    v.max_dataset_size, v.num_threads, v.batch_size, v.serial_batches = float("inf"), 0, 1, True
-    dataset = create_dataset(v).dataset
-    if not hasattr(dataset, "read_frame"):
-        raise SystemExit("noise reads --dataset_mode rawvideo")
+    dataset = open_rawvideo(opt, rest, "noise")
     rt = ops_runtime(opt.gpu_ids[0] if opt.gpu_ids else 0)
     acc, read = estimate(rt, dataset, int(opt.bit_depth), own.frames)
     try:

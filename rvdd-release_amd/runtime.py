@@ -263,21 +263,79 @@ def raw_frames_to_device(frames, device) -> torch.Tensor:
     return frames.to(device)
 
 
+_WORD32 = (torch.int32, getattr(torch, "uint32", torch.int32))     # counters the library adds to: either reading of the 32 bits
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+def _dev_tensor(t, name: str, device: Optional[int], dtype=torch.float32, shape=None, nbytes: Optional[int] = None,
+                contiguous: Optional[str] = "copy", form: Optional[str] = None) -> torch.Tensor:
+    """The one check of a tensor that crosses the ABI: on the GPU, on cuda:`device` (None: any), then its form -- `dtype` (one, a
+    tuple of alternatives, None: any), `shape` (None: any; an entry None: any extent), `nbytes`, and its layout: contiguous "copy"
+    returns a dense copy of a strided tensor, "require" refuses one (an output, or frames corrected in place), None leaves the
+    strides to the caller.  form: the sentence that describes the form, for callers whose message names all of it at once."""
+    if not getattr(t, "is_cuda", False):
+        raise RuntimeError(f"{name} must be a GPU tensor (rvdd has no CPU path)")
+    if device is not None and t.device.index != device:
+        raise RuntimeError(f"{name} lives on cuda:{t.device.index} but this runtime drives cuda:{device}")
+    if shape is not None and t.shape != shape and (        # shape: a tuple or a torch.Size, which compare as tuples
+            len(shape) != t.dim() or any(e is not None and e != g for e, g in zip(shape, t.shape))):
+        raise RuntimeError(f"{form}, got {t.dtype} {tuple(t.shape)}" if form else f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if dtype is not None and t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
+        raise RuntimeError(f"{form}, got {t.dtype} {tuple(t.shape)}" if form else f"{name} must be {str(dtype).replace('torch.', '')}")
+    if nbytes is not None and t.numel() * t.element_size() != nbytes:
+        raise RuntimeError(f"{form}, got {t.dtype} {tuple(t.shape)}" if form else f"{name} must hold {nbytes} bytes, got {t.numel() * t.element_size()}")
+    if contiguous is None or t.is_contiguous():
+        return t
+    if contiguous == "require":
+        raise RuntimeError(f"{form}, got {t.dtype} {tuple(t.shape)} with strides {t.stride()}" if form else
+                           f"{name} must be contiguous (it is written where it lies)")
+    return t.contiguous()
+
+
+def _out_or_new(out, name: str, shape, tdev: torch.device, dtype=torch.float32, *, zero: bool = False, nbytes: Optional[int] = None,
+                form: Optional[str] = None) -> torch.Tensor:
+    """The output of an op: a new tensor of `shape` and `dtype` (the first of a tuple) on `tdev` -- zeroed for an accumulator -- or
+    the caller's `out`, checked: on that device, of that dtype and shape (with nbytes: of any shape of that many bytes), contiguous."""
+    if out is None:
+        return (torch.zeros if zero else torch.empty)(shape, dtype=dtype[0] if isinstance(dtype, tuple) else dtype, device=tdev)
+    return _dev_tensor(out, name, tdev.index, dtype, None if nbytes is not None else shape, nbytes, "require", form)
+
+
+def _frames(t, c: int, spec: str, name: str, device: int, contiguous: str = "copy"):
+    """A batch of c-channel frames [n,c,h,w] -> (the tensor checked, n, h, w).  spec: "<op>: <what> is [n,c,h,w]", the sentence of
+    the message for anything else -- said first, whatever device the argument is on."""
+    if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != c:
+        raise RuntimeError(f"{spec}, got {tuple(getattr(t, 'shape', ()))}")
+    return _dev_tensor(t, name, device, contiguous=contiguous), t.shape[0], t.shape[2], t.shape[3]
+
+
+def _raw_dtype(dtype) -> Optional[int]:
+    """enum rvdd_raw_dtype of a torch dtype: float32, or uint16 / int16 (read as the same 16 bits, unsigned: the view numpy's uint16
+    arrays upload as where torch's own uint16 support is thin); None for any other"""
+    if dtype == torch.float32:
+        return _lib.RAW_F32
+    if dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        return _lib.RAW_U16
+    return None
+
+
+def _pattern_index(pattern, who: str) -> int:
+    if pattern not in BAYER_PATTERNS:
+        raise ValueError(f"{who}: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
+    return BAYER_PATTERNS.index(pattern)
+
+
 def _raw_frames(t: torch.Tensor, layout: str, name: str, device: int):
     """-> (contiguous tensor, enum rvdd_raw_dtype, enum rvdd_raw_layout, n, hh, ww) of sensor frames [n,2hh,2ww] ("mosaic")
-    or [n,hh,ww,4] ("packed_hwc").  Accepted dtypes: torch.uint16, torch.int16 (read as the same 16 bits, unsigned: the
-    view numpy's uint16 arrays upload as where torch's own uint16 support is thin) and torch.float32."""
+    or [n,hh,ww,4] ("packed_hwc"), of the dtypes `_raw_dtype` knows."""
     if layout not in RAW_LAYOUTS:
         raise ValueError(f"{name}: layout {layout!r} is not one of {', '.join(RAW_LAYOUTS)}")
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"{name}: frames must be a GPU tensor (rvdd has no CPU path)")
-    if t.device.index != device:
-        raise RuntimeError(f"{name}: frames live on cuda:{t.device.index} but this runtime drives cuda:{device}")
-    if t.dtype == torch.float32:
-        dtype = _lib.RAW_F32
-    elif t.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
-        dtype = _lib.RAW_U16
-    else:
+    t = _dev_tensor(t, f"{name}: frames", device, dtype=None)
+    dtype = _raw_dtype(t.dtype)
+    if dtype is None:
         raise RuntimeError(f"{name}: frames must be uint16 (or its int16 view) or float32, got {t.dtype}")
     if layout == "mosaic":
         if t.dim() != 3 or t.shape[1] % 2 or t.shape[2] % 2:
@@ -287,23 +345,7 @@ def _raw_frames(t: torch.Tensor, layout: str, name: str, device: int):
         if t.dim() != 4 or t.shape[3] != 4:
             raise RuntimeError(f"{name}: packed_hwc frames are [n,hh,ww,4], got {tuple(t.shape)}")
         n, hh, ww = t.shape[0], t.shape[1], t.shape[2]
-    return (t if t.is_contiguous() else t.contiguous()), dtype, RAW_LAYOUTS[layout], n, hh, ww
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
-def _chk_dev(t: torch.Tensor, shape: Tuple[int, ...], name: str, device: Optional[int] = None) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a GPU tensor (rvdd has no CPU path)")
-    if device is not None and t.device.index != device:
-        raise RuntimeError(f"{name} lives on cuda:{t.device.index} but this runtime drives cuda:{device}")
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32")
-    return t if t.is_contiguous() else t.contiguous()
+    return t, dtype, RAW_LAYOUTS[layout], n, hh, ww
 
 
 def _batch_strided(t: Optional[torch.Tensor], shape: Tuple[int, ...], name: str, device: int):
@@ -312,19 +354,20 @@ def _batch_strided(t: Optional[torch.Tensor], shape: Tuple[int, ...], name: str,
     only what is not laid out like that."""
     if t is None:
         return None, 0
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a GPU tensor (rvdd has no CPU path)")
-    if t.device.index != device:
-        raise RuntimeError(f"{name} lives on cuda:{t.device.index} but this runtime drives cuda:{device}")
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32")
+    _dev_tensor(t, name, device, torch.float32, shape, None, None)       # positional: once per input of every step
     C, h, w = shape[1:]
     if t.stride()[1:] == (h * w, w, 1) and t.stride(0) >= C * h * w:
         return t, t.stride(0)
     t = t.contiguous()
     return t, C * h * w
+
+
+def _common_stride(items, dense: int):
+    """[(tensor or None, batch stride)] of `_batch_strided` -> (the items, their one batch stride); `dense` where all are None"""
+    strides = {st for t, st in items if t is not None}
+    if len(strides) > 1:        # slices of different tensors: fall back to dense copies
+        return [(None if t is None else t.contiguous(), dense) for t, _ in items], dense
+    return items, (strides.pop() if strides else dense)
 
 
 class RvddRuntime:
@@ -355,6 +398,10 @@ class RvddRuntime:
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self._tdev).cuda_stream
+
+    def _pattern(self, pattern: Optional[str], who: str) -> int:
+        """enum rvdd_bayer of one of BAYER_PATTERNS; None = the pattern set_option("bayer_pattern", ...) gave this runtime"""
+        return getattr(self, "bayer_pattern", 0) if pattern is None else _pattern_index(pattern, who)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
@@ -433,23 +480,14 @@ class RvddRuntime:
             flow_prev = flow_next = None
         elif flow_prev is None:
             raise RuntimeError("rvdd_step: flow_prev is required (no --no_warp option set on this runtime)")
-        raws = [_batch_strided(t, rs, n, self.device) for t, n in ((raw_prev, "raw_prev"), (raw_cur, "raw_cur"), (raw_next, "raw_next"))]
-        flows = [_batch_strided(t, fs, n, self.device) for t, n in ((flow_prev, "flow_prev"), (flow_next, "flow_next"))]
+        dev = self.device
+        raws = [_batch_strided(raw_prev, rs, "raw_prev", dev), _batch_strided(raw_cur, rs, "raw_cur", dev), _batch_strided(raw_next, rs, "raw_next", dev)]
+        flows = [_batch_strided(flow_prev, fs, "flow_prev", dev), _batch_strided(flow_next, fs, "flow_next", dev)]
         if raws[1][0] is None:
             raise RuntimeError("rvdd_step: raw_cur is required")
-
-        def common_stride(items, dense):
-            strides = {st for t, st in items if t is not None}
-            if len(strides) > 1:        # slices of different tensors: fall back to dense copies
-                return [(None if t is None else t.contiguous(), dense) for t, _ in items], dense
-            return items, (strides.pop() if strides else dense)
-        raws, rstride = common_stride(raws, rs[1] * rs[2] * rs[3])
-        flows, fstride = common_stride(flows, fs[1] * fs[2] * fs[3])
-        if out is None:
-            out = torch.empty(B, 3, H, W, dtype=torch.float32, device=self._tdev)
-        else:
-            _chk_dev(out, (B, 3, H, W), "out", self.device)
-            assert out.is_contiguous()
+        raws, rstride = _common_stride(raws, rs[1] * rs[2] * rs[3])
+        flows, fstride = _common_stride(flows, fs[1] * fs[2] * fs[3])
+        out = _out_or_new(out, "out", (B, 3, H, W), self._tdev)
         if live is not None:
             self._check(self.lib.rvdd_step_live(self.h, live, _ptr(raws[0][0]), _ptr(raws[1][0]), _ptr(raws[2][0]),
                                                 _ptr(flows[0][0]), _ptr(flows[1][0]), rstride, fstride, _ptr(out),
@@ -477,16 +515,8 @@ class RvddRuntime:
         """[n,3,H,W] RGB in [-1,1] -> [n,H/2,W/2]: the gray plane, in DN, of its re-mosaic in `pattern` (one of BAYER_PATTERNS;
         None = the pattern set_option("bayer_pattern", ...) gave this runtime) -- what `ingest_raw` gives for the sensor frame
         (rvdd_gray_of_rgb)."""
-        if pattern is None:
-            pat = getattr(self, "bayer_pattern", 0)
-        elif pattern in BAYER_PATTERNS:
-            pat = BAYER_PATTERNS.index(pattern)
-        else:
-            raise ValueError(f"gray_of_rgb: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
-        if not torch.is_tensor(rgb) or rgb.dim() != 4 or rgb.shape[1] != 3:
-            raise RuntimeError(f"gray_of_rgb: rgb is [n,3,H,W], got {tuple(getattr(rgb, 'shape', ()))}")
-        n, _, H, W = rgb.shape
-        rgb = _chk_dev(rgb, rgb.shape, "rgb", self.device)
+        pat = self._pattern(pattern, "gray_of_rgb")
+        rgb, n, H, W = _frames(rgb, 3, "gray_of_rgb: rgb is [n,3,H,W]", "rgb", self.device)
         gray = torch.empty(n, H // 2, W // 2, dtype=torch.float32, device=self._tdev)
         self._check(self.lib.rvdd_gray_of_rgb(self.h, _ptr(rgb), n, H, W, pat, int(bit_depth), _ptr(gray), self._stream()),
                     "rvdd_gray_of_rgb")
@@ -501,33 +531,14 @@ class RvddRuntime:
         pattern set_option("bayer_pattern", ...) gave this runtime.  out: a tensor of that shape and dtype to write into."""
         if layout not in OUT_LAYOUTS:
             raise ValueError(f"egress: layout {layout!r} is not one of {', '.join(OUT_LAYOUTS)}")
-        if pattern is None:
-            pat = getattr(self, "bayer_pattern", 0)
-        elif pattern in BAYER_PATTERNS:
-            pat = BAYER_PATTERNS.index(pattern)
-        else:
-            raise ValueError(f"egress: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
-        if dtype == torch.float32:
-            dt = _lib.RAW_F32
-        elif dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
-            dt = _lib.RAW_U16
-        else:
+        pat = self._pattern(pattern, "egress")
+        dt = _raw_dtype(dtype)
+        if dt is None:
             raise RuntimeError(f"egress: dtype must be torch.uint16 (or torch.int16, its view) or torch.float32, got {dtype}")
-        if not torch.is_tensor(rgb) or rgb.dim() != 4 or rgb.shape[1] != 3:
-            raise RuntimeError(f"egress: rgb is [n,3,H,W], got {tuple(getattr(rgb, 'shape', ()))}")
-        n, _, H, W = rgb.shape
-        rgb = _chk_dev(rgb, rgb.shape, "rgb", self.device)
+        rgb, n, H, W = _frames(rgb, 3, "egress: rgb is [n,3,H,W]", "rgb", self.device)
         shape = {"rgb_hwc": (n, H, W, 3), "mosaic": (n, H, W), "packed_hwc": (n, H // 2, W // 2, 4)}[layout]
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=self._tdev)
-        else:
-            if not torch.is_tensor(out) or not out.is_cuda:
-                raise RuntimeError("egress: out must be a GPU tensor (rvdd has no CPU path)")
-            if out.device.index != self.device:
-                raise RuntimeError(f"egress: out lives on cuda:{out.device.index} but this runtime drives cuda:{self.device}")
-            if tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
-                raise RuntimeError(f"egress: out must be a contiguous {dtype} tensor of shape {shape}, got {out.dtype} "
-                                   f"{tuple(out.shape)}")
+        out = _out_or_new(out, "egress: out", shape, self._tdev, dtype,
+                          form=f"egress: out must be a contiguous {dtype} tensor of shape {shape}")
         self._check(self.lib.rvdd_egress(self.h, _ptr(rgb), n, H, W, OUT_LAYOUTS[layout], dt, int(bit_depth), pat, _ptr(out),
                                          self._stream()), "rvdd_egress")
         return out
@@ -536,12 +547,8 @@ class RvddRuntime:
         """the uint8 GPU tensor of n tight frames of 2hh rows of bits_row_bytes(2ww, bit_depth, order) bytes, checked"""
         if order not in BITS_ORDERS:
             raise ValueError(f"{name}: order {order!r} is not one of {', '.join(BITS_ORDERS)}")
-        if not torch.is_tensor(frames) or not frames.is_cuda:
-            raise RuntimeError(f"{name}: frames must be a GPU tensor (rvdd has no CPU path)")
-        if frames.device.index != self.device:
-            raise RuntimeError(f"{name}: frames live on cuda:{frames.device.index} but this runtime drives cuda:{self.device}")
-        if frames.dtype != torch.uint8 or not frames.is_contiguous():
-            raise RuntimeError(f"{name}: packed frames are a contiguous uint8 tensor, got {frames.dtype}")
+        _dev_tensor(frames, f"{name}: frames", self.device, dtype=torch.uint8, contiguous="require",
+                    form=f"{name}: packed frames are a contiguous uint8 tensor")
         rb = bits_row_bytes(2 * ww, bit_depth, order)
         if frames.numel() != n * 2 * hh * rb:
             raise RuntimeError(f"{name}: {n} frames of {2 * hh} rows of {rb} bytes ({2 * ww} samples of {bit_depth} bits, {order}) are "
@@ -572,25 +579,11 @@ class RvddRuntime:
         elements to write into."""
         if order not in BITS_ORDERS:
             raise ValueError(f"egress_bits: order {order!r} is not one of {', '.join(BITS_ORDERS)}")
-        if pattern is None:
-            pat = getattr(self, "bayer_pattern", 0)
-        elif pattern in BAYER_PATTERNS:
-            pat = BAYER_PATTERNS.index(pattern)
-        else:
-            raise ValueError(f"egress_bits: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
-        if not torch.is_tensor(rgb) or rgb.dim() != 4 or rgb.shape[1] != 3:
-            raise RuntimeError(f"egress_bits: rgb is [n,3,H,W], got {tuple(getattr(rgb, 'shape', ()))}")
-        n, _, H, W = rgb.shape
-        rgb = _chk_dev(rgb, rgb.shape, "rgb", self.device)
+        pat = self._pattern(pattern, "egress_bits")
+        rgb, n, H, W = _frames(rgb, 3, "egress_bits: rgb is [n,3,H,W]", "rgb", self.device)
         rb = bits_row_bytes(W, int(bit_depth), order)
-        if out is None:
-            out = torch.empty(n, H, rb, dtype=torch.uint8, device=self._tdev)
-        else:
-            if not torch.is_tensor(out) or not out.is_cuda or out.device.index != self.device:
-                raise RuntimeError(f"egress_bits: out must be a GPU tensor on cuda:{self.device} (rvdd has no CPU path)")
-            if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n * H * rb:
-                raise RuntimeError(f"egress_bits: out must be a contiguous uint8 tensor of {n * H * rb} elements, got {out.dtype} "
-                                   f"{tuple(out.shape)}")
+        out = _out_or_new(out, "egress_bits: out", (n, H, rb), self._tdev, torch.uint8, nbytes=n * H * rb,
+                          form=f"egress_bits: out must be a contiguous uint8 tensor of {n * H * rb} elements")
         self._check(self.lib.rvdd_egress_bits(self.h, _ptr(rgb), n, H, W, BITS_ORDERS[order], int(bit_depth), pat, _ptr(out),
                                               self._stream()), "rvdd_egress_bits")
         return out
@@ -602,22 +595,13 @@ class RvddRuntime:
         same-colour neighbours (rvdd_dpc; `cfg`: `dpc_cfg(k_hot, k_dead, noise_a, noise_b, var_floor)`, the curve in DN of
         `bit_depth`).  -> the corrected frames (`out`, or a new tensor; never `packed` itself).  gray [n,hh,ww]: patched in place at
         the cells with a flag; counts: int32 / uint32 [n,2] on the device, the hot / dead flags of every frame are added to it."""
-        if not torch.is_tensor(packed) or packed.dim() != 4 or packed.shape[1] != 4:
-            raise RuntimeError(f"dpc: packed is [n,4,hh,ww], got {tuple(getattr(packed, 'shape', ()))}")
-        n, _, hh, ww = packed.shape
-        packed = _chk_dev(packed, packed.shape, "packed", self.device)
-        if out is None:
-            out = torch.empty_like(packed)
-        else:
-            _chk_dev(out, packed.shape, "out", self.device)
-            assert out.is_contiguous()
+        packed, n, hh, ww = _frames(packed, 4, "dpc: packed is [n,4,hh,ww]", "packed", self.device)
+        out = _out_or_new(out, "out", packed.shape, self._tdev)
         if gray is not None:
-            _chk_dev(gray, (n, hh, ww), "gray", self.device)
-            assert gray.is_contiguous()
+            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
         if counts is not None:
-            if not counts.is_cuda or counts.device.index != self.device or counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) \
-                    or tuple(counts.shape) != (n, 2) or not counts.is_contiguous():
-                raise RuntimeError(f"dpc: counts is a contiguous int32 / uint32 tensor [{n},2] on cuda:{self.device}")
+            _dev_tensor(counts, "dpc: counts", self.device, dtype=_WORD32, shape=(n, 2), contiguous="require",
+                        form=f"dpc: counts is a contiguous int32 / uint32 tensor [{n},2] on cuda:{self.device}")
         self._check(self.lib.rvdd_dpc(self.h, _ptr(packed), _ptr(out), _ptr(gray), n, hh, ww, int(bit_depth), C.byref(cfg), _ptr(counts),
                                       self._stream()), "rvdd_dpc")
         return out
@@ -628,15 +612,9 @@ class RvddRuntime:
         `dpc_detect_cfg(dpc_cfg(...), tolerate)`): a device int32 tensor [4,hh,ww] -- None = a new zeroed one -- which is returned;
         hot frames in the low 16 bits, dead frames in the high 16, each saturating at 65535.  Accumulate any number of calls, then
         `dpc_map_from_hits(hits, frames, share)`.  Nothing is synchronised."""
-        if not torch.is_tensor(packed) or packed.dim() != 4 or packed.shape[1] != 4:
-            raise RuntimeError(f"dpc_detect: packed is [n,4,hh,ww], got {tuple(getattr(packed, 'shape', ()))}")
-        n, _, hh, ww = packed.shape
-        packed = _chk_dev(packed, packed.shape, "packed", self.device)
-        if hits is None:
-            hits = torch.zeros(4, hh, ww, dtype=torch.int32, device=self._tdev)
-        elif not torch.is_tensor(hits) or not hits.is_cuda or hits.device.index != self.device or not hits.is_contiguous() \
-                or hits.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(hits.shape) != (4, hh, ww):
-            raise RuntimeError(f"dpc_detect: hits is a contiguous int32 / uint32 tensor [4,{hh},{ww}] on cuda:{self.device}")
+        packed, n, hh, ww = _frames(packed, 4, "dpc_detect: packed is [n,4,hh,ww]", "packed", self.device)
+        hits = _out_or_new(hits, "dpc_detect: hits", (4, hh, ww), self._tdev, _WORD32, zero=True,
+                           form=f"dpc_detect: hits is a contiguous int32 / uint32 tensor [4,{hh},{ww}] on cuda:{self.device}")
         self._check(self.lib.rvdd_dpc_detect(self.h, _ptr(packed), n, hh, ww, int(bit_depth), C.byref(cfg), _ptr(hits), self._stream()),
                     "rvdd_dpc_detect")
         return hits
@@ -657,13 +635,9 @@ class RvddRuntime:
     def dpc_map_apply(self, packed: torch.Tensor, bit_depth: int = 12, gray: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Packed frames [n,4,hh,ww] corrected by the handle's map IN PLACE (rvdd_dpc_map_apply), gray [n,hh,ww] re-formed at the
         map's cells.  -> packed.  Both must be contiguous: they are written where they lie.  Nothing is synchronised."""
-        if not torch.is_tensor(packed) or packed.dim() != 4 or packed.shape[1] != 4:
-            raise RuntimeError(f"dpc_map_apply: packed is [n,4,hh,ww], got {tuple(getattr(packed, 'shape', ()))}")
-        n, _, hh, ww = packed.shape
-        if _chk_dev(packed, packed.shape, "packed", self.device) is not packed:
-            raise RuntimeError("dpc_map_apply: packed must be contiguous (it is corrected in place)")
-        if gray is not None and _chk_dev(gray, (n, hh, ww), "gray", self.device) is not gray:
-            raise RuntimeError("dpc_map_apply: gray must be contiguous (it is patched in place)")
+        packed, n, hh, ww = _frames(packed, 4, "dpc_map_apply: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
+        if gray is not None:
+            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
         self._check(self.lib.rvdd_dpc_map_apply(self.h, _ptr(packed), _ptr(gray), n, hh, ww, int(bit_depth), self._stream()),
                     "rvdd_dpc_map_apply")
         return packed
@@ -674,15 +648,12 @@ class RvddRuntime:
         (rvdd_noise_hist): a device tensor holding struct rvdd_noise_acc -- int32 [32904]; None = a new zeroed one -- which is
         returned.  Accumulate any number of calls of one bit depth, then `noise_fit(acc, bit_depth)`; `noise_acc_arrays(acc)` gives
         the histogram, the sums of means and the counters.  Nothing is synchronised."""
-        if not torch.is_tensor(packed) or packed.dim() != 4 or packed.shape[1] != 4:
-            raise RuntimeError(f"noise_hist: packed is [n,4,hh,ww], got {tuple(getattr(packed, 'shape', ()))}")
-        n, _, hh, ww = packed.shape
-        packed = _chk_dev(packed, packed.shape, "packed", self.device)
+        packed, n, hh, ww = _frames(packed, 4, "noise_hist: packed is [n,4,hh,ww]", "packed", self.device)
         if acc is None:
             acc = torch.zeros(NOISE_ACC_BYTES // 4, dtype=torch.int32, device=self._tdev)
-        elif not torch.is_tensor(acc) or not acc.is_cuda or acc.device.index != self.device or not acc.is_contiguous() \
-                or acc.numel() * acc.element_size() != NOISE_ACC_BYTES:
-            raise RuntimeError(f"noise_hist: acc is a contiguous tensor of {NOISE_ACC_BYTES} bytes on cuda:{self.device} (what noise_hist returned)")
+        else:           # words of any type: the struct's bytes
+            _dev_tensor(acc, "noise_hist: acc", self.device, dtype=None, nbytes=NOISE_ACC_BYTES, contiguous="require",
+                        form=f"noise_hist: acc is a contiguous tensor of {NOISE_ACC_BYTES} bytes on cuda:{self.device} (what noise_hist returned)")
         self._check(self.lib.rvdd_noise_hist(self.h, _ptr(packed), n, hh, ww, int(bit_depth), _ptr(acc), self._stream()), "rvdd_noise_hist")
         return acc
 
@@ -695,26 +666,16 @@ class RvddRuntime:
         if not torch.is_tensor(gray) or gray.dim() != 3:
             raise RuntimeError(f"frame_sigs: gray is [n,hh,ww], got {tuple(getattr(gray, 'shape', ()))}")
         n, hh, ww = gray.shape
-        gray = _chk_dev(gray, gray.shape, "gray", self.device)
-        if out is None:
-            out = torch.empty(n, FRAME_SIG_BYTES, dtype=torch.uint8, device=self._tdev)
-        elif not torch.is_tensor(out) or not out.is_cuda or out.device.index != self.device or out.dtype != torch.uint8 \
-                or tuple(out.shape) != (n, FRAME_SIG_BYTES) or not out.is_contiguous():
-            raise RuntimeError(f"frame_sigs: out is a contiguous uint8 tensor [{n},{FRAME_SIG_BYTES}] on cuda:{self.device}")
+        gray = _dev_tensor(gray, "gray", self.device)
+        out = _out_or_new(out, "frame_sigs: out", (n, FRAME_SIG_BYTES), self._tdev, torch.uint8,
+                          form=f"frame_sigs: out is a contiguous uint8 tensor [{n},{FRAME_SIG_BYTES}] on cuda:{self.device}")
         self._check(self.lib.rvdd_frame_sigs(self.h, _ptr(gray), n, hh, ww, int(bit_depth), _ptr(out), self._stream()), "rvdd_frame_sigs")
         return out
 
     # -- footage matched to the checkpoint's noise curve ---------------------------------
     def _match(self, fn, name: str, t: torch.Tensor, c: int, cfg, out: Optional[torch.Tensor]) -> torch.Tensor:
-        if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != c:
-            raise RuntimeError(f"{name}: the frames are [n,{c},h,w], got {tuple(getattr(t, 'shape', ()))}")
-        n, _, d0, d1 = t.shape
-        t = _chk_dev(t, t.shape, "frames", self.device)
-        if out is None:
-            out = torch.empty_like(t)
-        else:
-            _chk_dev(out, t.shape, "out", self.device)
-            assert out.is_contiguous()
+        t, n, d0, d1 = _frames(t, c, f"{name}: the frames are [n,{c},h,w]", "frames", self.device)
+        out = _out_or_new(out, "out", t.shape, self._tdev)
         self._check(fn(self.h, _ptr(t), _ptr(out), n, d0, d1, None if cfg is None else C.byref(cfg), self._stream()), "rvdd_" + name)
         return out
 
@@ -782,11 +743,7 @@ class RvddRuntime:
             if any(not 0 <= v <= 255 for v in items):
                 raise ValueError("video_push: ctl entries are PUSH_NEXT (0), PUSH_FIRST (1) or PUSH_IDLE (2)")
             c = (C.c_uint8 * B)(*items)
-        if out is None:
-            out = torch.empty(B, 3, H, W, dtype=torch.float32, device=self._tdev)
-        else:
-            _chk_dev(out, (B, 3, H, W), "out", self.device)
-            assert out.is_contiguous()
+        out = _out_or_new(out, "out", (B, 3, H, W), self._tdev)
         valid = (C.c_uint8 * B)()
         self._check(self.lib.rvdd_video_push(self.h, _ptr(t), dtype, lay, int(bit_depth), c, _ptr(out), valid, self._stream()),
                     "rvdd_video_push")
@@ -802,16 +759,16 @@ class RvddRuntime:
     def set_state(self, lastden=None, lastfeat=None):
         B, H, W = self.B, self.H, self.W
         if lastden is not None:
-            lastden = _chk_dev(lastden, (B, 3, H, W), "lastden", self.device)
+            lastden = _dev_tensor(lastden, "lastden", self.device, shape=(B, 3, H, W))
         if lastfeat is not None:
-            lastfeat = _chk_dev(lastfeat, (B, 48, H, W), "lastfeat", self.device)
+            lastfeat = _dev_tensor(lastfeat, "lastfeat", self.device, shape=(B, 48, H, W))
         self._check(self.lib.rvdd_set_state(self.h, _ptr(lastden), _ptr(lastfeat), self._stream()),
                     "rvdd_set_state")
 
     def psnr_l1(self, den: torch.Tensor, gt: torch.Tensor) -> Tuple[float, float]:
         """-> (L1*100, PSNR) as compute_losses (models/recurrent_model.py:512-525)."""
-        den = _chk_dev(den, den.shape, "den", self.device)
-        gt = _chk_dev(gt, den.shape, "gt", self.device)
+        den = _dev_tensor(den, "den", self.device)
+        gt = _dev_tensor(gt, "gt", self.device, shape=den.shape)
         out = (C.c_float * 2)()
         self._check(self.lib.rvdd_psnr_l1(self.h, _ptr(den), _ptr(gt), den.numel(), out, self._stream()),
                     "rvdd_psnr_l1")
@@ -820,8 +777,8 @@ class RvddRuntime:
     def psnr_l1_batch(self, den: torch.Tensor, gt: torch.Tensor) -> List[Tuple[float, float]]:
         """psnr_l1 of every sequence of a batch ([n, ...] each), one synchronisation: [(L1*100, PSNR)] * n, each pair
         bit for bit what psnr_l1 gives for that sequence alone."""
-        den = _chk_dev(den, den.shape, "den", self.device)
-        gt = _chk_dev(gt, den.shape, "gt", self.device)
+        den = _dev_tensor(den, "den", self.device)
+        gt = _dev_tensor(gt, "gt", self.device, shape=den.shape)
         n = den.shape[0] if den.dim() else 1
         if n == 0:
             return []
@@ -833,9 +790,9 @@ class RvddRuntime:
     # -- single ops -----------------------------------------------------------
     def unet_forward(self, x, feat_in=None):
         B, H, W = self.B, self.H, self.W
-        x = _chk_dev(x, (B, 3 * (2 + self.future), H, W), "x", self.device)
+        x = _dev_tensor(x, "x", self.device, shape=(B, 3 * (2 + self.future), H, W))
         if feat_in is not None:
-            feat_in = _chk_dev(feat_in, (B, 48, H, W), "feat_in", self.device)
+            feat_in = _dev_tensor(feat_in, "feat_in", self.device, shape=(B, 48, H, W))
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=self._tdev)
         fo = torch.empty(B, 48, H, W, dtype=torch.float32, device=self._tdev) if self.feat else None
         self._check(self.lib.rvdd_unet_forward(self.h, _ptr(x), _ptr(feat_in), _ptr(out), _ptr(fo),
@@ -844,21 +801,20 @@ class RvddRuntime:
 
     def demosaic(self, raw: torch.Tensor, pattern: str = "gbrg") -> torch.Tensor:
         """HamiltonAdam(pattern)(raw): [n,4k,h,w] packed raw -> [n,3k,2h,2w] (pattern: one of BAYER_PATTERNS)."""
-        if pattern not in BAYER_PATTERNS:
-            raise ValueError(f"demosaic: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
+        pat = _pattern_index(pattern, "demosaic")
         n, c, h, w = raw.shape
-        raw = _chk_dev(raw, raw.shape, "raw", self.device)
+        raw = _dev_tensor(raw, "raw", self.device)
         assert c % 4 == 0
         k = n * (c // 4)
         out = torch.empty(n, 3 * (c // 4), 2 * h, 2 * w, dtype=torch.float32, device=raw.device)
-        self._check(self.lib.rvdd_demosaic_ha_bayer(self.h, _ptr(raw), k, h, w, BAYER_PATTERNS.index(pattern), _ptr(out),
+        self._check(self.lib.rvdd_demosaic_ha_bayer(self.h, _ptr(raw), k, h, w, pat, _ptr(out),
                                                     self._stream()), "rvdd_demosaic_ha_bayer")
         return out
 
     def warp(self, x: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
         n, c, H, W = x.shape
-        x = _chk_dev(x, x.shape, "x", self.device)
-        flow = _chk_dev(flow, (n, 2, H, W), "flow", self.device)
+        x = _dev_tensor(x, "x", self.device)
+        flow = _dev_tensor(flow, "flow", self.device, shape=(n, 2, H, W))
         y = torch.empty_like(x)
         self._check(self.lib.rvdd_warp_bicubic(self.h, _ptr(x), _ptr(flow), n, c, H, W, _ptr(y),
                                                self._stream()), "rvdd_warp_bicubic")
@@ -866,7 +822,7 @@ class RvddRuntime:
 
     def upsample_factor_2(self, t: torch.Tensor, multiply_by: float = 1.0) -> torch.Tensor:
         *rem, c, h, w = t.shape
-        t = _chk_dev(t, t.shape, "t", self.device)
+        t = _dev_tensor(t, "t", self.device)
         n = 1
         for r in rem:
             n *= r
@@ -878,8 +834,8 @@ class RvddRuntime:
     def tvl1flow(self, I0: torch.Tensor, I1: torch.Tensor, want_iterations: bool = False):
         """[ny,nx] x2 -> flow [2,ny,nx] (libBridge tvl1flow, libBridge.cpp:44)."""
         ny, nx = I0.shape
-        I0 = _chk_dev(I0, (ny, nx), "I0", self.device)
-        I1 = _chk_dev(I1, (ny, nx), "I1", self.device)
+        I0 = _dev_tensor(I0, "I0", self.device, shape=(ny, nx))
+        I1 = _dev_tensor(I1, "I1", self.device, shape=(ny, nx))
         u = torch.empty(2, ny, nx, dtype=torch.float32, device=I0.device)
         it = C.c_int32(0)
         self._check(self.lib.rvdd_tvl1flow(self.h, _ptr(I0), _ptr(I1), _ptr(u), nx, ny,
@@ -889,8 +845,8 @@ class RvddRuntime:
     def tvl1flow_batch(self, I0: torch.Tensor, I1: torch.Tensor, want_iterations: bool = False):
         """[n,ny,nx] x2 -> flows [n,2,ny,nx]: n independent pairs, two per cooperative launch."""
         n, ny, nx = I0.shape
-        I0 = _chk_dev(I0, (n, ny, nx), "I0", self.device)
-        I1 = _chk_dev(I1, (n, ny, nx), "I1", self.device)
+        I0 = _dev_tensor(I0, "I0", self.device, shape=(n, ny, nx))
+        I1 = _dev_tensor(I1, "I1", self.device, shape=(n, ny, nx))
         u = torch.empty(n, 2, ny, nx, dtype=torch.float32, device=I0.device)
         it = (C.c_int32 * max(n, 1))()
         self._check(self.lib.rvdd_tvl1flow_batch(self.h, _ptr(I0), _ptr(I1), _ptr(u), n, nx, ny,
@@ -901,10 +857,8 @@ class RvddRuntime:
               bit_depth: int, layout: str = "nchw", want_float: bool = False):
         """dataset/fwd_ppipe.py:48-77,131-141.  img [n,3,H,W] ("nchw") or [n,H,W,3] ("hwc"), any strides.
         -> uint8 [n,H,W,3] (and the float32 sRGB x 255 image before rounding)."""
-        if not img.is_cuda or img.dtype != torch.float32 or img.dim() != 4:
-            raise RuntimeError("ppipe: img must be a 4-D float32 GPU tensor (rvdd has no CPU path)")
-        if img.device.index != self.device:
-            raise RuntimeError(f"ppipe: img lives on cuda:{img.device.index} but this runtime drives cuda:{self.device}")
+        _dev_tensor(img, "ppipe: img", self.device, shape=(None,) * 4, contiguous=None,
+                    form="ppipe: img must be a 4-D float32 GPU tensor (rvdd has no CPU path)")
         if layout == "nchw":
             n, c, H, W = img.shape
             sn, sc, sy, sx = img.stride()
@@ -925,13 +879,6 @@ class RvddRuntime:
     # -- raw datasets from sRGB video -------------------------------------------
     UNPROCESS_OUTPUTS = ("lin_f32", "lin_u16", "gt_raw", "noisy")
 
-    def _unprocess_plane(self, t, shape, name):
-        if t is None:
-            return None
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"unprocess: {name} must be a GPU tensor (rvdd has no CPU path)")
-        return _chk_dev(t, shape, name, self.device)
-
     def unprocess(self, srgb: torch.Tensor, rgb_gain: float, red_gain: float, blue_gain: float, iso: int,
                   pattern: str = "gbrg", dither: Optional[torch.Tensor] = None, normal: Optional[torch.Tensor] = None,
                   seed: int = 0, frame0: int = 0, want=UNPROCESS_OUTPUTS) -> Dict[str, torch.Tensor]:
@@ -940,30 +887,26 @@ class RvddRuntime:
         lin_u16 [n,H,W,3] uint16, gt_raw and noisy [n,H/2,W/2,4] float32 in `pattern` (one of BAYER_PATTERNS), the packed HWC
         layout `ingest_raw` / `video_push` read.  dither [n,H,W,3] / normal [n,H/2,W/2,4]: the random planes; where None the
         kernel draws them from (seed, frame0 + i) for image i (`unprocess_draws` gives the same planes)."""
-        if pattern not in BAYER_PATTERNS:
-            raise ValueError(f"unprocess: pattern {pattern!r} is not one of {', '.join(BAYER_PATTERNS)}")
+        pat = _pattern_index(pattern, "unprocess")
         unknown = [w for w in want if w not in self.UNPROCESS_OUTPUTS]
         if unknown:
             raise ValueError(f"unprocess: unknown outputs {unknown}; known: {', '.join(self.UNPROCESS_OUTPUTS)}")
-        if not torch.is_tensor(srgb) or not srgb.is_cuda:
-            raise RuntimeError("unprocess: srgb must be a GPU tensor (rvdd has no CPU path)")
-        if srgb.device.index != self.device:
-            raise RuntimeError(f"unprocess: srgb lives on cuda:{srgb.device.index} but this runtime drives cuda:{self.device}")
-        if srgb.dtype != torch.uint8 or srgb.dim() != 4 or srgb.shape[3] != 3:
-            raise RuntimeError(f"unprocess: srgb is uint8 [n,H,W,3], got {srgb.dtype} {tuple(srgb.shape)}")
+        srgb = _dev_tensor(srgb, "unprocess: srgb", self.device, dtype=torch.uint8, shape=(None, None, None, 3),
+                           form="unprocess: srgb is uint8 [n,H,W,3]")
         n, H, W, _ = srgb.shape
         if H % 2 or W % 2:
             raise RuntimeError(f"unprocess: H and W must be even (crop the frame as the reference does), got {H} x {W}")
-        srgb = srgb if srgb.is_contiguous() else srgb.contiguous()
-        dither = self._unprocess_plane(dither, (n, H, W, 3), "dither")
-        normal = self._unprocess_plane(normal, (n, H // 2, W // 2, 4), "normal")
+        if dither is not None:
+            dither = _dev_tensor(dither, "dither", self.device, shape=(n, H, W, 3))
+        if normal is not None:
+            normal = _dev_tensor(normal, "normal", self.device, shape=(n, H // 2, W // 2, 4))
         out = {}
         for name, shape, dt in (("lin_f32", (n, H, W, 3), torch.float32), ("lin_u16", (n, H, W, 3), torch.uint16),
                                 ("gt_raw", (n, H // 2, W // 2, 4), torch.float32), ("noisy", (n, H // 2, W // 2, 4), torch.float32)):
             if name in want:
                 out[name] = torch.empty(shape, dtype=dt, device=self._tdev)
         self._check(self.lib.rvdd_unprocess(self.h, _ptr(srgb), n, H, W, float(rgb_gain), float(red_gain), float(blue_gain), int(iso),
-                                            BAYER_PATTERNS.index(pattern), _ptr(dither), _ptr(normal), int(seed) & (2 ** 64 - 1),
+                                            pat, _ptr(dither), _ptr(normal), int(seed) & (2 ** 64 - 1),
                                             int(frame0), _ptr(out.get("lin_f32")), _ptr(out.get("lin_u16")), _ptr(out.get("gt_raw")),
                                             _ptr(out.get("noisy")), self._stream()), "rvdd_unprocess")
         return out
@@ -984,12 +927,8 @@ class RvddRuntime:
         """dataset/fwd_ppipe.py:79-86 on uint8 [n,H,W,3] images -> (psnr[n], ssim[n]) Python floats."""
         if a.shape != b.shape:
             raise RuntimeError(f"srgb_metrics: shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
-        if not (a.is_cuda and b.is_cuda) or a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 4 \
-                or a.shape[3] != 3:
-            raise RuntimeError("srgb_metrics: a, b must be uint8 GPU tensors [n,H,W,3]")
-        if a.device.index != self.device or b.device.index != self.device:
-            raise RuntimeError(f"srgb_metrics: a, b must live on cuda:{self.device}, the device this runtime drives")
-        a, b = a.contiguous(), b.contiguous()
+        a, b = (_dev_tensor(t, f"srgb_metrics: {name}", self.device, dtype=torch.uint8, shape=(None, None, None, 3),
+                            form="srgb_metrics: a, b must be uint8 GPU tensors [n,H,W,3]") for t, name in ((a, "a"), (b, "b")))
         n, H, W, _ = a.shape
         ps, ss = (C.c_double * n)(), (C.c_double * n)()
         self._check(self.lib.rvdd_srgb_metrics(self.h, _ptr(a), _ptr(b), n, H, W, ps, ss, self._stream()),

@@ -111,6 +111,38 @@ def test_ingest_bits_ramp_through_every_value(order, bits):
     _check_ingest(rt, np.ascontiguousarray(x[:, :, :36]), bits, order)      # ww = 18: the byte form
 
 
+def test_footage_ingest_frames_is_the_direct_ingest():
+    """`footage.ingest_frames` -- the host-frames-to-packed/gray branch of noise, cuts and dpc_map -- against `ingest_raw` /
+    `ingest_bits` called directly, bit for bit: two 32 x 48 frames as a uint16 mosaic, as float32 packed_hwc, as a 10-bit msb and a
+    12-bit mipi container, through a stub dataset that carries `container` and `layout` and nothing else."""
+    import types
+    from rvdd_release_amd import footage
+    from rvdd_release_amd.runtime import raw_frames_to_device
+    rt = _rt()
+    cases = []
+    for bits, container in ((12, None), (10, "msb"), (12, "mipi")):
+        x = _frames("random", 2, 16, 24, bits, 7 + bits)
+        if container is None:
+            hwc = np.stack([x[:, k >> 1::2, k & 1::2] for k in range(4)], axis=-1).astype(np.float32)
+            cases.append((bits, "mosaic", None, x, rt.ingest_raw(raw_frames_to_device(x, "cuda"), bits, "mosaic")))
+            cases.append((bits, "packed_hwc", None, hwc, rt.ingest_raw(_dev(hwc), bits, "packed_hwc")))
+            assert all(torch.equal(a, b) for a, b in zip(cases[0][4], cases[1][4]))      # the same frames: the same planes
+        else:
+            rows = bits_ref.pack(x, bits, container)
+            assert rows.shape == (2, 32, 48 * bits // 8) and rows.dtype == np.uint8
+            cases.append((bits, "mosaic", container, rows, rt.ingest_bits(_dev(rows), container, bits, 16, 24, n=2)))
+            assert all(torch.equal(a, b) for a, b in zip(cases[-1][4], rt.ingest_raw(to_gpu(x), bits, "mosaic")))
+    for bits, layout, container, frames, (want_p, want_g) in cases:
+        ds = types.SimpleNamespace(container=container, layout=layout)
+        assert want_p.shape == (2, 4, 16, 24) and want_g.shape == (2, 16, 24)
+        got_p, got_g = footage.ingest_frames(rt, ds, frames, bits)
+        assert torch.equal(got_p, want_p) and torch.equal(got_g, want_g), (bits, layout, container)
+        only_p = footage.ingest_frames(rt, ds, frames, bits, want_gray=False)
+        only_g = footage.ingest_frames(rt, ds, frames, bits, want_packed=False)
+        assert only_p[1] is None and torch.equal(only_p[0], want_p) and only_g[0] is None and torch.equal(only_g[1], want_g)
+        assert footage.ingest_frames(rt, ds, frames, bits, want_packed=False, want_gray=False) == (None, None)
+
+
 # ---- 2. egress -------------------------------------------------------------------------------------------------------------------
 # (32,32): the dword form; (18,36): the byte form (W/2 = 18; 45-byte rows at 10 bits); (10,14): an odd ww
 @pytest.mark.parametrize("H,W", [(32, 32), (18, 36), (10, 14)])
