@@ -1,5 +1,5 @@
-"""numpy restatement of rvdd_gray_of_rgb (include/rvdd.h), one f32 operation at a time, and the composition of existing entry
-points that rvdd_video_push with option "stream_flow_from_denoised" must equal.  Beside stream_ref.py."""
+"""numpy restatement of rvdd_gray_of_rgb (include/rvdd.h), one f32 operation at a time.  Beside stream_ref.py; what rvdd_video_push
+with option "stream_flow_from_denoised" must equal is stream_compose.compose(from_denoised=True)."""
 import numpy as np
 
 PATTERNS = ("gbrg", "grbg", "rggb", "bggr")          # enum rvdd_bayer, in order
@@ -18,22 +18,3 @@ def gray_of_rgb_ref(rgb, pattern, bit_depth):
     assert gray.dtype == np.float32
     return np.ascontiguousarray(gray)
 
-
-def compose_from_denoised(rt, video, future, no_warp=False, reset_each=False, bit_depth=12):
-    """The outputs of a video (uint16 mosaics [T,H,W]) through the entry points of a batch-1 handle: ingest_raw, then per output
-    frame c the flow towards the previous frame as tvl1flow_batch(gray_c, gray_prev) for the first output and
-    tvl1flow_batch(gray_c, gray_of_rgb(previous output)) for every later one, the flow towards the next frame always noisy
-    against noisy, reset() on the first step (on every step: reset_each), step().  -> [denoised centre frames 1 .. T-1-future]"""
-    from stream_ref import to_gpu
-    T = video.shape[0]
-    pg = [rt.ingest_raw(to_gpu(video[t:t + 1]), bit_depth, "mosaic") for t in range(T)]
-    outs = []
-    for c in range(1, T - future):
-        fp = fn = None
-        if not no_warp:
-            fp = rt.tvl1flow_batch(pg[c][1], pg[c - 1][1] if c == 1 else rt.gray_of_rgb(outs[-1], bit_depth))
-            fn = rt.tvl1flow_batch(pg[c][1], pg[c + 1][1]) if future else None
-        if c == 1 or reset_each:
-            rt.reset()
-        outs.append(rt.step(pg[c - 1][0], pg[c][0], pg[c + 1][0] if future else None, fp, fn).clone())
-    return outs

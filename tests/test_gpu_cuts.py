@@ -12,27 +12,12 @@ import bits_ref
 import cuts_ref as R
 import dpc_ref
 from conftest import WEIGHTS
+from gpu_support import ops_rt as _rt, upload
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 KINDS = ("integer", "fractions", "outside", "flat")
-
-
-def _rt():
-    from rvdd_release_amd.util._ops import ops_runtime
-    return ops_runtime(0)
-
-
-def _offset(a):
-    """the array on the device, starting 4 bytes behind a 16-byte boundary"""
-    a = np.ascontiguousarray(a)
-    t = torch.empty(a.size + 1, dtype=torch.from_numpy(a).dtype, device="cuda")
-    assert t.data_ptr() % 16 == 0
-    v = t[1:].view(a.shape)
-    v.copy_(torch.from_numpy(a))
-    assert v.data_ptr() % 16 == 4
-    return v
 
 
 def _frames(hh, ww, bits, seed):
@@ -51,7 +36,7 @@ def _frames(hh, ww, bits, seed):
 
 
 def _sigs(gray, bits, offset=False, out=None):
-    g = _offset(gray) if offset else torch.from_numpy(np.ascontiguousarray(gray)).cuda()
+    g = upload(gray, offset=offset)
     assert g.data_ptr() % 16 == (4 if offset else 0)
     sig = _rt().frame_sigs(g, bits, out)
     torch.cuda.synchronize()

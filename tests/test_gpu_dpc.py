@@ -7,11 +7,10 @@ import numpy as np
 import pytest
 import torch
 
-import bits_ref
 import dpc_ref as R
-from conftest import load_weights
-from stream_ref import cells_of, to_gpu
-from test_gpu_stream import FIRST, IDLE, NEXT, _video
+from gpu_support import bits_of as _bits, dpc_rule as _cfg, ops_rt as _rt, same as _same, upload
+from stream_compose import compose, push_two_slots as _push_all, small_runtime as _runtime, small_videos as _videos
+from stream_ref import cells_of
 
 pytestmark = pytest.mark.gpu
 
@@ -19,33 +18,8 @@ SHAPES = [(1, 2, 2), (1, 3, 5), (3, 16, 20), (2, 18, 17), (1, 16, 24)]
 CLASSES = {"corner", "edge", "pair", "marginal", "batch", "plane0", "plane1", "plane2", "plane3"}
 
 
-def _rt():
-    from rvdd_release_amd.util._ops import ops_runtime
-    return ops_runtime(0)
-
-
-def _cfg(k_hot, k_dead, a, b, floor=1.0):
-    from rvdd_release_amd.runtime import dpc_cfg
-    return dpc_cfg(k_hot, k_dead, a, b, floor)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint32)
-
-
-def _offset(a, dev="cuda"):
-    """the array on the device, starting 4 bytes behind a 16-byte boundary"""
-    a = np.ascontiguousarray(a)
-    t = torch.empty(a.size + 1, dtype=torch.from_numpy(a).dtype, device=dev)
-    assert t.data_ptr() % 16 == 0
-    v = t[1:].view(a.shape)
-    v.copy_(torch.from_numpy(a))
-    assert v.data_ptr() % 16 == 4
-    return v
-
-
 def _run(rt, packed, gray, counts0, bits, cfg, offset=False):
-    up = _offset if offset else (lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda())
+    up = lambda a: upload(a, offset=offset)
     p, g, c = up(packed), up(gray), up(np.asarray(counts0, np.int32))
     out = up(np.zeros_like(packed))
     rt.dpc(p, cfg, bits, gray=g, counts=c, out=out)
@@ -173,95 +147,6 @@ def test_argument_errors_launch_nothing():
 
 
 # ---- 5 - 7. the stage inside the stream -------------------------------------------------------------------------------------
-H = W = 32                                                    # 16 x 16 cells: the least rvdd_video_push takes
-STEM = {0: "recurrent-convunet-iso3200", 1: "recurrent-convunet-future-iso3200"}
-
-
-def _runtime(future, B, **options):
-    from rvdd_release_amd.runtime import RvddRuntime
-    rt = RvddRuntime("convunet", future, B, H, W, 0)
-    rt.load_state_dict(load_weights(STEM[future]))
-    for k, v in options.items():
-        rt.set_option(k, v)
-    return rt
-
-
-def _videos(bits=12, defects=True):
-    """three videos of 5, 5 and 3 frames of 32 x 32 sites, uint16 mosaics of `bits` bits, with a hot and a dead sample per frame that
-    move from frame to frame (and stay clear of each other)"""
-    out = []
-    for v, T in enumerate((5, 5, 3)):
-        m = _video(T, H, W, seed=300 + v) >> (12 - bits)
-        if defects:
-            for t in range(T):
-                m[t, 2 * (3 + v) + (t & 1), 2 * (4 + t) + 1] = 2 ** bits - 1      # hot: plane 1 or 3, cell (3 + v, 4 + t)
-                m[t, 2 * 10 + 1, 2 * (2 + 2 * t)] = 0                               # dead: plane 2, cell (10, 2 + 2 t)
-                m[t, 0, 0] = 2 ** bits - 1                                          # hot in the frame's corner, plane 0
-        out.append(m)
-    return out
-
-
-def _schedule(videos):
-    """the pushes: per push one (ctl, video, frame) per slot.  Slot 0: video 0, one IDLE, video 2; slot 1: video 1, then IDLE."""
-    a, b, c = (len(v) for v in videos)
-    s = [[(FIRST if t == 0 else NEXT, 0, t), (FIRST if t == 0 else NEXT, 1, t)] for t in range(a)]
-    s.append([(IDLE, -1, -1), (IDLE, -1, -1)])
-    s += [[(FIRST if t == 0 else NEXT, 2, t), (IDLE, -1, -1)] for t in range(c)]
-    s.append([(IDLE, -1, -1), (IDLE, -1, -1)])
-    assert a == b
-    return s
-
-
-def _push_all(rt, videos, bits=12, container=None):
-    """-> {slot: [outputs in order]}"""
-    got = {0: [], 1: []}
-    for step in _schedule(videos):
-        if container is None:
-            batch = np.zeros((2, H, W), np.uint16)
-        else:
-            batch = np.zeros((2, H, bits_ref.row_bytes(W, bits, container)), np.uint8)
-        for s, (c, v, t) in enumerate(step):
-            if c != IDLE:
-                batch[s] = videos[v][t] if container is None else bits_ref.pack(videos[v][t], bits, container)
-        frames = to_gpu(batch) if container is None else torch.from_numpy(batch).cuda()
-        out, valid = rt.video_push(frames, [c for c, _, _ in step], bits, "mosaic", container=container)
-        for s in range(2):
-            if valid[s]:
-                got[s].append(out[s:s + 1].clone())
-    rt.set_option("tvl1_async", 0)                            # the deferred check of the pushes' flow batches: nothing gave up
-    return got
-
-
-def _compose(rt, video, future, all_frames, cfg, bits=12):
-    """The outputs of one video by hand, on a batch-1 handle without the stage: rvdd_ingest_raw -> rvdd_dpc (packed corrected, gray
-    patched) -> rvdd_tvl1flow_batch on the gray planes -> reset on the video's first steps -> step.  Without "stream_all_frames" the
-    centres 1 .. N-1-future; with it every frame: the head (c = 0) with itself as the previous frame and a zero flow, reset again at
-    c = 1, and with a future frame the tail (c = N - 1) with itself as the next frame and a zero flow."""
-    N = video.shape[0]
-    pg = []
-    for t in range(N):
-        p, g = rt.ingest_raw(to_gpu(video[t:t + 1]), bits, "mosaic")
-        pg.append((rt.dpc(p, cfg, bits, gray=g), g))
-    zeros = torch.zeros(1, 2, H // 2, W // 2, device="cuda")
-    outs = []
-    for c in (range(N) if all_frames else range(1, N - future)):
-        head, tail = c == 0, bool(future) and c == N - 1
-        prev = pg[c] if head else pg[c - 1]
-        nxt = (pg[c] if tail else pg[c + 1]) if future else None
-        fp = zeros if head else rt.tvl1flow_batch(pg[c][1], pg[c - 1][1])
-        fn = (zeros if tail else rt.tvl1flow_batch(pg[c][1], pg[c + 1][1])) if future else None
-        if c <= 1:
-            rt.reset()
-        outs.append(rt.step(prev[0], pg[c][0], nxt[0] if future else None, fp, fn).clone())
-    return outs
-
-
-def _same(got, want, what=""):
-    assert len(got) == len(want) and len(want) > 0, (what, len(got), len(want))
-    for k, (g, w) in enumerate(zip(got, want)):
-        assert torch.isfinite(g).all() and torch.equal(g, w), (what, k, float((g - w).abs().max()))
-
-
 @pytest.mark.parametrize("all_frames", [0, 1])
 @pytest.mark.parametrize("future", [0, 1])
 def test_stream_with_the_stage_is_the_composition(future, all_frames):
@@ -280,7 +165,7 @@ def test_stream_with_the_stage_is_the_composition(future, all_frames):
     got = _push_all(rt, videos)
     assert rt.dpc_counts() == [tuple(int(x) for x in totals[0] + totals[2]), tuple(int(x) for x in totals[1])]
     alone = _runtime(future, 1)
-    want = [_compose(alone, v, future, all_frames, cfg) for v in videos]
+    want = [compose(alone, v, future, all_frames=all_frames, dpc=cfg) for v in videos]
     _same(got[0], want[0] + want[2], "slot 0")
     _same(got[1], want[1], "slot 1")
     # the stage matters on these frames: the same pushes without it give other outputs

@@ -14,10 +14,14 @@ import torch
 
 import dpc_map_ref as M
 import dpc_ref as R
+from gpu_support import bits_of as _bits, dpc_rule as _cfg, files_of as _files, ops_rt as _rt, same as _same, upload as _up
+from stream_compose import SMALL, compose, push_two_slots as _push_all, small_runtime as _runtime
+from stream_compose import static_videos as _static_videos
 from stream_ref import to_gpu
-from test_gpu_dpc import H, W, _bits, _cfg, _offset, _push_all, _rt, _runtime, _same, _videos
 
 pytestmark = pytest.mark.gpu
+
+H = W = SMALL
 
 DETECT_SHAPES = [(1, 2, 2), (1, 3, 5), (3, 16, 20), (2, 18, 17), (1, 16, 24)]
 APPLY_SHAPES = [(1, 3, 3), (1, 3, 5), (3, 16, 20), (2, 18, 17), (1, 16, 24)]
@@ -35,13 +39,6 @@ def _hits0(hh, ww, seed):
     h[0, 0, 0] = 65534 | (65535 << 16)
     h[1, 0, ww - 1] = 2 | (65534 << 16)
     return h
-
-
-def _up(a, offset=False):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return _offset(a) if offset else torch.from_numpy(a).cuda()
 
 
 # ---- 1. detection -----------------------------------------------------------------------------------------------------------
@@ -227,50 +224,6 @@ def test_argument_errors_launch_nothing():
 
 
 # ---- 4. the stage inside the stream -----------------------------------------------------------------------------------------
-STATIC = [(0, 0, 0, "hot"), (1, 3, 4, "hot"), (2, 10, 2, "dead"), (0, 6, 6, "hot"), (0, 6, 7, "hot"), (3, 15, 15, "dead"), (3, 0, 9, "hot")]
-
-
-def _static_videos(bits=12):
-    """test_gpu_dpc's three videos without its moving defects, with the same static defects in every frame of every video: singles in
-    every plane, at a corner and on an edge, and an equal hot pair.  -> (videos, cellmask [16,16])"""
-    videos = _videos(bits=bits, defects=False)
-    mask = np.zeros((H // 2, W // 2), np.uint8)
-    for k, y, x, kind in STATIC:
-        mask[y, x] |= 1 << k
-        for m in videos:
-            m[:, 2 * y + (k >> 1), 2 * x + (k & 1)] = 2 ** bits - 1 if kind == "hot" else 0
-    return videos, mask
-
-
-def _compose(rt, video, future, all_frames, bits=12, dpc=None, match=None):
-    """The outputs of one video by hand on a batch-1 handle that HAS the map and no stage: rvdd_ingest_raw -> rvdd_dpc_map_apply
-    (packed and gray in place) -> (rvdd_dpc) -> (rvdd_match_raw) -> rvdd_tvl1flow_batch on the gray planes -> reset at c <= 1 -> step
-    (-> rvdd_unmatch_rgb); heads and tails of "stream_all_frames" as tests/test_gpu_dpc.py composes them."""
-    N = video.shape[0]
-    pg = []
-    for t in range(N):
-        p, g = rt.ingest_raw(to_gpu(video[t:t + 1]), bits, "mosaic")
-        rt.dpc_map_apply(p, bits, gray=g)
-        if dpc is not None:
-            p = rt.dpc(p, dpc, bits, gray=g)
-        if match is not None:
-            p = rt.match_raw(p, match)
-        pg.append((p, g))
-    zeros = torch.zeros(1, 2, H // 2, W // 2, device="cuda")
-    outs = []
-    for c in (range(N) if all_frames else range(1, N - future)):
-        head, tail = c == 0, bool(future) and c == N - 1
-        prev = pg[c] if head else pg[c - 1]
-        nxt = (pg[c] if tail else pg[c + 1]) if future else None
-        fp = zeros if head else rt.tvl1flow_batch(pg[c][1], pg[c - 1][1])
-        fn = (zeros if tail else rt.tvl1flow_batch(pg[c][1], pg[c + 1][1])) if future else None
-        if c <= 1:
-            rt.reset()
-        out = rt.step(prev[0], pg[c][0], nxt[0] if future else None, fp, fn)
-        outs.append(rt.unmatch_rgb(out, match) if match is not None else out.clone())
-    return outs
-
-
 @pytest.mark.parametrize("future,all_frames,stage", [(0, 0, "map"), (1, 1, "map+dpc"), (0, 1, "map+match")])
 def test_stream_with_the_map_is_the_composition(future, all_frames, stage):
     from rvdd_release_amd.runtime import match_cfg
@@ -285,7 +238,7 @@ def test_stream_with_the_map_is_the_composition(future, all_frames, stage):
     got = _push_all(rt, videos)
     alone = _runtime(future, 1)
     alone.set_dpc_map(mask)
-    want = [_compose(alone, v, future, all_frames, dpc=dpc, match=match) for v in videos]
+    want = [compose(alone, v, future, all_frames=all_frames, dmap=True, dpc=dpc, match=match) for v in videos]
     _same(got[0], want[0] + want[2], "slot 0")
     _same(got[1], want[1], "slot 1")
     if dpc is not None:
@@ -316,7 +269,7 @@ def test_map_on_mipi_raw10_is_the_map_on_the_unpacked_frames():
     got = _push_all(mipi, videos, bits=10, container="mipi")
     alone = _runtime(1, 1)
     alone.set_dpc_map(mask)
-    by_hand = [_compose(alone, v, 1, 1, bits=10) for v in videos]
+    by_hand = [compose(alone, v, 1, all_frames=True, dmap=True, bit_depth=10) for v in videos]
     for s in range(2):
         _same(got[s], want[s], s)
     _same(got[0], by_hand[0] + by_hand[2], "slot 0 by hand")
@@ -363,7 +316,6 @@ def tree(tmp_path_factory):
 def test_map_command_is_the_restatement_and_denoise_takes_its_file(tree, tmp_path, capsys):
     from conftest import WEIGHTS
     from rvdd_release_amd import denoise, dpc_map
-    from test_gpu_match import _files
     root, cells, truth = tree
     a, b = R.iso_curve(3200, 12)
     path = str(tmp_path / "map.tif")

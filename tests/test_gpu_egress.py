@@ -10,18 +10,13 @@ import torch
 
 from conftest import WEIGHTS
 from egress_ref import LAYOUTS, PATTERNS, col, egress_ref, fill, special_values
+from gpu_support import files_of, ops_rt as _rt, upload
 from stream_ref import mosaic_of, quantised_dn, to_gpu
-from test_gpu_stream import _tree
 
 pytestmark = pytest.mark.gpu
 
 U16 = getattr(torch, "uint16", torch.int16)
 DTYPES = ((U16, np.uint16), (torch.float32, np.float32))
-
-
-def _rt():
-    from rvdd_release_amd.util._ops import ops_runtime
-    return ops_runtime(0)
 
 
 def _host(t):
@@ -39,13 +34,6 @@ def _same(got, want):
         return np.array_equal(got, want)
     nan = np.isnan(want)
     return np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
-
-
-def _offset_view(t, fill_value):
-    """The same values one element into a larger allocation filled with `fill_value`: (view, whole allocation)."""
-    whole = torch.full((t.numel() + 8,), fill_value, dtype=t.dtype, device=t.device)
-    whole[1:1 + t.numel()] = t.reshape(-1)
-    return whole[1:1 + t.numel()].view(t.shape), whole
 
 
 def _patterns(layout):
@@ -83,7 +71,7 @@ def test_every_tie_and_special_value_in_every_form(n, H, W):
     assert n * H * W >= special_values().size
     x = fill(n, H, W, seed=H)
     dev = torch.from_numpy(x).cuda()
-    odd, _ = _offset_view(dev, 0.0)
+    odd = upload(dev, offset=True)
     assert odd.data_ptr() % 16 == 4
     for layout in LAYOUTS:
         for tdt, ndt in DTYPES:
@@ -145,7 +133,7 @@ def test_wide_equals_narrow_and_nothing_else_is_written(layout):
     rt = _rt()
     n, H, W = 2, 16, 32
     x = torch.from_numpy(fill(n, H, W, seed=5)).cuda()
-    x_odd, _ = _offset_view(x, 0.0)
+    x_odd = upload(x, offset=True)
     assert x.data_ptr() % 16 == 0 and x_odd.data_ptr() % 16 == 4
     for tdt, ndt in DTYPES:
         sentinel = 7.0 if tdt == torch.float32 else 0x5A5A
@@ -157,7 +145,7 @@ def test_wide_equals_narrow_and_nothing_else_is_written(layout):
             store = wide.view(torch.int16) if tdt != torch.float32 else wide          # (fills and copies of 16-bit words)
             for src in (x, x_odd):
                 # into a 16-byte aligned tensor (wide only with the aligned source) and into one that starts one element in
-                for out, whole in ((torch.full_like(store, sentinel), None), _offset_view(torch.full_like(store, sentinel), sentinel)):
+                for out, whole in ((torch.full_like(store, sentinel), None), upload(torch.full_like(store, sentinel), offset=store.element_size(), fill=sentinel)):
                     assert (out.data_ptr() % 16 == 0) == (whole is None)
                     got = rt.egress(src, layout, tdt, bit_depth, "grbg", out=out.view(tdt))
                     assert got.data_ptr() == out.data_ptr() and _same(_host(got), want), (ndt.__name__, bit_depth, whole is None)
@@ -249,7 +237,7 @@ def test_denoise_main_writes_sensor_formats(tmp_path, future):
     def run(fmt, dataroot=str(root), folder="noisy", extra=()):
         res = tmp_path / ("res_" + fmt + "_" + folder)
         stats = denoise.main(flags + ["--dataroot", dataroot, "--nFolder", folder, "--results_dir", str(res), "--out_format", fmt] + list(extra))
-        return res, _tree(str(res)), stats
+        return res, files_of(str(res)), stats
 
     res32, f32, stats = run("f32")
     stems = sorted(k[:-len("_denoised.tif")] for k in f32)

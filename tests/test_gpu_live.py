@@ -10,6 +10,8 @@ import pytest
 import torch
 
 from conftest import WEIGHTS, load_weights
+from formats_support import write_dataset
+from gpu_support import frames_of as _frames, launches as _launches, make_runtime, run_alone, step_frames as _step, synth_videos as _videos
 
 pytestmark = pytest.mark.gpu
 
@@ -33,42 +35,6 @@ CASES = {
 }
 
 RVDD_ERR_ARG = -1      # RVDD_ERR_STATE is -2: the wrapper's message carries "(-2)"
-
-
-def _videos(lengths, H, W, future, seed0=500):
-    from rvdd_release_amd import synth
-    return [synth.make_sequence(T + future, H, W, iso=3200, seed=seed0 + v, device="cuda") for v, T in enumerate(lengths)]
-
-
-def _runtime(arch, sd, future, B, H, W, opts):
-    from rvdd_release_amd.runtime import RvddRuntime
-    rt = RvddRuntime(arch, future, B, H, W, 0)
-    rt.load_state_dict(sd)
-    for k, v in opts.items():
-        rt.set_option(k, v)
-    return rt
-
-
-def _frames(seq, future):
-    return seq.raw.shape[0] - future
-
-
-def _step(rt, seqs, frame, future, live=None):
-    """One step over frame = [(video, t)] * n."""
-    st = lambda f: torch.stack([f(seqs[v], t) for v, t in frame])
-    return rt.step(st(lambda s, t: s.raw[t - 1]), st(lambda s, t: s.raw[t]), st(lambda s, t: s.raw[t + 1]) if future else None,
-                   st(lambda s, t: s.flow_prev[t]), st(lambda s, t: s.flow_next[t]) if future else None, live=live)
-
-
-def run_alone(arch, sd, future, seqs, H, W, opts):
-    """Each video on a batch-1 handle from rvdd_reset: -> per video, its output frames [T-1-f, 3, H, W]."""
-    rt = _runtime(arch, sd, future, 1, H, W, opts)
-    outs = []
-    for v, s in enumerate(seqs):
-        rt.reset()
-        outs.append(torch.cat([_step(rt, seqs, [(v, t)], future).clone() for t in range(1, _frames(s, future))]))
-    rt.close()
-    return outs
 
 
 def compact_plan(seqs, future, B):
@@ -118,7 +84,7 @@ def test_compact_plan_exact(case):
     sd = load_weights(stem)
     seqs = _videos(LENGTHS, H, W, future)
     want = run_alone(arch, sd, future, seqs, H, W, opts)
-    rt = _runtime(arch, sd, future, 4, H, W, opts)
+    rt = make_runtime(arch, sd, future, 4, H, W, **opts)
     got, pack = run_compact(rt, seqs, future)
     rt.close()
     # the plan does exercise what the test is about: refills, moves, every live count from 4 down to 1
@@ -134,16 +100,12 @@ def test_compact_tail_exact_720p_b8():
     lengths = [3, 6, 4, 8, 2, 5, 9, 7]
     seqs = _videos(lengths, H, W, 0, seed0=700)
     want = run_alone("convunet+feat", sd, 0, seqs, H, W, {})
-    rt = _runtime("convunet+feat", sd, 0, 8, H, W, {})
+    rt = make_runtime("convunet+feat", sd, 0, 8, H, W)
     got, pack = run_compact(rt, seqs, 0)
     rt.close()
     assert sorted({len(r) for r in pack}) == list(range(1, 9))
     assert sum(len(r.moves) for r in pack) >= 3
     _assert_videos_equal(got, want, "720p")
-
-
-def _launches(rt):
-    return {p["name"]: (p["launches"], p["bytes"]) for p in rt.profile_read() if p["launches"]}
 
 
 def test_full_width_is_step_strided():
@@ -152,7 +114,7 @@ def test_full_width_is_step_strided():
     seqs = _videos([6] * B, H, W, 0, seed0=300)
     seen = {}
     for tag, live in (("strided", None), ("live_full", B), ("live_part", n)):
-        rt = _runtime("convunet+feat", sd, 0, B, H, W, {})
+        rt = make_runtime("convunet+feat", sd, 0, B, H, W)
         rt.reset()
         outs = []
         for t in range(1, 5):
@@ -183,7 +145,7 @@ def test_move_semantics():
     sd = load_weights(stem)
     seqs = _videos([8, 8, 8, 4], H, W, 0, seed0=900)
     want = run_alone(arch, sd, 0, seqs, H, W, {})
-    rt = _runtime(arch, sd, 0, B, H, W, {})
+    rt = make_runtime(arch, sd, 0, B, H, W)
     rt.reset()
     for t in (1, 2, 3):
         _step(rt, seqs, [(0, t), (1, t), (2, t)], 0)
@@ -233,7 +195,7 @@ def test_move_keeps_the_sequence_in_every_set():
     seqs = _videos([8, 8], H, W, 0, seed0=950)
     want = run_alone(arch, sd, 0, seqs, H, W, {})
     for k in (1, 2, 3, 4):
-        rt = _runtime(arch, sd, 0, 2, H, W, {})
+        rt = make_runtime(arch, sd, 0, 2, H, W)
         rt.reset()
         for t in range(1, k + 1):
             _step(rt, seqs, [(0, t), (1, t)], 0)
@@ -250,7 +212,7 @@ def test_undefined_slots():
     sd = load_weights(stem)
     seqs = _videos([10, 10, 8, 5], H, W, 0, seed0=1100)
     want = run_alone(arch, sd, 0, seqs, H, W, {})
-    rt = _runtime(arch, sd, 0, B, H, W, {})
+    rt = make_runtime(arch, sd, 0, B, H, W)
     rt.reset()
     for t in (1, 2):
         _step(rt, seqs, [(0, t), (1, t), (2, t)], 0)
@@ -283,7 +245,6 @@ def test_undefined_slots():
 @pytest.mark.parametrize("online", [False, True], ids=["dataset_flow", "online_flow"])
 def test_compact_validation_on_disk(tmp_path, online):
     from rvdd_release_amd import synth, validate
-    from test_formats import write_dataset
     seqs = [synth.make_sequence(T, 64, 96, iso=3200, seed=80 + v) for v, T in enumerate([4, 2, 5, 3, 3])]
     root = tmp_path / "validation"
     write_dataset(str(root), seqs, iso=3200)

@@ -15,8 +15,9 @@ import dpc_ref
 import match_ref as R
 import noise_ref
 from conftest import WEIGHTS, load_weights
+from gpu_support import bits_of as _bits, files_of as _files, ops_rt as _rt, same as _same, upload as _up
+from stream_compose import compose, push_two_slots as _push_all, small_runtime as _runtime, small_videos as _videos
 from stream_ref import mosaic_of, to_gpu
-from test_gpu_dpc import H, W, _push_all, _runtime, _same, _videos      # _push_all walks test_gpu_dpc._schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -24,29 +25,9 @@ CAM60 = R.camera_curve(60.0, 256)                         # noisier than both ch
 CAM3 = R.camera_curve(3.0, 256)                           # cleaner: s = 2.67
 
 
-def _rt():
-    from rvdd_release_amd.util._ops import ops_runtime
-    return ops_runtime(0)
-
-
 def _coeffs(curve, iso=3200, bits=12):
     from rvdd_release_amd.runtime import match_coeffs
     return match_coeffs(curve[0], curve[1], bits, iso)[0]
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint32)
-
-
-def _up(a, offset):
-    """the array on the device: 16-byte aligned, or starting 4 bytes behind a 16-byte boundary"""
-    a = np.ascontiguousarray(a)
-    t = torch.empty(a.size + 4, dtype=torch.float32, device="cuda")
-    assert t.data_ptr() % 16 == 0
-    v = t[1:1 + a.size].view(a.shape) if offset else t[:a.size].view(a.shape)
-    v.copy_(torch.from_numpy(a))
-    assert v.data_ptr() % 16 == (4 if offset else 0)
-    return v
 
 
 def _samples(shape, seed):
@@ -162,33 +143,6 @@ def test_device_round_trip_returns_every_dn(bits, side):
 
 
 # ---- 3. the stage inside the stream ---------------------------------------------------------------------------------------------
-def _compose(rt, video, future, all_frames, cfg, bits=12, dpc=None, from_den=False):
-    """The outputs of one video by hand, on a batch-1 handle without the stage: rvdd_ingest_raw (-> rvdd_dpc) -> rvdd_match_raw on the
-    packed frames -> rvdd_tvl1flow_batch on the UN-MAPPED gray planes -> reset at c <= 1 -> step -> rvdd_unmatch_rgb.  Heads and tails
-    of "stream_all_frames" as tests/test_gpu_dpc.py composes them; from_den ("stream_flow_from_denoised", without all_frames): from the
-    second output on the flow towards the previous frame is matched against the gray plane of the previous un-mapped output."""
-    N = video.shape[0]
-    pg = []
-    for t in range(N):
-        p, g = rt.ingest_raw(to_gpu(video[t:t + 1]), bits, "mosaic")
-        if dpc is not None:
-            p = rt.dpc(p, dpc, bits, gray=g)
-        pg.append((rt.match_raw(p, cfg), g))
-    zeros = torch.zeros(1, 2, H // 2, W // 2, device="cuda")
-    outs = []
-    for c in (range(N) if all_frames else range(1, N - future)):
-        head, tail = c == 0, bool(future) and c == N - 1
-        prev = pg[c] if head else pg[c - 1]
-        nxt = (pg[c] if tail else pg[c + 1]) if future else None
-        prev_gray = rt.gray_of_rgb(outs[-1], bits) if from_den and c >= 2 else pg[c - 1][1]
-        fp = zeros if head else rt.tvl1flow_batch(pg[c][1], prev_gray)
-        fn = (zeros if tail else rt.tvl1flow_batch(pg[c][1], pg[c + 1][1])) if future else None
-        if c <= 1:
-            rt.reset()
-        outs.append(rt.unmatch_rgb(rt.step(prev[0], pg[c][0], nxt[0] if future else None, fp, fn), cfg))
-    return outs
-
-
 @pytest.mark.parametrize("all_frames", [0, 1])
 @pytest.mark.parametrize("future", [0, 1])
 def test_stream_with_the_stage_is_the_composition(future, all_frames):
@@ -198,7 +152,7 @@ def test_stream_with_the_stage_is_the_composition(future, all_frames):
     rt.set_match(cfg)
     got = _push_all(rt, videos)
     alone = _runtime(future, 1)
-    want = [_compose(alone, v, future, all_frames, cfg) for v in videos]
+    want = [compose(alone, v, future, all_frames=all_frames, match=cfg) for v in videos]
     _same(got[0], want[0] + want[2], "slot 0")
     _same(got[1], want[1], "slot 1")
     # the stage matters: the same pushes with it off give other outputs, those of a handle that never had it
@@ -217,11 +171,11 @@ def test_stage_with_flows_from_denoised():
     rt.set_match(cfg)
     got = _push_all(rt, videos)
     alone = _runtime(1, 1)
-    want = [_compose(alone, v, 1, 0, cfg, from_den=True) for v in videos]
+    want = [compose(alone, v, 1, match=cfg, from_denoised=True) for v in videos]
     _same(got[0], want[0] + want[2], "slot 0")
     _same(got[1], want[1], "slot 1")
     # the plane matters here: the composition on the noisy pairs gives other outputs from the second one on
-    noisy = _compose(alone, videos[0], 1, 0, cfg)
+    noisy = compose(alone, videos[0], 1, match=cfg)
     assert torch.equal(noisy[0], want[0][0]) and not torch.equal(noisy[1], want[0][1])
 
 
@@ -237,11 +191,11 @@ def test_stage_behind_the_correction():
     rt.set_match(cfg)
     got = _push_all(rt, videos)
     alone = _runtime(1, 1)
-    want = [_compose(alone, v, 1, 1, cfg, dpc=dpc) for v in videos]
+    want = [compose(alone, v, 1, all_frames=True, match=cfg, dpc=dpc) for v in videos]
     _same(got[0], want[0] + want[2], "slot 0")
     _same(got[1], want[1], "slot 1")
     assert all(h >= 10 and d >= 5 for h, d in rt.dpc_counts())
-    uncorrected = _compose(alone, videos[0], 1, 1, cfg)
+    uncorrected = compose(alone, videos[0], 1, all_frames=True, match=cfg)
     assert not torch.equal(uncorrected[0], want[0][0])
 
 
@@ -254,7 +208,7 @@ def test_stage_on_mipi_raw10_is_the_stage_on_the_unpacked_frames():
     mipi.set_match(cfg)
     got = _push_all(mipi, videos, bits=10, container="mipi")
     alone = _runtime(1, 1)
-    want = [_compose(alone, v, 1, 1, cfg, bits=10) for v in videos]
+    want = [compose(alone, v, 1, all_frames=True, match=cfg, bit_depth=10) for v in videos]
     _same(got[0], want[0] + want[2], "slot 0")
     _same(got[1], want[1], "slot 1")
 
@@ -286,15 +240,6 @@ def tree(tmp_path_factory):
         for t in range(T):
             tiffio.write(str(root / "u16" / ("%03d/%08d.tif" % (v, t))), m[t])
     return root
-
-
-def _files(res):
-    out = {}
-    for d, _, names in os.walk(res):
-        for name in names:
-            with open(os.path.join(d, name), "rb") as f:
-                out[os.path.relpath(os.path.join(d, name), res)] = f.read()
-    return out
 
 
 def test_denoise_auto_is_denoise_with_the_printed_numbers(tree, tmp_path, capsys, monkeypatch):

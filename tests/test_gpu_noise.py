@@ -13,26 +13,11 @@ import bits_ref
 import dpc_ref
 import noise_ref as R
 from conftest import WEIGHTS
+from gpu_support import files_of as _files, ops_rt as _rt, upload
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-
-
-def _rt():
-    from rvdd_release_amd.util._ops import ops_runtime
-    return ops_runtime(0)
-
-
-def _offset(a):
-    """the array on the device, starting 4 bytes behind a 16-byte boundary"""
-    a = np.ascontiguousarray(a)
-    t = torch.empty(a.size + 1, dtype=torch.from_numpy(a).dtype, device="cuda")
-    assert t.data_ptr() % 16 == 0
-    v = t[1:].view(a.shape)
-    v.copy_(torch.from_numpy(a))
-    assert v.data_ptr() % 16 == 4
-    return v
 
 
 def _arrays(acc):
@@ -48,7 +33,7 @@ def _same(got, want, what=""):
 
 
 def _hist(packed, bits, acc=None, offset=False):
-    p = _offset(packed) if offset else torch.from_numpy(np.ascontiguousarray(packed)).cuda()
+    p = upload(packed, offset=offset)
     if not offset:
         assert p.data_ptr() % 16 == 0
     acc = _rt().noise_hist(p, bits, acc)
@@ -233,15 +218,6 @@ def tree(tmp_path_factory):
             tiffio.write(str(root / "u16" / ("%03d/%08d.tif" % (v, t))), m[t])
             bits_ref.pack(m[t], 12, "mipi").tofile(str(root / "mipi" / ("%03d/%08d.raw" % (v, t))))
     return root, acc
-
-
-def _files(res):
-    out = {}
-    for d, _, names in os.walk(res):
-        for name in names:
-            with open(os.path.join(d, name), "rb") as f:
-                out[os.path.relpath(os.path.join(d, name), res)] = f.read()
-    return out
 
 
 def test_noise_command_reads_every_container_the_same(tree, capsys):

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import REPO, load_weights
-from test_gpu_live import _launches, _runtime, _step, _videos
+from gpu_support import launches as _launches, make_runtime, step_frames as _step, synth_videos as _videos
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +21,7 @@ def test_debug_bench_leaves_the_selection():
     seqs = _videos([3], H, W, 0, seed0=1500)
     frames = []
     for hook in (False, True):
-        rt = _runtime("convunet", sd, 0, 1, H, W, {"conv_kernel": 2})
+        rt = make_runtime("convunet", sd, 0, 1, H, W, conv_kernel=2)
         if hook:
             rt.debug_conv_bench(0, 1, 1)
         rt.reset()
@@ -45,7 +45,7 @@ def test_switches_are_per_handle():
     sd = load_weights("recurrent-convunet+feat-iso3200")
     seqs = _videos([T + 1], H, W, 0, seed0=1600)
 
-    alone = _runtime(arch, sd, 0, 1, H, W, {})
+    alone = make_runtime(arch, sd, 0, 1, H, W)
     alone.reset()
     want = [_step(alone, seqs, [(0, t)], 0).clone() for t in range(1, T + 1)]
     want_feat = alone.get_state()[1].clone()
@@ -53,11 +53,11 @@ def test_switches_are_per_handle():
 
     for b_first in (False, True):
         if b_first:
-            b = _runtime(arch, sd, 0, 1, H, W, {})
-            a = _runtime(arch, sd, 0, 1, H, W, off)
+            b = make_runtime(arch, sd, 0, 1, H, W)
+            a = make_runtime(arch, sd, 0, 1, H, W, **off)
         else:
-            a = _runtime(arch, sd, 0, 1, H, W, off)
-            b = _runtime(arch, sd, 0, 1, H, W, {})
+            a = make_runtime(arch, sd, 0, 1, H, W, **off)
+            b = make_runtime(arch, sd, 0, 1, H, W)
         a.reset()
         b.reset()
         for t in range(1, T + 1):
@@ -80,7 +80,7 @@ def test_every_option_round_trips():
     on = {"fuse_upsample", "next_split", "next_pipe", "next_pool", "next_projfuse", "block_fp", "fuse_pre", "pre5_cin8", "cout_split",
           "small_prestage"}                                   # default 1; every other option defaults to 0
     assert on <= set(documented)
-    rt = _runtime("convunet", load_weights("recurrent-convunet-iso3200"), 0, 1, 32, 48, {})
+    rt = make_runtime("convunet", load_weights("recurrent-convunet-iso3200"), 0, 1, 32, 48)
     lib, h = rt.lib, rt.h
     for name in documented:
         assert lib.rvdd_set_option(h, name.encode(), 1 if name in on else 0) == 0, (name, lib.rvdd_last_error(h).decode())

@@ -8,6 +8,8 @@ import pytest
 import torch
 
 from conftest import WEIGHTS, load_weights
+from formats_support import write_dataset
+from gpu_support import frames_of as _frames, make_runtime, parity_psnr, run_alone, synth_videos as _videos
 
 pytestmark = pytest.mark.gpu
 
@@ -27,44 +29,6 @@ CASES = {
     "feat-prev_noisy": ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"prev_noisy_frame": 1}),
     "feat-block_fp0": ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"block_fp": 0}),
 }
-
-
-def parity_psnr(a, b):
-    mse = float(((a.double() - b.double()) ** 2).mean())
-    return 200.0 if mse == 0 else 10 * math.log10(4.0 / mse)
-
-
-def _videos(lengths, H, W, future, seed0=500):
-    from rvdd_release_amd import synth
-    return [synth.make_sequence(T + future, H, W, iso=3200, seed=seed0 + v, device="cuda") for v, T in enumerate(lengths)]
-
-
-def _runtime(arch, sd, future, B, H, W, opts):
-    from rvdd_release_amd.runtime import RvddRuntime
-    rt = RvddRuntime(arch, future, B, H, W, 0)
-    rt.load_state_dict(sd)
-    for k, v in opts.items():
-        rt.set_option(k, v)
-    return rt
-
-
-def _frames(seq, future):
-    return seq.raw.shape[0] - future
-
-
-def run_alone(arch, sd, future, seqs, H, W, opts):
-    """Each video on a batch-1 handle from rvdd_reset: -> per video, its output frames [T-1-f, 3, H, W]."""
-    rt = _runtime(arch, sd, future, 1, H, W, opts)
-    outs = []
-    for s in seqs:
-        rt.reset()
-        fr = []
-        for t in range(1, _frames(s, future)):
-            fr.append(rt.step(s.raw[t - 1][None], s.raw[t][None], s.raw[t + 1][None] if future else None,
-                              s.flow_prev[t][None], s.flow_next[t][None] if future else None).clone())
-        outs.append(torch.cat(fr))
-    rt.close()
-    return outs
 
 
 def run_packed(rt, seqs, future):
@@ -115,7 +79,7 @@ def test_staggered_resets_exact(case):
     seqs = _videos(LENGTHS, H, W, future)
     want = run_alone(arch, sd, future, seqs, H, W, opts)
     for B in (2, 3):
-        rt = _runtime(arch, sd, future, B, H, W, opts)
+        rt = make_runtime(arch, sd, future, B, H, W, **opts)
         got, _ = run_packed(rt, seqs, future)
         rt.close()
         for v in range(len(seqs)):
@@ -131,7 +95,7 @@ def test_staggered_resets_exact_720p_b8():
     lengths = [3, 5, 2, 4, 3, 2, 6, 3, 4, 2, 3]
     seqs = _videos(lengths, H, W, 0, seed0=700)
     want = run_alone("convunet+feat", sd, 0, seqs, H, W, {})
-    rt = _runtime("convunet+feat", sd, 0, 8, H, W, {})
+    rt = make_runtime("convunet+feat", sd, 0, 8, H, W)
     got, started = run_packed(rt, seqs, 0)
     rt.close()
     assert any(s > 0 for s in started.values())
@@ -161,7 +125,7 @@ def test_mask_semantics():
     ts = [1, 2, 3, 4, 5, 6]
 
     def fresh():
-        rt = _runtime("convunet+feat", sd, 0, 3, H, W, {})
+        rt = make_runtime("convunet+feat", sd, 0, 3, H, W)
         rt.reset()
         return rt
 
@@ -214,7 +178,7 @@ def test_mask_semantics():
 def test_psnr_l1_batch_equals_single(size):
     H, W = size
     B = 4
-    rt = _runtime("convunet", load_weights("recurrent-convunet-iso3200"), 0, 1, 64, 64, {})
+    rt = make_runtime("convunet", load_weights("recurrent-convunet-iso3200"), 0, 1, 64, 64)
     g = torch.Generator(device="cuda").manual_seed(5)
     den = torch.rand(B, 3, H, W, device="cuda", generator=g) * 2 - 1
     gt = torch.rand(B, 3, H, W, device="cuda", generator=g) * 2 - 1
@@ -242,7 +206,7 @@ def test_oracle_anchor_after_mid_batch_reset():
     stem = "recurrent-convunet+feat-iso3200"
     sd = load_weights(stem)
     seqs = _videos([3, 6, 5], H, W, 0, seed0=1200)
-    rt = _runtime("convunet+feat", sd, 0, 2, H, W, {})
+    rt = make_runtime("convunet+feat", sd, 0, 2, H, W)
     got, started = run_packed(rt, seqs, 0)
     rt.close()
     assert started[2] > 0
@@ -256,7 +220,6 @@ def test_oracle_anchor_after_mid_batch_reset():
 @pytest.mark.parametrize("online", [False, True], ids=["dataset_flow", "online_flow"])
 def test_packed_validation_on_disk(tmp_path, online):
     from rvdd_release_amd import synth, validate
-    from test_formats import write_dataset
     seqs = [synth.make_sequence(T, 64, 96, iso=3200, seed=80 + v) for v, T in enumerate([4, 2, 5, 3, 3])]
     root = tmp_path / "validation"
     write_dataset(str(root), seqs, iso=3200)

@@ -7,7 +7,6 @@ Tolerances (fp32, the HIP kernels sum in a different order than oneDNN):
   U-Net forward, sequences      max-abs 1e-4, parity PSNR >= 100 dB,
                                 task PSNR within 0.01 dB (north-star bar)
 """
-import math
 import os
 
 import numpy as np
@@ -16,6 +15,7 @@ import torch
 
 import rvdd_oracle as O
 from conftest import GOLDEN, VARIANTS, WEIGHTS, load_weights
+from gpu_support import parity_psnr
 
 pytestmark = pytest.mark.gpu
 
@@ -29,11 +29,6 @@ BUILT = [n for n in sorted(VARIANTS) if not ARCH[n].startswith("next") or os.env
 
 def _npz(name):
     return {k: torch.from_numpy(v) for k, v in np.load(os.path.join(GOLDEN, name)).items()}
-
-
-def parity_psnr(a, b):
-    mse = float(((a.double() - b.double()) ** 2).mean())
-    return 200.0 if mse == 0 else 10 * math.log10(4.0 / mse)
 
 
 @pytest.fixture(params=["auto", "winograd", "f32"])

@@ -7,7 +7,6 @@ Bars: max-abs < 1e-4 on EVERY frame (the per-frame curve is in the assertion mes
 of the reference's / the oracle's on the same frame, L1 within 1e-3.
 """
 import json
-import math
 import os
 import socket
 import subprocess
@@ -18,15 +17,11 @@ import torch
 
 import rvdd_oracle as O
 from conftest import LONG, REPO, WEIGHTS, load_long, load_weights
+from gpu_support import parity_psnr
 
 pytestmark = pytest.mark.gpu
 
 NETSTR = {"convunet+feat": "convunet-mode=fixedfeatures+feat", "next+feat": "newunet-mode=feat"}
-
-
-def parity_psnr(a, b):
-    mse = float(((a.double() - b.double()) ** 2).mean())
-    return 200.0 if mse == 0 else 10 * math.log10(4.0 / mse)
 
 
 @pytest.mark.parametrize("name", sorted(LONG))

@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from conftest import load_weights
-from test_gpu_live import _launches, _runtime, _step, _videos
+from gpu_support import launches as _launches, make_runtime, step_frames as _step, synth_videos as _videos
 
 pytestmark = pytest.mark.gpu
 
@@ -24,12 +24,12 @@ def test_bare_forward_between_steps(arch, stem, future):
     xs = [(torch.rand(B, 3 * (2 + future), H, W, device="cuda", generator=g) * 2 - 1,
            torch.rand(B, 48, H, W, device="cuda", generator=g)) for _ in range(2)]
     # the forwards on a handle that never stepped
-    rt = _runtime(arch, sd, future, B, H, W, {})
+    rt = make_runtime(arch, sd, future, B, H, W)
     fwd_want = [tuple(t.clone() for t in rt.unet_forward(x, f)) for x, f in xs]
     rt.close()
 
     def run(forwards):
-        rt = _runtime(arch, sd, future, B, H, W, {})
+        rt = make_runtime(arch, sd, future, B, H, W)
         rt.reset()
         outs, fwd = [], []
         for t in range(1, 6):
@@ -58,7 +58,7 @@ def test_live_count_selects_the_kernel():
     seqs = _videos([4] * 5, H, W, 0, seed0=1400)
     seen = {}
     for tag, B, live in (("live4of5", 5, 4), ("full4", 4, None), ("full5", 5, None)):
-        rt = _runtime("convunet+feat", sd, 0, B, H, W, {"conv_kernel": 4})
+        rt = make_runtime("convunet+feat", sd, 0, B, H, W, conv_kernel=4)
         rt.reset()
         outs = []
         for t in (1, 2, 3):

@@ -7,36 +7,20 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import WEIGHTS, load_weights
+from conftest import WEIGHTS
+from gpu_support import files_of, make_runtime as _runtime, ops_rt, same
+from stream_compose import CASES, FIRST, IDLE, NEXT, compose, mid_stream_schedule, push_alone as _stream_alone, push_schedule
+from stream_compose import synth_video as _video
 from stream_ref import ingest_ref, mosaic_of, quantised_dn, to_gpu
 
 pytestmark = pytest.mark.gpu
-
-NEXT, FIRST, IDLE = 0, 1, 2
-
-
-def _runtime(arch, stem, future, B, H, W, **options):
-    from rvdd_release_amd.runtime import RvddRuntime
-    rt = RvddRuntime(arch, future, B, H, W, 0)
-    rt.load_state_dict(load_weights(stem))
-    for k, v in options.items():
-        rt.set_option(k, v)
-    return rt
-
-
-def _video(T, H, W, seed, iso=3200, device="cpu"):
-    """T whole-DN 12-bit frames as uint16 mosaics [T,H,W] (numpy)."""
-    from rvdd_release_amd import synth
-    s = synth.make_sequence(T, H, W, iso=iso, seed=seed, device=device)
-    return mosaic_of(quantised_dn(s.raw.cpu())).astype(np.uint16)
 
 
 # ---- 5. the ingest kernel ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("hh,ww", [(18, 26), (128, 128), (360, 640)])
 @pytest.mark.parametrize("bit_depth", [10, 12, 14])
 def test_ingest_raw_is_the_restatement(hh, ww, bit_depth):
-    from rvdd_release_amd.util._ops import ops_runtime
-    rt = ops_runtime(0)
+    rt = ops_rt()
     rng = np.random.default_rng(hh * 100 + bit_depth)
     top = 2 ** bit_depth - 1
     for n in (1, 8):
@@ -66,8 +50,7 @@ def test_ingest_raw_is_the_restatement(hh, ww, bit_depth):
 
 
 def test_ingest_raw_bad_arguments():
-    from rvdd_release_amd.util._ops import ops_runtime
-    rt = ops_runtime(0)
+    rt = ops_rt()
     f = torch.zeros(1, 32, 32, dtype=torch.int16, device="cuda")
     for bd in (0, 17, -1):
         with pytest.raises(RuntimeError, match=r"\(-1\).*bit_depth"):
@@ -82,44 +65,6 @@ def test_ingest_raw_bad_arguments():
 
 
 # ---- 6. the stream is the composition ------------------------------------------------------------------------------------
-def _compose(rt, video, future, no_warp=False, reset_each=False, bit_depth=12):
-    """The outputs of a video through the EXISTING entry points of a batch-1 handle: ingest_raw -> tvl1flow_batch(gray_centre,
-    gray_neighbour) -> reset() on the first step -> step(...).  -> [denoised centre frames 1 .. T-1-future]"""
-    T = video.shape[0]
-    pg = [rt.ingest_raw(to_gpu(video[t:t + 1]), bit_depth, "mosaic") for t in range(T)]
-    outs = []
-    for c in range(1, T - future):
-        fp = fn = None
-        if not no_warp:
-            fp = rt.tvl1flow_batch(pg[c][1], pg[c - 1][1])
-            fn = rt.tvl1flow_batch(pg[c][1], pg[c + 1][1]) if future else None
-        if c == 1 or reset_each:
-            rt.reset()
-        outs.append(rt.step(pg[c - 1][0], pg[c][0], pg[c + 1][0] if future else None, fp, fn).clone())
-    return outs
-
-
-def _stream_alone(rt, video, future, bit_depth=12):
-    """The same video pushed through a batch-1 handle.  -> (outputs, the valid flag of every push)"""
-    outs, flags = [], []
-    for t in range(video.shape[0]):
-        out, valid = rt.video_push(to_gpu(video[t:t + 1]), [FIRST if t == 0 else NEXT], bit_depth, "mosaic")
-        flags.append(valid[0])
-        if valid[0]:
-            outs.append(out.clone())
-    return outs, flags
-
-
-CASES = [
-    ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {}),
-    ("convunet+feat", "recurrent-convunet+feat-future-iso12800", 1, {}),
-    ("next+feat", "recurrent-ConvNeXtUnet+feat-future-iso3200", 1, {}),
-    ("convunet", "recurrent-convunet-iso3200", 0, {"no_warp": 1}),
-    ("convunet+feat", "recurrent-convunet+feat-iso3200", 0, {"bayer_pattern": 2}),
-    ("convunet", "non_recurrent-convunet-iso3200", 0, {"stream_reset_each": 1}),
-]
-
-
 @pytest.mark.parametrize("arch,stem,future,options", CASES, ids=[f"{c[1]}-{'-'.join(c[3]) or 'plain'}" for c in CASES])
 def test_stream_is_the_composition(arch, stem, future, options):
     H, W, T = 64, 96, 6
@@ -127,11 +72,10 @@ def test_stream_is_the_composition(arch, stem, future, options):
     a = _runtime(arch, stem, future, 1, H, W, **options)
     b = _runtime(arch, stem, future, 1, H, W, **{k: v for k, v in options.items() if k != "stream_reset_each"})
     got, flags = _stream_alone(a, video, future)
-    want = _compose(b, video, future, no_warp=bool(options.get("no_warp")), reset_each=bool(options.get("stream_reset_each")))
+    want = compose(b, video, future, no_warp=bool(options.get("no_warp")), reset_each=bool(options.get("stream_reset_each")))
     assert flags == [False] * (1 + future) + [True] * (T - 1 - future)
     assert len(got) == len(want) == T - 1 - future
-    for k, (g, w) in enumerate(zip(got, want)):
-        assert torch.isfinite(g).all() and torch.equal(g, w), (k, float((g - w).abs().max()))
+    same(got, want)
     a.set_option("tvl1_async", 0)            # the deferred check of the pushes' flow batches: nothing gave up
     if options.get("stream_reset_each"):
         # ... and the option matters: the same pushes without it carry the recurrence on, which is another output
@@ -149,24 +93,16 @@ def test_slots_are_independent(future):
     lengths = (6, 3, 7, 4, 4)
     videos = [_video(n, H, W, seed=40 + v) for v, n in enumerate(lengths)]
     rt = _runtime("convunet+feat", stem, future, B, H, W)
-    got = {v: [] for v in range(len(lengths))}
-    for step in deal_slots(lengths, B):
-        batch = np.zeros((B, H, W), np.uint16)
-        for b, (c, v, k) in enumerate(step):
-            if c != IDLE:
-                batch[b] = videos[v][k]
-        out, valid = rt.video_push(to_gpu(batch), [c for c, _, _ in step], 12, "mosaic")
-        for b, (c, v, k) in enumerate(step):
-            assert valid[b] == (c != IDLE and k >= 1 + future)
-            if valid[b]:
-                got[v].append(out[b:b + 1].clone())
+    steps = deal_slots(lengths, B)
+    pushed = push_schedule(rt, videos, steps)
+    for step, valid in zip(steps, pushed.flags):
+        assert valid == [c != IDLE and k >= 1 + future for c, _, k in step], step
     rt.set_option("tvl1_async", 0)
     alone = _runtime("convunet+feat", stem, future, 1, H, W)
     for v, n in enumerate(lengths):
         want, _ = _stream_alone(alone, videos[v], future)
-        assert len(got[v]) == len(want) == n - 1 - future
-        for k, (g, w) in enumerate(zip(got[v], want)):
-            assert torch.equal(g, w), (v, k, float((g - w).abs().max()))
+        assert len(want) == n - 1 - future
+        same(pushed.by_video[v], want, v)
 
 
 def test_slots_are_independent_720p_batch_8():
@@ -176,37 +112,17 @@ def test_slots_are_independent_720p_batch_8():
     videos = [_video(T, H, W, seed=50 + v, iso=12800, device="cuda") for v in range(B)]
     short = _video(3, H, W, seed=70, iso=12800, device="cuda")
     rt = _runtime("convunet+feat", stem, future, B, H, W)
-    got = {b: [] for b in range(B)}
-    for t in range(T + 3):
-        batch = np.zeros((B, H, W), np.uint16)
-        ctl = []
-        for b in range(B):
-            # slot 5 holds a video of three frames first, then starts its video of T frames mid-stream; the others idle at the end
-            k = t - 3 if b == 5 else t
-            if b == 5 and t < 3:
-                batch[b], c = short[t], (FIRST if t == 0 else NEXT)
-            elif k < T:
-                batch[b], c = videos[b][k], (FIRST if k == 0 else NEXT)
-            else:
-                c = IDLE
-            ctl.append(c)
-        out, valid = rt.video_push(to_gpu(batch), ctl, 12, "mosaic")
-        for b in range(B):
-            k = t - 3 if b == 5 else t
-            if b == 5 and t < 3:
-                assert valid[b] == (t == 2)
-            else:
-                assert valid[b] == (2 <= k < T)
-                if valid[b]:
-                    got[b].append(out[b:b + 1].clone())
+    steps = mid_stream_schedule(B, T)
+    pushed = push_schedule(rt, videos + [short], steps)
+    for step, valid in zip(steps, pushed.flags):
+        assert valid == [c != IDLE and k >= 2 for c, _, k in step], step
     rt.set_option("tvl1_async", 0)
     del rt
     alone = _runtime("convunet+feat", stem, future, 1, H, W)
     for b in (0, 5, 7):
         want, _ = _stream_alone(alone, videos[b], future)
-        assert len(got[b]) == len(want) == T - 2
-        for g, w in zip(got[b], want):
-            assert torch.equal(g, w), (b, float((g - w).abs().max()))
+        assert len(want) == T - 2
+        same(pushed.by_video[b], want, b)
 
 
 # ---- 8. ctl errors ---------------------------------------------------------------------------------------------------------
@@ -310,15 +226,10 @@ def _write_three_ways(root, cells_per_video):
             tiffio.write(os.path.join(dirs["noisy_mosaic"], code + ".tiff"), mosaic_of(cells[t:t + 1])[0].astype(np.uint16))
 
 
-def _tree(root):
-    return {os.path.relpath(os.path.join(d, f), root): open(os.path.join(d, f), "rb").read() for d, _, fs in os.walk(root) for f in fs}
-
-
 @pytest.mark.parametrize("future", [0, 1])
 def test_denoise_main_writes_what_validate_writes(tmp_path, future):
     from rvdd_release_amd import denoise, synth, validate
     from rvdd_release_amd.library import iio_read
-    from rvdd_release_amd.util._ops import ops_runtime
     H, W = 64, 96
     iso = 12800 if future else 3200
     name = "recurrent-convunet+feat-future-iso12800" if future else "recurrent-convunet+feat-iso3200"
@@ -332,7 +243,7 @@ def test_denoise_main_writes_what_validate_writes(tmp_path, future):
     validate.main(model_flags + ["--val_dataroot", root, "--nFolder", "noisy_f32", "--gt_linear_RGB_Folder", "gt_rgb", "--suffix", "t",
                                  "--checkpoints_dir", str(ck), "--val_videos", ",".join("%03d" % v for v in range(len(lengths)))])
     assert os.path.isdir(os.path.join(root, "flow"))                     # validate's --check_data pass computed the flow files
-    want = {k: b for k, b in _tree(str(ck / f"recurrent-{net}-warp-i3o3-t" / "val_visuals")).items() if k.endswith("_denoised.tif")}
+    want = {k: b for k, b in files_of(str(ck / f"recurrent-{net}-warp-i3o3-t" / "val_visuals")).items() if k.endswith("_denoised.tif")}
     assert len(want) == sum(n - 1 - future for n in lengths)
     for folder in ("noisy_f32", "noisy_u16x4", "noisy_mosaic"):
         for B in (1, 3):
@@ -340,7 +251,7 @@ def test_denoise_main_writes_what_validate_writes(tmp_path, future):
             srgb = folder == "noisy_mosaic" and B == 3
             stats = denoise.main(model_flags + ["--dataroot", root, "--nFolder", folder, "--results_dir", str(res), "--batch_size", str(B)]
                                  + (["--srgb", "%d,1.3,1.9,1.5" % iso] if srgb else []))
-            got = _tree(str(res))
+            got = files_of(str(res))
             tifs = {k: b for k, b in got.items() if k.endswith("_denoised.tif")}
             assert sorted(tifs) == sorted(want), (folder, B)
             assert all(tifs[k] == want[k] for k in want), (folder, B, [k for k in want if tifs[k] != want[k]])
@@ -350,7 +261,7 @@ def test_denoise_main_writes_what_validate_writes(tmp_path, future):
                 assert [k[:-len("_srgb.png")] for k in pngs] == sorted(k[:-len("_denoised.tif")] for k in want)
                 for k in pngs[:3]:
                     img = torch.from_numpy(iio_read(str(res / (k[:-len("_srgb.png")] + "_denoised.tif")))).cuda()
-                    u8 = ops_runtime(0).ppipe(img[None], 1 / 1.3, 1.9, 1.5, iso, 8, "hwc")
+                    u8 = ops_rt().ppipe(img[None], 1 / 1.3, 1.9, 1.5, iso, 8, "hwc")
                     assert np.array_equal(iio_read(str(res / k)), u8[0].cpu().numpy()), k
             else:
                 assert not any(k.endswith(".png") for k in got)

@@ -2,6 +2,7 @@
 (frame 0) and the tail (the last frame, with a future frame) against the existing entry points of a batch-1 handle that never
 saw the option, the head leaving no trace, short videos, slot independence, FIRST straight after a last frame, the option
 switched off, and the command line on disk.  Every comparison is exact."""
+import functools
 import os
 
 import numpy as np
@@ -9,9 +10,11 @@ import pytest
 import torch
 
 from conftest import WEIGHTS
+from gpu_support import files_of, make_runtime as _runtime, same as _same
+from stream_compose import CASES as STREAM_CASES
+from stream_compose import FIRST, IDLE, NEXT, compose, push_alone as _stream_alone, push_schedule
+from stream_compose import synth_video as _video
 from stream_ref import mosaic_of, quantised_dn, to_gpu
-from test_gpu_stream import CASES as STREAM_CASES
-from test_gpu_stream import FIRST, IDLE, NEXT, _runtime, _stream_alone, _tree, _video
 
 pytestmark = pytest.mark.gpu
 
@@ -20,55 +23,7 @@ ON = {"stream_all_frames": 1}
 FEAT = {0: "recurrent-convunet+feat-iso3200", 1: "recurrent-convunet+feat-future-iso12800"}
 
 
-def compose_all(rt, video, future, no_warp=False, reset_each=False, from_denoised=False, bit_depth=12):
-    """EVERY frame of a video (uint16 mosaics [N,H,W]) through the existing entry points of a batch-1 handle -- _compose of
-    test_gpu_stream.py and compose_from_denoised of stream_den_ref.py, extended by the head and the tail:
-      head (c = 0): reset(); step(p0, p0, p1 | None, zeros, tvl1(g0, g1) | None);
-      c = 1: reset() again, then the regular outputs as those two compose them (from_denoised: the flow towards the previous frame
-             against gray_of_rgb(previous output) from c = 2 on -- never against the head's output);
-      tail (c = N - 1, future frame): step(p[N-2], p[N-1], p[N-1], tvl1(g[N-1], g[N-2] | previous output), zeros), the state
-             carried on (reset only where c <= 1).  N = 1 with a future frame is head and tail in one step.
-    -> [N denoised frames]"""
-    N = video.shape[0]
-    pg = [rt.ingest_raw(to_gpu(video[t:t + 1]), bit_depth, "mosaic") for t in range(N)]
-    zeros = torch.zeros(1, 2, H // 2, W // 2, device="cuda")
-    outs = []
-    for c in range(N):
-        head, tail = c == 0, bool(future) and c == N - 1
-        prev = pg[c] if head else pg[c - 1]
-        nxt = (pg[c] if tail else pg[c + 1]) if future else None
-        fp = fn = None
-        if not no_warp:
-            if head:
-                fp = zeros
-            else:
-                fp = rt.tvl1flow_batch(pg[c][1], rt.gray_of_rgb(outs[-1], bit_depth) if from_denoised and c >= 2 else pg[c - 1][1])
-            if future:
-                fn = zeros if tail else rt.tvl1flow_batch(pg[c][1], pg[c + 1][1])
-        if c <= 1 or reset_each:
-            rt.reset()
-        outs.append(rt.step(prev[0], pg[c][0], nxt[0] if future else None, fp, fn).clone())
-    return outs
-
-
-def stream_all(rt, video, future, bit_depth=12, idle=True):
-    """A video pushed through a batch-1 handle: FIRST, NEXT ..., and with a future frame (and `idle`) one IDLE.
-    -> (outputs, the valid flag of every push)"""
-    N = video.shape[0]
-    outs, flags = [], []
-    for t in range(N + (1 if future and idle else 0)):
-        frame = to_gpu(video[min(t, N - 1):min(t, N - 1) + 1])      # an IDLE push's frame is not read
-        out, valid = rt.video_push(frame, [IDLE if t == N else FIRST if t == 0 else NEXT], bit_depth, "mosaic")
-        flags.append(valid[0])
-        if valid[0]:
-            outs.append(out.clone())
-    return outs, flags
-
-
-def _same(got, want, what=""):
-    assert len(got) == len(want), (what, len(got), len(want))
-    for k, (g, w) in enumerate(zip(got, want)):
-        assert torch.isfinite(g).all() and torch.equal(g, w), (what, k, float((g - w).abs().max()))
+stream_all = functools.partial(_stream_alone, idle=True)       # with a future frame one IDLE behind the video: the push that gives the tail
 
 
 # ---- 1. the composition ----------------------------------------------------------------------------------------------------
@@ -87,8 +42,8 @@ def test_all_frames_is_the_composition(arch, stem, future, options):
     a = _runtime(arch, stem, future, 1, H, W, **options, **ON)
     b = _runtime(arch, stem, future, 1, H, W, **{k: v for k, v in options.items() if k not in STREAM_ONLY})
     got, flags = stream_all(a, video, future)
-    want = compose_all(b, video, future, no_warp=bool(options.get("no_warp")), reset_each=bool(options.get("stream_reset_each")),
-                       from_denoised=bool(options.get("stream_flow_from_denoised")))
+    want = compose(b, video, future, all_frames=True, no_warp=bool(options.get("no_warp")), reset_each=bool(options.get("stream_reset_each")),
+                   from_denoised=bool(options.get("stream_flow_from_denoised")))
     assert flags == [False] * future + [True] * N
     assert len(got) == N
     _same(got, want)
@@ -121,7 +76,7 @@ def test_short_videos(N, future):
     b = _runtime("convunet+feat", FEAT[future], future, 1, H, W)
     got, flags = stream_all(a, video, future)
     assert flags == [False] * future + [True] * N and len(got) == N
-    _same(got, compose_all(b, video, future))
+    _same(got, compose(b, video, future, all_frames=True))
     # the slot is idle afterwards (with a future frame), as after any IDLE: NEXT is refused, FIRST starts a video
     if future:
         with pytest.raises(RuntimeError, match=r"\(-2\).*slot 0.*idle"):
@@ -139,18 +94,12 @@ def test_slots_are_independent(future):
     lengths = (6, 1, 7, 2, 4)
     videos = [_video(n, H, W, seed=160 + v) for v, n in enumerate(lengths)]
     rt = _runtime("convunet+feat", FEAT[future], future, B, H, W, **ON)
-    got = {v: [] for v in range(len(lengths))}
     steps = deal_slots(lengths, B, tail=future)
-    for step in steps:
-        batch = np.zeros((B, H, W), np.uint16)
-        for b, (c, v, k) in enumerate(step):
-            if c != IDLE:
-                batch[b] = videos[v][k]
-        out, valid = rt.video_push(to_gpu(batch), [c for c, _, _ in step], 12, "mosaic")
+    pushed = push_schedule(rt, videos, steps)
+    got = pushed.by_video
+    for step, valid in zip(steps, pushed.flags):
         for b, (c, v, k) in enumerate(step):
             assert valid[b] == (v >= 0 and k >= future), (step, b)
-            if valid[b]:
-                got[v].append(out[b:b + 1].clone())
     rt.set_option("tvl1_async", 0)
     # what the dealing is meant to exercise, said of the steps themselves
     kinds = [{"head" if k == future else "tail" if c == IDLE else "mid" for c, v, k in s if v >= 0 and k >= future} for s in steps]
@@ -257,7 +206,7 @@ def test_denoise_all_frames_on_disk(tmp_path, future):
     def run(name, dataroot, folder, *more):
         res = str(tmp_path / name)
         stats = denoise.main(flags + ["--dataroot", dataroot, "--nFolder", folder, "--results_dir", res] + list(more))
-        return stats, _tree(res)
+        return stats, files_of(res)
 
     stats, plain = run("plain", root, "noisy", "--batch_size", "3")
     assert stats["frames"] == len(inner) and sorted(plain) == [k + "_denoised.tif" for k in inner]

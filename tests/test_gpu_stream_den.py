@@ -9,9 +9,11 @@ import pytest
 import torch
 
 from conftest import WEIGHTS
-from stream_den_ref import PATTERNS, compose_from_denoised, gray_of_rgb_ref
+from gpu_support import files_of, make_runtime as _runtime, ops_rt, same, upload
+from stream_compose import FIRST, IDLE, NEXT, compose, mid_stream_schedule, push_alone as _stream_alone, push_schedule
+from stream_compose import synth_video as _video
+from stream_den_ref import PATTERNS, gray_of_rgb_ref
 from stream_ref import mosaic_of, quantised_dn, to_gpu
-from test_gpu_stream import FIRST, IDLE, NEXT, _runtime, _stream_alone, _tree, _video
 
 pytestmark = pytest.mark.gpu
 
@@ -21,15 +23,14 @@ ON = {"stream_flow_from_denoised": 1}
 # ---- 1. the op against its restatement -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("H,W", [(36, 52), (256, 256), (720, 1280)])
 def test_gray_of_rgb_is_the_restatement(H, W):
-    from rvdd_release_amd.util._ops import ops_runtime
-    rt = ops_runtime(0)
+    rt = ops_rt()
     rng = np.random.default_rng(H + W)
     for n in (1, 8):
         x = rng.uniform(-1.2, 1.2, size=(n, 3, H, W)).astype(np.float32)
         x[0, :, :2, :2], x[-1, :, -2:, -2:] = -1.0, 1.0
         dev = torch.from_numpy(x).cuda()
         # the same frames one float off a 16-byte boundary: the one-cell form
-        odd = torch.cat([torch.zeros(1, device="cuda"), dev.reshape(-1)])[1:].view(n, 3, H, W)
+        odd = upload(dev, offset=True)
         assert odd.data_ptr() % 16 == 4 and dev.data_ptr() % 16 == 0
         for pattern in PATTERNS:
             for bit_depth in (10, 12, 14):
@@ -51,8 +52,7 @@ def test_gray_of_rgb_pattern_defaults_to_the_handles():
 
 
 def test_gray_of_rgb_bad_arguments():
-    from rvdd_release_amd.util._ops import ops_runtime
-    rt = ops_runtime(0)
+    rt = ops_rt()
     x = torch.zeros(1, 3, 32, 32, device="cuda")
     g = torch.full((1, 16, 16), 7.0, device="cuda")
 
@@ -93,11 +93,10 @@ def test_stream_from_denoised_is_the_composition(arch, stem, future, options):
     a = _runtime(arch, stem, future, 1, H, W, **options, **ON)
     b = _runtime(arch, stem, future, 1, H, W, **{k: v for k, v in options.items() if k != "stream_reset_each"})
     got, flags = _stream_alone(a, video, future)
-    want = compose_from_denoised(b, video, future, no_warp=bool(options.get("no_warp")), reset_each=bool(options.get("stream_reset_each")))
+    want = compose(b, video, future, from_denoised=True, no_warp=bool(options.get("no_warp")), reset_each=bool(options.get("stream_reset_each")))
     assert flags == [False] * (1 + future) + [True] * (T - 1 - future)
     assert len(got) == len(want) == T - 1 - future
-    for k, (g, w) in enumerate(zip(got, want)):
-        assert torch.isfinite(g).all() and torch.equal(g, w), (k, float((g - w).abs().max()))
+    same(got, want)
     a.set_option("tvl1_async", 0)            # the deferred check of the pushes' flow batches: nothing gave up
     # against the same pushes with the option off: the first output keeps the noisy pair, the later ones do not
     off, _ = _stream_alone(_runtime(arch, stem, future, 1, H, W, **options), video, future)
@@ -142,25 +141,17 @@ def test_slots_are_independent_from_denoised(future):
     lengths = (6, 3, 7, 4, 4)
     videos = [_video(n, H, W, seed=40 + v) for v, n in enumerate(lengths)]
     rt = _runtime("convunet+feat", stem, future, B, H, W, **ON)
-    got = {v: [] for v in range(len(lengths))}
-    for step in deal_slots(lengths, B):
-        batch = np.zeros((B, H, W), np.uint16)
-        for b, (c, v, k) in enumerate(step):
-            if c != IDLE:
-                batch[b] = videos[v][k]
-        out, valid = rt.video_push(to_gpu(batch), [c for c, _, _ in step], 12, "mosaic")
-        for b, (c, v, k) in enumerate(step):
-            assert valid[b] == (c != IDLE and k >= 1 + future)
-            if valid[b]:
-                got[v].append(out[b:b + 1].clone())
-        out.fill_(float("nan"))              # the caller owns out_rgb between pushes: the plane was taken inside the push
+    steps = deal_slots(lengths, B)
+    # the caller owns out_rgb between pushes: the plane was taken inside the push
+    pushed = push_schedule(rt, videos, steps, after=lambda i, out: out.fill_(float("nan")))
+    for step, valid in zip(steps, pushed.flags):
+        assert valid == [c != IDLE and k >= 1 + future for c, _, k in step], step
     rt.set_option("tvl1_async", 0)
     alone = _runtime("convunet+feat", stem, future, 1, H, W, **ON)
     for v, n in enumerate(lengths):
         want, _ = _stream_alone(alone, videos[v], future)
-        assert len(got[v]) == len(want) == n - 1 - future
-        for k, (g, w) in enumerate(zip(got[v], want)):
-            assert torch.equal(g, w), (v, k, float((g - w).abs().max()))
+        assert len(want) == n - 1 - future
+        same(pushed.by_video[v], want, v)
 
 
 def test_slots_are_independent_from_denoised_720p_batch_8():
@@ -170,37 +161,17 @@ def test_slots_are_independent_from_denoised_720p_batch_8():
     videos = [_video(T, H, W, seed=50 + v, iso=12800, device="cuda") for v in range(B)]
     short = _video(3, H, W, seed=70, iso=12800, device="cuda")
     rt = _runtime("convunet+feat", stem, future, B, H, W, **ON)
-    got = {b: [] for b in range(B)}
-    for t in range(T + 3):
-        batch = np.zeros((B, H, W), np.uint16)
-        ctl = []
-        for b in range(B):
-            # slot 5 holds a video of three frames first, then starts its video of T frames mid-stream; the others idle at the end
-            k = t - 3 if b == 5 else t
-            if b == 5 and t < 3:
-                batch[b], c = short[t], (FIRST if t == 0 else NEXT)
-            elif k < T:
-                batch[b], c = videos[b][k], (FIRST if k == 0 else NEXT)
-            else:
-                c = IDLE
-            ctl.append(c)
-        out, valid = rt.video_push(to_gpu(batch), ctl, 12, "mosaic")
-        for b in range(B):
-            k = t - 3 if b == 5 else t
-            if b == 5 and t < 3:
-                assert valid[b] == (t == 2)
-            else:
-                assert valid[b] == (2 <= k < T)
-                if valid[b]:
-                    got[b].append(out[b:b + 1].clone())
+    steps = mid_stream_schedule(B, T)
+    pushed = push_schedule(rt, videos + [short], steps)
+    for step, valid in zip(steps, pushed.flags):
+        assert valid == [c != IDLE and k >= 2 for c, _, k in step], step
     rt.set_option("tvl1_async", 0)
     del rt
     alone = _runtime("convunet+feat", stem, future, 1, H, W, **ON)
     for b in (0, 5, 7):
         want, _ = _stream_alone(alone, videos[b], future)
-        assert len(got[b]) == len(want) == T - 2
-        for g, w in zip(got[b], want):
-            assert torch.equal(g, w), (b, float((g - w).abs().max()))
+        assert len(want) == T - 2
+        same(pushed.by_video[b], want, b)
 
 
 # ---- 4. option off is the push without the option ------------------------------------------------------------------------
@@ -242,7 +213,7 @@ def test_denoise_main_with_flows_from_denoised(tmp_path):
         res = str(tmp_path / tag)
         stats = denoise.main(flags + ["--results_dir", res] + extra)
         assert stats["frames"] == sum(n - 1 for n in lengths)
-        return _tree(res)
+        return files_of(res)
 
     on1 = run("on1", ["--val_flow_from_denoised", "--batch_size", "1"])
     on3 = run("on3", ["--val_flow_from_denoised", "--batch_size", "3"])

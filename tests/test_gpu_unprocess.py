@@ -11,6 +11,7 @@ import torch
 
 import unprocess_ref as U
 from conftest import GOLDEN, WEIGHTS
+from gpu_support import files_of, ops_rt
 
 pytestmark = pytest.mark.gpu
 
@@ -21,8 +22,7 @@ OUTPUTS = ("lin_f32", "lin_u16", "gt_raw", "noisy")
 
 @pytest.fixture(scope="module")
 def rt():
-    from rvdd_release_amd.util._ops import ops_runtime
-    return ops_runtime(0)
+    return ops_rt()
 
 
 @pytest.fixture(scope="module")
@@ -185,10 +185,6 @@ def test_argument_errors(rt):
 
 
 # ---- on disk ------------------------------------------------------------------------------------------------------------------
-def _tree(root):
-    return {os.path.relpath(os.path.join(d, f), root): open(os.path.join(d, f), "rb").read() for d, _, fs in os.walk(root) for f in fs}
-
-
 def test_main_on_disk_feeds_denoise_and_ppipe(rt, tmp_path):
     from PIL import Image
     from rvdd_release_amd import denoise, ppipe, tiffio, unprocess
@@ -207,7 +203,7 @@ def test_main_on_disk_feeds_denoise_and_ppipe(rt, tmp_path):
                             "--nb_seq_val", "2", "--nb_seq_train", "0", "--ISO", "3200", "--first", "0", "--last", "2", "--seed", "3",
                             "--batch", str(batch)])
         assert n == {"train": 0, "val": 6}
-        trees[batch] = _tree(str(out))
+        trees[batch] = files_of(str(out))
     assert set(trees[1]) == {f"{folder}_iso3200/{s:03d}/{i:08d}.{'png' if folder == 'gt_RGB' else 'tiff'}"
                              for folder in ("gt", "gt_raw_linear_RGB", "noisy", "gt_RGB") for s in range(2) for i in range(3)}
     assert trees[1] == trees[3]                                          # byte for byte, whatever --batch is

@@ -9,10 +9,9 @@ from collections import Counter, OrderedDict
 import pytest
 import torch
 
+from packed_fakes import FakeDataset, FakeLoader, FakeModel, VIDEOS, _opt
 from rvdd_release_amd import validate
 from rvdd_release_amd.data.packed import PackedLoader, plan_packs
-
-from test_packed_host import FakeDataset, FakeLoader, FakeModel, VIDEOS, _opt
 
 # the default mix of tools/packed_bench.py (seed 2024): frames per video; a video of T frames has T - 1 samples
 BENCH_LENGTHS = [17, 35, 9, 9, 36, 13, 39, 32, 18, 40, 10, 37]
