@@ -29,6 +29,12 @@ UNET_PAIRS = tuple((f"{g}.{i}.blocks.0.0", f"{g}.{i}.blocks.1.0")
                    for g, n in (("EncoderConvs", 4), ("DecoderConvs", 3)) for i in range(n))
 UNET_ZERO = "EncoderConvs.2.blocks.1.0"               # an all-zero 3x3 bank (mx == 0)
 
+# rel_err(hip, f64) <= R * e_ref per kernel family (test_gpu_random_weights.py has the table and how each value came about)
+R_CAP = 8
+R = {"split-f16 conv": 8, "direct f32": 6, "Winograd f32": 3, "ConvBlock split": 5, "ConvBlock f32": 3,
+     "composed first layer": 8}
+assert all(v <= R_CAP for v in R.values())
+
 _shapes = {}
 
 

@@ -45,13 +45,10 @@ import torch
 
 import rvdd_oracle as O
 import random_weights as RW
+from hard_flows import _device_steps, _oracle_steps, _sequences, wild
+from random_weights import R
 
 pytestmark = pytest.mark.gpu
-
-R_CAP = 8
-R = {"split-f16 conv": 8, "direct f32": 6, "Winograd f32": 3, "ConvBlock split": 5, "ConvBlock f32": 3,
-     "composed first layer": 8}
-assert all(v <= R_CAP for v in R.values())
 
 # one tile with every pixel within two of the border; ragged tiles, odd level sizes (zero_pad_features at every decoder
 # stage), a batch; a second ragged size; 80 tiles: the output-channel split at every level, workgroups of the pipelined
@@ -141,58 +138,6 @@ def test_convnext_forward_vs_f64_oracle(arch, stem, fut, profile, seed, B, H, W)
     assert not bad, bad
 
 
-def _oracle_steps(sd, fut, raw, dtype, flow_prev=None, flow_next=None):
-    """Two frame-steps of the recurrence (oracle/rvdd_oracle.py RecurrentOracle.step) with the net, the state and the warps in
-    `dtype`; flow_prev None = --no_warp.  raw [T,B,4,h,w], flows [T,B,2,h,w] -> [out 1, out 2, features after step 2].
-    The demosaic is always the f32 one (the device's, bit for bit) and is cast: in f32 this is RecurrentOracle itself."""
-    sdd = {k: v.to(dtype) for k, v in sd.items()}
-    ha = lambda r: O.hamilton_adams(r).to(dtype)
-    up = lambda fl: O.upsample_factor_2(fl.to(dtype), multiply_by=2)
-    lastden = ha(raw[0])
-    B, _, H, W = lastden.shape
-    feat = torch.zeros(B, 48, H, W, dtype=dtype)
-    outs = []
-    with torch.no_grad():
-        for t in (1, 2):
-            n_cur = ha(raw[t])
-            if flow_prev is None:
-                parts, fin = [lastden, n_cur], feat
-            else:
-                fp = up(flow_prev[t])
-                parts, fin = [O.warp(lastden, fp), n_cur], O.warp(feat, fp)
-            if fut:
-                parts.append(ha(raw[t + 1]) if flow_prev is None else O.warp(ha(raw[t + 1]), up(flow_next[t])))
-            lastden, feat = O.net_forward(sdd, torch.cat(parts, 1), fin)
-            outs.append(lastden)
-    return outs + [feat]
-
-
-def _device_steps(arch, fut, shape, sd, raw, options, flow_prev=None, flow_next=None):
-    from rvdd_release_amd.runtime import RvddRuntime
-    rt = RvddRuntime(arch, fut, *shape, 0)
-    try:
-        for k, v in options.items():
-            rt.set_option(k, v)
-        rt.load_state_dict(sd)
-        raw = raw.cuda()
-        fp = None if flow_prev is None else flow_prev.cuda()
-        fn = None if flow_next is None or not fut else flow_next.cuda()
-        outs = []
-        for t in (1, 2):
-            outs.append(rt.step(raw[0] if t == 1 else None, raw[t], raw[t + 1] if fut else None,
-                                None if fp is None else fp[t], None if fn is None else fn[t]).cpu())
-        return outs + [rt.get_state()[1].cpu()]
-    finally:
-        rt.close()
-
-
-def _sequences(B, H, W, T, seed0, iso=3200):
-    from rvdd_release_amd import synth
-    seqs = [synth.make_sequence(T, H, W, iso=iso, seed=seed0 + b) for b in range(B)]
-    st = lambda key: torch.stack([getattr(s, key) for s in seqs], 1)      # [T,B,...]
-    return st("raw"), st("flow_prev"), st("flow_next")
-
-
 @pytest.mark.parametrize("B,H,W", [(3, 50, 66), (1, 16, 16)])
 @pytest.mark.parametrize("profile", ["he", "pow2"])
 @pytest.mark.parametrize("arch,stem,fut,family", [
@@ -233,8 +178,7 @@ def test_feature_warp_projection_half_dense_weights(profile, flows):
     sd = RW.random_state_dict(stem, 7, profile)
     raw, fp, fn = _sequences(B, H, W, 4, 1680)
     if flows == "wild":
-        gen = torch.Generator().manual_seed(5)
-        fp = fp * 6.0 + torch.randn(fp.shape, generator=gen) * 9.0
+        fp = wild(fp, 5)
     o32 = _oracle_steps(sd, fut, raw, torch.float32, fp, fn)
     o64 = _oracle_steps(sd, fut, raw, torch.float64, fp, fn)
     e_ref = [RW.rel_err(a, b) for a, b in zip(o32, o64)]
