@@ -807,6 +807,12 @@ int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, 
  *               small sequence: the launches there are 5-15 us each, back to back) forms them in one kernel; a larger step
  *               without a future frame forms the network input in that kernel too, tile by tile with the green plane in
  *               on-chip memory, behind the bound's own small launch; same bits.  Per handle.
+ *   "warp48_pairs": 1 = the bicubic warp of the 48 recurrent feature channels (warp48_kernel) shares its loads within
+ *               horizontally adjacent pixel pairs only (20 loads for two pixels whose 4x4 footprints line up).  Default 0: the
+ *               four pixels of a 2x2 quad whose footprints are the same five rows and columns share 25 loads; quads that do not
+ *               line up fall back to the pair form row by row.  The same values, weights and order of sums per pixel: same bits
+ *               (the A/B reference).  Inert where the warp carries ConvNeXtUnet's projection (warp48_proj_kernel: pairs
+ *               always).  Per handle.
  *   "tvl1_async": 1 = rvdd_tvl1flow_batch called without iteration counts enqueues its launches on the stream and returns
  *               (the flows are ready in stream order; nothing is read back, the stream is not synchronised): the form for a
  *               caller that feeds the flows straight into rvdd_step on the same stream (validate.py's --val_flow_from_denoised loop

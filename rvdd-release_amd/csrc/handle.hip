@@ -95,6 +95,7 @@ int opt_conv_kernel(rvdd_t* h, int32_t value) {
     X("pre5_cin8", nullptr, pre5_cin8, 0, 1, nullptr, nullptr)                                                                   \
     X("cout_split", "RVDD_COUT_SPLIT", cout_split, 0, 1, nullptr, nullptr)                                                       \
     X("small_prestage", "RVDD_SMALL_PRESTAGE", small_prestage, 0, 1, nullptr, nullptr)                                           \
+    X("warp48_pairs", nullptr, warp48_pairs, 0, 1, nullptr, nullptr)                                                             \
     X("bayer_pattern", nullptr, bayer, RVDD_BAYER_GBRG, RVDD_BAYER_BGGR,                                                         \
       "rvdd_set_option: bayer_pattern must be 0 (GBRG), 1 (GRBG), 2 (RGGB) or 3 (BGGR)", nullptr)                                \
     X("stream_reset_each", nullptr, stream_reset_each, 0, 1, nullptr, nullptr)                                                   \

@@ -150,6 +150,7 @@ struct Options {
     int small_prestage = 1;   // the three pre-stage kernels of a small frame-step without a future frame as one (netin_small_kernel)
     int fuse_pre = 1;         // feat nets: preprocessing_layer and EncoderConvs[0][0] composed (0: one after the other, A/B reference)
     int pre5_cin8 = 1;        // 0: the 13-chunk bank of that composition also where the 7-chunk one exists (A/B reference)
+    int warp48_pairs = 0;     // 1: the feature warp shares its gather within pairs of pixels only, not within 2x2 quads (A/B reference)
     int next_split = 1;       // ConvNeXt, fused blocks: the two 1x1 convs on the F16 matrix pipe with split f32 operands (0: f32 MFMA)
     int next_pipe = 1;        // ConvNeXt, fused split-f16 blocks as a front / back pipeline over tiles (0: convblock_kernel's phases)
     int next_pool = 1;        // ConvNeXt, fused blocks: MaxPool2d(2) from the epilogue of the block in front of a DownConv

@@ -230,8 +230,10 @@ hipError_t launch_remosaick4(const float* rgb4, float* raw, int B, int H, int W,
 // ---- warp.hip -- bicubic backward warps with the raw-resolution flow (x2 bilinear upsample, align_corners=True, times 2, fused)
 // src NHWC4 -> dst[(b*H*W + p)*dpstride + c], c<3.
 hipError_t launch_warp3(const float* src4, const float* flow_raw, float* dst, int dpstride, int B, int H, int W, hipStream_t s);
-// src NHWC48 -> dst NHWC48.
-hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W, hipStream_t s, int64_t flow_bstride = 0);
+// src NHWC48 -> dst NHWC48.  pairs = true: the gather shares loads within pairs of pixels only, never within 2 x 2 quads
+// (option "warp48_pairs" 1; same bits)
+hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W, hipStream_t s, int64_t flow_bstride = 0,
+                         bool pairs = false);
 // the same, and a 48 -> 48 projection of every warped pixel: dst = W warp(src) + bias; frag / inv_e = the projection as a
 // NextProj's split-f16 fragments and scale (net_convnext.hip), applied per pixel in block floating point (warp48_proj_kernel)
 hipError_t launch_warp48_proj(const float* src, const float* flow_raw, float* dst, int B, int H, int W, const float* frag,

@@ -42,90 +42,45 @@ __global__ void warp3_kernel(const float* __restrict__ src4, const float* __rest
     o[2] = acc[2];
 }
 
-// grid = (ceil(W/32), H, B), 192 threads = 16 PAIRS of horizontally adjacent pixels x 12 float4 chunks.
+// grid = (ceil(W/32), ceil(H/2), B), 192 threads = 16 QUADS of 2 x 2 pixels x 12 float4 chunks.
 //  * The 16 taps of a pixel (flow upsample, coordinate round trip, cubic weights: ~150 VALU instructions) are
-//    computed ONCE per pixel by the first 32 threads and shared through LDS; computed by each of the 12 lanes of
-//    a pixel they cost as much SIMD time as the gather itself.
-//  * The gather is bound by the texture-address path (16 x 16-B loads per lane and pixel, not by HBM: neighbouring
-//    pixels re-read the same lines from L1).  Where the flow is smooth the 4x4 footprints of the two pixels of a
-//    pair are the same rows and columns shifted by one: 20 loads serve both instead of 32.  Pairs whose footprints
-//    do not line up (flow discontinuities, the clamped image border) take the plain 2 x 16 path; the arithmetic of
-//    a pixel is the same in both.
+//    computed ONCE per pixel, by the first 64 threads for the 64 pixels, and shared through LDS; computed by each of
+//    the 12 lanes of a pixel they cost as much SIMD time as the gather itself.
+//  * The gather is bound by the texture-address path (16-B loads per lane, not by HBM: neighbouring pixels re-read
+//    the same lines from L1).  Where the flow is smooth the 4x4 footprints of the four pixels of a quad are the same
+//    five rows and five columns: 25 loads serve all four instead of 64.  Quads whose footprints do not line up (flow
+//    discontinuities, the clamped image border) fall back row by row to the pair form (20 loads for two pixels) and
+//    to the plain 16 loads per pixel; the arithmetic of a pixel is the same in all three (warp.h warp48_gather_quad).
+//    pairs = 1 (option "warp48_pairs"): never the quad form, the A/B reference.
 __global__ __launch_bounds__(192) void warp48_kernel(const float* __restrict__ src,
                                                      const float* __restrict__ flow_raw,
-                                                     float* __restrict__ dst, int B, int H, int W, int64_t fbs) {
-    __shared__ int s_i[32][8];      // xi[4], yi[4] * W
-    __shared__ float s_w[32][8];    // wx[4], wy[4]
-    const int y = blockIdx.y, b = blockIdx.z, x0 = blockIdx.x * 32;
-    if (threadIdx.x < 32) {
-        const int x = x0 + threadIdx.x;
-        if (x < W) {
-            const int h = H / 2, w = W / 2;
-            float fx, fy;
-            flow_at(flow_raw + (size_t)b * fbs, h, w, H, W, y, x, fx, fy);
-            Taps t;
-            make_taps(fx, fy, x, y, H, W, t);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                s_i[threadIdx.x][k] = t.xi[k];
-                s_i[threadIdx.x][4 + k] = t.yi[k] * W;
-                s_w[threadIdx.x][k] = t.wx[k];
-                s_w[threadIdx.x][4 + k] = t.wy[k];
-            }
-        }
-    }
+                                                     float* __restrict__ dst, int B, int H, int W, int64_t fbs, int pairs) {
+    __shared__ int s_i[64][8];      // xi[4], yi[4] * W
+    __shared__ float s_w[64][8];    // wx[4], wy[4]
+    const int y = blockIdx.y * 2, b = blockIdx.z, x0 = blockIdx.x * 32;
+    warp48_make_taps(flow_raw + (size_t)b * fbs, H, W, x0, y, 2, s_i, s_w);
     __syncthreads();
     const int p = threadIdx.x / 12;
     const int c4 = threadIdx.x - p * 12;
-    const int pa = 2 * p, pb = 2 * p + 1, xa = x0 + pa;
+    const int xa = x0 + 2 * p;
     if (xa >= W) return;
-    const bool has_b = xa + 1 < W;
+    const bool has_b = xa + 1 < W, has_c = y + 1 < H;
     const f32x4* s = reinterpret_cast<const f32x4*>(src) + (size_t)b * H * W * 12 + c4;
     f32x4* o = reinterpret_cast<f32x4*>(dst) + (((size_t)b * H + y) * W + xa) * 12 + c4;
-    int xia[4], yia[4], xib[4], yib[4];
-    float wxa[4], wya[4], wxb[4], wyb[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        xia[k] = s_i[pa][k]; yia[k] = s_i[pa][4 + k]; wxa[k] = s_w[pa][k]; wya[k] = s_w[pa][4 + k];
-        xib[k] = s_i[pb][k]; yib[k] = s_i[pb][4 + k]; wxb[k] = s_w[pb][k]; wyb[k] = s_w[pb][4 + k];
+    f32x4 acc[4];
+    warp48_gather_quad(s, s_i, s_w, 2 * p, has_b, has_c, pairs != 0, acc);
+    o[0] = acc[0];
+    if (has_b) o[12] = acc[1];
+    if (has_c) {
+        o[(size_t)W * 12] = acc[2];
+        if (has_b) o[(size_t)W * 12 + 12] = acc[3];
     }
-    const bool lined_up = has_b && yib[0] == yia[0] && yib[1] == yia[1] && yib[2] == yia[2] && yib[3] == yia[3] &&
-                          xib[0] == xia[1] && xib[1] == xia[2] && xib[2] == xia[3];
-    f32x4 acca = {0.f, 0.f, 0.f, 0.f}, accb = {0.f, 0.f, 0.f, 0.f};
-    if (lined_up) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x4 v0 = s[(yia[j] + xia[0]) * 12], v1 = s[(yia[j] + xia[1]) * 12], v2 = s[(yia[j] + xia[2]) * 12];
-            const f32x4 v3 = s[(yia[j] + xia[3]) * 12], v4 = s[(yia[j] + xib[3]) * 12];
-            f32x4 ra = {0.f, 0.f, 0.f, 0.f}, rb = {0.f, 0.f, 0.f, 0.f};
-            ra = ra + v0 * wxa[0]; ra = ra + v1 * wxa[1]; ra = ra + v2 * wxa[2]; ra = ra + v3 * wxa[3];
-            rb = rb + v1 * wxb[0]; rb = rb + v2 * wxb[1]; rb = rb + v3 * wxb[2]; rb = rb + v4 * wxb[3];
-            acca = acca + ra * wya[j];
-            accb = accb + rb * wyb[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            f32x4 ra = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ra = ra + s[(yia[j] + xia[i]) * 12] * wxa[i];
-            acca = acca + ra * wya[j];
-        }
-        if (has_b) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                f32x4 rb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) rb = rb + s[(yib[j] + xib[i]) * 12] * wxb[i];
-                accb = accb + rb * wyb[j];
-            }
-        }
-    }
-    o[0] = acca;
-    if (has_b) o[12] = accb;
 }
 
-// warp48_kernel with a 48 -> 48 projection of the warped pixel on its way out: dst = W warp(src) + bias.  ConvNeXtUnet's first
+// The feature warp with a 48 -> 48 projection of the warped pixel on its way out: dst = W warp(src) + bias.  One row of 32 pixels
+// per workgroup, grid = (ceil(W/32), H, B), and warp.h's gather at its row-pair level: the 32 x 2 form with the quad level
+// (64 pixels staged, two 16-pixel groups per projecting wave) gave bits that changed from run to run at 720p, B = 8 -- cause
+// not found, LABBOOK.md -- so this kernel keeps the geometry it had.  ConvNeXtUnet's first
 // encoder block projects cat[y, warped features] 96 -> 48 (networks/new_unet.py:381-382, 85-88); the projection is linear
 // in the two maps and the warped features have no other reader, so their half of it rides here and the other half in the
 // epilogue of the block that forms y (convnext.hip PROJ) -- the projection kernel and its 4 S of traffic are gone.
@@ -153,7 +108,7 @@ __device__ __forceinline__ void wp_split4(f32x4 x, unsigned (&hi)[2], unsigned (
     hi[0] = u01; hi[1] = u23;
     lo[0] = __builtin_bit_cast(unsigned, l01); lo[1] = __builtin_bit_cast(unsigned, l23);
 }
-__global__ __launch_bounds__(192) void warp48_proj_kernel(const float* __restrict__ src, const float* __restrict__ flow_raw,
+__global__ __launch_bounds__(192, 4) void warp48_proj_kernel(const float* __restrict__ src, const float* __restrict__ flow_raw,
                                                           float* __restrict__ dst, int B, int H, int W, int64_t fbs,
                                                           const float* __restrict__ frag, int inv_e, const float* __restrict__ bias) {
     __shared__ int s_i[32][8];      // xi[4], yi[4] * W
@@ -165,23 +120,7 @@ __global__ __launch_bounds__(192) void warp48_proj_kernel(const float* __restric
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         reinterpret_cast<f32x4*>(s_f)[threadIdx.x + 192 * k] = reinterpret_cast<const f32x4*>(frag)[threadIdx.x + 192 * k];
-    if (threadIdx.x < 32) {
-        const int x = x0 + threadIdx.x;
-        if (x < W) {
-            const int h = H / 2, w = W / 2;
-            float fx, fy;
-            flow_at(flow_raw + (size_t)b * fbs, h, w, H, W, y, x, fx, fy);
-            Taps t;
-            make_taps(fx, fy, x, y, H, W, t);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                s_i[threadIdx.x][k] = t.xi[k];
-                s_i[threadIdx.x][4 + k] = t.yi[k] * W;
-                s_w[threadIdx.x][k] = t.wx[k];
-                s_w[threadIdx.x][4 + k] = t.wy[k];
-            }
-        }
-    }
+    warp48_make_taps(flow_raw + (size_t)b * fbs, H, W, x0, y, 1, s_i, s_w);
     __syncthreads();
     const int p = threadIdx.x / 12;
     const int c4 = threadIdx.x - p * 12;
@@ -190,44 +129,10 @@ __global__ __launch_bounds__(192) void warp48_proj_kernel(const float* __restric
     if (xa < W) {
         const bool has_b = xa + 1 < W;
         const f32x4* s = reinterpret_cast<const f32x4*>(src) + (size_t)b * H * W * 12 + c4;
-        int xia[4], yia[4], xib[4], yib[4];
-        float wxa[4], wya[4], wxb[4], wyb[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            xia[k] = s_i[pa][k]; yia[k] = s_i[pa][4 + k]; wxa[k] = s_w[pa][k]; wya[k] = s_w[pa][4 + k];
-            xib[k] = s_i[pb][k]; yib[k] = s_i[pb][4 + k]; wxb[k] = s_w[pb][k]; wyb[k] = s_w[pb][4 + k];
-        }
-        const bool lined_up = has_b && yib[0] == yia[0] && yib[1] == yia[1] && yib[2] == yia[2] && yib[3] == yia[3] &&
-                              xib[0] == xia[1] && xib[1] == xia[2] && xib[2] == xia[3];
-        if (lined_up) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 v0 = s[(yia[j] + xia[0]) * 12], v1 = s[(yia[j] + xia[1]) * 12], v2 = s[(yia[j] + xia[2]) * 12];
-                const f32x4 v3 = s[(yia[j] + xia[3]) * 12], v4 = s[(yia[j] + xib[3]) * 12];
-                f32x4 ra = {0.f, 0.f, 0.f, 0.f}, rb = {0.f, 0.f, 0.f, 0.f};
-                ra = ra + v0 * wxa[0]; ra = ra + v1 * wxa[1]; ra = ra + v2 * wxa[2]; ra = ra + v3 * wxa[3];
-                rb = rb + v1 * wxb[0]; rb = rb + v2 * wxb[1]; rb = rb + v3 * wxb[2]; rb = rb + v4 * wxb[3];
-                acca = acca + ra * wya[j];
-                accb = accb + rb * wyb[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                f32x4 ra = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ra = ra + s[(yia[j] + xia[i]) * 12] * wxa[i];
-                acca = acca + ra * wya[j];
-            }
-            if (has_b) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f32x4 rb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) rb = rb + s[(yib[j] + xib[i]) * 12] * wxb[i];
-                    accb = accb + rb * wyb[j];
-                }
-            }
-        }
+        PieceTaps ta, tb;
+        warp48_read_taps(s_i, s_w, pa, ta);
+        warp48_read_taps(s_i, s_w, pb, tb);
+        warp48_gather_pair(s, ta, tb, has_b, acca, accb);
     }
     *reinterpret_cast<f32x4*>(&s_t[pa][4 * c4]) = acca;
     *reinterpret_cast<f32x4*>(&s_t[pb][4 * c4]) = accb;
@@ -329,10 +234,10 @@ hipError_t launch_warp3(const float* src4, const float* flow_raw, float* dst, in
 }
 
 hipError_t launch_warp48(const float* src, const float* flow_raw, float* dst, int B, int H, int W,
-                         hipStream_t s, int64_t flow_bstride) {
+                         hipStream_t s, int64_t flow_bstride, bool pairs) {
     if (!B || !H || !W) return hipSuccess;
-    hipLaunchKernelGGL(warp48_kernel, dim3((W + 31) / 32, H, B), dim3(192), 0, s, src, flow_raw, dst, B, H, W,
-                       flow_bstride ? flow_bstride : (int64_t)2 * (H / 2) * (W / 2));
+    hipLaunchKernelGGL(warp48_kernel, dim3((W + 31) / 32, (H + 1) / 2, B), dim3(192), 0, s, src, flow_raw, dst, B, H, W,
+                       flow_bstride ? flow_bstride : (int64_t)2 * (H / 2) * (W / 2), (int)pairs);
     return hipGetLastError();
 }
 
