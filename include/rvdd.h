@@ -427,7 +427,8 @@ enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
  *       push whose outputs have no TV-L1 pair at all runs no TV-L1, its step reads a zeroed flow tensor.
  * The handle keeps the last 2 + future ingested frames of every slot (packed and gray) on the device: allocated by the
  * first push, freed with the handle (20 (2 + future) + 24 (1 + future) bytes per raw cell and slot with the flow batch's
- * buffers; 4 more with option "stream_flow_from_denoised", 16 more with rvdd_set_dpc, each allocated by the first push that has it on).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
+ * buffers; 4 more with option "stream_flow_from_denoised", 16 more with rvdd_set_dpc, and 3072 bytes per slot with rvdd_set_resid, each allocated by the
+ * first push that has it on).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
  * I1 = gray[previous]) and, with a future frame, (gray[centre], gray[next]) for all of them in ONE batch call in the form of
  * option "tvl1_async" 1 (whatever the option says), then one rvdd_step_strided on the kept packed frames and those flows.  A
  * slot's first ready push carries its reset mark (rvdd_reset_slots; raw_prev = its oldest frame), so every output is bit for
@@ -701,6 +702,99 @@ int rvdd_unmatch_rgb(rvdd_t* h, const float* rgb_in /* [n,3,H,W] */, float* rgb_
  * gray planes -> rvdd_step -> rvdd_unmatch_rgb on a handle of batch 1.  The stage allocates nothing; with it off a push makes exactly the
  * launches it made before.  Switch it between videos: frames mapped with other coefficients stay in the ring as they are. */
 int rvdd_set_match(rvdd_t* h, const rvdd_match_cfg* cfg /* NULL = off, the default */);
+
+/* ---- denoised footage checked without ground truth: residual statistics -------- */
+
+/* If the output is the clean frame, then noisy - remosaic(denoised) is the noise: its variance at level m is a * m - b, its mean is
+ * zero, and neighbouring samples of one colour plane are uncorrelated.  Variance below the curve means noise left in the output (or a
+ * curve that was over-estimated); variance above it together with a positive neighbour correlation means scene detail removed; a
+ * mean away from zero means a level shift.  rvdd_resid_stats reduces a frame pair to 3072 bytes of integers on the device,
+ * rvdd_resid_fit judges a host copy of them against a curve.
+ * What the numbers can and cannot tell (DESIGN.md 4.19 has the measured table, synthetic sequences with ground truth, three seeds): the
+ * output is never the clean frame, so the matched baseline is not ratio 1 and not one number -- 1.80-1.82 with rho 0.26-0.36 for the ISO 3200
+ * checkpoint, 1.17-1.20 with rho 0.09-0.12 for the ISO 12800 one -- and a report is read against the matched run of the same family.
+ * Against that, ratio separates the wrong family, a match curve off by a factor 2 either way and footage of half or double the gain;
+ * it does not rank quality, it barely moves (1.23 against 1.17-1.20) for the one case that loses 7.7 dB, and a black level off by 16 DN
+ * shows as a lower ratio_lo, not in bias, because the network follows the level.  Nothing is measured on real footage.
+ * The rule, on packed [n,4,hh,ww] (the noisy frames as rvdd_ingest_raw / rvdd_dpc / rvdd_match_raw leave them) and rgb [n,3,2hh,2ww]
+ * (the outputs for them), with top = (float)(2^bit_depth - 1), dn(v) = ((v + 1) * 0.5) * top and S = 2^(15 - bit_depth) (1/8 DN at 12
+ * bits), every operation rounded to f32 on its own (no fused multiply-add) and every sum an integer, so that every word below is
+ * reproducible bit for bit in NumPy (tests/resid_ref.py).  Per plane k = 0..3 and cell (y, x):
+ *   c  = dn(packed[k][y][x])
+ *   d  = dn(rgb[col(k)][2y + (k >> 1)][2x + (k & 1)])      col(k): the colour of `pattern` at CFA position k (rvdd_gray_of_rgb's v_k)
+ *   rq = (int)rintf(fminf(fmaxf((c - d) * S, -2^17), 2^17))  the residual in units of 1 / S DN, clamped (ties round to even)
+ *   dc = fminf(fmaxf(d, 0), top)
+ *   j  = min((int)(dc * (64 / 2^bit_depth)), 63)           the level bin of the DENOISED value (rvdd_frame_sigs' power-of-two scale)
+ *   n[j] += 1;  msum[j] += (uint64)rintf(dc * 16);  s1[j] += rq;  s2[j] += rq * rq
+ *   and where x < ww - 1:  n11[j] += 1;  s11[j] += rq(x) * rq(x + 1)   the right neighbour of the same plane and row; binned by j of x
+ * All sums wrap modulo 2^64.  Real frames stay far below that: rq * rq is below 2^34 at the clamp and below 2^24 for a residual of
+ * 500 DN at 12 bits, so one bin holds 2^40 such samples -- thirty thousand frames of 3840 x 2160 sites that all fall into it -- and an
+ * accumulator lives for one shot.  With NaN or inf in an input the counts are unspecified (as it happens fmaxf / fminf put NaN at an
+ * end of the range), but both j and rq are clamped and nothing outside the tensors is read or written. */
+typedef struct rvdd_resid_acc {   /* 3072 bytes */
+    uint64_t n[64];               /* samples in level bin j */
+    uint64_t msum[64];            /* sum of (uint64)rintf(dc * 16) */
+    int64_t  s1[64];              /* sum of rq */
+    uint64_t s2[64];              /* sum of rq * rq */
+    uint64_t n11[64];             /* pairs (x < ww - 1) */
+    int64_t  s11[64];             /* sum of rq(x) * rq(x + 1) */
+} rvdd_resid_acc;
+
+/* The sums of frame i are ADDED to acc[i] (DEVICE, n structs, 8-byte aligned; the caller zeroes them once): one accumulator per frame,
+ * integer atomics, so a batch gives what its frames give one at a time whatever the order of arrival, and calls accumulate.  One
+ * kernel.  With ww % 4 == 0 and `packed` and `rgb` 16-byte aligned a thread owns four neighbouring cells (16-byte loads of the four
+ * planes and of the two RGB rows they need), one cell otherwise: same integers either way.  Equal bins are combined inside the wave
+ * before LDS is touched, the workgroup's 64 x 6 table is folded into acc[i] with one 64-bit atomic per non-zero word, and a frame is
+ * walked by at most 128 workgroups, so that a flat frame -- one bin -- costs what a scene costs.
+ * RVDD_ERR_ARG (the message names the argument) and nothing launched: pattern outside 0..3; bit_depth outside 1..16; hh or ww < 1;
+ * n < 0; NULL packed / rgb / acc with n > 0; acc not 8-byte aligned; a launch of more than 2^31 - 1 blocks.  n = 0 does nothing.
+ * Asynchronous and stream-ordered; nothing is read back. */
+int rvdd_resid_stats(rvdd_t* h, const float* packed /* [n,4,hh,ww] */, const float* rgb /* [n,3,2hh,2ww] */, int32_t n, int32_t hh,
+                     int32_t ww, int32_t pattern /* enum rvdd_bayer */, int32_t bit_depth,
+                     rvdd_resid_acc* acc /* DEVICE [n], 8-byte aligned, accumulated; caller zeroes */, void* stream);
+
+/* The judgement against the curve var(m) = a * m - b (DN of bit_depth), in f64 on the host; needs neither a device nor a handle
+ * (errors go where rvdd_noise_fit's go: rvdd_last_error(NULL)).  Each operation as written, sums over the bins in ascending j, so
+ * that the same formulas in Python floats give the same numbers (tests/resid_ref.py).  With S = 2^(15 - bit_depth):
+ *   usable bins: n[j] >= 1024 and p_j = a * m_j - b > 0, where m_j = msum[j] / 16 / n[j]
+ *   per usable bin: u_j = s1[j] / n[j] / S;  var_j = s2[j] / n[j] / (S * S) - u_j * u_j;  ratio_j = var_j / p_j
+ *   ratio    = (sum of n[j] * ratio_j) / (sum of n[j]) over the usable bins; `samples` is that sum of n[j], `bins` their number
+ *   ratio_lo = the same mean over the darkest third of the usable samples: walking the usable bins upwards with T = samples / 3 and
+ *              c = 0, a bin weighs w = min(n[j], T - c) while w > 0, then c += w (the bin that straddles T counts in part);
+ *   ratio_hi = the same, walking downwards: the brightest third
+ *   bias     = SUM s1 / SUM n / S                        in DN; the SUMs here and in rho are exact integer sums over ALL 64 bins,
+ *   rho      = (SUM s11 / SUM n11) / (SUM s2 / SUM n)    each converted to f64 once; 0 where SUM n11 or SUM s2 is 0
+ *   a_fit, b_fit: weighted least squares of var_j = a_fit * m_j - b_fit over the usable bins with var_j > 0, weights n[j] / var_j^2,
+ *              centred exactly as rvdd_noise_fit's; both 0 where fewer than 2 such bins exist or their m_j do not differ
+ * RVDD_ERR_ARG: NULL acc_host / out, bit_depth outside 1..16, a or b not finite.  RVDD_ERR_STATE, *out untouched, when fewer than 4
+ * bins are usable (too few frames, or a curve that predicts no noise at the footage's levels). */
+typedef struct rvdd_resid_report {
+    double ratio, ratio_lo, ratio_hi;   /* measured / predicted variance: all usable samples, their darkest and brightest third */
+    double bias;                        /* mean residual, DN */
+    double rho;                         /* correlation of horizontal same-plane neighbours */
+    double a_fit, b_fit;                /* the curve the residual itself follows, DN */
+    uint64_t samples;                   /* samples in the usable bins */
+    int32_t bins;                       /* usable bins */
+    int32_t reserved;                   /* 0 */
+} rvdd_resid_report;
+int rvdd_resid_fit(const rvdd_resid_acc* acc_host /* HOST copy */, int32_t bit_depth, double a, double b, rvdd_resid_report* out);
+
+/* The measurement as a stage of rvdd_video_push: on != 0 switches it on, 0 off (the default).  Per handle; synchronises the device;
+ * off -> on zeroes the accumulators.  With the stage on a push enqueues, right behind its frame-step and BEFORE rvdd_set_match's way
+ * back, one rvdd_resid_stats launch per run of slots that gave an output (valid[b] = 1: heads and tails of option
+ * "stream_all_frames" like any other; a slot without an output is not measured): the ring's centre frame -- as corrected by
+ * rvdd_set_dpc_map / rvdd_set_dpc and as mapped by rvdd_set_match -- against out_rgb, into the slot's own accumulator
+ * (cfg.batch x 3072 bytes on the device, allocated by the first push that has the stage on, freed with the handle), in the handle's
+ * "bayer_pattern".  The unit: with rvdd_set_match on both sides are in the network's domain and bit_depth is 12, the unit of the
+ * checkpoint's curve; with it off it is the push's bit_depth.  The stage only reads: out_rgb, valid and the recurrent state are bit
+ * for bit those of the same pushes without it.  With the stage off a push makes exactly the launches it made before and allocates
+ * nothing. */
+int rvdd_set_resid(rvdd_t* h, int32_t on);
+
+/* Slot `slot`'s accumulator copied to *host_out and zeroed on the device, both on `stream`, which is then synchronised: call it
+ * where the loop synchronises anyway (the end of a video or of a shot).  All zeros on a handle that never pushed with the stage on.
+ * RVDD_ERR_ARG: NULL host_out, slot outside 0 .. cfg.batch - 1. */
+int rvdd_resid_read(rvdd_t* h, int32_t slot, rvdd_resid_acc* host_out /* HOST */, void* stream /* synchronised */);
 
 /* ---- raw datasets from sRGB video ------------------------------------------- */
 

@@ -62,6 +62,18 @@ class RvddFrameSig(C.Structure):
     _fields_ = [("hist", (C.c_uint32 * 64) * 16), ("sum", (C.c_uint64 * 16) * 16)]
 
 
+class RvddResidAcc(C.Structure):
+    """struct rvdd_resid_acc (rvdd_resid_stats, rvdd_resid_read, rvdd_resid_fit): 3072 bytes"""
+    _fields_ = [("n", C.c_uint64 * 64), ("msum", C.c_uint64 * 64), ("s1", C.c_int64 * 64), ("s2", C.c_uint64 * 64),
+                ("n11", C.c_uint64 * 64), ("s11", C.c_int64 * 64)]
+
+
+class RvddResidReport(C.Structure):
+    """struct rvdd_resid_report (rvdd_resid_fit)"""
+    _fields_ = [("ratio", C.c_double), ("ratio_lo", C.c_double), ("ratio_hi", C.c_double), ("bias", C.c_double), ("rho", C.c_double),
+                ("a_fit", C.c_double), ("b_fit", C.c_double), ("samples", C.c_uint64), ("bins", C.c_int32), ("reserved", C.c_int32)]
+
+
 # symbol -> (restype, argtypes); exactly the functions include/rvdd.h declares
 _P = C.c_void_p
 _PROTOS = {
@@ -111,6 +123,10 @@ _PROTOS = {
     "rvdd_match_raw": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddMatchCfg), _P]),
     "rvdd_unmatch_rgb": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddMatchCfg), _P]),
     "rvdd_set_match": (C.c_int, [_P, C.POINTER(RvddMatchCfg)]),
+    "rvdd_resid_stats": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rvdd_resid_fit": (C.c_int, [C.POINTER(RvddResidAcc), C.c_int32, C.c_double, C.c_double, C.POINTER(RvddResidReport)]),
+    "rvdd_set_resid": (C.c_int, [_P, C.c_int32]),
+    "rvdd_resid_read": (C.c_int, [_P, C.c_int32, C.POINTER(RvddResidAcc), _P]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                  _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),

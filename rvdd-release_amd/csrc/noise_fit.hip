@@ -1,4 +1,4 @@
-// rvdd_noise_fit, rvdd_cut_score and rvdd_match_coeffs: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
+// rvdd_noise_fit, rvdd_resid_fit, rvdd_cut_score and rvdd_match_coeffs: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
 // Host code only, f64, no device and no handle; compiled -ffp-contract=off so that tests/noise_ref.py, which runs the same sums in
 // the same order in Python doubles, gets the same numbers.
 #include "runtime_internal.h"
@@ -85,6 +85,102 @@ extern "C" int rvdd_noise_fit(const rvdd_noise_acc* acc, int32_t bit_depth, rvdd
         sr += ns[k] * (r * r);
     }
     *out = rvdd_noise_curve{a, b, m_min, m_max, std::sqrt(sr / (double)blocks), blocks, bins, 0};
+    return RVDD_OK;
+}
+
+// rvdd_resid_fit: a host copy of rvdd_resid_stats' accumulator judged against the curve var(m) = a m - b (the rule is in include/rvdd.h).
+// f64, each operation as written, sums over the bins in ascending order; the totals are exact integer sums converted once: the same
+// formulas in Python floats and integers give the same numbers (tests/resid_ref.py).
+extern "C" int rvdd_resid_fit(const rvdd_resid_acc* acc, int32_t bit_depth, double a, double b, rvdd_resid_report* out) {
+    if (!acc) return fail(nullptr, RVDD_ERR_ARG, "rvdd_resid_fit: acc_host is required");
+    if (!out) return fail(nullptr, RVDD_ERR_ARG, "rvdd_resid_fit: out is required");
+    if (bit_depth < 1 || bit_depth > 16) return fail(nullptr, RVDD_ERR_ARG, "rvdd_resid_fit: bit_depth must be 1..16, got %d", bit_depth);
+    if (!std::isfinite(a)) return fail(nullptr, RVDD_ERR_ARG, "rvdd_resid_fit: a must be finite, got %g", a);
+    if (!std::isfinite(b)) return fail(nullptr, RVDD_ERR_ARG, "rvdd_resid_fit: b must be finite, got %g", b);
+    constexpr uint64_t kMinSamples = 1024;
+    const double S = bit_depth == 16 ? 0.5 : (double)(1u << (15 - bit_depth));
+    double ms[64], vs[64], rs[64], ns[64];
+    int bins = 0;
+    uint64_t samples = 0;
+    for (int j = 0; j < 64; ++j) {
+        if (acc->n[j] < kMinSamples) continue;
+        const double n = (double)acc->n[j];
+        const double m = (double)acc->msum[j] / 16.0 / n;
+        const double p = a * m - b;
+        if (!(p > 0.0)) continue;
+        const double u = (double)acc->s1[j] / n / S;
+        const double v = (double)acc->s2[j] / n / (S * S) - u * u;
+        ms[bins] = m;
+        vs[bins] = v;
+        rs[bins] = v / p;
+        ns[bins] = n;
+        samples += acc->n[j];
+        ++bins;
+    }
+    if (bins < kMinBins)
+        return fail(nullptr, RVDD_ERR_STATE, "rvdd_resid_fit: %d usable level bins (of %llu samples or more, where the curve a = %g, b = %g predicts "
+                    "noise), at least %d are needed: too few frames, or a curve that predicts no noise at the footage's levels", bins,
+                    (unsigned long long)kMinSamples, a, b, kMinBins);
+    rvdd_resid_report r{};
+    double sn = 0.0, snr = 0.0;
+    for (int k = 0; k < bins; ++k) {
+        sn += ns[k];
+        snr += ns[k] * rs[k];
+    }
+    r.ratio = snr / sn;
+    const double third = (double)samples / 3.0;
+    for (int side = 0; side < 2; ++side) {      // the darkest third walking upwards, the brightest walking downwards
+        double c = 0.0, sw = 0.0, swr = 0.0;
+        for (int i = 0; i < bins; ++i) {
+            const int k = side ? bins - 1 - i : i;
+            const double rest = third - c;
+            const double w = ns[k] < rest ? ns[k] : rest;
+            if (!(w > 0.0)) break;
+            sw += w;
+            swr += w * rs[k];
+            c += w;
+        }
+        (side ? r.ratio_hi : r.ratio_lo) = swr / sw;
+    }
+    __int128 t1 = 0, t11 = 0;
+    unsigned __int128 tn = 0, t2 = 0, tn11 = 0;
+    for (int j = 0; j < 64; ++j) {
+        tn += acc->n[j];
+        t1 += acc->s1[j];
+        t2 += acc->s2[j];
+        tn11 += acc->n11[j];
+        t11 += acc->s11[j];
+    }
+    r.bias = (double)t1 / (double)tn / S;
+    r.rho = tn11 && t2 ? ((double)t11 / (double)tn11) / ((double)t2 / (double)tn) : 0.0;
+    // the curve the residual follows: rvdd_noise_fit's centred normal equations over the bins that have a variance
+    double sw = 0.0, swm = 0.0, swv = 0.0;
+    int fit = 0;
+    for (int k = 0; k < bins; ++k) {
+        if (!(vs[k] > 0.0)) continue;
+        const double w = ns[k] / (vs[k] * vs[k]);
+        sw += w;
+        swm += w * ms[k];
+        swv += w * vs[k];
+        ++fit;
+    }
+    if (fit >= 2) {
+        const double mbar = swm / sw, vbar = swv / sw;
+        double smm = 0.0, smv = 0.0;
+        for (int k = 0; k < bins; ++k) {
+            if (!(vs[k] > 0.0)) continue;
+            const double w = ns[k] / (vs[k] * vs[k]);
+            smm += w * ((ms[k] - mbar) * (ms[k] - mbar));
+            smv += w * ((ms[k] - mbar) * (vs[k] - vbar));
+        }
+        if (smm > 0.0) {
+            r.a_fit = smv / smm;
+            r.b_fit = r.a_fit * mbar - vbar;
+        }
+    }
+    r.samples = samples;
+    r.bins = bins;
+    *out = r;
     return RVDD_OK;
 }
 

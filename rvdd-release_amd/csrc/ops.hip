@@ -433,6 +433,27 @@ int rvdd_frame_sigs(rvdd_t* h, const float* gray, int32_t n, int32_t hh, int32_t
     return RVDD_OK;
 }
 
+int rvdd_resid_stats(rvdd_t* h, const float* packed, const float* rgb, int32_t n, int32_t hh, int32_t ww, int32_t pattern, int32_t bit_depth,
+                     rvdd_resid_acc* acc, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
+        return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: bit_depth must be 1..16, got %d", bit_depth);
+    if (hh < 1) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: hh must be >= 1, got %d", hh);
+    if (ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: ww must be >= 1, got %d", ww);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: n must be >= 0, got %d", n);
+    if (reinterpret_cast<uintptr_t>(acc) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: acc must be 8-byte aligned (its sums are 64-bit atomics)");
+    if (n == 0) return RVDD_OK;
+    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: packed is required");
+    if (!rgb) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: rgb is required");
+    if (!acc) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: acc is required");
+    if (resid_blocks(n, hh, ww, resid_wide(packed, rgb, ww), nullptr) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
+    ENTER(h);
+    HIPCHK(h, launch_resid(packed, rgb, n, hh, ww, pattern, bit_depth, acc, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 // the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine
 static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int32_t W) {
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);

@@ -257,6 +257,12 @@ struct rvdd_handle {
         rvdd_match_cfg cfg{};            // the checked coefficients (match_params)
     } match;
 
+    // rvdd_set_resid: residual statistics of every output against its centre frame (rvdd_video_push), read by rvdd_resid_read
+    struct Resid {
+        bool on = false;
+        rvdd_resid_acc* acc = nullptr;   // DEVICE [B]: one accumulator per slot (allocated by the first push that has the stage on)
+    } resid;
+
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
         const void* p[6];

@@ -454,6 +454,17 @@ hipError_t launch_frame_sigs(const float* gray, int n, int hh, int ww, int bit_d
 // whether that launch takes the wide form (16-byte loads)
 bool frame_sig_wide(const float* gray, int ww);
 
+// resid.hip -- residual statistics of outputs against their noisy frames (rvdd_resid_stats, the stage behind rvdd_set_resid)
+struct rvdd_resid_acc;
+// the sums of packed [n][4][hh][ww] against rgb [n][3][2hh][2ww] in pattern `bayer` added to acc[i] (DEVICE, 8-byte aligned), one
+// accumulator per frame; n = 0 launches nothing; hh, ww >= 1
+hipError_t launch_resid(const float* packed, const float* rgb, int n, int hh, int ww, int bayer, int bit_depth, rvdd_resid_acc* acc,
+                        hipStream_t s);
+// whether that launch takes the wide form (a thread owns four cells), and its grid (*groups: the workgroups of one frame); -1 = more
+// than 2^31 - 1 blocks, or tensors whose element offsets leave 64 bits
+bool resid_wide(const float* packed, const float* rgb, int ww);
+int64_t resid_blocks(int n, int hh, int ww, bool wide, int* groups);
+
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from
 // (seed, frame0 + image) then); lin_f32 / lin_u16 [n][2hh][2ww][3], gt_raw / noisy [n][hh][ww][4], each nullable

@@ -65,6 +65,9 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         return fail(h, RVDD_ERR_ARG, "rvdd_video_push: the map of rvdd_set_dpc_map is one of %d x %d cells, the frames have %d x %d", dmap.hh, dmap.ww, hh, ww);
     // rvdd_set_match: the ring's packed frames are mapped in place behind the ingest (and the correction), out_rgb is mapped back
     const auto match = h->match;
+    // rvdd_set_resid: one accumulator per slot, allocated (zeroed) by the first push that has the stage on
+    auto& resid = h->resid;
+    if (resid.on && !resid.acc) RC(dmalloc(h, reinterpret_cast<void**>(&resid.acc), (size_t)B * sizeof(rvdd_resid_acc)));
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
         if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
@@ -160,6 +163,14 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         RC(rvdd_reset_slots(h, mask.data()));
     }
     RC(rvdd_step_strided(h, packed_at(pp), packed_at(pc), fut ? packed_at(pos) : nullptr, flow_prev, flow_next, 0, 0, out_rgb, stream));
+    // rvdd_set_resid: the centre frames as the step read them against the outputs as it wrote them, before the way back: with the match
+    // on both are in the network's domain, whose unit is the 12-bit DN of the checkpoint's curve
+    if (resid.on)
+        RC(for_each_run(B, [&](int b) { return centre[(size_t)b] >= 0; }, [&](int b, int e) -> int {
+            HIPCHK(h, launch_resid(packed_at(pc) + (size_t)b * 4 * hw, out_rgb + (size_t)b * 12 * hw, e - b, hh, ww, h->opt.bayer,
+                                   match.on ? 12 : bit_depth, resid.acc + b, s));
+            return RVDD_OK;
+        }));
     // every slot, ready or not: one launch; the recurrent state stays in the network's own domain
     if (match.on) HIPCHK(h, launch_match(out_rgb, out_rgb, (int64_t)B * 12 * (int64_t)hw, match.cfg.scale, match.cfg.offset, true, s));
     if (from_den) {
@@ -233,6 +244,33 @@ extern "C" int rvdd_set_match(rvdd_t* h, const rvdd_match_cfg* cfg) {
     HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight keep the coefficients they were enqueued with
     h->match.on = cfg != nullptr;
     if (cfg) h->match.cfg = *cfg;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_set_resid(rvdd_t* h, int32_t on) {
+    if (!h) return RVDD_ERR_ARG;
+    ENTER(h);
+    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: the accumulators must be at rest
+    auto& resid = h->resid;
+    if (on && !resid.on && resid.acc) HIPCHK(h, hipMemset(resid.acc, 0, (size_t)h->cfg.batch * sizeof(rvdd_resid_acc)));      // switched on: from zero
+    resid.on = on != 0;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_resid_read(rvdd_t* h, int32_t slot, rvdd_resid_acc* host_out, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (!host_out) return fail(h, RVDD_ERR_ARG, "rvdd_resid_read: host_out is required");
+    if (slot < 0 || slot >= h->cfg.batch) return fail(h, RVDD_ERR_ARG, "rvdd_resid_read: slot must be 0 .. %d, got %d", h->cfg.batch - 1, slot);
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto& resid = h->resid;
+    if (resid.acc) {
+        HIPCHK(h, hipMemcpyAsync(host_out, resid.acc + slot, sizeof(rvdd_resid_acc), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemsetAsync(resid.acc + slot, 0, sizeof(rvdd_resid_acc), s));
+    } else {
+        std::memset(host_out, 0, sizeof(rvdd_resid_acc));
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
     return RVDD_OK;
 }
 

@@ -88,6 +88,19 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       The thresholds rest on synthetic scenes of 128 x 192 cells and more; NOTHING is measured on
                       real footage.  Look-alike shots and fades are not found, which leaves today's behaviour.  --dpc_noise auto still
                       reads the first frames of every FOLDER.  Without --cuts no new call is made and the output files keep their bytes.
+  --report FILE       check the outputs without ground truth: if the output is the clean frame, noisy - remosaic(denoised) is the noise.
+                      The stream reduces every output and its (corrected, matched) centre frame to residual statistics on the device
+                      (`rvdd_set_resid`), read at the end of every video -- of every shot under --cuts -- and judged against a noise curve
+                      (`rvdd_resid_fit`).  FILE gets one JSON line per video: {"video": key, "frames": N, "ratio", "ratio_lo", "ratio_hi",
+                      "bias", "rho", "a_fit", "b_fit", "samples", "bins", "curve": {"a", "b", "bit_depth", "source"}} (under --cuts also
+                      "from": the shot's first frame).  ratio = measured / predicted variance of the residual (lo / hi: the darkest / brightest
+                      third): below the baseline means noise left in, or a curve that is too high; above it WITH a positive rho (the
+                      correlation of horizontal neighbours of one colour) means detail removed; bias (DN) is a level shift.  The baseline
+                      is not 1: DESIGN.md 4.19 has the measured table, and says what the numbers separate and what they do not.
+                      The curve: with --match_noise the checkpoint family's (--match_iso), in the 12-bit DN the network sees; otherwise
+  --report_noise C    a,b in DN of --bit_depth, auto (the run's own estimate, shared with --dpc_noise auto), iso3200 or iso12800.
+                      Required without --match_noise.  Prints one `report:` line with the totals over all videos at the end.
+                      Without --report no new call is made and the output files keep their bytes.
 Videos of different frame sizes are grouped by size and run one group after the other, one runtime per size.
 """
 from __future__ import annotations
@@ -103,8 +116,9 @@ import torch
 
 from . import _lib
 from . import tiffio
-from .footage import add_dpc_arguments, dpc_arguments, estimate_noise, open_rawvideo, to_device
-from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, match_coeffs
+from .footage import (add_dpc_arguments, add_report_arguments, dpc_arguments, estimate_noise, open_rawvideo, report_arguments, report_record,
+                      to_device)
+from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, match_coeffs, resid_add
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
 # --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
@@ -338,6 +352,7 @@ def _parse(argv):
     p.add_argument('--match_noise', type=str, default=None, help="a,b: the footage's curve var = a * m - b in DN of the frames, mapped onto "
                    'the curve of --match_iso; auto: estimated from the footage')
     p.add_argument('--match_iso', type=int, default=None, help="the checkpoint family's noise curve: 3200 or 12800")
+    add_report_arguments(p)
     own, rest = p.parse_known_args(argv)
     if own.out_format not in OUT_FORMATS:
         raise SystemExit("--out_format %r is not one of %s" % (own.out_format, ', '.join(OUT_FORMATS)))
@@ -354,6 +369,7 @@ def _parse(argv):
                                     opt.dpc is not None)
     opt.dpc_static_only = own.dpc_static_only
     opt.match = match_arguments(own.match_noise, own.match_iso)
+    opt.report = report_arguments(own.report, own.report_noise, opt.match, int(opt.bit_depth))
     opt.cuts = cuts_arguments(own.cuts, own, opt.future_patch_depth)
     if opt.raw_container is not None:
         if opt.raw_container != 'mipi':
@@ -374,7 +390,8 @@ def _parse(argv):
 
 def prepasses(opt, dataset, dev):
     """What is decided on the run's own footage before any push, in this order: the noise curve of --dpc_noise auto / --match_noise auto
-    (ONE estimate for both), the defect map, the match coefficients, the shots.  Completes opt.dpc and opt.match; -> (dmap: the cellmask
+    (ONE estimate for both, and for --report_noise auto), the defect map, the match coefficients, the shots.  Completes opt.dpc, opt.match
+    and opt.report; -> (dmap: the cellmask
     or None, match: struct rvdd_match_cfg or None, shots [(key, [paths])])."""
     curve = None
     if opt.dpc is not None and opt.dpc[2] is None:
@@ -390,6 +407,9 @@ def prepasses(opt, dataset, dev):
             curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--match_noise')
             opt.match = curve + opt.match[2:]
         match = match_report(opt.match[0], opt.match[1], int(opt.bit_depth), opt.match[2])
+    if opt.report is not None and opt.report[2] is None:
+        curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--report_noise')
+        opt.report = opt.report[:2] + curve + opt.report[4:]
     # --cuts: every shot is a video of its own from here on, under its video's key
     shots = dataset.videos if opt.cuts is None else find_shots(dataset, dev, opt)
     return dmap, match, shots
@@ -415,10 +435,11 @@ def write_frame(opt, rt, out_b, host_b, key, path, W):
         iio_write(png[0].cpu().numpy(), os.path.join(opt.results_dir, key, stem + '_srgb.png'))
 
 
-def run_group(opt, model, dataset, videos, H, W, dmap, match) -> int:
+def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -> int:
     """The videos [(key, [paths])] of one frame size H x W through one runtime: its options and stages set, the videos dealt to the
     slots (`deal_slots`), every step pushed, its valid outputs taken to the host in one egress and written (`write_frame`), and the
-    `dpc:` line of every video that ended.  -> the frames written."""
+    `dpc:` line of every video that ended and, with --report, its record (`report_out`: {"file": the open file, "total": the sum of
+    the accumulators read so far or None, "frames": those they cover}).  -> the frames written."""
     layout, sample, _ = OUT_FORMATS[opt.out_format]
     depth = 8 if opt.out_format == "f32" else opt.out_bit_depth
     dev, fut = model.device, int(opt.future_patch_depth)
@@ -438,6 +459,10 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match) -> int:
     if dmap is not None:
         rt.set_dpc_map(dmap)
     rt.set_match(match)
+    report = getattr(opt, "report", None)
+    if report is not None:
+        rt.set_resid(True)
+    measured = [0] * B                          # outputs of the slot's video the stage has measured
     dpc_seen = rt.dpc_counts() if opt.dpc is not None else None      # rvdd_dpc_counts at the end of the slot's last video
     dpc_frames = [0] * B                        # frames the slot's video has pushed
     container = dataset.container               # None, or "msb" / "mipi": the frames stay bit-packed up to the device
@@ -473,6 +498,7 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match) -> int:
             if last:                                # --cuts: several shots share a key; the line names the shot's first frame
                 ends.append((b, key if opt.cuts is None else '%s from %s' % (key, os.path.basename(frames[0]))))
             if valid[b]:
+                measured[b] += 1
                 write_frame(opt, rt, out[b:b + 1], host[b], key, frames[k - fut], W)      # the centre frame
                 written += 1
         if ended:
@@ -483,7 +509,17 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match) -> int:
                     print('dpc: %d hot, %d dead samples corrected in %d frames (%s)'
                           % (now[b][0] - dpc_seen[b][0], now[b][1] - dpc_seen[b][1], dpc_frames[b], key))
                     dpc_seen[b] = now[b]
+            if report is not None:                  # the slot's accumulator holds this video's outputs: read, which zeroes it
+                for b, key in ends:
+                    acc = rt.resid_read(b)
+                    names = {"video": key} if opt.cuts is None else {"video": key.split(' from ')[0], "from": key.split(' from ')[1]}
+                    report_out["file"].write(json.dumps(report_record(acc, measured[b], report, **names)) + '\n')
+                    report_out["total"] = acc if report_out["total"] is None else resid_add(report_out["total"], acc)
+                    report_out["frames"] += measured[b]
+                    measured[b] = 0
     rt.set_option("tvl1_async", 0)
+    if report is not None:
+        rt.set_resid(False)
     return written
 
 
@@ -499,10 +535,18 @@ def main(argv=None) -> dict:
         groups.setdefault(dataset.frame_size(frames[0]), []).append((key, frames))
     written = 0
     t0 = time.time()
+    report_out = None if opt.report is None else {"file": open(opt.report[0], "w"), "total": None, "frames": 0}
     for (H, W), videos in groups.items():
-        written += run_group(opt, model, dataset, videos, H, W, dmap, match)
+        if report_out is None:
+            written += run_group(opt, model, dataset, videos, H, W, dmap, match)
+        else:
+            written += run_group(opt, model, dataset, videos, H, W, dmap, match, report_out)
     torch.cuda.synchronize(model.device)
     dt = time.time() - t0
+    if report_out is not None:
+        report_out["file"].close()
+        if report_out["total"] is not None:      # the sums of all videos judged as one: every figure weighted by its samples
+            print('report: ' + json.dumps(report_record(report_out["total"], report_out["frames"], opt.report, videos=len(shots))))
     print('(denoise, %d frames, %.3f s, %.2f frames/s)' % (written, dt, written / max(dt, 1e-9)))
     return {'frames': written, 'seconds': dt, 'fps': written / max(dt, 1e-9)}
 

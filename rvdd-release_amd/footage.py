@@ -1,5 +1,5 @@
 """What the four footage commands (`denoise`, `noise`, `cuts`, `dpc_map`) share: opening the rawvideo dataset, host frames to the device
-and through the ingest, and the `--dpc*` flags with the noise estimate they may ask for.  The commands import this module and the
+and through the ingest, the `--dpc*` flags with the noise estimate they may ask for, and the `--report*` flags.  The commands import this module and the
 feature modules; nothing here or there imports a command.
 """
 from __future__ import annotations
@@ -106,3 +106,66 @@ def estimate_noise(dataset, dev, bit_depth, frames, flag='--dpc_noise'):
         raise SystemExit("%s auto: %s -- pass the curve as %s a,b" % (flag, err, flag))
     print('noise: ' + noise.format_line(r))
     return (r["a"], r["b"])
+
+
+def add_report_arguments(p) -> None:
+    """the two flags of the residual report, for `denoise`; `report_arguments` reads them"""
+    p.add_argument('--report', type=str, default=None, help='FILE: one JSON line per video with the residual statistics of its outputs '
+                   '(noisy - remosaic(denoised)) judged against a noise curve: no ground truth needed')
+    p.add_argument('--report_noise', type=str, default=None, help='the curve of --report without --match_noise: a,b (var = a * m - b in DN of '
+                   'the frames), auto (estimated from the footage), iso3200 or iso12800')
+
+
+def report_arguments(report, report_noise, match, bit_depth):
+    """--report / --report_noise -> None (no --report) or (path, source, a, b, unit): the curve var = a * m - b in DN of `unit` bits the
+    residual is judged against, and where it comes from -- "match_iso<ISO>" (match = what `match_arguments` returned: the checkpoint
+    family's curve in 12-bit DN, the unit the stage measures in under the match), "a,b", "iso<ISO>" or "auto" (a and b None, for the
+    command to estimate from the footage).  SystemExit where the flags do not fit together."""
+    if report is None:
+        if report_noise is not None:
+            raise SystemExit("--report_noise belongs to --report FILE")
+        return None
+    if match is not None:
+        if report_noise is not None:
+            raise SystemExit("--report_noise does not go with --match_noise: matched footage is judged against the curve of --match_iso, "
+                             "the one the network sees")
+        a, b = DPC_ISO_CURVES[match[2]]
+        return (report, "match_iso%d" % match[2], a, b, 12)
+    if report_noise is None:
+        raise SystemExit("--report needs the noise curve the residual is judged against: --report_noise a,b (var = a * m - b in DN of the "
+                         "frames), --report_noise auto (estimated from the footage), --report_noise iso3200 / iso12800 (a checkpoint "
+                         "family's curve, rescaled to --bit_depth) -- or --match_noise, whose --match_iso curve then serves")
+    if report_noise == 'auto':
+        return (report, "auto", None, None, int(bit_depth))
+    if report_noise.startswith('iso'):
+        try:
+            iso = int(report_noise[3:])
+            a, b = dpc_iso_curve(iso, bit_depth)
+        except ValueError:
+            raise SystemExit("--report_noise %s: the families are %s" % (report_noise, ', '.join('iso%d' % k for k in DPC_ISO_CURVES)))
+        return (report, "iso%d" % iso, a, b, int(bit_depth))
+    f = report_noise.split(',')
+    try:
+        a, b = (float(v) for v in f)
+    except ValueError:
+        raise SystemExit("--report_noise takes a,b, auto, iso3200 or iso12800, got %r" % report_noise)
+    if not abs(a) < float("inf") or not abs(b) < float("inf"):
+        raise SystemExit("--report_noise: a and b must be finite, got %r" % report_noise)
+    return (report, "a,b", a, b, int(bit_depth))
+
+
+REPORT_KEYS = ("ratio", "ratio_lo", "ratio_hi", "bias", "rho", "a_fit", "b_fit", "samples", "bins")
+
+
+def report_record(acc, frames, spec, **names):
+    """One record of --report: `names` (the video's key, ...), the frames measured, the fields of `runtime.resid_fit` on `acc` -- None,
+    with "error": the library's message, where the fit refuses (fewer than 4 usable level bins) -- and the curve it was judged against."""
+    from .runtime import resid_fit
+    _, source, a, b, unit = spec
+    rec = dict(names, frames=int(frames))
+    try:
+        rec.update(resid_fit(acc, unit, a, b))
+    except RuntimeError as err:
+        rec.update({k: None for k in REPORT_KEYS}, error=str(err))
+    rec["curve"] = {"a": a, "b": b, "bit_depth": unit, "source": source}
+    return rec

@@ -206,6 +206,63 @@ def cut_score(a, b, hh: int, ww: int) -> Tuple[float, float]:
     return float(out[0]), float(out[1])
 
 
+RESID_ACC_BYTES = C.sizeof(_lib.RvddResidAcc)     # struct rvdd_resid_acc: six arrays of 64 64-bit words
+RESID_FIELDS = tuple(name for name, _ in _lib.RvddResidAcc._fields_)
+RESID_REPORT_FIELDS = tuple(name for name, _ in _lib.RvddResidReport._fields_ if name != "reserved")
+
+
+def _resid_struct(acc, what: str) -> "_lib.RvddResidAcc":
+    """ONE struct rvdd_resid_acc on the host: the struct itself, the dict `resid_acc_arrays` gives, or a tensor / array / bytes of its
+    3072 bytes (a device tensor is copied, which synchronises)"""
+    import numpy as np
+    if isinstance(acc, _lib.RvddResidAcc):
+        return acc
+    if isinstance(acc, dict):
+        raw = b"".join(np.ascontiguousarray(np.asarray(acc[name]).astype(np.int64 if name in ("s1", "s11") else np.uint64)).tobytes()
+                       for name in RESID_FIELDS)
+    elif torch.is_tensor(acc):
+        raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()
+    else:
+        raw = np.ascontiguousarray(acc).tobytes() if isinstance(acc, np.ndarray) else bytes(acc)
+    if len(raw) != RESID_ACC_BYTES:
+        raise RuntimeError(f"{what}: an accumulator is {RESID_ACC_BYTES} bytes (struct rvdd_resid_acc), got {len(raw)}")
+    return _lib.RvddResidAcc.from_buffer_copy(raw)
+
+
+def resid_acc_arrays(acc):
+    """Accumulators of `RvddRuntime.resid_stats` / `resid_read` (a tensor [n,384] of 64-bit words, one struct, or any array / bytes of n
+    structs rvdd_resid_acc) as NumPy arrays on the host: {"n", "msum", "s2", "n11": uint64 [n,64]; "s1", "s11": int64 [n,64]}."""
+    import numpy as np
+    if isinstance(acc, _lib.RvddResidAcc):
+        raw = np.frombuffer(bytes(acc), np.uint8)
+    elif torch.is_tensor(acc):
+        raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy().reshape(-1)
+    else:
+        raw = np.ascontiguousarray(acc).view(np.uint8).reshape(-1) if isinstance(acc, np.ndarray) else np.frombuffer(bytes(acc), np.uint8)
+    if raw.size % RESID_ACC_BYTES:
+        raise RuntimeError(f"resid_acc_arrays: an accumulator is {RESID_ACC_BYTES} bytes (struct rvdd_resid_acc), got {raw.size}")
+    words = raw.view(np.uint64).reshape(-1, 6, 64)
+    return {name: (words[:, k].view(np.int64) if name in ("s1", "s11") else words[:, k]).copy() for k, name in enumerate(RESID_FIELDS)}
+
+
+def resid_add(a, b):
+    """the sum of two accumulators as `resid_acc_arrays` gives them (modulo 2^64, as the device adds)"""
+    return {name: a[name] + b[name] for name in RESID_FIELDS}
+
+
+def resid_fit(acc, bit_depth: int, a: float, b: float) -> Dict[str, float]:
+    """ONE accumulator judged against the curve var(m) = a * m - b in DN of `bit_depth` (rvdd_resid_fit: on the host, no GPU needed).
+    acc: as `_resid_struct` takes it; a dict of [1,64] or [64] arrays is one accumulator.  -> {"ratio", "ratio_lo", "ratio_hi", "bias",
+    "rho", "a_fit", "b_fit", "samples", "bins"}; RuntimeError with the library's message where fewer than 4 level bins are usable."""
+    lib = _lib.load()
+    host = _resid_struct(acc, "resid_fit")
+    out = _lib.RvddResidReport()
+    rc = lib.rvdd_resid_fit(C.byref(host), int(bit_depth), float(a), float(b), C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"rvdd_resid_fit failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    return {name: (int if name in ("samples", "bins") else float)(getattr(out, name)) for name in RESID_REPORT_FIELDS}
+
+
 def nearest_iso(a: float, b: float, bit_depth: int = 12, levels=(0.20, 0.45, 0.80)):
     """Which of DPC_ISO_CURVES lies closest to the curve (a, b) in DN of `bit_depth`: -> (iso, ratios), the ISO whose predicted
     standard deviation at 20 %, 45 % and 80 % of 2^bit_depth - 1 is nearest in the log (the largest |log ratio| over the levels is
@@ -695,6 +752,35 @@ class RvddRuntime:
         correction of `set_dpc`), the outputs mapped back; flows are still matched on the sensor's own gray planes.
         cfg = `match_cfg(...)`, None = off (the default)."""
         self._check(self.lib.rvdd_set_match(self.h, None if cfg is None else C.byref(cfg)), "rvdd_set_match")
+
+    # -- denoised footage checked without ground truth ---------------------------------------
+    def resid_stats(self, packed: torch.Tensor, rgb: torch.Tensor, bit_depth: int = 12, pattern: Optional[str] = None,
+                    acc: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The residual statistics of noisy packed frames [n,4,hh,ww] against the outputs for them, rgb [n,3,2hh,2ww], added to `acc`
+        (rvdd_resid_stats): a device int64 tensor [n,384], one struct rvdd_resid_acc per frame -- None = a new zeroed one -- which is
+        returned.  pattern: one of BAYER_PATTERNS, None = the pattern set_option("bayer_pattern", ...) gave this runtime.
+        `resid_acc_arrays(acc)` gives the sums, `resid_fit` judges one accumulator against a curve.  Nothing is synchronised."""
+        pat = self._pattern(pattern, "resid_stats")
+        packed, n, hh, ww = _frames(packed, 4, "resid_stats: packed is [n,4,hh,ww]", "packed", self.device)
+        rgb = _dev_tensor(rgb, "rgb", self.device, shape=(n, 3, 2 * hh, 2 * ww),
+                          form=f"resid_stats: rgb is a float32 tensor [{n},3,{2 * hh},{2 * ww}], the outputs of packed")
+        acc = _out_or_new(acc, "resid_stats: acc", (n, RESID_ACC_BYTES // 8), self._tdev, torch.int64, zero=True, nbytes=n * RESID_ACC_BYTES,
+                          form=f"resid_stats: acc is a contiguous int64 tensor of {n} x {RESID_ACC_BYTES // 8} words on cuda:{self.device}")
+        self._check(self.lib.rvdd_resid_stats(self.h, _ptr(packed), _ptr(rgb), n, hh, ww, pat, int(bit_depth), _ptr(acc), self._stream()),
+                    "rvdd_resid_stats")
+        return acc
+
+    def set_resid(self, on: bool = True):
+        """The measurement as a stage of `video_push` (rvdd_set_resid): every output is measured against its centre frame -- as
+        corrected and as mapped -- into the slot's accumulator, which `resid_read` fetches.  With `set_match` on the unit is 12-bit DN,
+        the checkpoint curve's; otherwise the push's bit depth."""
+        self._check(self.lib.rvdd_set_resid(self.h, 1 if on else 0), "rvdd_set_resid")
+
+    def resid_read(self, slot: int):
+        """Slot `slot`'s accumulator as `resid_acc_arrays` gives one ([1,64] arrays), zeroed on the device (rvdd_resid_read; synchronises)."""
+        host = _lib.RvddResidAcc()
+        self._check(self.lib.rvdd_resid_read(self.h, int(slot), C.byref(host), self._stream()), "rvdd_resid_read")
+        return resid_acc_arrays(host)
 
     def set_dpc(self, cfg=None):
         """The correction as a stage of `video_push`, between the ingest and the kept frames (rvdd_set_dpc): cfg = `dpc_cfg(...)`,
