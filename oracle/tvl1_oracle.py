@@ -11,8 +11,9 @@ function citing the C lines it follows, including the quirks a reader would "fix
   * `hypot` runs in double and is rounded to float (tvl1flow_lib.c:224-225).
 
 Parity status: PINNED against the reference itself compiled from its own sources
-(`oracle/Makefile` -> `oracle/_ref/libBridge.so`): tests/test_tvl1_oracle.py checks this file
-against it when the library is present, and against golden flows generated with it
+(`oracle/Makefile` -> `oracle/_ref/libBridge.so`): tests/test_tvl1.py (smooth pairs) and
+tests/test_tvl1_hard_host.py (the hard pairs of tests/hard_pairs.py) check this file against it
+when the library is present, and against golden flows generated with it
 (tests/golden/tvl1_*.npz, tools/make_golden_tvl1.py) everywhere else.  The reference sums its
 convergence error with an OpenMP reduction, so its iteration count near the threshold -- and hence
 its flow in the last digits -- depends on the thread count; comparisons are by tolerance.
