@@ -427,7 +427,7 @@ enum rvdd_push { RVDD_PUSH_NEXT = 0, RVDD_PUSH_FIRST = 1, RVDD_PUSH_IDLE = 2 };
  *       push whose outputs have no TV-L1 pair at all runs no TV-L1, its step reads a zeroed flow tensor.
  * The handle keeps the last 2 + future ingested frames of every slot (packed and gray) on the device: allocated by the
  * first push, freed with the handle (20 (2 + future) + 24 (1 + future) bytes per raw cell and slot with the flow batch's
- * buffers; 4 more with option "stream_flow_from_denoised", 16 more with rvdd_set_dpc, and 3072 bytes per slot with rvdd_set_resid, each allocated by the
+ * buffers; 4 more with option "stream_flow_from_denoised", 16 more with rvdd_set_dpc, 3072 bytes per slot with rvdd_set_resid and 10 hh + 24 bytes per slot with rvdd_set_rows, each allocated by the
  * first push that has it on).  For the ready slots a push is exactly the existing path: rvdd_tvl1flow_batch(I0 = gray[centre],
  * I1 = gray[previous]) and, with a future frame, (gray[centre], gray[next]) for all of them in ONE batch call in the form of
  * option "tvl1_async" 1 (whatever the option says), then one rvdd_step_strided on the kept packed frames and those flows.  A
@@ -795,6 +795,85 @@ int rvdd_set_resid(rvdd_t* h, int32_t on);
  * where the loop synchronises anyway (the end of a video or of a shot).  All zeros on a handle that never pushed with the stage on.
  * RVDD_ERR_ARG: NULL host_out, slot outside 0 .. cfg.batch - 1. */
 int rvdd_resid_read(rvdd_t* h, int32_t slot, rvdd_resid_acc* host_out /* HOST */, void* stream /* synchronised */);
+
+/* ---- row noise (banding) ---------------------------------------------------------- */
+
+/* The readout of a CMOS sensor adds to every sample of a mosaic row one offset that changes from row to row and from frame to frame:
+ * horizontal banding that flickers.  It is common to the two colours of the mosaic row, so ONE offset is estimated per frame i, row
+ * parity j (planes k = 2j and 2j + 1 of the packed [n,4,hh,ww] tensor, channel k = CFA position (k >> 1, k & 1)) and plane row r, from
+ * the 2 ww samples of the row, and taken out of both planes.  Every operation is rounded to f32 on its own (no fused multiply-add):
+ * offsets, states, counts and the corrected samples are reproducible bit for bit in NumPy f32 (tests/rows_ref.py).  With
+ * top = (float)(2^bit_depth - 1), dn(v) = ((v + 1) * 0.5) * top and rvdd_dpc's way back 2 * (dn / top) - 1:
+ *   per sample (k, r, c):
+ *     x   = dn(p[k][r][c]); the eight vertical neighbours dn(p[k][r + dr][c]), dr in {+-1, +-2, +-3, +-4}, an index outside the plane
+ *           mirrored about the site (r + dr -> r - dr: hence hh >= 5); where r - dr lies outside as well -- only in planes of fewer than
+ *           nine rows -- it is reflected about the plane's edge (-q -> q, hh - 1 + q -> hh - 1 - q)
+ *     m   = (s3 + s4) * 0.5, s3 / s4 the 4th / 5th of the eight in ascending order;  d = x - m
+ *     var = fmaxf(noise_a * m - noise_b, var_floor)       the noise curve in DN of this bit depth
+ *     the sample is USED iff d * d <= (k_gate * k_gate) * var      (edges, texture and defects fall outside the gate)
+ *   per row (i, j, r):
+ *     cnt = the used samples among the 2 ww.  The row is APPLIED iff cnt > 0 and 2 * cnt >= 2 * ww (integers: a row with exactly half
+ *           of its samples used is applied), else SKIPPED with o = 0
+ *     o   = (v[(cnt - 1) / 2] + v[cnt / 2]) * 0.5 of the used d in ascending order (d is never -0 under round-to-nearest: sorting by
+ *           value is unambiguous), then clamped to [-max_dn, +max_dn]; the row is CLAMPED if the clamp changed it
+ *   apply: in a row that is applied with o != 0 every sample of planes 2j and 2j + 1 becomes 2 * ((x - o) / top) - 1 (no clamp to the
+ *     range); every other sample keeps its bits, and a frame in which no row has a non-zero offset is a bit copy.  gray [n,hh,ww]
+ *     (nullable, patched IN PLACE): a gray row r in which at least one of the two parities has a non-zero offset is rewritten as
+ *     (((d0 + d1) + d2) + d3) * 0.25 with d_k = dn(p[k][r][c]) - o[k >> 1][r]; every other gray row is not written.
+ * What it cannot do: the median of eight vertical neighbours is itself shifted by THEIR rows' offsets, so about 0.4 of the offsets'
+ * amplitude stays behind as a slow vertical drift that cannot be told from scene shading -- a limit of any single-frame rule without
+ * optically black columns.  Rows that a long horizontal edge crosses are skipped, or biased by less than the gate.
+ * Column fixed-pattern noise, offsets per plane and the use of the previous frame are out of scope.  Nothing is measured on real footage.
+ * On footage WITHOUT row noise the estimate has an rms of about 1.35 sqrt(var / (2 ww)) of its own, which the stage then adds.
+ *
+ * rvdd_rows_estimate writes offsets (DEVICE float [n,2,hh]) and state (DEVICE uint8 [n,2,hh]: 0 skipped, 1 applied, 2 applied and
+ * clamped), every word, and ADDS the rows of frame i to acc[i] (DEVICE, nullable, 8-byte aligned; integer atomics, the caller zeroes):
+ * `applied` counts the rows of state 1 and 2, `clamped` those of state 2, sum_q2 is the sum of q * q with q = (int)rintf(o * 16), o as
+ * written.  One workgroup per (frame, parity, row); the median of the used d is exact and takes the same steps whatever the values
+ * (a digit-wise search of the keys' bit patterns: no histogram, no sorting of the row).  ww <= 4096.
+ * rvdd_rows_apply takes the offsets out IN PLACE: a pure stream.  With ww % 4 == 0 and packed / gray 16-byte aligned a thread owns four
+ * neighbouring cells (16-byte loads and stores), every other case one cell.  Same bits either way.
+ * Inputs are assumed finite: with NaN or inf the result is unspecified, but nothing outside the tensors is read or written.
+ * RVDD_ERR_ARG (the message names the argument) and nothing launched: NULL cfg; k_gate or max_dn not > 0 or not finite; noise_a /
+ * noise_b not finite; var_floor not > 0 (or not finite); bit_depth outside 1..16; hh < 5; ww < 1 or > 4096; n < 0; NULL packed /
+ * offsets / state with n > 0; acc not 8-byte aligned; a launch of more than 2^31 - 1 blocks.  n = 0 does nothing.  Asynchronous and
+ * stream-ordered; nothing is read back. */
+typedef struct rvdd_rows_cfg {
+    float k_gate;             /* the gate in standard deviations of the noise curve, around 3 */
+    float noise_a, noise_b;   /* var(m) = noise_a * m - noise_b, in DN of the frames' bit depth */
+    float var_floor;          /* the least variance assumed, > 0 */
+    float max_dn;             /* the largest offset taken out, in DN, > 0 */
+} rvdd_rows_cfg;
+typedef struct rvdd_rows_acc {   /* 24 bytes */
+    uint32_t applied;         /* rows with an offset (state 1 or 2) */
+    uint32_t skipped;         /* rows without (state 0) */
+    uint32_t clamped;         /* rows whose offset met the clamp (state 2) */
+    uint32_t reserved;        /* 0 */
+    int64_t sum_q2;           /* sum of q * q, q = (int)rintf(o * 16): the rms offset is sqrt(sum_q2 / applied) / 16 DN */
+} rvdd_rows_acc;
+int rvdd_rows_estimate(rvdd_t* h, const float* packed /* [n,4,hh,ww] */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+                       const rvdd_rows_cfg* cfg, float* offsets /* DEVICE [n,2,hh] */, uint8_t* state /* DEVICE [n,2,hh] */,
+                       rvdd_rows_acc* acc /* DEVICE [n], nullable, accumulated */, void* stream);
+int rvdd_rows_apply(rvdd_t* h, float* packed /* [n,4,hh,ww], IN PLACE */, float* gray /* [n,hh,ww], nullable, in place */,
+                    const float* offsets /* DEVICE [n,2,hh] */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream);
+
+/* The correction as a stage of rvdd_video_push: cfg = the parameters of rvdd_rows_estimate (checked as there: RVDD_ERR_ARG, the
+ * message names the field, and nothing changes), NULL = off, the default.  Per handle; synchronises the device, as rvdd_set_dpc does;
+ * off -> on zeroes the accumulators.  With the stage on a push runs, for every run of slots that got a frame, rvdd_rows_estimate and
+ * rvdd_rows_apply on the ring's packed frames and gray planes IN PLACE with the push's bit_depth and cfg's curve -- the sensor's own,
+ * in the DN of the footage -- behind rvdd_set_dpc_map and rvdd_set_dpc (defects are outliers that the gate drops anyway, but a
+ * corrected sample counts) and in front of rvdd_set_match: two launches per run.  Everything downstream reads the ring, so the
+ * corrected frames are what TV-L1 matches, what the step denoises, what rvdd_set_resid compares against and what option
+ * "stream_all_frames" copies for a head or a tail, under every "stream_container".  The first push with the stage on allocates
+ * offsets, states and one rvdd_rows_acc per slot (10 hh + 24 bytes per slot, freed with the handle); frames of hh < 5 or ww > 4096
+ * cells are RVDD_ERR_ARG then.  With the stage off a push makes exactly the launches it made before and allocates nothing; a frame
+ * whose offsets are all zero leaves the ring bit for bit what a push without the stage leaves. */
+int rvdd_set_rows(rvdd_t* h, const rvdd_rows_cfg* cfg /* NULL = off, the default */);
+
+/* Slot `slot`'s accumulator copied to *host_out and zeroed on the device, both on `stream`, which is then synchronised: call it where
+ * the loop synchronises anyway (the end of a video or of a shot).  All zeros on a handle that never pushed with the stage on.
+ * RVDD_ERR_ARG: NULL host_out, slot outside 0 .. cfg.batch - 1. */
+int rvdd_rows_read(rvdd_t* h, int32_t slot, rvdd_rows_acc* host_out /* HOST */, void* stream /* synchronised */);
 
 /* ---- raw datasets from sRGB video ------------------------------------------- */
 

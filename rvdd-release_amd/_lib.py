@@ -74,6 +74,16 @@ class RvddResidReport(C.Structure):
                 ("a_fit", C.c_double), ("b_fit", C.c_double), ("samples", C.c_uint64), ("bins", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RvddRowsCfg(C.Structure):
+    """struct rvdd_rows_cfg (rvdd_rows_estimate, rvdd_set_rows)"""
+    _fields_ = [("k_gate", C.c_float), ("noise_a", C.c_float), ("noise_b", C.c_float), ("var_floor", C.c_float), ("max_dn", C.c_float)]
+
+
+class RvddRowsAcc(C.Structure):
+    """struct rvdd_rows_acc (rvdd_rows_estimate, rvdd_rows_read): 24 bytes"""
+    _fields_ = [("applied", C.c_uint32), ("skipped", C.c_uint32), ("clamped", C.c_uint32), ("reserved", C.c_uint32), ("sum_q2", C.c_int64)]
+
+
 # symbol -> (restype, argtypes); exactly the functions include/rvdd.h declares
 _P = C.c_void_p
 _PROTOS = {
@@ -127,6 +137,10 @@ _PROTOS = {
     "rvdd_resid_fit": (C.c_int, [C.POINTER(RvddResidAcc), C.c_int32, C.c_double, C.c_double, C.POINTER(RvddResidReport)]),
     "rvdd_set_resid": (C.c_int, [_P, C.c_int32]),
     "rvdd_resid_read": (C.c_int, [_P, C.c_int32, C.POINTER(RvddResidAcc), _P]),
+    "rvdd_rows_estimate": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddRowsCfg), _P, _P, _P, _P]),
+    "rvdd_rows_apply": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "rvdd_set_rows": (C.c_int, [_P, C.POINTER(RvddRowsCfg)]),
+    "rvdd_rows_read": (C.c_int, [_P, C.c_int32, C.POINTER(RvddRowsAcc), _P]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                  _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),

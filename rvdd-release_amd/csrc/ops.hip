@@ -62,6 +62,27 @@ int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* ou
     return RVDD_OK;
 }
 
+int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out) {
+    if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
+    if (!(cfg->k_gate > 0.0f) || !std::isfinite(cfg->k_gate)) return fail(h, RVDD_ERR_ARG, "%s: k_gate must be finite and > 0, got %g", fn, cfg->k_gate);
+    if (!std::isfinite(cfg->noise_a)) return fail(h, RVDD_ERR_ARG, "%s: noise_a must be finite, got %g", fn, cfg->noise_a);
+    if (!std::isfinite(cfg->noise_b)) return fail(h, RVDD_ERR_ARG, "%s: noise_b must be finite, got %g", fn, cfg->noise_b);
+    if (!(cfg->var_floor > 0.0f) || !std::isfinite(cfg->var_floor)) return fail(h, RVDD_ERR_ARG, "%s: var_floor must be finite and > 0, got %g", fn, cfg->var_floor);
+    if (!(cfg->max_dn > 0.0f) || !std::isfinite(cfg->max_dn)) return fail(h, RVDD_ERR_ARG, "%s: max_dn must be finite and > 0, got %g", fn, cfg->max_dn);
+    // the square rounded to f32 once, here (+inf for a huge gate: every finite sample is used)
+    *out = RowsParams{cfg->k_gate * cfg->k_gate, cfg->noise_a, cfg->noise_b, cfg->var_floor, cfg->max_dn, 0.0f};
+    return RVDD_OK;
+}
+
+int rows_shape(rvdd_t* h, const char* fn, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth) {
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 1..16, got %d", fn, bit_depth);
+    if (hh < 5) return fail(h, RVDD_ERR_ARG, "%s: hh must be >= 5 (four vertical neighbours on either side, mirrored about the site), got %d", fn, hh);
+    if (ww < 1) return fail(h, RVDD_ERR_ARG, "%s: ww must be >= 1, got %d", fn, ww);
+    if (ww > rows_max_ww()) return fail(h, RVDD_ERR_ARG, "%s: ww must be <= %d (a workgroup holds the 2 ww samples of a row in registers), got %d", fn, rows_max_ww(), ww);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    return RVDD_OK;
+}
+
 int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg) {
     if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
     if (!(cfg->scale > 0.0f) || !std::isfinite(cfg->scale)) return fail(h, RVDD_ERR_ARG, "%s: scale must be finite and > 0, got %g", fn, cfg->scale);
@@ -451,6 +472,37 @@ int rvdd_resid_stats(rvdd_t* h, const float* packed, const float* rgb, int32_t n
         return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
     ENTER(h);
     HIPCHK(h, launch_resid(packed, rgb, n, hh, ww, pattern, bit_depth, acc, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_rows_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, const rvdd_rows_cfg* cfg,
+                       float* offsets, uint8_t* state, rvdd_rows_acc* acc, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    RowsParams p;
+    RC(rows_params(h, "rvdd_rows_estimate", cfg, &p));
+    RC(rows_shape(h, "rvdd_rows_estimate", n, hh, ww, bit_depth));
+    if (reinterpret_cast<uintptr_t>(acc) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: acc must be 8-byte aligned (sum_q2 is a 64-bit atomic)");
+    if (n == 0) return RVDD_OK;
+    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: packed is required");
+    if (!offsets) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: offsets is required");
+    if (!state) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: state is required");
+    if (rows_estimate_blocks(n, hh) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: n * 2 * hh = %d * 2 * %d needs a launch of more than 2^31 - 1 blocks", n, hh);
+    ENTER(h);
+    HIPCHK(h, launch_rows_estimate(packed, n, hh, ww, bit_depth, p, offsets, state, acc, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
+int rvdd_rows_apply(rvdd_t* h, float* packed, float* gray, const float* offsets, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    RC(rows_shape(h, "rvdd_rows_apply", n, hh, ww, bit_depth));
+    if (n == 0) return RVDD_OK;
+    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: packed is required");
+    if (!offsets) return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: offsets is required");
+    if (rows_apply_blocks(n, hh, ww, rows_apply_wide(packed, gray, ww), nullptr) < 0)
+        return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
+    ENTER(h);
+    HIPCHK(h, launch_rows_apply(packed, gray, offsets, n, hh, ww, bit_depth, static_cast<hipStream_t>(stream)));
     return RVDD_OK;
 }
 

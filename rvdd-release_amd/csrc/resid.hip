@@ -28,17 +28,6 @@ constexpr int kResidThreads = 256;
 constexpr int kResidGroups = 128;         // workgroups per frame at most: what meets on one word of a flat frame's accumulator
 constexpr int kResidWords = 6 * 64;       // struct rvdd_resid_acc as 64-bit words: [quantity][bin]
 
-// the sum of v over the 64 lanes of a wave (DPP; every lane must be active): wave-uniform
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);      // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);      // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);      // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);      // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true);      // row_bcast:15 into rows 1, 3
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true);      // row_bcast:31 into rows 2, 3
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 struct Sample {
     int rq, j;
     unsigned mq;

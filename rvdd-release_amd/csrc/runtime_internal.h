@@ -263,6 +263,15 @@ struct rvdd_handle {
         rvdd_resid_acc* acc = nullptr;   // DEVICE [B]: one accumulator per slot (allocated by the first push that has the stage on)
     } resid;
 
+    // rvdd_set_rows: row noise taken out of the ring's frames behind the correction (rvdd_video_push), counted for rvdd_rows_read
+    struct Rows {
+        bool on = false;
+        RowsParams p{};                  // the checked parameters (rows_params)
+        float* offsets = nullptr;        // DEVICE [B][2][hh]: the offsets of every slot's last frame (allocated by the first push that has the stage on)
+        uint8_t* state = nullptr;        // DEVICE [B][2][hh]
+        rvdd_rows_acc* acc = nullptr;    // DEVICE [B]: one accumulator per slot
+    } rows;
+
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
         const void* p[6];
@@ -452,6 +461,8 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s);
 // ---- ops.hip
 // the checks rvdd_dpc and rvdd_set_dpc share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
 int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* out);
+// the checks rvdd_rows_estimate and rvdd_set_rows share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
+int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out);
 // the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
 int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg);
 int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,

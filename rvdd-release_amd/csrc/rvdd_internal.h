@@ -152,6 +152,16 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
     v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true));      // row_bcast:31 into rows 2, 3
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
+// the sum of v over the 64 lanes of a wave (DPP; every lane must be active): wave-uniform
+__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);      // row_shr:1
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);      // row_shr:2
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);      // row_shr:4
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);      // row_shr:8
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true);      // row_bcast:15 into rows 1, 3
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true);      // row_bcast:31 into rows 2, 3
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
 // the reader's side: lane l < kAmaxLines holds word l of its sequence (other lanes 0) -> the maximum, wave-uniform
 __device__ __forceinline__ unsigned amax_lines_max(unsigned v) {
     v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));
@@ -464,6 +474,25 @@ hipError_t launch_resid(const float* packed, const float* rgb, int n, int hh, in
 // than 2^31 - 1 blocks, or tensors whose element offsets leave 64 bits
 bool resid_wide(const float* packed, const float* rgb, int ww);
 int64_t resid_blocks(int n, int hh, int ww, bool wide, int* groups);
+
+// rows.hip -- row noise: one offset per frame, row parity and plane row (rvdd_rows_estimate, rvdd_rows_apply, the stage behind rvdd_set_rows)
+struct rvdd_rows_acc;
+// k2 = k_gate * k_gate rounded to f32 (formed once on the host); top is filled in by the launch
+struct RowsParams {
+    float k2, a, b, floor, max_dn, top;
+};
+// offsets / state [n][2][hh] (DEVICE, every word written) of packed [n][4][hh][ww], the rows' counts added to acc[i] (DEVICE, nullable);
+// one workgroup per (frame, parity, row).  hh >= 5, 1 <= ww <= rows_max_ww(); n <= 0 launches nothing
+hipError_t launch_rows_estimate(const float* packed, int n, int hh, int ww, int bit_depth, const RowsParams& p, float* offsets, uint8_t* state,
+                                rvdd_rows_acc* acc, hipStream_t s);
+int rows_max_ww();                                // the widest plane a workgroup's registers hold
+int64_t rows_estimate_blocks(int n, int hh);      // the grid of that launch; -1 = more than 2^31 - 1 blocks
+// packed [n][4][hh][ww] IN PLACE, gray [n][hh][ww] (nullable) in place: offsets [n][2][hh] taken out of the rows where they are not zero
+hipError_t launch_rows_apply(float* packed, float* gray, const float* offsets, int n, int hh, int ww, int bit_depth, hipStream_t s);
+// whether that launch takes the wide form (a thread owns four cells), and its grid (*per_frame: the blocks of one frame); -1 = more
+// than 2^31 - 1 blocks
+bool rows_apply_wide(const float* packed, const float* gray, int ww);
+int64_t rows_apply_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame);
 
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from

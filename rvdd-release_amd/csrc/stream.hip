@@ -68,6 +68,15 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     // rvdd_set_resid: one accumulator per slot, allocated (zeroed) by the first push that has the stage on
     auto& resid = h->resid;
     if (resid.on && !resid.acc) RC(dmalloc(h, reinterpret_cast<void**>(&resid.acc), (size_t)B * sizeof(rvdd_resid_acc)));
+    // rvdd_set_rows: offsets, states and one accumulator per slot, allocated (zeroed) by the first push that has the stage on
+    auto& rows = h->rows;
+    if (rows.on && hh < 5) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with rvdd_set_rows hh must be >= 5, got %d cell rows", hh);
+    if (rows.on && ww > rows_max_ww()) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with rvdd_set_rows ww must be <= %d, got %d cells", rows_max_ww(), ww);
+    if (rows.on && !rows.acc) {
+        RC(dmalloc(h, reinterpret_cast<void**>(&rows.offsets), (size_t)B * 2 * hh * sizeof(float)));
+        RC(dmalloc(h, reinterpret_cast<void**>(&rows.state), (size_t)B * 2 * hh));
+        RC(dmalloc(h, reinterpret_cast<void**>(&rows.acc), (size_t)B * sizeof(rvdd_rows_acc)));      // last: the mark of a complete allocation
+    }
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
         if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
@@ -91,6 +100,17 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         if (dmap.on && dmap.ncells)
             HIPCHK(h, launch_dpc_map_apply(packed, ring_gray, e - b, hh, ww, bit_depth, dmap.mask, dmap.cells, dmap.ncells, s));
         if (dpc.on) HIPCHK(h, launch_dpc(packed, ring_packed, ring_gray, e - b, hh, ww, bit_depth, dpc.p, dpc.counts + 2 * (size_t)b, s));
+        // rvdd_set_rows: the row offsets of the (corrected) frames estimated and taken out of the ring's planes and gray planes in place
+        if (rows.on) {
+            const double cells = (double)(e - b) * 4.0 * (double)hw;
+            {
+                Scope sc(h, s, "rows_estimate_kernel", 0.0, cells * 4.0);
+                HIPCHK(h, launch_rows_estimate(ring_packed, e - b, hh, ww, bit_depth, rows.p, rows.offsets + (size_t)b * 2 * hh,
+                                               rows.state + (size_t)b * 2 * hh, rows.acc + b, s));
+            }
+            Scope sc(h, s, "rows_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
+            HIPCHK(h, launch_rows_apply(ring_packed, ring_gray, rows.offsets + (size_t)b * 2 * hh, e - b, hh, ww, bit_depth, s));
+        }
         // the gray planes stay the sensor's: TV-L1 matches what it always matched
         if (match.on) HIPCHK(h, launch_match(ring_packed, ring_packed, (int64_t)(e - b) * 4 * (int64_t)hw, match.cfg.scale, match.cfg.offset, false, s));
         return RVDD_OK;
@@ -244,6 +264,36 @@ extern "C" int rvdd_set_match(rvdd_t* h, const rvdd_match_cfg* cfg) {
     HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight keep the coefficients they were enqueued with
     h->match.on = cfg != nullptr;
     if (cfg) h->match.cfg = *cfg;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_set_rows(rvdd_t* h, const rvdd_rows_cfg* cfg) {
+    if (!h) return RVDD_ERR_ARG;
+    RowsParams p{};
+    if (cfg) RC(rows_params(h, "rvdd_set_rows", cfg, &p));
+    ENTER(h);
+    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight keep the parameters they were enqueued with; the accumulators must be at rest
+    auto& rows = h->rows;
+    if (cfg && !rows.on && rows.acc) HIPCHK(h, hipMemset(rows.acc, 0, (size_t)h->cfg.batch * sizeof(rvdd_rows_acc)));      // switched on: from zero
+    rows.on = cfg != nullptr;
+    if (cfg) rows.p = p;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_rows_read(rvdd_t* h, int32_t slot, rvdd_rows_acc* host_out, void* stream) {
+    if (!h) return RVDD_ERR_ARG;
+    if (!host_out) return fail(h, RVDD_ERR_ARG, "rvdd_rows_read: host_out is required");
+    if (slot < 0 || slot >= h->cfg.batch) return fail(h, RVDD_ERR_ARG, "rvdd_rows_read: slot must be 0 .. %d, got %d", h->cfg.batch - 1, slot);
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto& rows = h->rows;
+    if (rows.acc) {
+        HIPCHK(h, hipMemcpyAsync(host_out, rows.acc + slot, sizeof(rvdd_rows_acc), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemsetAsync(rows.acc + slot, 0, sizeof(rvdd_rows_acc), s));
+    } else {
+        std::memset(host_out, 0, sizeof(rvdd_rows_acc));
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
     return RVDD_OK;
 }
 

@@ -88,6 +88,22 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       The thresholds rest on synthetic scenes of 128 x 192 cells and more; NOTHING is measured on
                       real footage.  Look-alike shots and fades are not found, which leaves today's behaviour.  --dpc_noise auto still
                       reads the first frames of every FOLDER.  Without --cuts no new call is made and the output files keep their bytes.
+  --row_noise K       take row noise (horizontal banding that flickers: one readout offset per mosaic row and frame) out of every frame
+                      on the device (`rvdd_set_rows`), behind --dpc_map / --dpc and in front of --match_noise: per frame, row parity and
+                      plane row one offset is the median, over the row's two colour planes, of every sample's difference to the median
+                      of its eight vertical same-colour neighbours; samples further than K standard deviations of the noise curve from
+                      that median (edges, texture, defects) are left out, a row with fewer than half of its samples left is not touched.
+                      K is around 3.  TV-L1, the network and --report see the corrected frames.  Prints, per video (per shot under
+                      --cuts), `rows: <applied> applied, <skipped> skipped, <clamped> clamped rows, rms offset <x> DN (the estimate
+                      alone, on flat footage without row noise: <y> DN)`: y = 1.35 sqrt(var(mid level) / (2 ww)) is what the estimate
+                      finds in white noise; footage whose x sits at or near y has no row noise, and the flag should stay off -- it
+                      then only adds y.  About 0.4 of the offsets' amplitude stays behind as a slow vertical drift (the neighbours carry
+                      offsets too); rows crossed by a long horizontal edge are skipped or biased by less than the gate; column pattern
+                      noise is not touched; NOTHING is measured on real footage.
+  --row_noise_curve C the sensor's curve in DN of --bit_depth: a,b[,floor], auto (the run's own estimate, shared with --dpc_noise auto),
+                      iso3200 or iso12800.  Default: the curve of --dpc; without either it is an error.
+  --row_noise_max DN  the largest offset taken out (default (2^bit_depth - 1) / 64, a guess).
+                      Without --row_noise no new call is made and the output files keep their bytes.
   --report FILE       check the outputs without ground truth: if the output is the clean frame, noisy - remosaic(denoised) is the noise.
                       The stream reduces every output and its (corrected, matched) centre frame to residual statistics on the device
                       (`rvdd_set_resid`), read at the end of every video -- of every shot under --cuts -- and judged against a noise curve
@@ -116,9 +132,9 @@ import torch
 
 from . import _lib
 from . import tiffio
-from .footage import (add_dpc_arguments, add_report_arguments, dpc_arguments, estimate_noise, open_rawvideo, report_arguments, report_record,
-                      to_device)
-from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, match_coeffs, resid_add
+from .footage import (add_dpc_arguments, add_report_arguments, add_rows_arguments, dpc_arguments, estimate_noise, open_rawvideo,
+                      report_arguments, report_record, rows_arguments, rows_line, to_device)
+from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, match_coeffs, resid_add, rows_cfg
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
 # --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
@@ -343,6 +359,7 @@ def _parse(argv):
     p.add_argument('--out_bit_depth', type=int, default=None, help='bit depth of the sensor formats (default: --bit_depth)')
     p.add_argument('--all_frames', action='store_true', help='write every input frame, the first and the last of a video too')
     add_dpc_arguments(p)
+    add_rows_arguments(p)
     p.add_argument('--dpc_map', type=str, default=None, help='FILE: correct the sites of this defect map (python -m rvdd_release_amd.dpc_map '
                    'writes one); auto: find the map in the footage before streaming starts, with the rule of --dpc')
     p.add_argument('--dpc_map_frames', type=int, default=None, help='with --dpc_map auto: frames read per video, spread over it (default 16)')
@@ -368,6 +385,7 @@ def _parse(argv):
     opt.dpc_map = dpc_map_arguments(own.dpc_map, own.dpc_map_frames, own.dpc_map_share, own.dpc_map_tolerate, own.dpc_static_only,
                                     opt.dpc is not None)
     opt.dpc_static_only = own.dpc_static_only
+    opt.rows = rows_arguments(own.row_noise, own.row_noise_curve, own.row_noise_max, opt.dpc, int(opt.bit_depth))
     opt.match = match_arguments(own.match_noise, own.match_iso)
     opt.report = report_arguments(own.report, own.report_noise, opt.match, int(opt.bit_depth))
     opt.cuts = cuts_arguments(own.cuts, own, opt.future_patch_depth)
@@ -390,13 +408,17 @@ def _parse(argv):
 
 def prepasses(opt, dataset, dev):
     """What is decided on the run's own footage before any push, in this order: the noise curve of --dpc_noise auto / --match_noise auto
-    (ONE estimate for both, and for --report_noise auto), the defect map, the match coefficients, the shots.  Completes opt.dpc, opt.match
-    and opt.report; -> (dmap: the cellmask
+    (ONE estimate for both, for --row_noise_curve auto and for --report_noise auto), the defect map, the match coefficients, the shots.  Completes opt.dpc, opt.match
+    opt.rows and opt.report; -> (dmap: the cellmask
     or None, match: struct rvdd_match_cfg or None, shots [(key, [paths])])."""
     curve = None
     if opt.dpc is not None and opt.dpc[2] is None:
         curve = estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames)
         opt.dpc = opt.dpc[:2] + curve + opt.dpc[4:]
+    rows = getattr(opt, "rows", None)
+    if rows is not None and rows[2] is None:      # auto, or the curve of --dpc_noise auto: the one estimate
+        curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--row_noise_curve')
+        opt.rows = rows[:2] + curve + rows[4:]
     # --dpc_map: ONE map for the run, read or found before any push; --dpc_static_only: --dpc has named the rule and is done
     dmap = None if opt.dpc_map is None else find_dpc_map(dataset, dev, opt)
     if opt.dpc_static_only:
@@ -438,7 +460,7 @@ def write_frame(opt, rt, out_b, host_b, key, path, W):
 def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -> int:
     """The videos [(key, [paths])] of one frame size H x W through one runtime: its options and stages set, the videos dealt to the
     slots (`deal_slots`), every step pushed, its valid outputs taken to the host in one egress and written (`write_frame`), and the
-    `dpc:` line of every video that ended and, with --report, its record (`report_out`: {"file": the open file, "total": the sum of
+    `dpc:` and `rows:` lines of every video that ended and, with --report, its record (`report_out`: {"file": the open file, "total": the sum of
     the accumulators read so far or None, "frames": those they cover}).  -> the frames written."""
     layout, sample, _ = OUT_FORMATS[opt.out_format]
     depth = 8 if opt.out_format == "f32" else opt.out_bit_depth
@@ -458,6 +480,9 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
                          % (2 * dmap.shape[1], 2 * dmap.shape[0], videos[0][0], W, H))
     if dmap is not None:
         rt.set_dpc_map(dmap)
+    rows = getattr(opt, "rows", None)
+    if rows is not None:
+        rt.set_rows(rows_cfg(rows[0], *rows[2:]))
     rt.set_match(match)
     report = getattr(opt, "report", None)
     if report is not None:
@@ -509,6 +534,9 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
                     print('dpc: %d hot, %d dead samples corrected in %d frames (%s)'
                           % (now[b][0] - dpc_seen[b][0], now[b][1] - dpc_seen[b][1], dpc_frames[b], key))
                     dpc_seen[b] = now[b]
+            if rows is not None:                    # the slot's counts are this video's frames: read, which zeroes them
+                for b, key in ends:
+                    print(rows_line(rt.rows_read(b), dpc_frames[b], rows, int(opt.bit_depth), W // 2, key))
             if report is not None:                  # the slot's accumulator holds this video's outputs: read, which zeroes it
                 for b, key in ends:
                     acc = rt.resid_read(b)
@@ -520,6 +548,8 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
     rt.set_option("tvl1_async", 0)
     if report is not None:
         rt.set_resid(False)
+    if rows is not None:
+        rt.set_rows(None)
     return written
 
 

@@ -1,5 +1,5 @@
 """What the four footage commands (`denoise`, `noise`, `cuts`, `dpc_map`) share: opening the rawvideo dataset, host frames to the device
-and through the ingest, the `--dpc*` flags with the noise estimate they may ask for, and the `--report*` flags.  The commands import this module and the
+and through the ingest, the `--dpc*` flags with the noise estimate they may ask for, the `--row_noise*` flags and the `--report*` flags.  The commands import this module and the
 feature modules; nothing here or there imports a command.
 """
 from __future__ import annotations
@@ -106,6 +106,70 @@ def estimate_noise(dataset, dev, bit_depth, frames, flag='--dpc_noise'):
         raise SystemExit("%s auto: %s -- pass the curve as %s a,b" % (flag, err, flag))
     print('noise: ' + noise.format_line(r))
     return (r["a"], r["b"])
+
+
+def add_rows_arguments(p) -> None:
+    """the three flags of the row-noise correction, beside --dpc; `rows_arguments` reads them"""
+    p.add_argument('--row_noise', type=float, default=None, help='take row noise (banding) out of every frame on the device: the gate K in '
+                   'standard deviations of the noise curve, around 3')
+    p.add_argument('--row_noise_curve', type=str, default=None, help='the curve of --row_noise: a,b[,floor] (var = a * m - b in DN of the frames), '
+                   'auto (estimated from the footage), iso3200 or iso12800; default: the curve of --dpc')
+    p.add_argument('--row_noise_max', type=float, default=None, help='the largest offset taken out, in DN (default (2^bit_depth - 1) / 64)')
+
+
+def rows_arguments(row_noise, curve, max_dn, dpc, bit_depth):
+    """--row_noise / --row_noise_curve / --row_noise_max -> None (no --row_noise) or (k_gate, source, a, b, floor, max_dn): the gate, where
+    the curve var = a * m - b (DN of `bit_depth`) comes from -- "a,b", "iso<ISO>", "auto" (a and b None, for the command to estimate from
+    the footage) or "dpc" (dpc = what `dpc_arguments` returned: its curve and floor, a and b None under --dpc_noise auto) -- the least
+    variance and the clamp.  SystemExit where the flags do not fit together."""
+    if row_noise is None:
+        if curve is not None or max_dn is not None:
+            raise SystemExit("--row_noise_curve and --row_noise_max belong to --row_noise K")
+        return None
+    if not (row_noise > 0 and row_noise < float("inf")):
+        raise SystemExit("--row_noise is the gate in standard deviations, > 0 (around 3), got %r" % row_noise)
+    top = float((1 << int(bit_depth)) - 1)
+    max_dn = top / 64.0 if max_dn is None else float(max_dn)
+    if not (max_dn > 0 and max_dn < float("inf")):
+        raise SystemExit("--row_noise_max is the largest offset taken out in DN, > 0, got %r" % max_dn)
+    floor = 1.0
+    if curve is None:
+        if dpc is None:
+            raise SystemExit("--row_noise needs the sensor's noise curve: --row_noise_curve a,b[,floor] (var = a * m - b in DN of the frames), "
+                             "--row_noise_curve auto (estimated from the footage), --row_noise_curve iso3200 / iso12800 (a checkpoint "
+                             "family's curve, rescaled to --bit_depth) -- or the curve of --dpc, which then serves")
+        return (float(row_noise), "dpc", dpc[2], dpc[3], dpc[4], max_dn)
+    if curve == 'auto':
+        return (float(row_noise), "auto", None, None, floor, max_dn)
+    if curve.startswith('iso'):
+        try:
+            iso = int(curve[3:])
+            a, b = dpc_iso_curve(iso, bit_depth)
+        except ValueError:
+            raise SystemExit("--row_noise_curve %s: the families are %s" % (curve, ', '.join('iso%d' % k for k in DPC_ISO_CURVES)))
+        return (float(row_noise), "iso%d" % iso, a, b, floor, max_dn)
+    f = curve.split(',')
+    try:
+        if len(f) not in (2, 3):
+            raise ValueError(curve)
+        a, b = float(f[0]), float(f[1])
+        floor = float(f[2]) if len(f) == 3 else 1.0
+    except ValueError:
+        raise SystemExit("--row_noise_curve takes a,b[,floor], auto, iso3200 or iso12800, got %r" % curve)
+    if not abs(a) < float("inf") or not abs(b) < float("inf"):
+        raise SystemExit("--row_noise_curve: a and b must be finite, got %r" % curve)
+    if not (floor > 0 and floor < float("inf")):
+        raise SystemExit("--row_noise_curve: the floor must be > 0, got %r" % floor)
+    return (float(row_noise), "a,b", a, b, floor, max_dn)
+
+
+def rows_line(acc, frames, spec, bit_depth, ww, key):
+    """the `rows:` line of one video or shot: `acc` as `runtime.rows_acc_arrays` gives it, spec = what `rows_arguments` returned"""
+    from .runtime import rows_floor_rms, rows_rms
+    _, _, a, b, floor, _ = spec
+    return ('rows: %d applied, %d skipped, %d clamped rows, rms offset %.3f DN (the estimate alone, on flat footage without row noise: %.3f DN) '
+            'in %d frames (%s)' % (int(acc["applied"].sum()), int(acc["skipped"].sum()), int(acc["clamped"].sum()), rows_rms(acc),
+                                   rows_floor_rms(a, b, floor, bit_depth, ww), frames, key))
 
 
 def add_report_arguments(p) -> None:

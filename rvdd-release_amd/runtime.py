@@ -263,6 +263,55 @@ def resid_fit(acc, bit_depth: int, a: float, b: float) -> Dict[str, float]:
     return {name: (int if name in ("samples", "bins") else float)(getattr(out, name)) for name in RESID_REPORT_FIELDS}
 
 
+ROWS_ACC_BYTES = C.sizeof(_lib.RvddRowsAcc)       # struct rvdd_rows_acc: three counts, a reserved word, one 64-bit sum
+ROWS_FIELDS = ("applied", "skipped", "clamped", "sum_q2")
+ROWS_MAX_WW = 4096                                # the widest plane rvdd_rows_estimate takes
+
+
+def rows_cfg(k_gate: float, noise_a: float, noise_b: float, var_floor: float = 1.0, max_dn: float = 64.0) -> "_lib.RvddRowsCfg":
+    """struct rvdd_rows_cfg: the gate in standard deviations of the curve var(m) = noise_a * m - noise_b (DN of the frames' bit
+    depth), the least variance assumed, and the largest offset taken out (DN)."""
+    return _lib.RvddRowsCfg(float(k_gate), float(noise_a), float(noise_b), float(var_floor), float(max_dn))
+
+
+def rows_acc_arrays(acc) -> Dict[str, "object"]:
+    """Accumulators of `RvddRuntime.rows_estimate` (an int64 tensor [n,3] of 24-byte structs rvdd_rows_acc, one struct, or bytes) on
+    the host: {"applied", "skipped", "clamped": uint32 [n]; "sum_q2": int64 [n]}."""
+    import numpy as np
+    if isinstance(acc, _lib.RvddRowsAcc):
+        raw = np.frombuffer(bytes(acc), np.uint8)
+    elif torch.is_tensor(acc):
+        raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy().reshape(-1)
+    else:
+        raw = np.ascontiguousarray(acc).view(np.uint8).reshape(-1) if isinstance(acc, np.ndarray) else np.frombuffer(bytes(acc), np.uint8)
+    if raw.size % ROWS_ACC_BYTES:
+        raise RuntimeError(f"rows_acc_arrays: an accumulator is {ROWS_ACC_BYTES} bytes (struct rvdd_rows_acc), got {raw.size}")
+    words = raw.view(np.uint32).reshape(-1, 6)
+    return {"applied": words[:, 0].copy(), "skipped": words[:, 1].copy(), "clamped": words[:, 2].copy(),
+            "sum_q2": np.ascontiguousarray(words[:, 4:6]).view(np.int64).reshape(-1).copy()}
+
+
+def rows_add(a, b):
+    """the sum of two accumulators as `rows_acc_arrays` gives them"""
+    return {name: a[name] + b[name] for name in ROWS_FIELDS}
+
+
+def rows_rms(acc) -> float:
+    """the rms offset in DN of accumulators as `rows_acc_arrays` gives them, summed: sqrt(sum_q2 / applied) / 16; 0 without a row"""
+    applied, q2 = int(acc["applied"].sum()), int(acc["sum_q2"].sum())
+    return (q2 / applied) ** 0.5 / 16.0 if applied else 0.0
+
+
+def rows_floor_rms(noise_a: float, noise_b: float, var_floor: float, bit_depth: int, ww: int) -> float:
+    """The rms the estimate has of its own on flat footage WITHOUT row noise, in DN: 1.35 sqrt(var(mid) / (2 ww)) with var at the
+    mid level (2^bit_depth - 1) / 2 of the curve.  The median of eight normal samples has 0.168 of their variance, so a sample's
+    d = x - median of eight has 1.168 var; the median of N = 2 ww independent such d has pi / (2 N) of theirs; sqrt(pi / 2 * 1.168) =
+    1.355, and a gate at three standard deviations changes it by a per cent.  The rule gives 1.38 on white noise (tests/test_rows_host.py).
+    A scene's vertical curvature adds to every d, so footage with detail sits somewhat above the floor without any row noise."""
+    mid = ((1 << int(bit_depth)) - 1) / 2.0
+    return 1.35 * (max(noise_a * mid - noise_b, var_floor) / (2.0 * ww)) ** 0.5
+
+
 def nearest_iso(a: float, b: float, bit_depth: int = 12, levels=(0.20, 0.45, 0.80)):
     """Which of DPC_ISO_CURVES lies closest to the curve (a, b) in DN of `bit_depth`: -> (iso, ratios), the ISO whose predicted
     standard deviation at 20 %, 45 % and 80 % of 2^bit_depth - 1 is nearest in the log (the largest |log ratio| over the levels is
@@ -781,6 +830,44 @@ class RvddRuntime:
         host = _lib.RvddResidAcc()
         self._check(self.lib.rvdd_resid_read(self.h, int(slot), C.byref(host), self._stream()), "rvdd_resid_read")
         return resid_acc_arrays(host)
+
+    # -- row noise ------------------------------------------------------------------------------
+    def rows_estimate(self, packed: torch.Tensor, cfg, bit_depth: int = 12, acc: Optional[torch.Tensor] = None):
+        """One offset per frame, row parity and plane row of packed frames [n,4,hh,ww] (rvdd_rows_estimate; cfg: `rows_cfg(...)`, the
+        curve in DN of `bit_depth`).  -> (offsets float32 [n,2,hh], state uint8 [n,2,hh]: 0 skipped, 1 applied, 2 applied and clamped,
+        acc: a device int64 tensor [n,3], one struct rvdd_rows_acc per frame -- None = a new zeroed one -- to which the rows are
+        added; `rows_acc_arrays(acc)` gives the counts).  Nothing is synchronised."""
+        packed, n, hh, ww = _frames(packed, 4, "rows_estimate: packed is [n,4,hh,ww]", "packed", self.device)
+        offsets = torch.empty((n, 2, hh), dtype=torch.float32, device=self._tdev)
+        state = torch.empty((n, 2, hh), dtype=torch.uint8, device=self._tdev)
+        acc = _out_or_new(acc, "rows_estimate: acc", (n, ROWS_ACC_BYTES // 8), self._tdev, torch.int64, zero=True, nbytes=n * ROWS_ACC_BYTES,
+                          form=f"rows_estimate: acc is a contiguous int64 tensor of {n} x {ROWS_ACC_BYTES // 8} words on cuda:{self.device}")
+        self._check(self.lib.rvdd_rows_estimate(self.h, _ptr(packed), n, hh, ww, int(bit_depth), C.byref(cfg), _ptr(offsets), _ptr(state),
+                                                _ptr(acc), self._stream()), "rvdd_rows_estimate")
+        return offsets, state, acc
+
+    def rows_apply(self, packed: torch.Tensor, offsets: torch.Tensor, bit_depth: int = 12, gray: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`offsets` [n,2,hh] taken out of packed frames [n,4,hh,ww] IN PLACE (rvdd_rows_apply), gray [n,hh,ww] re-formed in the rows
+        with a non-zero offset.  -> packed.  Both must be contiguous: they are written where they lie.  Nothing is synchronised."""
+        packed, n, hh, ww = _frames(packed, 4, "rows_apply: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
+        offsets = _dev_tensor(offsets, "offsets", self.device, shape=(n, 2, hh),
+                              form=f"rows_apply: offsets is a float32 tensor [{n},2,{hh}], as rows_estimate gives it")
+        if gray is not None:
+            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
+        self._check(self.lib.rvdd_rows_apply(self.h, _ptr(packed), _ptr(gray), _ptr(offsets), n, hh, ww, int(bit_depth), self._stream()),
+                    "rvdd_rows_apply")
+        return packed
+
+    def set_rows(self, cfg=None):
+        """The row-noise correction as a stage of `video_push`, behind `set_dpc` and in front of `set_match` (rvdd_set_rows): cfg =
+        `rows_cfg(...)`, the sensor's own curve in DN of the pushes' bit depth; None = off (the default).  Synchronises the device."""
+        self._check(self.lib.rvdd_set_rows(self.h, None if cfg is None else C.byref(cfg)), "rvdd_set_rows")
+
+    def rows_read(self, slot: int):
+        """Slot `slot`'s accumulator as `rows_acc_arrays` gives one ([1] arrays), zeroed on the device (rvdd_rows_read; synchronises)."""
+        host = _lib.RvddRowsAcc()
+        self._check(self.lib.rvdd_rows_read(self.h, int(slot), C.byref(host), self._stream()), "rvdd_rows_read")
+        return rows_acc_arrays(host)
 
     def set_dpc(self, cfg=None):
         """The correction as a stage of `video_push`, between the ingest and the kept frames (rvdd_set_dpc): cfg = `dpc_cfg(...)`,
