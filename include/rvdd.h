@@ -823,7 +823,7 @@ int rvdd_resid_read(rvdd_t* h, int32_t slot, rvdd_resid_acc* host_out /* HOST */
  * What it cannot do: the median of eight vertical neighbours is itself shifted by THEIR rows' offsets, so about 0.4 of the offsets'
  * amplitude stays behind as a slow vertical drift that cannot be told from scene shading -- a limit of any single-frame rule without
  * optically black columns.  Rows that a long horizontal edge crosses are skipped, or biased by less than the gate.
- * Column fixed-pattern noise, offsets per plane and the use of the previous frame are out of scope.  Nothing is measured on real footage.
+ * Column fixed-pattern noise is the rule below (rvdd_cols_estimate); offsets per plane and the use of the previous frame are out of scope.  Nothing is measured on real footage.
  * On footage WITHOUT row noise the estimate has an rms of about 1.35 sqrt(var / (2 ww)) of its own, which the stage then adds.
  *
  * rvdd_rows_estimate writes offsets (DEVICE float [n,2,hh]) and state (DEVICE uint8 [n,2,hh]: 0 skipped, 1 applied, 2 applied and
@@ -874,6 +874,90 @@ int rvdd_set_rows(rvdd_t* h, const rvdd_rows_cfg* cfg /* NULL = off, the default
  * the loop synchronises anyway (the end of a video or of a shot).  All zeros on a handle that never pushed with the stage on.
  * RVDD_ERR_ARG: NULL host_out, slot outside 0 .. cfg.batch - 1. */
 int rvdd_rows_read(rvdd_t* h, int32_t slot, rvdd_rows_acc* host_out /* HOST */, void* stream /* synchronised */);
+
+/* ---- column fixed-pattern noise ---------------------------------------------------- */
+
+/* The other half of a CMOS readout: every mosaic column has its own amplifier or ADC offset, and that offset does NOT change from
+ * frame to frame -- vertical stripes that stay put while the scene moves under them.  A mosaic column is shared by planes j and j + 2
+ * of the packed [n,4,hh,ww] tensor (channel k = CFA position (k >> 1, k & 1); j = k & 1 is the column parity), so there is ONE offset
+ * per column parity j and plane column c.  It is estimated per frame from the column's 2 hh samples (rvdd_cols_estimate, the transpose
+ * of the row rule), pooled over F frames of a moving scene on the host (rvdd_cols_fit: the estimate's error falls as 1 / sqrt(F), scene
+ * detail averages out, and a column is tested against its own spread before anything is changed), and taken out as a static map
+ * (rvdd_cols_apply).  Every operation is rounded to f32 on its own (no fused multiply-add): offsets, states, the map and the corrected
+ * samples are reproducible bit for bit in NumPy f32 (tests/cols_ref.py).  With top, dn(v) and the way back as for the rows:
+ *   per sample (k, r, c):
+ *     x   = dn(p[k][r][c]); the eight horizontal neighbours dn(p[k][r][c + dc]), dc in {+-1, +-2, +-3, +-4}, an index outside the plane
+ *           mirrored about the site (c + dc -> c - dc: hence ww >= 5); where c - dc lies outside as well -- only in planes of fewer than
+ *           nine columns -- it is reflected about the plane's edge (-q -> q, ww - 1 + q -> ww - 1 - q)
+ *     m   = (s3 + s4) * 0.5, s3 / s4 the 4th / 5th of the eight in ascending order;  d = x - m
+ *     var = fmaxf(noise_a * m - noise_b, var_floor)       the noise curve in DN of this bit depth
+ *     the sample is USED iff d * d <= (k_gate * k_gate) * var
+ *   per frame and column (i, j, c):
+ *     cnt = the used samples among the 2 hh.  The column is APPLIED (state 1) iff cnt > 0 and cnt >= hh, with
+ *     e   = (v[(cnt - 1) / 2] + v[cnt / 2]) * 0.5 of the used d in ascending order (the exact median); else SKIPPED (state 0), e = 0.
+ *           There is no clamp here.
+ *   the fit over F frames (rvdd_cols_fit, on the host, f32, in this order), for each (j, c):
+ *     v   = the e of the frames with state 1, ascending; nf = how many there are.  nf < max(1, min_frames): map = 0, mstate 0
+ *           (UNSUPPORTED).  Otherwise
+ *     o   = (v[(nf - 1) / 2] + v[nf / 2]) * 0.5;  a[i] = |v[i] - o|, ascending;  mad = (a[(nf - 1) / 2] + a[nf / 2]) * 0.5
+ *     (o * o) * (float)nf < (k_sig * k_sig) * (3.4528f * (mad * mad)): map = 0, mstate 3 (INSIGNIFICANT).  3.4528 = (1.4826 * 1.2533)^2
+ *           is the variance of a median in units of MAD^2; k_sig = 0 keeps every supported column.  Otherwise
+ *     map = o clamped to [-max_dn, +max_dn], mstate 1 (APPLIED), or 2 if the clamp changed it (CLAMPED).
+ *   apply (map [2,ww] f32 in DN of the frames' bit depth, in place, a pure stream): where map[k & 1][c] != 0 the sample becomes
+ *     2 * ((x - map) / top) - 1 (no clamp to the range); every other sample keeps its bits.  gray [n,hh,ww] (nullable): a gray cell in a
+ *     column c where at least one parity's map is non-zero is rewritten as (((d0 + d1) + d2) + d3) * 0.25, d_k = dn(p[k][r][c]) -
+ *     map[k & 1][c]; every other gray cell is not written.  A map of zeros leaves the tensors bit for bit.
+ * What it cannot do: the neighbours carry offsets too, so the estimate is a high-pass of the pattern -- slow horizontal shading of the
+ * pattern stays, as for the rows.  In a tripod shot of a static scene a vertical edge passes the significance test, because its spread
+ * over time is only noise: estimate on footage that moves.  One camera setting per map.  Offsets per plane and per-column gains are
+ * out of scope.  Nothing is measured on real footage.
+ *
+ * rvdd_cols_estimate writes offsets (DEVICE float [n,2,ww]) and state (DEVICE uint8 [n,2,ww]: 0 skipped, 1 applied), every word.  One
+ * workgroup per (frame, parity, strip of 32 / 16 / 8 / 4 neighbouring columns for hh <= 639 / 1279 / 2559 / 4096): the strip's keys lie
+ * column-major in LDS, one wave finds a column's exact median by a digit-wise search of the keys' bit patterns that takes the same
+ * steps whatever the values.  hh <= 4096: four columns of 2 hh 32-bit keys are what fits the 160 KiB of a CU with a wave's count
+ * below 2^16.  Inputs are assumed finite.  RVDD_ERR_ARG (the message names the argument) and nothing launched: NULL cfg; k_gate not
+ * > 0 or not finite; noise_a / noise_b not finite; var_floor not > 0 (or not finite); bit_depth outside 1..16; ww < 5; hh < 1 or
+ * > 4096; n < 0; NULL packed / offsets / state with n > 0; a launch of more than 2^31 - 1 blocks.  n = 0 does nothing.  Asynchronous
+ * and stream-ordered; nothing is read back.
+ * rvdd_cols_fit needs no device and no handle (errors: rvdd_last_error(NULL)).  stats (nullable): counts[s] = the columns of mstate s,
+ * sum_q2 = the sum of q * q with q = (int)rintf(16 * map), floor_dn = the mean over the supported columns (mstate 1, 2, 3) of
+ * ((1.2533f * 1.4826f) * mad) / sqrtf(nf), summed in f64 in the order (j, c): the standard error of the pooled estimate.
+ * RVDD_ERR_ARG: a NULL pointer but stats; F < 1; ww < 1; k_sig < 0 or not finite; max_dn not > 0 or not finite.
+ * rvdd_cols_apply takes map_dev (DEVICE [2,ww]) out IN PLACE.  With ww % 4 == 0 and packed / gray / map_dev 16-byte aligned a thread
+ * owns four neighbouring cells (16-byte loads and stores), every other case one cell.  Same bits either way.  RVDD_ERR_ARG as for the
+ * estimate's shape (hh has no cap here), NULL packed / map_dev with n > 0. */
+typedef struct rvdd_cols_cfg {
+    float k_gate;             /* the gate in standard deviations of the noise curve, around 3 */
+    float noise_a, noise_b;   /* var(m) = noise_a * m - noise_b, in DN of the frames' bit depth */
+    float var_floor;          /* the least variance assumed, > 0 */
+} rvdd_cols_cfg;
+typedef struct rvdd_cols_fit_cfg {
+    int32_t min_frames;       /* the least number of applied frames a column needs; below 1 counts as 1 */
+    float k_sig;              /* the significance threshold in standard errors of the pooled median, >= 0; 0 keeps every supported column */
+    float max_dn;             /* the largest offset taken out, in DN, > 0 */
+} rvdd_cols_fit_cfg;
+typedef struct rvdd_cols_stats {   /* 32 bytes */
+    uint32_t counts[4];       /* columns by mstate: 0 unsupported, 1 applied, 2 applied and clamped, 3 insignificant */
+    int64_t sum_q2;           /* sum of q * q, q = (int)rintf(16 * map): the map's rms is sqrt(sum_q2 / (2 ww)) / 16 DN */
+    double floor_dn;          /* the mean standard error of the pooled estimates, in DN */
+} rvdd_cols_stats;
+int rvdd_cols_estimate(rvdd_t* h, const float* packed /* [n,4,hh,ww] */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+                       const rvdd_cols_cfg* cfg, float* offsets /* DEVICE [n,2,ww] */, uint8_t* state /* DEVICE [n,2,ww] */, void* stream);
+int rvdd_cols_fit(const float* offsets_host /* [F,2,ww] */, const uint8_t* state_host /* [F,2,ww] */, int32_t F, int32_t ww,
+                  const rvdd_cols_fit_cfg* fit_cfg, float* map_host /* [2,ww] */, uint8_t* mstate_host /* [2,ww] */,
+                  rvdd_cols_stats* stats_host /* nullable */);
+int rvdd_cols_apply(rvdd_t* h, float* packed /* [n,4,hh,ww], IN PLACE */, float* gray /* [n,hh,ww], nullable, in place */,
+                    const float* map_dev /* DEVICE [2,ww] */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream);
+
+/* The map as a stage of rvdd_video_push: map_host [2,ww] f32 in DN of the pushes' bit depth (every value finite, ww >= 5: else
+ * RVDD_ERR_ARG and nothing changes), NULL = off, the default.  Per handle; synchronises the device as rvdd_set_dpc_map does, copies
+ * the map to the device (8 ww bytes, freed by the next call and with the handle).  With the stage on a push runs, for every run of
+ * slots that got a frame, ONE rvdd_cols_apply on the ring's packed frames and gray planes IN PLACE, behind rvdd_set_dpc_map and
+ * rvdd_set_dpc and in front of rvdd_set_rows and rvdd_set_match; a push of frames with another ww is RVDD_ERR_ARG.  The map is static:
+ * no per-slot state and no read call.  With the stage off a push makes exactly the launches it made before and allocates nothing; a
+ * map of zeros leaves the ring bit for bit what a push without the stage leaves. */
+int rvdd_set_cols(rvdd_t* h, const float* map_host /* [2,ww]; NULL = off, the default */, int32_t ww);
 
 /* ---- raw datasets from sRGB video ------------------------------------------- */
 

@@ -84,6 +84,21 @@ class RvddRowsAcc(C.Structure):
     _fields_ = [("applied", C.c_uint32), ("skipped", C.c_uint32), ("clamped", C.c_uint32), ("reserved", C.c_uint32), ("sum_q2", C.c_int64)]
 
 
+class RvddColsCfg(C.Structure):
+    """struct rvdd_cols_cfg (rvdd_cols_estimate)"""
+    _fields_ = [("k_gate", C.c_float), ("noise_a", C.c_float), ("noise_b", C.c_float), ("var_floor", C.c_float)]
+
+
+class RvddColsFitCfg(C.Structure):
+    """struct rvdd_cols_fit_cfg (rvdd_cols_fit)"""
+    _fields_ = [("min_frames", C.c_int32), ("k_sig", C.c_float), ("max_dn", C.c_float)]
+
+
+class RvddColsStats(C.Structure):
+    """struct rvdd_cols_stats (rvdd_cols_fit): 32 bytes"""
+    _fields_ = [("counts", C.c_uint32 * 4), ("sum_q2", C.c_int64), ("floor_dn", C.c_double)]
+
+
 # symbol -> (restype, argtypes); exactly the functions include/rvdd.h declares
 _P = C.c_void_p
 _PROTOS = {
@@ -141,6 +156,10 @@ _PROTOS = {
     "rvdd_rows_apply": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "rvdd_set_rows": (C.c_int, [_P, C.POINTER(RvddRowsCfg)]),
     "rvdd_rows_read": (C.c_int, [_P, C.c_int32, C.POINTER(RvddRowsAcc), _P]),
+    "rvdd_cols_estimate": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddColsCfg), _P, _P, _P]),
+    "rvdd_cols_fit": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(RvddColsFitCfg), _P, _P, C.POINTER(RvddColsStats)]),
+    "rvdd_cols_apply": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "rvdd_set_cols": (C.c_int, [_P, _P, C.c_int32]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                  _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),

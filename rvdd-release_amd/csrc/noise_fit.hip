@@ -184,6 +184,63 @@ extern "C" int rvdd_resid_fit(const rvdd_resid_acc* acc, int32_t bit_depth, doub
     return RVDD_OK;
 }
 
+// rvdd_cols_fit: the static column map from host copies of rvdd_cols_estimate's offsets and states of F frames (the rule is in
+// include/rvdd.h).  f32, every operation rounded on its own, in the order written there; the floor's mean alone is summed in f64 over
+// the columns in the order (parity, column): tests/cols_ref.py says the same in NumPy f32 and gets the same bits.
+extern "C" int rvdd_cols_fit(const float* offsets, const uint8_t* state, int32_t F, int32_t ww, const rvdd_cols_fit_cfg* cfg, float* map,
+                             uint8_t* mstate, rvdd_cols_stats* stats) {
+    if (!offsets) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: offsets_host is required");
+    if (!state) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: state_host is required");
+    if (!cfg) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: fit_cfg is required");
+    if (!map) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: map_host is required");
+    if (!mstate) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: mstate_host is required");
+    if (F < 1) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: F must be >= 1, got %d", F);
+    if (ww < 1) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: ww must be >= 1, got %d", ww);
+    if (!(cfg->k_sig >= 0.0f) || !std::isfinite(cfg->k_sig)) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: k_sig must be finite and >= 0, got %g", cfg->k_sig);
+    if (!(cfg->max_dn > 0.0f) || !std::isfinite(cfg->max_dn)) return fail(nullptr, RVDD_ERR_ARG, "rvdd_cols_fit: max_dn must be finite and > 0, got %g", cfg->max_dn);
+    const int need = cfg->min_frames > 1 ? cfg->min_frames : 1;
+    const float k2 = cfg->k_sig * cfg->k_sig;
+    rvdd_cols_stats st{};
+    double floor_sum = 0.0;
+    uint64_t supported = 0;
+    std::vector<float> v, a;
+    for (int64_t jc = 0; jc < 2 * (int64_t)ww; ++jc) {
+        v.clear();
+        for (int i = 0; i < F; ++i)
+            if (state[(int64_t)i * 2 * ww + jc] == 1) v.push_back(offsets[(int64_t)i * 2 * ww + jc]);
+        const int nf = (int)v.size();
+        map[jc] = 0.0f;
+        if (nf < need) {
+            mstate[jc] = 0;
+            st.counts[0] += 1;
+            continue;
+        }
+        std::sort(v.begin(), v.end());
+        const float o = (v[(size_t)(nf - 1) / 2] + v[(size_t)nf / 2]) * 0.5f;
+        a.resize((size_t)nf);
+        for (int i = 0; i < nf; ++i) a[(size_t)i] = std::fabs(v[(size_t)i] - o);
+        std::sort(a.begin(), a.end());
+        const float mad = (a[(size_t)(nf - 1) / 2] + a[(size_t)nf / 2]) * 0.5f;
+        floor_sum += (double)(((1.2533f * 1.4826f) * mad) / std::sqrt((float)nf));
+        ++supported;
+        if ((o * o) * (float)nf < k2 * (3.4528f * (mad * mad))) {
+            mstate[jc] = 3;
+            st.counts[3] += 1;
+            continue;
+        }
+        const float oc = std::fmin(std::fmax(o, -cfg->max_dn), cfg->max_dn);
+        const int s = oc != o ? 2 : 1;
+        map[jc] = oc;
+        mstate[jc] = (uint8_t)s;
+        st.counts[s] += 1;
+        const long long q = (long long)(int)std::rint(16.0f * oc);
+        st.sum_q2 += q * q;
+    }
+    st.floor_dn = supported ? floor_sum / (double)supported : 0.0;
+    if (stats) *stats = st;
+    return RVDD_OK;
+}
+
 // rvdd_cut_score: the distance of two frame signatures (rvdd_frame_sigs; the rule is in include/rvdd.h).  Integer sums, each converted to
 // f64 once, one division each: the same formulas on Python integers give the same bits (tests/cuts_ref.py).
 extern "C" int rvdd_cut_score(const rvdd_frame_sig* a, const rvdd_frame_sig* b, int32_t hh, int32_t ww, double* out2) {

@@ -506,6 +506,58 @@ int rvdd_rows_apply(rvdd_t* h, float* packed, float* gray, const float* offsets,
     return RVDD_OK;
 }
 
+static int cols_shape(rvdd_t* h, const char* fn, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth) {
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 1..16, got %d", fn, bit_depth);
+    if (ww < 5) return fail(h, RVDD_ERR_ARG, "%s: ww must be >= 5 (four horizontal neighbours on either side, mirrored about the site), got %d", fn, ww);
+    if (hh < 1) return fail(h, RVDD_ERR_ARG, "%s: hh must be >= 1, got %d", fn, hh);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    return RVDD_OK;
+}
+
+int rvdd_cols_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, const rvdd_cols_cfg* cfg,
+                       float* offsets, uint8_t* state, void* stream) {
+    const char* fn = "rvdd_cols_estimate";
+    if (!h) return RVDD_ERR_ARG;
+    if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
+    if (!(cfg->k_gate > 0.0f) || !std::isfinite(cfg->k_gate)) return fail(h, RVDD_ERR_ARG, "%s: k_gate must be finite and > 0, got %g", fn, cfg->k_gate);
+    if (!std::isfinite(cfg->noise_a)) return fail(h, RVDD_ERR_ARG, "%s: noise_a must be finite, got %g", fn, cfg->noise_a);
+    if (!std::isfinite(cfg->noise_b)) return fail(h, RVDD_ERR_ARG, "%s: noise_b must be finite, got %g", fn, cfg->noise_b);
+    if (!(cfg->var_floor > 0.0f) || !std::isfinite(cfg->var_floor)) return fail(h, RVDD_ERR_ARG, "%s: var_floor must be finite and > 0, got %g", fn, cfg->var_floor);
+    RC(cols_shape(h, fn, n, hh, ww, bit_depth));
+    if (hh > cols_max_hh())
+        return fail(h, RVDD_ERR_ARG, "%s: hh must be <= %d (a workgroup holds the 2 hh keys of four columns in LDS), got %d", fn, cols_max_hh(), hh);
+    if (n == 0) return RVDD_OK;
+    if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
+    if (!offsets) return fail(h, RVDD_ERR_ARG, "%s: offsets is required", fn);
+    if (!state) return fail(h, RVDD_ERR_ARG, "%s: state is required", fn);
+    if (cols_estimate_blocks(n, hh, ww) < 0)
+        return fail(h, RVDD_ERR_ARG, "%s: n = %d frames of ww = %d columns need a launch of more than 2^31 - 1 blocks", fn, n, ww);
+    ENTER(h);
+    // the square rounded to f32 once, here (+inf for a huge gate: every finite sample is used)
+    const RowsParams p{cfg->k_gate * cfg->k_gate, cfg->noise_a, cfg->noise_b, cfg->var_floor, 0.0f, 0.0f};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scope sc(h, s, "cols_estimate_kernel", 0.0, (double)n * 4.0 * hh * ww * 4.0);
+    HIPCHK(h, launch_cols_estimate(packed, n, hh, ww, bit_depth, p, offsets, state, s));
+    return RVDD_OK;
+}
+
+int rvdd_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream) {
+    const char* fn = "rvdd_cols_apply";
+    if (!h) return RVDD_ERR_ARG;
+    RC(cols_shape(h, fn, n, hh, ww, bit_depth));
+    if (n == 0) return RVDD_OK;
+    if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
+    if (!map_dev) return fail(h, RVDD_ERR_ARG, "%s: map_dev is required", fn);
+    if (cols_apply_blocks(n, hh, ww, cols_apply_wide(packed, gray, map_dev, ww)) < 0)
+        return fail(h, RVDD_ERR_ARG, "%s: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, n, hh, ww);
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const double cells = (double)n * 4.0 * hh * ww;
+    Scope sc(h, s, "cols_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
+    HIPCHK(h, launch_cols_apply(packed, gray, map_dev, n, hh, ww, bit_depth, s));
+    return RVDD_OK;
+}
+
 // the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine
 static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int32_t W) {
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);

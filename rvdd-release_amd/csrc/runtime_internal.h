@@ -272,6 +272,13 @@ struct rvdd_handle {
         rvdd_rows_acc* acc = nullptr;    // DEVICE [B]: one accumulator per slot
     } rows;
 
+    // rvdd_set_cols: the static column map taken out of the ring's frames behind the correction and in front of the rows (rvdd_video_push)
+    struct Cols {
+        bool on = false;
+        int ww = 0;                      // the map's width in cells
+        float* map = nullptr;            // DEVICE [2][ww]: DN of the pushes' bit depth (freed by rvdd_set_cols / rvdd_destroy)
+    } cols;
+
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
         const void* p[6];
@@ -462,8 +469,7 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s);
 // the checks rvdd_dpc and rvdd_set_dpc share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
 int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* out);
 // the checks rvdd_rows_estimate and rvdd_set_rows share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
-int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out);
-// the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
+int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out);// the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
 int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg);
 int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
                    void* stream, bool async);

@@ -494,6 +494,20 @@ hipError_t launch_rows_apply(float* packed, float* gray, const float* offsets, i
 bool rows_apply_wide(const float* packed, const float* gray, int ww);
 int64_t rows_apply_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame);
 
+// cols.hip -- column fixed-pattern noise: one offset per frame, column parity and plane column (rvdd_cols_estimate), a static map
+// taken out (rvdd_cols_apply, the stage behind rvdd_set_cols).  The gate's parameters are RowsParams (max_dn is not read: no clamp here)
+// offsets / state [n][2][ww] (DEVICE, every word written) of packed [n][4][hh][ww]; one workgroup per (frame, parity, strip of
+// cols_strip(hh) columns).  1 <= hh <= cols_max_hh(), ww >= 5; n <= 0 launches nothing
+hipError_t launch_cols_estimate(const float* packed, int n, int hh, int ww, int bit_depth, const RowsParams& p, float* offsets, uint8_t* state,
+                                hipStream_t s);
+int cols_max_hh();                                       // the tallest plane whose column keys fit a CU's LDS four columns at a time
+int cols_strip(int hh);                                  // the columns of a workgroup's strip: 32, 16, 8 or 4
+int64_t cols_estimate_blocks(int n, int hh, int ww);     // the grid of that launch; -1 = more than 2^31 - 1 blocks
+// packed [n][4][hh][ww] IN PLACE, gray [n][hh][ww] (nullable) in place: map [2][ww] (DEVICE, DN) taken out of the columns where it is not zero
+hipError_t launch_cols_apply(float* packed, float* gray, const float* map, int n, int hh, int ww, int bit_depth, hipStream_t s);
+bool cols_apply_wide(const float* packed, const float* gray, const float* map, int ww);
+int64_t cols_apply_blocks(int n, int hh, int ww, bool wide);      // -1 = more than 2^31 - 1 blocks
+
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from
 // (seed, frame0 + image) then); lin_f32 / lin_u16 [n][2hh][2ww][3], gt_raw / noisy [n][hh][ww][4], each nullable

@@ -77,6 +77,10 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         RC(dmalloc(h, reinterpret_cast<void**>(&rows.state), (size_t)B * 2 * hh));
         RC(dmalloc(h, reinterpret_cast<void**>(&rows.acc), (size_t)B * sizeof(rvdd_rows_acc)));      // last: the mark of a complete allocation
     }
+    // rvdd_set_cols: the static column map is taken out of the ring's frames behind the correction; nothing is allocated here
+    const auto cols = h->cols;
+    if (cols.on && cols.ww != ww)
+        return fail(h, RVDD_ERR_ARG, "rvdd_video_push: the map of rvdd_set_cols is one of %d cell columns, the frames have %d", cols.ww, ww);
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
         if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
@@ -100,6 +104,12 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
         if (dmap.on && dmap.ncells)
             HIPCHK(h, launch_dpc_map_apply(packed, ring_gray, e - b, hh, ww, bit_depth, dmap.mask, dmap.cells, dmap.ncells, s));
         if (dpc.on) HIPCHK(h, launch_dpc(packed, ring_packed, ring_gray, e - b, hh, ww, bit_depth, dpc.p, dpc.counts + 2 * (size_t)b, s));
+        // rvdd_set_cols: the static column offsets taken out of the ring's planes and gray planes in place: one launch
+        if (cols.on) {
+            const double cells = (double)(e - b) * 4.0 * (double)hw;
+            Scope sc(h, s, "cols_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
+            HIPCHK(h, launch_cols_apply(ring_packed, ring_gray, cols.map, e - b, hh, ww, bit_depth, s));
+        }
         // rvdd_set_rows: the row offsets of the (corrected) frames estimated and taken out of the ring's planes and gray planes in place
         if (rows.on) {
             const double cells = (double)(e - b) * 4.0 * (double)hw;
@@ -264,6 +274,29 @@ extern "C" int rvdd_set_match(rvdd_t* h, const rvdd_match_cfg* cfg) {
     HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight keep the coefficients they were enqueued with
     h->match.on = cfg != nullptr;
     if (cfg) h->match.cfg = *cfg;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_set_cols(rvdd_t* h, const float* map_host, int32_t ww) {
+    if (!h) return RVDD_ERR_ARG;
+    if (map_host) {
+        if (ww < 5) return fail(h, RVDD_ERR_ARG, "rvdd_set_cols: ww must be >= 5, got %d", ww);
+        for (int64_t i = 0; i < 2 * (int64_t)ww; ++i)
+            if (!std::isfinite(map_host[i]))
+                return fail(h, RVDD_ERR_ARG, "rvdd_set_cols: map_host[%d][%d] = %g is not finite", (int)(i / ww), (int)(i % ww), (double)map_host[i]);
+    }
+    ENTER(h);
+    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc_map: pushes in flight read the map they were enqueued with
+    auto& c = h->cols;
+    if (c.map) HIPCHK(h, hipFree(c.map));
+    c.map = nullptr;
+    c.on = false;
+    c.ww = 0;
+    if (!map_host) return RVDD_OK;
+    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&c.map), 2 * (size_t)ww * sizeof(float)));
+    HIPCHK(h, hipMemcpy(c.map, map_host, 2 * (size_t)ww * sizeof(float), hipMemcpyHostToDevice));
+    c.ww = ww;
+    c.on = true;
     return RVDD_OK;
 }
 

@@ -104,6 +104,28 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       iso3200 or iso12800.  Default: the curve of --dpc; without either it is an error.
   --row_noise_max DN  the largest offset taken out (default (2^bit_depth - 1) / 64, a guess).
                       Without --row_noise no new call is made and the output files keep their bytes.
+  --col_noise FILE    take column fixed-pattern noise (vertical stripes that stay put: one readout offset per mosaic column, the same in
+                      every frame) out of every frame on the device (`rvdd_set_cols`), behind --dpc_map / --dpc and in front of
+                      --row_noise and --match_noise: FILE is a one-row float32 TIFF of one offset per mosaic column in DN of --bit_depth
+                      (python -m rvdd_release_amd.col_noise writes one; a camera's own calibration serves as well).  Columns whose
+                      offset is 0 keep their bits.  TV-L1, the network and --report see the corrected frames.
+  --col_noise auto    the map found in the run's own footage before streaming starts (`rvdd_cols_estimate`, `rvdd_cols_fit`; python -m
+                      rvdd_release_amd.col_noise is the same pass on its own): --col_noise_frames F (default 32) frames spread evenly
+                      over up to 16 videos; per frame and column the median, over the column's two colour planes, of every sample's
+                      difference to the median of its eight horizontal same-colour neighbours, samples further than --col_noise_gate K
+                      (default 3) standard deviations of the noise curve left out; per column the median over the frames, taken only
+                      where at least half of the frames gave an estimate and it is at least --col_noise_sigma (default 3) standard
+                      errors of itself, measured from the column's own spread over the frames; --col_noise_max DN is the largest
+                      offset taken out (default (2^bit_depth - 1) / 64, a guess).
+  --col_noise_curve C with --col_noise auto, the sensor's curve in DN of --bit_depth: a,b[,floor], auto (the run's own estimate, shared
+                      with --dpc_noise auto), iso3200 or iso12800.  Default: the curve of --dpc; without either it is an error.
+                      Prints `cols: <applied> applied, <insignificant> insignificant, <unsupported> unsupported, <clamped> clamped of
+                      <n> columns, map rms <x> DN (the pooled estimate alone: <y> DN), from F frames` (or what a FILE holds).  Limits: the
+                      neighbours carry offsets too, so slow horizontal shading of the pattern stays; in a tripod shot of a static scene
+                      a vertical edge passes the significance test, since its spread over time is only noise -- estimate on footage
+                      that moves; one camera setting per run; offsets per plane and per-column gains are not modelled; NOTHING is
+                      measured on real footage.  Without --col_noise no new call is made and the output files keep
+                      their bytes.
   --report FILE       check the outputs without ground truth: if the output is the clean frame, noisy - remosaic(denoised) is the noise.
                       The stream reduces every output and its (corrected, matched) centre frame to residual statistics on the device
                       (`rvdd_set_resid`), read at the end of every video -- of every shot under --cuts -- and judged against a noise curve
@@ -132,8 +154,8 @@ import torch
 
 from . import _lib
 from . import tiffio
-from .footage import (add_dpc_arguments, add_report_arguments, add_rows_arguments, dpc_arguments, estimate_noise, open_rawvideo,
-                      report_arguments, report_record, rows_arguments, rows_line, to_device)
+from .footage import (add_cols_arguments, add_dpc_arguments, add_report_arguments, add_rows_arguments, cols_arguments, dpc_arguments,
+                      estimate_noise, open_rawvideo, report_arguments, report_record, rows_arguments, rows_line, to_device)
 from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, match_coeffs, resid_add, rows_cfg
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
@@ -326,6 +348,26 @@ def split_shots(videos, cuts_by_key):
     return shots
 
 
+def find_cols_map(dataset, dev, opt):
+    """--col_noise: the run's column map float32 [2,ww] in DN of --bit_depth, its `cols:` line sent to the log.  auto:
+    `col_noise.estimate` on the run's own videos and the fit (`col_noise.report`), before any push."""
+    from . import col_noise as M
+    from .runtime import cols_cfg
+    from .util._ops import ops_runtime
+    try:
+        if opt.cols[0] == "file":
+            cmap = M.read_map(opt.cols[1])
+            print(M.file_line(cmap, opt.cols[1]))
+            return cmap
+        _, frames, gate, sigma, max_dn, _, a, b, floor = opt.cols
+        offsets, state = M.estimate(ops_runtime(dev.index or 0), dataset, int(opt.bit_depth), cols_cfg(gate, a, b, floor), frames)
+        cmap, r = M.report(offsets, state, sigma, max_dn)
+    except (RuntimeError, tiffio.TiffError, OSError) as err:
+        raise SystemExit("--col_noise %s: %s" % (opt.cols[0] if opt.cols[0] == "auto" else opt.cols[1], err))
+    print(M.summary_line(r, '%d frames' % r["frames"]))
+    return cmap
+
+
 def find_shots(dataset, dev, opt):
     """--cuts: the run's videos as their shots (`split_shots`), one `cuts: <key>: N frames, shots at [0, k1, ...]` line per video sent to
     the log.  auto: `cuts.detect` on the run's own videos, before any push."""
@@ -360,6 +402,7 @@ def _parse(argv):
     p.add_argument('--all_frames', action='store_true', help='write every input frame, the first and the last of a video too')
     add_dpc_arguments(p)
     add_rows_arguments(p)
+    add_cols_arguments(p)
     p.add_argument('--dpc_map', type=str, default=None, help='FILE: correct the sites of this defect map (python -m rvdd_release_amd.dpc_map '
                    'writes one); auto: find the map in the footage before streaming starts, with the rule of --dpc')
     p.add_argument('--dpc_map_frames', type=int, default=None, help='with --dpc_map auto: frames read per video, spread over it (default 16)')
@@ -386,6 +429,8 @@ def _parse(argv):
                                     opt.dpc is not None)
     opt.dpc_static_only = own.dpc_static_only
     opt.rows = rows_arguments(own.row_noise, own.row_noise_curve, own.row_noise_max, opt.dpc, int(opt.bit_depth))
+    opt.cols = cols_arguments(own.col_noise, own.col_noise_curve, own.col_noise_frames, own.col_noise_gate, own.col_noise_sigma,
+                              own.col_noise_max, opt.dpc, int(opt.bit_depth))
     opt.match = match_arguments(own.match_noise, own.match_iso)
     opt.report = report_arguments(own.report, own.report_noise, opt.match, int(opt.bit_depth))
     opt.cuts = cuts_arguments(own.cuts, own, opt.future_patch_depth)
@@ -408,8 +453,8 @@ def _parse(argv):
 
 def prepasses(opt, dataset, dev):
     """What is decided on the run's own footage before any push, in this order: the noise curve of --dpc_noise auto / --match_noise auto
-    (ONE estimate for both, for --row_noise_curve auto and for --report_noise auto), the defect map, the match coefficients, the shots.  Completes opt.dpc, opt.match
-    opt.rows and opt.report; -> (dmap: the cellmask
+    (ONE estimate for both, for --row_noise_curve auto, --col_noise_curve auto and for --report_noise auto), the defect map, the column map, the match coefficients, the shots.  Completes opt.dpc, opt.match
+    opt.rows, opt.cols and opt.report, leaves the column map of --col_noise in opt.cols_map; -> (dmap: the cellmask
     or None, match: struct rvdd_match_cfg or None, shots [(key, [paths])])."""
     curve = None
     if opt.dpc is not None and opt.dpc[2] is None:
@@ -419,8 +464,14 @@ def prepasses(opt, dataset, dev):
     if rows is not None and rows[2] is None:      # auto, or the curve of --dpc_noise auto: the one estimate
         curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--row_noise_curve')
         opt.rows = rows[:2] + curve + rows[4:]
+    cols = getattr(opt, "cols", None)
+    if cols is not None and cols[0] == "auto" and cols[6] is None:      # auto, or the curve of --dpc_noise auto: the one estimate
+        curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--col_noise_curve')
+        opt.cols = cols[:6] + curve + cols[8:]
     # --dpc_map: ONE map for the run, read or found before any push; --dpc_static_only: --dpc has named the rule and is done
     dmap = None if opt.dpc_map is None else find_dpc_map(dataset, dev, opt)
+    # --col_noise: ONE column map for the run, read or found before any push
+    opt.cols_map = None if cols is None else find_cols_map(dataset, dev, opt)
     if opt.dpc_static_only:
         opt.dpc = None
     match = None
@@ -480,6 +531,12 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
                          % (2 * dmap.shape[1], 2 * dmap.shape[0], videos[0][0], W, H))
     if dmap is not None:
         rt.set_dpc_map(dmap)
+    cmap = getattr(opt, "cols_map", None)
+    if cmap is not None and cmap.shape[1] != W // 2:
+        raise SystemExit("--col_noise: the map is one of %d mosaic columns, video %r has frames of %d x %d (one camera per run)"
+                         % (2 * cmap.shape[1], videos[0][0], W, H))
+    if cmap is not None:
+        rt.set_cols(cmap)
     rows = getattr(opt, "rows", None)
     if rows is not None:
         rt.set_rows(rows_cfg(rows[0], *rows[2:]))
@@ -550,6 +607,8 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
         rt.set_resid(False)
     if rows is not None:
         rt.set_rows(None)
+    if cmap is not None:
+        rt.set_cols(None)
     return written
 
 

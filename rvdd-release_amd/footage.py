@@ -1,5 +1,5 @@
-"""What the four footage commands (`denoise`, `noise`, `cuts`, `dpc_map`) share: opening the rawvideo dataset, host frames to the device
-and through the ingest, the `--dpc*` flags with the noise estimate they may ask for, the `--row_noise*` flags and the `--report*` flags.  The commands import this module and the
+"""What the five footage commands (`denoise`, `noise`, `cuts`, `dpc_map`, `col_noise`) share: opening the rawvideo dataset, host frames to the device
+and through the ingest, the `--dpc*` flags with the noise estimate they may ask for, the `--row_noise*` flags, the `--col_noise*` flags and the `--report*` flags.  The commands import this module and the
 feature modules; nothing here or there imports a command.
 """
 from __future__ import annotations
@@ -170,6 +170,77 @@ def rows_line(acc, frames, spec, bit_depth, ww, key):
     return ('rows: %d applied, %d skipped, %d clamped rows, rms offset %.3f DN (the estimate alone, on flat footage without row noise: %.3f DN) '
             'in %d frames (%s)' % (int(acc["applied"].sum()), int(acc["skipped"].sum()), int(acc["clamped"].sum()), rows_rms(acc),
                                    rows_floor_rms(a, b, floor, bit_depth, ww), frames, key))
+
+
+def add_cols_arguments(p) -> None:
+    """the six flags of the column-noise correction, beside --row_noise; `cols_arguments` reads them"""
+    p.add_argument('--col_noise', type=str, default=None, help='take column fixed-pattern noise out of every frame on the device: FILE (a map '
+                   'python -m rvdd_release_amd.col_noise wrote) or auto (found in the footage before streaming starts)')
+    p.add_argument('--col_noise_curve', type=str, default=None, help='with --col_noise auto, the curve of the gate: a,b[,floor] (var = a * m - b in '
+                   'DN of the frames), auto (estimated from the footage), iso3200 or iso12800; default: the curve of --dpc')
+    p.add_argument('--col_noise_frames', type=int, default=None, help='with --col_noise auto: frames estimated per run, spread over the videos (default 32)')
+    p.add_argument('--col_noise_gate', type=float, default=None, help='with --col_noise auto: the gate K in standard deviations of the curve (default 3)')
+    p.add_argument('--col_noise_sigma', type=float, default=None, help='with --col_noise auto: a column is changed where its offset is at least this '
+                   'many standard errors of its own estimate (default 3; 0 changes every column)')
+    p.add_argument('--col_noise_max', type=float, default=None, help='with --col_noise auto: the largest offset taken out, in DN (default (2^bit_depth - 1) / 64)')
+
+
+def cols_arguments(col_noise, curve, frames, gate, sigma, max_dn, dpc, bit_depth):
+    """--col_noise and its five flags -> None (no --col_noise), ("file", path) or ("auto", frames, k_gate, k_sig, max_dn, source, a, b,
+    floor): source says where the curve var = a * m - b (DN of `bit_depth`) comes from, as `rows_arguments` does ("a,b", "iso<ISO>",
+    "auto" with a and b None for the command to estimate, or "dpc": dpc = what `dpc_arguments` returned).  SystemExit where the flags
+    do not fit together."""
+    given = [n for n, v in (("col_noise_curve", curve), ("col_noise_frames", frames), ("col_noise_gate", gate), ("col_noise_sigma", sigma),
+                            ("col_noise_max", max_dn)) if v is not None]
+    if col_noise is None:
+        if given:
+            raise SystemExit("--col_noise_curve, --col_noise_frames, --col_noise_gate, --col_noise_sigma and --col_noise_max belong to --col_noise auto")
+        return None
+    if col_noise != "auto":
+        if given:
+            raise SystemExit("--%s belongs to --col_noise auto: --col_noise %s reads a map that is already made" % (given[0], col_noise))
+        return ("file", col_noise)
+    inf = float("inf")
+    frames, gate, sigma = 32 if frames is None else int(frames), 3.0 if gate is None else float(gate), 3.0 if sigma is None else float(sigma)
+    if frames < 1:
+        raise SystemExit("--col_noise_frames must be >= 1, got %d" % frames)
+    if not (gate > 0 and gate < inf):
+        raise SystemExit("--col_noise_gate is the gate in standard deviations, > 0 (around 3), got %r" % gate)
+    if not (sigma >= 0 and sigma < inf):
+        raise SystemExit("--col_noise_sigma is a number of standard errors, >= 0 (around 3; 0 changes every column), got %r" % sigma)
+    max_dn = float((1 << int(bit_depth)) - 1) / 64.0 if max_dn is None else float(max_dn)      # a guess, as for the rows
+    if not (max_dn > 0 and max_dn < inf):
+        raise SystemExit("--col_noise_max is the largest offset taken out in DN, > 0, got %r" % max_dn)
+    head = ("auto", frames, gate, sigma, max_dn)
+    floor = 1.0
+    if curve is None:
+        if dpc is None:
+            raise SystemExit("--col_noise auto needs the sensor's noise curve: --col_noise_curve a,b[,floor] (var = a * m - b in DN of the frames), "
+                             "--col_noise_curve auto (estimated from the footage), --col_noise_curve iso3200 / iso12800 (a checkpoint "
+                             "family's curve, rescaled to --bit_depth) -- or the curve of --dpc, which then serves")
+        return head + ("dpc", dpc[2], dpc[3], dpc[4])
+    if curve == 'auto':
+        return head + ("auto", None, None, floor)
+    if curve.startswith('iso'):
+        try:
+            iso = int(curve[3:])
+            a, b = dpc_iso_curve(iso, bit_depth)
+        except ValueError:
+            raise SystemExit("--col_noise_curve %s: the families are %s" % (curve, ', '.join('iso%d' % k for k in DPC_ISO_CURVES)))
+        return head + ("iso%d" % iso, a, b, floor)
+    f = curve.split(',')
+    try:
+        if len(f) not in (2, 3):
+            raise ValueError(curve)
+        a, b = float(f[0]), float(f[1])
+        floor = float(f[2]) if len(f) == 3 else 1.0
+    except ValueError:
+        raise SystemExit("--col_noise_curve takes a,b[,floor], auto, iso3200 or iso12800, got %r" % curve)
+    if not abs(a) < inf or not abs(b) < inf:
+        raise SystemExit("--col_noise_curve: a and b must be finite, got %r" % curve)
+    if not (floor > 0 and floor < inf):
+        raise SystemExit("--col_noise_curve: the floor must be > 0, got %r" % floor)
+    return head + ("a,b", a, b, floor)
 
 
 def add_report_arguments(p) -> None:

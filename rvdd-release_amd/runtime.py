@@ -312,6 +312,40 @@ def rows_floor_rms(noise_a: float, noise_b: float, var_floor: float, bit_depth: 
     return 1.35 * (max(noise_a * mid - noise_b, var_floor) / (2.0 * ww)) ** 0.5
 
 
+COLS_MAX_HH = 4096                                # the tallest plane rvdd_cols_estimate takes
+COLS_STATES = ("unsupported", "applied", "clamped", "insignificant")      # mstate 0 .. 3 of rvdd_cols_fit
+
+
+def cols_cfg(k_gate: float, noise_a: float, noise_b: float, var_floor: float = 1.0) -> "_lib.RvddColsCfg":
+    """struct rvdd_cols_cfg: the gate in standard deviations of the curve var(m) = noise_a * m - noise_b (DN of the frames' bit
+    depth) and the least variance assumed."""
+    return _lib.RvddColsCfg(float(k_gate), float(noise_a), float(noise_b), float(var_floor))
+
+
+def cols_fit(offsets, state, min_frames: int, k_sig: float = 3.0, max_dn: float = 64.0):
+    """The static column map from the per-frame estimates of F frames (rvdd_cols_fit: on the host, no GPU needed; device tensors are
+    copied, which synchronises).  offsets float32 [F,2,ww], state uint8 [F,2,ww], as `RvddRuntime.cols_estimate` gives them.
+    -> (map float32 [2,ww] in DN, mstate uint8 [2,ww]: 0 unsupported, 1 applied, 2 applied and clamped, 3 insignificant,
+    stats {"unsupported", "applied", "clamped", "insignificant", "sum_q2": ints; "floor_dn": float})."""
+    import numpy as np
+    lib = _lib.load()
+    o = np.ascontiguousarray(offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else offsets)
+    st = np.ascontiguousarray(state.detach().cpu().numpy() if torch.is_tensor(state) else state)
+    if o.ndim != 3 or o.shape[1] != 2 or o.dtype != np.float32 or st.shape != o.shape or st.dtype != np.uint8:
+        raise RuntimeError(f"cols_fit: offsets is float32 [F,2,ww] and state uint8 [F,2,ww], got {o.dtype} {o.shape} and {st.dtype} {st.shape}")
+    F, _, ww = o.shape
+    m = np.zeros((2, ww), np.float32)
+    ms = np.zeros((2, ww), np.uint8)
+    stats = _lib.RvddColsStats()
+    cfg = _lib.RvddColsFitCfg(int(min_frames), float(k_sig), float(max_dn))
+    rc = lib.rvdd_cols_fit(o.ctypes.data, st.ctypes.data, F, ww, C.byref(cfg), m.ctypes.data, ms.ctypes.data, C.byref(stats))
+    if rc != 0:
+        raise RuntimeError(f"rvdd_cols_fit failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    out = {name: int(stats.counts[i]) for i, name in enumerate(COLS_STATES)}
+    out.update(sum_q2=int(stats.sum_q2), floor_dn=float(stats.floor_dn))
+    return m, ms, out
+
+
 def nearest_iso(a: float, b: float, bit_depth: int = 12, levels=(0.20, 0.45, 0.80)):
     """Which of DPC_ISO_CURVES lies closest to the curve (a, b) in DN of `bit_depth`: -> (iso, ratios), the ISO whose predicted
     standard deviation at 20 %, 45 % and 80 % of 2^bit_depth - 1 is nearest in the log (the largest |log ratio| over the levels is
@@ -868,6 +902,43 @@ class RvddRuntime:
         host = _lib.RvddRowsAcc()
         self._check(self.lib.rvdd_rows_read(self.h, int(slot), C.byref(host), self._stream()), "rvdd_rows_read")
         return rows_acc_arrays(host)
+
+    # -- column fixed-pattern noise -------------------------------------------------------------
+    def cols_estimate(self, packed: torch.Tensor, cfg, bit_depth: int = 12):
+        """One offset per frame, column parity and plane column of packed frames [n,4,hh,ww] (rvdd_cols_estimate; cfg:
+        `cols_cfg(...)`, the curve in DN of `bit_depth`).  -> (offsets float32 [n,2,ww], state uint8 [n,2,ww]: 0 skipped, 1 applied);
+        `cols_fit` pools them over the frames.  Nothing is synchronised."""
+        packed, n, hh, ww = _frames(packed, 4, "cols_estimate: packed is [n,4,hh,ww]", "packed", self.device)
+        offsets = torch.empty((n, 2, ww), dtype=torch.float32, device=self._tdev)
+        state = torch.empty((n, 2, ww), dtype=torch.uint8, device=self._tdev)
+        self._check(self.lib.rvdd_cols_estimate(self.h, _ptr(packed), n, hh, ww, int(bit_depth), C.byref(cfg), _ptr(offsets), _ptr(state),
+                                                self._stream()), "rvdd_cols_estimate")
+        return offsets, state
+
+    def cols_apply(self, packed: torch.Tensor, cmap: torch.Tensor, bit_depth: int = 12, gray: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The map `cmap` (a device float32 tensor [2,ww], DN of `bit_depth`) taken out of packed frames [n,4,hh,ww] IN PLACE
+        (rvdd_cols_apply), gray [n,hh,ww] re-formed in the columns with a non-zero offset.  -> packed.  Both must be contiguous: they
+        are written where they lie.  Nothing is synchronised."""
+        packed, n, hh, ww = _frames(packed, 4, "cols_apply: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
+        cmap = _dev_tensor(cmap, "cmap", self.device, shape=(2, ww), form=f"cols_apply: cmap is a float32 tensor [2,{ww}], as cols_fit gives it")
+        if gray is not None:
+            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
+        self._check(self.lib.rvdd_cols_apply(self.h, _ptr(packed), _ptr(gray), _ptr(cmap), n, hh, ww, int(bit_depth), self._stream()),
+                    "rvdd_cols_apply")
+        return packed
+
+    def set_cols(self, cmap=None):
+        """The column map as a stage of `video_push`, behind `set_dpc` and in front of `set_rows` and `set_match` (rvdd_set_cols):
+        cmap float32 [2,ww] on the host (a NumPy array or CPU tensor, DN of the pushes' bit depth), None = off (the default).
+        Synchronises the device."""
+        if cmap is None:
+            self._check(self.lib.rvdd_set_cols(self.h, None, 0), "rvdd_set_cols")
+            return
+        import numpy as np
+        m = np.ascontiguousarray(cmap.cpu().numpy() if torch.is_tensor(cmap) else cmap)
+        if m.ndim != 2 or m.shape[0] != 2 or m.dtype != np.float32:
+            raise RuntimeError(f"set_cols: cmap is float32 [2,ww], got {m.dtype} {m.shape}")
+        self._check(self.lib.rvdd_set_cols(self.h, m.ctypes.data, m.shape[1]), "rvdd_set_cols")
 
     def set_dpc(self, cfg=None):
         """The correction as a stage of `video_push`, between the ingest and the kept frames (rvdd_set_dpc): cfg = `dpc_cfg(...)`,
