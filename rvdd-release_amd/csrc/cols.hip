@@ -1,77 +1,48 @@
 // Column fixed-pattern noise of packed raw frames: one offset per frame, column parity and plane column estimated (rvdd_cols_estimate),
 // pooled over the frames on the host (rvdd_cols_fit, noise_fit.hip) and taken out in place as a static map (rvdd_cols_apply); the stage
-// rvdd_set_cols puts behind rvdd_set_dpc in rvdd_video_push.  The rule is in include/rvdd.h.  Compiled -ffp-contract=off like rows.hip:
-// every operation below is rounded to f32 on its own, so that offsets, states and the written samples are the bits of the NumPy
-// restatement (tests/cols_ref.py).
+// rvdd_set_cols puts behind rvdd_set_dpc in rvdd_video_push.  The rule is in include/rvdd.h, its device form -- the gated key, the
+// digit-wise median search, the per-cell step -- in line_noise.h, which rows.hip shares.  Compiled -ffp-contract=off like rows.hip:
+// every operation is rounded to f32 on its own, so that offsets, states and the written samples are the bits of the NumPy restatement
+// (tests/cols_ref.py).  What is this file's own:
 //
-// Estimate.  The transpose of rows.hip's: a column's 2 hh samples lie ww floats apart, so a workgroup per column would read 4-byte
-// words at a stride.  Instead a workgroup owns a STRIP of CB neighbouring plane columns of one (frame, parity): 64 min(CB, 16) threads,
-// thread t on strip column t % CB for good -- its nine column indices (the site and the eight mirrored neighbours) are formed once --
-// walking the 2 hh rows of planes j and j + 2, a wave covering 64 / CB whole row segments of CB floats a step.  The eight neighbours
-// are loaded like the site: lanes next to each other read words next to each other, and all but the halo of eight columns a strip
-// are the workgroup's own sites, so they come from the vector cache.  The sample's d = x - median of eight goes to LDS as rows.hip's
-// 32-bit key (0xffffffff outside the gate), column-major: keys[column][2 hh] at a pitch of 2 hh | 1 words.  The pitch is ODD, so the
-// CB lanes that write one row of the strip fall on CB different banks (ds_write_b32 banks are word % 32, CB <= 32), and the 64 lanes
-// that read consecutive keys of one column read consecutive words: neither conflicts.
+// Estimate.  A column's 2 hh samples lie ww floats apart, so a workgroup per column would read 4-byte words at a stride.  Instead a
+// workgroup owns a STRIP of CB neighbouring plane columns of one (frame, parity): 64 min(CB, 16) threads, thread t on strip column
+// t % CB for good -- its nine column indices (the site and the eight mirrored neighbours) are formed once -- walking the 2 hh rows of
+// planes j and j + 2, a wave covering 64 / CB whole row segments of CB floats a step.  The eight neighbours are loaded like the site:
+// lanes next to each other read words next to each other, and all but the halo of eight columns a strip are the workgroup's own
+// sites, so they come from the vector cache.  The sample's key goes to LDS, column-major: keys[column][2 hh] at a pitch of 2 hh | 1
+// words.  The pitch is ODD, so the CB lanes that write one row of the strip fall on CB different banks (ds_write_b32 banks are
+// word % 32, CB <= 32), and the 64 lanes that read consecutive keys of one column read consecutive words: neither conflicts.
 //
-// After ONE barrier a wave owns a column (wave w the columns w, w + waves, ...) and runs rows.hip's digit-wise search over the
-// column's keys from LDS: two bits a round, three thresholds counted at once, one DPP sum per wave and threshold pair, no barrier and
-// no LDS word written in the search at all -- 16 rounds, one more (a count and a minimum) for the upper middle of an even count.  No
-// histogram, no LDS atomics: frames of quantised DN are full of equal d, and the search takes the same steps whatever the values.
+// After ONE barrier a wave owns a column (wave w the columns w, w + waves, ...) and runs the search over the column's keys from LDS:
+// one DPP sum per wave and threshold pair, no barrier and no LDS word written in the search at all.
 //
 // CB is the largest of 32, 16, 8, 4 whose keys fit the 160 KiB of a CU: 4 CB (2 hh | 1) bytes, which gives 32 columns up to 639 rows,
 // 16 up to 1279, 8 up to 2559, 4 up to the cap of 4096 rows (kColsMaxHH; a lane then counts 128 keys a round and a wave's count
 // stays below 2^16, so that two counts share a register).  With CB < 16 a workgroup is CB waves: a wave per column in the search.
 //
-// Apply.  rows.hip's stream with the offset indexed by column: a thread owns the four planes of NC cells of a cell row (NC = 4:
-// ww % 4 == 0 and 16-byte aligned tensors, 16-byte loads and stores; NC = 1 otherwise; the same arithmetic per sample, the same bits).
-// A sample whose column has a zero offset keeps the bits it was loaded with; a gray cell whose two offsets are zero is not written.
+// Apply.  A pure stream in place, the offset indexed by column.  A sample whose column has a zero offset keeps the bits it was loaded
+// with; a gray cell whose two offsets are zero is not written.
 #include "../../include/rvdd.h"
-#include "dpc_rule.h"      // dn_of, norm_dn, sort8
+#include "line_noise.h"
 
 namespace {
 
 constexpr int kColsMaxHH = 4096;
 constexpr int kColsMaxThreads = 1024;
-constexpr int kColsThreads = 256;                                    // the apply kernel's
+constexpr int kColsThreads = kLineApplyThreads;                      // the apply kernel's
 constexpr size_t kColsLds = 160 * 1024;
-constexpr unsigned kColsNoKey = 0xffffffffu;
-
-// the plane column of the horizontal neighbour dc of column c: mirrored about the site where c + dc lies outside; in a plane of fewer
-// than nine columns c - dc may lie outside as well, and is then reflected about the plane's edge (-q -> q, ww - 1 + q -> ww - 1 - q)
-__device__ __forceinline__ int cols_neighbour(int c, int dc, int ww) {
-    int q = c + dc;
-    if (q < 0 || q >= ww) q = c - dc;
-    if (q < 0) q = -q;
-    if (q >= ww) q = 2 * (ww - 1) - q;
-    return q;
-}
-
-__device__ __forceinline__ unsigned cols_key(float d) {
-    const unsigned u = __float_as_uint(d);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-
-__device__ __forceinline__ float cols_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
 // |{key < t[n]}| over one column's nk keys for NT <= 3 thresholds: every lane of the wave arrives, every lane gets the counts.  A lane
 // counts the keys lane, lane + 64, ... -- at most 128, so that a wave's count stays below 2^16 and two counts share a register
 template <int NT>
 __device__ __forceinline__ void cols_count(const unsigned* __restrict__ col, int nk, int lane, const unsigned (&t)[NT], unsigned (&out)[NT]) {
-    static_assert(NT >= 1 && NT <= 3, "two counts below 2^16 in one register");
     unsigned lo = 0, hi = 0;
 #pragma unroll 4
-    for (int q = lane; q < nk; q += 64) {
-        const unsigned key = col[q];
-        lo += key < t[0] ? 1u : 0u;
-        if constexpr (NT > 1) lo += key < t[1] ? 0x10000u : 0u;
-        if constexpr (NT > 2) hi += key < t[2] ? 1u : 0u;
-    }
+    for (int q = lane; q < nk; q += 64) line_count_add(col[q], t, lo, hi);
     lo = wave_sum_u32(lo);
     if constexpr (NT > 2) hi = wave_sum_u32(hi);
-    out[0] = NT > 1 ? lo & 0xffffu : lo;
-    if constexpr (NT > 1) out[1] = lo >> 16;
-    if constexpr (NT > 2) out[2] = hi;
+    line_count_unpack(lo, hi, out);
 }
 
 // CB: the strip's columns (a power of two <= 32); blockDim.x = 64 * min(CB, 16); dynamic LDS: CB * pitch words, pitch = 2 hh | 1
@@ -92,7 +63,7 @@ __global__ void __launch_bounds__(kColsMaxThreads) cols_estimate_kernel(const fl
         if (c < ww) {
             int at[9];
 #pragma unroll
-            for (int e = 0; e < 9; ++e) at[e] = e == 4 ? c : cols_neighbour(c, e - 4, ww);
+            for (int e = 0; e < 9; ++e) at[e] = e == 4 ? c : line_neighbour(c, e - 4, ww);
             unsigned* mine = cols_keys + sc * pitch;
             const int step = (int)blockDim.x >> cb_log2;
             for (int s = tid >> cb_log2; s < nk; s += step) {
@@ -100,12 +71,7 @@ __global__ void __launch_bounds__(kColsMaxThreads) cols_estimate_kernel(const fl
                 float w[9];
 #pragma unroll
                 for (int e = 0; e < 9; ++e) w[e] = dn_of(row[at[e]], P.top);
-                float v[8] = {w[0], w[1], w[2], w[3], w[5], w[6], w[7], w[8]};
-                sort8(v);
-                const float m = (v[3] + v[4]) * 0.5f;
-                const float d = w[4] - m;
-                const float var = fmaxf(P.a * m - P.b, P.floor);
-                mine[s] = d * d <= P.k2 * var ? cols_key(d) : kColsNoKey;
+                mine[s] = line_key(w, P);
             }
         }
     }
@@ -114,45 +80,27 @@ __global__ void __launch_bounds__(kColsMaxThreads) cols_estimate_kernel(const fl
     for (int sc = wave; sc < CB && c0 + sc < ww; sc += waves) {      // uniform in the wave
         const unsigned* col = cols_keys + sc * pitch;
         const int64_t out = (int64_t)ij * ww + c0 + sc;
-        unsigned cnt;
-        {
-            const unsigned t[1] = {kColsNoKey};
-            unsigned c[1];
-            cols_count<1>(col, nk, lane, t, c);
-            cnt = c[0];
-        }
-        if (cnt == 0 || cnt < (unsigned)hh) {                        // skipped: 2 cnt >= 2 hh is not met
+        const LineMedian med = line_median(
+            (unsigned)hh, [&](const auto& t, auto& c) { cols_count(col, nk, lane, t, c); },
+            [&](unsigned prefix) {
+                unsigned le = 0, above = kLineNoKey;
+#pragma unroll 4
+                for (int q = lane; q < nk; q += 64) {
+                    const unsigned key = col[q];
+                    le += key <= prefix ? 1u : 0u;
+                    above = min(above, key > prefix ? key : kLineNoKey);
+                }
+                return LineAbove{wave_sum_u32(le), ~wave_max_u32(~above)};      // the wave's sum and minimum
+            });
+        if (med.skipped) {
             if (lane == 0) {
                 offsets[out] = 0.0f;
                 state[out] = 0;
             }
             continue;
         }
-        const unsigned k = (cnt - 1) >> 1;
-        unsigned prefix = 0;
-#pragma unroll 1
-        for (int b = 30; b >= 0; b -= 2) {
-            const unsigned t[3] = {prefix | (1u << b), prefix | (2u << b), prefix | (3u << b)};
-            unsigned c[3];
-            cols_count<3>(col, nk, lane, t, c);
-            const unsigned digit = (c[0] <= k ? 1u : 0u) + (c[1] <= k ? 1u : 0u) + (c[2] <= k ? 1u : 0u);      // the counts ascend
-            prefix |= digit << b;
-        }
-        unsigned upper = prefix;                                     // the key of rank cnt / 2
-        if (!(cnt & 1)) {
-            unsigned le = 0, above = kColsNoKey;
-#pragma unroll 4
-            for (int q = lane; q < nk; q += 64) {
-                const unsigned key = col[q];
-                le += key <= prefix ? 1u : 0u;
-                above = min(above, key > prefix ? key : kColsNoKey);
-            }
-            le = wave_sum_u32(le);
-            above = ~wave_max_u32(~above);                           // the wave's minimum
-            if (le < k + 2) upper = above;                           // rank k + 1 lies above the key of rank k
-        }
         if (lane == 0) {
-            offsets[out] = (cols_unkey(prefix) + cols_unkey(upper)) * 0.5f;
+            offsets[out] = line_midpoint(med);
             state[out] = 1;
         }
     }
@@ -189,28 +137,15 @@ __global__ void __launch_bounds__(kColsThreads) cols_apply_kernel(float* __restr
         const float(&o)[NC] = o2[k & 1];
         float* p = packed + ((int64_t)img * 4 + k) * hw + (int64_t)y * ww + x;
         float c[NC], v[NC];
-        if constexpr (NC == 4) {
-            const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-            c[0] = q[0]; c[1] = q[1]; c[2] = q[2]; c[3] = q[3];
-        } else {
-            c[0] = p[0];
-        }
+        line_load_cells<NC>(p, c);
         bool hit = false;
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
-            const float d = dn_of(c[i], top) - o[i];
-            g[i] = k ? g[i] + d : d;
+            const float d = line_take(c[i], o[i], top, k, g[i]);
             v[i] = o[i] != 0.0f ? norm_dn(d, top) : c[i];            // a column without an offset keeps its bits
             hit = hit || o[i] != 0.0f;
         }
-        if (hit) {
-            if constexpr (NC == 4) {
-                const f32x4 q = {v[0], v[1], v[2], v[3]};
-                *reinterpret_cast<f32x4*>(p) = q;
-            } else {
-                p[0] = v[0];
-            }
-        }
+        if (hit) line_store_cells<NC>(p, v);
     }
     if (gray) {
         float* gp = gray + (int64_t)img * hw + (int64_t)y * ww + x;
@@ -219,15 +154,14 @@ __global__ void __launch_bounds__(kColsThreads) cols_apply_kernel(float* __restr
 #pragma unroll
             for (int i = 0; i < 4; ++i) all = all && (o2[0][i] != 0.0f || o2[1][i] != 0.0f);
             if (all) {
-                const f32x4 q = {g[0] * 0.25f, g[1] * 0.25f, g[2] * 0.25f, g[3] * 0.25f};
-                *reinterpret_cast<f32x4*>(gp) = q;
+                line_store_gray<4>(gp, g);
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (o2[0][i] != 0.0f || o2[1][i] != 0.0f) gp[i] = g[i] * 0.25f;
             }
         } else {
-            gp[0] = g[0] * 0.25f;
+            line_store_gray<1>(gp, g);
         }
     }
 }
@@ -258,7 +192,7 @@ hipError_t launch_cols_estimate(const float* packed, int n, int hh, int ww, int 
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(cols_estimate_kernel), kColsLds, attr_done); e != hipSuccess) return e;
     RowsParams P = p;
-    P.top = (float)((1u << bit_depth) - 1u);
+    P.top = top_of(bit_depth);
     const int cb = cols_strip(hh);
     const int cb_log2 = cb == 32 ? 5 : cb == 16 ? 4 : cb == 8 ? 3 : 2;
     const size_t lds = 4 * ((size_t)(2 * hh) | 1) * (size_t)cb;
@@ -268,29 +202,17 @@ hipError_t launch_cols_estimate(const float* packed, int n, int hh, int ww, int 
     return hipGetLastError();
 }
 
-bool cols_apply_wide(const float* packed, const float* gray, const float* map, int ww) {
-    return (ww & 3) == 0 &&
-           ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(gray) | reinterpret_cast<uintptr_t>(map)) & 15) == 0;
-}
-
-int64_t cols_apply_blocks(int n, int hh, int ww, bool wide) {
-    const int64_t per = (int64_t)hh * (wide ? ww >> 2 : ww);         // threads per frame
-    const int64_t bpf = (per + kColsThreads - 1) / kColsThreads;
-    if (bpf > 0x7fffffffll || (bpf > 0 && n > 0x7fffffffll / bpf)) return -1;
-    return n * bpf;
-}
-
 hipError_t launch_cols_apply(float* packed, float* gray, const float* map, int n, int hh, int ww, int bit_depth, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (!packed || !map || hh < 1 || ww < 1 || bit_depth < 1 || bit_depth > 16) return hipErrorInvalidValue;
-    const bool wide = cols_apply_wide(packed, gray, map, ww);
-    const int64_t blocks = cols_apply_blocks(n, hh, ww, wide);
+    const bool wide = line_apply_wide(ww, packed, gray, map);
+    int64_t bpf = 0;
+    const int64_t blocks = line_apply_blocks(n, hh, ww, wide, &bpf);
     if (blocks < 0) return hipErrorInvalidValue;
-    const unsigned bpf = (unsigned)(blocks / n);
-    const float top = (float)((1u << bit_depth) - 1u);
+    const float top = top_of(bit_depth);
     if (wide)
-        hipLaunchKernelGGL(cols_apply_kernel<4>, dim3((unsigned)blocks), dim3(kColsThreads), 0, s, packed, gray, map, hh, ww, bpf, top);
+        hipLaunchKernelGGL(cols_apply_kernel<4>, dim3((unsigned)blocks), dim3(kColsThreads), 0, s, packed, gray, map, hh, ww, (unsigned)bpf, top);
     else
-        hipLaunchKernelGGL(cols_apply_kernel<1>, dim3((unsigned)blocks), dim3(kColsThreads), 0, s, packed, gray, map, hh, ww, bpf, top);
+        hipLaunchKernelGGL(cols_apply_kernel<1>, dim3((unsigned)blocks), dim3(kColsThreads), 0, s, packed, gray, map, hh, ww, (unsigned)bpf, top);
     return hipGetLastError();
 }

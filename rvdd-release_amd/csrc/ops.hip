@@ -62,24 +62,40 @@ int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* ou
     return RVDD_OK;
 }
 
-int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out) {
+// the gate of rvdd_rows_cfg and rvdd_cols_cfg (Cfg): the fields the two share, in their order; *out = the kernel's parameters without a clamp
+template <class Cfg>
+static int line_params(rvdd_t* h, const char* fn, const Cfg* cfg, RowsParams* out) {
     if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
     if (!(cfg->k_gate > 0.0f) || !std::isfinite(cfg->k_gate)) return fail(h, RVDD_ERR_ARG, "%s: k_gate must be finite and > 0, got %g", fn, cfg->k_gate);
     if (!std::isfinite(cfg->noise_a)) return fail(h, RVDD_ERR_ARG, "%s: noise_a must be finite, got %g", fn, cfg->noise_a);
     if (!std::isfinite(cfg->noise_b)) return fail(h, RVDD_ERR_ARG, "%s: noise_b must be finite, got %g", fn, cfg->noise_b);
     if (!(cfg->var_floor > 0.0f) || !std::isfinite(cfg->var_floor)) return fail(h, RVDD_ERR_ARG, "%s: var_floor must be finite and > 0, got %g", fn, cfg->var_floor);
-    if (!(cfg->max_dn > 0.0f) || !std::isfinite(cfg->max_dn)) return fail(h, RVDD_ERR_ARG, "%s: max_dn must be finite and > 0, got %g", fn, cfg->max_dn);
     // the square rounded to f32 once, here (+inf for a huge gate: every finite sample is used)
-    *out = RowsParams{cfg->k_gate * cfg->k_gate, cfg->noise_a, cfg->noise_b, cfg->var_floor, cfg->max_dn, 0.0f};
+    *out = RowsParams{cfg->k_gate * cfg->k_gate, cfg->noise_a, cfg->noise_b, cfg->var_floor, 0.0f, 0.0f};
     return RVDD_OK;
 }
 
-int rows_shape(rvdd_t* h, const char* fn, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth) {
+int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out) {
+    RC(line_params(h, fn, cfg, out));
+    if (!(cfg->max_dn > 0.0f) || !std::isfinite(cfg->max_dn)) return fail(h, RVDD_ERR_ARG, "%s: max_dn must be finite and > 0, got %g", fn, cfg->max_dn);
+    out->max_dn = cfg->max_dn;
+    return RVDD_OK;
+}
+
+// the shape checks of the row (rows = true) and column calls: the axis the eight neighbours lie along needs five, the other one
+static int line_shape(rvdd_t* h, const char* fn, bool rows, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth) {
     if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 1..16, got %d", fn, bit_depth);
-    if (hh < 5) return fail(h, RVDD_ERR_ARG, "%s: hh must be >= 5 (four vertical neighbours on either side, mirrored about the site), got %d", fn, hh);
-    if (ww < 1) return fail(h, RVDD_ERR_ARG, "%s: ww must be >= 1, got %d", fn, ww);
-    if (ww > rows_max_ww()) return fail(h, RVDD_ERR_ARG, "%s: ww must be <= %d (a workgroup holds the 2 ww samples of a row in registers), got %d", fn, rows_max_ww(), ww);
+    if ((rows ? hh : ww) < 5) return fail(h, RVDD_ERR_ARG, "%s: %s must be >= 5 (four %s neighbours on either side, mirrored about the site), got %d", fn, rows ? "hh" : "ww", rows ? "vertical" : "horizontal", rows ? hh : ww);
+    if ((rows ? ww : hh) < 1) return fail(h, RVDD_ERR_ARG, "%s: %s must be >= 1, got %d", fn, rows ? "ww" : "hh", rows ? ww : hh);
+    if (rows && ww > rows_max_ww()) return fail(h, RVDD_ERR_ARG, "%s: ww must be <= %d (a workgroup holds the 2 ww samples of a row in registers), got %d", fn, rows_max_ww(), ww);
     if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    return RVDD_OK;
+}
+
+int run_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int n, int hh, int ww, int bit_depth, hipStream_t s) {
+    const double cells = (double)n * 4.0 * hh * ww;
+    Scope sc(h, s, "cols_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
+    HIPCHK(h, launch_cols_apply(packed, gray, map_dev, n, hh, ww, bit_depth, s));
     return RVDD_OK;
 }
 
@@ -480,7 +496,7 @@ int rvdd_rows_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, in
     if (!h) return RVDD_ERR_ARG;
     RowsParams p;
     RC(rows_params(h, "rvdd_rows_estimate", cfg, &p));
-    RC(rows_shape(h, "rvdd_rows_estimate", n, hh, ww, bit_depth));
+    RC(line_shape(h, "rvdd_rows_estimate", true, n, hh, ww, bit_depth));
     if (reinterpret_cast<uintptr_t>(acc) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: acc must be 8-byte aligned (sum_q2 is a 64-bit atomic)");
     if (n == 0) return RVDD_OK;
     if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: packed is required");
@@ -495,22 +511,14 @@ int rvdd_rows_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, in
 
 int rvdd_rows_apply(rvdd_t* h, float* packed, float* gray, const float* offsets, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream) {
     if (!h) return RVDD_ERR_ARG;
-    RC(rows_shape(h, "rvdd_rows_apply", n, hh, ww, bit_depth));
+    RC(line_shape(h, "rvdd_rows_apply", true, n, hh, ww, bit_depth));
     if (n == 0) return RVDD_OK;
     if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: packed is required");
     if (!offsets) return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: offsets is required");
-    if (rows_apply_blocks(n, hh, ww, rows_apply_wide(packed, gray, ww), nullptr) < 0)
+    if (line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray), nullptr) < 0)
         return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
     ENTER(h);
     HIPCHK(h, launch_rows_apply(packed, gray, offsets, n, hh, ww, bit_depth, static_cast<hipStream_t>(stream)));
-    return RVDD_OK;
-}
-
-static int cols_shape(rvdd_t* h, const char* fn, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth) {
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 1..16, got %d", fn, bit_depth);
-    if (ww < 5) return fail(h, RVDD_ERR_ARG, "%s: ww must be >= 5 (four horizontal neighbours on either side, mirrored about the site), got %d", fn, ww);
-    if (hh < 1) return fail(h, RVDD_ERR_ARG, "%s: hh must be >= 1, got %d", fn, hh);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
     return RVDD_OK;
 }
 
@@ -518,12 +526,9 @@ int rvdd_cols_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, in
                        float* offsets, uint8_t* state, void* stream) {
     const char* fn = "rvdd_cols_estimate";
     if (!h) return RVDD_ERR_ARG;
-    if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
-    if (!(cfg->k_gate > 0.0f) || !std::isfinite(cfg->k_gate)) return fail(h, RVDD_ERR_ARG, "%s: k_gate must be finite and > 0, got %g", fn, cfg->k_gate);
-    if (!std::isfinite(cfg->noise_a)) return fail(h, RVDD_ERR_ARG, "%s: noise_a must be finite, got %g", fn, cfg->noise_a);
-    if (!std::isfinite(cfg->noise_b)) return fail(h, RVDD_ERR_ARG, "%s: noise_b must be finite, got %g", fn, cfg->noise_b);
-    if (!(cfg->var_floor > 0.0f) || !std::isfinite(cfg->var_floor)) return fail(h, RVDD_ERR_ARG, "%s: var_floor must be finite and > 0, got %g", fn, cfg->var_floor);
-    RC(cols_shape(h, fn, n, hh, ww, bit_depth));
+    RowsParams p;
+    RC(line_params(h, fn, cfg, &p));
+    RC(line_shape(h, fn, false, n, hh, ww, bit_depth));
     if (hh > cols_max_hh())
         return fail(h, RVDD_ERR_ARG, "%s: hh must be <= %d (a workgroup holds the 2 hh keys of four columns in LDS), got %d", fn, cols_max_hh(), hh);
     if (n == 0) return RVDD_OK;
@@ -533,8 +538,6 @@ int rvdd_cols_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, in
     if (cols_estimate_blocks(n, hh, ww) < 0)
         return fail(h, RVDD_ERR_ARG, "%s: n = %d frames of ww = %d columns need a launch of more than 2^31 - 1 blocks", fn, n, ww);
     ENTER(h);
-    // the square rounded to f32 once, here (+inf for a huge gate: every finite sample is used)
-    const RowsParams p{cfg->k_gate * cfg->k_gate, cfg->noise_a, cfg->noise_b, cfg->var_floor, 0.0f, 0.0f};
     hipStream_t s = static_cast<hipStream_t>(stream);
     Scope sc(h, s, "cols_estimate_kernel", 0.0, (double)n * 4.0 * hh * ww * 4.0);
     HIPCHK(h, launch_cols_estimate(packed, n, hh, ww, bit_depth, p, offsets, state, s));
@@ -544,18 +547,14 @@ int rvdd_cols_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, in
 int rvdd_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream) {
     const char* fn = "rvdd_cols_apply";
     if (!h) return RVDD_ERR_ARG;
-    RC(cols_shape(h, fn, n, hh, ww, bit_depth));
+    RC(line_shape(h, fn, false, n, hh, ww, bit_depth));
     if (n == 0) return RVDD_OK;
     if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
     if (!map_dev) return fail(h, RVDD_ERR_ARG, "%s: map_dev is required", fn);
-    if (cols_apply_blocks(n, hh, ww, cols_apply_wide(packed, gray, map_dev, ww)) < 0)
+    if (line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray, map_dev), nullptr) < 0)
         return fail(h, RVDD_ERR_ARG, "%s: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, n, hh, ww);
     ENTER(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const double cells = (double)n * 4.0 * hh * ww;
-    Scope sc(h, s, "cols_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
-    HIPCHK(h, launch_cols_apply(packed, gray, map_dev, n, hh, ww, bit_depth, s));
-    return RVDD_OK;
+    return run_cols_apply(h, packed, gray, map_dev, n, hh, ww, bit_depth, static_cast<hipStream_t>(stream));
 }
 
 // the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine

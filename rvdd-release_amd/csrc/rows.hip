@@ -1,53 +1,27 @@
 // Row noise (banding) of packed raw frames: one offset per frame, row parity and plane row estimated (rvdd_rows_estimate) and taken
 // out in place (rvdd_rows_apply); the stage rvdd_set_rows puts behind rvdd_set_dpc in rvdd_video_push.  The rule is in
-// include/rvdd.h.  Compiled -ffp-contract=off like dpc.hip: every operation below is rounded to f32 on its own, so that offsets,
-// states, counts and the written samples are the bits of the NumPy restatement (tests/rows_ref.py).
+// include/rvdd.h, its device form -- the gated key, the digit-wise median search, the per-cell step -- in line_noise.h, which
+// cols.hip shares.  Compiled -ffp-contract=off like dpc.hip: every operation is rounded to f32 on its own, so that offsets, states,
+// counts and the written samples are the bits of the NumPy restatement (tests/rows_ref.py).  What is this file's own:
 //
 // Estimate.  One workgroup of 256 threads owns one (frame, parity, plane row): the 2 ww samples of planes 2j and 2j + 1, sample s on
 // thread s % 256, KPT = ceil(2 ww / 256) <= 32 of them per thread.  Workgroup ((i * 2 + j) * hh + r) reads the rows r - 4 .. r + 4 in
 // that order, so that workgroups next to each other read eight of their nine rows twice from L2 and a frame once from memory.  A
-// sample's d = x - median of its eight vertical neighbours stays in a register as a 32-bit key that sorts as d does (sign bit flipped,
-// negative values inverted); a sample outside the gate, or past the row's end, holds 0xffffffff -- no used d has that key (it is a
-// NaN's), and no threshold below exceeds it.
+// sample's key stays in a register.  A round of the search counts in the thread's own registers (counting by ballots kept a hundred
+// scalar pairs alive and spilled them), one DPP sum per wave, lane 0 of each wave leaves its counts in LDS, ONE barrier (the rounds
+// alternate between two sets of LDS words), every thread adds the four waves' counts.  The offset is clamped to +-max_dn and the
+// row counted in the frame's accumulator.
 //
-// The median of the cnt used d is exact and takes the same steps whatever the values: a frame of quantised DN is full of equal d, so
-// nothing here depends on how many keys are equal (no histogram, no LDS atomics).  The key of rank k = (cnt - 1) / 2 is the largest
-// P with |{key < P}| <= k; P is built from the top, two bits a round: the three thresholds prefix | (1, 2, 3) << b are counted at once
-// -- one compare and one add per key and threshold in the thread's own registers (counting by ballots kept a hundred scalar pairs alive
-// and spilled them), one DPP sum per wave, lane 0 of each wave leaves its counts in LDS, ONE barrier (the rounds alternate between two
-// sets of LDS words), every thread adds the four waves' counts -- and the digit is the
-// number of thresholds with a count <= k.  16 rounds.  The key of rank cnt / 2 (cnt even) is the same key where |{key <= P}| >= k + 2,
-// else the least key above P: one more round, a count and a minimum.
-//
-// Apply.  A pure stream in place: a thread owns the four planes of NC cells of a cell row (NC = 4: ww % 4 == 0 and 16-byte aligned
-// tensors, 16-byte loads and stores; NC = 1 otherwise; the same arithmetic per sample, the same bits).  A row whose two offsets are
-// zero is left after two loads; a plane whose offset is zero is read for the gray value and not written.
+// Apply.  A pure stream in place.  A row whose two offsets are zero is left after two loads; a plane whose offset is zero is read for
+// the gray value and not written.
 #include "../../include/rvdd.h"
-#include "dpc_rule.h"      // dn_of, norm_dn, sort8
+#include "line_noise.h"
 
 namespace {
 
-constexpr int kRowsThreads = 256;
+constexpr int kRowsThreads = kLineApplyThreads;
 constexpr int kRowsWaves = kRowsThreads / 64;
 constexpr int kRowsMaxKeys = 32;                                     // keys per thread at most: 2 ww <= 256 * 32
-constexpr unsigned kRowsNoKey = 0xffffffffu;
-
-// the plane row of the vertical neighbour dr of row r: mirrored about the site where r + dr lies outside; in a plane of fewer than
-// nine rows r - dr may lie outside as well, and is then reflected about the plane's edge (-q -> q, hh - 1 + q -> hh - 1 - q)
-__device__ __forceinline__ int rows_neighbour(int r, int dr, int hh) {
-    int q = r + dr;
-    if (q < 0 || q >= hh) q = r - dr;
-    if (q < 0) q = -q;
-    if (q >= hh) q = 2 * (hh - 1) - q;
-    return q;
-}
-
-__device__ __forceinline__ unsigned rows_key(float d) {
-    const unsigned u = __float_as_uint(d);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-
-__device__ __forceinline__ float rows_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
 // |{key < t[n]}| over the workgroup for NT <= 3 thresholds: every thread of the workgroup arrives, every thread gets the counts.
 // A thread counts its own keys -- at most 32, so that a wave's count stays below 2^16 and two counts share a register --, the wave
@@ -56,14 +30,10 @@ __device__ __forceinline__ float rows_unkey(unsigned k) { return __uint_as_float
 template <int KPT, int NT>
 __device__ __forceinline__ void rows_count(const unsigned (&key)[KPT], const unsigned (&t)[NT], unsigned (*words)[2], int lane, int wave,
                                            unsigned (&out)[NT]) {
-    static_assert(NT >= 1 && NT <= 3 && KPT <= 32, "two counts below 2^16 in one register");
+    static_assert(KPT <= 32, "two counts below 2^16 in one register");
     unsigned lo = 0, hi = 0;
 #pragma unroll
-    for (int q = 0; q < KPT; ++q) {
-        lo += key[q] < t[0] ? 1u : 0u;
-        if constexpr (NT > 1) lo += key[q] < t[1] ? 0x10000u : 0u;
-        if constexpr (NT > 2) hi += key[q] < t[2] ? 1u : 0u;
-    }
+    for (int q = 0; q < KPT; ++q) line_count_add(key[q], t, lo, hi);
     lo = wave_sum_u32(lo);
     if constexpr (NT > 2) hi = wave_sum_u32(hi);
     if (lane == 0) {
@@ -77,9 +47,7 @@ __device__ __forceinline__ void rows_count(const unsigned (&key)[KPT], const uns
         lo += words[w][0];
         if constexpr (NT > 2) hi += words[w][1];
     }
-    out[0] = NT > 1 ? lo & 0xffffu : lo;      // four waves of at most 2048 each
-    if constexpr (NT > 1) out[1] = lo >> 16;
-    if constexpr (NT > 2) out[2] = hi;
+    line_count_unpack(lo, hi, out);                                  // four waves of at most 2048 each
 }
 
 template <int KPT>
@@ -96,38 +64,54 @@ __global__ void __launch_bounds__(kRowsThreads) rows_estimate_kernel(const float
     // the nine rows in ascending dr; uniform
     int64_t at[9];
 #pragma unroll
-    for (int e = 0; e < 9; ++e) at[e] = (int64_t)(e == 4 ? r : rows_neighbour(r, e - 4, hh)) * ww;
+    for (int e = 0; e < 9; ++e) at[e] = (int64_t)(e == 4 ? r : line_neighbour(r, e - 4, hh)) * ww;
 
     unsigned key[KPT];
 #pragma unroll
     for (int q = 0; q < KPT; ++q) {
         const int s = tid + q * kRowsThreads;
-        unsigned k = kRowsNoKey;
+        unsigned k = kLineNoKey;
         if (s < 2 * ww) {
             const float* col = s < ww ? pl + s : pl + hw + (s - ww);
             float w[9];
 #pragma unroll
             for (int e = 0; e < 9; ++e) w[e] = dn_of(col[at[e]], P.top);
-            float v[8] = {w[0], w[1], w[2], w[3], w[5], w[6], w[7], w[8]};
-            sort8(v);
-            const float m = (v[3] + v[4]) * 0.5f;
-            const float d = w[4] - m;
-            const float var = fmaxf(P.a * m - P.b, P.floor);
-            if (d * d <= P.k2 * var) k = rows_key(d);
+            k = line_key(w, P);
         }
         key[q] = k;
     }
 
     int phase = 0;
-    unsigned cnt;
-    {
-        const unsigned t[1] = {kRowsNoKey};
-        unsigned c[1];
-        rows_count<KPT, 1>(key, t, words[phase], lane, wave, c);
-        phase ^= 1;
-        cnt = c[0];
-    }
-    if (cnt == 0 || cnt < (unsigned)ww) {                            // skipped (uniform): 2 cnt >= 2 ww is not met
+    const LineMedian med = line_median(
+        (unsigned)ww,
+        [&](const auto& t, auto& c) {
+            rows_count<KPT>(key, t, words[phase], lane, wave, c);
+            phase ^= 1;
+        },
+        [&](unsigned prefix) {
+            unsigned le = 0, above = kLineNoKey;
+#pragma unroll
+            for (int q = 0; q < KPT; ++q) {
+                le += key[q] <= prefix ? 1u : 0u;
+                above = min(above, key[q] > prefix ? key[q] : kLineNoKey);
+            }
+            le = wave_sum_u32(le);
+            above = ~wave_max_u32(~above);                           // the wave's minimum
+            if (lane == 0) {
+                words[phase][wave][0] = le;
+                words[phase][wave][1] = above;
+            }
+            __syncthreads();
+            le = 0;
+            above = kLineNoKey;
+#pragma unroll
+            for (int w = 0; w < kRowsWaves; ++w) {
+                le += words[phase][w][0];
+                above = min(above, words[phase][w][1]);
+            }
+            return LineAbove{le, above};
+        });
+    if (med.skipped) {                                               // uniform
         if (tid == 0) {
             offsets[row] = 0.0f;
             state[row] = 0;
@@ -135,43 +119,8 @@ __global__ void __launch_bounds__(kRowsThreads) rows_estimate_kernel(const float
         }
         return;
     }
-    const unsigned k = (cnt - 1) >> 1;
-    unsigned prefix = 0;
-#pragma unroll 1
-    for (int b = 30; b >= 0; b -= 2) {
-        const unsigned t[3] = {prefix | (1u << b), prefix | (2u << b), prefix | (3u << b)};
-        unsigned c[3];
-        rows_count<KPT, 3>(key, t, words[phase], lane, wave, c);
-        phase ^= 1;
-        const unsigned digit = (c[0] <= k ? 1u : 0u) + (c[1] <= k ? 1u : 0u) + (c[2] <= k ? 1u : 0u);      // the counts ascend
-        prefix |= digit << b;
-    }
-    unsigned upper = prefix;                                         // the key of rank cnt / 2
-    if (!(cnt & 1)) {                                                // uniform
-        unsigned le = 0, above = kRowsNoKey;
-#pragma unroll
-        for (int q = 0; q < KPT; ++q) {
-            le += key[q] <= prefix ? 1u : 0u;
-            above = min(above, key[q] > prefix ? key[q] : kRowsNoKey);
-        }
-        le = wave_sum_u32(le);
-        above = ~wave_max_u32(~above);                               // the wave's minimum
-        if (lane == 0) {
-            words[phase][wave][0] = le;
-            words[phase][wave][1] = above;
-        }
-        __syncthreads();
-        le = 0;
-        above = kRowsNoKey;
-#pragma unroll
-        for (int w = 0; w < kRowsWaves; ++w) {
-            le += words[phase][w][0];
-            above = min(above, words[phase][w][1]);
-        }
-        if (le < k + 2) upper = above;                               // rank k + 1 lies above the key of rank k
-    }
     if (tid == 0) {
-        const float o = (rows_unkey(prefix) + rows_unkey(upper)) * 0.5f;
+        const float o = line_midpoint(med);
         const float oc = fminf(fmaxf(o, -P.max_dn), P.max_dn);
         const bool clamped = oc != o;
         offsets[row] = oc;
@@ -203,36 +152,12 @@ __global__ void __launch_bounds__(kRowsThreads) rows_apply_kernel(float* __restr
         const float o = o2[k >> 1];
         float* p = packed + ((int64_t)img * 4 + k) * hw + (int64_t)y * ww + x;
         float c[NC], v[NC];
-        if constexpr (NC == 4) {
-            const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-            c[0] = q[0]; c[1] = q[1]; c[2] = q[2]; c[3] = q[3];
-        } else {
-            c[0] = p[0];
-        }
+        line_load_cells<NC>(p, c);
 #pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            const float d = dn_of(c[i], top) - o;
-            g[i] = k ? g[i] + d : d;
-            v[i] = norm_dn(d, top);
-        }
-        if (o != 0.0f) {
-            if constexpr (NC == 4) {
-                const f32x4 q = {v[0], v[1], v[2], v[3]};
-                *reinterpret_cast<f32x4*>(p) = q;
-            } else {
-                p[0] = v[0];
-            }
-        }
+        for (int i = 0; i < NC; ++i) v[i] = norm_dn(line_take(c[i], o, top, k, g[i]), top);
+        if (o != 0.0f) line_store_cells<NC>(p, v);
     }
-    if (gray) {
-        float* gp = gray + (int64_t)img * hw + (int64_t)y * ww + x;
-        if constexpr (NC == 4) {
-            const f32x4 q = {g[0] * 0.25f, g[1] * 0.25f, g[2] * 0.25f, g[3] * 0.25f};
-            *reinterpret_cast<f32x4*>(gp) = q;
-        } else {
-            gp[0] = g[0] * 0.25f;
-        }
-    }
+    if (gray) line_store_gray<NC>(gray + (int64_t)img * hw + (int64_t)y * ww + x, g);
 }
 
 template <int KPT>
@@ -257,7 +182,7 @@ hipError_t launch_rows_estimate(const float* packed, int n, int hh, int ww, int 
     const int64_t blocks = rows_estimate_blocks(n, hh);
     if (blocks < 0) return hipErrorInvalidValue;
     RowsParams P = p;
-    P.top = (float)((1u << bit_depth) - 1u);
+    P.top = top_of(bit_depth);
     const int need = (2 * ww + kRowsThreads - 1) / kRowsThreads;     // keys per thread
     const unsigned b = (unsigned)blocks;
     if (need <= 1) rows_estimate_go<1>(b, s, packed, offsets, state, acc, hh, ww, P);
@@ -270,26 +195,14 @@ hipError_t launch_rows_estimate(const float* packed, int n, int hh, int ww, int 
     return hipGetLastError();
 }
 
-bool rows_apply_wide(const float* packed, const float* gray, int ww) {
-    return (ww & 3) == 0 && ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(gray)) & 15) == 0;
-}
-
-int64_t rows_apply_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame) {
-    const int64_t per = (int64_t)hh * (wide ? ww >> 2 : ww);         // threads per frame
-    const int64_t bpf = (per + kRowsThreads - 1) / kRowsThreads;
-    if (per_frame) *per_frame = bpf;
-    if (bpf > 0x7fffffffll || (bpf > 0 && n > 0x7fffffffll / bpf)) return -1;
-    return n * bpf;
-}
-
 hipError_t launch_rows_apply(float* packed, float* gray, const float* offsets, int n, int hh, int ww, int bit_depth, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (!packed || !offsets || hh < 1 || ww < 1 || bit_depth < 1 || bit_depth > 16) return hipErrorInvalidValue;
-    const bool wide = rows_apply_wide(packed, gray, ww);
+    const bool wide = line_apply_wide(ww, packed, gray);
     int64_t bpf = 0;
-    const int64_t blocks = rows_apply_blocks(n, hh, ww, wide, &bpf);
+    const int64_t blocks = line_apply_blocks(n, hh, ww, wide, &bpf);
     if (blocks < 0) return hipErrorInvalidValue;
-    const float top = (float)((1u << bit_depth) - 1u);
+    const float top = top_of(bit_depth);
     if (wide)
         hipLaunchKernelGGL(rows_apply_kernel<4>, dim3((unsigned)blocks), dim3(kRowsThreads), 0, s, packed, gray, offsets, hh, ww, (unsigned)bpf, top);
     else

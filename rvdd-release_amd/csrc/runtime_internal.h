@@ -469,7 +469,10 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s);
 // the checks rvdd_dpc and rvdd_set_dpc share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
 int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* out);
 // the checks rvdd_rows_estimate and rvdd_set_rows share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
-int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out);// the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
+int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out);
+// launch_cols_apply inside its profile class, for rvdd_cols_apply and the stage behind rvdd_set_cols: 0, or the HIP error on the handle
+int run_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int n, int hh, int ww, int bit_depth, hipStream_t s);
+// the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
 int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg);
 int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
                    void* stream, bool async);

@@ -489,10 +489,20 @@ int rows_max_ww();                                // the widest plane a workgrou
 int64_t rows_estimate_blocks(int n, int hh);      // the grid of that launch; -1 = more than 2^31 - 1 blocks
 // packed [n][4][hh][ww] IN PLACE, gray [n][hh][ww] (nullable) in place: offsets [n][2][hh] taken out of the rows where they are not zero
 hipError_t launch_rows_apply(float* packed, float* gray, const float* offsets, int n, int hh, int ww, int bit_depth, hipStream_t s);
-// whether that launch takes the wide form (a thread owns four cells), and its grid (*per_frame: the blocks of one frame); -1 = more
-// than 2^31 - 1 blocks
-bool rows_apply_wide(const float* packed, const float* gray, int ww);
-int64_t rows_apply_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame);
+// whether an apply launch of rows.hip or cols.hip takes the wide form (a thread owns four cells: ww % 4 == 0 and every tensor it is
+// given 16-byte aligned), and its grid of kLineApplyThreads (*per_frame: the blocks of one frame); -1 = more than 2^31 - 1 blocks
+constexpr int kLineApplyThreads = 256;
+template <class... T>
+inline bool line_apply_wide(int ww, const T*... tensors) {
+    return (ww & 3) == 0 && ((reinterpret_cast<uintptr_t>(tensors) | ...) & 15) == 0;
+}
+inline int64_t line_apply_blocks(int n, int hh, int ww, bool wide, int64_t* per_frame) {
+    const int64_t per = (int64_t)hh * (wide ? ww >> 2 : ww);         // threads per frame
+    const int64_t bpf = (per + kLineApplyThreads - 1) / kLineApplyThreads;
+    if (per_frame) *per_frame = bpf;
+    if (bpf > 0x7fffffffll || (bpf > 0 && n > 0x7fffffffll / bpf)) return -1;
+    return n * bpf;
+}
 
 // cols.hip -- column fixed-pattern noise: one offset per frame, column parity and plane column (rvdd_cols_estimate), a static map
 // taken out (rvdd_cols_apply, the stage behind rvdd_set_cols).  The gate's parameters are RowsParams (max_dn is not read: no clamp here)
@@ -505,8 +515,6 @@ int cols_strip(int hh);                                  // the columns of a wor
 int64_t cols_estimate_blocks(int n, int hh, int ww);     // the grid of that launch; -1 = more than 2^31 - 1 blocks
 // packed [n][4][hh][ww] IN PLACE, gray [n][hh][ww] (nullable) in place: map [2][ww] (DEVICE, DN) taken out of the columns where it is not zero
 hipError_t launch_cols_apply(float* packed, float* gray, const float* map, int n, int hh, int ww, int bit_depth, hipStream_t s);
-bool cols_apply_wide(const float* packed, const float* gray, const float* map, int ww);
-int64_t cols_apply_blocks(int n, int hh, int ww, bool wide);      // -1 = more than 2^31 - 1 blocks
 
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from

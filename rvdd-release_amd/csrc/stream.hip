@@ -105,11 +105,7 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
             HIPCHK(h, launch_dpc_map_apply(packed, ring_gray, e - b, hh, ww, bit_depth, dmap.mask, dmap.cells, dmap.ncells, s));
         if (dpc.on) HIPCHK(h, launch_dpc(packed, ring_packed, ring_gray, e - b, hh, ww, bit_depth, dpc.p, dpc.counts + 2 * (size_t)b, s));
         // rvdd_set_cols: the static column offsets taken out of the ring's planes and gray planes in place: one launch
-        if (cols.on) {
-            const double cells = (double)(e - b) * 4.0 * (double)hw;
-            Scope sc(h, s, "cols_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
-            HIPCHK(h, launch_cols_apply(ring_packed, ring_gray, cols.map, e - b, hh, ww, bit_depth, s));
-        }
+        if (cols.on) RC(run_cols_apply(h, ring_packed, ring_gray, cols.map, e - b, hh, ww, bit_depth, s));
         // rvdd_set_rows: the row offsets of the (corrected) frames estimated and taken out of the ring's planes and gray planes in place
         if (rows.on) {
             const double cells = (double)(e - b) * 4.0 * (double)hw;

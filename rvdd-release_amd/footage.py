@@ -108,6 +108,43 @@ def estimate_noise(dataset, dev, bit_depth, frames, flag='--dpc_noise'):
     return (r["a"], r["b"])
 
 
+def curve_argument(flag, curve, dpc, bit_depth):
+    """--row_noise_curve / --col_noise_curve (`flag`, with its dashes) -> (source, a, b, floor): where the curve var = a * m - b (DN of
+    `bit_depth`) comes from -- "a,b", "iso<ISO>", "auto" (a and b None, for the command to estimate from the footage) or, without the
+    flag, "dpc" (dpc = what `dpc_arguments` returned: its curve and floor, a and b None under --dpc_noise auto) -- and the least
+    variance.  SystemExit where it cannot be read."""
+    owner = {'--row_noise_curve': "--row_noise", '--col_noise_curve': "--col_noise auto"}[flag]      # what the curve is asked for
+    floor = 1.0
+    if curve is None:
+        if dpc is None:
+            raise SystemExit("%s needs the sensor's noise curve: %s a,b[,floor] (var = a * m - b in DN of the frames), "
+                             "%s auto (estimated from the footage), %s iso3200 / iso12800 (a checkpoint "
+                             "family's curve, rescaled to --bit_depth) -- or the curve of --dpc, which then serves" % (owner, flag, flag, flag))
+        return ("dpc", dpc[2], dpc[3], dpc[4])
+    if curve == 'auto':
+        return ("auto", None, None, floor)
+    if curve.startswith('iso'):
+        try:
+            iso = int(curve[3:])
+            a, b = dpc_iso_curve(iso, bit_depth)
+        except ValueError:
+            raise SystemExit("%s %s: the families are %s" % (flag, curve, ', '.join('iso%d' % k for k in DPC_ISO_CURVES)))
+        return ("iso%d" % iso, a, b, floor)
+    f = curve.split(',')
+    try:
+        if len(f) not in (2, 3):
+            raise ValueError(curve)
+        a, b = float(f[0]), float(f[1])
+        floor = float(f[2]) if len(f) == 3 else 1.0
+    except ValueError:
+        raise SystemExit("%s takes a,b[,floor], auto, iso3200 or iso12800, got %r" % (flag, curve))
+    if not abs(a) < float("inf") or not abs(b) < float("inf"):
+        raise SystemExit("%s: a and b must be finite, got %r" % (flag, curve))
+    if not (floor > 0 and floor < float("inf")):
+        raise SystemExit("%s: the floor must be > 0, got %r" % (flag, floor))
+    return ("a,b", a, b, floor)
+
+
 def add_rows_arguments(p) -> None:
     """the three flags of the row-noise correction, beside --dpc; `rows_arguments` reads them"""
     p.add_argument('--row_noise', type=float, default=None, help='take row noise (banding) out of every frame on the device: the gate K in '
@@ -132,35 +169,8 @@ def rows_arguments(row_noise, curve, max_dn, dpc, bit_depth):
     max_dn = top / 64.0 if max_dn is None else float(max_dn)
     if not (max_dn > 0 and max_dn < float("inf")):
         raise SystemExit("--row_noise_max is the largest offset taken out in DN, > 0, got %r" % max_dn)
-    floor = 1.0
-    if curve is None:
-        if dpc is None:
-            raise SystemExit("--row_noise needs the sensor's noise curve: --row_noise_curve a,b[,floor] (var = a * m - b in DN of the frames), "
-                             "--row_noise_curve auto (estimated from the footage), --row_noise_curve iso3200 / iso12800 (a checkpoint "
-                             "family's curve, rescaled to --bit_depth) -- or the curve of --dpc, which then serves")
-        return (float(row_noise), "dpc", dpc[2], dpc[3], dpc[4], max_dn)
-    if curve == 'auto':
-        return (float(row_noise), "auto", None, None, floor, max_dn)
-    if curve.startswith('iso'):
-        try:
-            iso = int(curve[3:])
-            a, b = dpc_iso_curve(iso, bit_depth)
-        except ValueError:
-            raise SystemExit("--row_noise_curve %s: the families are %s" % (curve, ', '.join('iso%d' % k for k in DPC_ISO_CURVES)))
-        return (float(row_noise), "iso%d" % iso, a, b, floor, max_dn)
-    f = curve.split(',')
-    try:
-        if len(f) not in (2, 3):
-            raise ValueError(curve)
-        a, b = float(f[0]), float(f[1])
-        floor = float(f[2]) if len(f) == 3 else 1.0
-    except ValueError:
-        raise SystemExit("--row_noise_curve takes a,b[,floor], auto, iso3200 or iso12800, got %r" % curve)
-    if not abs(a) < float("inf") or not abs(b) < float("inf"):
-        raise SystemExit("--row_noise_curve: a and b must be finite, got %r" % curve)
-    if not (floor > 0 and floor < float("inf")):
-        raise SystemExit("--row_noise_curve: the floor must be > 0, got %r" % floor)
-    return (float(row_noise), "a,b", a, b, floor, max_dn)
+    source, a, b, floor = curve_argument('--row_noise_curve', curve, dpc, bit_depth)
+    return (float(row_noise), source, a, b, floor, max_dn)
 
 
 def rows_line(acc, frames, spec, bit_depth, ww, key):
@@ -211,36 +221,7 @@ def cols_arguments(col_noise, curve, frames, gate, sigma, max_dn, dpc, bit_depth
     max_dn = float((1 << int(bit_depth)) - 1) / 64.0 if max_dn is None else float(max_dn)      # a guess, as for the rows
     if not (max_dn > 0 and max_dn < inf):
         raise SystemExit("--col_noise_max is the largest offset taken out in DN, > 0, got %r" % max_dn)
-    head = ("auto", frames, gate, sigma, max_dn)
-    floor = 1.0
-    if curve is None:
-        if dpc is None:
-            raise SystemExit("--col_noise auto needs the sensor's noise curve: --col_noise_curve a,b[,floor] (var = a * m - b in DN of the frames), "
-                             "--col_noise_curve auto (estimated from the footage), --col_noise_curve iso3200 / iso12800 (a checkpoint "
-                             "family's curve, rescaled to --bit_depth) -- or the curve of --dpc, which then serves")
-        return head + ("dpc", dpc[2], dpc[3], dpc[4])
-    if curve == 'auto':
-        return head + ("auto", None, None, floor)
-    if curve.startswith('iso'):
-        try:
-            iso = int(curve[3:])
-            a, b = dpc_iso_curve(iso, bit_depth)
-        except ValueError:
-            raise SystemExit("--col_noise_curve %s: the families are %s" % (curve, ', '.join('iso%d' % k for k in DPC_ISO_CURVES)))
-        return head + ("iso%d" % iso, a, b, floor)
-    f = curve.split(',')
-    try:
-        if len(f) not in (2, 3):
-            raise ValueError(curve)
-        a, b = float(f[0]), float(f[1])
-        floor = float(f[2]) if len(f) == 3 else 1.0
-    except ValueError:
-        raise SystemExit("--col_noise_curve takes a,b[,floor], auto, iso3200 or iso12800, got %r" % curve)
-    if not abs(a) < inf or not abs(b) < inf:
-        raise SystemExit("--col_noise_curve: a and b must be finite, got %r" % curve)
-    if not (floor > 0 and floor < inf):
-        raise SystemExit("--col_noise_curve: the floor must be > 0, got %r" % floor)
-    return head + ("a,b", a, b, floor)
+    return ("auto", frames, gate, sigma, max_dn) + curve_argument('--col_noise_curve', curve, dpc, bit_depth)
 
 
 def add_report_arguments(p) -> None:

@@ -1,13 +1,16 @@
 """The column-noise rule of include/rvdd.h (rvdd_cols_estimate, rvdd_cols_fit, rvdd_cols_apply) restated in NumPy float32, every
-operation rounded on its own, and the inputs the host and GPU tests share.  estimate() / fit() / apply() are vectorised;
-estimate_slow() / fit_slow() / apply_slow() say the same with plain loops and np.float32 scalars (tests/test_cols_host.py holds the two
-together word for word).  The transpose of tests/rows_ref.py."""
+operation rounded on its own, and the inputs the host and GPU tests share: tests/line_ref.py along the columns, plus what the columns
+alone have -- the strips of the estimate kernel, the fit over the frames and the map's file order.  estimate() / fit() / apply() are
+vectorised; estimate_slow() / fit_slow() / apply_slow() say the same with plain loops and np.float32 scalars (tests/test_cols_host.py
+holds the two together word for word)."""
 import numpy as np
 
-f32 = np.float32
-DCS = (-4, -3, -2, -1, 1, 2, 3, 4)
+import line_ref as L
+from line_ref import CLASSES, cfg, classes, dn, f32, gray_of, neighbour, norm_dn, packed_of, top_of      # noqa: F401 -- the tests read them here
+
+DCS = L.OFFS
 MAX_HH = 4096
-SKIPPED, APPLIED = 0, 1
+SKIPPED, APPLIED = L.SKIPPED, L.APPLIED
 UNSUPPORTED, FIT_APPLIED, FIT_CLAMPED, INSIGNIFICANT = 0, 1, 2, 3
 VAR_MEDIAN = f32(3.4528)                # (1.4826 * 1.2533)^2: the variance of a median in units of MAD^2
 SE_MEDIAN = f32(1.2533) * f32(1.4826)   # the standard error of a median in units of MAD / sqrt(n)
@@ -18,40 +21,10 @@ STRIPS = ((32, 639), (16, 1279), (8, 2559), (4, MAX_HH))
 SHAPES = ([(1, 1, 5), (1, 3, 8), (2, 37, 53)] + [(1, 8, cb + e) for cb, _ in STRIPS for e in (-1, 0, 1) if cb + e >= 5]
           + [(1, hh + e, cb + 1) for cb, hh in STRIPS[:-1] for e in (0, 1)] + [(1, MAX_HH, 5), (1, 8, 640)])
 SHAPES = sorted(set(SHAPES))
-CLASSES = {"applied", "skipped", "half", "half_minus_one", "even", "odd", "zero", "empty"}
 
 
 def strip_of(hh):
     return next(cb for cb, last in STRIPS if hh <= last)
-
-
-def cfg(k_gate, noise_a, noise_b, var_floor=1.0):
-    """the fields of struct rvdd_cols_cfg, as f32"""
-    return tuple(f32(v) for v in (k_gate, noise_a, noise_b, var_floor))
-
-
-def top_of(bits):
-    return f32((1 << bits) - 1)
-
-
-def dn(v, top):
-    return ((v + f32(1.0)) * f32(0.5)) * top
-
-
-def norm_dn(d, top):
-    return f32(2.0) * (d / top) - f32(1.0)
-
-
-def neighbour(c, dc, ww):
-    """the plane column of the horizontal neighbour dc of column c: mirrored about the site, then (fewer than nine columns) about the edge"""
-    q = c + dc
-    if q < 0 or q >= ww:
-        q = c - dc
-    if q < 0:
-        q = -q
-    if q >= ww:
-        q = 2 * (ww - 1) - q
-    return q
 
 
 def mosaic_of(cmap):
@@ -66,36 +39,16 @@ def map_of(line):
 
 def deviations(packed, bits, c):
     """-> (d, used): every sample's d = x - median of its eight horizontal neighbours, and whether the gate takes it"""
-    k_gate, a, b, floor = c
-    top = top_of(bits)
     n, _, hh, ww = packed.shape
     assert packed.dtype == np.float32 and 1 <= hh <= MAX_HH and ww >= 5
-    x = dn(packed, top)
-    nb = np.stack([x[:, :, :, [neighbour(col, dc, ww) for col in range(ww)]] for dc in DCS])
-    s = np.sort(nb, axis=0)
-    m = (s[3] + s[4]) * f32(0.5)
-    d = x - m
-    var = np.maximum(a * m - b, floor)
-    used = d * d <= (k_gate * k_gate) * var
-    return d, used
+    return L.deviations(packed, bits, c, L.COLS)
 
 
 def estimate(packed, bits, c):
     """-> {"offsets": f32 [n,2,ww], "state": u8 [n,2,ww], "cnt": the used samples [n,2,ww]}"""
     n, _, hh, ww = packed.shape
-    d, used = deviations(packed, bits, c)
-    offsets = np.zeros((n, 2, ww), np.float32)
-    state = np.zeros((n, 2, ww), np.uint8)
-    cnts = np.zeros((n, 2, ww), np.int64)
-    for i in range(n):
-        for j in range(2):
-            for col in range(ww):
-                v = np.sort(np.concatenate([d[i, j, :, col][used[i, j, :, col]], d[i, j + 2, :, col][used[i, j + 2, :, col]]]))
-                cnt = cnts[i, j, col] = v.size
-                if cnt > 0 and cnt >= hh:
-                    offsets[i, j, col] = (v[(cnt - 1) // 2] + v[cnt // 2]) * f32(0.5)
-                    state[i, j, col] = APPLIED
-    return {"offsets": offsets, "state": state, "cnt": cnts}
+    assert packed.dtype == np.float32 and 1 <= hh <= MAX_HH and ww >= 5
+    return L.estimate(packed, bits, c, L.COLS)
 
 
 def fit(offsets, state, min_frames, k_sig, max_dn):
@@ -132,56 +85,14 @@ def fit(offsets, state, min_frames, k_sig, max_dn):
     return {"map": cmap, "mstate": mstate, "stats": stats}
 
 
-def gray_of(packed, bits):
-    """the gray plane the ingest leaves beside packed frames"""
-    x = dn(packed, top_of(bits))
-    return (((x[:, 0] + x[:, 1]) + x[:, 2]) + x[:, 3]) * f32(0.25)
-
-
 def apply(packed, gray, cmap, bits):
     """-> (packed, gray) with the map [2,ww] taken out: copies; gray may be None"""
-    top = top_of(bits)
-    out = packed.copy()
-    g = None if gray is None else gray.copy()
-    o = cmap[[0, 1, 0, 1]][None, :, None, :]                              # [1,4,1,ww]: plane k has map[k & 1]
-    dd = dn(packed, top) - o
-    hit = np.broadcast_to(o != 0, packed.shape)
-    out[hit] = norm_dn(dd, top)[hit]
-    if g is not None:
-        cols = np.broadcast_to((cmap != 0).any(axis=0)[None, None, :], g.shape)
-        new = (((dd[:, 0] + dd[:, 1]) + dd[:, 2]) + dd[:, 3]) * f32(0.25)
-        g[cols] = new[cols]
-    return out, g
+    return L.apply(packed, gray, L.spread(cmap, L.COLS), bits)
 
 
 # ---- the same, slowly ---------------------------------------------------------------------------------------------------------------
 def estimate_slow(packed, bits, c):
-    k_gate, a, b, floor = c
-    top = top_of(bits)
-    n, _, hh, ww = packed.shape
-    k2 = f32(k_gate * k_gate)
-    offsets = np.zeros((n, 2, ww), np.float32)
-    state = np.zeros((n, 2, ww), np.uint8)
-    cnts = np.zeros((n, 2, ww), np.int64)
-    for i in range(n):
-        for j in range(2):
-            for col in range(ww):
-                ds = []
-                for k in (j, j + 2):
-                    for r in range(hh):
-                        x = f32(f32(f32(packed[i, k, r, col] + f32(1.0)) * f32(0.5)) * top)
-                        nb = sorted(f32(f32(f32(packed[i, k, r, neighbour(col, dc, ww)] + f32(1.0)) * f32(0.5)) * top) for dc in DCS)
-                        m = f32(f32(nb[3] + nb[4]) * f32(0.5))
-                        d = f32(x - m)
-                        var = max(f32(f32(a * m) - b), floor)
-                        if f32(d * d) <= f32(k2 * var):
-                            ds.append(d)
-                ds.sort()
-                cnt = cnts[i, j, col] = len(ds)
-                if cnt > 0 and cnt >= hh:
-                    offsets[i, j, col] = f32(f32(ds[(cnt - 1) // 2] + ds[cnt // 2]) * f32(0.5))
-                    state[i, j, col] = APPLIED
-    return {"offsets": offsets, "state": state, "cnt": cnts}
+    return L.estimate_slow(packed, bits, c, L.COLS)
 
 
 def fit_slow(offsets, state, min_frames, k_sig, max_dn):
@@ -219,92 +130,28 @@ def fit_slow(offsets, state, min_frames, k_sig, max_dn):
 
 
 def apply_slow(packed, gray, cmap, bits):
-    top = top_of(bits)
-    n, _, hh, ww = packed.shape
-    out, g = packed.copy(), gray.copy()
-    for i in range(n):
-        for col in range(ww):
-            if cmap[0, col] == 0 and cmap[1, col] == 0:
-                continue
-            for r in range(hh):
-                total = None
-                for k in range(4):
-                    o = cmap[k & 1, col]
-                    d = f32(f32(f32(f32(packed[i, k, r, col] + f32(1.0)) * f32(0.5)) * top) - o)
-                    total = d if total is None else f32(total + d)
-                    if o != 0:
-                        out[i, k, r, col] = f32(f32(f32(2.0) * f32(d / top)) - f32(1.0))
-                g[i, r, col] = f32(total * f32(0.25))
-    return out, g
-
-
-# ---- what fired ---------------------------------------------------------------------------------------------------------------------
-def classes(est, hh):
-    """the classes of CLASSES that an estimate holds"""
-    o, st, cnt = est["offsets"], est["state"], est["cnt"]
-    got = set()
-    got |= {"applied"} if (st != SKIPPED).any() else set()
-    got |= {"skipped"} if (st == SKIPPED).any() else set()
-    got |= {"half"} if ((cnt == hh) & (st != SKIPPED)).any() else set()
-    got |= {"half_minus_one"} if ((cnt == hh - 1) & (st == SKIPPED)).any() else set()
-    got |= {"even"} if ((st != SKIPPED) & (cnt % 2 == 0)).any() else set()
-    got |= {"odd"} if ((st != SKIPPED) & (cnt % 2 == 1)).any() else set()
-    got |= {"zero"} if ((st == APPLIED) & (o == 0)).any() else set()
-    got |= {"empty"} if (cnt == 0).any() else set()
-    return got
+    return L.apply_slow(packed, gray, L.spread(cmap, L.COLS), bits)
 
 
 # ---- inputs -------------------------------------------------------------------------------------------------------------------------
-def packed_of(dnv, bits):
-    """whole DN [n,4,hh,ww] -> the packed planes the ingest writes"""
-    return norm_dn(np.clip(np.rint(dnv), 0, (1 << bits) - 1).astype(np.float32), top_of(bits)).astype(np.float32)
-
-
 def scene(n, hh, ww, seed, level=800.0, swing=600.0):
     """a smooth scene in DN, [n,4,hh,ww]: planes 0, 2 and 0.8 of them + 50 in planes 1, 3, moving a little from frame to frame"""
-    y, x = np.mgrid[0:hh, 0:ww].astype(np.float64)
-    out = np.empty((n, 4, hh, ww))
-    for i in range(n):
-        base = level + swing * np.sin((y + 3 * i + seed) / 37.0) * np.cos(x / 23.0) + 2.0 * x
-        out[i, 0] = out[i, 2] = base
-        out[i, 1] = out[i, 3] = 0.8 * base + 50.0
-    return out
+    return L.scene(n, hh, ww, seed, L.COLS, level, swing)
 
 
 def with_cols(clean, sigma, sigma_col, rng):
     """clean DN + white noise + one static Gaussian offset per (parity, column) -> (DN, the offsets [2,ww])"""
-    n, _, hh, ww = clean.shape
-    cols = rng.normal(0.0, 1.0, (2, ww)) * sigma_col
-    return clean + rng.normal(0.0, sigma, clean.shape) + cols[[0, 1, 0, 1]][None, :, None, :], cols
+    return L.with_lines(clean, sigma, sigma_col, rng, L.COLS)
 
 
 def crafted(n, hh, ww):
-    """A constant 12-bit frame (every d = 0) with columns made by hand under a constant curve of variance 100 and a gate of 3
-    (|d| <= 30): a column of parity 0 whose plane-0 half lies far outside the gate (exactly hh used: applied), a column of parity 1
-    with one sample more outside (hh - 1 used: skipped).  The columns lie as far apart as ww lets them; in a narrow plane they meet
-    in each other's windows and some classes fall away (the tests ask for the union over the shapes)."""
-    v = np.full((n, 4, hh, ww), 1000.0)
-    i = n - 1
-    v[i, 0, :, 1] = 1500.0                                                 # parity 0, column 1: plane 0 out, plane 2 in
-    v[i, 1, :, ww - 2] = 1500.0                                            # parity 1, column ww - 2: plane 1 out ...
-    v[i, 3, 0, ww - 2] = 400.0                                             # ... and one sample of plane 3
-    return v
+    """line_ref.crafted's columns: column 1 of parity 0 applied on exactly hh used, column ww - 2 of parity 1 skipped on hh - 1"""
+    return L.crafted(n, hh, ww, L.COLS)
 
 
 def cases(shape):
     """The inputs of one shape: [(name, packed f32 [n,4,hh,ww], bit depth, cfg)] -- tests/rows_ref.py's five, transposed."""
-    n, hh, ww = shape
-    rng = np.random.default_rng(1000 * n + 10 * hh + ww)
-    noisy, _ = with_cols(scene(n, hh, ww, seed=hh), 30.0, 10.0, rng)
-    out = [("scene12", packed_of(noisy, 12), 12, cfg(3.0, 1.0, -100.0, 1.0))]
-    low, _ = with_cols(scene(n, hh, ww, seed=1, level=7.0, swing=3.0) * [[[[1.0]], [[1.25]], [[1.0]], [[1.25]]]] - 2.0, 0.8, 0.7, rng)
-    out.append(("bits4", packed_of(low, 4), 4, cfg(3.0, 0.0, -1.0, 0.25)))
-    out.append(("constant", packed_of(np.full((n, 4, hh, ww), 517.0), 12), 12, cfg(3.0, 8.0, 2043.5, 1.0)))
-    step = scene(n, hh, ww, seed=5) + rng.normal(0.0, 30.0, (n, 4, hh, ww))
-    step[:, :, :, ww // 2:] += 1500.0
-    out.append(("step", packed_of(step, 12), 12, cfg(3.0, 0.0, -900.0, 1.0)))
-    out.append(("crafted", packed_of(crafted(n, hh, ww), 12), 12, cfg(3.0, 0.0, -100.0, 1.0)))
-    return out
+    return L.cases(shape, L.COLS)
 
 
 def fit_cfg_for(bits, frames):
