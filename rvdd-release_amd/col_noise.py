@@ -4,7 +4,7 @@
 
 Every mosaic column has its own amplifier or ADC offset, and it does not change from frame to frame: vertical stripes that stay put
 while the scene moves under them.  The command reads the tree `denoise` reads (`--dataset_mode rawvideo`), takes --col_noise_frames
-frames SPREAD EVENLY over the videos of ONE frame size (up to 16 videos; `dpc_map.spread_indices`: pooling needs the scene to change),
+frames SPREAD EVENLY over the videos of ONE frame size (up to 16 videos; `footage.spread_indices`: pooling needs the scene to change),
 ingests them on the device as `noise.estimate` does, estimates one offset per frame and mosaic column (`rvdd_cols_estimate`: the
 median, over the column's two colour planes, of every sample's difference to the median of its eight horizontal same-colour
 neighbours, samples outside the gate of K standard deviations left out), copies the [F,2,ww] estimates back once and pools them on the
@@ -33,9 +33,8 @@ import numpy as np
 import torch
 
 from . import tiffio
-from .dpc_map import MAX_VIDEOS, spread_indices
-from .footage import add_cols_arguments, cols_arguments, estimate_noise, ingest_frames, open_rawvideo
-from .runtime import cols_cfg, cols_fit
+from .footage import MAX_VIDEOS, add_cols_arguments, cols_arguments, estimate_noise, open_rawvideo, sampled_frames
+from .runtime import cols_fit
 
 
 def mosaic_of(cmap):
@@ -59,26 +58,9 @@ def estimate(rt, dataset, bit_depth: int, cfg, frames: int = 32, max_videos: int
     (ceil(frames / videos) of each, `spread_indices`, `frames` in all), ingested on `rt`'s device as `video_push` ingests them; cfg =
     `cols_cfg(...)`.  -> (offsets float32 [F,2,ww], state uint8 [F,2,ww]) on the host, copied back ONCE.  RuntimeError where the
     videos differ in frame size."""
-    videos = dataset.videos[:max_videos]
-    if not videos:
-        raise RuntimeError("no video to read")
-    per = -(-int(frames) // len(videos))
-    outs, states, size, left = [], [], None, int(frames)
-    for key, paths in videos:
-        if left <= 0:
-            break
-        paths = [paths[i] for i in spread_indices(len(paths), min(per, left))]
-        H, W = dataset.frame_size(paths[0])
-        if size is not None and (H, W) != size:
-            raise RuntimeError("a column map is one sensor's: video %r has frames of %d x %d, the videos before it %d x %d" % (key, W, H, size[1], size[0]))
-        size = (H, W)
-        for p in paths:                               # one frame per call: the estimates do not depend on the split, the memory does
-            packed, _ = ingest_frames(rt, dataset, dataset.read_frame(p)[None], bit_depth, want_gray=False)
-            o, s = rt.cols_estimate(packed, cfg, int(bit_depth))
-            outs.append(o)
-            states.append(s)
-            left -= 1
-    return torch.cat(outs).cpu().numpy(), torch.cat(states).cpu().numpy()
+    found = [rt.cols_estimate(packed, cfg, int(bit_depth))
+             for packed in sampled_frames(rt, dataset, bit_depth, frames, "a column map", in_all=True, max_videos=max_videos)]
+    return torch.cat([o for o, _ in found]).cpu().numpy(), torch.cat([s for _, s in found]).cpu().numpy()
 
 
 def report(offsets, state, k_sig: float, max_dn: float, min_frames=None):
@@ -143,13 +125,12 @@ def main(argv=None) -> dict:
                           int(opt.bit_depth))
     dataset = open_rawvideo(opt, rest, "col_noise")
     dev = torch.device("cuda", opt.gpu_ids[0] if opt.gpu_ids else 0)
-    _, frames, gate, sigma, max_dn, _, a, b, floor = spec
-    if a is None:
-        a, b = estimate_noise(dataset, dev, int(opt.bit_depth), 4, '--col_noise_curve')
+    if spec.needs_curve:
+        spec = spec.with_curve(*estimate_noise(dataset, dev, int(opt.bit_depth), 4, '--col_noise_curve'))
     rt = ops_runtime(dev.index or 0)
     try:
-        offsets, state = estimate(rt, dataset, int(opt.bit_depth), cols_cfg(gate, a, b, floor), frames)
-        cmap, r = report(offsets, state, sigma, max_dn)
+        offsets, state = estimate(rt, dataset, int(opt.bit_depth), spec.cfg(), spec.frames)
+        cmap, r = report(offsets, state, spec.k_sig, spec.max_dn)
     except RuntimeError as err:
         raise SystemExit(str(err))
     write_map(own.out, cmap)

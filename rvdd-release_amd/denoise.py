@@ -147,16 +147,21 @@ import argparse
 import json
 import os
 import time
-from typing import List, Sequence, Tuple
+from typing import List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
 from . import tiffio
-from .footage import (add_cols_arguments, add_dpc_arguments, add_report_arguments, add_rows_arguments, cols_arguments, dpc_arguments,
-                      estimate_noise, open_rawvideo, report_arguments, report_record, rows_arguments, rows_line, to_device)
-from .runtime import BAYER_PATTERNS, BITS_DEPTHS, DPC_ISO_CURVES, bits_row_bytes, dpc_cfg, match_coeffs, resid_add, rows_cfg
+from .footage import (FileSpec, add_cols_arguments, add_dpc_arguments, add_report_arguments, add_rows_arguments, cols_arguments,
+                      dpc_arguments, estimate_noise, match_arguments, open_rawvideo, report_arguments, report_record, rows_arguments,
+                      rows_line, to_device)
+from .runtime import BAYER_PATTERNS, BITS_DEPTHS, bits_row_bytes, match_coeffs, resid_add
+
+# --dpc_map auto and --cuts auto, kind "auto"; their FILE forms are a FileSpec, kind "file"
+DpcMapAuto = NamedTuple("DpcMapAuto", [("kind", str), ("frames", int), ("share", float), ("tolerate", int)])
+CutsAuto = NamedTuple("CutsAuto", [("kind", str), ("t_hist", float), ("t_grid", float), ("min_len", int)])
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
 # --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
@@ -203,8 +208,8 @@ def deal_slots(lengths: Sequence[int], slots: int, tail: int = 0) -> List[List[T
 
 
 def dpc_map_arguments(dpc_map, frames, share, tolerate, static_only, have_dpc):
-    """--dpc_map / --dpc_map_frames / --dpc_map_share / --dpc_map_tolerate / --dpc_static_only -> None (no --dpc_map), ("file", path)
-    or ("auto", frames, share, tolerate); `have_dpc`: --dpc K was given.  SystemExit where the flags do not fit together."""
+    """--dpc_map / --dpc_map_frames / --dpc_map_share / --dpc_map_tolerate / --dpc_static_only -> None (no --dpc_map), a FileSpec or a
+    DpcMapAuto; `have_dpc`: --dpc K was given.  SystemExit where the flags do not fit together."""
     from .dpc_map import check_detect_flags
     given = [n for n, v in (("dpc_map_frames", frames), ("dpc_map_share", share), ("dpc_map_tolerate", tolerate)) if v is not None]
     if dpc_map is None:
@@ -216,13 +221,13 @@ def dpc_map_arguments(dpc_map, frames, share, tolerate, static_only, have_dpc):
             raise SystemExit("--%s belongs to --dpc_map auto: --dpc_map %s reads a map that is already made" % (given[0], dpc_map))
         if static_only:
             raise SystemExit("--dpc_static_only belongs to --dpc_map auto: with --dpc_map FILE leave --dpc away to keep the dynamic stage off")
-        return ("file", dpc_map)
+        return FileSpec("file", dpc_map)
     if not have_dpc:
         raise SystemExit("--dpc_map auto needs --dpc K with --dpc_iso ISO or --dpc_noise a,b / auto: the rule whose persistence is counted "
                          "(--dpc_static_only keeps the dynamic stage itself off)")
     frames, share, tolerate = 16 if frames is None else frames, 0.5 if share is None else share, 0 if tolerate is None else tolerate
     check_detect_flags(frames, share, tolerate, "--dpc_map_")
-    return ("auto", int(frames), float(share), int(tolerate))
+    return DpcMapAuto("auto", int(frames), float(share), int(tolerate))
 
 
 def find_dpc_map(dataset, dev, opt):
@@ -230,44 +235,18 @@ def find_dpc_map(dataset, dev, opt):
     log.  auto: `dpc_map.detect` on the run's own videos with the rule of --dpc, before any push."""
     from . import dpc_map as M
     from .util._ops import ops_runtime
+    spec = opt.dpc_map
     try:
-        if opt.dpc_map[0] == "file":
-            mask = M.read_map(opt.dpc_map[1])
-            print(M.summary_line(mask, opt.dpc_map[1]))
+        if spec.kind == "file":
+            mask = M.read_map(spec.path)
+            print(M.summary_line(mask, spec.path))
             return mask
-        _, frames, share, tolerate = opt.dpc_map
-        hits, read = M.detect(ops_runtime(dev.index or 0), dataset, int(opt.bit_depth), dpc_cfg(*opt.dpc), frames, tolerate)
-        mask, _ = M.report(hits, read, share, tolerate)
+        hits, read = M.detect(ops_runtime(dev.index or 0), dataset, int(opt.bit_depth), opt.dpc.cfg(), spec.frames, spec.tolerate)
+        mask, _ = M.report(hits, read, spec.share, spec.tolerate)
     except (RuntimeError, tiffio.TiffError, OSError) as err:
-        raise SystemExit("--dpc_map %s: %s" % (opt.dpc_map[0] if opt.dpc_map[0] == "auto" else opt.dpc_map[1], err))
+        raise SystemExit("--dpc_map %s: %s" % ("auto" if spec.kind == "auto" else spec.path, err))
     print(M.summary_line(mask, '%d frames' % read))
     return mask
-
-
-def match_arguments(match_noise, match_iso):
-    """--match_noise / --match_iso -> None (neither) or (a, b, iso), a and b Python doubles in DN of --bit_depth -- None with
-    --match_noise auto, for `main` to estimate from the footage; SystemExit where the flags do not fit together."""
-    if match_noise is None and match_iso is None:
-        return None
-    isos = ', '.join(str(k) for k in DPC_ISO_CURVES)
-    if match_iso is None:
-        raise SystemExit("--match_noise needs --match_iso {%s}: the checkpoint family whose curve the footage is mapped onto" % isos)
-    if match_noise is None:
-        raise SystemExit("--match_iso belongs to --match_noise a,b or --match_noise auto")
-    if match_iso not in DPC_ISO_CURVES:
-        raise SystemExit("--match_iso must be one of %s, got %r" % (isos, match_iso))
-    if match_noise == 'auto':
-        return (None, None, match_iso)
-    f = match_noise.split(',')
-    if len(f) != 2:
-        raise SystemExit("--match_noise takes a,b or auto, got %r" % match_noise)
-    try:
-        a, b = float(f[0]), float(f[1])
-    except ValueError:
-        raise SystemExit("--match_noise takes numbers a,b or auto, got %r" % match_noise)
-    if not (0 < a < float("inf")) or not abs(b) < float("inf"):
-        raise SystemExit("--match_noise: a must be finite and > 0 and b finite, got %r" % match_noise)
-    return (a, b, match_iso)
 
 
 def match_report(a, b, bit_depth, iso):
@@ -286,7 +265,7 @@ def match_report(a, b, bit_depth, iso):
 
 
 def cuts_arguments(cuts, own, future):
-    """--cuts / --cut_hist / --cut_grid / --cut_min_len -> None (no --cuts), ("auto", t_hist, t_grid, min_len) or ("file", path);
+    """--cuts / --cut_hist / --cut_grid / --cut_min_len -> None (no --cuts), a CutsAuto or a FileSpec;
     SystemExit where the flags do not fit together.  min_len is at least 2 + future: a shot that yields a frame."""
     from . import cuts as C
     given = [f for f in ("cut_hist", "cut_grid", "cut_min_len") if getattr(own, f) is not None]
@@ -295,10 +274,10 @@ def cuts_arguments(cuts, own, future):
             raise SystemExit("--cut_hist, --cut_grid and --cut_min_len belong to --cuts auto")
         return None
     if cuts == "auto":
-        return ("auto",) + C.thresholds(own, 2 + int(future))
+        return CutsAuto("auto", *C.thresholds(own, 2 + int(future)))
     if given:
         raise SystemExit("--%s belongs to --cuts auto: --cuts %s reads cuts that are already decided" % (given[0], cuts))
-    return ("file", cuts)
+    return FileSpec("file", cuts)
 
 
 def read_cuts_file(path):
@@ -352,18 +331,17 @@ def find_cols_map(dataset, dev, opt):
     """--col_noise: the run's column map float32 [2,ww] in DN of --bit_depth, its `cols:` line sent to the log.  auto:
     `col_noise.estimate` on the run's own videos and the fit (`col_noise.report`), before any push."""
     from . import col_noise as M
-    from .runtime import cols_cfg
     from .util._ops import ops_runtime
+    spec = opt.cols
     try:
-        if opt.cols[0] == "file":
-            cmap = M.read_map(opt.cols[1])
-            print(M.file_line(cmap, opt.cols[1]))
+        if spec.kind == "file":
+            cmap = M.read_map(spec.path)
+            print(M.file_line(cmap, spec.path))
             return cmap
-        _, frames, gate, sigma, max_dn, _, a, b, floor = opt.cols
-        offsets, state = M.estimate(ops_runtime(dev.index or 0), dataset, int(opt.bit_depth), cols_cfg(gate, a, b, floor), frames)
-        cmap, r = M.report(offsets, state, sigma, max_dn)
+        offsets, state = M.estimate(ops_runtime(dev.index or 0), dataset, int(opt.bit_depth), spec.cfg(), spec.frames)
+        cmap, r = M.report(offsets, state, spec.k_sig, spec.max_dn)
     except (RuntimeError, tiffio.TiffError, OSError) as err:
-        raise SystemExit("--col_noise %s: %s" % (opt.cols[0] if opt.cols[0] == "auto" else opt.cols[1], err))
+        raise SystemExit("--col_noise %s: %s" % ("auto" if spec.kind == "auto" else spec.path, err))
     print(M.summary_line(r, '%d frames' % r["frames"]))
     return cmap
 
@@ -371,17 +349,17 @@ def find_cols_map(dataset, dev, opt):
 def find_shots(dataset, dev, opt):
     """--cuts: the run's videos as their shots (`split_shots`), one `cuts: <key>: N frames, shots at [0, k1, ...]` line per video sent to
     the log.  auto: `cuts.detect` on the run's own videos, before any push."""
-    if opt.cuts[0] == "auto":
+    spec = opt.cuts
+    if spec.kind == "auto":
         from . import cuts as C
         from .util._ops import ops_runtime
-        _, t_hist, t_grid, min_len = opt.cuts
         t0 = time.time()
-        found = C.detect(ops_runtime(dev.index or 0), dataset, dataset.videos, int(opt.bit_depth), t_hist, t_grid, min_len)
+        found = C.detect(ops_runtime(dev.index or 0), dataset, dataset.videos, int(opt.bit_depth), spec.t_hist, spec.t_grid, spec.min_len)
         by_key = {key: cuts for key, _, cuts, _ in found}
         print('cuts: measured %d frames in %.3f s (--cuts FILE with the lines of python -m rvdd_release_amd.cuts saves the pass)'
               % (sum(n for _, n, _, _ in found), time.time() - t0))
     else:
-        by_key = read_cuts_file(opt.cuts[1])
+        by_key = read_cuts_file(spec.path)
     shots = split_shots(dataset.videos, by_key)
     for key, frames in dataset.videos:
         print('cuts: %s: %d frames, shots at [%s]' % (key, len(frames), ', '.join(str(k) for k in [0] + sorted(set(by_key.get(key, ()))))))
@@ -434,6 +412,7 @@ def _parse(argv):
     opt.match = match_arguments(own.match_noise, own.match_iso)
     opt.report = report_arguments(own.report, own.report_noise, opt.match, int(opt.bit_depth))
     opt.cuts = cuts_arguments(own.cuts, own, opt.future_patch_depth)
+    opt.cols_map = None                           # the column map of --col_noise: `prepasses` leaves it here
     if opt.raw_container is not None:
         if opt.raw_container != 'mipi':
             raise SystemExit("--raw_container %r: headerless frames are 'mipi' (packed TIFFs are recognised by themselves)" % opt.raw_container)
@@ -452,37 +431,36 @@ def _parse(argv):
 
 
 def prepasses(opt, dataset, dev):
-    """What is decided on the run's own footage before any push, in this order: the noise curve of --dpc_noise auto / --match_noise auto
-    (ONE estimate for both, for --row_noise_curve auto, --col_noise_curve auto and for --report_noise auto), the defect map, the column map, the match coefficients, the shots.  Completes opt.dpc, opt.match
-    opt.rows, opt.cols and opt.report, leaves the column map of --col_noise in opt.cols_map; -> (dmap: the cellmask
-    or None, match: struct rvdd_match_cfg or None, shots [(key, [paths])])."""
-    curve = None
-    if opt.dpc is not None and opt.dpc[2] is None:
-        curve = estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames)
-        opt.dpc = opt.dpc[:2] + curve + opt.dpc[4:]
-    rows = getattr(opt, "rows", None)
-    if rows is not None and rows[2] is None:      # auto, or the curve of --dpc_noise auto: the one estimate
-        curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--row_noise_curve')
-        opt.rows = rows[:2] + curve + rows[4:]
-    cols = getattr(opt, "cols", None)
-    if cols is not None and cols[0] == "auto" and cols[6] is None:      # auto, or the curve of --dpc_noise auto: the one estimate
-        curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--col_noise_curve')
-        opt.cols = cols[:6] + curve + cols[8:]
+    """What is decided on the run's own footage before any push, in this order: the noise curve of the stages on `auto` (ONE estimate
+    for --dpc_noise, --row_noise_curve, --col_noise_curve, --match_noise and --report_noise, made for the first that asks), the defect
+    map, the column map, the match coefficients, the shots.  Completes the records opt.dpc, opt.rows, opt.cols, opt.match and
+    opt.report, leaves the column map of --col_noise in opt.cols_map; -> (dmap: the cellmask or None, match: struct rvdd_match_cfg or
+    None, shots [(key, [paths])])."""
+    found = []
+
+    def auto(flag):
+        """the run's ONE estimate: whoever asks first is named where the fit refuses"""
+        if not found:
+            found.append(estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, flag))
+        return found[0]
+
+    for stage, flag in (("dpc", '--dpc_noise'), ("rows", '--row_noise_curve'), ("cols", '--col_noise_curve')):
+        spec = getattr(opt, stage)
+        if getattr(spec, "needs_curve", False):     # auto, or the curve of --dpc_noise auto; a stage that is off, or reads a FILE, has none
+            setattr(opt, stage, spec.with_curve(*auto(flag)))
     # --dpc_map: ONE map for the run, read or found before any push; --dpc_static_only: --dpc has named the rule and is done
     dmap = None if opt.dpc_map is None else find_dpc_map(dataset, dev, opt)
     # --col_noise: ONE column map for the run, read or found before any push
-    opt.cols_map = None if cols is None else find_cols_map(dataset, dev, opt)
+    opt.cols_map = None if opt.cols is None else find_cols_map(dataset, dev, opt)
     if opt.dpc_static_only:
         opt.dpc = None
     match = None
     if opt.match is not None:
-        if opt.match[0] is None:
-            curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--match_noise')
-            opt.match = curve + opt.match[2:]
-        match = match_report(opt.match[0], opt.match[1], int(opt.bit_depth), opt.match[2])
-    if opt.report is not None and opt.report[2] is None:
-        curve = curve or estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, '--report_noise')
-        opt.report = opt.report[:2] + curve + opt.report[4:]
+        if opt.match.needs_curve:
+            opt.match = opt.match.with_curve(*auto('--match_noise'))
+        match = match_report(opt.match.a, opt.match.b, int(opt.bit_depth), opt.match.iso)
+    if opt.report is not None and opt.report.needs_curve:
+        opt.report = opt.report.with_curve(*auto('--report_noise'))
     # --cuts: every shot is a video of its own from here on, under its video's key
     shots = dataset.videos if opt.cuts is None else find_shots(dataset, dev, opt)
     return dmap, match, shots
@@ -508,6 +486,11 @@ def write_frame(opt, rt, out_b, host_b, key, path, W):
         iio_write(png[0].cpu().numpy(), os.path.join(opt.results_dir, key, stem + '_srgb.png'))
 
 
+def shot_name(key, first):
+    """what the `dpc:` and `rows:` lines call a video, or the shot of it that starts with the frame `first`"""
+    return key if first is None else '%s from %s' % (key, first)
+
+
 def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -> int:
     """The videos [(key, [paths])] of one frame size H x W through one runtime: its options and stages set, the videos dealt to the
     slots (`deal_slots`), every step pushed, its valid outputs taken to the host in one egress and written (`write_frame`), and the
@@ -525,23 +508,21 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
     rt.set_option("stream_reset_each", int(model.training_unrollings == 1))
     rt.set_option("stream_flow_from_denoised", int(bool(getattr(opt, "val_flow_from_denoised", False))))
     rt.set_option("stream_all_frames", int(opt.all_frames))
-    rt.set_dpc(None if opt.dpc is None else dpc_cfg(*opt.dpc))
+    rt.set_dpc(None if opt.dpc is None else opt.dpc.cfg())
     if dmap is not None and dmap.shape != (H // 2, W // 2):
         raise SystemExit("--dpc_map: the map is one of a %d x %d mosaic, video %r has frames of %d x %d (one camera per run)"
                          % (2 * dmap.shape[1], 2 * dmap.shape[0], videos[0][0], W, H))
     if dmap is not None:
         rt.set_dpc_map(dmap)
-    cmap = getattr(opt, "cols_map", None)
+    cmap, rows, report = opt.cols_map, opt.rows, opt.report
     if cmap is not None and cmap.shape[1] != W // 2:
         raise SystemExit("--col_noise: the map is one of %d mosaic columns, video %r has frames of %d x %d (one camera per run)"
                          % (2 * cmap.shape[1], videos[0][0], W, H))
     if cmap is not None:
         rt.set_cols(cmap)
-    rows = getattr(opt, "rows", None)
     if rows is not None:
-        rt.set_rows(rows_cfg(rows[0], *rows[2:]))
+        rt.set_rows(rows.cfg())
     rt.set_match(match)
-    report = getattr(opt, "report", None)
     if report is not None:
         rt.set_resid(True)
     measured = [0] * B                          # outputs of the slot's video the stage has measured
@@ -577,8 +558,8 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
             last = k == len(frames) - (0 if opt.all_frames and fut else 1)      # the step that ends the video
             ended = ended or last
             dpc_frames[b] = min(k + 1, len(frames))
-            if last:                                # --cuts: several shots share a key; the line names the shot's first frame
-                ends.append((b, key if opt.cuts is None else '%s from %s' % (key, os.path.basename(frames[0]))))
+            if last:                                # --cuts: several shots share a key; the lines name the shot's first frame
+                ends.append((b, key, None if opt.cuts is None else os.path.basename(frames[0])))
             if valid[b]:
                 measured[b] += 1
                 write_frame(opt, rt, out[b:b + 1], host[b], key, frames[k - fut], W)      # the centre frame
@@ -587,17 +568,17 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
             rt.set_option("tvl1_async", 0)          # synchronises: reports a TV-L1 exchange of this video's pushes that gave up
             if opt.dpc is not None:                 # ... and before the slot's next FIRST push: the difference is this video's
                 now = rt.dpc_counts()
-                for b, key in ends:
+                for b, key, first in ends:
                     print('dpc: %d hot, %d dead samples corrected in %d frames (%s)'
-                          % (now[b][0] - dpc_seen[b][0], now[b][1] - dpc_seen[b][1], dpc_frames[b], key))
+                          % (now[b][0] - dpc_seen[b][0], now[b][1] - dpc_seen[b][1], dpc_frames[b], shot_name(key, first)))
                     dpc_seen[b] = now[b]
             if rows is not None:                    # the slot's counts are this video's frames: read, which zeroes them
-                for b, key in ends:
-                    print(rows_line(rt.rows_read(b), dpc_frames[b], rows, int(opt.bit_depth), W // 2, key))
+                for b, key, first in ends:
+                    print(rows_line(rt.rows_read(b), dpc_frames[b], rows, int(opt.bit_depth), W // 2, shot_name(key, first)))
             if report is not None:                  # the slot's accumulator holds this video's outputs: read, which zeroes it
-                for b, key in ends:
+                for b, key, first in ends:
                     acc = rt.resid_read(b)
-                    names = {"video": key} if opt.cuts is None else {"video": key.split(' from ')[0], "from": key.split(' from ')[1]}
+                    names = {"video": key} if first is None else {"video": key, "from": first}
                     report_out["file"].write(json.dumps(report_record(acc, measured[b], report, **names)) + '\n')
                     report_out["total"] = acc if report_out["total"] is None else resid_add(report_out["total"], acc)
                     report_out["frames"] += measured[b]
@@ -624,12 +605,9 @@ def main(argv=None) -> dict:
         groups.setdefault(dataset.frame_size(frames[0]), []).append((key, frames))
     written = 0
     t0 = time.time()
-    report_out = None if opt.report is None else {"file": open(opt.report[0], "w"), "total": None, "frames": 0}
+    report_out = None if opt.report is None else {"file": open(opt.report.path, "w"), "total": None, "frames": 0}
     for (H, W), videos in groups.items():
-        if report_out is None:
-            written += run_group(opt, model, dataset, videos, H, W, dmap, match)
-        else:
-            written += run_group(opt, model, dataset, videos, H, W, dmap, match, report_out)
+        written += run_group(opt, model, dataset, videos, H, W, dmap, match, report_out)
     torch.cuda.synchronize(model.device)
     dt = time.time() - t0
     if report_out is not None:

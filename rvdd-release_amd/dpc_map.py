@@ -26,44 +26,24 @@ none.  The rule is tested on synthetic frames only; NOTHING is 
 from __future__ import annotations
 
 import argparse
-import math
 
 import numpy as np
 import torch
 
 from . import tiffio
-from .footage import add_dpc_arguments, dpc_arguments, estimate_noise, ingest_frames, open_rawvideo
-from .runtime import dpc_cfg, dpc_detect_cfg, dpc_map_from_hits, dpc_map_from_mosaic, dpc_map_stats, dpc_map_to_mosaic
-
-MAX_VIDEOS = 16
-
-
-def spread_indices(n: int, k: int):
-    """min(k, n) frame indices spread evenly over a video of n frames: round(i (n - 1) / (k - 1)), halves up; ascending, no repeats"""
-    k = max(1, min(int(k), int(n)))
-    if k == 1:
-        return [0]
-    return sorted({int(math.floor(i * (n - 1) / (k - 1) + 0.5)) for i in range(k)})
-
+from .footage import MAX_VIDEOS, add_dpc_arguments, dpc_arguments, estimate_noise, open_rawvideo, sampled_frames
+from .footage import spread_indices  # noqa: F401 -- lives in footage.py with the sampler; kept under this name too
+from .runtime import dpc_detect_cfg, dpc_map_from_hits, dpc_map_from_mosaic, dpc_map_stats, dpc_map_to_mosaic
 
 def detect(rt, dataset, bit_depth: int, rule, frames: int = 16, tolerate: int = 0, max_videos: int = MAX_VIDEOS):
     """The persistence counts (a device tensor [4,hh,ww], `RvddRuntime.dpc_detect`) of `frames` frames spread over each of the first
     `max_videos` videos of a rawvideo dataset, ingested on `rt`'s device as `video_push` ingests them; rule = `dpc_cfg(...)`.
     -> (hits, frames read).  RuntimeError where the videos differ in frame size.  Nothing is synchronised."""
     cfg = dpc_detect_cfg(rule, tolerate)
-    hits, read, size = None, 0, None
-    for key, paths in dataset.videos[:max_videos]:
-        paths = [paths[i] for i in spread_indices(len(paths), frames)]
-        H, W = dataset.frame_size(paths[0])
-        if size is not None and (H, W) != size:
-            raise RuntimeError("a defect map is one sensor's: video %r has frames of %d x %d, the videos before it %d x %d" % (key, W, H, size[1], size[0]))
-        size = (H, W)
-        for p in paths:                               # one frame per call: the totals do not depend on the split, the memory does
-            packed, _ = ingest_frames(rt, dataset, dataset.read_frame(p)[None], bit_depth, want_gray=False)
-            hits = rt.dpc_detect(packed, cfg, int(bit_depth), hits)
-            read += 1
-    if hits is None:
-        raise RuntimeError("no video to read")
+    hits, read = None, 0
+    for packed in sampled_frames(rt, dataset, bit_depth, frames, "a defect map", max_videos=max_videos):
+        hits = rt.dpc_detect(packed, cfg, int(bit_depth), hits)
+        read += 1
     return hits, read
 
 
@@ -133,11 +113,11 @@ def main(argv=None) -> dict:
     rule = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth), own.dpc_noise_frames)
     dataset = open_rawvideo(opt, rest, "dpc_map")
     dev = torch.device("cuda", opt.gpu_ids[0] if opt.gpu_ids else 0)
-    if rule[2] is None:
-        rule = rule[:2] + estimate_noise(dataset, dev, int(opt.bit_depth), 4 if own.dpc_noise_frames is None else own.dpc_noise_frames) + rule[4:]
+    if rule.needs_curve:
+        rule = rule.with_curve(*estimate_noise(dataset, dev, int(opt.bit_depth), own.dpc_noise_frames or 4))
     rt = ops_runtime(dev.index or 0)
     try:
-        hits, read = detect(rt, dataset, int(opt.bit_depth), dpc_cfg(*rule), own.frames, own.tolerate)
+        hits, read = detect(rt, dataset, int(opt.bit_depth), rule.cfg(), own.frames, own.tolerate)
         mask, r = report(hits, read, own.share, own.tolerate)
     except RuntimeError as err:
         raise SystemExit(str(err))

@@ -35,10 +35,8 @@ import argparse
 import numpy as np
 import torch
 
-from .footage import ingest_frames, open_rawvideo
+from .footage import MAX_VIDEOS, ingest_frames, open_rawvideo
 from .runtime import DPC_ISO_CURVES, NOISE_ACC_BYTES, match_coeffs, nearest_iso, noise_acc_arrays, noise_fit
-
-MAX_VIDEOS = 16
 
 
 def estimate(rt, dataset, bit_depth: int, frames: int = 4, max_videos: int = MAX_VIDEOS):

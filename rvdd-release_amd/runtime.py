@@ -110,18 +110,38 @@ def dpc_map_from_mosaic(plane):
     return m
 
 
+def _host_call(name: str, *args) -> None:
+    """One of the library's host-only entry points (no handle, no GPU needed); RuntimeError with its message where it refuses"""
+    lib = _lib.load()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+
+
+def _host_bytes(x, struct, message: str, n: Optional[int] = None):
+    """The bytes of whole structs (n: of exactly n) as a flat uint8 array on the host: x is a struct instance, a tensor (a device tensor is
+    copied, which synchronises), an array or bytes.  RuntimeError(`message`, got <bytes>) for any other size."""
+    import numpy as np
+    if torch.is_tensor(x):
+        raw = x.detach().cpu().contiguous().view(torch.uint8).numpy()
+    elif isinstance(x, np.ndarray):
+        raw = np.ascontiguousarray(x).view(np.uint8)
+    else:
+        raw = np.frombuffer(bytes(x), np.uint8)
+    if raw.size % C.sizeof(struct) or (n is not None and raw.size != n * C.sizeof(struct)):
+        raise RuntimeError(f"{message}, got {raw.size}")
+    return raw.reshape(-1)
+
+
 def dpc_map_stats(cellmask) -> Dict[str, int]:
     """{"samples", "cells", "unfixable"} of a map uint8 [hh,ww] (rvdd_dpc_map_stats: on the host, no GPU needed): its defective
     samples and cells, and the samples no ring of which has a good site -- `dpc_map_apply` leaves those as they are."""
     import numpy as np
-    lib = _lib.load()
     m = np.ascontiguousarray(cellmask)
     if m.ndim != 2 or m.dtype != np.uint8:
         raise RuntimeError(f"dpc_map_stats: cellmask is uint8 [hh,ww], got {m.dtype} {m.shape}")
     out = (C.c_int64 * 3)()
-    rc = lib.rvdd_dpc_map_stats(m.ctypes.data, m.shape[0], m.shape[1], out)
-    if rc != 0:
-        raise RuntimeError(f"rvdd_dpc_map_stats failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    _host_call("rvdd_dpc_map_stats", m.ctypes.data, m.shape[0], m.shape[1], out)
     return {"samples": int(out[0]), "cells": int(out[1]), "unfixable": int(out[2])}
 
 
@@ -132,10 +152,7 @@ def noise_acc_arrays(acc):
     """struct rvdd_noise_acc as numpy arrays (copies on the host): {"hist": int64 [64,512], "msum": int64 [64], "counters": int64 [4]}
     of an accumulator `RvddRuntime.noise_hist` returned (any tensor or array of its 131616 bytes)."""
     import numpy as np
-    raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy() if torch.is_tensor(acc) else np.frombuffer(bytes(acc), np.uint8)
-    if raw.size != NOISE_ACC_BYTES:
-        raise RuntimeError(f"a noise accumulator is {NOISE_ACC_BYTES} bytes (struct rvdd_noise_acc), got {raw.size}")
-    raw = raw.tobytes()
+    raw = _host_bytes(acc, _lib.RvddNoiseAcc, f"a noise accumulator is {NOISE_ACC_BYTES} bytes (struct rvdd_noise_acc)", 1)
     return {"hist": np.frombuffer(raw, np.uint32, 64 * 512).reshape(64, 512).astype(np.int64),
             "msum": np.frombuffer(raw, np.uint64, 64, 64 * 512 * 4).astype(np.int64),
             "counters": np.frombuffer(raw, np.uint64, 4, 64 * 512 * 4 + 64 * 8).astype(np.int64)}
@@ -146,18 +163,10 @@ def noise_fit(acc, bit_depth: int) -> Dict[str, float]:
     the host, no GPU needed; a device tensor is copied, which synchronises).  acc: the tensor, or any array / bytes of struct
     rvdd_noise_acc.  -> {"a", "b", "bins", "blocks", "m_min", "m_max", "rms"}; RuntimeError with the library's message where the
     fit refuses (fewer than 4 usable mean bins, or too little tonal range)."""
-    lib = _lib.load()
-    if isinstance(acc, _lib.RvddNoiseAcc):
-        host = acc
-    else:
-        raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes() if torch.is_tensor(acc) else bytes(acc)
-        if len(raw) != NOISE_ACC_BYTES:
-            raise RuntimeError(f"noise_fit: an accumulator is {NOISE_ACC_BYTES} bytes (struct rvdd_noise_acc), got {len(raw)}")
-        host = _lib.RvddNoiseAcc.from_buffer_copy(raw)
+    host = _lib.RvddNoiseAcc.from_buffer_copy(
+        _host_bytes(acc, _lib.RvddNoiseAcc, f"noise_fit: an accumulator is {NOISE_ACC_BYTES} bytes (struct rvdd_noise_acc)", 1))
     out = _lib.RvddNoiseCurve()
-    rc = lib.rvdd_noise_fit(C.byref(host), int(bit_depth), C.byref(out))
-    if rc != 0:
-        raise RuntimeError(f"rvdd_noise_fit failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    _host_call("rvdd_noise_fit", C.byref(host), int(bit_depth), C.byref(out))
     return {"a": out.a, "b": out.b, "bins": int(out.bins), "blocks": int(out.blocks), "m_min": out.m_min, "m_max": out.m_max,
             "rms": out.rms}
 
@@ -167,15 +176,7 @@ FRAME_SIG_BYTES = C.sizeof(_lib.RvddFrameSig)      # struct rvdd_frame_sig: u32 
 
 def _frame_sig_bytes(sig, what: str):
     """the bytes of n whole structs rvdd_frame_sig as a C-contiguous uint8 array [n,6144] on the host (a device tensor is copied)"""
-    import numpy as np
-    if torch.is_tensor(sig):
-        raw = sig.detach().cpu().contiguous().view(torch.uint8).numpy()
-    elif isinstance(sig, np.ndarray):
-        raw = np.ascontiguousarray(sig).view(np.uint8)
-    else:
-        raw = np.frombuffer(bytes(sig), np.uint8)
-    if raw.size % FRAME_SIG_BYTES:
-        raise RuntimeError(f"{what}: a frame signature is {FRAME_SIG_BYTES} bytes (struct rvdd_frame_sig), got {raw.size}")
+    raw = _host_bytes(sig, _lib.RvddFrameSig, f"{what}: a frame signature is {FRAME_SIG_BYTES} bytes (struct rvdd_frame_sig)")
     return raw.reshape(-1, FRAME_SIG_BYTES)
 
 
@@ -192,7 +193,6 @@ def cut_score(a, b, hh: int, ww: int) -> Tuple[float, float]:
     """(d_hist, d_grid) of two frames of hh x ww cells from their signatures (rvdd_cut_score: on the host, no GPU needed).  a, b: one
     struct rvdd_frame_sig each -- a row of the tensor `RvddRuntime.frame_sigs` returned (a device tensor is copied, which
     synchronises), an array or bytes of its 6144 bytes.  RuntimeError with the library's message for signatures of another frame size."""
-    lib = _lib.load()
     host = []
     for s, name in ((a, "a"), (b, "b")):
         raw = _frame_sig_bytes(s, "cut_score")
@@ -200,9 +200,7 @@ def cut_score(a, b, hh: int, ww: int) -> Tuple[float, float]:
             raise RuntimeError(f"cut_score: {name} is ONE signature of {FRAME_SIG_BYTES} bytes, got {raw.shape[0]}")
         host.append(_lib.RvddFrameSig.from_buffer_copy(raw.tobytes()))
     out = (C.c_double * 2)()
-    rc = lib.rvdd_cut_score(C.byref(host[0]), C.byref(host[1]), int(hh), int(ww), out)
-    if rc != 0:
-        raise RuntimeError(f"rvdd_cut_score failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    _host_call("rvdd_cut_score", C.byref(host[0]), C.byref(host[1]), int(hh), int(ww), out)
     return float(out[0]), float(out[1])
 
 
@@ -218,29 +216,17 @@ def _resid_struct(acc, what: str) -> "_lib.RvddResidAcc":
     if isinstance(acc, _lib.RvddResidAcc):
         return acc
     if isinstance(acc, dict):
-        raw = b"".join(np.ascontiguousarray(np.asarray(acc[name]).astype(np.int64 if name in ("s1", "s11") else np.uint64)).tobytes()
+        acc = b"".join(np.ascontiguousarray(np.asarray(acc[name]).astype(np.int64 if name in ("s1", "s11") else np.uint64)).tobytes()
                        for name in RESID_FIELDS)
-    elif torch.is_tensor(acc):
-        raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()
-    else:
-        raw = np.ascontiguousarray(acc).tobytes() if isinstance(acc, np.ndarray) else bytes(acc)
-    if len(raw) != RESID_ACC_BYTES:
-        raise RuntimeError(f"{what}: an accumulator is {RESID_ACC_BYTES} bytes (struct rvdd_resid_acc), got {len(raw)}")
-    return _lib.RvddResidAcc.from_buffer_copy(raw)
+    return _lib.RvddResidAcc.from_buffer_copy(
+        _host_bytes(acc, _lib.RvddResidAcc, f"{what}: an accumulator is {RESID_ACC_BYTES} bytes (struct rvdd_resid_acc)", 1))
 
 
 def resid_acc_arrays(acc):
     """Accumulators of `RvddRuntime.resid_stats` / `resid_read` (a tensor [n,384] of 64-bit words, one struct, or any array / bytes of n
     structs rvdd_resid_acc) as NumPy arrays on the host: {"n", "msum", "s2", "n11": uint64 [n,64]; "s1", "s11": int64 [n,64]}."""
     import numpy as np
-    if isinstance(acc, _lib.RvddResidAcc):
-        raw = np.frombuffer(bytes(acc), np.uint8)
-    elif torch.is_tensor(acc):
-        raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy().reshape(-1)
-    else:
-        raw = np.ascontiguousarray(acc).view(np.uint8).reshape(-1) if isinstance(acc, np.ndarray) else np.frombuffer(bytes(acc), np.uint8)
-    if raw.size % RESID_ACC_BYTES:
-        raise RuntimeError(f"resid_acc_arrays: an accumulator is {RESID_ACC_BYTES} bytes (struct rvdd_resid_acc), got {raw.size}")
+    raw = _host_bytes(acc, _lib.RvddResidAcc, f"resid_acc_arrays: an accumulator is {RESID_ACC_BYTES} bytes (struct rvdd_resid_acc)")
     words = raw.view(np.uint64).reshape(-1, 6, 64)
     return {name: (words[:, k].view(np.int64) if name in ("s1", "s11") else words[:, k]).copy() for k, name in enumerate(RESID_FIELDS)}
 
@@ -254,12 +240,9 @@ def resid_fit(acc, bit_depth: int, a: float, b: float) -> Dict[str, float]:
     """ONE accumulator judged against the curve var(m) = a * m - b in DN of `bit_depth` (rvdd_resid_fit: on the host, no GPU needed).
     acc: as `_resid_struct` takes it; a dict of [1,64] or [64] arrays is one accumulator.  -> {"ratio", "ratio_lo", "ratio_hi", "bias",
     "rho", "a_fit", "b_fit", "samples", "bins"}; RuntimeError with the library's message where fewer than 4 level bins are usable."""
-    lib = _lib.load()
     host = _resid_struct(acc, "resid_fit")
     out = _lib.RvddResidReport()
-    rc = lib.rvdd_resid_fit(C.byref(host), int(bit_depth), float(a), float(b), C.byref(out))
-    if rc != 0:
-        raise RuntimeError(f"rvdd_resid_fit failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    _host_call("rvdd_resid_fit", C.byref(host), int(bit_depth), float(a), float(b), C.byref(out))
     return {name: (int if name in ("samples", "bins") else float)(getattr(out, name)) for name in RESID_REPORT_FIELDS}
 
 
@@ -278,14 +261,7 @@ def rows_acc_arrays(acc) -> Dict[str, "object"]:
     """Accumulators of `RvddRuntime.rows_estimate` (an int64 tensor [n,3] of 24-byte structs rvdd_rows_acc, one struct, or bytes) on
     the host: {"applied", "skipped", "clamped": uint32 [n]; "sum_q2": int64 [n]}."""
     import numpy as np
-    if isinstance(acc, _lib.RvddRowsAcc):
-        raw = np.frombuffer(bytes(acc), np.uint8)
-    elif torch.is_tensor(acc):
-        raw = acc.detach().cpu().contiguous().view(torch.uint8).numpy().reshape(-1)
-    else:
-        raw = np.ascontiguousarray(acc).view(np.uint8).reshape(-1) if isinstance(acc, np.ndarray) else np.frombuffer(bytes(acc), np.uint8)
-    if raw.size % ROWS_ACC_BYTES:
-        raise RuntimeError(f"rows_acc_arrays: an accumulator is {ROWS_ACC_BYTES} bytes (struct rvdd_rows_acc), got {raw.size}")
+    raw = _host_bytes(acc, _lib.RvddRowsAcc, f"rows_acc_arrays: an accumulator is {ROWS_ACC_BYTES} bytes (struct rvdd_rows_acc)")
     words = raw.view(np.uint32).reshape(-1, 6)
     return {"applied": words[:, 0].copy(), "skipped": words[:, 1].copy(), "clamped": words[:, 2].copy(),
             "sum_q2": np.ascontiguousarray(words[:, 4:6]).view(np.int64).reshape(-1).copy()}
@@ -328,7 +304,6 @@ def cols_fit(offsets, state, min_frames: int, k_sig: float = 3.0, max_dn: float 
     -> (map float32 [2,ww] in DN, mstate uint8 [2,ww]: 0 unsupported, 1 applied, 2 applied and clamped, 3 insignificant,
     stats {"unsupported", "applied", "clamped", "insignificant", "sum_q2": ints; "floor_dn": float})."""
     import numpy as np
-    lib = _lib.load()
     o = np.ascontiguousarray(offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else offsets)
     st = np.ascontiguousarray(state.detach().cpu().numpy() if torch.is_tensor(state) else state)
     if o.ndim != 3 or o.shape[1] != 2 or o.dtype != np.float32 or st.shape != o.shape or st.dtype != np.uint8:
@@ -338,9 +313,7 @@ def cols_fit(offsets, state, min_frames: int, k_sig: float = 3.0, max_dn: float 
     ms = np.zeros((2, ww), np.uint8)
     stats = _lib.RvddColsStats()
     cfg = _lib.RvddColsFitCfg(int(min_frames), float(k_sig), float(max_dn))
-    rc = lib.rvdd_cols_fit(o.ctypes.data, st.ctypes.data, F, ww, C.byref(cfg), m.ctypes.data, ms.ctypes.data, C.byref(stats))
-    if rc != 0:
-        raise RuntimeError(f"rvdd_cols_fit failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    _host_call("rvdd_cols_fit", o.ctypes.data, st.ctypes.data, F, ww, C.byref(cfg), m.ctypes.data, ms.ctypes.data, C.byref(stats))
     out = {name: int(stats.counts[i]) for i, name in enumerate(COLS_STATES)}
     out.update(sum_q2=int(stats.sum_q2), floor_dn=float(stats.floor_dn))
     return m, ms, out
@@ -373,7 +346,6 @@ def match_coeffs(a: float, b: float, bit_depth: int, iso_or_curve):
     curve itself as (a_ref, b_ref) in 12-bit DN.  -> (cfg, s, t): cfg the struct `match_raw` / `unmatch_rgb` / `set_match` take
     (v' = cfg.scale * v + cfg.offset on samples in [-1,1]), s and t the map x' = s * x + t in 12-bit DN.  s > 1 means footage cleaner
     than the checkpoint's curve: the map stretches it beyond the trained range."""
-    lib = _lib.load()
     if isinstance(iso_or_curve, (tuple, list)):
         if len(iso_or_curve) != 2:
             raise ValueError(f"match_coeffs: a curve is (a_ref, b_ref) in 12-bit DN, got {iso_or_curve!r}")
@@ -383,9 +355,7 @@ def match_coeffs(a: float, b: float, bit_depth: int, iso_or_curve):
     else:
         raise ValueError(f"match_coeffs: {iso_or_curve!r} is not one of {', '.join(str(k) for k in DPC_ISO_CURVES)} or a curve (a_ref, b_ref)")
     cfg, st = _lib.RvddMatchCfg(), (C.c_double * 2)()
-    rc = lib.rvdd_match_coeffs(float(a), float(b), int(bit_depth), a_ref, b_ref, C.byref(cfg), st)
-    if rc != 0:
-        raise RuntimeError(f"rvdd_match_coeffs failed ({rc}): {lib.rvdd_last_error(None).decode()}")
+    _host_call("rvdd_match_coeffs", float(a), float(b), int(bit_depth), a_ref, b_ref, C.byref(cfg), st)
     return cfg, float(st[0]), float(st[1])
 
 
