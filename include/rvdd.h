@@ -823,7 +823,8 @@ int rvdd_resid_read(rvdd_t* h, int32_t slot, rvdd_resid_acc* host_out /* HOST */
  * What it cannot do: the median of eight vertical neighbours is itself shifted by THEIR rows' offsets, so about 0.4 of the offsets'
  * amplitude stays behind as a slow vertical drift that cannot be told from scene shading -- a limit of any single-frame rule without
  * optically black columns.  Rows that a long horizontal edge crosses are skipped, or biased by less than the gate.
- * Column fixed-pattern noise is the rule below (rvdd_cols_estimate); offsets per plane and the use of the previous frame are out of scope.  Nothing is measured on real footage.
+ * Column fixed-pattern noise is the rule below (rvdd_cols_estimate), the gain between the two green planes the one after it
+ * (rvdd_green_estimate); other offsets per plane and the use of the previous frame are out of scope.  Nothing is measured on real footage.
  * On footage WITHOUT row noise the estimate has an rms of about 1.35 sqrt(var / (2 ww)) of its own, which the stage then adds.
  *
  * rvdd_rows_estimate writes offsets (DEVICE float [n,2,hh]) and state (DEVICE uint8 [n,2,hh]: 0 skipped, 1 applied, 2 applied and
@@ -909,8 +910,8 @@ int rvdd_rows_read(rvdd_t* h, int32_t slot, rvdd_rows_acc* host_out /* HOST */, 
  *     map[k & 1][c]; every other gray cell is not written.  A map of zeros leaves the tensors bit for bit.
  * What it cannot do: the neighbours carry offsets too, so the estimate is a high-pass of the pattern -- slow horizontal shading of the
  * pattern stays, as for the rows.  In a tripod shot of a static scene a vertical edge passes the significance test, because its spread
- * over time is only noise: estimate on footage that moves.  One camera setting per map.  Offsets per plane and per-column gains are
- * out of scope.  Nothing is measured on real footage.
+ * over time is only noise: estimate on footage that moves.  One camera setting per map.  The gain between the two green planes is the next rule
+ * (rvdd_green_estimate); other offsets per plane and per-column gains are out of scope.  Nothing is measured on real footage.
  *
  * rvdd_cols_estimate writes offsets (DEVICE float [n,2,ww]) and state (DEVICE uint8 [n,2,ww]: 0 skipped, 1 applied), every word.  One
  * workgroup per (frame, parity, strip of 32 / 16 / 8 / 4 neighbouring columns for hh <= 639 / 1279 / 2559 / 4096): the strip's keys lie
@@ -958,6 +959,112 @@ int rvdd_cols_apply(rvdd_t* h, float* packed /* [n,4,hh,ww], IN PLACE */, float*
  * no per-slot state and no read call.  With the stage off a push makes exactly the launches it made before and allocates nothing; a
  * map of zeros leaves the ring bit for bit what a push without the stage leaves. */
 int rvdd_set_cols(rvdd_t* h, const float* map_host /* [2,ww]; NULL = off, the default */, int32_t ww);
+
+/* ---- green imbalance ------------------------------------------------------------------ */
+
+/* The green sites of the red rows (Gr) and of the blue rows (Gb) see the same light through different neighbours, and pixel crosstalk
+ * makes their responses differ by up to a few per cent of the signal: a gain that varies slowly over the field with the ray angle
+ * and is static for one camera, lens and aperture.  Hamilton-Adams interpolates green at a red or blue site from two sites of either
+ * kind and picks the direction by gradients, so an imbalance below the noise becomes a maze pattern.  The gain is estimated per frame
+ * and block (rvdd_green_estimate), pooled over F frames on the host with a significance test (rvdd_green_fit) and taken out as a
+ * static map (rvdd_green_apply).  Every operation is rounded to f32 on its own (no fused multiply-add): e, level, states, the map and
+ * the corrected samples are reproducible bit for bit in NumPy f32 (tests/green_ref.py).
+ *   planes and geometry: packed [n,4,hh,ww], plane k = CFA position (k >> 1, k & 1).  Under GBRG / GRBG the greens are planes 0 and 3,
+ *     under RGGB / BGGR planes 1 and 2.  A = the green plane of CFA row 0, B = that of CFA row 1; dx = -1 where A sits in CFA column
+ *     0, +1 where it sits in column 1.  top, dn(v) and the way back are as for the rows.
+ *   per sample, two sides:
+ *     A-side: a cell (r, c) is an A-side sample iff the four B cells (r + {0, -1}, c + {0, dx}) lie in the plane -- the B sites
+ *       diagonally next to A(r, c) on the mosaic.  B-side: iff the four A cells (r + {0, +1}, c + {0, -dx}) lie in the plane.  Cells
+ *       that are not samples do not count anywhere.
+ *     x   = the sample's DN;  m = (s1 + s2) * 0.5, s1 / s2 the 2nd / 3rd of the four neighbours in ascending order;  d = x - m
+ *     var = fmaxf(noise_a * m - noise_b, var_floor);  the sample is USED iff d * d <= (k_gate * k_gate) * var.  The four neighbours are
+ *       symmetric about the site, so a planar scene gradient cancels in d.
+ *   per frame and block of RVDD_GREEN_BLOCK x RVDD_GREEN_BLOCK = 32 x 32 cells (gh = ceil(hh / 32), gw = ceil(ww / 32); the last
+ *   blocks are partial):
+ *     tot_A, tot_B = the block's samples of each side, cnt_A, cnt_B = the used ones.  The block is APPLIED (state 1) iff cnt_A > 0,
+ *       cnt_B > 0, 2 cnt_A >= tot_A and 2 cnt_B >= tot_B.  Then
+ *     e     = (med_A - med_B) * 0.5, med the exact median (v[(cnt - 1) / 2] + v[cnt / 2]) * 0.5 of the side's used d.  The scene's
+ *       curvature enters both sides with the same sign and cancels; the imbalance enters with opposite signs and stays.
+ *     level = (float)((double)S / (double)(cnt_A + cnt_B)), S the 64-bit integer sum of (int)rintf(m) over the used samples of both
+ *       sides.  Else the block is SKIPPED (state 0) with e = level = 0.
+ *   the fit over F frames (rvdd_green_fit, on the host, f32, in this order), per block:
+ *     v   = q = e / (level - black) of the frames with state 1 and level - black >= min_signal, ascending; nf of them.  Then exactly
+ *       rvdd_cols_fit's pooled step: nf < max(1, min_frames): map = 0, mstate 0.  o = the median, mad = the median of |v - o|.
+ *       o == 0, or (o * o) * (float)nf < (k_sig * k_sig) * (3.4528f * (mad * mad)): map = 0, mstate 3.  Else map = o clamped to
+ *       [-max_gain, +max_gain], mstate 1, or 2 if the clamp changed it.
+ *     stats: counts by mstate; sum_q2 with q = (int)rintf(16384 * map); floor = the mean over the supported blocks (mstate 1, 2, 3) of
+ *       ((1.2533f * 1.4826f) * mad) / sqrtf(nf), summed in f64 in block order; the FLAT estimate: the same pooled step (at least one
+ *       value) over the o of the supported blocks, in block order, in the frames' place: flat_gain, flat_se, flat_state.
+ *   apply (map [gh,gw] f32 gains of A relative to B -- the frame's own grid, or [1,1] for a flat gain --, in place, a pure stream), per
+ *   cell (r, c):
+ *     fy = ((float)r + 0.5f) * (1 / 32) - 0.5f clamped to [0, gh - 1];  y0 = (int)fy, y1 = min(y0 + 1, gh - 1), wy = fy - (float)y0;
+ *       likewise fx, x0, x1, wx from c and gw.
+ *     t = g[y0][x0] + wx * (g[y0][x1] - g[y0][x0]);  u likewise on row y1;  g = t + wy * (u - t);  h = 0.5f * g.
+ *     where g != 0: A's sample becomes x - h * (x - black), B's x + h * (x - black), packed again as 2 * (dn / top) - 1 with no clamp
+ *       to the range, and the gray cell (gray [n,hh,ww], nullable) is rewritten as (((d0 + d1) + d2) + d3) * 0.25 with the corrected
+ *       DN.  Where g == 0 the four samples keep their bits and the gray cell is not written.  The two planes that are not green are
+ *       never written.  A map of zeros leaves the tensors bit for bit.
+ * What it cannot do: the gate is centred on zero, so an imbalance of delta shrinks by about phi(k) / phi(0) of itself on the way in
+ * (a throw-away f64 prototype of this rule recovered 0.93 - 0.95 of an injected 1 - 5 %).  e is a MEDIAN of differences and level a MEAN:
+ * where the signal varies several-fold inside a block and is dark-heavy, the median lies below the mean and less comes back (0.63 -
+ * 0.72 on the synthetic sequences of DESIGN.md 4.22).  Texture finer than two cells aliases into
+ * d.  One camera, lens and aperture per map.  Nothing is measured on real footage.
+ *
+ * rvdd_green_estimate writes e, level (DEVICE float [n,gh,gw]) and state (DEVICE uint8 [n,gh,gw]: 0 skipped, 1 applied), every word,
+ * skipped blocks included, and only reads packed.  One workgroup per (frame, block): the block's two green planes go to LDS once with
+ * their one-cell halo, the two medians are exact (the digit-wise search of the rows and columns).  Inputs are assumed finite.
+ * RVDD_ERR_ARG (the message names the argument) and nothing launched: NULL cfg; k_gate or var_floor not > 0 or not finite; noise_a /
+ * noise_b / black not finite; bit_depth outside 1..16; pattern outside enum rvdd_bayer; hh < 2 or ww < 2; n < 0; NULL packed / e /
+ * level / state with n > 0; more than 2^31 - 1 blocks.  n = 0 does nothing.  Asynchronous and stream-ordered; nothing is read back.
+ * cfg.black is not read by the estimate: it travels with the rule to the fit and the apply.
+ * rvdd_green_fit needs no device and no handle (errors: rvdd_last_error(NULL)).  RVDD_ERR_ARG: a NULL pointer but stats; F, gh or gw
+ * < 1; black not finite; k_sig < 0 or not finite; max_gain or min_signal not > 0 or not finite.
+ * rvdd_green_apply takes map_dev (DEVICE [gh,gw]) out IN PLACE.  With ww % 4 == 0 and packed / gray 16-byte aligned a thread owns
+ * four neighbouring cells (16-byte loads and stores), every other case one cell.  Same bits either way.  RVDD_ERR_ARG as for the
+ * estimate's shape and pattern; NULL packed / map_dev with n > 0; black not finite; a grid (gh, gw) that is neither [1,1] nor the
+ * frame's own. */
+#define RVDD_GREEN_BLOCK 32
+typedef struct rvdd_green_cfg {
+    float k_gate;             /* the gate in standard deviations of the noise curve, around 3 */
+    float noise_a, noise_b;   /* var(m) = noise_a * m - noise_b, in DN of the frames' bit depth */
+    float var_floor;          /* the least variance assumed, > 0 */
+    float black;              /* the level without signal, in DN: noise_b / noise_a where the curve's variance is zero there */
+} rvdd_green_cfg;
+typedef struct rvdd_green_fit_cfg {
+    int32_t min_frames;       /* the least number of usable frames a block needs; below 1 counts as 1 */
+    float k_sig;              /* the significance threshold in standard errors of the pooled median, >= 0 */
+    float max_gain;           /* the largest gain taken out, > 0 (0.10 = 10 %) */
+    float min_signal;         /* the least level - black, in DN, at which a frame's block counts, > 0 */
+} rvdd_green_fit_cfg;
+typedef struct rvdd_green_stats {   /* 48 bytes */
+    uint32_t counts[4];       /* blocks by mstate: 0 unsupported, 1 applied, 2 applied and clamped, 3 insignificant */
+    int64_t sum_q2;           /* sum of q * q, q = (int)rintf(16384 * map): the map's rms gain is sqrt(sum_q2 / (gh gw)) / 16384 */
+    double floor;             /* the mean standard error of the pooled estimates, as a gain */
+    float flat_gain;          /* the flat estimate: the pooled median of the supported blocks' medians, clamped; 0 unless flat_state is 1 or 2 */
+    float flat_se;            /* its standard error */
+    int32_t flat_state;       /* its mstate */
+    int32_t reserved;         /* 0 */
+} rvdd_green_stats;
+int rvdd_green_estimate(rvdd_t* h, const float* packed /* [n,4,hh,ww] */, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth,
+                        int32_t pattern /* enum rvdd_bayer */, const rvdd_green_cfg* cfg, float* e /* DEVICE [n,gh,gw] */,
+                        float* level /* DEVICE [n,gh,gw] */, uint8_t* state /* DEVICE [n,gh,gw] */, void* stream);
+int rvdd_green_fit(const float* e_host /* [F,gh,gw] */, const float* level_host /* [F,gh,gw] */, const uint8_t* state_host /* [F,gh,gw] */,
+                   int32_t F, int32_t gh, int32_t gw, float black, const rvdd_green_fit_cfg* fit_cfg, float* map_host /* [gh,gw] */,
+                   uint8_t* mstate_host /* [gh,gw] */, rvdd_green_stats* stats_host /* nullable */);
+int rvdd_green_apply(rvdd_t* h, float* packed /* [n,4,hh,ww], IN PLACE */, float* gray /* [n,hh,ww], nullable, in place */,
+                     const float* map_dev /* DEVICE [gh,gw] */, int32_t gh, int32_t gw, float black, int32_t n, int32_t hh, int32_t ww,
+                     int32_t bit_depth, int32_t pattern /* enum rvdd_bayer */, void* stream);
+
+/* The map as a stage of rvdd_video_push: map_host [gh,gw] f32 gains (every value finite, gh and gw >= 1, black finite: else
+ * RVDD_ERR_ARG and nothing changes), NULL = off, the default.  Per handle; synchronises the device and copies the map, as
+ * rvdd_set_cols does (4 gh gw bytes, freed by the next call and with the handle).  With the stage on a push runs, for every run of
+ * slots that got a frame, ONE rvdd_green_apply on the ring's packed frames and gray planes IN PLACE under the handle's option
+ * "bayer_pattern", behind rvdd_set_dpc_map, rvdd_set_dpc, rvdd_set_cols and rvdd_set_rows -- readout offsets come off before a pixel
+ * gain is judged -- and in front of rvdd_set_match.  A push whose frames have another grid than a map that is not [1,1] is
+ * RVDD_ERR_ARG, as is one of frames with hh < 2 or ww < 2.  The map is static: no per-slot state and no read call.  With the stage off
+ * a push makes exactly the launches it made before and allocates nothing; a map of zeros leaves the ring bit for bit what a push
+ * without the stage leaves. */
+int rvdd_set_green(rvdd_t* h, const float* map_host /* [gh,gw]; NULL = off, the default */, int32_t gh, int32_t gw, float black);
 
 /* ---- raw datasets from sRGB video ------------------------------------------- */
 

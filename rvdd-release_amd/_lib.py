@@ -99,6 +99,22 @@ class RvddColsStats(C.Structure):
     _fields_ = [("counts", C.c_uint32 * 4), ("sum_q2", C.c_int64), ("floor_dn", C.c_double)]
 
 
+class RvddGreenCfg(C.Structure):
+    """struct rvdd_green_cfg (rvdd_green_estimate)"""
+    _fields_ = [("k_gate", C.c_float), ("noise_a", C.c_float), ("noise_b", C.c_float), ("var_floor", C.c_float), ("black", C.c_float)]
+
+
+class RvddGreenFitCfg(C.Structure):
+    """struct rvdd_green_fit_cfg (rvdd_green_fit)"""
+    _fields_ = [("min_frames", C.c_int32), ("k_sig", C.c_float), ("max_gain", C.c_float), ("min_signal", C.c_float)]
+
+
+class RvddGreenStats(C.Structure):
+    """struct rvdd_green_stats (rvdd_green_fit): 48 bytes"""
+    _fields_ = [("counts", C.c_uint32 * 4), ("sum_q2", C.c_int64), ("floor", C.c_double), ("flat_gain", C.c_float), ("flat_se", C.c_float),
+                ("flat_state", C.c_int32), ("reserved", C.c_int32)]
+
+
 # symbol -> (restype, argtypes); exactly the functions include/rvdd.h declares
 _P = C.c_void_p
 _PROTOS = {
@@ -160,6 +176,11 @@ _PROTOS = {
     "rvdd_cols_fit": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(RvddColsFitCfg), _P, _P, C.POINTER(RvddColsStats)]),
     "rvdd_cols_apply": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "rvdd_set_cols": (C.c_int, [_P, _P, C.c_int32]),
+    "rvdd_green_estimate": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RvddGreenCfg), _P, _P, _P, _P]),
+    "rvdd_green_fit": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(RvddGreenFitCfg), _P, _P,
+                                 C.POINTER(RvddGreenStats)]),
+    "rvdd_green_apply": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "rvdd_set_green": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float]),
     "rvdd_video_push": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvdd_unprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                  _P, _P, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P]),

@@ -357,6 +357,7 @@ void rvdd_destroy(rvdd_t* h) {
     if (h->dmap.mask) (void)hipFree(h->dmap.mask);
     if (h->dmap.cells) (void)hipFree(h->dmap.cells);
     if (h->cols.map) (void)hipFree(h->cols.map);
+    if (h->geq.map) (void)hipFree(h->geq.map);
     tvl1_free(h->tvl1);
     for (auto& p : h->pending) {
         (void)hipEventDestroy(p.e0);

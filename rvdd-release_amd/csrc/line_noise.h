@@ -16,7 +16,8 @@
 // 16 rounds.  The key of rank cnt / 2 (cnt even) is the same key where |{key <= P}| >= k + 2, else the least key above P: one more
 // round, a count and a minimum.  The offset is the midpoint of the two (line_midpoint).  A line with no used sample,
 // or with fewer than half of its samples used, is skipped.  How the counts of a line's keys are gathered -- registers or LDS, one
-// wave or four -- is the caller's: line_median takes it as two callables.
+// wave or four -- is the caller's: line_median takes it as two callables; line_group_count / line_group_above are the workgroup-wide
+// form with the keys in registers, which rows.hip and green.hip share.
 //
 // Apply.  A thread owns the four planes of NC cells of a cell row (NC = 4: ww % 4 == 0 and 16-byte aligned tensors, 16-byte loads and
 // stores; NC = 1 otherwise; the same arithmetic per sample, the same bits): line_load_cells / line_store_cells, and per cell
@@ -47,14 +48,19 @@ __device__ __forceinline__ unsigned line_key_of(float d) {
 
 __device__ __forceinline__ float line_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
+// the gate: a site of x DN whose neighbours' middle is m -> the key of d = x - m, or kLineNoKey where d lies outside k_gate standard
+// deviations of the noise curve at m (green.hip takes its four diagonal neighbours through here as well)
+__device__ __forceinline__ unsigned line_gate(float x, float m, const RowsParams& P) {
+    const float d = x - m;
+    const float var = fmaxf(P.a * m - P.b, P.floor);
+    return d * d <= P.k2 * var ? line_key_of(d) : kLineNoKey;
+}
+
 // nine DN across the lines in ascending distance, the site in the middle -> the key of the site's d, or kLineNoKey outside the gate
 __device__ __forceinline__ unsigned line_key(const float (&w)[9], const RowsParams& P) {
     float v[8] = {w[0], w[1], w[2], w[3], w[5], w[6], w[7], w[8]};
     sort8(v);
-    const float m = (v[3] + v[4]) * 0.5f;
-    const float d = w[4] - m;
-    const float var = fmaxf(P.a * m - P.b, P.floor);
-    return d * d <= P.k2 * var ? line_key_of(d) : kLineNoKey;
+    return line_gate(w[4], (v[3] + v[4]) * 0.5f, P);
 }
 
 // one key against NT <= 3 thresholds: |{key < t[0]}| in the low half of lo, t[1]'s in its high half, t[2]'s in hi
@@ -72,6 +78,33 @@ __device__ __forceinline__ void line_count_unpack(unsigned lo, unsigned hi, unsi
     out[0] = NT > 1 ? lo & 0xffffu : lo;
     if constexpr (NT > 1) out[1] = lo >> 16;
     if constexpr (NT > 2) out[2] = hi;
+}
+
+// |{key < t[n]}| over a workgroup of WAVES waves for NT <= 3 thresholds: every thread of the workgroup arrives, every thread gets the
+// counts.  A thread counts its own KPT keys -- the caller keeps a wave's count below 2^16, so that two counts share a register --, the
+// wave adds them up (DPP), lane 0 leaves them in LDS.  `words`: this round's LDS words [wave][2]; the caller alternates between two
+// sets, which makes one barrier a round enough
+template <int WAVES, int KPT, int NT>
+__device__ __forceinline__ void line_group_count(const unsigned (&key)[KPT], const unsigned (&t)[NT], unsigned (*words)[2], int lane, int wave,
+                                                 unsigned (&out)[NT]) {
+    static_assert(KPT <= 32, "two counts below 2^16 in one register");
+    unsigned lo = 0, hi = 0;
+#pragma unroll
+    for (int q = 0; q < KPT; ++q) line_count_add(key[q], t, lo, hi);
+    lo = wave_sum_u32(lo);
+    if constexpr (NT > 2) hi = wave_sum_u32(hi);
+    if (lane == 0) {
+        words[wave][0] = lo;
+        if constexpr (NT > 2) words[wave][1] = hi;
+    }
+    __syncthreads();
+    lo = hi = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        lo += words[w][0];
+        if constexpr (NT > 2) hi += words[w][1];
+    }
+    line_count_unpack(lo, hi, out);
 }
 
 struct LineMedian {
@@ -110,6 +143,32 @@ __device__ __forceinline__ LineMedian line_median(unsigned half, Count count, Ab
         if (a.le < k + 2) upper = a.above;                           // rank k + 1 lies above the key of rank k
     }
     return {false, prefix, upper};
+}
+
+// |{key <= P}| and the least key > P over the workgroup's keys, gathered as line_group_count gathers its counts
+template <int WAVES, int KPT>
+__device__ __forceinline__ LineAbove line_group_above(const unsigned (&key)[KPT], unsigned prefix, unsigned (*words)[2], int lane, int wave) {
+    unsigned le = 0, above = kLineNoKey;
+#pragma unroll
+    for (int q = 0; q < KPT; ++q) {
+        le += key[q] <= prefix ? 1u : 0u;
+        above = min(above, key[q] > prefix ? key[q] : kLineNoKey);
+    }
+    le = wave_sum_u32(le);
+    above = ~wave_max_u32(~above);                                   // the wave's minimum
+    if (lane == 0) {
+        words[wave][0] = le;
+        words[wave][1] = above;
+    }
+    __syncthreads();
+    le = 0;
+    above = kLineNoKey;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        le += words[w][0];
+        above = min(above, words[w][1]);
+    }
+    return LineAbove{le, above};
 }
 
 __device__ __forceinline__ float line_midpoint(const LineMedian& m) { return (line_unkey(m.prefix) + line_unkey(m.upper)) * 0.5f; }

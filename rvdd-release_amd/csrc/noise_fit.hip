@@ -1,4 +1,4 @@
-// rvdd_noise_fit, rvdd_resid_fit, rvdd_cut_score and rvdd_match_coeffs: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
+// rvdd_noise_fit, rvdd_resid_fit, rvdd_cols_fit, rvdd_green_fit, rvdd_cut_score and rvdd_match_coeffs: the noise curve var(m) = a m - b from a host copy of rvdd_noise_hist's accumulator (the rule is in include/rvdd.h).
 // Host code only, f64, no device and no handle; compiled -ffp-contract=off so that tests/noise_ref.py, which runs the same sums in
 // the same order in Python doubles, gets the same numbers.
 #include "runtime_internal.h"
@@ -31,6 +31,30 @@ double noise_quantile(const uint32_t* row, uint64_t count, double q) {
         cum += c;
     }
     return noise_edge(512);      // not reached: the counts add up to `count`
+}
+
+// The pooled step rvdd_cols_fit and rvdd_green_fit share (the rule is in include/rvdd.h): the median o of the nf values v, tested against
+// its own spread -- the median mad of |v - o| -- and clamped to +-limit.  f32, every operation rounded on its own, in the order written
+// there.  v is sorted in place, a is scratch.  state: 0 unsupported (nf < need: nothing else is formed), 3 insignificant, 1 applied, 2
+// applied and clamped; value: what the map gets; o: the median before the clamp; se: its standard error.  zero_is_nothing: a median of
+// exactly zero is insignificant whatever its spread (the green rule; the column rule applies it with a map of zero)
+struct Pooled {
+    int state;
+    float value, o, se;
+};
+Pooled pooled_median(std::vector<float>& v, std::vector<float>& a, int need, float k2, float limit, bool zero_is_nothing) {
+    const int nf = (int)v.size();
+    if (nf < need) return {0, 0.0f, 0.0f, 0.0f};
+    std::sort(v.begin(), v.end());
+    const float o = (v[(size_t)(nf - 1) / 2] + v[(size_t)nf / 2]) * 0.5f;
+    a.resize((size_t)nf);
+    for (int i = 0; i < nf; ++i) a[(size_t)i] = std::fabs(v[(size_t)i] - o);
+    std::sort(a.begin(), a.end());
+    const float mad = (a[(size_t)(nf - 1) / 2] + a[(size_t)nf / 2]) * 0.5f;
+    const float se = ((1.2533f * 1.4826f) * mad) / std::sqrt((float)nf);
+    if ((zero_is_nothing && o == 0.0f) || (o * o) * (float)nf < k2 * (3.4528f * (mad * mad))) return {3, 0.0f, o, se};
+    const float oc = std::fmin(std::fmax(o, -limit), limit);
+    return {oc != o ? 2 : 1, oc, o, se};
 }
 
 }  // namespace
@@ -208,35 +232,72 @@ extern "C" int rvdd_cols_fit(const float* offsets, const uint8_t* state, int32_t
         v.clear();
         for (int i = 0; i < F; ++i)
             if (state[(int64_t)i * 2 * ww + jc] == 1) v.push_back(offsets[(int64_t)i * 2 * ww + jc]);
-        const int nf = (int)v.size();
-        map[jc] = 0.0f;
-        if (nf < need) {
-            mstate[jc] = 0;
-            st.counts[0] += 1;
-            continue;
-        }
-        std::sort(v.begin(), v.end());
-        const float o = (v[(size_t)(nf - 1) / 2] + v[(size_t)nf / 2]) * 0.5f;
-        a.resize((size_t)nf);
-        for (int i = 0; i < nf; ++i) a[(size_t)i] = std::fabs(v[(size_t)i] - o);
-        std::sort(a.begin(), a.end());
-        const float mad = (a[(size_t)(nf - 1) / 2] + a[(size_t)nf / 2]) * 0.5f;
-        floor_sum += (double)(((1.2533f * 1.4826f) * mad) / std::sqrt((float)nf));
+        const Pooled p = pooled_median(v, a, need, k2, cfg->max_dn, false);
+        map[jc] = p.value;
+        mstate[jc] = (uint8_t)p.state;
+        st.counts[p.state] += 1;
+        if (p.state == 0) continue;
+        floor_sum += (double)p.se;
         ++supported;
-        if ((o * o) * (float)nf < k2 * (3.4528f * (mad * mad))) {
-            mstate[jc] = 3;
-            st.counts[3] += 1;
-            continue;
-        }
-        const float oc = std::fmin(std::fmax(o, -cfg->max_dn), cfg->max_dn);
-        const int s = oc != o ? 2 : 1;
-        map[jc] = oc;
-        mstate[jc] = (uint8_t)s;
-        st.counts[s] += 1;
-        const long long q = (long long)(int)std::rint(16.0f * oc);
+        if (p.state == 3) continue;
+        const long long q = (long long)(int)std::rint(16.0f * p.value);
         st.sum_q2 += q * q;
     }
     st.floor_dn = supported ? floor_sum / (double)supported : 0.0;
+    if (stats) *stats = st;
+    return RVDD_OK;
+}
+
+// rvdd_green_fit: the static map of green gains from host copies of rvdd_green_estimate's e, level and state of F frames (the rule is in
+// include/rvdd.h).  f32, every operation rounded on its own; the pooled step is rvdd_cols_fit's (pooled_median); the floor's mean alone
+// is summed in f64 over the blocks in their order: tests/green_ref.py says the same in NumPy f32 and gets the same bits.
+extern "C" int rvdd_green_fit(const float* e, const float* level, const uint8_t* state, int32_t F, int32_t gh, int32_t gw, float black,
+                              const rvdd_green_fit_cfg* cfg, float* map, uint8_t* mstate, rvdd_green_stats* stats) {
+    const char* fn = "rvdd_green_fit";
+    if (!e) return fail(nullptr, RVDD_ERR_ARG, "%s: e_host is required", fn);
+    if (!level) return fail(nullptr, RVDD_ERR_ARG, "%s: level_host is required", fn);
+    if (!state) return fail(nullptr, RVDD_ERR_ARG, "%s: state_host is required", fn);
+    if (!cfg) return fail(nullptr, RVDD_ERR_ARG, "%s: fit_cfg is required", fn);
+    if (!map) return fail(nullptr, RVDD_ERR_ARG, "%s: map_host is required", fn);
+    if (!mstate) return fail(nullptr, RVDD_ERR_ARG, "%s: mstate_host is required", fn);
+    if (F < 1) return fail(nullptr, RVDD_ERR_ARG, "%s: F must be >= 1, got %d", fn, F);
+    if (gh < 1) return fail(nullptr, RVDD_ERR_ARG, "%s: gh must be >= 1, got %d", fn, gh);
+    if (gw < 1) return fail(nullptr, RVDD_ERR_ARG, "%s: gw must be >= 1, got %d", fn, gw);
+    if (!std::isfinite(black)) return fail(nullptr, RVDD_ERR_ARG, "%s: black must be finite, got %g", fn, (double)black);
+    if (!(cfg->k_sig >= 0.0f) || !std::isfinite(cfg->k_sig)) return fail(nullptr, RVDD_ERR_ARG, "%s: k_sig must be finite and >= 0, got %g", fn, cfg->k_sig);
+    if (!(cfg->max_gain > 0.0f) || !std::isfinite(cfg->max_gain)) return fail(nullptr, RVDD_ERR_ARG, "%s: max_gain must be finite and > 0, got %g", fn, cfg->max_gain);
+    if (!(cfg->min_signal > 0.0f) || !std::isfinite(cfg->min_signal)) return fail(nullptr, RVDD_ERR_ARG, "%s: min_signal must be finite and > 0, got %g", fn, cfg->min_signal);
+    const int need = cfg->min_frames > 1 ? cfg->min_frames : 1;
+    const float k2 = cfg->k_sig * cfg->k_sig;
+    const int64_t blocks = (int64_t)gh * gw;
+    rvdd_green_stats st{};
+    double floor_sum = 0.0;
+    uint64_t supported = 0;
+    std::vector<float> v, a, os;
+    for (int64_t b = 0; b < blocks; ++b) {
+        v.clear();
+        for (int i = 0; i < F; ++i) {
+            const int64_t at = (int64_t)i * blocks + b;
+            const float signal = level[at] - black;
+            if (state[at] == 1 && signal >= cfg->min_signal) v.push_back(e[at] / signal);
+        }
+        const Pooled p = pooled_median(v, a, need, k2, cfg->max_gain, true);
+        map[b] = p.value;
+        mstate[b] = (uint8_t)p.state;
+        st.counts[p.state] += 1;
+        if (p.state == 0) continue;
+        floor_sum += (double)p.se;
+        ++supported;
+        os.push_back(p.o);
+        if (p.state == 3) continue;
+        const long long q = (long long)(int)std::rint(16384.0f * p.value);
+        st.sum_q2 += q * q;
+    }
+    st.floor = supported ? floor_sum / (double)supported : 0.0;
+    const Pooled flat = pooled_median(os, a, 1, k2, cfg->max_gain, true);      // the supported blocks' medians in the frames' place
+    st.flat_gain = flat.value;
+    st.flat_se = flat.se;
+    st.flat_state = flat.state;
     if (stats) *stats = st;
     return RVDD_OK;
 }

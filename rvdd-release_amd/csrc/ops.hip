@@ -62,7 +62,7 @@ int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* ou
     return RVDD_OK;
 }
 
-// the gate of rvdd_rows_cfg and rvdd_cols_cfg (Cfg): the fields the two share, in their order; *out = the kernel's parameters without a clamp
+// the gate of rvdd_rows_cfg, rvdd_cols_cfg and rvdd_green_cfg (Cfg): the fields the three share, in their order; *out = the kernel's parameters without a clamp
 template <class Cfg>
 static int line_params(rvdd_t* h, const char* fn, const Cfg* cfg, RowsParams* out) {
     if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
@@ -96,6 +96,14 @@ int run_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, 
     const double cells = (double)n * 4.0 * hh * ww;
     Scope sc(h, s, "cols_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
     HIPCHK(h, launch_cols_apply(packed, gray, map_dev, n, hh, ww, bit_depth, s));
+    return RVDD_OK;
+}
+
+int run_green_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int gh, int gw, float black, int n, int hh, int ww, int bit_depth,
+                    int bayer, hipStream_t s) {
+    const double cells = (double)n * hh * ww;                       // two planes read and written, two read, the gray plane written
+    Scope sc(h, s, "green_apply_kernel", 0.0, cells * 4.0 * (gray ? 7.0 : 4.0));
+    HIPCHK(h, launch_green_apply(packed, gray, map_dev, gh, gw, black, n, hh, ww, bit_depth, bayer, s));
     return RVDD_OK;
 }
 
@@ -555,6 +563,59 @@ int rvdd_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev,
         return fail(h, RVDD_ERR_ARG, "%s: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, n, hh, ww);
     ENTER(h);
     return run_cols_apply(h, packed, gray, map_dev, n, hh, ww, bit_depth, static_cast<hipStream_t>(stream));
+}
+
+// the shape and pattern checks of the two green calls
+static int green_shape(rvdd_t* h, const char* fn, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, int32_t pattern) {
+    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 1..16, got %d", fn, bit_depth);
+    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
+        return fail(h, RVDD_ERR_ARG, "%s: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", fn, pattern);
+    if (hh < 2) return fail(h, RVDD_ERR_ARG, "%s: hh must be >= 2 (a sample's four neighbours lie in two cell rows), got %d", fn, hh);
+    if (ww < 2) return fail(h, RVDD_ERR_ARG, "%s: ww must be >= 2 (a sample's four neighbours lie in two cell columns), got %d", fn, ww);
+    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    return RVDD_OK;
+}
+
+int rvdd_green_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, int32_t pattern,
+                        const rvdd_green_cfg* cfg, float* e, float* level, uint8_t* state, void* stream) {
+    const char* fn = "rvdd_green_estimate";
+    if (!h) return RVDD_ERR_ARG;
+    RowsParams p;
+    RC(line_params(h, fn, cfg, &p));
+    if (!std::isfinite(cfg->black)) return fail(h, RVDD_ERR_ARG, "%s: black must be finite, got %g", fn, cfg->black);
+    RC(green_shape(h, fn, n, hh, ww, bit_depth, pattern));
+    if (n == 0) return RVDD_OK;
+    if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
+    if (!e) return fail(h, RVDD_ERR_ARG, "%s: e is required", fn);
+    if (!level) return fail(h, RVDD_ERR_ARG, "%s: level is required", fn);
+    if (!state) return fail(h, RVDD_ERR_ARG, "%s: state is required", fn);
+    if (green_estimate_blocks(n, hh, ww) < 0)
+        return fail(h, RVDD_ERR_ARG, "%s: n = %d frames of %d x %d cells need a launch of more than 2^31 - 1 blocks", fn, n, hh, ww);
+    ENTER(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scope sc(h, s, "green_estimate_kernel", 0.0, (double)n * 2.0 * hh * ww * 4.0);
+    HIPCHK(h, launch_green_estimate(packed, n, hh, ww, bit_depth, pattern, p, e, level, state, s));
+    return RVDD_OK;
+}
+
+int rvdd_green_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int32_t gh, int32_t gw, float black, int32_t n, int32_t hh,
+                     int32_t ww, int32_t bit_depth, int32_t pattern, void* stream) {
+    const char* fn = "rvdd_green_apply";
+    if (!h) return RVDD_ERR_ARG;
+    RC(green_shape(h, fn, n, hh, ww, bit_depth, pattern));
+    if (!std::isfinite(black)) return fail(h, RVDD_ERR_ARG, "%s: black must be finite, got %g", fn, (double)black);
+    int fgh, fgw;
+    green_grid(hh, ww, &fgh, &fgw);
+    if (!(gh == 1 && gw == 1) && !(gh == fgh && gw == fgw))
+        return fail(h, RVDD_ERR_ARG, "%s: the map's grid gh x gw = %d x %d is neither 1 x 1 nor the %d x %d blocks of frames of %d x %d cells", fn, gh, gw,
+                    fgh, fgw, hh, ww);
+    if (n == 0) return RVDD_OK;
+    if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
+    if (!map_dev) return fail(h, RVDD_ERR_ARG, "%s: map_dev is required", fn);
+    if (line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray), nullptr) < 0)
+        return fail(h, RVDD_ERR_ARG, "%s: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, n, hh, ww);
+    ENTER(h);
+    return run_green_apply(h, packed, gray, map_dev, gh, gw, black, n, hh, ww, bit_depth, pattern, static_cast<hipStream_t>(stream));
 }
 
 // the shape checks rvdd_unprocess and rvdd_unprocess_draws share; 0 = fine

@@ -9,8 +9,8 @@
 // that order, so that workgroups next to each other read eight of their nine rows twice from L2 and a frame once from memory.  A
 // sample's key stays in a register.  A round of the search counts in the thread's own registers (counting by ballots kept a hundred
 // scalar pairs alive and spilled them), one DPP sum per wave, lane 0 of each wave leaves its counts in LDS, ONE barrier (the rounds
-// alternate between two sets of LDS words), every thread adds the four waves' counts.  The offset is clamped to +-max_dn and the
-// row counted in the frame's accumulator.
+// alternate between two sets of LDS words), every thread adds the four waves' counts (line_noise.h's line_group_count).  The offset
+// is clamped to +-max_dn and the row counted in the frame's accumulator.
 //
 // Apply.  A pure stream in place.  A row whose two offsets are zero is left after two loads; a plane whose offset is zero is read for
 // the gray value and not written.
@@ -22,33 +22,6 @@ namespace {
 constexpr int kRowsThreads = kLineApplyThreads;
 constexpr int kRowsWaves = kRowsThreads / 64;
 constexpr int kRowsMaxKeys = 32;                                     // keys per thread at most: 2 ww <= 256 * 32
-
-// |{key < t[n]}| over the workgroup for NT <= 3 thresholds: every thread of the workgroup arrives, every thread gets the counts.
-// A thread counts its own keys -- at most 32, so that a wave's count stays below 2^16 and two counts share a register --, the wave
-// adds them up (DPP), lane 0 leaves them in LDS.  `words`: this round's LDS words [wave][2]; the caller alternates between two sets,
-// which makes one barrier a round enough
-template <int KPT, int NT>
-__device__ __forceinline__ void rows_count(const unsigned (&key)[KPT], const unsigned (&t)[NT], unsigned (*words)[2], int lane, int wave,
-                                           unsigned (&out)[NT]) {
-    static_assert(KPT <= 32, "two counts below 2^16 in one register");
-    unsigned lo = 0, hi = 0;
-#pragma unroll
-    for (int q = 0; q < KPT; ++q) line_count_add(key[q], t, lo, hi);
-    lo = wave_sum_u32(lo);
-    if constexpr (NT > 2) hi = wave_sum_u32(hi);
-    if (lane == 0) {
-        words[wave][0] = lo;
-        if constexpr (NT > 2) words[wave][1] = hi;
-    }
-    __syncthreads();
-    lo = hi = 0;
-#pragma unroll
-    for (int w = 0; w < kRowsWaves; ++w) {
-        lo += words[w][0];
-        if constexpr (NT > 2) hi += words[w][1];
-    }
-    line_count_unpack(lo, hi, out);                                  // four waves of at most 2048 each
-}
 
 template <int KPT>
 __global__ void __launch_bounds__(kRowsThreads) rows_estimate_kernel(const float* __restrict__ packed, float* __restrict__ offsets,
@@ -85,32 +58,10 @@ __global__ void __launch_bounds__(kRowsThreads) rows_estimate_kernel(const float
     const LineMedian med = line_median(
         (unsigned)ww,
         [&](const auto& t, auto& c) {
-            rows_count<KPT>(key, t, words[phase], lane, wave, c);
+            line_group_count<kRowsWaves>(key, t, words[phase], lane, wave, c);      // four waves of at most 2048 each
             phase ^= 1;
         },
-        [&](unsigned prefix) {
-            unsigned le = 0, above = kLineNoKey;
-#pragma unroll
-            for (int q = 0; q < KPT; ++q) {
-                le += key[q] <= prefix ? 1u : 0u;
-                above = min(above, key[q] > prefix ? key[q] : kLineNoKey);
-            }
-            le = wave_sum_u32(le);
-            above = ~wave_max_u32(~above);                           // the wave's minimum
-            if (lane == 0) {
-                words[phase][wave][0] = le;
-                words[phase][wave][1] = above;
-            }
-            __syncthreads();
-            le = 0;
-            above = kLineNoKey;
-#pragma unroll
-            for (int w = 0; w < kRowsWaves; ++w) {
-                le += words[phase][w][0];
-                above = min(above, words[phase][w][1]);
-            }
-            return LineAbove{le, above};
-        });
+        [&](unsigned prefix) { return line_group_above<kRowsWaves>(key, prefix, words[phase], lane, wave); });
     if (med.skipped) {                                               // uniform
         if (tid == 0) {
             offsets[row] = 0.0f;

@@ -279,6 +279,14 @@ struct rvdd_handle {
         float* map = nullptr;            // DEVICE [2][ww]: DN of the pushes' bit depth (freed by rvdd_set_cols / rvdd_destroy)
     } cols;
 
+    // rvdd_set_green: the static map of green gains taken out of the ring's frames behind the rows and in front of the match (rvdd_video_push)
+    struct Green {
+        bool on = false;
+        int gh = 0, gw = 0;              // the map's grid: a frame's blocks, or 1 x 1 for a flat gain
+        float black = 0.0f;              // the level without signal, DN of the pushes' bit depth
+        float* map = nullptr;            // DEVICE [gh][gw]: gains of plane A relative to plane B (freed by rvdd_set_green / rvdd_destroy)
+    } geq;
+
     // hipGraph replay of a frame-step (see rvdd_step)
     struct StepKey {
         const void* p[6];
@@ -472,6 +480,9 @@ int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* ou
 int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out);
 // launch_cols_apply inside its profile class, for rvdd_cols_apply and the stage behind rvdd_set_cols: 0, or the HIP error on the handle
 int run_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int n, int hh, int ww, int bit_depth, hipStream_t s);
+// launch_green_apply inside its profile class, for rvdd_green_apply and the stage behind rvdd_set_green: 0, or the HIP error on the handle
+int run_green_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int gh, int gw, float black, int n, int hh, int ww, int bit_depth,
+                    int bayer, hipStream_t s);
 // the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
 int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg);
 int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,

@@ -516,6 +516,21 @@ int64_t cols_estimate_blocks(int n, int hh, int ww);     // the grid of that lau
 // packed [n][4][hh][ww] IN PLACE, gray [n][hh][ww] (nullable) in place: map [2][ww] (DEVICE, DN) taken out of the columns where it is not zero
 hipError_t launch_cols_apply(float* packed, float* gray, const float* map, int n, int hh, int ww, int bit_depth, hipStream_t s);
 
+// green.hip -- green imbalance: the gain of the green plane of CFA row 0 (A) against that of CFA row 1 (B) per frame and block of
+// RVDD_GREEN_BLOCK^2 cells (rvdd_green_estimate), a static map taken out (rvdd_green_apply, the stage behind rvdd_set_green).  The
+// gate's parameters are RowsParams (max_dn is not read)
+inline int green_plane_a(int bayer) { return bayer >= 2 ? 1 : 0; }      // enum rvdd_bayer -> plane A: 0 (GBRG, GRBG) or 1 (RGGB, BGGR); B is 3 - A
+void green_grid(int hh, int ww, int* gh, int* gw);                       // the blocks of a frame: ceil(hh / 32) x ceil(ww / 32)
+int64_t green_estimate_blocks(int n, int hh, int ww);                    // the grid of the estimate's launch; -1 = more than 2^31 - 1 blocks
+// e / level / state [n][gh][gw] (DEVICE, every word written) of packed [n][4][hh][ww]; one workgroup per (frame, block).  hh, ww >= 2;
+// n <= 0 launches nothing
+hipError_t launch_green_estimate(const float* packed, int n, int hh, int ww, int bit_depth, int bayer, const RowsParams& p, float* e, float* level,
+                                 uint8_t* state, hipStream_t s);
+// packed [n][4][hh][ww] IN PLACE, gray [n][hh][ww] (nullable) in place: the gains map [gh][gw] (DEVICE; the frame's grid, or [1][1])
+// interpolated per cell and taken out of the two green planes where they are not zero; the grid is line_apply_blocks'
+hipError_t launch_green_apply(float* packed, float* gray, const float* map, int gh, int gw, float black, int n, int hh, int ww, int bit_depth,
+                              int bayer, hipStream_t s);
+
 // unprocess.hip -- sRGB video to the raw dataset's four images (dataset/generate_raw_from_RGB.py) and the random planes alone
 // srgb [n][2hh][2ww][3] u8; g: the three inverted gains; dither [n][2hh][2ww][3] / normal [n][hh][ww][4] nullable (drawn from
 // (seed, frame0 + image) then); lin_f32 / lin_u16 [n][2hh][2ww][3], gt_raw / noisy [n][hh][ww][4], each nullable

@@ -81,6 +81,16 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     const auto cols = h->cols;
     if (cols.on && cols.ww != ww)
         return fail(h, RVDD_ERR_ARG, "rvdd_video_push: the map of rvdd_set_cols is one of %d cell columns, the frames have %d", cols.ww, ww);
+    // rvdd_set_green: the static map of green gains is taken out behind the rows; nothing is allocated here
+    const auto green = h->geq;
+    if (green.on) {
+        if (hh < 2 || ww < 2) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with rvdd_set_green hh and ww must be >= 2, got %d x %d cells", hh, ww);
+        int gh, gw;
+        green_grid(hh, ww, &gh, &gw);
+        if (!(green.gh == 1 && green.gw == 1) && (green.gh != gh || green.gw != gw))
+            return fail(h, RVDD_ERR_ARG, "rvdd_video_push: the map of rvdd_set_green is one of %d x %d blocks, frames of %d x %d cells have %d x %d",
+                        green.gh, green.gw, hh, ww, gh, gw);
+    }
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
         if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
@@ -117,6 +127,9 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
             Scope sc(h, s, "rows_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
             HIPCHK(h, launch_rows_apply(ring_packed, ring_gray, rows.offsets + (size_t)b * 2 * hh, e - b, hh, ww, bit_depth, s));
         }
+        // rvdd_set_green: the green gains taken out of the ring's two green planes and gray planes in place: one launch
+        if (green.on)
+            RC(run_green_apply(h, ring_packed, ring_gray, green.map, green.gh, green.gw, green.black, e - b, hh, ww, bit_depth, h->opt.bayer, s));
         // the gray planes stay the sensor's: TV-L1 matches what it always matched
         if (match.on) HIPCHK(h, launch_match(ring_packed, ring_packed, (int64_t)(e - b) * 4 * (int64_t)hw, match.cfg.scale, match.cfg.offset, false, s));
         return RVDD_OK;
@@ -293,6 +306,34 @@ extern "C" int rvdd_set_cols(rvdd_t* h, const float* map_host, int32_t ww) {
     HIPCHK(h, hipMemcpy(c.map, map_host, 2 * (size_t)ww * sizeof(float), hipMemcpyHostToDevice));
     c.ww = ww;
     c.on = true;
+    return RVDD_OK;
+}
+
+extern "C" int rvdd_set_green(rvdd_t* h, const float* map_host, int32_t gh, int32_t gw, float black) {
+    if (!h) return RVDD_ERR_ARG;
+    if (map_host) {
+        if (gh < 1) return fail(h, RVDD_ERR_ARG, "rvdd_set_green: gh must be >= 1, got %d", gh);
+        if (gw < 1) return fail(h, RVDD_ERR_ARG, "rvdd_set_green: gw must be >= 1, got %d", gw);
+        if (!std::isfinite(black)) return fail(h, RVDD_ERR_ARG, "rvdd_set_green: black must be finite, got %g", (double)black);
+        for (int64_t i = 0; i < (int64_t)gh * gw; ++i)
+            if (!std::isfinite(map_host[i]))
+                return fail(h, RVDD_ERR_ARG, "rvdd_set_green: map_host[%d][%d] = %g is not finite", (int)(i / gw), (int)(i % gw), (double)map_host[i]);
+    }
+    ENTER(h);
+    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_cols: pushes in flight read the map they were enqueued with
+    auto& g = h->geq;
+    if (g.map) HIPCHK(h, hipFree(g.map));
+    g.map = nullptr;
+    g.on = false;
+    g.gh = g.gw = 0;
+    if (!map_host) return RVDD_OK;
+    const size_t bytes = (size_t)gh * (size_t)gw * sizeof(float);
+    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&g.map), bytes));
+    HIPCHK(h, hipMemcpy(g.map, map_host, bytes, hipMemcpyHostToDevice));
+    g.gh = gh;
+    g.gw = gw;
+    g.black = black;
+    g.on = true;
     return RVDD_OK;
 }
 

@@ -126,6 +126,30 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       that moves; one camera setting per run; offsets per plane and per-column gains are not modelled; NOTHING is
                       measured on real footage.  Without --col_noise no new call is made and the output files keep
                       their bytes.
+  --green_eq FILE     balance the two green planes (the green sites of the red rows and of the blue rows see the same light through
+                      different neighbours; crosstalk makes them differ by up to a few per cent, slowly over the field and the same in
+                      every frame; Hamilton-Adams turns that into a maze pattern) of every frame on the device (`rvdd_set_green`),
+                      behind --dpc_map / --dpc, --col_noise and --row_noise and in front of --match_noise: FILE is a one-sample float32
+                      TIFF of one gain per block of 32 x 32 cells, or one value (python -m rvdd_release_amd.green_eq writes one).  It
+                      needs the level without signal: --green_eq_black DN, or b / a of --green_eq_curve or of the curve of --dpc.
+                      Cells whose gain is 0 keep their bits.  TV-L1, the network and --report see the corrected frames.
+  --green_eq auto     the map found in the run's own footage before streaming starts (`rvdd_green_estimate`, `rvdd_green_fit`; python -m
+                      rvdd_release_amd.green_eq is the same pass on its own): --green_eq_frames F (default 32) frames spread evenly
+                      over up to 16 videos; per frame and block either green plane's samples against the middle of their four diagonal
+                      neighbours of the other plane, samples further than --green_eq_gate K (default 3) standard deviations of the
+                      noise curve left out; per block the median over the frames of the difference over the level above black, taken
+                      only where at least half of the frames gave an estimate at a level of --green_eq_min_signal DN (default
+                      (2^bit_depth - 1) / 64, a guess) above black and it is at least --green_eq_sigma (default 3) standard errors of
+                      itself; --green_eq_max (default 0.10) is the largest gain taken out; --green_eq_field map (default) | flat takes
+                      one gain per block, or the one pooled over the blocks.
+  --green_eq_curve C  the sensor's curve in DN of --bit_depth: a,b[,floor], auto (the run's own estimate, shared with --dpc_noise auto),
+                      iso3200 or iso12800.  Default: the curve of --dpc; without either it is an error under auto.
+                      Prints `green: <applied> applied, <insignificant> insignificant, <unsupported> unsupported, <clamped> clamped of
+                      <n> blocks, map rms gain <x> (the pooled estimate alone: <y>), flat estimate <g> +- <se> (<state>), ...` (or what a
+                      FILE holds).  Limits: the gate is centred on zero, so an imbalance shrinks by about phi(K) / phi(0) of itself
+                      (a prototype recovered 0.93 - 0.95 of an injected 1 - 5 %; 0.63 - 0.72 on dark-heavy `synth` blocks); texture finer than two cells aliases; one camera,
+                      lens and aperture per map; NOTHING is measured on real footage.  A map in which no block is
+                      significant leaves every byte of the output alone; without --green_eq no new call is made.
   --report FILE       check the outputs without ground truth: if the output is the clean frame, noisy - remosaic(denoised) is the noise.
                       The stream reduces every output and its (corrected, matched) centre frame to residual statistics on the device
                       (`rvdd_set_resid`), read at the end of every video -- of every shot under --cuts -- and judged against a noise curve
@@ -154,10 +178,10 @@ import torch
 
 from . import _lib
 from . import tiffio
-from .footage import (FileSpec, add_cols_arguments, add_dpc_arguments, add_report_arguments, add_rows_arguments, cols_arguments,
-                      dpc_arguments, estimate_noise, match_arguments, open_rawvideo, report_arguments, report_record, rows_arguments,
-                      rows_line, to_device)
-from .runtime import BAYER_PATTERNS, BITS_DEPTHS, bits_row_bytes, match_coeffs, resid_add
+from .footage import (FileSpec, add_cols_arguments, add_dpc_arguments, add_green_arguments, add_report_arguments, add_rows_arguments,
+                      cols_arguments, dpc_arguments, estimate_noise, green_arguments, match_arguments, open_rawvideo, report_arguments,
+                      report_record, rows_arguments, rows_line, to_device)
+from .runtime import BAYER_PATTERNS, BITS_DEPTHS, bits_row_bytes, green_grid, match_coeffs, resid_add
 
 # --dpc_map auto and --cuts auto, kind "auto"; their FILE forms are a FileSpec, kind "file"
 DpcMapAuto = NamedTuple("DpcMapAuto", [("kind", str), ("frames", int), ("share", float), ("tolerate", int)])
@@ -346,6 +370,25 @@ def find_cols_map(dataset, dev, opt):
     return cmap
 
 
+def find_green_map(dataset, dev, opt):
+    """--green_eq: the run's map of green gains float32 [gh,gw] (or [1,1]), its `green:` line sent to the log.  auto:
+    `green_eq.estimate` on the run's own videos and the fit (`green_eq.report`), before any push."""
+    from . import green_eq as M
+    from .util._ops import ops_runtime
+    spec = opt.green
+    try:
+        if spec.kind == "file":
+            gmap = M.read_map(spec.path)
+            print(M.file_line(gmap, spec.black_dn, spec.path))
+            return gmap
+        e, level, state = M.estimate(ops_runtime(dev.index or 0), dataset, int(opt.bit_depth), spec.cfg(), spec.frames, opt.bayer_pattern)
+        gmap, r = M.report(e, level, state, spec.black_dn, spec.k_sig, spec.max_gain, spec.min_signal, spec.field)
+    except (RuntimeError, tiffio.TiffError, OSError) as err:
+        raise SystemExit("--green_eq %s: %s" % ("auto" if spec.kind == "auto" else spec.path, err))
+    print(M.summary_line(r, '%d frames' % r["frames"]))
+    return gmap
+
+
 def find_shots(dataset, dev, opt):
     """--cuts: the run's videos as their shots (`split_shots`), one `cuts: <key>: N frames, shots at [0, k1, ...]` line per video sent to
     the log.  auto: `cuts.detect` on the run's own videos, before any push."""
@@ -381,6 +424,7 @@ def _parse(argv):
     add_dpc_arguments(p)
     add_rows_arguments(p)
     add_cols_arguments(p)
+    add_green_arguments(p)
     p.add_argument('--dpc_map', type=str, default=None, help='FILE: correct the sites of this defect map (python -m rvdd_release_amd.dpc_map '
                    'writes one); auto: find the map in the footage before streaming starts, with the rule of --dpc')
     p.add_argument('--dpc_map_frames', type=int, default=None, help='with --dpc_map auto: frames read per video, spread over it (default 16)')
@@ -409,10 +453,13 @@ def _parse(argv):
     opt.rows = rows_arguments(own.row_noise, own.row_noise_curve, own.row_noise_max, opt.dpc, int(opt.bit_depth))
     opt.cols = cols_arguments(own.col_noise, own.col_noise_curve, own.col_noise_frames, own.col_noise_gate, own.col_noise_sigma,
                               own.col_noise_max, opt.dpc, int(opt.bit_depth))
+    opt.green = green_arguments(own.green_eq, own.green_eq_curve, own.green_eq_field, own.green_eq_frames, own.green_eq_gate, own.green_eq_sigma,
+                                own.green_eq_max, own.green_eq_min_signal, own.green_eq_black, opt.dpc, int(opt.bit_depth))
     opt.match = match_arguments(own.match_noise, own.match_iso)
     opt.report = report_arguments(own.report, own.report_noise, opt.match, int(opt.bit_depth))
     opt.cuts = cuts_arguments(own.cuts, own, opt.future_patch_depth)
     opt.cols_map = None                           # the column map of --col_noise: `prepasses` leaves it here
+    opt.green_map = None                          # the map of green gains of --green_eq, likewise
     if opt.raw_container is not None:
         if opt.raw_container != 'mipi':
             raise SystemExit("--raw_container %r: headerless frames are 'mipi' (packed TIFFs are recognised by themselves)" % opt.raw_container)
@@ -432,9 +479,9 @@ def _parse(argv):
 
 def prepasses(opt, dataset, dev):
     """What is decided on the run's own footage before any push, in this order: the noise curve of the stages on `auto` (ONE estimate
-    for --dpc_noise, --row_noise_curve, --col_noise_curve, --match_noise and --report_noise, made for the first that asks), the defect
-    map, the column map, the match coefficients, the shots.  Completes the records opt.dpc, opt.rows, opt.cols, opt.match and
-    opt.report, leaves the column map of --col_noise in opt.cols_map; -> (dmap: the cellmask or None, match: struct rvdd_match_cfg or
+    for --dpc_noise, --row_noise_curve, --col_noise_curve, --green_eq_curve, --match_noise and --report_noise, made for the first that
+    asks), the defect map, the column map, the map of green gains, the match coefficients, the shots.  Completes the records opt.dpc,
+    opt.rows, opt.cols, opt.green, opt.match and opt.report, leaves the maps of --col_noise and --green_eq in opt.cols_map and opt.green_map; -> (dmap: the cellmask or None, match: struct rvdd_match_cfg or
     None, shots [(key, [paths])])."""
     found = []
 
@@ -444,14 +491,16 @@ def prepasses(opt, dataset, dev):
             found.append(estimate_noise(dataset, dev, int(opt.bit_depth), opt.dpc_noise_frames, flag))
         return found[0]
 
-    for stage, flag in (("dpc", '--dpc_noise'), ("rows", '--row_noise_curve'), ("cols", '--col_noise_curve')):
-        spec = getattr(opt, stage)
+    for stage, flag in (("dpc", '--dpc_noise'), ("rows", '--row_noise_curve'), ("cols", '--col_noise_curve'), ("green", '--green_eq_curve')):
+        spec = getattr(opt, stage, None)
         if getattr(spec, "needs_curve", False):     # auto, or the curve of --dpc_noise auto; a stage that is off, or reads a FILE, has none
             setattr(opt, stage, spec.with_curve(*auto(flag)))
     # --dpc_map: ONE map for the run, read or found before any push; --dpc_static_only: --dpc has named the rule and is done
     dmap = None if opt.dpc_map is None else find_dpc_map(dataset, dev, opt)
     # --col_noise: ONE column map for the run, read or found before any push
     opt.cols_map = None if opt.cols is None else find_cols_map(dataset, dev, opt)
+    # --green_eq: ONE map of green gains for the run, read or found before any push
+    opt.green_map = None if getattr(opt, "green", None) is None else find_green_map(dataset, dev, opt)
     if opt.dpc_static_only:
         opt.dpc = None
     match = None
@@ -522,6 +571,12 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
         rt.set_cols(cmap)
     if rows is not None:
         rt.set_rows(rows.cfg())
+    gmap = getattr(opt, "green_map", None)
+    if gmap is not None and gmap.shape != (1, 1) and gmap.shape != green_grid(H // 2, W // 2):
+        raise SystemExit("--green_eq: the map is one of %d x %d blocks, video %r has frames of %d x %d, which are %d x %d blocks (one camera per run)"
+                         % ((gmap.shape[0], gmap.shape[1], videos[0][0], W, H) + green_grid(H // 2, W // 2)))
+    if gmap is not None:
+        rt.set_green(gmap, opt.green.black_dn)
     rt.set_match(match)
     if report is not None:
         rt.set_resid(True)
@@ -590,6 +645,8 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
         rt.set_rows(None)
     if cmap is not None:
         rt.set_cols(None)
+    if gmap is not None:
+        rt.set_green(None)
     return written
 
 

@@ -1,6 +1,6 @@
-"""What the footage commands (`denoise`, `noise`, `cuts`, `dpc_map`, `col_noise`) share: opening the rawvideo dataset, host frames to
+"""What the footage commands (`denoise`, `noise`, `cuts`, `dpc_map`, `col_noise`, `green_eq`) share: opening the rawvideo dataset, host frames to
 the device and through the ingest, the frames a map pre-pass samples (`sampled_frames`), one named record per stage's settings
-(`DpcSpec`, `RowsSpec`, `ColsSpec`, `MatchSpec`, `ReportSpec`), the one reader of a noise curve given on the command line
+(`DpcSpec`, `RowsSpec`, `ColsSpec`, `GreenSpec`, `MatchSpec`, `ReportSpec`), the one reader of a noise curve given on the command line
 (`curve_word` over the table CURVE_WORDS) with the `*_arguments` functions that hold each stage's cross-flag rules, and the
 estimate `auto` asks for.  The commands import this module and the feature modules; nothing here or there imports a command.
 """
@@ -12,7 +12,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from .runtime import DPC_ISO_CURVES, cols_cfg, dpc_cfg, dpc_iso_curve, raw_frames_to_device, rows_cfg
+from .runtime import DPC_ISO_CURVES, cols_cfg, dpc_cfg, dpc_iso_curve, green_cfg, raw_frames_to_device, rows_cfg
 
 MAX_VIDEOS = 16                                   # the videos a pre-pass reads of a run
 INF = float("inf")
@@ -72,6 +72,40 @@ class ColsSpec(NamedTuple):
         return cols_cfg(k_gate=self.k_gate, noise_a=self.a, noise_b=self.b, var_floor=self.floor)
 
 
+class GreenSpec(NamedTuple):
+    """--green_eq: kind is "auto" (path None) or "file" (the map is read from path; frames .. field are not used); black None: the level
+    noise_b / noise_a at which the curve's variance is zero; source as for the rows, or "black" where --green_eq_black alone serves a FILE"""
+    kind: str
+    path: Optional[str]
+    frames: int
+    k_gate: float
+    k_sig: float
+    max_gain: float
+    min_signal: float
+    field: str
+    black: Optional[float]
+    source: str
+    a: Optional[float]
+    b: Optional[float]
+    floor: float
+
+    @property
+    def needs_curve(self) -> bool:
+        return self.a is None and (self.kind == "auto" or self.black is None)
+
+    with_curve = _with_curve
+
+    @property
+    def black_dn(self) -> float:
+        """the level without signal in DN: --green_eq_black, else noise_b / noise_a (0 for a curve without a slope)"""
+        if self.black is not None:
+            return self.black
+        return self.b / self.a if self.a else 0.0
+
+    def cfg(self):
+        return green_cfg(k_gate=self.k_gate, noise_a=self.a, noise_b=self.b, var_floor=self.floor, black=self.black_dn)
+
+
 class MatchSpec(NamedTuple):
     """--match_noise / --match_iso: the footage's curve in DN of --bit_depth and the checkpoint's family"""
     a: Optional[float]
@@ -117,6 +151,7 @@ CURVE_WORDS = {
                                check=(lambda a, b: 0 < a < INF and abs(b) < INF, "a must be finite and > 0 and b finite")),
     '--row_noise_curve': CurveWord(_LINE, _LINE, floor=True, iso=True, check=_FINITE),
     '--col_noise_curve': CurveWord(_LINE, _LINE, floor=True, iso=True, check=_FINITE),
+    '--green_eq_curve': CurveWord(_LINE, _LINE, floor=True, iso=True, check=_FINITE),
     '--report_noise': CurveWord(_REPORT, _REPORT, iso=True, check=_FINITE),
 }
 
@@ -272,7 +307,7 @@ def curve_argument(flag, curve, dpc, bit_depth):
     if curve is not None:
         return curve_word(flag, curve, bit_depth)
     if dpc is None:
-        owner = {'--row_noise_curve': "--row_noise", '--col_noise_curve': "--col_noise auto"}[flag]      # what the curve is asked for
+        owner = {'--row_noise_curve': "--row_noise", '--col_noise_curve': "--col_noise auto", '--green_eq_curve': "--green_eq"}[flag]      # what the curve is asked for
         raise SystemExit("%s needs the sensor's noise curve: %s a,b[,floor] (var = a * m - b in DN of the frames), "
                          "%s auto (estimated from the footage), %s iso3200 / iso12800 (a checkpoint "
                          "family's curve, rescaled to --bit_depth) -- or the curve of --dpc, which then serves" % (owner, flag, flag, flag))
@@ -351,6 +386,73 @@ def cols_arguments(col_noise, curve, frames, gate, sigma, max_dn, dpc, bit_depth
     if not (max_dn > 0 and max_dn < INF):
         raise SystemExit("--col_noise_max is the largest offset taken out in DN, > 0, got %r" % max_dn)
     return ColsSpec("auto", frames, gate, sigma, max_dn, *curve_argument('--col_noise_curve', curve, dpc, bit_depth))
+
+
+GREEN_FLAGS = ("green_eq_curve", "green_eq_field", "green_eq_frames", "green_eq_gate", "green_eq_sigma", "green_eq_max", "green_eq_min_signal",
+               "green_eq_black")
+
+
+def add_green_arguments(p) -> None:
+    """the nine flags of the green equilibration, beside --col_noise; `green_arguments` reads them"""
+    p.add_argument('--green_eq', type=str, default=None, help='balance the two green planes of every frame on the device: FILE (a map python -m '
+                   'rvdd_release_amd.green_eq wrote) or auto (found in the footage before streaming starts)')
+    p.add_argument('--green_eq_curve', type=str, default=None, help='the curve of the gate, and of the black level: a,b[,floor] (var = a * m - b in DN '
+                   'of the frames), auto (estimated from the footage), iso3200 or iso12800; default: the curve of --dpc')
+    p.add_argument('--green_eq_field', type=str, default=None, help='with --green_eq auto: map (one gain per block of 32 x 32 cells, the default) or '
+                   'flat (one gain for the frame)')
+    p.add_argument('--green_eq_frames', type=int, default=None, help='with --green_eq auto: frames estimated per run, spread over the videos (default 32)')
+    p.add_argument('--green_eq_gate', type=float, default=None, help='with --green_eq auto: the gate K in standard deviations of the curve (default 3)')
+    p.add_argument('--green_eq_sigma', type=float, default=None, help='with --green_eq auto: a block is changed where its gain is at least this many '
+                   'standard errors of its own estimate (default 3)')
+    p.add_argument('--green_eq_max', type=float, default=None, help='with --green_eq auto: the largest gain taken out (default 0.10)')
+    p.add_argument('--green_eq_min_signal', type=float, default=None, help="with --green_eq auto: the least level above black, in DN, at which a frame's "
+                   'block counts (default (2^bit_depth - 1) / 64, a guess)')
+    p.add_argument('--green_eq_black', type=float, default=None, help='the level without signal, in DN of the frames (default: b / a of the curve)')
+
+
+def green_arguments(green_eq, curve, field, frames, gate, sigma, max_gain, min_signal, black, dpc, bit_depth):
+    """--green_eq and its eight flags -> None (no --green_eq) or a GreenSpec, its curve as `rows_arguments` takes it (`curve_argument`;
+    dpc = the DpcSpec of the run or None).  A FILE needs the black level alone: --green_eq_black, or a curve.  SystemExit where the
+    flags do not fit together."""
+    values = (curve, field, frames, gate, sigma, max_gain, min_signal, black)
+    given = [n for n, v in zip(GREEN_FLAGS, values) if v is not None]
+    if green_eq is None:
+        if given:
+            raise SystemExit("%s belong to --green_eq auto | FILE" % ', '.join('--' + n for n in GREEN_FLAGS))
+        return None
+    if black is not None and not abs(black) < INF:
+        raise SystemExit("--green_eq_black is a level in DN, finite, got %r" % black)
+    top = float((1 << int(bit_depth)) - 1)
+    if green_eq != "auto":
+        own = [n for n in given if n not in ("green_eq_curve", "green_eq_black")]
+        if own:
+            raise SystemExit("--%s belongs to --green_eq auto: --green_eq %s reads a map that is already made" % (own[0], green_eq))
+        if curve is None and dpc is None:
+            if black is None:
+                raise SystemExit("--green_eq %s needs the level without signal: --green_eq_black DN, or a noise curve whose b / a it is "
+                                 "(--green_eq_curve, or the curve of --dpc)" % green_eq)
+            source, a, b, floor = "black", None, None, 1.0
+        else:
+            source, a, b, floor = curve_argument('--green_eq_curve', curve, dpc, bit_depth)
+        return GreenSpec("file", green_eq, 0, 3.0, 3.0, 0.10, top / 64.0, "map", black, source, a, b, floor)
+    field = "map" if field is None else field
+    if field not in ("map", "flat"):
+        raise SystemExit("--green_eq_field is map or flat, got %r" % field)
+    frames, gate, sigma = 32 if frames is None else int(frames), 3.0 if gate is None else float(gate), 3.0 if sigma is None else float(sigma)
+    if frames < 1:
+        raise SystemExit("--green_eq_frames must be >= 1, got %d" % frames)
+    if not (gate > 0 and gate < INF):
+        raise SystemExit("--green_eq_gate is the gate in standard deviations, > 0 (around 3), got %r" % gate)
+    if not (sigma >= 0 and sigma < INF):
+        raise SystemExit("--green_eq_sigma is a number of standard errors, >= 0 (around 3), got %r" % sigma)
+    max_gain = 0.10 if max_gain is None else float(max_gain)
+    if not (max_gain > 0 and max_gain < INF):
+        raise SystemExit("--green_eq_max is the largest gain taken out, > 0 (0.10 = 10 %%), got %r" % max_gain)
+    min_signal = top / 64.0 if min_signal is None else float(min_signal)      # a guess, as the clamps of the rows and columns are
+    if not (min_signal > 0 and min_signal < INF):
+        raise SystemExit("--green_eq_min_signal is a level above black in DN, > 0, got %r" % min_signal)
+    return GreenSpec("auto", None, frames, gate, sigma, max_gain, min_signal, field, black,
+                     *curve_argument('--green_eq_curve', curve, dpc, bit_depth))
 
 
 def match_arguments(match_noise, match_iso):

@@ -319,6 +319,49 @@ def cols_fit(offsets, state, min_frames: int, k_sig: float = 3.0, max_dn: float 
     return m, ms, out
 
 
+GREEN_BLOCK = 32                                  # RVDD_GREEN_BLOCK: the cells along either side of a block of rvdd_green_estimate
+GREEN_STATES = COLS_STATES                        # mstate 0 .. 3 of rvdd_green_fit
+
+
+def green_grid(hh: int, ww: int) -> Tuple[int, int]:
+    """(gh, gw): the blocks of a frame of hh x ww cells"""
+    return (int(hh) + GREEN_BLOCK - 1) // GREEN_BLOCK, (int(ww) + GREEN_BLOCK - 1) // GREEN_BLOCK
+
+
+def green_cfg(k_gate: float, noise_a: float, noise_b: float, var_floor: float = 1.0, black: Optional[float] = None) -> "_lib.RvddGreenCfg":
+    """struct rvdd_green_cfg: the gate in standard deviations of the curve var(m) = noise_a * m - noise_b (DN of the frames' bit
+    depth), the least variance assumed, and the level without signal -- None: noise_b / noise_a, where the curve's variance is zero
+    (0 for a curve without a slope)."""
+    if black is None:
+        black = float(noise_b) / float(noise_a) if noise_a else 0.0
+    return _lib.RvddGreenCfg(float(k_gate), float(noise_a), float(noise_b), float(var_floor), float(black))
+
+
+def green_fit(e, level, state, black: float, min_frames: int, k_sig: float = 3.0, max_gain: float = 0.10, min_signal: float = 64.0):
+    """The static map of green gains from the per-frame estimates of F frames (rvdd_green_fit: on the host, no GPU needed; device
+    tensors are copied, which synchronises).  e, level float32 [F,gh,gw], state uint8 [F,gh,gw], as `RvddRuntime.green_estimate`
+    gives them.  -> (map float32 [gh,gw]: gains of plane A relative to plane B, mstate uint8 [gh,gw]: 0 unsupported, 1 applied, 2
+    applied and clamped, 3 insignificant, stats {"unsupported", "applied", "clamped", "insignificant", "sum_q2": ints; "floor",
+    "flat_gain", "flat_se": floats; "flat_state": int})."""
+    import numpy as np
+    host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t)
+    e, level, st = host(e), host(level), host(state)
+    if e.ndim != 3 or e.dtype != np.float32 or level.shape != e.shape or level.dtype != np.float32 or st.shape != e.shape or st.dtype != np.uint8:
+        raise RuntimeError(f"green_fit: e and level are float32 [F,gh,gw] and state uint8 [F,gh,gw], got {e.dtype} {e.shape}, "
+                           f"{level.dtype} {level.shape} and {st.dtype} {st.shape}")
+    F, gh, gw = e.shape
+    m = np.zeros((gh, gw), np.float32)
+    ms = np.zeros((gh, gw), np.uint8)
+    stats = _lib.RvddGreenStats()
+    cfg = _lib.RvddGreenFitCfg(int(min_frames), float(k_sig), float(max_gain), float(min_signal))
+    _host_call("rvdd_green_fit", e.ctypes.data, level.ctypes.data, st.ctypes.data, F, gh, gw, float(black), C.byref(cfg), m.ctypes.data,
+               ms.ctypes.data, C.byref(stats))
+    out = {name: int(stats.counts[i]) for i, name in enumerate(GREEN_STATES)}
+    out.update(sum_q2=int(stats.sum_q2), floor=float(stats.floor), flat_gain=float(stats.flat_gain), flat_se=float(stats.flat_se),
+               flat_state=int(stats.flat_state))
+    return m, ms, out
+
+
 def nearest_iso(a: float, b: float, bit_depth: int = 12, levels=(0.20, 0.45, 0.80)):
     """Which of DPC_ISO_CURVES lies closest to the curve (a, b) in DN of `bit_depth`: -> (iso, ratios), the ISO whose predicted
     standard deviation at 20 %, 45 % and 80 % of 2^bit_depth - 1 is nearest in the log (the largest |log ratio| over the levels is
@@ -909,6 +952,47 @@ class RvddRuntime:
         if m.ndim != 2 or m.shape[0] != 2 or m.dtype != np.float32:
             raise RuntimeError(f"set_cols: cmap is float32 [2,ww], got {m.dtype} {m.shape}")
         self._check(self.lib.rvdd_set_cols(self.h, m.ctypes.data, m.shape[1]), "rvdd_set_cols")
+
+    # -- green imbalance ------------------------------------------------------------------------
+    def green_estimate(self, packed: torch.Tensor, cfg, bit_depth: int = 12, pattern: Optional[str] = None):
+        """The imbalance of the two green planes per frame and block of 32 x 32 cells of packed frames [n,4,hh,ww]
+        (rvdd_green_estimate; cfg: `green_cfg(...)`, the curve in DN of `bit_depth`; pattern: one of BAYER_PATTERNS, None = the
+        pattern set_option("bayer_pattern", ...) gave this runtime).  -> (e float32 [n,gh,gw] in DN, level float32 [n,gh,gw] in
+        DN, state uint8 [n,gh,gw]: 0 skipped, 1 applied); `green_fit` pools them over the frames.  Nothing is synchronised."""
+        packed, n, hh, ww = _frames(packed, 4, "green_estimate: packed is [n,4,hh,ww]", "packed", self.device)
+        gh, gw = green_grid(hh, ww)
+        e = torch.empty((n, gh, gw), dtype=torch.float32, device=self._tdev)
+        level = torch.empty((n, gh, gw), dtype=torch.float32, device=self._tdev)
+        state = torch.empty((n, gh, gw), dtype=torch.uint8, device=self._tdev)
+        self._check(self.lib.rvdd_green_estimate(self.h, _ptr(packed), n, hh, ww, int(bit_depth), self._pattern(pattern, "green_estimate"),
+                                                 C.byref(cfg), _ptr(e), _ptr(level), _ptr(state), self._stream()), "rvdd_green_estimate")
+        return e, level, state
+
+    def green_apply(self, packed: torch.Tensor, gmap: torch.Tensor, black: float, bit_depth: int = 12, gray: Optional[torch.Tensor] = None,
+                    pattern: Optional[str] = None) -> torch.Tensor:
+        """The gains `gmap` (a device float32 tensor [gh,gw]: the frames' own grid, or [1,1] for a flat gain) taken out of the two
+        green planes of packed frames [n,4,hh,ww] IN PLACE (rvdd_green_apply), gray [n,hh,ww] re-formed in the cells with a
+        non-zero gain.  -> packed.  Both must be contiguous: they are written where they lie.  Nothing is synchronised."""
+        packed, n, hh, ww = _frames(packed, 4, "green_apply: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
+        gmap = _dev_tensor(gmap, "gmap", self.device, shape=(None, None), form="green_apply: gmap is a float32 tensor [gh,gw], as green_fit gives it")
+        if gray is not None:
+            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
+        self._check(self.lib.rvdd_green_apply(self.h, _ptr(packed), _ptr(gray), _ptr(gmap), gmap.shape[0], gmap.shape[1], float(black), n, hh, ww,
+                                              int(bit_depth), self._pattern(pattern, "green_apply"), self._stream()), "rvdd_green_apply")
+        return packed
+
+    def set_green(self, gmap=None, black: float = 0.0):
+        """The map of green gains as a stage of `video_push`, behind `set_dpc`, `set_cols` and `set_rows` and in front of `set_match`
+        (rvdd_set_green): gmap float32 [gh,gw] on the host (a NumPy array or CPU tensor; the frames' grid, or [1,1]), black in DN of
+        the pushes' bit depth; None = off (the default).  The planes are those of option "bayer_pattern".  Synchronises the device."""
+        if gmap is None:
+            self._check(self.lib.rvdd_set_green(self.h, None, 0, 0, 0.0), "rvdd_set_green")
+            return
+        import numpy as np
+        m = np.ascontiguousarray(gmap.cpu().numpy() if torch.is_tensor(gmap) else gmap)
+        if m.ndim != 2 or m.dtype != np.float32:
+            raise RuntimeError(f"set_green: gmap is float32 [gh,gw], got {m.dtype} {m.shape}")
+        self._check(self.lib.rvdd_set_green(self.h, m.ctypes.data, m.shape[0], m.shape[1], float(black)), "rvdd_set_green")
 
     def set_dpc(self, cfg=None):
         """The correction as a stage of `video_push`, between the ingest and the kept frames (rvdd_set_dpc): cfg = `dpc_cfg(...)`,
