@@ -354,10 +354,7 @@ void rvdd_destroy(rvdd_t* h) {
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->scratch) (void)hipFree(h->scratch);
     if (h->loss_batch) (void)hipFree(h->loss_batch);
-    if (h->dmap.mask) (void)hipFree(h->dmap.mask);
-    if (h->dmap.cells) (void)hipFree(h->dmap.cells);
-    if (h->cols.map) (void)hipFree(h->cols.map);
-    if (h->geq.map) (void)hipFree(h->geq.map);
+    stages_free(h);
     tvl1_free(h->tvl1);
     for (auto& p : h->pending) {
         (void)hipEventDestroy(p.e0);

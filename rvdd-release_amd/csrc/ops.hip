@@ -26,6 +26,17 @@ int psnr_l1_n(rvdd_t* h, const char* fn, const float* den, const float* gt, int3
 }
 }  // namespace
 
+// the TV-L1 workspace of nx x ny images (rvdd_tvl1flow, tvl1flow_batch): the cached one, or a new one in its place
+static int ensure_tvl1(rvdd_t* h, int nx, int ny, void* stream) {
+    if (h->tvl1 && tvl1_ws_nx(h->tvl1) == nx && tvl1_ws_ny(h->tvl1) == ny) return RVDD_OK;
+    HIPCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, tvl1_check(h->tvl1, static_cast<hipStream_t>(stream)));      // what an asynchronous batch on the old workspace left unread
+    tvl1_free(h->tvl1);
+    h->tvl1 = nullptr;
+    HIPCHK(h, tvl1_alloc(&h->tvl1, nx, ny));
+    return RVDD_OK;
+}
+
 // rvdd_tvl1flow_batch; `async`: without iteration counts the batch is enqueued and the call returns (option "tvl1_async")
 int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
                    void* stream, bool async) {
@@ -35,13 +46,7 @@ int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_
     ENTER(h);
     if (!tvl1_size_ok(nx, ny))
         return fail(h, RVDD_ERR_ARG, "rvdd_tvl1flow_batch: image too skinny for its pyramid (the reference reads out of bounds at this size)");
-    if (!h->tvl1 || tvl1_ws_nx(h->tvl1) != nx || tvl1_ws_ny(h->tvl1) != ny) {
-        HIPCHK(h, hipDeviceSynchronize());
-        HIPCHK(h, tvl1_check(h->tvl1, static_cast<hipStream_t>(stream)));      // what an asynchronous batch on the old workspace left unread
-        tvl1_free(h->tvl1);
-        h->tvl1 = nullptr;
-        HIPCHK(h, tvl1_alloc(&h->tvl1, nx, ny));
-    }
+    RC(ensure_tvl1(h, nx, ny, stream));
     std::vector<int> it((size_t)n, 0);
     HIPCHK(h, tvl1_run_batch(h->tvl1, I0, I1, u, n, static_cast<hipStream_t>(stream), iterations ? it.data() : nullptr, async));
     if (iterations)
@@ -50,7 +55,7 @@ int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_
 }
 
 int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* out) {
-    if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
+    RC(need_ptr(h, fn, cfg, "cfg"));
     if (!(cfg->k_hot >= 0.0f) || !std::isfinite(cfg->k_hot)) return fail(h, RVDD_ERR_ARG, "%s: k_hot must be finite and >= 0 (0 = off), got %g", fn, cfg->k_hot);
     if (!(cfg->k_dead >= 0.0f) || !std::isfinite(cfg->k_dead)) return fail(h, RVDD_ERR_ARG, "%s: k_dead must be finite and >= 0 (0 = off), got %g", fn, cfg->k_dead);
     if (!std::isfinite(cfg->noise_a)) return fail(h, RVDD_ERR_ARG, "%s: noise_a must be finite, got %g", fn, cfg->noise_a);
@@ -65,7 +70,7 @@ int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* ou
 // the gate of rvdd_rows_cfg, rvdd_cols_cfg and rvdd_green_cfg (Cfg): the fields the three share, in their order; *out = the kernel's parameters without a clamp
 template <class Cfg>
 static int line_params(rvdd_t* h, const char* fn, const Cfg* cfg, RowsParams* out) {
-    if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
+    RC(need_ptr(h, fn, cfg, "cfg"));
     if (!(cfg->k_gate > 0.0f) || !std::isfinite(cfg->k_gate)) return fail(h, RVDD_ERR_ARG, "%s: k_gate must be finite and > 0, got %g", fn, cfg->k_gate);
     if (!std::isfinite(cfg->noise_a)) return fail(h, RVDD_ERR_ARG, "%s: noise_a must be finite, got %g", fn, cfg->noise_a);
     if (!std::isfinite(cfg->noise_b)) return fail(h, RVDD_ERR_ARG, "%s: noise_b must be finite, got %g", fn, cfg->noise_b);
@@ -84,31 +89,16 @@ int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams*
 
 // the shape checks of the row (rows = true) and column calls: the axis the eight neighbours lie along needs five, the other one
 static int line_shape(rvdd_t* h, const char* fn, bool rows, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth) {
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 1..16, got %d", fn, bit_depth);
+    RC(need_bit_depth(h, fn, bit_depth));
     if ((rows ? hh : ww) < 5) return fail(h, RVDD_ERR_ARG, "%s: %s must be >= 5 (four %s neighbours on either side, mirrored about the site), got %d", fn, rows ? "hh" : "ww", rows ? "vertical" : "horizontal", rows ? hh : ww);
     if ((rows ? ww : hh) < 1) return fail(h, RVDD_ERR_ARG, "%s: %s must be >= 1, got %d", fn, rows ? "ww" : "hh", rows ? ww : hh);
     if (rows && ww > rows_max_ww()) return fail(h, RVDD_ERR_ARG, "%s: ww must be <= %d (a workgroup holds the 2 ww samples of a row in registers), got %d", fn, rows_max_ww(), ww);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
-    return RVDD_OK;
-}
-
-int run_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int n, int hh, int ww, int bit_depth, hipStream_t s) {
-    const double cells = (double)n * 4.0 * hh * ww;
-    Scope sc(h, s, "cols_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
-    HIPCHK(h, launch_cols_apply(packed, gray, map_dev, n, hh, ww, bit_depth, s));
-    return RVDD_OK;
-}
-
-int run_green_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int gh, int gw, float black, int n, int hh, int ww, int bit_depth,
-                    int bayer, hipStream_t s) {
-    const double cells = (double)n * hh * ww;                       // two planes read and written, two read, the gray plane written
-    Scope sc(h, s, "green_apply_kernel", 0.0, cells * 4.0 * (gray ? 7.0 : 4.0));
-    HIPCHK(h, launch_green_apply(packed, gray, map_dev, gh, gw, black, n, hh, ww, bit_depth, bayer, s));
+    RC(need_count(h, fn, n));
     return RVDD_OK;
 }
 
 int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg) {
-    if (!cfg) return fail(h, RVDD_ERR_ARG, "%s: cfg is required", fn);
+    RC(need_ptr(h, fn, cfg, "cfg"));
     if (!(cfg->scale > 0.0f) || !std::isfinite(cfg->scale)) return fail(h, RVDD_ERR_ARG, "%s: scale must be finite and > 0, got %g", fn, cfg->scale);
     if (!std::isfinite(cfg->offset)) return fail(h, RVDD_ERR_ARG, "%s: offset must be finite, got %g", fn, cfg->offset);
     return RVDD_OK;
@@ -121,12 +111,11 @@ int match_call(rvdd_t* h, const char* fn, const char* in_name, const char* out_n
                float* out, int32_t n, int c, int32_t d0, int32_t d1, const rvdd_match_cfg* cfg, bool inverse, void* stream) {
     if (!h) return RVDD_ERR_ARG;
     RC(match_params(h, fn, cfg));
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    RC(need_count(h, fn, n));
     if (d0 < 1) return fail(h, RVDD_ERR_ARG, "%s: %s must be >= 1, got %d", fn, d0_name, d0);
     if (d1 < 1) return fail(h, RVDD_ERR_ARG, "%s: %s must be >= 1, got %d", fn, d1_name, d1);
     if (n == 0) return RVDD_OK;
-    if (!in) return fail(h, RVDD_ERR_ARG, "%s: %s is required", fn, in_name);
-    if (!out) return fail(h, RVDD_ERR_ARG, "%s: %s is required", fn, out_name);
+    RC(need_ptrs(h, fn, {{in, in_name}, {out, out_name}}));
     const int64_t count = (int64_t)n * c * d0 * d1;      // below 2^63: three 31-bit factors and c <= 4
     if (match_blocks(count, match_wide(in, out, count)) < 0)
         return fail(h, RVDD_ERR_ARG, "%s: n * %s * %s = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, d0_name, d1_name, n, d0, d1);
@@ -162,8 +151,7 @@ int rvdd_psnr_l1_batch(rvdd_t* h, const float* den, const float* gt, int32_t n, 
 }
 
 int rvdd_demosaic_ha_bayer(rvdd_t* h, const float* raw, int32_t n, int32_t hh, int32_t ww, int32_t pattern, float* rgb, void* stream) {
-    if (h && (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR))
-        return fail(h, RVDD_ERR_ARG, "rvdd_demosaic_ha_bayer: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    if (h) RC(need_bayer(h, "rvdd_demosaic_ha_bayer", pattern));
     if (h && n == 0) return RVDD_OK;       // an empty batch is valid and launches nothing
     if (!h || !raw || !rgb || n < 0 || hh < 1 || ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_demosaic_ha_bayer: bad argument");
     ENTER(h);
@@ -202,13 +190,7 @@ int rvdd_tvl1flow(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t
     ENTER(h);
     if (!tvl1_size_ok(nx, ny))
         return fail(h, RVDD_ERR_ARG, "rvdd_tvl1flow: image too skinny for its pyramid (the reference reads out of bounds at this size)");
-    if (!h->tvl1 || tvl1_ws_nx(h->tvl1) != nx || tvl1_ws_ny(h->tvl1) != ny) {
-        HIPCHK(h, hipDeviceSynchronize());
-        HIPCHK(h, tvl1_check(h->tvl1, static_cast<hipStream_t>(stream)));      // what an asynchronous batch on the old workspace left unread
-        tvl1_free(h->tvl1);
-        h->tvl1 = nullptr;
-        HIPCHK(h, tvl1_alloc(&h->tvl1, nx, ny));
-    }
+    RC(ensure_tvl1(h, nx, ny, stream));
     int it = 0;
     HIPCHK(h, tvl1_run(h->tvl1, I0, I1, u, static_cast<hipStream_t>(stream), iterations ? &it : nullptr));
     if (iterations) *iterations = it;
@@ -260,7 +242,7 @@ int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
     if (dtype != RVDD_RAW_U16 && dtype != RVDD_RAW_F32) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: dtype must be 0 (u16) or 1 (f32), got %d", dtype);
     if (layout != RVDD_RAW_MOSAIC && layout != RVDD_RAW_PACKED_HWC)
         return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: layout must be 0 (mosaic) or 1 (packed HWC), got %d", layout);
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: bit_depth must be 1..16, got %d", bit_depth);
+    RC(need_bit_depth(h, "rvdd_ingest_raw", bit_depth));
     if (n == 0) return RVDD_OK;
     if (!frames || n < 0 || hh < 1 || ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_raw: bad argument (frames, n >= 0, hh, ww >= 1)");
     ENTER(h);
@@ -271,13 +253,12 @@ int rvdd_ingest_raw(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout
 int rvdd_gray_of_rgb(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t W, int32_t pattern, int32_t bit_depth, float* gray,
                      void* stream) {
     if (!h) return RVDD_ERR_ARG;
-    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
-        return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: bit_depth must be 1..16, got %d", bit_depth);
+    RC(need_bayer(h, "rvdd_gray_of_rgb", pattern));
+    RC(need_bit_depth(h, "rvdd_gray_of_rgb", bit_depth));
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: H must be even and >= 2, got %d", H);
     if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: W must be even and >= 2, got %d", W);
     if (n == 0) return RVDD_OK;
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: n must be >= 0, got %d", n);
+    RC(need_count(h, "rvdd_gray_of_rgb", n));
     if (!rgb || !gray) return fail(h, RVDD_ERR_ARG, "rvdd_gray_of_rgb: rgb and gray are required");
     ENTER(h);
     HIPCHK(h, launch_gray_of_rgb(rgb, n, H / 2, W / 2, pattern, bit_depth, gray, static_cast<hipStream_t>(stream)));
@@ -290,18 +271,16 @@ int rvdd_egress(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t W, in
     if (layout < RVDD_OUT_RGB_HWC || layout > RVDD_OUT_PACKED_HWC)
         return fail(h, RVDD_ERR_ARG, "rvdd_egress: layout must be 0 (RGB HWC), 1 (mosaic) or 2 (packed HWC), got %d", layout);
     if (dtype != RVDD_RAW_U16 && dtype != RVDD_RAW_F32) return fail(h, RVDD_ERR_ARG, "rvdd_egress: dtype must be 0 (u16) or 1 (f32), got %d", dtype);
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_egress: bit_depth must be 1..16, got %d", bit_depth);
+    RC(need_bit_depth(h, "rvdd_egress", bit_depth));
     const bool cfa = layout != RVDD_OUT_RGB_HWC;
-    if (cfa && (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR))
-        return fail(h, RVDD_ERR_ARG, "rvdd_egress: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    if (cfa) RC(need_bayer(h, "rvdd_egress", pattern));
     if (H < 1 || (cfa && (H & 1))) return fail(h, RVDD_ERR_ARG, "rvdd_egress: H must be >= 1, and even for the mosaic layouts, got %d", H);
     if (W < 1 || (cfa && (W & 1))) return fail(h, RVDD_ERR_ARG, "rvdd_egress: W must be >= 1, and even for the mosaic layouts, got %d", W);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_egress: n must be >= 0, got %d", n);
+    RC(need_count(h, "rvdd_egress", n));
     if (n == 0) return RVDD_OK;
     if (!rgb || !out) return fail(h, RVDD_ERR_ARG, "rvdd_egress: rgb and out are required");
     bool wide;
-    if (egress_blocks(rgb, n, H, W, layout, dtype, out, &wide) < 0)
-        return fail(h, RVDD_ERR_ARG, "rvdd_egress: n * H * W = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, H, W);
+    RC(need_blocks(h, "rvdd_egress", egress_blocks(rgb, n, H, W, layout, dtype, out, &wide), "n * H * W", n, H, W));
     ENTER(h);
     HIPCHK(h, launch_egress(rgb, n, H, W, layout, dtype, bit_depth, pattern, out, static_cast<hipStream_t>(stream)));
     return RVDD_OK;
@@ -319,14 +298,13 @@ static int bits_args(rvdd_t* h, const char* fn, int32_t order, int32_t bit_depth
 int rvdd_ingest_bits(rvdd_t* h, const uint8_t* frames, int32_t order, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, float* packed,
                      float* gray, void* stream) {
     if (!h) return RVDD_ERR_ARG;
-    if (hh < 1) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: hh must be >= 1, got %d", hh);
-    if (ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: ww must be >= 1, got %d", ww);
+    RC(need_min(h, "rvdd_ingest_bits", "hh", hh, 1));
+    RC(need_min(h, "rvdd_ingest_bits", "ww", ww, 1));
     RC(bits_args(h, "rvdd_ingest_bits", order, bit_depth, ww));
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: n must be >= 0, got %d", n);
+    RC(need_count(h, "rvdd_ingest_bits", n));
     if (n == 0) return RVDD_OK;
-    if (!frames) return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: frames is required");
-    if (bits_blocks(n, hh, ww, ingest_bits_fast(frames, ww, packed, gray)) < 0)
-        return fail(h, RVDD_ERR_ARG, "rvdd_ingest_bits: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
+    RC(need_ptr(h, "rvdd_ingest_bits", frames, "frames"));
+    RC(need_blocks(h, "rvdd_ingest_bits", bits_blocks(n, hh, ww, ingest_bits_fast(frames, ww, packed, gray)), "n * hh * ww", n, hh, ww));
     ENTER(h);
     HIPCHK(h, launch_ingest_bits(frames, order, n, hh, ww, bit_depth, packed, gray, static_cast<hipStream_t>(stream)));
     return RVDD_OK;
@@ -338,13 +316,11 @@ int rvdd_egress_bits(rvdd_t* h, const float* rgb, int32_t n, int32_t H, int32_t 
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: H must be even and >= 2, got %d", H);
     if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: W must be even and >= 2, got %d", W);
     RC(bits_args(h, "rvdd_egress_bits", order, bit_depth, W / 2));
-    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
-        return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: n must be >= 0, got %d", n);
+    RC(need_bayer(h, "rvdd_egress_bits", pattern));
+    RC(need_count(h, "rvdd_egress_bits", n));
     if (n == 0) return RVDD_OK;
     if (!rgb || !out) return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: rgb and out are required");
-    if (bits_blocks(n, H / 2, W / 2, egress_bits_fast(rgb, W, out)) < 0)
-        return fail(h, RVDD_ERR_ARG, "rvdd_egress_bits: n * H * W = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, H, W);
+    RC(need_blocks(h, "rvdd_egress_bits", bits_blocks(n, H / 2, W / 2, egress_bits_fast(rgb, W, out)), "n * H * W", n, H, W));
     ENTER(h);
     HIPCHK(h, launch_egress_bits(rgb, n, H, W, order, bit_depth, pattern, out, static_cast<hipStream_t>(stream)));
     return RVDD_OK;
@@ -355,14 +331,13 @@ int rvdd_dpc(rvdd_t* h, const float* packed_in, float* packed_out, float* gray, 
     if (!h) return RVDD_ERR_ARG;
     DpcParams p;
     RC(dpc_params(h, "rvdd_dpc", cfg, &p));
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: bit_depth must be 1..16, got %d", bit_depth);
-    if (hh < 2) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: hh must be >= 2 (the neighbours are mirrored about the site), got %d", hh);
-    if (ww < 2) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: ww must be >= 2 (the neighbours are mirrored about the site), got %d", ww);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: n must be >= 0, got %d", n);
+    RC(need_bit_depth(h, "rvdd_dpc", bit_depth));
+    RC(need_min(h, "rvdd_dpc", "hh", hh, 2, "the neighbours are mirrored about the site"));
+    RC(need_min(h, "rvdd_dpc", "ww", ww, 2, "the neighbours are mirrored about the site"));
+    RC(need_count(h, "rvdd_dpc", n));
     if (n == 0) return RVDD_OK;
     if (!packed_in || !packed_out) return fail(h, RVDD_ERR_ARG, "rvdd_dpc: packed_in and packed_out are required");
-    if (dpc_blocks(n, hh, ww, dpc_wide(packed_in, packed_out, gray, ww), nullptr) < 0)
-        return fail(h, RVDD_ERR_ARG, "rvdd_dpc: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
+    RC(need_blocks(h, "rvdd_dpc", dpc_blocks(n, hh, ww, dpc_wide(packed_in, packed_out, gray, ww), nullptr), "n * hh * ww", n, hh, ww));
     // a thread reads the neighbours other threads write: in place is a race, and so is any other overlap
     const uintptr_t a = reinterpret_cast<uintptr_t>(packed_in), b = reinterpret_cast<uintptr_t>(packed_out);
     const uintptr_t bytes = (uintptr_t)n * 4 * (uintptr_t)hh * (uintptr_t)ww * sizeof(float);
@@ -375,19 +350,19 @@ int rvdd_dpc(rvdd_t* h, const float* packed_in, float* packed_out, float* gray, 
 int rvdd_dpc_detect(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, const rvdd_dpc_detect_cfg* cfg,
                     uint32_t* hits, void* stream) {
     if (!h) return RVDD_ERR_ARG;
-    if (!cfg) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: cfg is required");
+    RC(need_ptr(h, "rvdd_dpc_detect", cfg, "cfg"));
     DpcParams p;
     RC(dpc_params(h, "rvdd_dpc_detect", &cfg->rule, &p));
     if (cfg->tolerate < 0 || cfg->tolerate > 3) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: tolerate must be 0..3 (the median of eight bears three), got %d", cfg->tolerate);
     if (cfg->reserved != 0) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: reserved must be 0, got %d", cfg->reserved);
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: bit_depth must be 1..16, got %d", bit_depth);
-    if (hh < 2) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: hh must be >= 2 (the neighbours are mirrored about the site), got %d", hh);
-    if (ww < 2) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: ww must be >= 2 (the neighbours are mirrored about the site), got %d", ww);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: n must be >= 0, got %d", n);
-    if (!hits) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: hits is required");
+    RC(need_bit_depth(h, "rvdd_dpc_detect", bit_depth));
+    RC(need_min(h, "rvdd_dpc_detect", "hh", hh, 2, "the neighbours are mirrored about the site"));
+    RC(need_min(h, "rvdd_dpc_detect", "ww", ww, 2, "the neighbours are mirrored about the site"));
+    RC(need_count(h, "rvdd_dpc_detect", n));
+    RC(need_ptr(h, "rvdd_dpc_detect", hits, "hits"));
     if (reinterpret_cast<uintptr_t>(hits) & 3) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: hits must be 4-byte aligned (32-bit words)");
     if (n == 0) return RVDD_OK;
-    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: packed is required");
+    RC(need_ptr(h, "rvdd_dpc_detect", packed, "packed"));
     if (dpc_detect_blocks(hh, ww, dpc_detect_wide(packed, hits, ww)) < 0)
         return fail(h, RVDD_ERR_ARG, "rvdd_dpc_detect: hh * ww = %d * %d needs a launch of more than 2^31 - 1 blocks", hh, ww);
     ENTER(h);
@@ -427,11 +402,11 @@ int rvdd_dpc_map_stats(const uint8_t* cellmask, int32_t hh, int32_t ww, int64_t*
 
 int rvdd_dpc_map_apply(rvdd_t* h, float* packed, float* gray, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, void* stream) {
     if (!h) return RVDD_ERR_ARG;
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: bit_depth must be 1..16, got %d", bit_depth);
-    if (hh < 3) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: hh must be >= 3 (the second ring is reflected about the edge), got %d", hh);
-    if (ww < 3) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: ww must be >= 3 (the second ring is reflected about the edge), got %d", ww);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: n must be >= 0, got %d", n);
-    if (n > 0 && !packed) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_map_apply: packed is required");
+    RC(need_bit_depth(h, "rvdd_dpc_map_apply", bit_depth));
+    RC(need_min(h, "rvdd_dpc_map_apply", "hh", hh, 3, "the second ring is reflected about the edge"));
+    RC(need_min(h, "rvdd_dpc_map_apply", "ww", ww, 3, "the second ring is reflected about the edge"));
+    RC(need_count(h, "rvdd_dpc_map_apply", n));
+    if (n > 0) RC(need_ptr(h, "rvdd_dpc_map_apply", packed, "packed"));
     const auto& m = h->dmap;
     if (!m.on) return fail(h, RVDD_ERR_STATE, "rvdd_dpc_map_apply: no map is set (rvdd_set_dpc_map)");
     if (m.hh != hh || m.ww != ww)
@@ -446,17 +421,17 @@ int rvdd_dpc_map_apply(rvdd_t* h, float* packed, float* gray, int32_t n, int32_t
 
 int rvdd_noise_hist(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, rvdd_noise_acc* acc, void* stream) {
     if (!h) return RVDD_ERR_ARG;
-    if (!acc) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: acc is required");
+    RC(need_ptr(h, "rvdd_noise_hist", acc, "acc"));
     if (reinterpret_cast<uintptr_t>(acc) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: acc must be 8-byte aligned (its sums are 64-bit atomics)");
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: bit_depth must be 1..16, got %d", bit_depth);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: n must be >= 0, got %d", n);
-    if (hh < 0) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: hh must be >= 0, got %d", hh);
-    if (ww < 0) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: ww must be >= 0, got %d", ww);
+    RC(need_bit_depth(h, "rvdd_noise_hist", bit_depth));
+    RC(need_count(h, "rvdd_noise_hist", n));
+    RC(need_min(h, "rvdd_noise_hist", "hh", hh, 0));
+    RC(need_min(h, "rvdd_noise_hist", "ww", ww, 0));
     const int64_t groups = noise_groups(n, hh, ww, nullptr);
     if (groups < 0)
         return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 workgroups", n, hh, ww);
     if (groups == 0) return RVDD_OK;       // no frame, or frames smaller than one block
-    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_noise_hist: packed is required");
+    RC(need_ptr(h, "rvdd_noise_hist", packed, "packed"));
     ENTER(h);
     HIPCHK(h, launch_noise_hist(packed, n, hh, ww, bit_depth, acc, static_cast<hipStream_t>(stream)));
     return RVDD_OK;
@@ -464,13 +439,12 @@ int rvdd_noise_hist(rvdd_t* h, const float* packed, int32_t n, int32_t hh, int32
 
 int rvdd_frame_sigs(rvdd_t* h, const float* gray, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, rvdd_frame_sig* sig, void* stream) {
     if (!h) return RVDD_ERR_ARG;
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: bit_depth must be 1..16, got %d", bit_depth);
-    if (hh < 16) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: hh must be >= 16 (16 bands of at least one row), got %d", hh);
-    if (ww < 16) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: ww must be >= 16 (16 columns of at least one cell), got %d", ww);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: n must be >= 0, got %d", n);
+    RC(need_bit_depth(h, "rvdd_frame_sigs", bit_depth));
+    RC(need_min(h, "rvdd_frame_sigs", "hh", hh, 16, "16 bands of at least one row"));
+    RC(need_min(h, "rvdd_frame_sigs", "ww", ww, 16, "16 columns of at least one cell"));
+    RC(need_count(h, "rvdd_frame_sigs", n));
     if (n == 0) return RVDD_OK;
-    if (!gray) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: gray is required");
-    if (!sig) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: sig is required");
+    RC(need_ptrs(h, "rvdd_frame_sigs", {{gray, "gray"}, {sig, "sig"}}));
     if (reinterpret_cast<uintptr_t>(sig) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: sig must be 8-byte aligned (its sums are 64-bit words)");
     if (n > 0x7fffffff / 16) return fail(h, RVDD_ERR_ARG, "rvdd_frame_sigs: n = %d needs a launch of more than 2^31 - 1 blocks (16 per frame)", n);
     ENTER(h);
@@ -481,19 +455,15 @@ int rvdd_frame_sigs(rvdd_t* h, const float* gray, int32_t n, int32_t hh, int32_t
 int rvdd_resid_stats(rvdd_t* h, const float* packed, const float* rgb, int32_t n, int32_t hh, int32_t ww, int32_t pattern, int32_t bit_depth,
                      rvdd_resid_acc* acc, void* stream) {
     if (!h) return RVDD_ERR_ARG;
-    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
-        return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: bit_depth must be 1..16, got %d", bit_depth);
-    if (hh < 1) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: hh must be >= 1, got %d", hh);
-    if (ww < 1) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: ww must be >= 1, got %d", ww);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: n must be >= 0, got %d", n);
+    RC(need_bayer(h, "rvdd_resid_stats", pattern));
+    RC(need_bit_depth(h, "rvdd_resid_stats", bit_depth));
+    RC(need_min(h, "rvdd_resid_stats", "hh", hh, 1));
+    RC(need_min(h, "rvdd_resid_stats", "ww", ww, 1));
+    RC(need_count(h, "rvdd_resid_stats", n));
     if (reinterpret_cast<uintptr_t>(acc) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: acc must be 8-byte aligned (its sums are 64-bit atomics)");
     if (n == 0) return RVDD_OK;
-    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: packed is required");
-    if (!rgb) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: rgb is required");
-    if (!acc) return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: acc is required");
-    if (resid_blocks(n, hh, ww, resid_wide(packed, rgb, ww), nullptr) < 0)
-        return fail(h, RVDD_ERR_ARG, "rvdd_resid_stats: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
+    RC(need_ptrs(h, "rvdd_resid_stats", {{packed, "packed"}, {rgb, "rgb"}, {acc, "acc"}}));
+    RC(need_blocks(h, "rvdd_resid_stats", resid_blocks(n, hh, ww, resid_wide(packed, rgb, ww), nullptr), "n * hh * ww", n, hh, ww));
     ENTER(h);
     HIPCHK(h, launch_resid(packed, rgb, n, hh, ww, pattern, bit_depth, acc, static_cast<hipStream_t>(stream)));
     return RVDD_OK;
@@ -507,9 +477,7 @@ int rvdd_rows_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, in
     RC(line_shape(h, "rvdd_rows_estimate", true, n, hh, ww, bit_depth));
     if (reinterpret_cast<uintptr_t>(acc) & 7) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: acc must be 8-byte aligned (sum_q2 is a 64-bit atomic)");
     if (n == 0) return RVDD_OK;
-    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: packed is required");
-    if (!offsets) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: offsets is required");
-    if (!state) return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: state is required");
+    RC(need_ptrs(h, "rvdd_rows_estimate", {{packed, "packed"}, {offsets, "offsets"}, {state, "state"}}));
     if (rows_estimate_blocks(n, hh) < 0)
         return fail(h, RVDD_ERR_ARG, "rvdd_rows_estimate: n * 2 * hh = %d * 2 * %d needs a launch of more than 2^31 - 1 blocks", n, hh);
     ENTER(h);
@@ -521,10 +489,8 @@ int rvdd_rows_apply(rvdd_t* h, float* packed, float* gray, const float* offsets,
     if (!h) return RVDD_ERR_ARG;
     RC(line_shape(h, "rvdd_rows_apply", true, n, hh, ww, bit_depth));
     if (n == 0) return RVDD_OK;
-    if (!packed) return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: packed is required");
-    if (!offsets) return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: offsets is required");
-    if (line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray), nullptr) < 0)
-        return fail(h, RVDD_ERR_ARG, "rvdd_rows_apply: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", n, hh, ww);
+    RC(need_ptrs(h, "rvdd_rows_apply", {{packed, "packed"}, {offsets, "offsets"}}));
+    RC(need_blocks(h, "rvdd_rows_apply", line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray), nullptr), "n * hh * ww", n, hh, ww));
     ENTER(h);
     HIPCHK(h, launch_rows_apply(packed, gray, offsets, n, hh, ww, bit_depth, static_cast<hipStream_t>(stream)));
     return RVDD_OK;
@@ -540,9 +506,7 @@ int rvdd_cols_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, in
     if (hh > cols_max_hh())
         return fail(h, RVDD_ERR_ARG, "%s: hh must be <= %d (a workgroup holds the 2 hh keys of four columns in LDS), got %d", fn, cols_max_hh(), hh);
     if (n == 0) return RVDD_OK;
-    if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
-    if (!offsets) return fail(h, RVDD_ERR_ARG, "%s: offsets is required", fn);
-    if (!state) return fail(h, RVDD_ERR_ARG, "%s: state is required", fn);
+    RC(need_ptrs(h, fn, {{packed, "packed"}, {offsets, "offsets"}, {state, "state"}}));
     if (cols_estimate_blocks(n, hh, ww) < 0)
         return fail(h, RVDD_ERR_ARG, "%s: n = %d frames of ww = %d columns need a launch of more than 2^31 - 1 blocks", fn, n, ww);
     ENTER(h);
@@ -557,22 +521,19 @@ int rvdd_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev,
     if (!h) return RVDD_ERR_ARG;
     RC(line_shape(h, fn, false, n, hh, ww, bit_depth));
     if (n == 0) return RVDD_OK;
-    if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
-    if (!map_dev) return fail(h, RVDD_ERR_ARG, "%s: map_dev is required", fn);
-    if (line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray, map_dev), nullptr) < 0)
-        return fail(h, RVDD_ERR_ARG, "%s: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, n, hh, ww);
+    RC(need_ptrs(h, fn, {{packed, "packed"}, {map_dev, "map_dev"}}));
+    RC(need_blocks(h, fn, line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray, map_dev), nullptr), "n * hh * ww", n, hh, ww));
     ENTER(h);
     return run_cols_apply(h, packed, gray, map_dev, n, hh, ww, bit_depth, static_cast<hipStream_t>(stream));
 }
 
 // the shape and pattern checks of the two green calls
 static int green_shape(rvdd_t* h, const char* fn, int32_t n, int32_t hh, int32_t ww, int32_t bit_depth, int32_t pattern) {
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 1..16, got %d", fn, bit_depth);
-    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
-        return fail(h, RVDD_ERR_ARG, "%s: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", fn, pattern);
-    if (hh < 2) return fail(h, RVDD_ERR_ARG, "%s: hh must be >= 2 (a sample's four neighbours lie in two cell rows), got %d", fn, hh);
-    if (ww < 2) return fail(h, RVDD_ERR_ARG, "%s: ww must be >= 2 (a sample's four neighbours lie in two cell columns), got %d", fn, ww);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    RC(need_bit_depth(h, fn, bit_depth));
+    RC(need_bayer(h, fn, pattern));
+    RC(need_min(h, fn, "hh", hh, 2, "a sample's four neighbours lie in two cell rows"));
+    RC(need_min(h, fn, "ww", ww, 2, "a sample's four neighbours lie in two cell columns"));
+    RC(need_count(h, fn, n));
     return RVDD_OK;
 }
 
@@ -585,10 +546,7 @@ int rvdd_green_estimate(rvdd_t* h, const float* packed, int32_t n, int32_t hh, i
     if (!std::isfinite(cfg->black)) return fail(h, RVDD_ERR_ARG, "%s: black must be finite, got %g", fn, cfg->black);
     RC(green_shape(h, fn, n, hh, ww, bit_depth, pattern));
     if (n == 0) return RVDD_OK;
-    if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
-    if (!e) return fail(h, RVDD_ERR_ARG, "%s: e is required", fn);
-    if (!level) return fail(h, RVDD_ERR_ARG, "%s: level is required", fn);
-    if (!state) return fail(h, RVDD_ERR_ARG, "%s: state is required", fn);
+    RC(need_ptrs(h, fn, {{packed, "packed"}, {e, "e"}, {level, "level"}, {state, "state"}}));
     if (green_estimate_blocks(n, hh, ww) < 0)
         return fail(h, RVDD_ERR_ARG, "%s: n = %d frames of %d x %d cells need a launch of more than 2^31 - 1 blocks", fn, n, hh, ww);
     ENTER(h);
@@ -610,10 +568,8 @@ int rvdd_green_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev
         return fail(h, RVDD_ERR_ARG, "%s: the map's grid gh x gw = %d x %d is neither 1 x 1 nor the %d x %d blocks of frames of %d x %d cells", fn, gh, gw,
                     fgh, fgw, hh, ww);
     if (n == 0) return RVDD_OK;
-    if (!packed) return fail(h, RVDD_ERR_ARG, "%s: packed is required", fn);
-    if (!map_dev) return fail(h, RVDD_ERR_ARG, "%s: map_dev is required", fn);
-    if (line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray), nullptr) < 0)
-        return fail(h, RVDD_ERR_ARG, "%s: n * hh * ww = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, n, hh, ww);
+    RC(need_ptrs(h, fn, {{packed, "packed"}, {map_dev, "map_dev"}}));
+    RC(need_blocks(h, fn, line_apply_blocks(n, hh, ww, line_apply_wide(ww, packed, gray), nullptr), "n * hh * ww", n, hh, ww));
     ENTER(h);
     return run_green_apply(h, packed, gray, map_dev, gh, gw, black, n, hh, ww, bit_depth, pattern, static_cast<hipStream_t>(stream));
 }
@@ -623,7 +579,7 @@ static int unprocess_shape(rvdd_t* h, const char* fn, int32_t n, int32_t H, int3
     if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2, got %d", fn, H);
     if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "%s: W must be even and >= 2, got %d", fn, W);
     if ((int64_t)H * W >= (1ll << 32)) return fail(h, RVDD_ERR_ARG, "%s: H * W must be below 2^32 (the draws count a frame's pixels in 32 bits), got %d x %d", fn, H, W);
-    if (n < 0) return fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n);
+    RC(need_count(h, fn, n));
     return RVDD_OK;
 }
 
@@ -632,11 +588,10 @@ int rvdd_unprocess(rvdd_t* h, const uint8_t* srgb, int32_t n, int32_t H, int32_t
                    uint16_t* lin_u16, float* gt_raw, float* noisy, void* stream) {
     if (!h) return RVDD_ERR_ARG;
     if (iso != 3200 && iso != 12800) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: iso must be 3200 or 12800, got %d", iso);
-    if (pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR)
-        return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", pattern);
+    RC(need_bayer(h, "rvdd_unprocess", pattern));
     RC(unprocess_shape(h, "rvdd_unprocess", n, H, W));
     if (n == 0) return RVDD_OK;
-    if (!srgb) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: srgb is required");
+    RC(need_ptr(h, "rvdd_unprocess", srgb, "srgb"));
     if (!(rgb_gain != 0.0) || !(red_gain != 0.0) || !(blue_gain != 0.0)) return fail(h, RVDD_ERR_ARG, "rvdd_unprocess: zero gain (rgb_gain, red_gain, blue_gain)");
     ENTER(h);
     // generate_raw_from_RGB.py:77: float32 tensors -- (1 / red_gain, 1, 1 / blue_gain) / rgb_gain, each quotient rounded to f32

@@ -1,5 +1,5 @@
 // Host side of librvdd_hip.so: the handle, the host types of both nets and of a frame-step, and the functions that cross
-// the host translation units (handle, net_convunet, net_convnext, step, stream, ops, profile).  Kernel files do not
+// the host translation units (handle, net_convunet, net_convnext, step, stream, stages, ops, profile).  Kernel files do not
 // include it: what they share with the host is rvdd_internal.h.  Nothing here is exported: the library's dynamic symbols
 // are the rvdd_ functions of include/rvdd.h alone (rvdd.map).
 #pragma once
@@ -328,6 +328,42 @@ inline uint64_t slots_below(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
 
 int fail(rvdd_t* h, int code, const char* fmt, ...);      // sets the handle's (h null: the thread's create) error string, returns code
 
+#define RC(expr)               \
+    do {                       \
+        int rc__ = (expr);     \
+        if (rc__) return rc__; \
+    } while (0)
+
+// The refusals the entry points of ops.hip, stream.hip and stages.hip share, each with the sentence its callers wrote out by hand before:
+// 0, or RVDD_ERR_ARG through fail().  A call site uses one only where this IS its sentence, byte for byte (tests/abi_refusals.cpp and
+// its golden hold every one); combined and differently worded refusals stay written out where they are.  `fn`: the entry point's name.
+inline int need_bit_depth(rvdd_t* h, const char* fn, int bit_depth) {
+    return bit_depth < 1 || bit_depth > 16 ? fail(h, RVDD_ERR_ARG, "%s: bit_depth must be 1..16, got %d", fn, bit_depth) : RVDD_OK;
+}
+inline int need_bayer(rvdd_t* h, const char* fn, int pattern) {
+    return pattern < RVDD_BAYER_GBRG || pattern > RVDD_BAYER_BGGR
+               ? fail(h, RVDD_ERR_ARG, "%s: pattern %d is not an rvdd_bayer (0 GBRG, 1 GRBG, 2 RGGB, 3 BGGR)", fn, pattern) : RVDD_OK;
+}
+inline int need_count(rvdd_t* h, const char* fn, int n) { return n < 0 ? fail(h, RVDD_ERR_ARG, "%s: n must be >= 0, got %d", fn, n) : RVDD_OK; }
+inline int need_ptr(rvdd_t* h, const char* fn, const void* p, const char* name) {
+    return p ? RVDD_OK : fail(h, RVDD_ERR_ARG, "%s: %s is required", fn, name);
+}
+// several of them, refused in the order given
+inline int need_ptrs(rvdd_t* h, const char* fn, std::initializer_list<std::pair<const void*, const char*>> ptrs) {
+    for (const auto& p : ptrs) RC(need_ptr(h, fn, p.first, p.second));
+    return RVDD_OK;
+}
+// `why`: the reason in the sentence's parentheses, or null for the sentence without them
+inline int need_min(rvdd_t* h, const char* fn, const char* name, int v, int least, const char* why = nullptr) {
+    if (v >= least) return RVDD_OK;
+    return why ? fail(h, RVDD_ERR_ARG, "%s: %s must be >= %d (%s), got %d", fn, name, least, why, v)
+               : fail(h, RVDD_ERR_ARG, "%s: %s must be >= %d, got %d", fn, name, least, v);
+}
+// the refusal of a launch over `product` (the caller's words, "n * hh * ww") of more than 2^31 - 1 blocks: `blocks` is the kernel's own count, -1 for that
+inline int need_blocks(rvdd_t* h, const char* fn, int64_t blocks, const char* product, int a, int b, int c) {
+    return blocks < 0 ? fail(h, RVDD_ERR_ARG, "%s: %s = %d * %d * %d needs a launch of more than 2^31 - 1 blocks", fn, product, a, b, c) : RVDD_OK;
+}
+
 #define ENTER(h)                                                                            \
     DeviceGuard guard__((h)->cfg.device);                                                   \
     if (guard__.err != hipSuccess)                                                          \
@@ -339,12 +375,6 @@ int fail(rvdd_t* h, int code, const char* fmt, ...);      // sets the handle's (
         if (e__ != hipSuccess)                                                              \
             return fail((h), RVDD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), \
                         __FILE__, __LINE__);                                                \
-    } while (0)
-
-#define RC(expr)               \
-    do {                       \
-        int rc__ = (expr);     \
-        if (rc__) return rc__; \
     } while (0)
 
 // the amax words (rvdd_internal.h) of map `slot`, from sequence b0 on
@@ -478,12 +508,18 @@ int run_prologue(rvdd_t* h, NetRun& run, Sub sb, hipStream_t s);
 int dpc_params(rvdd_t* h, const char* fn, const rvdd_dpc_cfg* cfg, DpcParams* out);
 // the checks rvdd_rows_estimate and rvdd_set_rows share: 0 and *out = the kernel's parameters, or RVDD_ERR_ARG with the field named
 int rows_params(rvdd_t* h, const char* fn, const rvdd_rows_cfg* cfg, RowsParams* out);
+// the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
+int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg);
+int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
+                   void* stream, bool async);
+// ---- stages.hip: the state of the stages of rvdd_video_push between its ingest and its output
+// do frames of hh x ww cells fit every stage as it is set (0, or the stage's refusal), and is the first-use storage of those that are on there
+int stages_fit(rvdd_t* h, int hh, int ww);
+// rvdd_set_rows' stage on slots [b, e): estimate and apply, each inside its profile class; `packed` and `gray` point at slot b
+int rows_run(rvdd_t* h, float* packed, float* gray, int b, int e, int hh, int ww, int bit_depth, hipStream_t s);
+void stages_free(rvdd_t* h);      // rvdd_destroy: the device maps the setters own
 // launch_cols_apply inside its profile class, for rvdd_cols_apply and the stage behind rvdd_set_cols: 0, or the HIP error on the handle
 int run_cols_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int n, int hh, int ww, int bit_depth, hipStream_t s);
 // launch_green_apply inside its profile class, for rvdd_green_apply and the stage behind rvdd_set_green: 0, or the HIP error on the handle
 int run_green_apply(rvdd_t* h, float* packed, float* gray, const float* map_dev, int gh, int gw, float black, int n, int hh, int ww, int bit_depth,
                     int bayer, hipStream_t s);
-// the checks rvdd_match_raw, rvdd_unmatch_rgb and rvdd_set_match share: 0, or RVDD_ERR_ARG with the field named
-int match_params(rvdd_t* h, const char* fn, const rvdd_match_cfg* cfg);
-int tvl1flow_batch(rvdd_t* h, const float* I0, const float* I1, float* u, int32_t n, int32_t nx, int32_t ny, int32_t* iterations,
-                   void* stream, bool async);

@@ -1,4 +1,5 @@
-// rvdd_video_push: raw frames in, denoised frames out -- ingest, flows and the step of every slot that has its frames.
+// rvdd_video_push: raw frames in, denoised frames out -- ring, control, ingest, flows and the step of every slot that has its frames.  The
+// stages between the ingest and the output are stages.hip's.
 #include "runtime_internal.h"
 
 extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int32_t layout, int32_t bit_depth, const uint8_t* ctl, float* out_rgb,
@@ -7,7 +8,7 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     if (dtype != RVDD_RAW_U16 && dtype != RVDD_RAW_F32) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: dtype must be 0 (u16) or 1 (f32), got %d", dtype);
     if (layout != RVDD_RAW_MOSAIC && layout != RVDD_RAW_PACKED_HWC)
         return fail(h, RVDD_ERR_ARG, "rvdd_video_push: layout must be 0 (mosaic) or 1 (packed HWC), got %d", layout);
-    if (bit_depth < 1 || bit_depth > 16) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: bit_depth must be 1..16, got %d", bit_depth);
+    RC(need_bit_depth(h, "rvdd_video_push", bit_depth));
     if (!frames || !out_rgb || !valid) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: frames, out_rgb and valid are required");
     const int B = h->cfg.batch, hh = h->cfg.height / 2, ww = h->cfg.width / 2, fut = h->cfg.future;
     // option "stream_container": the frames are packed bits, order container - 1 of enum rvdd_bits_order
@@ -52,45 +53,7 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     // option "stream_flow_from_denoised": the gray planes of the outputs, allocated by the first push that has it on
     const bool from_den = h->opt.stream_flow_from_denoised && !h->opt.no_warp;
     if (from_den && !st.dgray) RC(dmalloc(h, reinterpret_cast<void**>(&st.dgray), (size_t)B * hw * sizeof(float)));
-    // rvdd_set_dpc: the packed planes are ingested beside the ring and corrected into it; allocated by the first push that has the stage on
-    auto& dpc = h->dpc;
-    if (dpc.on && (hh < 2 || ww < 2)) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with rvdd_set_dpc hh and ww must be >= 2, got %d x %d cells", hh, ww);
-    if (dpc.on && !dpc.in) {
-        RC(dmalloc(h, reinterpret_cast<void**>(&dpc.counts), (size_t)B * 2 * sizeof(unsigned)));
-        RC(dmalloc(h, reinterpret_cast<void**>(&dpc.in), (size_t)B * 4 * hw * sizeof(float)));
-    }
-    // rvdd_set_dpc_map: the frames just ingested are corrected by the map in place, in front of rvdd_set_dpc's rule
-    const auto& dmap = h->dmap;
-    if (dmap.on && (dmap.hh != hh || dmap.ww != ww))
-        return fail(h, RVDD_ERR_ARG, "rvdd_video_push: the map of rvdd_set_dpc_map is one of %d x %d cells, the frames have %d x %d", dmap.hh, dmap.ww, hh, ww);
-    // rvdd_set_match: the ring's packed frames are mapped in place behind the ingest (and the correction), out_rgb is mapped back
-    const auto match = h->match;
-    // rvdd_set_resid: one accumulator per slot, allocated (zeroed) by the first push that has the stage on
-    auto& resid = h->resid;
-    if (resid.on && !resid.acc) RC(dmalloc(h, reinterpret_cast<void**>(&resid.acc), (size_t)B * sizeof(rvdd_resid_acc)));
-    // rvdd_set_rows: offsets, states and one accumulator per slot, allocated (zeroed) by the first push that has the stage on
-    auto& rows = h->rows;
-    if (rows.on && hh < 5) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with rvdd_set_rows hh must be >= 5, got %d cell rows", hh);
-    if (rows.on && ww > rows_max_ww()) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with rvdd_set_rows ww must be <= %d, got %d cells", rows_max_ww(), ww);
-    if (rows.on && !rows.acc) {
-        RC(dmalloc(h, reinterpret_cast<void**>(&rows.offsets), (size_t)B * 2 * hh * sizeof(float)));
-        RC(dmalloc(h, reinterpret_cast<void**>(&rows.state), (size_t)B * 2 * hh));
-        RC(dmalloc(h, reinterpret_cast<void**>(&rows.acc), (size_t)B * sizeof(rvdd_rows_acc)));      // last: the mark of a complete allocation
-    }
-    // rvdd_set_cols: the static column map is taken out of the ring's frames behind the correction; nothing is allocated here
-    const auto cols = h->cols;
-    if (cols.on && cols.ww != ww)
-        return fail(h, RVDD_ERR_ARG, "rvdd_video_push: the map of rvdd_set_cols is one of %d cell columns, the frames have %d", cols.ww, ww);
-    // rvdd_set_green: the static map of green gains is taken out behind the rows; nothing is allocated here
-    const auto green = h->geq;
-    if (green.on) {
-        if (hh < 2 || ww < 2) return fail(h, RVDD_ERR_ARG, "rvdd_video_push: with rvdd_set_green hh and ww must be >= 2, got %d x %d cells", hh, ww);
-        int gh, gw;
-        green_grid(hh, ww, &gh, &gw);
-        if (!(green.gh == 1 && green.gw == 1) && (green.gh != gh || green.gw != gw))
-            return fail(h, RVDD_ERR_ARG, "rvdd_video_push: the map of rvdd_set_green is one of %d x %d blocks, frames of %d x %d cells have %d x %d",
-                        green.gh, green.gw, hh, ww, gh, gw);
-    }
+    RC(stages_fit(h, hh, ww));      // the stages between the ingest and the output (stages.hip): each fits these frames as it is set, or refuses them
     // the whole ctl is judged before anything changes
     for (int b = 0; b < B; ++b)
         if ((ctl ? ctl[b] : RVDD_PUSH_NEXT) == RVDD_PUSH_NEXT && st.count[(size_t)b] == 0)
@@ -104,34 +67,22 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     RC(for_each_run(B, [&](int b) { return !(ctl && ctl[b] == RVDD_PUSH_IDLE); }, [&](int b, int e) -> int {
         float* ring_packed = st.packed + ((size_t)pos * B + b) * 4 * hw;
         float* ring_gray = st.gray + ((size_t)pos * B + b) * hw;
-        float* packed = dpc.on ? dpc.in + (size_t)b * 4 * hw : ring_packed;
+        float* packed = h->dpc.on ? h->dpc.in + (size_t)b * 4 * hw : ring_packed;      // rvdd_set_dpc corrects from beside the ring into it
         if (container)
             HIPCHK(h, launch_ingest_bits(static_cast<const uint8_t*>(frames) + (size_t)b * frame_bytes, container - 1, e - b, hh, ww, bit_depth,
                                          packed, ring_gray, s));
         else
             HIPCHK(h, launch_ingest_raw(static_cast<const char*>(frames) + (size_t)b * 4 * hw * esz, dtype, layout, e - b, hh, ww, bit_depth,
                                         packed, ring_gray, s));
-        if (dmap.on && dmap.ncells)
-            HIPCHK(h, launch_dpc_map_apply(packed, ring_gray, e - b, hh, ww, bit_depth, dmap.mask, dmap.cells, dmap.ncells, s));
-        if (dpc.on) HIPCHK(h, launch_dpc(packed, ring_packed, ring_gray, e - b, hh, ww, bit_depth, dpc.p, dpc.counts + 2 * (size_t)b, s));
-        // rvdd_set_cols: the static column offsets taken out of the ring's planes and gray planes in place: one launch
-        if (cols.on) RC(run_cols_apply(h, ring_packed, ring_gray, cols.map, e - b, hh, ww, bit_depth, s));
-        // rvdd_set_rows: the row offsets of the (corrected) frames estimated and taken out of the ring's planes and gray planes in place
-        if (rows.on) {
-            const double cells = (double)(e - b) * 4.0 * (double)hw;
-            {
-                Scope sc(h, s, "rows_estimate_kernel", 0.0, cells * 4.0);
-                HIPCHK(h, launch_rows_estimate(ring_packed, e - b, hh, ww, bit_depth, rows.p, rows.offsets + (size_t)b * 2 * hh,
-                                               rows.state + (size_t)b * 2 * hh, rows.acc + b, s));
-            }
-            Scope sc(h, s, "rows_apply_kernel", 0.0, cells * 8.0 + cells * 2.0);
-            HIPCHK(h, launch_rows_apply(ring_packed, ring_gray, rows.offsets + (size_t)b * 2 * hh, e - b, hh, ww, bit_depth, s));
-        }
-        // rvdd_set_green: the green gains taken out of the ring's two green planes and gray planes in place: one launch
-        if (green.on)
-            RC(run_green_apply(h, ring_packed, ring_gray, green.map, green.gh, green.gw, green.black, e - b, hh, ww, bit_depth, h->opt.bayer, s));
+        if (h->dmap.on && h->dmap.ncells)
+            HIPCHK(h, launch_dpc_map_apply(packed, ring_gray, e - b, hh, ww, bit_depth, h->dmap.mask, h->dmap.cells, h->dmap.ncells, s));
+        if (h->dpc.on) HIPCHK(h, launch_dpc(packed, ring_packed, ring_gray, e - b, hh, ww, bit_depth, h->dpc.p, h->dpc.counts + 2 * (size_t)b, s));
+        if (h->cols.on) RC(run_cols_apply(h, ring_packed, ring_gray, h->cols.map, e - b, hh, ww, bit_depth, s));
+        RC(rows_run(h, ring_packed, ring_gray, b, e, hh, ww, bit_depth, s));
+        if (h->geq.on)
+            RC(run_green_apply(h, ring_packed, ring_gray, h->geq.map, h->geq.gh, h->geq.gw, h->geq.black, e - b, hh, ww, bit_depth, h->opt.bayer, s));
         // the gray planes stay the sensor's: TV-L1 matches what it always matched
-        if (match.on) HIPCHK(h, launch_match(ring_packed, ring_packed, (int64_t)(e - b) * 4 * (int64_t)hw, match.cfg.scale, match.cfg.offset, false, s));
+        if (h->match.on) HIPCHK(h, launch_match(ring_packed, ring_packed, (int64_t)(e - b) * 4 * (int64_t)hw, h->match.cfg.scale, h->match.cfg.offset, false, s));
         return RVDD_OK;
     }));
     // Per slot: which frame of its video this push outputs (centre; -1: none).  The plain rule is centre = n - 1 - future >= 1.  Option
@@ -204,213 +155,19 @@ extern "C" int rvdd_video_push(rvdd_t* h, const void* frames, int32_t dtype, int
     RC(rvdd_step_strided(h, packed_at(pp), packed_at(pc), fut ? packed_at(pos) : nullptr, flow_prev, flow_next, 0, 0, out_rgb, stream));
     // rvdd_set_resid: the centre frames as the step read them against the outputs as it wrote them, before the way back: with the match
     // on both are in the network's domain, whose unit is the 12-bit DN of the checkpoint's curve
-    if (resid.on)
+    if (h->resid.on)
         RC(for_each_run(B, [&](int b) { return centre[(size_t)b] >= 0; }, [&](int b, int e) -> int {
             HIPCHK(h, launch_resid(packed_at(pc) + (size_t)b * 4 * hw, out_rgb + (size_t)b * 12 * hw, e - b, hh, ww, h->opt.bayer,
-                                   match.on ? 12 : bit_depth, resid.acc + b, s));
+                                   h->match.on ? 12 : bit_depth, h->resid.acc + b, s));
             return RVDD_OK;
         }));
     // every slot, ready or not: one launch; the recurrent state stays in the network's own domain
-    if (match.on) HIPCHK(h, launch_match(out_rgb, out_rgb, (int64_t)B * 12 * (int64_t)hw, match.cfg.scale, match.cfg.offset, true, s));
+    if (h->match.on) HIPCHK(h, launch_match(out_rgb, out_rgb, (int64_t)B * 12 * (int64_t)hw, h->match.cfg.scale, h->match.cfg.offset, true, s));
     if (from_den) {
         // the plane is taken from the output (with "prev_noisy_frame" lastden holds the noisy demosaic) inside the push that wrote it:
         // the caller may overwrite out_rgb before the next one
         HIPCHK(h, launch_gray_of_rgb(out_rgb, B, hh, ww, h->opt.bayer, bit_depth, st.dgray, s));
         for (int b : ready) st.dgray_ok[(size_t)b] = centre[(size_t)b] >= 1 && st.count[(size_t)b] > 0;      // not a head's, not a tail's
     }
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_set_dpc(rvdd_t* h, const rvdd_dpc_cfg* cfg) {
-    if (!h) return RVDD_ERR_ARG;
-    DpcParams p{};
-    if (cfg) RC(dpc_params(h, "rvdd_set_dpc", cfg, &p));
-    ENTER(h);
-    HIPCHK(h, hipDeviceSynchronize());      // pushes in flight keep the parameters they were enqueued with anyway; the counters must be at rest
-    auto& dpc = h->dpc;
-    if (cfg && !dpc.on) {                   // switched on: the totals start again
-        dpc.total.assign((size_t)h->cfg.batch * 2, 0);
-        if (dpc.counts) HIPCHK(h, hipMemset(dpc.counts, 0, (size_t)h->cfg.batch * 2 * sizeof(unsigned)));
-    }
-    dpc.on = cfg != nullptr;
-    if (cfg) dpc.p = p;
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_set_dpc_map(rvdd_t* h, const uint8_t* cellmask, int32_t hh, int32_t ww) {
-    if (!h) return RVDD_ERR_ARG;
-    std::vector<int> cells;
-    if (cellmask) {
-        if (hh < 3) return fail(h, RVDD_ERR_ARG, "rvdd_set_dpc_map: hh must be >= 3 (the second ring is reflected about the edge), got %d", hh);
-        if (ww < 3) return fail(h, RVDD_ERR_ARG, "rvdd_set_dpc_map: ww must be >= 3 (the second ring is reflected about the edge), got %d", ww);
-        if ((int64_t)hh * ww > 0x7fffffffll) return fail(h, RVDD_ERR_ARG, "rvdd_set_dpc_map: hh * ww = %d * %d must be below 2^31 (cell indices are 32-bit)", hh, ww);
-        const size_t hw = (size_t)hh * ww;
-        for (size_t i = 0; i < hw; ++i) {
-            if (cellmask[i] & 0xf0u)
-                return fail(h, RVDD_ERR_ARG, "rvdd_set_dpc_map: cellmask[%d][%d] = 0x%02x has a bit above the four planes' set", (int)(i / ww), (int)(i % ww),
-                            cellmask[i]);
-            if (cellmask[i]) cells.push_back((int)i);
-        }
-    }
-    ENTER(h);
-    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight read the map they were enqueued with
-    auto& m = h->dmap;
-    if (m.mask) HIPCHK(h, hipFree(m.mask));
-    m.mask = nullptr;
-    if (m.cells) HIPCHK(h, hipFree(m.cells));
-    m.cells = nullptr;
-    m.on = false;
-    m.ncells = 0;
-    if (!cellmask) return RVDD_OK;
-    if (!cells.empty()) {                   // an empty map is valid and owns nothing
-        const size_t hw = (size_t)hh * ww;
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&m.mask), hw));
-        HIPCHK(h, hipMemcpy(m.mask, cellmask, hw, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&m.cells), cells.size() * sizeof(int)));
-        HIPCHK(h, hipMemcpy(m.cells, cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    m.hh = hh;
-    m.ww = ww;
-    m.ncells = (int64_t)cells.size();
-    m.on = true;
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_set_match(rvdd_t* h, const rvdd_match_cfg* cfg) {
-    if (!h) return RVDD_ERR_ARG;
-    if (cfg) RC(match_params(h, "rvdd_set_match", cfg));
-    ENTER(h);
-    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight keep the coefficients they were enqueued with
-    h->match.on = cfg != nullptr;
-    if (cfg) h->match.cfg = *cfg;
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_set_cols(rvdd_t* h, const float* map_host, int32_t ww) {
-    if (!h) return RVDD_ERR_ARG;
-    if (map_host) {
-        if (ww < 5) return fail(h, RVDD_ERR_ARG, "rvdd_set_cols: ww must be >= 5, got %d", ww);
-        for (int64_t i = 0; i < 2 * (int64_t)ww; ++i)
-            if (!std::isfinite(map_host[i]))
-                return fail(h, RVDD_ERR_ARG, "rvdd_set_cols: map_host[%d][%d] = %g is not finite", (int)(i / ww), (int)(i % ww), (double)map_host[i]);
-    }
-    ENTER(h);
-    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc_map: pushes in flight read the map they were enqueued with
-    auto& c = h->cols;
-    if (c.map) HIPCHK(h, hipFree(c.map));
-    c.map = nullptr;
-    c.on = false;
-    c.ww = 0;
-    if (!map_host) return RVDD_OK;
-    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&c.map), 2 * (size_t)ww * sizeof(float)));
-    HIPCHK(h, hipMemcpy(c.map, map_host, 2 * (size_t)ww * sizeof(float), hipMemcpyHostToDevice));
-    c.ww = ww;
-    c.on = true;
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_set_green(rvdd_t* h, const float* map_host, int32_t gh, int32_t gw, float black) {
-    if (!h) return RVDD_ERR_ARG;
-    if (map_host) {
-        if (gh < 1) return fail(h, RVDD_ERR_ARG, "rvdd_set_green: gh must be >= 1, got %d", gh);
-        if (gw < 1) return fail(h, RVDD_ERR_ARG, "rvdd_set_green: gw must be >= 1, got %d", gw);
-        if (!std::isfinite(black)) return fail(h, RVDD_ERR_ARG, "rvdd_set_green: black must be finite, got %g", (double)black);
-        for (int64_t i = 0; i < (int64_t)gh * gw; ++i)
-            if (!std::isfinite(map_host[i]))
-                return fail(h, RVDD_ERR_ARG, "rvdd_set_green: map_host[%d][%d] = %g is not finite", (int)(i / gw), (int)(i % gw), (double)map_host[i]);
-    }
-    ENTER(h);
-    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_cols: pushes in flight read the map they were enqueued with
-    auto& g = h->geq;
-    if (g.map) HIPCHK(h, hipFree(g.map));
-    g.map = nullptr;
-    g.on = false;
-    g.gh = g.gw = 0;
-    if (!map_host) return RVDD_OK;
-    const size_t bytes = (size_t)gh * (size_t)gw * sizeof(float);
-    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&g.map), bytes));
-    HIPCHK(h, hipMemcpy(g.map, map_host, bytes, hipMemcpyHostToDevice));
-    g.gh = gh;
-    g.gw = gw;
-    g.black = black;
-    g.on = true;
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_set_rows(rvdd_t* h, const rvdd_rows_cfg* cfg) {
-    if (!h) return RVDD_ERR_ARG;
-    RowsParams p{};
-    if (cfg) RC(rows_params(h, "rvdd_set_rows", cfg, &p));
-    ENTER(h);
-    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: pushes in flight keep the parameters they were enqueued with; the accumulators must be at rest
-    auto& rows = h->rows;
-    if (cfg && !rows.on && rows.acc) HIPCHK(h, hipMemset(rows.acc, 0, (size_t)h->cfg.batch * sizeof(rvdd_rows_acc)));      // switched on: from zero
-    rows.on = cfg != nullptr;
-    if (cfg) rows.p = p;
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_rows_read(rvdd_t* h, int32_t slot, rvdd_rows_acc* host_out, void* stream) {
-    if (!h) return RVDD_ERR_ARG;
-    if (!host_out) return fail(h, RVDD_ERR_ARG, "rvdd_rows_read: host_out is required");
-    if (slot < 0 || slot >= h->cfg.batch) return fail(h, RVDD_ERR_ARG, "rvdd_rows_read: slot must be 0 .. %d, got %d", h->cfg.batch - 1, slot);
-    ENTER(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto& rows = h->rows;
-    if (rows.acc) {
-        HIPCHK(h, hipMemcpyAsync(host_out, rows.acc + slot, sizeof(rvdd_rows_acc), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemsetAsync(rows.acc + slot, 0, sizeof(rvdd_rows_acc), s));
-    } else {
-        std::memset(host_out, 0, sizeof(rvdd_rows_acc));
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_set_resid(rvdd_t* h, int32_t on) {
-    if (!h) return RVDD_ERR_ARG;
-    ENTER(h);
-    HIPCHK(h, hipDeviceSynchronize());      // as rvdd_set_dpc: the accumulators must be at rest
-    auto& resid = h->resid;
-    if (on && !resid.on && resid.acc) HIPCHK(h, hipMemset(resid.acc, 0, (size_t)h->cfg.batch * sizeof(rvdd_resid_acc)));      // switched on: from zero
-    resid.on = on != 0;
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_resid_read(rvdd_t* h, int32_t slot, rvdd_resid_acc* host_out, void* stream) {
-    if (!h) return RVDD_ERR_ARG;
-    if (!host_out) return fail(h, RVDD_ERR_ARG, "rvdd_resid_read: host_out is required");
-    if (slot < 0 || slot >= h->cfg.batch) return fail(h, RVDD_ERR_ARG, "rvdd_resid_read: slot must be 0 .. %d, got %d", h->cfg.batch - 1, slot);
-    ENTER(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto& resid = h->resid;
-    if (resid.acc) {
-        HIPCHK(h, hipMemcpyAsync(host_out, resid.acc + slot, sizeof(rvdd_resid_acc), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemsetAsync(resid.acc + slot, 0, sizeof(rvdd_resid_acc), s));
-    } else {
-        std::memset(host_out, 0, sizeof(rvdd_resid_acc));
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
-    return RVDD_OK;
-}
-
-extern "C" int rvdd_dpc_counts(rvdd_t* h, uint64_t* hot_dead, void* stream) {
-    if (!h) return RVDD_ERR_ARG;
-    if (!hot_dead) return fail(h, RVDD_ERR_ARG, "rvdd_dpc_counts: hot_dead is required");
-    ENTER(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto& dpc = h->dpc;
-    const size_t n = (size_t)h->cfg.batch * 2;
-    dpc.total.resize(n, 0);
-    if (dpc.counts) {                       // fold what the device counted since the last call into the totals, and start it at zero
-        std::vector<unsigned> got(n, 0);
-        HIPCHK(h, hipMemcpyAsync(got.data(), dpc.counts, n * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemsetAsync(dpc.counts, 0, n * sizeof(unsigned), s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        for (size_t i = 0; i < n; ++i) dpc.total[i] += got[i];
-    } else {
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
-    for (size_t i = 0; i < n; ++i) hot_dead[i] = dpc.total[i];
     return RVDD_OK;
 }

@@ -133,13 +133,20 @@ def _host_bytes(x, struct, message: str, n: Optional[int] = None):
     return raw.reshape(-1)
 
 
+def _host_map(x, dtype: Optional[str] = None, what: Optional[str] = None, shape: Tuple = ()):
+    """x -- a NumPy array or a tensor (a device tensor is copied, which synchronises) -- as a contiguous host array.  With `what`, the
+    caller's sentence: RuntimeError(`what`, got <dtype> <shape>) unless it is of `dtype` and of `shape` (None: any size along that axis)."""
+    import numpy as np
+    m = np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+    if what is not None and (m.dtype != np.dtype(dtype) or m.ndim != len(shape) or any(want not in (None, got) for want, got in zip(shape, m.shape))):
+        raise RuntimeError(f"{what}, got {m.dtype} {m.shape}")
+    return m
+
+
 def dpc_map_stats(cellmask) -> Dict[str, int]:
     """{"samples", "cells", "unfixable"} of a map uint8 [hh,ww] (rvdd_dpc_map_stats: on the host, no GPU needed): its defective
     samples and cells, and the samples no ring of which has a good site -- `dpc_map_apply` leaves those as they are."""
-    import numpy as np
-    m = np.ascontiguousarray(cellmask)
-    if m.ndim != 2 or m.dtype != np.uint8:
-        raise RuntimeError(f"dpc_map_stats: cellmask is uint8 [hh,ww], got {m.dtype} {m.shape}")
+    m = _host_map(cellmask, "uint8", "dpc_map_stats: cellmask is uint8 [hh,ww]", (None, None))
     out = (C.c_int64 * 3)()
     _host_call("rvdd_dpc_map_stats", m.ctypes.data, m.shape[0], m.shape[1], out)
     return {"samples": int(out[0]), "cells": int(out[1]), "unfixable": int(out[2])}
@@ -304,8 +311,7 @@ def cols_fit(offsets, state, min_frames: int, k_sig: float = 3.0, max_dn: float 
     -> (map float32 [2,ww] in DN, mstate uint8 [2,ww]: 0 unsupported, 1 applied, 2 applied and clamped, 3 insignificant,
     stats {"unsupported", "applied", "clamped", "insignificant", "sum_q2": ints; "floor_dn": float})."""
     import numpy as np
-    o = np.ascontiguousarray(offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else offsets)
-    st = np.ascontiguousarray(state.detach().cpu().numpy() if torch.is_tensor(state) else state)
+    o, st = _host_map(offsets), _host_map(state)
     if o.ndim != 3 or o.shape[1] != 2 or o.dtype != np.float32 or st.shape != o.shape or st.dtype != np.uint8:
         raise RuntimeError(f"cols_fit: offsets is float32 [F,2,ww] and state uint8 [F,2,ww], got {o.dtype} {o.shape} and {st.dtype} {st.shape}")
     F, _, ww = o.shape
@@ -344,8 +350,7 @@ def green_fit(e, level, state, black: float, min_frames: int, k_sig: float = 3.0
     applied and clamped, 3 insignificant, stats {"unsupported", "applied", "clamped", "insignificant", "sum_q2": ints; "floor",
     "flat_gain", "flat_se": floats; "flat_state": int})."""
     import numpy as np
-    host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t)
-    e, level, st = host(e), host(level), host(state)
+    e, level, st = _host_map(e), _host_map(level), _host_map(state)
     if e.ndim != 3 or e.dtype != np.float32 or level.shape != e.shape or level.dtype != np.float32 or st.shape != e.shape or st.dtype != np.uint8:
         raise RuntimeError(f"green_fit: e and level are float32 [F,gh,gw] and state uint8 [F,gh,gw], got {e.dtype} {e.shape}, "
                            f"{level.dtype} {level.shape} and {st.dtype} {st.shape}")
@@ -551,6 +556,25 @@ class RvddRuntime:
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self._tdev).cuda_stream
+
+    def _set_cfg(self, name: str, cfg):
+        """a stage's setter `name` with its struct, or NULL for None = off"""
+        self._check(getattr(self.lib, name)(self.h, None if cfg is None else C.byref(cfg)), name)
+
+    def _slot_read(self, name: str, struct, slot: int):
+        """the reader `name` of a stage's per-slot accumulator -> the host copy of slot `slot`'s, which the call zeroes on the device"""
+        host = struct()
+        self._check(getattr(self.lib, name)(self.h, int(slot), C.byref(host), self._stream()), name)
+        return host
+
+    def _in_place(self, who: str, packed, gray, between=None):
+        """packed [n,4,hh,ww] and gray [n,hh,ww] (or None) of a call that writes both where they lie: contiguous, on this device.
+        between(n, hh, ww): the caller's check of its own tensor, made between the two as it always was -> (packed, n, hh, ww, its result)"""
+        packed, n, hh, ww = _frames(packed, 4, f"{who}: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
+        mine = between(n, hh, ww) if between else None
+        if gray is not None:
+            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
+        return packed, n, hh, ww, mine
 
     def _pattern(self, pattern: Optional[str], who: str) -> int:
         """enum rvdd_bayer of one of BAYER_PATTERNS; None = the pattern set_option("bayer_pattern", ...) gave this runtime"""
@@ -779,18 +803,13 @@ class RvddRuntime:
         if cellmask is None:
             self._check(self.lib.rvdd_set_dpc_map(self.h, None, 0, 0), "rvdd_set_dpc_map")
             return
-        import numpy as np
-        m = np.ascontiguousarray(cellmask.cpu().numpy() if torch.is_tensor(cellmask) else cellmask)
-        if m.ndim != 2 or m.dtype != np.uint8:
-            raise RuntimeError(f"set_dpc_map: cellmask is uint8 [hh,ww], got {m.dtype} {m.shape}")
+        m = _host_map(cellmask, "uint8", "set_dpc_map: cellmask is uint8 [hh,ww]", (None, None))
         self._check(self.lib.rvdd_set_dpc_map(self.h, m.ctypes.data, m.shape[0], m.shape[1]), "rvdd_set_dpc_map")
 
     def dpc_map_apply(self, packed: torch.Tensor, bit_depth: int = 12, gray: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Packed frames [n,4,hh,ww] corrected by the handle's map IN PLACE (rvdd_dpc_map_apply), gray [n,hh,ww] re-formed at the
         map's cells.  -> packed.  Both must be contiguous: they are written where they lie.  Nothing is synchronised."""
-        packed, n, hh, ww = _frames(packed, 4, "dpc_map_apply: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
-        if gray is not None:
-            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
+        packed, n, hh, ww, _ = self._in_place("dpc_map_apply", packed, gray)
         self._check(self.lib.rvdd_dpc_map_apply(self.h, _ptr(packed), _ptr(gray), n, hh, ww, int(bit_depth), self._stream()),
                     "rvdd_dpc_map_apply")
         return packed
@@ -847,7 +866,7 @@ class RvddRuntime:
         """The map as a stage of `video_push` (rvdd_set_match): the kept packed frames are mapped behind the ingest (and the
         correction of `set_dpc`), the outputs mapped back; flows are still matched on the sensor's own gray planes.
         cfg = `match_cfg(...)`, None = off (the default)."""
-        self._check(self.lib.rvdd_set_match(self.h, None if cfg is None else C.byref(cfg)), "rvdd_set_match")
+        self._set_cfg("rvdd_set_match", cfg)
 
     # -- denoised footage checked without ground truth ---------------------------------------
     def resid_stats(self, packed: torch.Tensor, rgb: torch.Tensor, bit_depth: int = 12, pattern: Optional[str] = None,
@@ -874,9 +893,7 @@ class RvddRuntime:
 
     def resid_read(self, slot: int):
         """Slot `slot`'s accumulator as `resid_acc_arrays` gives one ([1,64] arrays), zeroed on the device (rvdd_resid_read; synchronises)."""
-        host = _lib.RvddResidAcc()
-        self._check(self.lib.rvdd_resid_read(self.h, int(slot), C.byref(host), self._stream()), "rvdd_resid_read")
-        return resid_acc_arrays(host)
+        return resid_acc_arrays(self._slot_read("rvdd_resid_read", _lib.RvddResidAcc, slot))
 
     # -- row noise ------------------------------------------------------------------------------
     def rows_estimate(self, packed: torch.Tensor, cfg, bit_depth: int = 12, acc: Optional[torch.Tensor] = None):
@@ -896,11 +913,8 @@ class RvddRuntime:
     def rows_apply(self, packed: torch.Tensor, offsets: torch.Tensor, bit_depth: int = 12, gray: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`offsets` [n,2,hh] taken out of packed frames [n,4,hh,ww] IN PLACE (rvdd_rows_apply), gray [n,hh,ww] re-formed in the rows
         with a non-zero offset.  -> packed.  Both must be contiguous: they are written where they lie.  Nothing is synchronised."""
-        packed, n, hh, ww = _frames(packed, 4, "rows_apply: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
-        offsets = _dev_tensor(offsets, "offsets", self.device, shape=(n, 2, hh),
-                              form=f"rows_apply: offsets is a float32 tensor [{n},2,{hh}], as rows_estimate gives it")
-        if gray is not None:
-            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
+        packed, n, hh, ww, offsets = self._in_place("rows_apply", packed, gray, lambda n, hh, ww: _dev_tensor(
+            offsets, "offsets", self.device, shape=(n, 2, hh), form=f"rows_apply: offsets is a float32 tensor [{n},2,{hh}], as rows_estimate gives it"))
         self._check(self.lib.rvdd_rows_apply(self.h, _ptr(packed), _ptr(gray), _ptr(offsets), n, hh, ww, int(bit_depth), self._stream()),
                     "rvdd_rows_apply")
         return packed
@@ -908,13 +922,11 @@ class RvddRuntime:
     def set_rows(self, cfg=None):
         """The row-noise correction as a stage of `video_push`, behind `set_dpc` and in front of `set_match` (rvdd_set_rows): cfg =
         `rows_cfg(...)`, the sensor's own curve in DN of the pushes' bit depth; None = off (the default).  Synchronises the device."""
-        self._check(self.lib.rvdd_set_rows(self.h, None if cfg is None else C.byref(cfg)), "rvdd_set_rows")
+        self._set_cfg("rvdd_set_rows", cfg)
 
     def rows_read(self, slot: int):
         """Slot `slot`'s accumulator as `rows_acc_arrays` gives one ([1] arrays), zeroed on the device (rvdd_rows_read; synchronises)."""
-        host = _lib.RvddRowsAcc()
-        self._check(self.lib.rvdd_rows_read(self.h, int(slot), C.byref(host), self._stream()), "rvdd_rows_read")
-        return rows_acc_arrays(host)
+        return rows_acc_arrays(self._slot_read("rvdd_rows_read", _lib.RvddRowsAcc, slot))
 
     # -- column fixed-pattern noise -------------------------------------------------------------
     def cols_estimate(self, packed: torch.Tensor, cfg, bit_depth: int = 12):
@@ -932,10 +944,8 @@ class RvddRuntime:
         """The map `cmap` (a device float32 tensor [2,ww], DN of `bit_depth`) taken out of packed frames [n,4,hh,ww] IN PLACE
         (rvdd_cols_apply), gray [n,hh,ww] re-formed in the columns with a non-zero offset.  -> packed.  Both must be contiguous: they
         are written where they lie.  Nothing is synchronised."""
-        packed, n, hh, ww = _frames(packed, 4, "cols_apply: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
-        cmap = _dev_tensor(cmap, "cmap", self.device, shape=(2, ww), form=f"cols_apply: cmap is a float32 tensor [2,{ww}], as cols_fit gives it")
-        if gray is not None:
-            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
+        packed, n, hh, ww, cmap = self._in_place("cols_apply", packed, gray, lambda n, hh, ww: _dev_tensor(
+            cmap, "cmap", self.device, shape=(2, ww), form=f"cols_apply: cmap is a float32 tensor [2,{ww}], as cols_fit gives it"))
         self._check(self.lib.rvdd_cols_apply(self.h, _ptr(packed), _ptr(gray), _ptr(cmap), n, hh, ww, int(bit_depth), self._stream()),
                     "rvdd_cols_apply")
         return packed
@@ -947,10 +957,7 @@ class RvddRuntime:
         if cmap is None:
             self._check(self.lib.rvdd_set_cols(self.h, None, 0), "rvdd_set_cols")
             return
-        import numpy as np
-        m = np.ascontiguousarray(cmap.cpu().numpy() if torch.is_tensor(cmap) else cmap)
-        if m.ndim != 2 or m.shape[0] != 2 or m.dtype != np.float32:
-            raise RuntimeError(f"set_cols: cmap is float32 [2,ww], got {m.dtype} {m.shape}")
+        m = _host_map(cmap, "float32", "set_cols: cmap is float32 [2,ww]", (2, None))
         self._check(self.lib.rvdd_set_cols(self.h, m.ctypes.data, m.shape[1]), "rvdd_set_cols")
 
     # -- green imbalance ------------------------------------------------------------------------
@@ -973,10 +980,8 @@ class RvddRuntime:
         """The gains `gmap` (a device float32 tensor [gh,gw]: the frames' own grid, or [1,1] for a flat gain) taken out of the two
         green planes of packed frames [n,4,hh,ww] IN PLACE (rvdd_green_apply), gray [n,hh,ww] re-formed in the cells with a
         non-zero gain.  -> packed.  Both must be contiguous: they are written where they lie.  Nothing is synchronised."""
-        packed, n, hh, ww = _frames(packed, 4, "green_apply: packed is [n,4,hh,ww]", "packed", self.device, contiguous="require")
-        gmap = _dev_tensor(gmap, "gmap", self.device, shape=(None, None), form="green_apply: gmap is a float32 tensor [gh,gw], as green_fit gives it")
-        if gray is not None:
-            _dev_tensor(gray, "gray", self.device, shape=(n, hh, ww), contiguous="require")
+        packed, n, hh, ww, gmap = self._in_place("green_apply", packed, gray, lambda n, hh, ww: _dev_tensor(
+            gmap, "gmap", self.device, shape=(None, None), form="green_apply: gmap is a float32 tensor [gh,gw], as green_fit gives it"))
         self._check(self.lib.rvdd_green_apply(self.h, _ptr(packed), _ptr(gray), _ptr(gmap), gmap.shape[0], gmap.shape[1], float(black), n, hh, ww,
                                               int(bit_depth), self._pattern(pattern, "green_apply"), self._stream()), "rvdd_green_apply")
         return packed
@@ -988,16 +993,13 @@ class RvddRuntime:
         if gmap is None:
             self._check(self.lib.rvdd_set_green(self.h, None, 0, 0, 0.0), "rvdd_set_green")
             return
-        import numpy as np
-        m = np.ascontiguousarray(gmap.cpu().numpy() if torch.is_tensor(gmap) else gmap)
-        if m.ndim != 2 or m.dtype != np.float32:
-            raise RuntimeError(f"set_green: gmap is float32 [gh,gw], got {m.dtype} {m.shape}")
+        m = _host_map(gmap, "float32", "set_green: gmap is float32 [gh,gw]", (None, None))
         self._check(self.lib.rvdd_set_green(self.h, m.ctypes.data, m.shape[0], m.shape[1], float(black)), "rvdd_set_green")
 
     def set_dpc(self, cfg=None):
         """The correction as a stage of `video_push`, between the ingest and the kept frames (rvdd_set_dpc): cfg = `dpc_cfg(...)`,
         None = off (the default)."""
-        self._check(self.lib.rvdd_set_dpc(self.h, None if cfg is None else C.byref(cfg)), "rvdd_set_dpc")
+        self._set_cfg("rvdd_set_dpc", cfg)
 
     def dpc_counts(self) -> List[Tuple[int, int]]:
         """[(hot, dead)] * B: the samples the stage corrected per slot since it was last switched on (rvdd_dpc_counts; synchronises)."""

@@ -5,6 +5,7 @@ callers' `pytest.raises(..., match=...)` across the suite keep matching.
 The checkers never touch a tensor's data, so a host tensor that SAYS it lives on cuda:k serves for every check behind the first."""
 import types
 
+import numpy as np
 import pytest
 import torch
 
@@ -30,6 +31,9 @@ def cuda(*shape, dtype=torch.float32, cls=OnCuda):
 
 TDEV = torch.device("cuda", 0)
 NO_GPU = r"must be a GPU tensor \(rvdd has no CPU path\)"
+# an RvddRuntime as far as the argument checks of its methods go
+ME = types.SimpleNamespace(device=0)
+ME._in_place = types.MethodType(R.RvddRuntime._in_place, ME)
 CASES = [
     # not a tensor, and a tensor on the host
     ("chk-none", lambda: R._dev_tensor(None, "rgb", 0), RuntimeError, "rgb " + NO_GPU),
@@ -98,6 +102,26 @@ CASES = [
     ("raw-layout", lambda: R._raw_frames(cuda(1, 4, 4), "chw", "ingest_raw", 0), ValueError, "ingest_raw: layout 'chw' is not one of mosaic, packed_hwc"),
     ("egress-dtype", lambda: R.RvddRuntime.egress(types.SimpleNamespace(_pattern=lambda pattern, who: 0), cuda(2, 3, 6, 10), "mosaic", torch.float16),
      RuntimeError, r"egress: dtype must be torch.uint16 \(or torch.int16, its view\) or torch.float32, got torch.float16"),
+    # host maps for the setters and the host-only calls: dtype, rank, a fixed first dimension; arrays and CPU tensors alike
+    ("map-dtype", lambda: R._host_map(np.zeros((4, 6), np.int32), "uint8", "set_dpc_map: cellmask is uint8 [hh,ww]", (None, None)), RuntimeError,
+     r"set_dpc_map: cellmask is uint8 \[hh,ww\], got int32 \(4, 6\)"),
+    ("map-rank", lambda: R._host_map(torch.zeros(2, 4, 6, dtype=torch.uint8), "uint8", "dpc_map_stats: cellmask is uint8 [hh,ww]", (None, None)),
+     RuntimeError, r"dpc_map_stats: cellmask is uint8 \[hh,ww\], got uint8 \(2, 4, 6\)"),
+    ("map-rows", lambda: R._host_map(np.zeros((3, 8), np.float32), "float32", "set_cols: cmap is float32 [2,ww]", (2, None)), RuntimeError,
+     r"set_cols: cmap is float32 \[2,ww\], got float32 \(3, 8\)"),
+    ("map-f64", lambda: R._host_map(torch.zeros(2, 3, dtype=torch.float64), "float32", "set_green: gmap is float32 [gh,gw]", (None, None)), RuntimeError,
+     r"set_green: gmap is float32 \[gh,gw\], got float64 \(2, 3\)"),
+    ("map-stats", lambda: R.dpc_map_stats(np.zeros(16, np.uint8)), RuntimeError, r"dpc_map_stats: cellmask is uint8 \[hh,ww\], got uint8 \(16,\)"),
+    # wrong twice: the tensor between packed and gray is named first, as before the preamble was shared
+    ("in-place-order-rows", lambda: R.RvddRuntime.rows_apply(ME, cuda(1, 4, 6, 8), cuda(1, 2, 5), gray=cuda(1, 6, 9)), RuntimeError,
+     r"rows_apply: offsets is a float32 tensor \[1,2,6\]"),
+    ("in-place-order-cols", lambda: R.RvddRuntime.cols_apply(ME, cuda(1, 4, 6, 8), cuda(2, 7), gray=cuda(1, 6, 9)), RuntimeError,
+     r"cols_apply: cmap is a float32 tensor \[2,8\]"),
+    ("in-place-order-green", lambda: R.RvddRuntime.green_apply(ME, cuda(1, 4, 6, 8), cuda(3), 64.0, gray=cuda(1, 6, 9)), RuntimeError,
+     r"green_apply: gmap is a float32 tensor \[gh,gw\]"),
+    ("in-place-gray", lambda: R.RvddRuntime.rows_apply(ME, cuda(1, 4, 6, 8), cuda(1, 2, 6), gray=cuda(1, 6, 9)), RuntimeError, "gray"),
+    ("map-fit", lambda: R.cols_fit(np.zeros((3, 2, 8), np.float32), np.zeros((3, 2, 8), np.float32), 1), RuntimeError,
+     r"cols_fit: offsets is float32 \[F,2,ww\] and state uint8 \[F,2,ww\], got float32 \(3, 2, 8\) and float32 \(3, 2, 8\)"),
 ]
 
 
@@ -108,6 +132,10 @@ def test_a_bad_argument_is_refused_with_the_message_its_callers_match(call, exc,
 
 
 def test_good_arguments_pass_and_come_back_dense():
+    m = np.arange(24, dtype=np.float32).reshape(2, 12)
+    assert R._host_map(m, "float32", "m", (2, None)) is m and R._host_map(m[:, ::2]).flags["C_CONTIGUOUS"]
+    assert np.array_equal(R._host_map(torch.from_numpy(m), "float32", "m", (None, 12)), m)
+    assert np.array_equal(R._host_map(torch.from_numpy(m).requires_grad_(), "float32", "m", (2, 12)), m)      # detached: accepted, never refused
     t = cuda(2, 4, 3, 5)
     assert R._dev_tensor(t, "t", 0, shape=(2, 4, 3, 5)) is t and R._dev_tensor(t, "t", None) is t
     assert R._dev_tensor(t, "t", 0, shape=(None, 4, None, 5)) is t
