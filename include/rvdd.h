@@ -1125,6 +1125,26 @@ int rvdd_ppipe(rvdd_t* h, const float* img, int32_t n, int32_t height, int32_t w
                int64_t stride_c, int64_t stride_y, int64_t stride_x, int32_t bit_depth, double rgb_gain,
                double red_gain, double blue_gain, int32_t iso, uint8_t* out_u8, float* out_f32, void* stream);
 
+/* Display images as frames of a Y'CbCr 4:2:0 video: BT.709, limited range, chroma a box average of each 2 x 2 quad (centre-sited,
+ * the `420jpeg` siting of Y4M), 8 or 10 bits.  Integer after ONE quantisation, so that it is held bit for bit (tests/ycbcr_ref.py):
+ *   disp     [n,H,W,3] float32 display values d nominally in [0,255] -- what rvdd_ppipe writes to out_f32; H, W even;
+ *   depth    D = 8 or 10; m = 2^(D-8); K = 65535 * 16384;
+ *   q_c      = (int) rintf(min(max(d_c, 0), 255) * 257.0f) in 0 .. 65535: one f32 product, rounded half to even; a NaN gives 0;
+ *   luma, per pixel:      L  = 3483 q_r + 11718 q_g + 1183 q_b (the coefficients sum to 16384),
+ *                         Y  = 16 m + floor((L * 219 m + K / 2) / K);
+ *   chroma, per 2 x 2 quad, s_c = the sum of its four q_c:
+ *                         cb = -1877 s_r - 6315 s_g + 8192 s_b,   cr = 8192 s_r - 7441 s_g - 751 s_b (each row sums to 0),
+ *                         Cb = 128 m + floor((cb * 224 m + 2 K) / (4 K)), Cr likewise: floor division of a signed 64-bit numerator;
+ *   frames   [n, H*W*3/2] samples, uint8 (D = 8) or little-endian uint16 (D = 10): per image one Y4M frame body, the Y plane
+ *            [H,W], then Cb, then Cr, [H/2,W/2] each.
+ * White is 235 m, black 16 m, any grey has Cb = Cr = 128 m, pure blue Cb = 240 m, exactly; against the real-valued BT.709 formula
+ * every sample lies within 0.5 + 0.09 codes (three 14-bit coefficient roundings, 3 * 2^-15 * 876 = 0.08, and the 16-bit input
+ * quantisation, 0.007).  n = 0 does nothing and accepts NULL pointers.  RVDD_ERR_ARG, the argument named: odd or non-positive H
+ * or W, a depth other than 8 or 10, n < 0, a NULL disp or frames with n > 0, a launch of more than 2^31 - 1 blocks.
+ * Asynchronous and stream-ordered; reads nothing back. */
+int rvdd_ycbcr(rvdd_t* h, const float* disp /* [n,H,W,3] */, int32_t n, int32_t H, int32_t W, int32_t depth /* 8 | 10 */,
+               void* frames /* [n, H*W*3/2] uint8 | uint16 */, void* stream);
+
 /* dataset/fwd_ppipe.py `psnr(img1, img2)` (:79-84) and `ssim` (:86, skimage.metrics.structural_similarity with
  * multichannel=True, data_range=255: 7x7 uniform window, sample covariance, 3-pixel border cropped) on uint8
  * [n,H,W,3] images.  psnr / ssim: HOST arrays of n doubles (either may be NULL).  H, W >= 7.  Synchronous. */

@@ -187,6 +187,7 @@ _PROTOS = {
     "rvdd_unprocess_draws": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "rvdd_ppipe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                              C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P]),
+    "rvdd_ycbcr": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvdd_srgb_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), _P]),
     "rvdd_profile_enable": (C.c_int, [_P, C.c_int32]),

@@ -210,6 +210,21 @@ int rvdd_ppipe(rvdd_t* h, const float* img, int32_t n, int32_t H, int32_t W, int
     return RVDD_OK;
 }
 
+int rvdd_ycbcr(rvdd_t* h, const float* disp, int32_t n, int32_t H, int32_t W, int32_t depth, void* frames, void* stream) {
+    const char* fn = "rvdd_ycbcr";
+    if (!h) return RVDD_ERR_ARG;
+    if (depth != 8 && depth != 10) return fail(h, RVDD_ERR_ARG, "%s: depth must be 8 or 10, got %d", fn, depth);
+    if (H < 2 || (H & 1)) return fail(h, RVDD_ERR_ARG, "%s: H must be even and >= 2 (chroma is one sample per 2 x 2 quad), got %d", fn, H);
+    if (W < 2 || (W & 1)) return fail(h, RVDD_ERR_ARG, "%s: W must be even and >= 2 (chroma is one sample per 2 x 2 quad), got %d", fn, W);
+    RC(need_count(h, fn, n));
+    if (n == 0) return RVDD_OK;
+    RC(need_ptrs(h, fn, {{disp, "disp"}, {frames, "frames"}}));
+    RC(need_blocks(h, fn, ycbcr_blocks(n, H, W, ycbcr_wide(disp, W, frames)), "n * H * W", n, H, W));
+    ENTER(h);
+    HIPCHK(h, launch_ycbcr(disp, n, H, W, depth, frames, static_cast<hipStream_t>(stream)));
+    return RVDD_OK;
+}
+
 int rvdd_srgb_metrics(rvdd_t* h, const uint8_t* a, const uint8_t* b, int32_t n, int32_t H, int32_t W, double* psnr,
                       double* ssim, void* stream) {
     if (!h || !a || !b || n < 1) return fail(h, RVDD_ERR_ARG, "rvdd_srgb_metrics: bad argument");

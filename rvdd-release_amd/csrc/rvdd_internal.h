@@ -360,6 +360,14 @@ hipError_t launch_ppipe(const float* img, int n, int H, int W, int64_t sn, int64
 size_t srgb_metrics_workspace(int n, int H, int W);
 hipError_t launch_srgb_metrics(const uint8_t* a, const uint8_t* b, int n, int H, int W, void* ws, hipStream_t s);
 
+// ycbcr.hip -- display images as frames of a Y'CbCr 4:2:0 video (rvdd_ycbcr; the rule: include/rvdd.h)
+// disp [n][H][W][3] display values (launch_ppipe's out_f32) -> frames [n][H*W*3/2] samples, uint8 (depth 8) or uint16 (depth 10): per
+// image the Y plane [H][W], then Cb, then Cr [H/2][W/2].  H, W even and >= 2; n <= 0 launches nothing
+hipError_t launch_ycbcr(const float* disp, int n, int H, int W, int depth, void* frames, hipStream_t s);
+// whether that launch takes the wide form (a thread owns two rows of eight pixels), and its grid; -1 = more than 2^31 - 1 blocks
+bool ycbcr_wide(const float* disp, int W, const void* frames);
+int64_t ycbcr_blocks(int n, int H, int W, bool wide);
+
 // ingest.hip -- sensor frames to the inputs of a step and of TV-L1 (rvdd_ingest_raw), and rvdd_video_push's copy kernels
 // frames: n frames, dtype 0 = u16 / 1 = f32, layout 0 = mosaic [n][2hh][2ww] / 1 = packed HWC [n][hh][ww][4];
 // packed [n][4][hh][ww] = 2 * (dn / (2^bit_depth - 1)) - 1, gray [n][hh][ww] = (((c0 + c1) + c2) + c3) * 0.25 in DN; either nullable

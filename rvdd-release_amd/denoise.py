@@ -29,6 +29,17 @@ against the re-mosaicked previous OUTPUT instead of the previous noisy frame (op
                       bit-packed as TIFF stores them (`rvdd_egress_bits`) -- again a tree `denoise` reads; mosaic_mipi: the same
                       samples as headerless <frame>.raw of MIPI CSI-2 RAW10 / 12 / 14 rows (read back with --raw_container mipi).
   --out_bit_depth N   the digital numbers' bit depth (default: --bit_depth)
+  --video_out V       y4m8 / y4m10: also write every video as ONE playable stream <results_dir>/<video>.y4m -- YUV4MPEG2, Y'CbCr 4:2:0 at 8
+                      or 10 bits (`y4m.Y4MWriter`), which players and encoders read.  Per push and for all slots at once: the display
+                      image of --video_render (`rvdd_ppipe`, its float image), BT.709 limited-range Y'CbCr with chroma averaged per
+                      2 x 2 quad (`rvdd_ycbcr`), one copy to the host; the frames of a video are appended in order.  Under --cuts one
+                      file per shot, <video>.<first frame of the shot>.y4m.  --all_frames decides, as for the other outputs, whether
+                      a video's first and last frames are in the stream.  Needs
+  --video_render ISO,n,red_gain,blue_gain   the four values of --srgb: the rendering is the reference's display pipeline with the
+                      gains given here, not a colour-managed one.
+  --video_fps N[:D]   the frame rate the header states (default 24).
+  --out_format none   with --video_out: no per-frame file, and no egress launch or copy for one.
+                      Without --video_out no new call is made and the output files keep their bytes.
   --all_frames        write EVERY input frame (option "stream_all_frames"): also frame 0 of a video -- denoised with itself as the
                       previous frame, a zero flow and a fresh recurrence; frame 1 then starts as always -- and, with a future frame,
                       the last frame, with itself as the next frame.  The files of frames 1 .. N-1-future keep their bytes.
@@ -181,11 +192,15 @@ from . import tiffio
 from .footage import (FileSpec, add_cols_arguments, add_dpc_arguments, add_green_arguments, add_report_arguments, add_rows_arguments,
                       cols_arguments, dpc_arguments, estimate_noise, green_arguments, match_arguments, open_rawvideo, report_arguments,
                       report_record, rows_arguments, rows_line, to_device)
+from .y4m import Y4MWriter
 from .runtime import BAYER_PATTERNS, BITS_DEPTHS, bits_row_bytes, green_grid, match_coeffs, resid_add
 
 # --dpc_map auto and --cuts auto, kind "auto"; their FILE forms are a FileSpec, kind "file"
 DpcMapAuto = NamedTuple("DpcMapAuto", [("kind", str), ("frames", int), ("share", float), ("tolerate", int)])
 CutsAuto = NamedTuple("CutsAuto", [("kind", str), ("t_hist", float), ("t_grid", float), ("min_len", int)])
+# --video_out with --video_render and --video_fps: sample depth, (ISO, n, red_gain, blue_gain), (fps numerator, denominator)
+VideoOut = NamedTuple("VideoOut", [("depth", int), ("render", tuple), ("fps", tuple)])
+VIDEO_OUTS = {"y4m8": 8, "y4m10": 10}
 
 NEXT, FIRST, IDLE = _lib.PUSH_NEXT, _lib.PUSH_FIRST, _lib.PUSH_IDLE
 # --out_format -> (layout of RvddRuntime.egress, sample type, file suffix); f32 is the reference's image: 8-bit scale, float32
@@ -286,6 +301,40 @@ def match_report(a, b, bit_depth, iso):
         print('match: WARNING: the footage is cleaner than the ISO %d checkpoints\' noise curve: matching stretches it by s = %.3f beyond '
               'the range the network was trained on, which can lose quality (DESIGN.md 4.16: the table of measured gains and losses)' % (iso, s))
     return cfg
+
+
+def render_arguments(flag, word):
+    """--srgb / --video_render ISO,n,red_gain,blue_gain -> (ISO, n, red_gain, blue_gain); SystemExit that names `flag` for anything else"""
+    f = word.split(',')
+    if len(f) != 4:
+        raise SystemExit("%s takes ISO,n,red_gain,blue_gain" % flag)
+    try:
+        iso, gains = int(f[0]), tuple(float(v) for v in f[1:])
+    except ValueError:
+        raise SystemExit("%s takes ISO,n,red_gain,blue_gain: an integer and three numbers, got %r" % (flag, word))
+    if not all(np.isfinite(g) and g != 0.0 for g in gains):
+        raise SystemExit("%s: n, red_gain and blue_gain must be finite and not zero, got %r" % (flag, word))
+    return (iso,) + gains
+
+
+def video_arguments(video_out, render, fps):
+    """--video_out / --video_render / --video_fps -> None (no --video_out) or a VideoOut; SystemExit where the flags do not fit together"""
+    if video_out is None:
+        if render is not None or fps is not None:
+            raise SystemExit("--video_render and --video_fps belong to --video_out")
+        return None
+    if video_out not in VIDEO_OUTS:
+        raise SystemExit("--video_out %r is not one of %s" % (video_out, ', '.join(VIDEO_OUTS)))
+    if render is None:
+        raise SystemExit("--video_out needs --video_render ISO,n,red_gain,blue_gain: the display rendering of the frames (the four values of --srgb)")
+    f = ("24" if fps is None else fps).split(':')
+    try:
+        rate = (int(f[0]), int(f[1]) if len(f) == 2 else 1)
+        if len(f) > 2 or min(rate) < 1:
+            raise ValueError
+    except ValueError:
+        raise SystemExit("--video_fps takes N or N:D, positive integers, got %r" % fps)
+    return VideoOut(VIDEO_OUTS[video_out], render_arguments("--video_render", render), rate)
 
 
 def cuts_arguments(cuts, own, future):
@@ -420,6 +469,9 @@ def _parse(argv):
     p.add_argument('--srgb', type=str, default=None, help='ISO,n,red_gain,blue_gain: also write <frame>_srgb.png')
     p.add_argument('--out_format', type=str, default='f32', help=', '.join(OUT_FORMATS))
     p.add_argument('--out_bit_depth', type=int, default=None, help='bit depth of the sensor formats (default: --bit_depth)')
+    p.add_argument('--video_out', type=str, default=None, help='y4m8, y4m10: also write every video as one Y4M stream <results_dir>/<video>.y4m')
+    p.add_argument('--video_render', type=str, default=None, help='ISO,n,red_gain,blue_gain: the display rendering of --video_out (the values of --srgb)')
+    p.add_argument('--video_fps', type=str, default=None, help='N or N:D: the frame rate the stream states (default 24)')
     p.add_argument('--all_frames', action='store_true', help='write every input frame, the first and the last of a video too')
     add_dpc_arguments(p)
     add_rows_arguments(p)
@@ -436,14 +488,17 @@ def _parse(argv):
     p.add_argument('--match_iso', type=int, default=None, help="the checkpoint family's noise curve: 3200 or 12800")
     add_report_arguments(p)
     own, rest = p.parse_known_args(argv)
-    if own.out_format not in OUT_FORMATS:
+    if own.out_format not in OUT_FORMATS and own.out_format != "none":
         raise SystemExit("--out_format %r is not one of %s" % (own.out_format, ', '.join(OUT_FORMATS)))
     opt = parse(rest)
     opt.results_dir, opt.srgb, opt.out_format, opt.all_frames = own.results_dir, own.srgb, own.out_format, own.all_frames
     opt.out_bit_depth = int(opt.bit_depth) if own.out_bit_depth is None else own.out_bit_depth
     if not 1 <= opt.out_bit_depth <= 16:
         raise SystemExit("--out_bit_depth must be 1..16, got %d" % opt.out_bit_depth)
-    if OUT_FORMATS[opt.out_format][0] == "bits" and opt.out_bit_depth not in BITS_DEPTHS:
+    opt.video = video_arguments(own.video_out, own.video_render, own.video_fps)
+    if opt.out_format == "none" and opt.video is None:
+        raise SystemExit("--out_format none writes no per-frame file: it needs --video_out %s" % ' | '.join(VIDEO_OUTS))
+    if opt.out_format != "none" and OUT_FORMATS[opt.out_format][0] == "bits" and opt.out_bit_depth not in BITS_DEPTHS:
         raise SystemExit("--out_format %s needs --out_bit_depth (default: --bit_depth) 10, 12 or 14, got %d" % (opt.out_format, opt.out_bit_depth))
     opt.dpc = dpc_arguments(own.dpc, own.dpc_dead, own.dpc_iso, own.dpc_noise, int(opt.bit_depth), own.dpc_noise_frames)
     opt.dpc_noise_frames = 4 if own.dpc_noise_frames is None else own.dpc_noise_frames
@@ -470,10 +525,7 @@ def _parse(argv):
     if not any(a == '--dataset_mode' or a.startswith('--dataset_mode=') for a in rest):
         opt.dataset_mode = 'rawvideo'
     if opt.srgb is not None:
-        f = opt.srgb.split(',')
-        if len(f) != 4:
-            raise SystemExit("--srgb takes ISO,n,red_gain,blue_gain")
-        opt.srgb = (int(f[0]), float(f[1]), float(f[2]), float(f[3]))
+        opt.srgb = render_arguments("--srgb", opt.srgb)
     return opt
 
 
@@ -520,10 +572,14 @@ def write_frame(opt, rt, out_b, host_b, key, path, W):
     name of `path`, and with --srgb the display image of `out_b`, the network output [1,3,H,W] on the device."""
     from .library import iio_write
     from .util import util
-    layout, sample, suffix = OUT_FORMATS[opt.out_format]
+    if opt.out_format == "none" and opt.srgb is None:      # --video_out alone: no per-frame file, no folder for one
+        return
+    layout, sample, suffix = OUT_FORMATS.get(opt.out_format, (None, None, None))
     stem = os.path.splitext(os.path.basename(path))[0]
     util.mkdir(os.path.join(opt.results_dir, key))
-    if layout != "bits":
+    if layout is None:
+        pass
+    elif layout != "bits":
         iio_write(host_b, os.path.join(opt.results_dir, key, stem + suffix))
     elif sample == "msb":
         tiffio.write_packed(os.path.join(opt.results_dir, key, stem + suffix), host_b, W, opt.out_bit_depth)
@@ -541,12 +597,27 @@ def shot_name(key, first):
 
 
 def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -> int:
+    """`push_group`, and the streams of --video_out that a refusal or an error in the middle of a video left open closed on the way out"""
+    writers = {}                                # slot -> the open Y4MWriter of its video (of its shot under --cuts)
+    try:
+        return push_group(opt, model, dataset, videos, H, W, dmap, match, report_out, writers)
+    finally:
+        for w in writers.values():
+            w.close()
+
+
+def push_group(opt, model, dataset, videos, H, W, dmap, match, report_out, writers) -> int:
     """The videos [(key, [paths])] of one frame size H x W through one runtime: its options and stages set, the videos dealt to the
-    slots (`deal_slots`), every step pushed, its valid outputs taken to the host in one egress and written (`write_frame`), and the
+    slots (`deal_slots`), every step pushed, its valid outputs taken to the host in one egress and written (`write_frame`) -- with
+    --video_out also rendered and converted for all slots at once (`ppipe`, `ycbcr`), taken to the host in one copy and appended to the
+    open stream of the slot's video, which is closed where the video ends --, and the
     `dpc:` and `rows:` lines of every video that ended and, with --report, its record (`report_out`: {"file": the open file, "total": the sum of
-    the accumulators read so far or None, "frames": those they cover}).  -> the frames written."""
-    layout, sample, _ = OUT_FORMATS[opt.out_format]
+    the accumulators read so far or None, "frames": those they cover}; `writers`: the caller's dict of the open streams by slot).  -> the
+    frames written."""
+    layout, sample, _ = OUT_FORMATS.get(opt.out_format, (None, None, None))      # none (with --video_out): no per-frame file, no egress
     depth = 8 if opt.out_format == "f32" else opt.out_bit_depth
+    video = getattr(opt, "video", None)         # --video_out: a VideoOut
+    vframes = None
     dev, fut = model.device, int(opt.future_patch_depth)
     B = max(1, min(int(opt.batch_size), len(videos)))
     rt = model._netDenoise.runtime_for(B, H, W, pin=True)
@@ -600,11 +671,17 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
                 batch[b] = dataset.read_frame(videos[vid][1][k])
         out, valid = rt.video_push(to_device(dataset, batch, dev), [c for c, _, _ in step], int(opt.bit_depth), dataset.layout, out,
                                    container=container)
-        host = None
-        if any(valid):                               # the files' samples of all slots: one kernel, one copy
+        host = vhost = None
+        if any(valid) and layout is not None:        # the files' samples of all slots: one kernel, one copy
             files = rt.egress_bits(out, sample, depth, out=files) if layout == "bits" else rt.egress(out, layout, sample, depth, out=files)
             host = files.cpu().numpy()
             host = host.view(np.uint16) if host.dtype == np.int16 else host
+        if any(valid) and video is not None:         # the streams' frame bodies of all slots: two kernels, one copy
+            iso, n, red, blue = video.render
+            _, disp = rt.ppipe(out, 1.0 / n, red, blue, iso, _lib.PPIPE_FROM_NET, "nchw", want_float=True)
+            vframes = rt.ycbcr(disp, video.depth, out=vframes)
+            vhost = vframes.cpu().numpy()
+            vhost = vhost.view(np.uint16) if vhost.dtype == np.int16 else vhost
         ended, ends = False, []
         for b, (c, vid, k) in enumerate(step):
             if vid < 0:
@@ -615,11 +692,20 @@ def run_group(opt, model, dataset, videos, H, W, dmap, match, report_out=None) -
             dpc_frames[b] = min(k + 1, len(frames))
             if last:                                # --cuts: several shots share a key; the lines name the shot's first frame
                 ends.append((b, key, None if opt.cuts is None else os.path.basename(frames[0])))
+            if video is not None and k == 0:        # the slot starts a video (a shot): its stream, named after the shot's first frame under --cuts
+                name = key if opt.cuts is None else '%s.%s' % (key, os.path.splitext(os.path.basename(frames[0]))[0])
+                os.makedirs(os.path.dirname(os.path.join(opt.results_dir, name)), exist_ok=True)
+                writers[b] = Y4MWriter(os.path.join(opt.results_dir, name + '.y4m'), W, H, video.depth, *video.fps)
             if valid[b]:
                 measured[b] += 1
-                write_frame(opt, rt, out[b:b + 1], host[b], key, frames[k - fut], W)      # the centre frame
+                write_frame(opt, rt, out[b:b + 1], None if host is None else host[b], key, frames[k - fut], W)      # the centre frame
+                if video is not None:
+                    writers[b].write(vhost[b])
                 written += 1
         if ended:
+            for b, _, _ in ends:                    # the streams of the videos (shots) that ended
+                if b in writers:
+                    writers.pop(b).close()
             rt.set_option("tvl1_async", 0)          # synchronises: reports a TV-L1 exchange of this video's pushes that gave up
             if opt.dpc is not None:                 # ... and before the slot's next FIRST push: the difference is this video's
                 now = rt.dpc_counts()

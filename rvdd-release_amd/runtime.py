@@ -1176,6 +1176,25 @@ class RvddRuntime:
                                         self._stream()), "rvdd_ppipe")
         return (u8, f32) if want_float else u8
 
+    def ycbcr(self, disp: torch.Tensor, depth: int = 8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[n,H,W,3] float32 display values in [0,255] -- the float image of `ppipe(..., want_float=True)` -- -> the frames of a
+        Y'CbCr 4:2:0 video (rvdd_ycbcr: BT.709, limited range, chroma the average of each 2 x 2 quad): [n, H*W*3//2] samples, uint8
+        for depth 8, torch.uint16 for depth 10 (torch.int16 where this torch has no uint16: the same 16 bits, as `egress` gives
+        them); per image the Y plane [H,W], then Cb, then Cr [H/2,W/2] -- the body of one Y4M frame (`y4m.Y4MWriter`).  H and W
+        even.  out: a tensor of that shape and dtype to write into."""
+        if depth not in (8, 10):
+            raise ValueError(f"ycbcr: depth must be 8 or 10, got {depth!r}")
+        disp = _dev_tensor(disp, "ycbcr: disp", self.device, shape=(None, None, None, 3), form="ycbcr: disp is float32 [n,H,W,3]")
+        n, H, W, _ = disp.shape
+        if H < 2 or W < 2 or H % 2 or W % 2:
+            raise RuntimeError(f"ycbcr: H and W must be even and >= 2 (chroma is one sample per 2 x 2 quad), got {H} x {W}")
+        dtype = torch.uint8 if depth == 8 else getattr(torch, "uint16", torch.int16)
+        shape = (n, H * W * 3 // 2)
+        out = _out_or_new(out, "ycbcr: out", shape, self._tdev, (dtype, torch.int16) if depth == 10 else dtype,
+                          form=f"ycbcr: out must be a contiguous {dtype} tensor of shape {shape}")
+        self._check(self.lib.rvdd_ycbcr(self.h, _ptr(disp), n, H, W, int(depth), _ptr(out), self._stream()), "rvdd_ycbcr")
+        return out
+
     # -- raw datasets from sRGB video -------------------------------------------
     UNPROCESS_OUTPUTS = ("lin_f32", "lin_u16", "gt_raw", "noisy")
 
